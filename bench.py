@@ -13,6 +13,9 @@ velocity references vx~U[-0.1,0.3], vy~U[-0.1,0.1], w~U[-0.2,0.2] redrawn every 
 MT19937-64 seeded 20100 + global gait index.  All inputs are resident in HBM before the timed region.
 
     python bench.py                       # 1 GPU, K = 200 steps, W = 50 warm-up steps
+    python bench.py --full                # and every secondary leg: CPU baseline, golden-file parity, one launch per
+                                          # tick, outs stored, the `kernels` legs, config5
+    python bench.py --dump-outputs DIR    # also write the timed path's results after its last step as DIR/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W      # weak scaling: 4096 gaits per GPU, one RCCL broadcast
 """
@@ -40,6 +43,7 @@ HBM_PEAK_GBS = 8000.0        # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 FP64_VECTOR_PEAK_TFLOPS = 78.6   # MI355X FP64 vector peak (spec): 256 CUs x 4 SIMDs x 16 lanes x 2 flop x 2.4 GHz
 BOX_CPU_SHARE = 16           # host cores that go with one GPU of the pool's boxes (used only when the OS shows no limit)
 CONFIG5_BATCH = 8192         # BASELINE configs[4]: N = 32 with foot-placement variables, batch = 8192
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs writes at most this much
 # counters of the timed kernel measured by rocprofv3 --pmc passes of this very command (tools/prof_round.sh files them)
 PMC_SUMMARY = os.path.join(ROOT, "profiles", "current_tick_pmc.json")
 
@@ -64,6 +68,14 @@ def velocity_table(lo, hi, n_seg):
         tab[:, k, 1] = r.uniform(-0.1, 0.1, n_seg)
         tab[:, k, 2] = r.uniform(-0.2, 0.2, n_seg)
     return tab
+
+
+def table_segments(K, W):
+    """Stretches of references in the table main() draws for W untimed and K timed ticks.  Every run sizes it for the --full
+    legs as well (the per-tick leg's min(K, 100) ticks, the outs leg's K, plus one period: the outs leg starts at the timed
+    region's phase): velocity_table draws all of a gait's vx before its vy and w, so a table of another length would hand the
+    timed ticks other references, and a plain run and a --full run would not time the same inputs."""
+    return (K + W + min(K, 100) + K + 2 * REDRAW_TICKS - 1) // REDRAW_TICKS
 
 
 def start_states(model, B):
@@ -406,6 +418,39 @@ def config5_leg(dev, flags, ticks=40, warm=10):
                               "kernel": kern_name}, **traffic)}
 
 
+def _flat_fields(prefix, a, out):
+    """structured array of a ctypes struct -> {prefix_field[_subfield]: float64 array}; padding fields are left out"""
+    for name in a.dtype.names:
+        if name.startswith("pad"):
+            continue
+        sub = a[name]
+        if sub.dtype.names:
+            _flat_fields(prefix + "_" + name, sub, out)
+        else:
+            out[prefix + "_" + name] = sub.astype(np.float64)
+
+
+def dump_outputs(dirname, snap, lo):
+    """--dump-outputs: what a caller of the timed path holds after its last step -- every gait's wg_gait_state_t, that tick's
+    diag row (ifail, n_iter, nact, n, m, nb_prw_steps) and, with --outs-on, its wg_tick_out_t -- one float64 array per field,
+    gait-major.  Over DUMP_LIMIT_BYTES, a fixed sample of gaits (seed 0) is written; gait_index.npy names the gaits kept."""
+    arrays = {}
+    _flat_fields("state", snap["states"].view(np.dtype(wg.GaitState)), arrays)
+    arrays["diag"] = snap["diag"].reshape(-1, 6).astype(np.float64)
+    if "outs" in snap:
+        _flat_fields("outs", snap["outs"].view(np.dtype(wg.TickOut)), arrays)
+    B = arrays["diag"].shape[0]
+    idx = np.arange(B)
+    per_gait = sum(a.nbytes for a in arrays.values()) / B + 8
+    budget = DUMP_LIMIT_BYTES - 256 * (len(arrays) + 1)                 # less the .npy headers
+    if per_gait * B > budget:
+        idx = np.sort(np.random.default_rng(0).choice(B, int(budget // per_gait), replace=False))
+    arrays["gait_index"] = (lo + idx).astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a if name == "gait_index" else np.ascontiguousarray(a[idx]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -429,7 +474,15 @@ def main():
     ap.add_argument("--no-staged-refs", action="store_true", help="one launch per stretch of constant velocity references "
                     "(wg_mpc_set_velref_dev + wg_mpc_run_batch_dev, round 1's plan) instead of one launch with the references "
                     "of every stretch staged on the device (wg_mpc_run_sched_dev)")
+    ap.add_argument("--full", action="store_true", help="also run the secondary legs (CPU baseline, golden-file parity, one launch "
+                    "per tick, outs stored, `kernels`, config5; each --no-* option still drops its leg); without it the run "
+                    "times the headline workload only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the timed path computed in its last "
+                    "step (the gaits' states, the tick's diagnostics, the outs with --outs-on) as DIR/<name>.npy, float64")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_parity = args.no_per_tick_leg = args.no_outs_leg = True
+        args.no_kernels = args.no_config5 = True
 
     # CPU baseline first: it forks one worker per host core, which must happen before this process touches the GPU
     cpu_line = None
@@ -476,7 +529,7 @@ def main():
     lo, hi = rank * B, (rank + 1) * B                         # weak scaling: B gaits per GPU
     K, W0 = args.steps, args.warmup
     W = W0 + max(0, args.preroll)                             # pre-roll + warm-up: all untimed, same launch plan
-    n_seg = (K + W + min(K, 100) + K + 2 * REDRAW_TICKS - 1) // REDRAW_TICKS    # + one period: the outs leg starts at the timed region's phase
+    n_seg = table_segments(K, W)
     vtab = torch.from_numpy(velocity_table(lo, hi, n_seg)).to(dev)
     states = start_states(model, B).to(dev)
     diag = torch.zeros(K + W, B, 6, dtype=torch.int32, device=dev)
@@ -541,6 +594,13 @@ def main():
     shard.barrier()
     elapsed = time.perf_counter() - t0
     elapsed = shard.max_over_ranks(elapsed, dev)
+
+    # the timed path's results after its last step, copied before any later leg moves the gaits on
+    snap = None
+    if args.dump_outputs and rank == 0:
+        snap = {"states": states.cpu().numpy(), "diag": diag[W + K - 1].cpu().numpy()}
+        if args.outs_on:
+            snap["outs"] = outs_buf[(K - 1) * B * out_bytes:K * B * out_bytes].cpu().numpy()
 
     # secondary figure, same process: one launch per tick (the batch drains between ticks) over the next ticks
     alt = None
@@ -693,6 +753,8 @@ def main():
                 line["parity"]["b1_tick_latency_us"]["cpu_reference_us_per_tick_one_core"] = 1e6 / cpu_line["value"]
         if cpu_line is not None:
             line["cpu_baseline"] = cpu_line
+        if snap is not None:
+            dump_outputs(args.dump_outputs, snap, lo)
         print(json.dumps(line), flush=True)
 
 

@@ -3,7 +3,7 @@
 
   herdt_emergency_stop_datref.npz : the reference's own golden file
         /root/reference/tests/TestHerdt2010EmergencyStopTestFGPI.datref.cmake  (4508 x 38), as data.
-  ql_golden.npz : QPs (inputs) + the COMPILED REFERENCE qld.cpp's outputs (x, u, ifail, final active set, and the
+  ql_golden_<k>.npz : QPs (inputs) + the COMPILED REFERENCE qld.cpp's outputs (x, u, ifail, final active set, and the
         add/drop HISTORY: +k = code k added, -k = dropped, in order -- from a throw-away build of the reference's qld.cpp
         with one log call at its add site (qld.cpp:1766) and one at its drop site (:1903), tests/oraclelib.py:ref_hist;
         x, u, ifail and the final set are taken from the UNPATCHED oracle/_ref build and must agree with the patched one)
@@ -137,13 +137,24 @@ def main():
         add("herdt_tick_%d" % it, q)
 
     hr.replay(model, state, events, 6000, on_tick=on_tick, legacy_running=True)
-    out = {}
-    for k, r in enumerate(recs):
-        for key, v in r.items():
-            out["%04d_%s" % (k, key)] = np.asarray(v)
-    out["count"] = np.array(len(recs))
-    np.savez_compressed(os.path.join(HERE, "ql_golden.npz"), **out)
+    save_ql_golden(recs)
     print("wrote", len(recs), "QPs")
+
+
+QL_SHARD = 64   # QPs per ql_golden_<k>.npz: every committed file stays under 1 MiB
+
+
+def save_ql_golden(recs):
+    """ql_golden_<k>.npz, k = 0, 1, ...: QPs [first, first + count) of recs under their global index"""
+    for first in range(0, len(recs), QL_SHARD):
+        out = {}
+        for k in range(first, min(first + QL_SHARD, len(recs))):
+            for key, v in recs[k].items():
+                out["%04d_%s" % (k, key)] = np.asarray(v)
+        out["first"], out["count"] = np.array(first), np.array(min(QL_SHARD, len(recs) - first))
+        path = os.path.join(HERE, "ql_golden_%d.npz" % (first // QL_SHARD))
+        np.savez_compressed(path, **out)
+        assert os.path.getsize(path) < 1 << 20, path
 
 
 if __name__ == "__main__":

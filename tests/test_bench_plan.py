@@ -65,3 +65,31 @@ def test_cpu_baseline_worker_count_is_what_the_process_may_use(monkeypatch):
     one, allc = b.cpu_baseline(8, 4)                                # a token sample: the bookkeeping, not a measurement
     assert allc["cores_used"] == min(2, used) and allc["value"] > 0 and 0 < allc["parallel_efficiency"]
     assert allc["worker_rate_min"] <= allc["worker_rate_max"] and allc["cores_visible"] == seen["os_cpu_count"]
+
+
+def test_dump_outputs_writes_every_field_as_float64_within_the_limit(tmp_path):
+    """--dump-outputs: one float64 array per field of the gaits' states, the last tick's diag row and (with --outs-on) its outs,
+    gait-major; over the size limit a fixed sample of gaits, the same on every run, with the gaits it kept."""
+    import ctypes as C
+    b = _bench()
+    wg = b.wg
+    B = 40
+    states = (wg.GaitState * B)()
+    for g in range(B):
+        states[g].clock = 0.005 * g
+        states[g].lf[1].x = -g
+    snap = {"states": np.frombuffer(bytes(states), dtype=np.uint8), "diag": np.arange(B * 6, dtype=np.int32),
+            "outs": np.zeros(B * C.sizeof(wg.TickOut), dtype=np.uint8)}
+    b.dump_outputs(str(tmp_path / "all"), snap, 4096)
+    got = {f[:-4]: np.load(tmp_path / "all" / f) for f in os.listdir(tmp_path / "all")}
+    assert all(a.dtype == np.float64 and len(a) == B for a in got.values())
+    assert np.array_equal(got["gait_index"], 4096 + np.arange(B)) and np.array_equal(got["state_clock"], 0.005 * np.arange(B))
+    assert np.array_equal(got["state_lf_x"][:, 1], -np.arange(B)) and got["diag"].shape == (B, 6) and got["diag"][1, 0] == 6
+    assert "outs_zmp_x" in got and got["outs_com_x"].shape == (B, wg.SAMPLES, 3) and not any("pad" in k for k in got)
+    b.DUMP_LIMIT_BYTES = 100000
+    for d in ("s1", "s2"):
+        b.dump_outputs(str(tmp_path / d), snap, 0)
+        assert sum(os.path.getsize(tmp_path / d / f) for f in os.listdir(tmp_path / d)) <= b.DUMP_LIMIT_BYTES
+    kept = np.load(tmp_path / "s1" / "gait_index.npy")
+    assert 0 < len(kept) < B and np.array_equal(kept, np.load(tmp_path / "s2" / "gait_index.npy"))
+    assert np.array_equal(np.load(tmp_path / "s1" / "state_clock.npy"), 0.005 * kept)

@@ -366,3 +366,40 @@ def test_matrix_core_gramian_as_the_hessian_source(N):
         print("N=%d: closed-loop CoM deviation from the fp64 oracle: f64 MFMA %.2e m, f32 MFMA %.2e m" % (N, out["f64"], out["f32"]))
     finally:
         wg.mpc_configure(wg.model_defaults())
+
+
+def test_bench_dump_outputs_hold_the_last_timed_tick(tmp_path):
+    """bench.py --dump-outputs, run as the benchmark is run: what it writes are the states after its last timed step and that
+    tick's diag row.  The same gaits, advanced one tick per call through the host-pointer entry point (wg_mpc_tick_batch) with
+    the references of bench.py's own table, end in the same arrays.  Ticks [0, 45) untimed, [45, 55) timed: two timed launches,
+    the second from a redraw with its references staged on the device."""
+    import json
+    import subprocess
+    bench = _bench_module()
+    B, P, W0, K = 64, 40, 5, 10
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W0),
+                        "--preroll", str(P), "--batch", str(B), "--dump-outputs", str(tmp_path / "bench")],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == K and line["ms_per_step"] > 0
+    wg.init(0)
+    model = wg.model_defaults()
+    wg.mpc_configure(model)
+    W = W0 + P
+    vt = bench.velocity_table(0, B, bench.table_segments(K, W))
+    st = _start(model, B)
+    for t in range(W + K):
+        if t % REDRAW == 0:
+            for k in range(B):
+                st[k].vref[0], st[k].vref[1], st[k].vref[2] = vt[t // REDRAW, k]
+        _, diag, _, _ = wg.mpc_tick_batch(st, want_out=False, advance_calls=1 if t == 0 else (19 if t == 1 else 20))
+    bench.dump_outputs(str(tmp_path / "ticks"), {"states": np.frombuffer(bytes(st), dtype=np.uint8),
+                                                 "diag": np.ascontiguousarray(diag, dtype=np.int32)}, 0)
+    names = sorted(os.listdir(tmp_path / "bench"))
+    assert names == sorted(os.listdir(tmp_path / "ticks")) and "diag.npy" in names and "state_clock.npy" in names
+    for f in names:
+        a, b = np.load(tmp_path / "bench" / f), np.load(tmp_path / "ticks" / f)
+        assert a.dtype == np.float64 and ol.same_bits_nan_aware(a, b), f
+    assert np.all(np.load(tmp_path / "bench" / "state_tick_count.npy") == W + K)

@@ -65,7 +65,7 @@ def test_family_bit_exact(family):
 
 
 def test_golden_vectors_and_reference_history_through_the_gpu():
-    """The committed fixture of the COMPILED REFERENCE (tests/golden/ql_golden.npz: x, u, ifail, final set and the reference's
+    """The committed fixture of the COMPILED REFERENCE (tests/golden/ql_golden_<k>.npz: x, u, ifail, final set and the reference's
     own add/drop history) against the HIP solver directly, no oracle in between: "bit-exact active-set index sequences"."""
     import test_ql_oracle as tqo
     wg = _wg()

@@ -1,6 +1,6 @@
 """Pins the oracle's QL restatement (oracle/ql_oracle.c):
    1. against committed golden vectors produced by the COMPILED REFERENCE qld.cpp
-      (tests/golden/ql_golden.npz, made by tests/golden/make_golden.py), bit for bit;
+      (tests/golden/ql_golden_<k>.npz, made by tests/golden/make_golden.py), bit for bit;
    2. where oracle/_ref/libqld_ref.so is present (it is built from the reference source
       by oracle/Makefile and travels with the repo), live against that library on fresh seeds.
 """
@@ -12,17 +12,22 @@ import pytest
 import oraclelib as ol
 import qpgen
 
-GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ql_golden.npz")
+GOLD_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def _golden():
-    z = np.load(GOLD)
-    for k in range(int(z["count"])):
-        g = lambda key: z["%04d_%s" % (k, key)]
-        q = dict(n=int(g("n")), m=int(g("m")), me=int(g("me")), mmax=int(g("mmax")), nmax=int(g("n")),
-                 C=np.asfortranarray(g("C")), d=g("d").copy(), A=np.asfortranarray(g("A")), b=g("b").copy(),
-                 xl=g("xl").copy(), xu=g("xu").copy())
-        yield str(g("tag")), q, dict(x=g("x"), u=g("u"), ifail=int(g("ifail")), iact=g("iact"), hist=g("hist"))
+    """the QPs of ql_golden_0.npz, ql_golden_1.npz, ... in their global order"""
+    shards = sorted((f for f in os.listdir(GOLD_DIR) if f.startswith("ql_golden_") and f.endswith(".npz")),
+                    key=lambda f: int(f[len("ql_golden_"):-4]))
+    for f in shards:
+        z = np.load(os.path.join(GOLD_DIR, f))
+        first = int(z["first"])
+        for k in range(first, first + int(z["count"])):
+            g = lambda key: z["%04d_%s" % (k, key)]
+            q = dict(n=int(g("n")), m=int(g("m")), me=int(g("me")), mmax=int(g("mmax")), nmax=int(g("n")),
+                     C=np.asfortranarray(g("C")), d=g("d").copy(), A=np.asfortranarray(g("A")), b=g("b").copy(),
+                     xl=g("xl").copy(), xu=g("xu").copy())
+            yield str(g("tag")), q, dict(x=g("x"), u=g("u"), ifail=int(g("ifail")), iact=g("iact"), hist=g("hist"))
 
 
 def test_oracle_matches_reference_golden_vectors_bit_for_bit():

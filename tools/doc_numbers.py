@@ -117,7 +117,7 @@ def block_current():
     L.append("")
     L.append("**Bench lines** (`bench.py`, one MI355X, B = 4096, N = 16, fp64, inputs resident; builder's boxes — the driver's clock decides):")
     L.append("")
-    L.append(f"| leg | default run (`--steps 200 --warmup 50`, `{tag}_bench.json`) | the driver's window (`--steps 20 --warmup 5`, `{tag}_bench_driver_window.json`) |")
+    L.append(f"| leg | default run (`--full --steps 200 --warmup 50`, `{tag}_bench.json`) | the driver's window (`--full --steps 20 --warmup 5`, `{tag}_bench_driver_window.json`) |")
     L.append("|---|---|---|")
     L.append(f"| **`value`: MPC ticks/s, one multi-tick launch** | **{M(bench['value'])}** ({bench['ms_per_step']:.4f} ms per step) | **{M(win['value'])}** ({win['ms_per_step']:.4f} ms per step) |")
     L.append(f"| `outs_on`: the same launch storing every gait-tick's `wg_tick_out_t` | {M(bench['outs_on']['value'])} ({100 * bench['outs_on']['delta_vs_value']:+.1f} %) | {M(win['outs_on']['value'])} ({100 * win['outs_on']['delta_vs_value']:+.1f} %) |")

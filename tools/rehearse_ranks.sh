@@ -7,4 +7,4 @@ R=${GRAFT_REPO_ROOT:?run this on the GPU box (gpurun sets GRAFT_REPO_ROOT)}
 N=${1:-2}
 export WG_BENCH_BACKEND=gloo WG_BENCH_DEVICE=0 HSA_ENABLE_IPC_MODE_LEGACY=0
 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port 29533 \
-  bench.py --gpus $N --steps 100 --warmup 50
+  bench.py --full --gpus $N --steps 100 --warmup 50
