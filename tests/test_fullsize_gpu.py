@@ -109,15 +109,18 @@ def _bench_module():
     return mod
 
 
-def bench_plan_run(ctx, model, B, t_end, timed_from, bench):
+def bench_plan_run(ctx, model, B, t_end, timed_from, bench, n_seg=None, vel_scale=1.0):
     """bench.py's own launch sequence on device-resident states (its launch_plan, its velocity_table, its entry points:
     wg_mpc_tick_batch_dev for the control loop's first two ticks, wg_mpc_set_velref_dev + wg_mpc_run_batch_dev for a stretch
     that does not start on a redraw, wg_mpc_run_sched_dev with the references of every later stretch staged for one that
-    does): ticks [0, timed_from) as its pre-roll + warm-up, [timed_from, t_end) as its timed region.  Returns the final states
-    (host bytes per gait), the per-tick diagnostics and the entry point of every launch."""
+    does): ticks [0, timed_from) as its pre-roll + warm-up, [timed_from, t_end) as its timed region.  n_seg: the length of the
+    velocity table (default: just enough stretches for t_end; bench.py draws bench.table_segments(K, W) of them, and a table
+    of another length hands the ticks other references); vel_scale multiplies the table (SOAK_VSCALE).  Returns the final
+    states (host bytes per gait), the per-tick diagnostics and the entry point of every launch."""
     import torch
-    n_seg = (t_end + bench.REDRAW_TICKS - 1) // bench.REDRAW_TICKS
-    vtab = torch.from_numpy(bench.velocity_table(0, B, n_seg)).cuda()
+    if n_seg is None:
+        n_seg = (t_end + bench.REDRAW_TICKS - 1) // bench.REDRAW_TICKS
+    vtab = torch.from_numpy(bench.velocity_table(0, B, n_seg) * vel_scale).cuda()
     states = bench.start_states(model, B).cuda()
     diag = torch.zeros(t_end, B, 6, dtype=torch.int32, device="cuda")
     sp, dp, dstride = states.data_ptr(), diag.data_ptr(), B * 6 * 4
@@ -151,7 +154,7 @@ def test_bench_plan_at_the_timed_size_ends_in_the_per_tick_runs_bytes(full_run):
     stretches' references staged) at the size it times it: bench.py's own pre-roll / warm-up / timed launch sequence over the
     first 200 ticks must leave every gait in the bytes the one-launch-per-tick host-pointer run left it in (which a sample of
     the oracle follows, test above), with the same ifail / iteration count / active-set size for every one of the 819 200
-    QPs.  tools/soak_parity.py is the longer soak with the oracle on every gait."""
+    QPs.  tests/test_fleet_parity_gpu.py follows every gait of bench.py's whole default run (350 ticks) with the oracle."""
     model, B, T, fin, st, fails, iters = full_run
     bench = _bench_module()
     assert B == bench.BATCH_PER_GPU and bench.PREROLL_TICKS + 50 == 150       # the default W: timed region starts at tick 150
