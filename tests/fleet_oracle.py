@@ -64,6 +64,10 @@ class FleetJob:
     def __init__(self, asyncs, n_gaits, n_ticks, keep_ticks, outs):
         self._asyncs, self.n_gaits, self.n_ticks, self.keep_ticks, self.outs = asyncs, n_gaits, n_ticks, keep_ticks, outs
 
+    def done(self):
+        """(chunks finished, chunks in all)"""
+        return sum(a.ready() for a in self._asyncs), len(self._asyncs)
+
     def result(self, timeout=None):
         parts = [a.get(timeout) for a in self._asyncs]
         parts.sort(key=lambda p: p["g0"])

@@ -71,12 +71,12 @@ def overdriven_tick_qp(gait=18, tick_wanted=87, B=32, scale=3.0):
     ~600 iterations of the same two bounds going in and out, an entry of Z that has become DENORMAL: the Givens rotation that
     meets it has gb = q / norm = 0 by underflow and ga = -1, which the reference carries out (two columns change sign)."""
     import ctypes as C
+    import workload as w
     ol.build_oracle()
     pt = C.CDLL(os.path.join(ol.ORACLE_DIR, "libwg_oracle_ptrig.so"))
     model = hr.default_model()
     rng = np.random.default_rng(333)
-    s = hr.init_state(model, [0.0316055, 0.0, 0.7116911], [0.0, 0.09, 0.0], [0.0, -0.09, 0.0])
-    s.nb_steps_left = 2
+    s = w.start_state(hr.init_state, model)
     for tick in range(tick_wanted + 1):
         if tick % 50 == 0:
             for g in range(B):

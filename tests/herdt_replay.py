@@ -175,7 +175,7 @@ def emergency_stop_setup(datref):
 
     Robot constants that the reference reads from the (absent) sample model were identified from the
     golden file itself: sole 0.25 x 0.14 m, no hip-yaw limits (fallback -30/+45 deg on both
-    legs, zero velocity bound), start CoM (0.0316055, 0, 0.7116911), feet at (0, +-0.09).
+    legs, zero velocity bound), the start CoM and feet of workload.START_COM / START_LEFT / START_RIGHT.
     Two things in the golden file predate the current reference source (ChangeLog [3.1.8]):
       * the initial support state had Y hard-coded to 0.1 (half the default feet distance) instead of the
         left foot's y,

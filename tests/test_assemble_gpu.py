@@ -13,6 +13,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import herdt_replay as hr  # noqa: E402
 import oraclelib as ol  # noqa: E402
+import workload as w  # noqa: E402
+from workload import ptrig as _ptrig, state_bytes as _bytes  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -23,21 +25,12 @@ def _wg():
     return wg
 
 
-def _ptrig():
-    ol.build_oracle()
-    return C.CDLL(os.path.join(ol.ORACLE_DIR, "libwg_oracle_ptrig.so"))
-
-
-def _bytes(x):
-    return bytes(memoryview(x).cast("B"))
-
-
 def _gaits(wg, model, B, seed):
     rng = np.random.default_rng(seed)
     states = (wg.GaitState * B)()
     for g in range(B):
-        s = wg.gait_init(model, [0.0316055 + rng.normal(0, 0.003), rng.normal(0, 0.003), 0.7116911], [0.0, 0.09, 0.0], [0.0, -0.09, 0.0])
-        s.nb_steps_left = 2
+        s = wg.gait_init(model, [w.START_COM[0] + rng.normal(0, 0.003), rng.normal(0, 0.003), w.START_COM[2]], w.START_LEFT, w.START_RIGHT)
+        s.nb_steps_left = w.STEPS_BEFORE_STOP
         s.vref[0], s.vref[1], s.vref[2] = rng.uniform(-0.1, 0.3), rng.uniform(-0.1, 0.1), rng.uniform(-0.2, 0.2)
         C.memmove(C.byref(states[g]), C.byref(s), C.sizeof(wg.GaitState))
     return states
@@ -59,16 +52,13 @@ def test_assembled_qp_is_the_oracles_and_its_dense_solve_is_the_fused_ticks(N):
     C.memmove(cpu, gpu, C.sizeof(gpu))
     sizes = set()
     for tick in range(30):
-        adv = 1 if tick == 0 else (19 if tick == 1 else 20)
+        adv = w.advance_calls(tick)
         before = _bytes(gpu)
         pk = wg.mpc_assemble_batch(gpu, advance_calls=adv, model=model)
         assert _bytes(gpu) == before, "assembling must not touch the states"
         dumps = []
         for g in range(B):
-            c = cpu[g].clock
-            for _ in range(adv):
-                c += model.Tctrl
-            cpu[g].clock = c
+            w.advance_clock(cpu[g], model, adv)
             d = hr.QpDump()
             assert pt.wgo_mpc_tick(C.byref(model), C.byref(cpu[g]), None, C.byref(d)) == 0
             dumps.append(d)
@@ -106,7 +96,7 @@ def test_one_robot_in_host_mapped_memory_equals_the_host_pointer_call():
     try:
         C.memmove(C.addressof(hm.state), C.byref(ref[0]), C.sizeof(wg.GaitState))
         for tick in range(40):
-            adv = 1 if tick == 0 else (19 if tick == 1 else 20)
+            adv = w.advance_calls(tick)
             outs, diag, _, _ = wg.mpc_tick_batch(ref, want_out=True, advance_calls=adv)
             hm.tick(adv)
             assert _bytes(hm.state) == _bytes(ref[0]), tick
@@ -130,7 +120,7 @@ def test_overlapping_launches_of_one_context_are_ordered(monkeypatch):
     model = wg.model_defaults()
     B = 4096
     one = _bytes(_gaits(wg, model, 1, 9)[0])
-    mk = lambda: torch.frombuffer(bytearray(one * B), dtype=torch.uint8).cuda()   # noqa: E731
+    mk = lambda: w.to_device(one, B)   # noqa: E731
     with wg.Context(0) as ctx, wg.Context(0) as other:
         ctx.mpc_configure(model); other.mpc_configure(model)
         a, b, c, ref = mk(), mk(), mk(), mk()
@@ -190,7 +180,7 @@ def test_assemble_launches_of_one_context_on_two_streams():
     ref = {}
     for key, g in (("a", ga), ("b", gb)):
         ref[key] = wg.mpc_assemble_batch(g, 20, nmax, mmax)
-    mk = lambda g: torch.frombuffer(bytearray(_bytes(g[0]) * B), dtype=torch.uint8).cuda()   # noqa: E731
+    mk = lambda g: w.to_device(g[0], B)   # noqa: E731
     sa, sb = mk(ga), mk(gb)
     def bufs():
         return dict(C=torch.zeros(B, nmax * nmax, dtype=torch.float64, device="cuda"), d=torch.zeros(B, nmax, dtype=torch.float64, device="cuda"),

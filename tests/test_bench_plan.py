@@ -1,21 +1,13 @@
 """bench.py's host-side bookkeeping (no GPU): the launch plan covers exactly the timed ticks, never crosses a change of the
 velocity references, keeps the control loop's first two ticks apart; the algorithmic-bytes formula is SURVEY 8(d)'s; the
-synthetic references are the same for a gait whatever shard it lands in."""
-import importlib.util
+synthetic references are the same for a gait whatever shard it lands in.  And the pins that hold tests/workload.py -- the
+workload as the suite and the tools state it -- to bench.py's own copy: either side drifting fails here."""
 import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _bench():
-    spec = importlib.util.spec_from_file_location("wg_bench", os.path.join(ROOT, "bench.py"))
-    mod = importlib.util.module_from_spec(spec)
-    sys.modules["wg_bench"] = mod
-    spec.loader.exec_module(mod)
-    return mod
+import workload as w
+from workload import bench_module as _bench
 
 
 def test_launch_plan_covers_ticks_and_respects_redraws():
@@ -67,7 +59,7 @@ def test_cpu_baseline_worker_count_is_what_the_process_may_use(monkeypatch):
     assert allc["worker_rate_min"] <= allc["worker_rate_max"] and allc["cores_visible"] == seen["os_cpu_count"]
 
 
-def test_dump_outputs_writes_every_field_as_float64_within_the_limit(tmp_path):
+def test_dump_outputs_writes_every_field_as_float64_within_the_limit(tmp_path, monkeypatch):
     """--dump-outputs: one float64 array per field of the gaits' states, the last tick's diag row and (with --outs-on) its outs,
     gait-major; over the size limit a fixed sample of gaits, the same on every run, with the gaits it kept."""
     import ctypes as C
@@ -86,10 +78,60 @@ def test_dump_outputs_writes_every_field_as_float64_within_the_limit(tmp_path):
     assert np.array_equal(got["gait_index"], 4096 + np.arange(B)) and np.array_equal(got["state_clock"], 0.005 * np.arange(B))
     assert np.array_equal(got["state_lf_x"][:, 1], -np.arange(B)) and got["diag"].shape == (B, 6) and got["diag"][1, 0] == 6
     assert "outs_zmp_x" in got and got["outs_com_x"].shape == (B, wg.SAMPLES, 3) and not any("pad" in k for k in got)
-    b.DUMP_LIMIT_BYTES = 100000
+    monkeypatch.setattr(b, "DUMP_LIMIT_BYTES", 100000)               # bench.py is loaded once per process: put the limit back
     for d in ("s1", "s2"):
         b.dump_outputs(str(tmp_path / d), snap, 0)
         assert sum(os.path.getsize(tmp_path / d / f) for f in os.listdir(tmp_path / d)) <= b.DUMP_LIMIT_BYTES
     kept = np.load(tmp_path / "s1" / "gait_index.npy")
     assert 0 < len(kept) < B and np.array_equal(kept, np.load(tmp_path / "s2" / "gait_index.npy"))
     assert np.array_equal(np.load(tmp_path / "s1" / "state_clock.npy"), 0.005 * kept)
+
+
+# ------------------------------------------------------------------------------- tests/workload.py pinned to bench.py
+def test_workload_references_are_bench_pys_table():
+    b = _bench()
+    assert w.REDRAW == b.REDRAW_TICKS
+    for lo, hi, n in ((0, 8, 3), (4, 12, 7), (7 * 4096, 7 * 4096 + 5, 9), (4095, 4096, 1)):
+        tab = b.velocity_table(lo, hi, n)
+        got = w.velocity_table(lo, hi, n)
+        assert got.dtype == tab.dtype and got.shape == tab.shape == (n, hi - lo, 3) and np.array_equal(got, tab)
+        for k, g in enumerate(range(lo, hi)):
+            assert np.array_equal(w.velocity(g, n), tab[:, k])
+    assert not np.array_equal(w.velocity(0, 4), w.velocity(1, 4))
+
+
+def test_workload_start_state_is_bench_pys():
+    b = _bench()
+    wg = b.wg
+    for N, B in ((16, 3), (32, 2)):
+        model = wg.model_defaults()
+        model.N = N
+        want = b.start_states(model, B).numpy().tobytes()
+        assert w.start_bytes(wg.gait_init, model, B) == want == w.state_bytes(w.start_array(wg.gait_init, model, B))
+        s = w.start_state(wg.gait_init, model)
+        assert s.nb_steps_left == w.STEPS_BEFORE_STOP == 2 and (s.com_x[0], s.com_y[0]) == w.START_COM[:2]
+        assert (s.lf[2].y, s.rf[2].y) == (w.START_LEFT[1], w.START_RIGHT[1]) == (0.09, -0.09)
+
+
+def test_workload_clock_schedule():
+    """The clock advances by 1, 19, 20, 20, ... control periods, by repeated addition of Tctrl.  That is not clock + n * Tctrl:
+    over the first 400 ticks of the default model the two differ in the last bits on nearly every tick (398 of 400 when this
+    was written), and a checker that multiplied would leave the kernels' bytes at once."""
+    wg = _bench().wg
+    model = wg.model_defaults()
+    per_tick = int(round(model.T / model.Tctrl))
+    assert per_tick == 20
+    assert [w.advance_calls(t) for t in range(5)] == [1, 19, 20, 20, 20] == [w.advance_calls(t, per_tick) for t in range(5)]
+    assert [w.advance_calls(t, 10) for t in range(4)] == [1, 9, 10, 10]
+    s = w.start_state(wg.gait_init, model)
+    literal = s.clock
+    differs = 0
+    for t in range(400):
+        n = 1 if t == 0 else (19 if t == 1 else 20)
+        multiplied = s.clock + n * model.Tctrl
+        for _ in range(n):
+            literal += model.Tctrl
+        w.advance_clock(s, model, n)
+        assert s.clock.hex() == literal.hex(), t
+        differs += s.clock != multiplied
+    assert abs(s.clock - 7980 * model.Tctrl) < 1e-9 and differs > 0

@@ -11,43 +11,24 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import oraclelib as ol  # noqa: E402
+import workload as w  # noqa: E402
+from workload import ptrig as _ptrig, to_device as _dev  # noqa: E402
 
 wg = importlib.import_module("jrl-walkgen_amd")
 pytestmark = pytest.mark.gpu
 SZ = C.sizeof(wg.GaitState)
 
 
-def _ptrig():
-    ol.build_oracle()
-    return C.CDLL(os.path.join(ol.ORACLE_DIR, "libwg_oracle_ptrig.so"))
-
-
 def _fleet(model, B, seed):
     rng = np.random.default_rng(seed)
-    arr = (wg.GaitState * B)()
-    for g in range(B):
-        s = wg.gait_init(model, [0.0316055, 0.0, 0.7116911], [0.0, 0.09, 0.0], [0.0, -0.09, 0.0])
-        s.nb_steps_left = 2
+    arr = w.start_array(wg.gait_init, model, B)
+    for s in arr:
         s.vref[0], s.vref[1], s.vref[2] = rng.uniform(-0.1, 0.3), rng.uniform(-0.1, 0.1), rng.uniform(-0.2, 0.2)
-        C.memmove(C.byref(arr[g]), C.byref(s), SZ)
     return arr
 
 
-def _dev(arr):
-    return torch.frombuffer(bytearray(bytes(memoryview(arr).cast("B"))), dtype=torch.uint8).cuda()
-
-
-def _oracle(pt, model, start, advs):
-    s = wg.GaitState()
-    C.memmove(C.byref(s), C.byref(start), SZ)
-    for k in advs:
-        c = s.clock
-        for _ in range(k):
-            c += model.Tctrl
-        s.clock = c
-        assert pt.wgo_mpc_tick(C.byref(model), C.byref(s), None, None) == 0
-    return bytes(memoryview(s).cast("B"))
+def _oracle(pt, model, start, n_ticks):
+    return w.oracle_follow(pt, model, start, None, n_ticks)
 
 
 def test_two_models_two_streams_interleaved_bit_exact():
@@ -66,7 +47,7 @@ def test_two_models_two_streams_interleaved_bit_exact():
         da, db = _dev(ha), _dev(hb)
         sa, sb = torch.cuda.Stream(), torch.cuda.Stream()
         torch.cuda.synchronize()
-        advs = [1, 19] + [20] * 14
+        advs = [w.advance_calls(t) for t in range(16)]
         # launches of the two contexts alternate from the host and overlap on the device (two streams, no events)
         ca.mpc_tick_batch_dev(Ba, da.data_ptr(), None, None, 1, stream=sa.cuda_stream)
         cb.mpc_tick_batch_dev(Bb, db.data_ptr(), None, None, 1, stream=sb.cuda_stream)
@@ -82,9 +63,9 @@ def test_two_models_two_streams_interleaved_bit_exact():
         torch.cuda.synchronize()
         fa = da.cpu().numpy().reshape(Ba, SZ); fb = db.cpu().numpy().reshape(Bb, SZ)
         for g in sorted(set(np.random.default_rng(1).choice(Ba, 20, replace=False).tolist()) | {0, Ba - 1}):
-            assert _oracle(pt, m16, ha[g], advs) == fa[g].tobytes(), ("N=16 context", g)
+            assert _oracle(pt, m16, ha[g], len(advs)) == fa[g].tobytes(), ("N=16 context", g)
         for g in sorted(set(np.random.default_rng(2).choice(Bb, 10, replace=False).tolist()) | {0, Bb - 1}):
-            assert _oracle(pt, m32, hb[g], advs) == fb[g].tobytes(), ("N=32 context", g)
+            assert _oracle(pt, m32, hb[g], len(advs)) == fb[g].tobytes(), ("N=32 context", g)
         # the whole batches again, one context at a time on the default stream: same bytes as the overlapped run
         for ctx, h, B, fin in ((ca, ha, Ba, fa), (cb, hb, Bb, fb)):
             d = _dev(h)
@@ -95,7 +76,7 @@ def test_two_models_two_streams_interleaved_bit_exact():
     # the default context still holds ITS model (N = 16) and works after the other two are gone
     assert wg.mpc_tick_lds_bytes() == wg.mpc_tick_lds_bytes_for(m16)
     h = _fleet(m16, 5, 3)
-    ref = [_oracle(pt, m16, h[g], [1]) for g in range(5)]
+    ref = [_oracle(pt, m16, h[g], 1) for g in range(5)]
     wg.mpc_tick_batch(h, want_out=False, advance_calls=1)
     assert [bytes(memoryview(h[g]).cast("B")) for g in range(5)] == ref
 
@@ -110,7 +91,7 @@ def test_two_robots_of_the_same_horizon_do_not_share_tables():
         ca.mpc_configure(ma)
         cb.mpc_configure(mb)                                        # configured later: must not replace ca's tables
         B = 64
-        advs = [1, 19] + [20] * 18
+        advs = [w.advance_calls(t) for t in range(20)]
         ha, hb = _fleet(ma, B, 7), _fleet(mb, B, 7)
         for k in advs:
             _, diag_a, _, _ = ca.mpc_tick_batch(ha, want_out=False, advance_calls=k)
@@ -120,8 +101,8 @@ def test_two_robots_of_the_same_horizon_do_not_share_tables():
         differ = 0
         for g in range(B):
             a, b = bytes(memoryview(ha[g]).cast("B")), bytes(memoryview(hb[g]).cast("B"))
-            assert a == _oracle(pt, ma, st[g], advs), g
-            assert b == _oracle(pt, mb, st[g], advs), g
+            assert a == _oracle(pt, ma, st[g], len(advs)), g
+            assert b == _oracle(pt, mb, st[g], len(advs)), g
             differ += a != b
         assert differ == B                                          # and the two robots really walk differently
 

@@ -11,6 +11,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import fleet_oracle as fo  # noqa: E402
+import workload as w  # noqa: E402
 
 wg = importlib.import_module("jrl-walkgen_amd")                 # POD layouts only: no library load
 B, T, REDRAW = 16, 60, 25                                       # redraws at ticks 0, 25 and 50
@@ -30,9 +31,8 @@ def _model(lib):
 
 def _start(lib, model):
     s = wg.GaitState()
-    lib.wgo_gait_init(C.byref(model), C.byref(s), (C.c_double * 3)(0.0316055, 0.0, 0.7116911),
-                      (C.c_double * 3)(0.0, 0.09, 0.0), (C.c_double * 3)(0.0, -0.09, 0.0))
-    s.nb_steps_left = 2
+    lib.wgo_gait_init(C.byref(model), C.byref(s), *((C.c_double * 3)(*v) for v in (w.START_COM, w.START_LEFT, w.START_RIGHT)))
+    s.nb_steps_left = w.STEPS_BEFORE_STOP
     return s
 
 
@@ -71,19 +71,14 @@ def test_pool_diag_and_outs_equal_a_plain_tick_loop(pooled):
     lib, model, s0, vel, res, res_dig = pooled
     diag = np.zeros((T, B, 6), dtype=np.int32)
     outs = {}
+    o = wg.TickOut()
+
+    def on_tick(t, s):
+        diag[t, g] = o.ifail, o.n_iter, o.nact, o.n, o.m, o.nb_prw_steps
+        outs.setdefault(t, []).append(bytes(o))
+        C.memset(C.byref(o), 0, C.sizeof(o))                   # every tick writes into a zeroed struct, as in the pool
     for g in range(B):
-        s = wg.GaitState.from_buffer_copy(bytes(s0))
-        for t in range(T):
-            if t % REDRAW == 0:
-                s.vref[0], s.vref[1], s.vref[2] = vel[t // REDRAW, g]
-            c = s.clock
-            for _ in range(1 if t == 0 else (19 if t == 1 else 20)):
-                c += model.Tctrl
-            s.clock = c
-            o = wg.TickOut()
-            assert lib.wgo_mpc_tick(C.addressof(model), C.addressof(s), C.addressof(o), None) == 0
-            diag[t, g] = o.ifail, o.n_iter, o.nact, o.n, o.m, o.nb_prw_steps
-            outs.setdefault(t, []).append(bytes(o))
+        w.oracle_follow(lib, model, s0, vel[:, g], T, redraw=REDRAW, out=o, on_tick=on_tick)
     assert np.array_equal(res["diag"], diag)
     assert (diag[..., 0] == 0).all() and (diag[..., 1] > 0).all() and set(np.unique(diag[..., 3])) <= {32, 34, 36}
     for t in (0, 37, T - 1):

@@ -25,7 +25,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import fleet_oracle as fo  # noqa: E402
-import test_fullsize_gpu as tf  # noqa: E402
+import workload as w  # noqa: E402
 
 wg = importlib.import_module("jrl-walkgen_amd")
 pytestmark = pytest.mark.gpu
@@ -65,7 +65,7 @@ def _workloads(bench):
 @pytest.fixture(scope="module")
 def fleet(request):
     """bench.py as a module, and the oracle runs of the selected tests, queued in test order on one pool"""
-    bench = tf._bench_module()
+    bench = w.bench_module()
     wg.init(0)
     work = _workloads(bench)
     wanted = [it.name for it in request.session.items if it.module is request.module and it.name in work]
@@ -146,7 +146,7 @@ def test_b_bench_default_run_every_gait_every_tick(fleet):
     B, T = bench.BATCH_PER_GPU, B_K + B_W
     model = wg.model_defaults()
     wg.mpc_configure(model)
-    fin, diag, names = tf.bench_plan_run(wg, model, B, T, B_W, bench, n_seg=bench.table_segments(B_K, B_W))
+    fin, diag, names = w.bench_plan_run(wg, model, B, T, B_W, bench, n_seg=bench.table_segments(B_K, B_W))
     assert names == ["wg_mpc_tick_batch_dev", "wg_mpc_tick_batch_dev", "wg_mpc_run_batch_dev", "wg_mpc_run_sched_dev",
                      "wg_mpc_run_sched_dev"]                      # ticks 0 | 1 | 2-49 | 50-149 | 150-349 (timed)
     res = _collect(job)
@@ -168,7 +168,7 @@ def test_c_config5_every_gait_every_tick(fleet):
     model.N = 32
     wg.mpc_configure(model)
     try:
-        fin, diag, names = tf.bench_plan_run(wg, model, B, T, C_WARM, bench)
+        fin, diag, names = w.bench_plan_run(wg, model, B, T, C_WARM, bench)
     finally:
         wg.mpc_configure(wg.model_defaults())
     assert names == ["wg_mpc_tick_batch_dev", "wg_mpc_tick_batch_dev", "wg_mpc_run_batch_dev", "wg_mpc_run_batch_dev"]
@@ -194,14 +194,14 @@ def test_d_overdriven_slice_through_the_multi_tick_launch(fleet):
     n_seg = T // R + 1
     model = wg.model_defaults()
     wg.mpc_configure(model)
-    fin, diag, names = tf.bench_plan_run(wg, model, B, T, T, bench, n_seg=n_seg, vel_scale=D_SCALE)
+    fin, diag, names = w.bench_plan_run(wg, model, B, T, T, bench, n_seg=n_seg, vel_scale=D_SCALE)
     assert names == ["wg_mpc_tick_batch_dev", "wg_mpc_tick_batch_dev", "wg_mpc_run_batch_dev", "wg_mpc_run_sched_dev"]
-    states = torch.frombuffer(bytearray(b"".join(fin)), dtype=torch.uint8).cuda()
+    states = w.to_device(b"".join(fin))
     vlast = torch.from_numpy(np.ascontiguousarray(table()[T // R])).cuda()
     outs = torch.zeros(B * layout["out_size"], dtype=torch.uint8, device="cuda")
     dlast = torch.zeros(B, 6, dtype=torch.int32, device="cuda")
     wg.mpc_set_velref_dev(B, states.data_ptr(), vlast.data_ptr())
-    wg.mpc_tick_batch_dev(B, states.data_ptr(), outs.data_ptr(), dlast.data_ptr(), 20)
+    wg.mpc_tick_batch_dev(B, states.data_ptr(), outs.data_ptr(), dlast.data_ptr(), w.advance_calls(T))
     torch.cuda.synchronize()
     gpu_diag = np.concatenate([diag, dlast.cpu().numpy()[None]])
     res = _collect(job)

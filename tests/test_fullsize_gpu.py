@@ -17,38 +17,28 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import oraclelib as ol  # noqa: E402
 import qpgen  # noqa: E402
+import workload as w  # noqa: E402
+from workload import REDRAW  # noqa: E402
 
 wg = importlib.import_module("jrl-walkgen_amd")
 pytestmark = pytest.mark.gpu
-REDRAW = 50
-
-
-def _vel(g, n_seg):
-    r = np.random.Generator(np.random.MT19937(20100 + g))          # bench.py's table
-    return np.stack([r.uniform(-0.1, 0.3, n_seg), r.uniform(-0.1, 0.1, n_seg), r.uniform(-0.2, 0.2, n_seg)], 1)
 
 
 def _start(model, B):
-    s0 = wg.gait_init(model, [0.0316055, 0.0, 0.7116911], [0.0, 0.09, 0.0], [0.0, -0.09, 0.0])
-    s0.nb_steps_left = 2
-    st = (wg.GaitState * B)()
-    for g in range(B):
-        C.memmove(C.byref(st[g]), C.byref(s0), C.sizeof(wg.GaitState))
-    return st
+    return w.start_array(wg.gait_init, model, B)
 
 
 def _run(model, gaits, n_ticks):
     """advance the listed global gait indices n_ticks; returns the final state bytes per gait + per-tick diag"""
     B = len(gaits)
     st = _start(model, B)
-    vt = [_vel(g, (n_ticks + REDRAW - 1) // REDRAW) for g in gaits]
+    vt = [w.velocity(g, (n_ticks + REDRAW - 1) // REDRAW) for g in gaits]
     fails = 0; iters = []
     for t in range(n_ticks):
         if t % REDRAW == 0:
             for k in range(B):
                 st[k].vref[0], st[k].vref[1], st[k].vref[2] = vt[k][t // REDRAW]
-        adv = 1 if t == 0 else (19 if t == 1 else 20)
-        _, diag, _, _ = wg.mpc_tick_batch(st, want_out=False, advance_calls=adv)
+        _, diag, _, _ = wg.mpc_tick_batch(st, want_out=False, advance_calls=w.advance_calls(t))
         fails += int((diag[:, 0] != 0).sum()); iters.append(diag[:, 1].copy())
     sz = C.sizeof(wg.GaitState)
     raw = bytes(memoryview(st).cast("B"))
@@ -81,72 +71,12 @@ def test_full_size_run_is_sane(full_run):
 
 def test_full_size_sample_followed_by_the_oracle(full_run):
     model, B, T, fin, st, fails, iters = full_run
-    pt = C.CDLL(os.path.join(ol.ORACLE_DIR, "libwg_oracle_ptrig.so"))
-    ol.build_oracle()
+    pt = w.ptrig()
     rng = np.random.default_rng(4096)
     sample = sorted(rng.choice(B, 48, replace=False).tolist()) + [0, B - 1]
+    start = w.start_state(wg.gait_init, model)
     for g in sample:
-        s = _start(model, 1)[0]
-        vt = _vel(g, (T + REDRAW - 1) // REDRAW)
-        for t in range(T):
-            if t % REDRAW == 0:
-                s.vref[0], s.vref[1], s.vref[2] = vt[t // REDRAW]
-            c = s.clock
-            for _ in range(1 if t == 0 else (19 if t == 1 else 20)):
-                c += model.Tctrl
-            s.clock = c
-            assert pt.wgo_mpc_tick(C.byref(model), C.byref(s), None, None) == 0
-        assert bytes(memoryview(s).cast("B")) == fin[g], g
-
-
-def _bench_module():
-    import importlib.util
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    spec = importlib.util.spec_from_file_location("wg_bench", os.path.join(root, "bench.py"))
-    mod = importlib.util.module_from_spec(spec)
-    sys.modules["wg_bench"] = mod
-    spec.loader.exec_module(mod)
-    return mod
-
-
-def bench_plan_run(ctx, model, B, t_end, timed_from, bench, n_seg=None, vel_scale=1.0):
-    """bench.py's own launch sequence on device-resident states (its launch_plan, its velocity_table, its entry points:
-    wg_mpc_tick_batch_dev for the control loop's first two ticks, wg_mpc_set_velref_dev + wg_mpc_run_batch_dev for a stretch
-    that does not start on a redraw, wg_mpc_run_sched_dev with the references of every later stretch staged for one that
-    does): ticks [0, timed_from) as its pre-roll + warm-up, [timed_from, t_end) as its timed region.  n_seg: the length of the
-    velocity table (default: just enough stretches for t_end; bench.py draws bench.table_segments(K, W) of them, and a table
-    of another length hands the ticks other references); vel_scale multiplies the table (SOAK_VSCALE).  Returns the final
-    states (host bytes per gait), the per-tick diagnostics and the entry point of every launch."""
-    import torch
-    if n_seg is None:
-        n_seg = (t_end + bench.REDRAW_TICKS - 1) // bench.REDRAW_TICKS
-    vtab = torch.from_numpy(bench.velocity_table(0, B, n_seg) * vel_scale).cuda()
-    states = bench.start_states(model, B).cuda()
-    diag = torch.zeros(t_end, B, 6, dtype=torch.int32, device="cuda")
-    sp, dp, dstride = states.data_ptr(), diag.data_ptr(), B * 6 * 4
-    stream = torch.cuda.Stream()
-    sh = stream.cuda_stream
-    names = []
-    with torch.cuda.stream(stream):
-        for t, n in bench.launch_plan(0, timed_from) + bench.launch_plan(timed_from, t_end):
-            staged = n > 1 and t % bench.REDRAW_TICKS == 0
-            if t % bench.REDRAW_TICKS == 0 and not staged:
-                ctx.mpc_set_velref_dev(B, sp, vtab[t // bench.REDRAW_TICKS].data_ptr(), sh)
-            adv = 1 if t == 0 else (19 if t == 1 else 20)
-            if n == 1 and t < 2:
-                names.append("wg_mpc_tick_batch_dev")
-                ctx.mpc_tick_batch_dev(B, sp, None, dp + t * dstride, adv, stream=sh)
-            elif staged:
-                names.append("wg_mpc_run_sched_dev")
-                ctx.mpc_run_sched_dev(B, sp, n, vtab[t // bench.REDRAW_TICKS].data_ptr(), bench.REDRAW_TICKS, adv, None,
-                                      dp + t * dstride, stream=sh)
-            else:
-                names.append("wg_mpc_run_batch_dev")
-                ctx.mpc_run_batch_dev(B, sp, n, adv, None, dp + t * dstride, stream=sh)
-    torch.cuda.synchronize()
-    raw = states.cpu().numpy().tobytes()
-    sz = C.sizeof(wg.GaitState)
-    return [raw[k * sz:(k + 1) * sz] for k in range(B)], diag.cpu().numpy(), names
+        assert w.oracle_follow(pt, model, start, w.velocity(g, (T + REDRAW - 1) // REDRAW), T) == fin[g], g
 
 
 def test_bench_plan_at_the_timed_size_ends_in_the_per_tick_runs_bytes(full_run):
@@ -156,9 +86,9 @@ def test_bench_plan_at_the_timed_size_ends_in_the_per_tick_runs_bytes(full_run):
     the oracle follows, test above), with the same ifail / iteration count / active-set size for every one of the 819 200
     QPs.  tests/test_fleet_parity_gpu.py follows every gait of bench.py's whole default run (350 ticks) with the oracle."""
     model, B, T, fin, st, fails, iters = full_run
-    bench = _bench_module()
+    bench = w.bench_module()
     assert B == bench.BATCH_PER_GPU and bench.PREROLL_TICKS + 50 == 150       # the default W: timed region starts at tick 150
-    fin2, diag, names = bench_plan_run(wg, model, B, T, 150, bench)
+    fin2, diag, names = w.bench_plan_run(wg, model, B, T, 150, bench)
     assert names == ["wg_mpc_tick_batch_dev", "wg_mpc_tick_batch_dev", "wg_mpc_run_batch_dev", "wg_mpc_run_sched_dev",
                      "wg_mpc_run_sched_dev"]                                  # ticks 0 | 1 | 2-49 | 50-149 (staged) | 150-199 (timed)
     assert int((diag[:, :, 0] != 0).sum()) == 0
@@ -195,7 +125,7 @@ def test_dense_qp_edge_sizes_bit_exact():
 
 
 def _horizon_vs_oracle(N, T, step, B, ticks, redraw):
-    pt = C.CDLL(os.path.join(ol.ORACLE_DIR, "libwg_oracle_ptrig.so"))
+    pt = w.ptrig()
     model = wg.model_defaults()
     model.N = N; model.T = T; model.t_double = T; model.step_period = step
     model.Tctrl = T / 20.0                                         # the ABI fixes 20 control samples per tick
@@ -212,15 +142,12 @@ def _horizon_vs_oracle(N, T, step, B, ticks, redraw):
                     v = [rng.uniform(-0.1, 0.3), rng.uniform(-0.1, 0.1), rng.uniform(-0.2, 0.2)]
                     for s in (st[g], ref[g]):
                         s.vref[0], s.vref[1], s.vref[2] = v
-            adv = 1 if t == 0 else (per_tick - 1 if t == 1 else per_tick)
+            adv = w.advance_calls(t, per_tick)
             _, diag, _, _ = wg.mpc_tick_batch(st, want_out=False, advance_calls=adv)
             assert (diag[:, 0] == 0).all(), diag[:, 0]
             sizes |= set(int(v) for v in diag[:, 3])
             for g in range(B):
-                c = ref[g].clock
-                for _ in range(adv):
-                    c += model.Tctrl
-                ref[g].clock = c
+                w.advance_clock(ref[g], model, adv)
                 assert pt.wgo_mpc_tick(C.byref(model), C.byref(ref[g]), None, None) == 0
             assert bytes(memoryview(st).cast("B")) == bytes(memoryview(ref).cast("B")), t
         return sizes
@@ -317,7 +244,7 @@ def test_horizon_beyond_the_tables_is_refused():
 
 def _closed_loop(model, B, ticks, redraw, seed, oracle=False):
     """CoM trajectories [ticks, B, 2] (+ iterations) of B gaits under seeded velocity references"""
-    pt = C.CDLL(os.path.join(ol.ORACLE_DIR, "libwg_oracle_ptrig.so")) if oracle else None
+    pt = w.ptrig() if oracle else None
     st = _start(model, B)
     rng = np.random.default_rng(seed)
     per_tick = int(round(model.T / model.Tctrl))
@@ -326,13 +253,10 @@ def _closed_loop(model, B, ticks, redraw, seed, oracle=False):
         if t % redraw == 0:
             for g in range(B):
                 st[g].vref[0], st[g].vref[1], st[g].vref[2] = rng.uniform(-0.1, 0.3), rng.uniform(-0.1, 0.1), rng.uniform(-0.2, 0.2)
-        adv = 1 if t == 0 else (per_tick - 1 if t == 1 else per_tick)
+        adv = w.advance_calls(t, per_tick)
         if oracle:
             for g in range(B):
-                c = st[g].clock
-                for _ in range(adv):
-                    c += model.Tctrl
-                st[g].clock = c
+                w.advance_clock(st[g], model, adv)
                 assert pt.wgo_mpc_tick(C.byref(model), C.byref(st[g]), None, None) == 0
         else:
             _, diag, _, _ = wg.mpc_tick_batch(st, want_out=False, advance_calls=adv)
@@ -378,7 +302,7 @@ def test_bench_dump_outputs_hold_the_last_timed_tick(tmp_path):
     the second from a redraw with its references staged on the device."""
     import json
     import subprocess
-    bench = _bench_module()
+    bench = w.bench_module()
     B, P, W0, K = 64, 40, 5, 10
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W0),
@@ -397,7 +321,7 @@ def test_bench_dump_outputs_hold_the_last_timed_tick(tmp_path):
         if t % REDRAW == 0:
             for k in range(B):
                 st[k].vref[0], st[k].vref[1], st[k].vref[2] = vt[t // REDRAW, k]
-        _, diag, _, _ = wg.mpc_tick_batch(st, want_out=False, advance_calls=1 if t == 0 else (19 if t == 1 else 20))
+        _, diag, _, _ = wg.mpc_tick_batch(st, want_out=False, advance_calls=w.advance_calls(t))
     bench.dump_outputs(str(tmp_path / "ticks"), {"states": np.frombuffer(bytes(st), dtype=np.uint8),
                                                  "diag": np.ascontiguousarray(diag, dtype=np.int32)}, 0)
     names = sorted(os.listdir(tmp_path / "bench"))

@@ -71,26 +71,13 @@ def test_tick_with_the_reference_compiled_solver_is_bit_identical():
 def test_c_run_loop_equals_the_python_loop():
     """wgo_mpc_run (bench.py's CPU leg) advances gaits exactly like the per-tick calls the tests make."""
     import ctypes as C
-    import importlib
-    wg = importlib.import_module("jrl-walkgen_amd")
+    import workload as w
     lib = ol.oracle()
     model = hr.default_model()
     ng, nt, redraw = 3, 30, 10
     rng = np.random.default_rng(5)
     vel = np.ascontiguousarray(rng.uniform(-0.1, 0.2, (3, ng, 3)))
-    a = (wg.GaitState * ng)(); b = (wg.GaitState * ng)()
-    for g in range(ng):
-        s = hr.init_state(model, [0.0316055, 0.0, 0.7116911], [0.0, 0.09, 0.0], [0.0, -0.09, 0.0]); s.nb_steps_left = 2
-        C.memmove(C.byref(a[g]), C.byref(s), C.sizeof(wg.GaitState)); C.memmove(C.byref(b[g]), C.byref(s), C.sizeof(wg.GaitState))
+    a = w.start_array(hr.init_state, model, ng)
+    b = [w.oracle_follow(lib, model, a[g], vel[:, g], nt, redraw=redraw) for g in range(ng)]
     assert lib.wgo_mpc_run(C.byref(model), a, ng, nt, vel.ctypes.data_as(C.c_void_p), redraw) == 0
-    for tick in range(nt):
-        adv = 1 if tick == 0 else (19 if tick == 1 else 20)
-        for g in range(ng):
-            if tick % redraw == 0:
-                b[g].vref[0], b[g].vref[1], b[g].vref[2] = vel[tick // redraw, g]
-            c = b[g].clock
-            for _ in range(adv):
-                c += model.Tctrl
-            b[g].clock = c
-            assert lib.wgo_mpc_tick(C.byref(model), C.byref(b[g]), None, None) == 0
-    assert bytes(memoryview(a).cast("B")) == bytes(memoryview(b).cast("B"))
+    assert w.state_bytes(a) == b"".join(b)

@@ -117,9 +117,8 @@ def test_footplans_are_valid_polytopes():
 
 
 def test_bench_plan_with_preroll_covers_every_tick_once():
-    spec = importlib.util.spec_from_file_location("wg_bench_plan", os.path.join(ROOT, "bench.py"))
-    b = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(b)
+    import workload
+    b = workload.bench_module()
     assert b.PREROLL_TICKS == 100
     for W0, K in ((50, 200), (5, 20), (0, 1)):
         W = W0 + b.PREROLL_TICKS

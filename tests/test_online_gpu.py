@@ -20,21 +20,16 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import herdt_replay as hr  # noqa: E402
-import oraclelib as ol  # noqa: E402
+from workload import ptrig, state_bytes as _bytes  # noqa: E402
 
 wg = importlib.import_module("jrl-walkgen_amd")
 pytestmark = pytest.mark.gpu
 GOLD = np.load(os.path.join(ROOT, "tests", "golden", "herdt_emergency_stop_datref.npz"))["datref"]
 
 
-def _bytes(x):
-    return bytes(memoryview(x).cast("B"))
-
-
 def test_online_schedule_every_tick_bit_exact_vs_oracle():
     wg.init(0)
-    ol.build_oracle()
-    pt = C.CDLL(os.path.join(ol.ORACLE_DIR, "libwg_oracle_ptrig.so"))
+    pt = ptrig()
     model, s_gpu, events = hr.online_walking_setup(GOLD)
     _, s_cpu, _ = hr.online_walking_setup(GOLD)
     wg.mpc_configure(model)

@@ -16,17 +16,10 @@ import numpy as np
 
 import herdt_replay as hr
 import oraclelib as ol
+import workload as w
+from workload import ptrig as _ptrig
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "herdt_emergency_stop_datref.npz")
-
-
-def _ptrig():
-    ol.build_oracle()
-    so = os.path.join(ol.ORACLE_DIR, "libwg_oracle_ptrig.so")
-    if not os.path.exists(so):
-        import subprocess
-        subprocess.check_call(["make", "-s", "-C", ol.ORACLE_DIR, "libwg_oracle_ptrig.so"])
-    return C.CDLL(so)
 
 
 def _trace(lib, setup, max_calls, legacy_running=False):
@@ -91,34 +84,24 @@ def test_online_walking_schedule_same_active_set_history_libm_vs_portable_trig()
 
 def test_benchmark_sample_same_active_set_history_libm_vs_portable_trig():
     """50 gaits of config 3's workload (seeds 20100 + g, references redrawn every 50 ticks), 200 ticks each."""
-    import importlib
-    wg = importlib.import_module("jrl-walkgen_amd")
-    libs = (ol.oracle(), _ptrig())
     model = hr.default_model()
     rng = np.random.default_rng(4096)
     sample = sorted(rng.choice(4096, 48, replace=False).tolist()) + [0, 4095]
+    start = w.start_state(hr.init_state, model)
+    d = hr.QpDump()
     n_hist = 0
+
+    def on_tick(t, s):
+        log.append((d.n, d.m, d.ifail, d.n_iter, d.nact, tuple(d.hist[:min(d.hist_len, hr.HIST_CAP)])))
+        C.memset(C.byref(d), 0, C.sizeof(d))                       # every tick dumps into a zeroed struct
     for g in sample:
-        r = np.random.Generator(np.random.MT19937(20100 + g))
-        vt = np.stack([r.uniform(-0.1, 0.3, 4), r.uniform(-0.1, 0.1, 4), r.uniform(-0.2, 0.2, 4)], 1)
-        st = []
-        for _ in libs:
-            s = hr.init_state(model, [0.0316055, 0.0, 0.7116911], [0.0, 0.09, 0.0], [0.0, -0.09, 0.0])
-            s.nb_steps_left = 2
-            st.append(s)
+        dumps, com = [], []
+        for lib in (ol.oracle(), _ptrig()):
+            log = []
+            com.append(hr.GaitState.from_buffer_copy(w.oracle_follow(lib, model, start, w.velocity(g, 4), 200, dump=d, on_tick=on_tick)))
+            dumps.append(log)
         for t in range(200):
-            dumps = []
-            for lib, s in zip(libs, st):
-                if t % 50 == 0:
-                    s.vref[0], s.vref[1], s.vref[2] = vt[t // 50]
-                c = s.clock
-                for _ in range(1 if t == 0 else (19 if t == 1 else 20)):
-                    c += model.Tctrl
-                s.clock = c
-                d = hr.QpDump()
-                assert lib.wgo_mpc_tick(C.byref(model), C.byref(s), None, C.byref(d)) == 0
-                dumps.append((d.n, d.m, d.ifail, d.n_iter, d.nact, tuple(d.hist[:min(d.hist_len, hr.HIST_CAP)])))
-            assert dumps[0] == dumps[1], (g, t, dumps[0][:5], dumps[1][:5])
-            n_hist += len(dumps[0][5])
-        assert abs(st[0].com_x[0] - st[1].com_x[0]) < 1e-10 and abs(st[0].com_y[0] - st[1].com_y[0]) < 1e-10   # after 20 s and metres of walking
+            assert dumps[0][t] == dumps[1][t], (g, t, dumps[0][t][:5], dumps[1][t][:5])
+            n_hist += len(dumps[0][t][5])
+        assert abs(com[0].com_x[0] - com[1].com_x[0]) < 1e-10 and abs(com[0].com_y[0] - com[1].com_y[0]) < 1e-10   # after 20 s and metres of walking
     assert n_hist > 50 * 200 * 5

@@ -4,35 +4,23 @@ must be the same bytes, whatever the order in which the queue happened to serve 
 than the resident wave slots (waves poll the queue), a batch of several rounds, a single tick, and the dense view."""
 import ctypes as C
 import importlib
-import os
 
 import numpy as np
 import pytest
 import torch
 
-import oraclelib as ol
+import workload as w
+from workload import to_device as _dev
 
 pytestmark = pytest.mark.gpu
 wg = importlib.import_module("jrl-walkgen_amd")
 
 
-def _ptrig():
-    ol.build_oracle()
-    return C.CDLL(os.path.join(ol.ORACLE_DIR, "libwg_oracle_ptrig.so"))
-
-
 def _start(model, B, rng):
-    s0 = wg.gait_init(model, [0.0316055, 0.0, 0.7116911], [0.0, 0.09, 0.0], [0.0, -0.09, 0.0])
-    s0.nb_steps_left = 2
-    arr = (wg.GaitState * B)()
+    arr = w.start_array(wg.gait_init, model, B)
     for g in range(B):
-        C.memmove(C.byref(arr[g]), C.byref(s0), C.sizeof(wg.GaitState))
         arr[g].vref[0], arr[g].vref[1], arr[g].vref[2] = rng.uniform(-0.1, 0.3), rng.uniform(-0.1, 0.1), rng.uniform(-0.2, 0.2)
     return arr
-
-
-def _dev(arr):
-    return torch.frombuffer(bytearray(bytes(memoryview(arr).cast("B"))), dtype=torch.uint8).cuda()
 
 
 @pytest.mark.parametrize("B,T,want_out", [(40, 30, True), (1, 7, False), (3000, 12, False), (64, 1, True), (2600, 10, True)])
@@ -62,18 +50,10 @@ def test_run_batch_equals_single_tick_launches_and_oracle(B, T, want_out):
         assert torch.equal(oa, ob)
     assert int((db[:, :, 0] != 0).sum()) == 0                     # every QP solved
     # and the oracle, on a sample of the gaits
-    pt = _ptrig()
+    pt = w.ptrig()
     final = b.cpu().numpy().reshape(B, -1)
     for g in sorted(set([0, B // 2, B - 1])):
-        ref = wg.GaitState()
-        C.memmove(C.byref(ref), C.byref(host[g]), C.sizeof(wg.GaitState))
-        for k in [1, adv - 1] + [adv] * T:
-            c = ref.clock
-            for _ in range(k):
-                c += model.Tctrl
-            ref.clock = c
-            assert pt.wgo_mpc_tick(C.byref(model), C.byref(ref), None, None) == 0
-        assert bytes(memoryview(ref).cast("B")) == final[g].tobytes(), g
+        assert w.oracle_follow(pt, model, host[g], None, T + 2, per_tick=adv) == final[g].tobytes(), g
 
 
 def test_run_batch_dense_view_and_arguments():

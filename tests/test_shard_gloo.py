@@ -21,6 +21,7 @@ def _worker(rank, world, port, q):
     shard = importlib.import_module("jrl-walkgen_amd.shard")
     wg = importlib.import_module("jrl-walkgen_amd")
     import herdt_replay as hr
+    import workload
     r, lr, w = shard.init_process_group("gloo")
     dev = torch.device("cpu")
     model = hr.default_model() if r == 0 else wg.Model()
@@ -31,8 +32,7 @@ def _worker(rank, world, port, q):
     lo, hi = shard.shard_range(total, r, w)
     com = []
     for g in range(lo, hi):
-        s = hr.init_state(model, [0.0316055, 0.0, 0.7116911], [0.0, 0.09, 0.0], [0.0, -0.09, 0.0])
-        s.nb_steps_left = 2
+        s = workload.start_state(hr.init_state, model)
         s.vref[0] = 0.1 + 0.01 * g
         s.clock = 0.005
         hr.oracle_tick(model, s)

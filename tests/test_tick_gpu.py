@@ -11,7 +11,8 @@ import numpy as np
 import pytest
 
 import herdt_replay as hr
-import oraclelib as ol
+import workload as w
+from workload import ptrig as _ptrig, state_bytes as _bytes
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "herdt_emergency_stop_datref.npz")
@@ -21,15 +22,6 @@ def _wg():
     wg = importlib.import_module("jrl-walkgen_amd")
     wg.init(0)
     return wg
-
-
-def _ptrig():
-    ol.build_oracle()
-    return C.CDLL(os.path.join(ol.ORACLE_DIR, "libwg_oracle_ptrig.so"))
-
-
-def _bytes(x):
-    return bytes(memoryview(x).cast("B"))
 
 
 def _gpu_tick_factory(wg):
@@ -100,9 +92,9 @@ def _random_gaits(wg, model, B, seed):
     rng = np.random.default_rng(seed)
     states = (wg.GaitState * B)()
     for g in range(B):
-        s = wg.gait_init(model, [0.0316055 + rng.normal(0, 0.003), rng.normal(0, 0.003), 0.7116911],
-                         [0.0, 0.09, 0.0], [0.0, -0.09, 0.0])
-        s.nb_steps_left = 2
+        s = wg.gait_init(model, [w.START_COM[0] + rng.normal(0, 0.003), rng.normal(0, 0.003), w.START_COM[2]],
+                         w.START_LEFT, w.START_RIGHT)
+        s.nb_steps_left = w.STEPS_BEFORE_STOP
         C.memmove(C.byref(states[g]), C.byref(s), C.sizeof(wg.GaitState))
     return states, rng
 
@@ -125,13 +117,10 @@ def test_batch_of_desynchronised_gaits_bit_exact():
                 v = [rng.uniform(-0.1, 0.3), rng.uniform(-0.1, 0.1), rng.uniform(-0.2, 0.2)]
                 for st in (states[g], ref_states[g]):
                     st.vref[0], st.vref[1], st.vref[2] = v
-        adv = 1 if tick == 0 else (19 if tick == 1 else 20)
+        adv = w.advance_calls(tick)
         outs, diag, _, _ = wg.mpc_tick_batch(states, want_out=False, advance_calls=adv)
         for g in range(B):
-            c = ref_states[g].clock
-            for _ in range(adv):
-                c += model.Tctrl
-            ref_states[g].clock = c
+            w.advance_clock(ref_states[g], model, adv)
             assert pt.wgo_mpc_tick(C.byref(model), C.byref(ref_states[g]), None, None) == 0
         assert _bytes(states) == _bytes(ref_states), tick
         sizes |= set(int(v) for v in diag[:, 3])
@@ -148,14 +137,11 @@ def test_pushed_gaits_including_infeasible_qps_bit_exact():
     wg.mpc_configure(model)
     B = 160
     rng = np.random.default_rng(77)
-    states = (wg.GaitState * B)()
-    for g in range(B):
-        s = wg.gait_init(model, [0.0316055, 0.0, 0.7116911], [0.0, 0.09, 0.0], [0.0, -0.09, 0.0])
-        s.nb_steps_left = 2
+    states = w.start_array(wg.gait_init, model, B)
+    for g, s in enumerate(states):
         amp = 0.05 + 0.45 * g / B
         s.com_x[1] = rng.uniform(-amp, amp); s.com_y[1] = rng.uniform(-0.6 * amp, 0.6 * amp)
         s.com_x[2] = rng.uniform(-amp, amp)
-        C.memmove(C.byref(states[g]), C.byref(s), C.sizeof(wg.GaitState))
     ref_states = (wg.GaitState * B)()
     C.memmove(ref_states, states, C.sizeof(states))
     seen_fail = set(); sizes = set(); max_act = 0
@@ -165,13 +151,10 @@ def test_pushed_gaits_including_infeasible_qps_bit_exact():
                 v = [rng.uniform(-0.2, 0.4), rng.uniform(-0.2, 0.2), rng.uniform(-0.3, 0.3)] if g % 3 else [0.0, 0.0, 0.0]
                 for st in (states[g], ref_states[g]):
                     st.vref[0], st.vref[1], st.vref[2] = v
-        adv = 1 if tick == 0 else (19 if tick == 1 else 20)
+        adv = w.advance_calls(tick)
         outs, diag, _, _ = wg.mpc_tick_batch(states, want_out=True, advance_calls=adv)
         for g in range(B):
-            c = ref_states[g].clock
-            for _ in range(adv):
-                c += model.Tctrl
-            ref_states[g].clock = c
+            w.advance_clock(ref_states[g], model, adv)
             o = hr.TickOut()
             assert pt.wgo_mpc_tick(C.byref(model), C.byref(ref_states[g]), C.byref(o), None) == 0
             assert o.ifail == diag[g, 0] and o.n_iter == diag[g, 1] and o.nact == diag[g, 2], (tick, g, o.ifail, diag[g])
@@ -198,11 +181,7 @@ def test_overdriven_gaits_through_failed_and_nan_solves_end_in_the_oracles_state
     model.N = N
     wg.mpc_configure(model)                                      # (N = 16: the first maxit exit of this seed comes at tick 87)
     rng = np.random.default_rng(333)
-    states = (wg.GaitState * B)()
-    for g in range(B):
-        s = wg.gait_init(model, [0.0316055, 0.0, 0.7116911], [0.0, 0.09, 0.0], [0.0, -0.09, 0.0])
-        s.nb_steps_left = 2
-        C.memmove(C.byref(states[g]), C.byref(s), C.sizeof(wg.GaitState))
+    states = w.start_array(wg.gait_init, model, B)
     ref_states = (wg.GaitState * B)()
     C.memmove(ref_states, states, C.sizeof(states))
     sz = C.sizeof(wg.GaitState)
@@ -221,15 +200,12 @@ def test_overdriven_gaits_through_failed_and_nan_solves_end_in_the_oracles_state
                 v = [scale * rng.uniform(-0.1, 0.3), scale * rng.uniform(-0.1, 0.1), scale * rng.uniform(-0.2, 0.2)]
                 for st in (states[g], ref_states[g]):
                     st.vref[0], st.vref[1], st.vref[2] = v
-        adv = 1 if tick == 0 else (19 if tick == 1 else 20)
+        adv = w.advance_calls(tick)
         outs, diag, _, _ = wg.mpc_tick_batch(states, want_out=True, advance_calls=adv)
         got = _bytes(states)
         got_outs = _bytes(outs); osz = C.sizeof(wg.TickOut)
         for g in range(B):
-            c = ref_states[g].clock
-            for _ in range(adv):
-                c += model.Tctrl
-            ref_states[g].clock = c
+            w.advance_clock(ref_states[g], model, adv)
             o = hr.TickOut()
             assert pt.wgo_mpc_tick(C.byref(model), C.byref(ref_states[g]), C.byref(o), None) == 0
             assert (o.ifail, o.n_iter) == (int(diag[g, 0]), int(diag[g, 1])), (tick, g, o.ifail, o.n_iter, diag[g])
