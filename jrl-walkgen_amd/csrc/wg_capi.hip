@@ -1,4 +1,4 @@
-// wg_capi.hip -- C ABI (include/wg_mpc.h) over the HIP kernels.  gfx950 only.
+// wg_capi.hip -- C ABI (include/wg_mpc.h) over the HIP kernels: host code only (the kernels are in the headers).  gfx950 only.
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -8,6 +8,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/wg_mpc.h"
@@ -19,6 +20,10 @@
 #include "wg_preview_device.hpp"
 #include "wg_gramian_device.hpp"
 #include "wg_zmpdisc_device.hpp"
+#include "wg_ql_kernels.hpp"
+#include "wg_pldp_kernels.hpp"
+#include "wg_dimitrov_kernels.hpp"
+
 
 namespace {
 
@@ -64,6 +69,29 @@ struct DevBuf {
   }
 };
 
+
+// environment knobs: read on EVERY call (tests flip them inside one process)
+inline int env_int(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
+inline bool env_flag(const char *name, bool dflt) { return env_int(name, dflt) != 0; }
+
+// Residency.  LDS is handed out in granules of 1280 B, 128 to a CU: how many workgroups of `lds` bytes a CU keeps, at most the
+// `wave_cap` waves the kernel's register budget admits, at least one (whatever passed the 160 KiB checks fits once)
+inline size_t per_cu_granules(size_t lds, size_t wave_cap) {
+  const size_t g = (lds + 1279) / 1280, k = g ? 128 / g : wave_cap;
+  return k > wave_cap ? wave_cap : (k < 1 ? 1 : k);
+}
+// the same by whole bytes of the CU's 160 KiB (where an operand is placed: the dense boundary, PLDP)
+inline size_t per_cu_160k(size_t lds, size_t cap) { const size_t k = (160 * 1024) / (lds ? lds : 1); return k > cap ? cap : k; }
+
+// longest-solve-first start order of one kind of launch: [iterations of the last batch (B) | start order (B)], and the batch
+// (array and size) those iterations belong to
+struct Lpt {
+  DevBuf buf;
+  const void *key = nullptr;
+  int B = 0;
+  void release() { buf.release(); key = nullptr; B = 0; }
+};
+
 }  // namespace
 
 // Everything the library keeps between calls: configured models (device copies of their tables), the workspaces its
@@ -88,14 +116,9 @@ struct wg_ctx {
   DevBuf qp_slot;
   struct SlotOrder { hipEvent_t ev = nullptr; hipStream_t stream = nullptr; bool armed = false; };
   SlotOrder qp_order;
-  DevBuf lpt_buf;                        // [iterations of the last tick (B) | start order (B)]
-  const wg_gait_state_t *lpt_states = nullptr;
-  int lpt_B = 0;
-  // the same for the dense QP boundary and the Dimitrov tick's QL back-ends: a batch that follows another one of the same size on
+  // the tick, the dense QP boundary and the Dimitrov tick's QL back-ends: a batch that follows another one of the same size on
   // the same arrays (an MPC loop: problem k of consecutive calls is the same robot a tick later) starts longest-solve-first
-  DevBuf qlpt_buf, dlpt_buf;
-  const void *qlpt_key = nullptr, *dlpt_key = nullptr;
-  int qlpt_B = 0, dlpt_B = 0;
+  Lpt tick_lpt, qp_lpt, dim_lpt;
   // The tick / run kernels keep their queue and per-block solver slots in run_buf / tick_z: launches of one context must
   // not overlap ON THE DEVICE.  Every such launch leaves an event behind; a launch that arrives on ANOTHER stream while that
   // event is still pending is made to wait for it (hipStreamWaitEvent: ordered, not refused -- a double-buffered pipeline that
@@ -140,14 +163,13 @@ struct wg_ctx {
     if (prev_F) (void)hipFree(prev_F);
     tables_dev = nullptr; model_dev = nullptr; pldp_dev = nullptr; dim_dev = nullptr; prev_F = nullptr;
     model_set = false; pldp_N = 0; dim_set = false; prev_set = false;
-    qlpt_key = dlpt_key = nullptr; qlpt_B = dlpt_B = 0;
-    for (DevBuf *b : {&tick_state, &tick_out, &tick_aux, &run_buf, &tick_z, &asm_state, &lpt_buf, &qlpt_buf, &dlpt_buf, &qp_slot, &pldp_buf, &dim_buf, &prev_buf, &in, &out, &gram_buf, &zd_buf})
+    for (DevBuf *b : {&tick_state, &tick_out, &tick_aux, &run_buf, &tick_z, &asm_state, &qp_slot, &pldp_buf, &dim_buf, &prev_buf, &in, &out, &gram_buf, &zd_buf})
       b->release();
+    for (Lpt *l : {&tick_lpt, &qp_lpt, &dim_lpt}) l->release();
     for (SlotOrder *o : {&guard_order, &qp_order, &asm_order, &aux_order}) {
       if (o->ev) (void)hipEventDestroy(o->ev);
       o->ev = nullptr; o->armed = false; o->stream = nullptr;
     }
-    lpt_states = nullptr; lpt_B = 0;
     if (pin_stream) (void)hipStreamDestroy(pin_stream);
     if (host_stream) (void)hipStreamDestroy(host_stream);
     host_stream = nullptr;
@@ -155,7 +177,6 @@ struct wg_ctx {
     pin_stream = nullptr; pin_flag = nullptr; pin_seq = 0;
   }
 };
-
 namespace {
 
 std::mutex g_default_mu;
@@ -179,7 +200,7 @@ int make_ctx(int device_ordinal, wg_ctx **out) {
     delete c;
     return fail(WG_ERR_HIP, "hipStreamCreateWithFlags failed for the context's host stream");
   }
-  if (const char *e = getenv("WG_OVERLAP_STRICT")) c->overlap_strict = atoi(e) != 0;   // read once per context, not per launch
+  c->overlap_strict = env_flag("WG_OVERLAP_STRICT", false);   // read once per context, not per launch
   *out = c;
   return WG_OK;
 }
@@ -229,12 +250,41 @@ int ctx_wait_own(wg_ctx *ctx) {
   if (ctx->pin_stream) HIP_TRY(hipStreamSynchronize(ctx->pin_stream));
   return WG_OK;
 }
-// staging copies of the host-pointer entry points: on the context's stream; the caller of these waits for that stream before it
-// returns (pageable host memory: the runtime stages the copy, the stream synchronise below covers both directions)
-#define WG_H2D(dst, src, bytes) HIP_TRY(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyHostToDevice, ctx->host_stream))
-#define WG_D2H(dst, src, bytes) HIP_TRY(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToHost, ctx->host_stream))
-#define WG_ZERO(dst, bytes) HIP_TRY(hipMemsetAsync((dst), 0, (bytes), ctx->host_stream))
-#define WG_HOST_WAIT() HIP_TRY(hipStreamSynchronize(ctx->host_stream))
+// Staging of the host-pointer entry points and the configure functions: copies, launches and copies back go on the context's
+// stream, from and to the caller's pageable arrays (the runtime stages those), and the call waits for that stream before it
+// returns -- on EVERY path: once anything was handed the stream, an error return first waits for what is queued on it.
+// Constructed with ctx->mu held, behind every host buffer the copies name (so that it is destroyed, and waits, before they are).
+struct HostScope {
+  wg_ctx *ctx;
+  bool used = false;
+  explicit HostScope(wg_ctx *c) : ctx(c) {}
+  HostScope(const HostScope &) = delete;
+  ~HostScope() { if (used) (void)hipStreamSynchronize(ctx->host_stream); }
+  hipStream_t stream() { used = true; return ctx->host_stream; }
+  hipError_t wait() { used = false; return hipStreamSynchronize(ctx->host_stream); }
+};
+#define WG_H2D(dst, src, bytes) HIP_TRY(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyHostToDevice, hs.stream()))
+#define WG_D2H(dst, src, bytes) HIP_TRY(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToHost, hs.stream()))
+#define WG_ZERO(dst, bytes) HIP_TRY(hipMemsetAsync((dst), 0, (bytes), hs.stream()))
+#define WG_HOST_WAIT() HIP_TRY(hs.wait())
+// One device buffer carved into the arrays of a call: take<T>() every array first, reserve() once, then arena(seg) is the
+// array (null for an array of no elements: an optional one the caller left out).  Every array starts on a 256-byte boundary.
+template <class T> struct Seg {
+  size_t off = 0, count = 0;
+  size_t bytes() const { return count * sizeof(T); }
+};
+struct Arena {
+  DevBuf &buf;
+  size_t size = 0;
+  explicit Arena(DevBuf &b) : buf(b) {}
+  template <class T> Seg<T> take(size_t count) {
+    Seg<T> s{size, count};
+    size += (count * sizeof(T) + 255) & ~(size_t)255;
+    return s;
+  }
+  int reserve() { return buf.reserve(size); }
+  template <class T> T *operator()(const Seg<T> &s) const { return s.count ? reinterpret_cast<T *>(static_cast<char *>(buf.p) + s.off) : nullptr; }
+};
 // after it: the event later launches are ordered behind
 int slot_mark(wg_ctx::SlotOrder &o, hipStream_t st) {
   if (!o.ev) HIP_TRY(hipEventCreateWithFlags(&o.ev, hipEventDisableTiming));
@@ -243,109 +293,29 @@ int slot_mark(wg_ctx::SlotOrder &o, hipStream_t st) {
   return WG_OK;
 }
 
-}  // namespace
-
-// ---------------------------------------------------------------------------
-// Dense batched QP kernel: one wavefront (= one workgroup) per QP.
-// Replaces ql0001_ (qld.hh:27-31) for B problems at once.
-// ---------------------------------------------------------------------------
-// kFixN / kFixM > 0: the Herdt-sized boundary (nmax == kFixN, mmax == kFixM, A, G and wa | b out of the LDS) with the strides, the
-// LDS layout and the solver's loop bounds as compile-time constants (QlView::carve_fixed_dense, DenseProbT<false, kFixN>)
-template <bool kALds, bool kGLds, bool kWLds = true, int kFixN = 0, int kFixM = 0>   // where A / G / wa | b live is known at compile time: ds_ or global_ accesses,
-// Left to itself the compiler takes 256 VGPRs plus 3 AGPRs -- 259 registers, one wave per SIMD, four QPs per CU where the LDS
-// would admit five at n = 36, m = 75.  Forced to two waves per SIMD (-DWG_QLD_WPE=2: 256 registers, 2-3 spilled, 12-16 B of
-// scratch) it measured 5 % SLOWER on the Herdt workload's real QPs (1.73 against 1.82 M QPs/s, B = 4096): the fifth QP per CU
-// does not pay for the tighter allocation.  The default stays.
-// With G read in place as well (21.7 KB of LDS at n = 36, m = 75: seven QPs per CU) the residency is worth the 256-register
-// build: that instantiation is compiled for two waves per SIMD.
-#ifdef WG_QLD_WPE
-#define WG_QLD_ATTR __attribute__((amdgpu_waves_per_eu(WG_QLD_WPE, WG_QLD_WPE)))
-#else
-#define WG_QLD_ATTR __attribute__((amdgpu_waves_per_eu(kGLds ? 1 : 2, kGLds ? 8 : 2)))
-#endif
-__global__ __launch_bounds__(64) WG_QLD_ATTR void wg_ql_dense_kernel(   // never flat_ (those also count on lgkmcnt and stall the LDS waits)
-    int B, int nmax_arg, int mmax_arg, const int *__restrict__ n_arr, const int *__restrict__ m_arr,
-    const int *__restrict__ me_arr, const double *__restrict__ C, const double *__restrict__ dvec,
-    const double *__restrict__ A, const double *__restrict__ bvec, const double *__restrict__ xl,
-    const double *__restrict__ xu, double eps, double *__restrict__ x, double *__restrict__ u,
-    int *__restrict__ ifail, int *__restrict__ n_iter, int *__restrict__ iact, int *__restrict__ nact,
-    int *__restrict__ hist, int hist_cap, int *__restrict__ hist_len, double *__restrict__ wab_slots,
-    const int *__restrict__ order, int *__restrict__ iters_out) {
-  extern __shared__ __attribute__((aligned(16))) double wg_lds[];
-  const int lane = threadIdx.x & 63;
-  // one QP per block (grid == B): nothing lane-dependent lives across QPs.  Blocks start in index order: `order`
-  // (wg_lpt_order_kernel) makes that the order of decreasing solve length, as far as the previous batch predicts it
-  const int qp = order ? wg::uni(order[blockIdx.x]) : (int)blockIdx.x;
-  const int nmax = kFixN > 0 ? kFixN : nmax_arg, mmax = kFixM > 0 ? kFixM : mmax_arg;   // the host checks the match
-  if (qp < B) {
-    const int n = n_arr ? n_arr[qp] : nmax;
-    const int m = m_arr ? m_arr[qp] : mmax - 1;
-    const int me = me_arr ? me_arr[qp] : 0;
-    wg::QlDims D(n, m, m, true, kALds, 0, true, true, kWLds, true, 0, kGLds);
-    wg::QlView q;
-    // kWLds = false: the constraint weights wa (m + n) and b (m) -- read lane-parallel once per iteration -- live in this
-    // block's slot of global memory [wa (mmax + nmax) | b (mmax)]: 1.5 KB less LDS, the eighth QP on the CU at n = 36, m = 75
-    if constexpr (kFixN > 0) q.template carve_fixed_dense<kFixN, kFixM>(wg_lds, n, m, me, wab_slots + (size_t)qp * (2 * kFixM + kFixN));
-    else if constexpr (kWLds) q.carve(wg_lds, D, me);
-    else q.template carve<true, false, true>(wg_lds, D, me, wab_slots + (size_t)qp * (2 * (size_t)mmax + nmax), mmax + nmax);
-
-    // ---- stage the problem into LDS (coalesced 8-byte lanes) ----
-    const double *Cg = C + (size_t)qp * nmax * nmax;
-    const double *Ag = A + (size_t)qp * mmax * nmax;
-    if constexpr (kGLds) {
-      for (int j = 0; j < n; ++j)
-        for (int i = lane; i < n; i += 64) q.G[i + j * q.ldg] = Cg[i + (size_t)j * nmax];
-    } else {                                   // G is cold after the factorisation: in place (L2), its diagonal in LDS
-      q.G = const_cast<double *>(Cg);
-      q.ldg = nmax;
-      for (int i = lane; i < n; i += 64) q.Gdiag[i] = Cg[i + (size_t)i * nmax];
-    }
-    if constexpr (kALds) {
-      for (int i = 0; i < n; ++i)
-        for (int k = lane; k < m; k += 64) q.A[k + i * q.lda] = Ag[k + (size_t)i * mmax];
-    } else {                                   // too large for LDS next to G, Z, R: the solver only reads A -> in place (L2)
-      q.A = const_cast<double *>(Ag);
-      q.lda = mmax;
-    }
-    for (int i = lane; i < n; i += 64) {
-      q.d[i] = dvec[(size_t)qp * nmax + i];
-      q.xl[i] = xl[(size_t)qp * nmax + i];
-      q.xu[i] = xu[(size_t)qp * nmax + i];
-    }
-    for (int k = lane; k < m; k += 64) q.b[k] = -bvec[(size_t)qp * mmax + k];   // qld.cpp:469-475
-    WG_WSYNC();
-    // qld.cpp:442-444: c(nmax,nmax) == 0 -> eps (inside the n x n block only if nmax == n)
-    typename std::conditional<(kFixN > 0), wg::DenseRegProb<(kFixN > 0 ? kFixN : 1), (kFixM > 0 ? kFixM : 1)>, wg::DenseProbT<kGLds, kFixN>>::type prob;
-    // (kFixN > 0: A's rows go into registers inside ql_solve, once R and Z exist -- m <= kFixM <= 128: two rows per lane)
-    if (nmax == n && lane == 0 && fabs(prob.Gd(q, n - 1)) == 0.0) prob.setGd(q, n - 1, eps);
-    WG_WSYNC();
-
-    int *hq = hist ? hist + (size_t)qp * hist_cap : nullptr;
-    wg::QlResult r = wg::ql_solve(q, prob, eps, hq, hist_cap);
-
-    // ---- results ----
-    for (int i = lane; i < n; i += 64) x[(size_t)qp * nmax + i] = q.x[i];
-    if (u) {
-      double *uq = u + (size_t)qp * (mmax + 2 * nmax);
-      if (r.ifail == 0) {                                   // qld.cpp:520-536
-        for (int j = lane; j < m + 2 * n; j += 64) uq[j] = 0.0;
-        WG_WSYNC();
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        for (int i = lane; i < r.nact; i += 64) uq[q.iact[i] - 1] = q.lam[i];
-      }
-    }
-    if (iact)
-      for (int i = lane; i < nmax; i += 64) iact[(size_t)qp * nmax + i] = (i < r.nact) ? q.iact[i] : 0;
-    if (lane == 0) {
-      ifail[qp] = r.ifail;
-      if (n_iter) n_iter[qp] = r.n_iter;
-      if (nact) nact[qp] = r.nact;
-      if (hist_len) hist_len[qp] = r.hist_len;
-      if (iters_out) iters_out[qp] = r.n_iter;
-    }
-    WG_WSYNC();
+// the order of one launch: (re)uses `s` for the batch (key, B) on stream st.  iters_out always; order only when the previous launch
+// of this kind was the same batch (its iteration counts are the prediction)
+int lpt_prepare(Lpt &s, const void *key, int B, hipStream_t st, int **order, int **iters_out) {
+  const bool known = s.key == key && s.B == B && s.buf.p;
+  if (int rc = s.buf.reserve((size_t)B * 2 * sizeof(int))) return rc;
+  *iters_out = static_cast<int *>(s.buf.p);
+  if (known) {
+    *order = *iters_out + B;
+    hipLaunchKernelGGL(wg_lpt_order_kernel, dim3(1), dim3(1024), 0, st, B, *iters_out, *order);
   }
+  s.key = key; s.B = B;
+  return WG_OK;
 }
+
+// the entry points without a context argument: the same call on the process-wide default context
+template <class R, class... P, class... A>
+R on_default(R (*fn)(wg_ctx *, P...), A... args) {
+  wg_ctx *c = nullptr;
+  if (int rc = default_ctx(&c)) return std::is_same<R, int>::value ? (R)rc : (R)-1;
+  return fn(c, args...);
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -429,10 +399,15 @@ int wg_prof_read(unsigned long long *out48) {          // 48 counters (wg_ql_dev
 
 size_t wg_qp_lds_bytes(int n, int m) { return wg::QlDims(n, m, m).bytes(); }
 
-int wg_qp_solve_batch_dev_ctx(wg_ctx_t *ctx, int B, int nmax, int mmax, const int *n, const int *m, const int *me, const double *C, const double *d, const double *A, const double *b, const double *xl, const double *xu, double eps, double *x, double *u, int *ifail, int *n_iter, int *iact, int *nact, int *hist, int hist_cap, int *hist_len, void *hip_stream) {
+static int qp_check(wg_ctx *ctx, int B, int nmax, int mmax, const double *C, const double *d, const double *A, const double *b, const double *xl, const double *xu, const double *x, const int *ifail) {
   if (int rc = use_ctx(ctx)) return rc;
   if (B < 0 || nmax <= 0 || mmax <= 0) return fail(WG_ERR_BAD_ARG, "bad sizes B=%d nmax=%d mmax=%d", B, nmax, mmax);
   if (!C || !d || !A || !b || !xl || !xu || !x || !ifail) return fail(WG_ERR_BAD_ARG, "null required pointer");
+  return WG_OK;
+}
+
+int wg_qp_solve_batch_dev_ctx(wg_ctx_t *ctx, int B, int nmax, int mmax, const int *n, const int *m, const int *me, const double *C, const double *d, const double *A, const double *b, const double *xl, const double *xu, double eps, double *x, double *u, int *ifail, int *n_iter, int *iact, int *nact, int *hist, int hist_cap, int *hist_len, void *hip_stream) {
+  if (int rc = qp_check(ctx, B, nmax, mmax, C, d, A, b, xl, xu, x, ifail)) return rc;
   if (hist && (!hist_len || hist_cap <= 0)) return fail(WG_ERR_BAD_ARG, "hist needs hist_len and hist_cap > 0");
   if (B == 0) return WG_OK;
   const int m_cap = m ? mmax : mmax - 1;
@@ -445,13 +420,12 @@ int wg_qp_solve_batch_dev_ctx(wg_ctx_t *ctx, int B, int nmax, int mmax, const in
   const size_t lds_noa = lds_for(false, true), lds_noag = lds_for(false, false);
   // residency each placement reaches: LDS, and the registers -- the kernels with G in LDS take 259 registers (one wave per
   // SIMD, four QPs per CU), the one with G in place is compiled for two waves per SIMD
-  auto per_cu = [](size_t l, size_t reg_cap) { const size_t k = (160 * 1024) / (l ? l : 1); return k > reg_cap ? reg_cap : k; };
-  if (per_cu(lds_noa, 4) > per_cu(lds, 4)) a_in_lds = 0;
+  if (per_cu_160k(lds_noa, 4) > per_cu_160k(lds, 4)) a_in_lds = 0;
   // G follows A out of the LDS when that buys at least two more resident QPs (G is cold after the factorisation; measured on the
   // Herdt workload's real QPs, n = 36, m = 75: 7 per CU against 4)
-  if (!a_in_lds && per_cu(lds_noag, 8) >= per_cu(lds_noa, 4) + 2) g_in_lds = 0;
-  if (const char *e = getenv("WG_QL_A_IN_LDS")) a_in_lds = atoi(e) != 0;   // tests force either path
-  if (const char *e = getenv("WG_QL_G_IN_LDS")) g_in_lds = atoi(e) != 0;
+  if (!a_in_lds && per_cu_160k(lds_noag, 8) >= per_cu_160k(lds_noa, 4) + 2) g_in_lds = 0;
+  a_in_lds = env_flag("WG_QL_A_IN_LDS", a_in_lds);                         // tests force either path
+  g_in_lds = env_flag("WG_QL_G_IN_LDS", g_in_lds);
   if (lds > 160 * 1024) a_in_lds = 0;
   if (a_in_lds) g_in_lds = 1;                                              // G leaves only after A
   if (!a_in_lds && lds_noa > 160 * 1024) g_in_lds = 0;
@@ -467,9 +441,7 @@ int wg_qp_solve_batch_dev_ctx(wg_ctx_t *ctx, int B, int nmax, int mmax, const in
   double *wab = nullptr;
   if (!a_in_lds && !g_in_lds) {
     const size_t lds_now = wg::QlDims(nmax, m_cap, m_cap, true, false, 0, true, true, false, true, 0, false).bytes();
-    auto gran_per_cu = [](size_t l) { const size_t k = 128 / ((l + 1279) / 1280); return k > 8 ? (size_t)8 : k; };
-    bool w_out = gran_per_cu(lds_now) > gran_per_cu(lds);
-    if (const char *e = getenv("WG_QL_W_IN_LDS")) w_out = atoi(e) == 0;
+    const bool w_out = !env_flag("WG_QL_W_IN_LDS", per_cu_granules(lds_now, 8) <= per_cu_granules(lds, 8));
     if (w_out && !slot_pending_elsewhere(ctx->qp_order, st)) {
       if (int rc = ctx->qp_slot.reserve((size_t)B * (2 * (size_t)mmax + nmax) * 8)) return rc;
       wab = static_cast<double *>(ctx->qp_slot.p);
@@ -479,103 +451,67 @@ int wg_qp_solve_batch_dev_ctx(wg_ctx_t *ctx, int B, int nmax, int mmax, const in
   // more QPs than resident waves: start them longest-solve-first by the iteration counts of the previous batch on the same
   // arrays (scheduling only; a caller that interleaves unrelated batches merely loses the benefit).  WG_QL_LPT=0: index order
   int *order = nullptr, *iters_out = nullptr;
-  {
-    size_t per_cu = 128 / ((lds + 1279) / 1280);
-    if (per_cu > 8) per_cu = 8;
-    if (per_cu < 1) per_cu = 1;
-    // the order lives in a buffer of the context: only a launch that also owns the context's wa | b slots uses it (those are
-    // handed to one launch at a time: see above), so no other launch rewrites the order under this one's blocks
-    bool lpt = wab != nullptr && (size_t)B > (size_t)ctx->num_cu * per_cu;
-    if (const char *e = getenv("WG_QL_LPT")) lpt = lpt && atoi(e) != 0;
-    if (lpt) {
-      const bool known = ctx->qlpt_key == C && ctx->qlpt_B == B && ctx->qlpt_buf.p;
-      if (int rc = ctx->qlpt_buf.reserve((size_t)B * 2 * sizeof(int))) return rc;
-      iters_out = static_cast<int *>(ctx->qlpt_buf.p);
-      if (known) {
-        order = iters_out + B;
-        hipLaunchKernelGGL(wg_lpt_order_kernel, dim3(1), dim3(1024), 0, st, B, iters_out, order);
-      }
-      ctx->qlpt_key = C; ctx->qlpt_B = B;
-    }
-  }
-  // the Herdt-sized boundary (what QPProblem::solve hands over at N = 16: nmax = 36, mmax = 76) has its own instantiation
-  bool fixed36 = wab && nmax == 36 && mmax == 76;
-  if (const char *e = getenv("WG_QL_FIXED")) fixed36 = fixed36 && atoi(e) != 0;
-  if (fixed36) {
-    lds = wg::QlView::fixed_dense_bytes<36>();
-    hipLaunchKernelGGL((wg_ql_dense_kernel<false, false, false, 36, 76>), dim3(B), dim3(64), lds, st, B, nmax, mmax, n, m, me, C, d, A, b,
-                       xl, xu, eps, x, u, ifail, n_iter, iact, nact, hist, hist_cap, hist_len, wab, order, iters_out);
+  // the order lives in a buffer of the context: only a launch that also owns the context's wa | b slots uses it (those are
+  // handed to one launch at a time: see above), so no other launch rewrites the order under this one's blocks
+  if (wab != nullptr && (size_t)B > (size_t)ctx->num_cu * per_cu_granules(lds, 8) && env_flag("WG_QL_LPT", true))
+    if (int rc = lpt_prepare(ctx->qp_lpt, C, B, st, &order, &iters_out)) return rc;
+  // where A / G / wa | b live is a template argument; the Herdt-sized boundary (what QPProblem::solve hands over at N = 16:
+  // nmax = 36, mmax = 76) has its own instantiation
+  const bool fixed36 = wab && nmax == 36 && mmax == 76 && env_flag("WG_QL_FIXED", true);
+  if (fixed36) lds = wg::QlView::fixed_dense_bytes<36>();
+  void (*kern)(int, int, int, const int *, const int *, const int *, const double *, const double *, const double *, const double *,
+               const double *, const double *, double, double *, double *, int *, int *, int *, int *, int *, int, int *, double *,
+               const int *, int *);
+  if (fixed36) kern = wg_ql_dense_kernel<false, false, false, 36, 76>;
+  else if (a_in_lds) kern = wg_ql_dense_kernel<true, true>;
+  else if (g_in_lds) kern = wg_ql_dense_kernel<false, true>;
+  else if (wab) kern = wg_ql_dense_kernel<false, false, false>;
+  else kern = wg_ql_dense_kernel<false, false>;
+  if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kern, dim3(B), dim3(64), lds, st, B, nmax, mmax, n, m, me, C, d, A, b, xl, xu, eps, x, u, ifail, n_iter, iact, nact,
+                     hist, hist_cap, hist_len, wab, order, iters_out);
+  if (wab)
     if (int rc = slot_mark(ctx->qp_order, st)) return rc;
-    HIP_TRY(hipGetLastError());
-    return WG_OK;
-  }
-  const void *kfn = a_in_lds ? reinterpret_cast<const void *>(wg_ql_dense_kernel<true, true>)
-                             : (g_in_lds ? reinterpret_cast<const void *>(wg_ql_dense_kernel<false, true>)
-                                         : (wab ? reinterpret_cast<const void *>(wg_ql_dense_kernel<false, false, false>)
-                                                : reinterpret_cast<const void *>(wg_ql_dense_kernel<false, false>)));
-  if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int grid = B;
-  if (a_in_lds)
-    hipLaunchKernelGGL((wg_ql_dense_kernel<true, true>), dim3(grid), dim3(64), lds, st, B, nmax, mmax, n, m, me, C, d, A, b,
-                       xl, xu, eps, x, u, ifail, n_iter, iact, nact, hist, hist_cap, hist_len, wab, order, iters_out);
-  else if (g_in_lds)
-    hipLaunchKernelGGL((wg_ql_dense_kernel<false, true>), dim3(grid), dim3(64), lds, st, B, nmax, mmax, n, m, me, C, d, A, b,
-                       xl, xu, eps, x, u, ifail, n_iter, iact, nact, hist, hist_cap, hist_len, wab, order, iters_out);
-  else if (!wab)
-    hipLaunchKernelGGL((wg_ql_dense_kernel<false, false>), dim3(grid), dim3(64), lds, st, B, nmax, mmax, n, m, me, C, d, A, b,
-                       xl, xu, eps, x, u, ifail, n_iter, iact, nact, hist, hist_cap, hist_len, wab, order, iters_out);
-  else {
-    hipLaunchKernelGGL((wg_ql_dense_kernel<false, false, false>), dim3(grid), dim3(64), lds, st, B, nmax, mmax, n, m, me, C, d, A, b,
-                       xl, xu, eps, x, u, ifail, n_iter, iact, nact, hist, hist_cap, hist_len, wab, order, iters_out);
-    if (int rc = slot_mark(ctx->qp_order, st)) return rc;
-  }
   HIP_TRY(hipGetLastError());
   return WG_OK;
 }
 
 int wg_qp_solve_batch_ctx(wg_ctx_t *ctx, int B, int nmax, int mmax, const int *n, const int *m, const int *me, const double *C, const double *d, const double *A, const double *b, const double *xl, const double *xu, double eps, double *x, double *u, int *ifail, int *n_iter, int *iact, int *nact, int *hist, int hist_cap, int *hist_len) {
-  if (int rc = use_ctx(ctx)) return rc;
-  if (B < 0 || nmax <= 0 || mmax <= 0) return fail(WG_ERR_BAD_ARG, "bad sizes B=%d nmax=%d mmax=%d", B, nmax, mmax);
-  if (!C || !d || !A || !b || !xl || !xu || !x || !ifail) return fail(WG_ERR_BAD_ARG, "null required pointer");
+  if (int rc = qp_check(ctx, B, nmax, mmax, C, d, A, b, xl, xu, x, ifail)) return rc;
   if (B == 0) return WG_OK;
   std::lock_guard<std::mutex> lk(ctx->mu);
-  const size_t sB = (size_t)B;
-  // input arena
-  struct Seg { const void *h; size_t bytes; size_t off; };
-  std::vector<Seg> in = {
-      {C, sB * nmax * nmax * 8, 0}, {d, sB * nmax * 8, 0},  {A, sB * mmax * nmax * 8, 0},
-      {b, sB * mmax * 8, 0},        {xl, sB * nmax * 8, 0}, {xu, sB * nmax * 8, 0},
-      {n, n ? sB * 4 : 0, 0},       {m, m ? sB * 4 : 0, 0}, {me, me ? sB * 4 : 0, 0}};
-  size_t tot = 0;
-  for (auto &s : in) { s.off = tot; tot += (s.bytes + 255) & ~(size_t)255; }
-  if (int rc = ctx->in.reserve(tot)) return rc;
-  char *din = static_cast<char *>(ctx->in.p);
-  for (auto &s : in)
-    if (s.bytes) WG_H2D(din + s.off, s.h, s.bytes);
-  struct OSeg { void *h; size_t bytes; size_t off; };
-  std::vector<OSeg> out = {{x, sB * nmax * 8, 0},
-                           {u, u ? sB * (mmax + 2 * (size_t)nmax) * 8 : 0, 0},
-                           {ifail, sB * 4, 0},
-                           {n_iter, n_iter ? sB * 4 : 0, 0},
-                           {iact, iact ? sB * nmax * 4 : 0, 0},
-                           {nact, nact ? sB * 4 : 0, 0},
-                           {hist, hist ? sB * hist_cap * 4 : 0, 0},
-                           {hist_len, hist_len ? sB * 4 : 0, 0}};
-  size_t otot = 0;
-  for (auto &s : out) { s.off = otot; otot += (s.bytes + 255) & ~(size_t)255; }
-  if (int rc = ctx->out.reserve(otot)) return rc;
-  char *dout = static_cast<char *>(ctx->out.p);
-  WG_ZERO(dout, otot);
-  auto ip = [&](int k) { return in[k].bytes ? din + in[k].off : nullptr; };
-  auto op = [&](int k) { return out[k].bytes ? dout + out[k].off : nullptr; };
-  int rc = wg_qp_solve_batch_dev_ctx(ctx, B, nmax, mmax, (const int *)ip(6), (const int *)ip(7), (const int *)ip(8),
-                                 (const double *)ip(0), (const double *)ip(1), (const double *)ip(2),
-                                 (const double *)ip(3), (const double *)ip(4), (const double *)ip(5), eps,
-                                 (double *)op(0), (double *)op(1), (int *)op(2), (int *)op(3), (int *)op(4),
-                                 (int *)op(5), (int *)op(6), hist_cap, (int *)op(7), ctx->host_stream);
-  if (rc) return rc;
-  for (auto &s : out)
-    if (s.bytes) WG_D2H(s.h, dout + s.off, s.bytes);
+  HostScope hs(ctx);
+  const size_t sB = (size_t)B, sn = (size_t)nmax, sm = (size_t)mmax;
+  Arena in(ctx->in), out(ctx->out);
+  const auto iC = in.take<double>(sB * sn * sn), id = in.take<double>(sB * sn), iA = in.take<double>(sB * sm * sn), ib = in.take<double>(sB * sm),
+             ixl = in.take<double>(sB * sn), ixu = in.take<double>(sB * sn);
+  const auto in_ = in.take<int>(n ? sB : 0), im = in.take<int>(m ? sB : 0), ime = in.take<int>(me ? sB : 0);
+  const auto ox = out.take<double>(sB * sn), ou = out.take<double>(u ? sB * (sm + 2 * sn) : 0);
+  const auto oifail = out.take<int>(sB), oiter = out.take<int>(n_iter ? sB : 0), oiact = out.take<int>(iact ? sB * sn : 0),
+             onact = out.take<int>(nact ? sB : 0), ohist = out.take<int>(hist ? sB * hist_cap : 0), ohlen = out.take<int>(hist_len ? sB : 0);
+  if (int rc = in.reserve()) return rc;
+  if (int rc = out.reserve()) return rc;
+  WG_H2D(in(iC), C, iC.bytes());
+  WG_H2D(in(id), d, id.bytes());
+  WG_H2D(in(iA), A, iA.bytes());
+  WG_H2D(in(ib), b, ib.bytes());
+  WG_H2D(in(ixl), xl, ixl.bytes());
+  WG_H2D(in(ixu), xu, ixu.bytes());
+  if (n) WG_H2D(in(in_), n, in_.bytes());
+  if (m) WG_H2D(in(im), m, im.bytes());
+  if (me) WG_H2D(in(ime), me, ime.bytes());
+  WG_ZERO(ctx->out.p, out.size);
+  if (int rc = wg_qp_solve_batch_dev_ctx(ctx, B, nmax, mmax, in(in_), in(im), in(ime), in(iC), in(id), in(iA), in(ib), in(ixl), in(ixu), eps, out(ox),
+                                         out(ou), out(oifail), out(oiter), out(oiact), out(onact), out(ohist), hist_cap, out(ohlen), hs.stream()))
+    return rc;
+  WG_D2H(x, out(ox), ox.bytes());
+  if (u) WG_D2H(u, out(ou), ou.bytes());
+  WG_D2H(ifail, out(oifail), oifail.bytes());
+  if (n_iter) WG_D2H(n_iter, out(oiter), oiter.bytes());
+  if (iact) WG_D2H(iact, out(oiact), oiact.bytes());
+  if (nact) WG_D2H(nact, out(onact), onact.bytes());
+  if (hist) WG_D2H(hist, out(ohist), ohist.bytes());
+  if (hist_len) WG_D2H(hist_len, out(ohlen), ohlen.bytes());
   WG_HOST_WAIT();
   return WG_OK;
 }
@@ -600,9 +536,8 @@ inline int tick_max_m(const wg_model_t &m) { return 1 + 4 * m.N + 5 * tick_smax(
 //                wg_mpc_assemble_batch, which writes the QP out
 // WG_TICK_VIEW=element sends N == 16 through the element view as well (tests).
 inline bool tick_compact(const wg_model_t &m) {
-  const char *e = getenv("WG_TICK_DENSE");
   const char *v = getenv("WG_TICK_VIEW");
-  return m.N == 16 && m.N * m.T <= 2.0 * m.step_period + 1e-12 && !(e && atoi(e) != 0) && !(v && *v);
+  return m.N == 16 && m.N * m.T <= 2.0 * m.step_period + 1e-12 && !env_flag("WG_TICK_DENSE", false) && !(v && *v);
 }
 // element view (-1: any horizon; 32: BASELINE config 5's horizon as a compile-time constant -- same LDS bytes, same slot, a fixed
 // layout): Z in a per-block slot of global memory instead of LDS (decided at compile time: mpc_tick<-1>, mpc_tick<32>)
@@ -651,8 +586,7 @@ inline int tick_elem_cap(const wg_model_t &m, int view) {
     return (c < n && fits(c)) ? c : 0;
   }
   // waves a CU holds by the registers the element view's kernels are compiled for (WG_TICK32_WPE per SIMD, four SIMDs)
-  const size_t wcap = 4 * (size_t)tick_waves_per_simd(view);
-  auto per_cu = [&](int c) { const size_t g = (tick_lds_with_cap(m, view, c) + 1279) / 1280; size_t k = 128 / g; return k > wcap ? wcap : k; };
+  auto per_cu = [&](int c) { return per_cu_granules(tick_lds_with_cap(m, view, c), 4 * (size_t)tick_waves_per_simd(view)); };
   const size_t full = per_cu(0);
   int best = 0;
   size_t best_k = full;
@@ -662,12 +596,10 @@ inline int tick_elem_cap(const wg_model_t &m, int view) {
 }
 // what the kernels receive: the column cap in the low 16 bits; tests may ask the solver to give up EARLIER than the layout
 // requires (WG_ELEM_ABORT_AT: active-set size at which the first attempt stops), so that the second route is taken often
-inline int tick_elem_cap_arg(const wg_model_t &m, int view) {
-  const int c = tick_elem_cap(m, view);
+inline int tick_elem_cap_arg(int c) {
   if (!c) return 0;
-  int a = c;
-  if (const char *e = getenv("WG_ELEM_ABORT_AT")) { const int v = atoi(e); if (v >= 1 && v < c) a = v; }
-  return c | (a << 16);
+  const int v = env_int("WG_ELEM_ABORT_AT", 0);
+  return c | ((v >= 1 && v < c ? v : c) << 16);
 }
 inline size_t tick_z_slot_doubles(const wg_model_t &m, int view) {
   const size_t n = (size_t)tick_max_n(m), mm = (size_t)tick_max_m(m);
@@ -681,8 +613,7 @@ inline size_t tick_lds_for(const wg_model_t &m, int view) { return tick_lds_with
 inline int tick_view(const wg_model_t &m) {
   if (tick_compact(m)) return 16;
   const bool dense_fits = tick_lds_for(m, 0) <= 160 * 1024;
-  const char *d = getenv("WG_TICK_DENSE");
-  if (d && atoi(d) != 0 && dense_fits) return 0;          // tests: the dense view where the element view would be taken
+  if (env_flag("WG_TICK_DENSE", false) && dense_fits) return 0;          // tests: the dense view where the element view would be taken
   // Everywhere else the element view: 5 - 12.6 KB of LDS per gait (twelve per CU, three on every SIMD) against the dense view's
   // G and A as LDS matrices (N = 20: 100 KB, ONE gait per CU -- measured 1.65 M against 0.39 M ticks/s; N = 24: 1.15 M against
   // 0.27 M; same bits).  Its pre-solve group lies over R (short horizons: in bytes of its own, TickLds::elem_overlay_apart)
@@ -690,17 +621,63 @@ inline int tick_view(const wg_model_t &m) {
   // LDS offset a constant, only the two-rows-per-lane forms of the solver); WG_TICK_ELEM_GENERIC=1 keeps the any-horizon
   // kernel there too (tests run both: same bytes)
   if (m.N == 32) {
-    const char *g = getenv("WG_TICK_ELEM_GENERIC");
-    if (g && atoi(g) != 0) return -1;
+    if (env_flag("WG_TICK_ELEM_GENERIC", false)) return -1;
 #ifdef WG_WITH_REGZ
-    const char *z = getenv("WG_TICK_REGZ");              // experiment builds: Z in registers, four gaits per CU (mpc_tick<33>)
-    if (z && atoi(z) != 0) return 33;
+    if (env_flag("WG_TICK_REGZ", false)) return 33;      // experiment builds: Z in registers, four gaits per CU (mpc_tick<33>)
 #endif
     return 32;
   }
   return -1;
 }
-inline size_t tick_ql_bytes(const wg_model_t &m) { return tick_ql_bytes_for(m, tick_view(m), tick_elem_cap(m, tick_view(m))); }
+
+// Everything a launch of the tick / run kernels derives from the model and the environment, in one place.
+struct TickPlan {
+  int view;            // problem view = template argument of the kernels
+  size_t lds;          // dynamic LDS per block (what wg_mpc_tick_lds_bytes* report)
+  size_t launch_lds;   // the same plus WG_TICK_LDS_PAD (experiments: lower the residency)
+  size_t qlb;          // the solver area's share of it
+  size_t zslot;        // doubles per block in tick_z (views that keep operands in a global slot; see `slots`)
+  int ecap;            // element view: the column cap of R as the kernels receive it
+  size_t wave_cap;     // waves per CU the kernel's register budget admits
+  bool slots;
+  explicit TickPlan(const wg_model_t &m) : view(tick_view(m)) {
+    const int cap = tick_elem_cap(m, view);
+    lds = tick_lds_with_cap(m, view, cap);
+    launch_lds = lds + (size_t)env_int("WG_TICK_LDS_PAD", 0);
+    qlb = tick_ql_bytes_for(m, view, cap);
+    zslot = tick_z_slot_doubles(m, view);
+    ecap = tick_elem_cap_arg(cap);
+    wave_cap = 4 * (size_t)tick_waves_per_simd(view);
+    slots = tick_z_global(view) || tick16_ext(view);
+  }
+  int per_cu() const { return (int)per_cu_granules(launch_lds, wave_cap); }   // blocks a CU keeps resident
+  // the per-block solver slots for a grid of `blocks`: sized for the grid a launch has (a one-robot facade pays for one slot, a
+  // fleet for its resident waves); growing never frees what a launch in flight may be using (DevBuf)
+  int reserve_slots(wg_ctx *ctx, int blocks, double **zs) const {
+    *zs = nullptr;
+    if (!slots) return WG_OK;
+    if (int rc = ctx->tick_z.reserve((size_t)blocks * zslot * 8)) return rc;
+    *zs = static_cast<double *>(ctx->tick_z.p);
+    return WG_OK;
+  }
+  int raise_lds(const void *kernel) const {
+    if (launch_lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)launch_lds));
+    return WG_OK;
+  }
+};
+// multi-tick launches, hand-over inside one XCD: ring slots per XCD (a gait is in at most one ring, at most once) and the bytes
+// of run_buf [control | rings | done flags]
+inline int run_ring_cap(int B) { int cap = 1; while (cap < 2 * B) cap <<= 1; return cap; }
+inline size_t run_buf_bytes(int B) { return sizeof(wg_xrun_ctl) + (size_t)kXcds * run_ring_cap(B) * 8 + (size_t)B * 4; }
+// hand-over inside one XCD (default) or through one device-wide queue (WG_RUN_QUEUE=global: A/B tests)
+inline bool run_queue_xcd() { const char *e = getenv("WG_RUN_QUEUE"); return !e || e[0] != 'g'; }
+
+int tick_check(wg_ctx *ctx, int B, const wg_gait_state_t *states) {
+  if (int rc = use_ctx(ctx)) return rc;
+  if (!ctx->model_set) return fail(WG_ERR_BAD_ARG, "wg_mpc_configure() has not been called on this context");
+  if (B < 0 || !states) return fail(WG_ERR_BAD_ARG, "bad arguments");
+  return WG_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -739,7 +716,7 @@ int wg_mpc_configure_ctx(wg_ctx_t *ctx, const wg_model_t *model) {
   if (model->N < 2 || model->N > wg::kNMaxH) return fail(WG_ERR_BAD_ARG, "N=%d outside [2,%d]", model->N, wg::kNMaxH);
   if ((int)(model->T / model->Tctrl) != WG_SAMPLES_PER_TICK)
     return fail(WG_ERR_BAD_ARG, "T/Tctrl must be %d", WG_SAMPLES_PER_TICK);
-  size_t lds = tick_lds_for(*model, tick_view(*model));
+  const size_t lds = TickPlan(*model).lds;
   if (lds > 160 * 1024) return fail(WG_ERR_TOO_LARGE, "tick needs %zu B of LDS > 160 KiB", lds);
   std::vector<double> qb;                              // Q_b from the matrix cores, when the model asks for it
   if (model->flags & (WG_FLAG_GRAMIAN_MFMA_F64 | WG_FLAG_GRAMIAN_MFMA_F32)) {
@@ -756,11 +733,12 @@ int wg_mpc_configure_ctx(wg_ctx_t *ctx, const wg_model_t *model) {
   if (!host_tables.blocks_ok && !qb.empty())
     return fail(WG_ERR_BAD_ARG, "the matrix-core Gramian is not positive definite enough for ql0002's factorisation");
   if (!ctx->tables_dev) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ctx->tables_dev), sizeof(wg::TickTables)));
+  if (!ctx->model_dev) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ctx->model_dev), sizeof(wg_model_t)));
   // a launch of an earlier configuration may still be reading the tables: this context's own launches, on whatever stream they
   // went (every tick / run / assemble launch leaves an event) -- other contexts and other work on the device are not waited for
   if (int rc = ctx_wait_own(ctx)) return rc;
+  HostScope hs(ctx);
   WG_H2D(ctx->tables_dev, &host_tables, sizeof host_tables);
-  if (!ctx->model_dev) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ctx->model_dev), sizeof(wg_model_t)));
   WG_H2D(ctx->model_dev, model, sizeof(wg_model_t));
   WG_HOST_WAIT();
   ctx->model = *model;
@@ -773,12 +751,12 @@ int wg_mpc_configure_ctx(wg_ctx_t *ctx, const wg_model_t *model) {
 
 size_t wg_mpc_tick_lds_bytes_for(const wg_model_t *model) {   // host arithmetic only: no device needed
   if (!model || model->N < 2 || model->N > wg::kNMaxH) return 0;
-  return tick_lds_for(*model, tick_view(*model));
+  return TickPlan(*model).lds;
 }
 
 size_t wg_mpc_tick_lds_bytes_ctx(wg_ctx_t *ctx) {
   if (!ctx || !ctx->model_set) return 0;
-  return tick_lds_for(ctx->model, tick_view(ctx->model));
+  return TickPlan(ctx->model).lds;
 }
 
 /* The tick / run kernels' per-block solver slots and queue for fleets of up to max_gaits, allocated now instead of by the first
@@ -787,64 +765,34 @@ int wg_mpc_reserve_ctx(wg_ctx_t *ctx, int max_gaits) {
   if (int rc = use_ctx(ctx)) return rc;
   if (!ctx->model_set) return fail(WG_ERR_BAD_ARG, "wg_mpc_configure() has not been called on this context");
   if (max_gaits < 1) return fail(WG_ERR_BAD_ARG, "max_gaits = %d", max_gaits);
-  const int view = tick_view(ctx->model);
+  const TickPlan plan(ctx->model);
   std::lock_guard<std::mutex> launch_lk(ctx->launch_mu);
-  if (tick_z_global(view) || tick16_ext(view))
-    if (int rc = ctx->tick_z.reserve((size_t)max_gaits * tick_z_slot_doubles(ctx->model, view) * 8)) return rc;
-  int cap = 1;
-  while (cap < 2 * max_gaits) cap <<= 1;
-  return ctx->run_buf.reserve(sizeof(wg_xrun_ctl) + (size_t)kXcds * cap * 8 + (size_t)max_gaits * 4);
+  double *zs = nullptr;
+  if (int rc = plan.reserve_slots(ctx, max_gaits, &zs)) return rc;
+  return ctx->run_buf.reserve(run_buf_bytes(max_gaits));
 }
 
 }  // extern "C"
 namespace {
 int tick_launch(wg_ctx_t *ctx, int B, wg_gait_state_t *states, wg_tick_out_t *outs, int *diag, int advance_calls, int *hist, int hist_cap, int *hist_len, void *hip_stream, wg_gait_state_t *host_states, int *host_done) {
-  if (int rc = use_ctx(ctx)) return rc;
-  if (!ctx->model_set) return fail(WG_ERR_BAD_ARG, "wg_mpc_configure() has not been called on this context");
-  if (B < 0 || !states) return fail(WG_ERR_BAD_ARG, "bad arguments");
+  if (int rc = tick_check(ctx, B, states)) return rc;
   if (hist && (!hist_len || hist_cap <= 0)) return fail(WG_ERR_BAD_ARG, "hist needs hist_len and hist_cap > 0");
   if (B == 0) return WG_OK;
-  const size_t qlb = tick_ql_bytes(ctx->model);
-  const int view = tick_view(ctx->model);
-  size_t lds = tick_lds_for(ctx->model, view);
-  if (const char *pad = getenv("WG_TICK_LDS_PAD")) lds += (size_t)atoi(pad);   // experiments: lower the residency
-  if (lds > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute(WG_KERNEL_BY_VIEW(wg_mpc_tick_kernel, view), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const TickPlan plan(ctx->model);
+  if (int rc = plan.raise_lds(WG_KERNEL_BY_VIEW(wg_mpc_tick_kernel, plan.view))) return rc;
   const int grid = B;                             // one gait per block; the dispatcher balances uneven iteration counts
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
   std::lock_guard<std::mutex> launch_lk(ctx->launch_mu);   // ordering test, launch and event record are one critical section
   if (int rc = slot_claim(ctx, ctx->guard_order, st, "tick / run")) return rc;
-  const int ecap = tick_elem_cap_arg(ctx->model, view);
   double *zs = nullptr;
-  const size_t zslot = tick_z_slot_doubles(ctx->model, view);
-  if (tick_z_global(view) || tick16_ext(view)) {
-    // sized here, for the grid this launch has (a one-robot facade pays for one slot, a fleet for its resident waves); growing
-    // never frees what a launch in flight may be using (DevBuf); wg_mpc_reserve sizes it ahead of time
-    if (int rc = ctx->tick_z.reserve((size_t)grid * zslot * 8)) return rc;
-    zs = static_cast<double *>(ctx->tick_z.p);
-  }
+  if (int rc = plan.reserve_slots(ctx, grid, &zs)) return rc;    // wg_mpc_reserve sizes them ahead of time
   // more gaits than resident waves: start them longest-solve-first (see wg_lpt_order_kernel); the iteration counts are those of
   // the previous call on the same state array -- a prediction, so a caller that interleaves batches merely loses the benefit
   int *order = nullptr, *iters_out = nullptr;
-  {
-    int per_cu = 128 / (int)((lds + 1279) / 1280);
-    const int max_waves = 4 * tick_waves_per_simd(view);
-    if (per_cu > max_waves) per_cu = max_waves;
-    bool lpt = B > ctx->num_cu * per_cu && !host_states;
-    if (const char *e = getenv("WG_TICK_LPT")) lpt = lpt && atoi(e) != 0;
-    if (lpt) {
-      const bool known = ctx->lpt_states == states && ctx->lpt_B == B && ctx->lpt_buf.p;
-      if (int rc = ctx->lpt_buf.reserve((size_t)B * 2 * sizeof(int))) return rc;
-      iters_out = static_cast<int *>(ctx->lpt_buf.p);
-      if (known) {
-        order = iters_out + B;
-        hipLaunchKernelGGL(wg_lpt_order_kernel, dim3(1), dim3(1024), 0, st, B, iters_out, order);
-      }
-      ctx->lpt_states = states; ctx->lpt_B = B;
-    }
-  }
-  WG_LAUNCH_BY_VIEW(wg_mpc_tick_kernel, view, grid, lds, st, B, ctx->model, ctx->tables_dev, states, outs, diag, advance_calls, hist, hist_cap,
-                    hist_len, (unsigned)qlb, zs, (unsigned)zslot, ecap, host_states, host_done, order, iters_out);
+  if (B > ctx->num_cu * plan.per_cu() && !host_states && env_flag("WG_TICK_LPT", true))
+    if (int rc = lpt_prepare(ctx->tick_lpt, states, B, st, &order, &iters_out)) return rc;
+  WG_LAUNCH_BY_VIEW(wg_mpc_tick_kernel, plan.view, grid, plan.launch_lds, st, B, ctx->model, ctx->tables_dev, states, outs, diag, advance_calls, hist,
+                    hist_cap, hist_len, (unsigned)plan.qlb, zs, (unsigned)plan.zslot, plan.ecap, host_states, host_done, order, iters_out);
   HIP_TRY(hipGetLastError());
   return slot_mark(ctx->guard_order, st);
 }
@@ -940,27 +888,26 @@ int wg_mpc_assemble_batch_ctx(wg_ctx_t *ctx, int B, const wg_gait_state_t *state
   if (B < 0 || !states || !C || !d || !A || !b || !xl || !xu || !n || !m || nmax <= 0 || mmax <= 0) return fail(WG_ERR_BAD_ARG, "bad arguments");
   if (B == 0) return WG_OK;
   std::lock_guard<std::mutex> lk(ctx->mu);
+  HostScope hs(ctx);
   const size_t sB = (size_t)B, sn = (size_t)nmax, sm = (size_t)mmax;
-  const size_t off_C = (sB * sizeof(wg_gait_state_t) + 255) & ~(size_t)255, off_d = off_C + sB * sn * sn * 8, off_A = off_d + sB * sn * 8,
-               off_b = off_A + sB * sm * sn * 8, off_xl = off_b + sB * sm * 8, off_xu = off_xl + sB * sn * 8, off_n = off_xu + sB * sn * 8,
-               off_m = off_n + sB * 4, tot = off_m + sB * 4;
-  if (int rc = ctx->in.reserve(tot)) return rc;
-  char *base = static_cast<char *>(ctx->in.p);
-  WG_H2D(base, states, sB * sizeof(wg_gait_state_t));
-  int rc = wg_mpc_assemble_batch_dev_ctx(ctx, B, reinterpret_cast<const wg_gait_state_t *>(base), advance_calls, nmax, mmax,
-                                         reinterpret_cast<double *>(base + off_C), reinterpret_cast<double *>(base + off_d),
-                                         reinterpret_cast<double *>(base + off_A), reinterpret_cast<double *>(base + off_b),
-                                         reinterpret_cast<double *>(base + off_xl), reinterpret_cast<double *>(base + off_xu),
-                                         reinterpret_cast<int *>(base + off_n), reinterpret_cast<int *>(base + off_m), ctx->host_stream);
-  if (rc) return rc;
-  WG_D2H(C, base + off_C, sB * sn * sn * 8);
-  WG_D2H(d, base + off_d, sB * sn * 8);
-  WG_D2H(A, base + off_A, sB * sm * sn * 8);
-  WG_D2H(b, base + off_b, sB * sm * 8);
-  WG_D2H(xl, base + off_xl, sB * sn * 8);
-  WG_D2H(xu, base + off_xu, sB * sn * 8);
-  WG_D2H(n, base + off_n, sB * 4);
-  WG_D2H(m, base + off_m, sB * 4);
+  Arena a(ctx->in);
+  const auto s_st = a.take<wg_gait_state_t>(sB);
+  const auto sC = a.take<double>(sB * sn * sn), sd = a.take<double>(sB * sn), sA = a.take<double>(sB * sm * sn), sb = a.take<double>(sB * sm),
+             sxl = a.take<double>(sB * sn), sxu = a.take<double>(sB * sn);
+  const auto s_n = a.take<int>(sB), s_m = a.take<int>(sB);
+  if (int rc = a.reserve()) return rc;
+  WG_H2D(a(s_st), states, s_st.bytes());
+  if (int rc = wg_mpc_assemble_batch_dev_ctx(ctx, B, a(s_st), advance_calls, nmax, mmax, a(sC), a(sd), a(sA), a(sb), a(sxl), a(sxu), a(s_n), a(s_m),
+                                             hs.stream()))
+    return rc;
+  WG_D2H(C, a(sC), sC.bytes());
+  WG_D2H(d, a(sd), sd.bytes());
+  WG_D2H(A, a(sA), sA.bytes());
+  WG_D2H(b, a(sb), sb.bytes());
+  WG_D2H(xl, a(sxl), sxl.bytes());
+  WG_D2H(xu, a(sxu), sxu.bytes());
+  WG_D2H(n, a(s_n), s_n.bytes());
+  WG_D2H(m, a(s_m), s_m.bytes());
   WG_HOST_WAIT();
   return WG_OK;
 }
@@ -974,35 +921,24 @@ int wg_mpc_run_sched_dev_ctx(wg_ctx_t *ctx, int B, wg_gait_state_t *states, int 
   if (!ctx->model_set) return fail(WG_ERR_BAD_ARG, "wg_mpc_configure() has not been called on this context");
   if (B < 0 || n_ticks < 0 || !states || period < 1) return fail(WG_ERR_BAD_ARG, "bad arguments");
   if (B == 0 || n_ticks == 0) return WG_OK;
-  if (vref_sched) {
-    bool xcd = true;
-    if (const char *e = getenv("WG_RUN_QUEUE")) xcd = e[0] != 'g';
-    if (!xcd) {                                      // the device-wide queue of round 1 has no staged form: one launch per stretch
-      for (int t = 0; t < n_ticks; t += period) {
-        const int n = n_ticks - t < period ? n_ticks - t : period;
-        if (int rc = wg_mpc_set_velref_dev_ctx(ctx, B, states, vref_sched + (size_t)(t / period) * B * 3, hip_stream)) return rc;
-        if (int rc = wg_mpc_run_sched_dev_ctx(ctx, B, states, n, advance_calls, nullptr, 1, outs ? outs + (size_t)t * B : nullptr,
-                                              diag ? diag + (size_t)t * B * 6 : nullptr, hip_stream))
-          return rc;
-      }
-      return WG_OK;
+  if (vref_sched && !run_queue_xcd()) {              // the device-wide queue of round 1 has no staged form: one launch per stretch
+    for (int t = 0; t < n_ticks; t += period) {
+      const int n = n_ticks - t < period ? n_ticks - t : period;
+      if (int rc = wg_mpc_set_velref_dev_ctx(ctx, B, states, vref_sched + (size_t)(t / period) * B * 3, hip_stream)) return rc;
+      if (int rc = wg_mpc_run_sched_dev_ctx(ctx, B, states, n, advance_calls, nullptr, 1, outs ? outs + (size_t)t * B : nullptr,
+                                            diag ? diag + (size_t)t * B * 6 : nullptr, hip_stream))
+        return rc;
     }
+    return WG_OK;
   }
   if ((long long)B * n_ticks > 0x3fffffffLL) return fail(WG_ERR_TOO_LARGE, "B * n_ticks = %lld work items", (long long)B * n_ticks);
   const int total = B * n_ticks;
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
   std::lock_guard<std::mutex> launch_lk(ctx->launch_mu);   // ordering test, launch and event record are one critical section
   if (int rc = slot_claim(ctx, ctx->guard_order, st, "tick / run")) return rc;
-  // hand-over inside one XCD (default) or through one device-wide queue (WG_RUN_QUEUE=global: A/B tests)
-  bool xcd_mode = true;
-  if (const char *e = getenv("WG_RUN_QUEUE")) xcd_mode = e[0] != 'g';
-  int cap = 1;
-  while (cap < 2 * B) cap <<= 1;                   // ring slots per XCD: a gait is in at most one ring, at most once
-  {
-    const size_t need = xcd_mode ? sizeof(wg_xrun_ctl) + (size_t)kXcds * cap * 8 + (size_t)B * 4
-                                 : sizeof(wg_run_queue) + (size_t)(total + B) * 4;
-    if (int rc = ctx->run_buf.reserve(need)) return rc;
-  }
+  const bool xcd_mode = run_queue_xcd();
+  const int cap = run_ring_cap(B);
+  if (int rc = ctx->run_buf.reserve(xcd_mode ? run_buf_bytes(B) : sizeof(wg_run_queue) + (size_t)(total + B) * 4)) return rc;
   wg_run_queue *q = static_cast<wg_run_queue *>(ctx->run_buf.p);
   int *ring = reinterpret_cast<int *>(q + 1), *done = ring + total;
   wg_xrun_ctl *xctl = static_cast<wg_xrun_ctl *>(ctx->run_buf.p);
@@ -1013,67 +949,50 @@ int wg_mpc_run_sched_dev_ctx(wg_ctx_t *ctx, int B, wg_gait_state_t *states, int 
     hipLaunchKernelGGL(wg_xrun_init_kernel, dim3((items + 255) / 256), dim3(256), 0, st, B, xctl, xrings, cap, xdone);
   } else
     hipLaunchKernelGGL(wg_run_queue_init_kernel, dim3((total + 255) / 256), dim3(256), 0, st, B, total, q, ring, done);
-  const size_t qlb = tick_ql_bytes(ctx->model);
-  const int view = tick_view(ctx->model);
-  size_t lds = tick_lds_for(ctx->model, view);
-  if (const char *pad = getenv("WG_TICK_LDS_PAD")) lds += (size_t)atoi(pad);   // experiments: lower the residency
-  if (lds > 64 * 1024) {
-    HIP_TRY(hipFuncSetAttribute(WG_KERNEL_BY_VIEW(wg_mpc_run_kernel, view), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIP_TRY(hipFuncSetAttribute(WG_KERNEL_BY_VIEW(wg_mpc_run_xcd_kernel, view), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  }
-  // as many blocks as the device keeps resident: LDS granules (1280 B, 128 per CU), at most 8 waves of 256 registers per CU
-  int per_cu = 128 / (int)((lds + 1279) / 1280);
-  const int max_waves = 4 * tick_waves_per_simd(view);   // what the kernel's register budget admits per CU
-  if (per_cu > max_waves) per_cu = max_waves;
-  if (per_cu < 1) per_cu = 1;
-  int grid = ctx->num_cu * per_cu;
+  const TickPlan plan(ctx->model);
+  if (int rc = plan.raise_lds(WG_KERNEL_BY_VIEW(wg_mpc_run_kernel, plan.view))) return rc;
+  if (int rc = plan.raise_lds(WG_KERNEL_BY_VIEW(wg_mpc_run_xcd_kernel, plan.view))) return rc;
+  // as many blocks as the device keeps resident: LDS granules, and the waves the kernel's register budget admits per CU
+  int grid = ctx->num_cu * plan.per_cu();
   if (grid > B) grid = B;
-  const int ecap = tick_elem_cap_arg(ctx->model, view);
   double *zs = nullptr;
-  const size_t zslot = tick_z_slot_doubles(ctx->model, view);
-  if (tick_z_global(view) || tick16_ext(view)) {
-    if (int rc = ctx->tick_z.reserve((size_t)grid * zslot * 8)) return rc;
-    zs = static_cast<double *>(ctx->tick_z.p);
-  }
+  if (int rc = plan.reserve_slots(ctx, grid, &zs)) return rc;
   int keep_k = 0;                                    // a wave keeps a gait that is behind its XCD's mean progress (see the kernel)
   if (const char *e = getenv("WG_RUN_KEEP")) keep_k = (e[0] == 'o' || e[0] == '-') ? -1 : atoi(e);
   else if (B <= grid) keep_k = -1;                   // a wave per gait: nothing waits, the launch takes what its slowest gait takes
   if (xcd_mode)
-    WG_LAUNCH_BY_VIEW(wg_mpc_run_xcd_kernel, view, grid, lds, st, B, n_ticks, ctx->model_dev, ctx->tables_dev, states, outs, diag, advance_calls,
-                      xctl, xrings, cap, xdone, (unsigned)qlb, zs, (unsigned)zslot, vref_sched, period, ecap, keep_k);
+    WG_LAUNCH_BY_VIEW(wg_mpc_run_xcd_kernel, plan.view, grid, plan.launch_lds, st, B, n_ticks, ctx->model_dev, ctx->tables_dev, states, outs, diag,
+                      advance_calls, xctl, xrings, cap, xdone, (unsigned)plan.qlb, zs, (unsigned)plan.zslot, vref_sched, period, plan.ecap, keep_k);
   else
-    WG_LAUNCH_BY_VIEW(wg_mpc_run_kernel, view, grid, lds, st, B, n_ticks, ctx->model_dev, ctx->tables_dev, states, outs, diag, advance_calls, q,
-                      ring, done, (unsigned)qlb, zs, (unsigned)zslot, ecap);
+    WG_LAUNCH_BY_VIEW(wg_mpc_run_kernel, plan.view, grid, plan.launch_lds, st, B, n_ticks, ctx->model_dev, ctx->tables_dev, states, outs, diag,
+                      advance_calls, q, ring, done, (unsigned)plan.qlb, zs, (unsigned)plan.zslot, plan.ecap);
   HIP_TRY(hipGetLastError());
   return slot_mark(ctx->guard_order, st);
 }
 
 int wg_mpc_tick_batch_ctx(wg_ctx_t *ctx, int B, wg_gait_state_t *states, wg_tick_out_t *outs, int *diag, int advance_calls, int *hist, int hist_cap, int *hist_len) {
-  if (int rc = use_ctx(ctx)) return rc;
-  if (!ctx->model_set) return fail(WG_ERR_BAD_ARG, "wg_mpc_configure() has not been called on this context");
-  if (B < 0 || !states) return fail(WG_ERR_BAD_ARG, "bad arguments");
+  if (int rc = tick_check(ctx, B, states)) return rc;
   if (B == 0) return WG_OK;
   std::lock_guard<std::mutex> lk(ctx->mu);
+  HostScope hs(ctx);
   const size_t sB = (size_t)B;
   if (int rc = ctx->tick_state.reserve(sB * sizeof(wg_gait_state_t))) return rc;
   if (outs) if (int rc = ctx->tick_out.reserve(sB * sizeof(wg_tick_out_t))) return rc;
-  const size_t aux_bytes = sB * 6 * 4 + (hist ? sB * hist_cap * 4 + sB * 4 : 0);
-  if (int rc = ctx->tick_aux.reserve(aux_bytes)) return rc;
-  WG_H2D(ctx->tick_state.p, states, sB * sizeof(wg_gait_state_t));
-  int *d_diag = static_cast<int *>(ctx->tick_aux.p);
-  int *d_hist = hist ? d_diag + sB * 6 : nullptr;
-  int *d_hlen = hist ? d_hist + sB * hist_cap : nullptr;
-  WG_ZERO(ctx->tick_aux.p, aux_bytes);
-  int rc = wg_mpc_tick_batch_dev_ctx(ctx, B, static_cast<wg_gait_state_t *>(ctx->tick_state.p),
-                                 outs ? static_cast<wg_tick_out_t *>(ctx->tick_out.p) : nullptr, d_diag, advance_calls,
-                                 d_hist, hist_cap, d_hlen, ctx->host_stream);
-  if (rc) return rc;
-  WG_D2H(states, ctx->tick_state.p, sB * sizeof(wg_gait_state_t));
-  if (outs) WG_D2H(outs, ctx->tick_out.p, sB * sizeof(wg_tick_out_t));
-  if (diag) WG_D2H(diag, d_diag, sB * 6 * 4);
+  Arena aux(ctx->tick_aux);
+  const auto s_diag = aux.take<int>(sB * 6), s_hist = aux.take<int>(hist ? sB * hist_cap : 0), s_hlen = aux.take<int>(hist ? sB : 0);
+  if (int rc = aux.reserve()) return rc;
+  wg_gait_state_t *d_states = static_cast<wg_gait_state_t *>(ctx->tick_state.p);
+  wg_tick_out_t *d_outs = outs ? static_cast<wg_tick_out_t *>(ctx->tick_out.p) : nullptr;
+  WG_H2D(d_states, states, sB * sizeof(wg_gait_state_t));
+  WG_ZERO(ctx->tick_aux.p, aux.size);
+  if (int rc = wg_mpc_tick_batch_dev_ctx(ctx, B, d_states, d_outs, aux(s_diag), advance_calls, aux(s_hist), hist_cap, aux(s_hlen), hs.stream()))
+    return rc;
+  WG_D2H(states, d_states, sB * sizeof(wg_gait_state_t));
+  if (outs) WG_D2H(outs, d_outs, sB * sizeof(wg_tick_out_t));
+  if (diag) WG_D2H(diag, aux(s_diag), s_diag.bytes());
   if (hist) {
-    WG_D2H(hist, d_hist, sB * hist_cap * 4);
-    WG_D2H(hist_len, d_hlen, sB * 4);
+    WG_D2H(hist, aux(s_hist), s_hist.bytes());
+    WG_D2H(hist_len, aux(s_hlen), s_hlen.bytes());
   }
   WG_HOST_WAIT();
   return WG_OK;
@@ -1093,30 +1012,16 @@ int wg_mpc_set_velref_dev_ctx(wg_ctx_t *ctx, int B, wg_gait_state_t *states, con
 
 // ---- PLDP / OptCholesky back-end -----------------------------------------------------------------------------------
 
-template <bool kALds>                                      // A's place known at compile time (see wg_ql_dense_kernel)
-__global__ void __launch_bounds__(64)
-wg_pldp_kernel(int B, int mcap, const wg::PldpModel *__restrict__ model, const int *__restrict__ m,
-               const double *__restrict__ D, const double *__restrict__ A, const double *__restrict__ b,
-               const double *__restrict__ zmpref, const double *__restrict__ xkyk, const int *__restrict__ similar,
-               const int *__restrict__ n_removed, const int *__restrict__ starting, int max_iter,
-               wg_pldp_state_t *states, double *X, int *ret, int *n_iter, int *active, int *n_active) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char pldp_lds[];
-  const wg::PldpModel &M = *model;
-  const int n = 2 * M.N;
-  const size_t aslot = (size_t)(mcap + 1) * n;
-  const int p = blockIdx.x;                        // one problem per block (grid == B)
-  if (p < B) {
-    int mp = m[p];
-    if (mp < 0 || mp > mcap) {                      // refuse rather than index out of the slot
-      if (threadIdx.x == 0) { ret[p] = WG_PLDP_BAD_INPUT; if (n_iter) n_iter[p] = 0; if (n_active) n_active[p] = 0; }
-      return;
-    }
-    wg::pldp_problem<kALds>(M, pldp_lds, mcap, mp, D + (size_t)p * n, A + p * aslot, b + (size_t)p * mcap,
-                     zmpref + (size_t)p * n, xkyk + (size_t)p * 6, similar + (size_t)p * mcap, n_removed[p], starting[p],
-                     max_iter, states + p, X + (size_t)p * n, ret + p, n_iter ? n_iter + p : nullptr,
-                     active ? active + (size_t)p * mcap : nullptr, n_active ? n_active + p : nullptr);
-  }
+namespace {
+int pldp_check(wg_ctx *ctx, int B, int mcap, const int *m, const double *D, const double *A, const double *b, const double *zmpref, const double *xkyk, const int *similar, const int *n_removed, const int *starting, const wg_pldp_state_t *states, const double *X, const int *ret) {
+  if (int rc = use_ctx(ctx)) return rc;
+  if (!ctx->pldp_N) return fail(WG_ERR_BAD_ARG, "wg_pldp_configure() has not been called on this context");
+  if (B < 0 || mcap < 1 || mcap > WG_PLDP_MMAX) return fail(WG_ERR_BAD_ARG, "need 1 <= mcap <= %d", WG_PLDP_MMAX);
+  if (!m || !D || !A || !b || !zmpref || !xkyk || !similar || !n_removed || !starting || !states || !X || !ret)
+    return fail(WG_ERR_BAD_ARG, "null argument");
+  return WG_OK;
 }
+}  // namespace
 
 extern "C" {
 
@@ -1143,6 +1048,7 @@ int wg_pldp_configure_ctx(wg_ctx_t *ctx, int N, const double *iPu, const double 
     }
   if (!ctx->pldp_dev) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ctx->pldp_dev), sizeof(wg::PldpModel)));
   if (int rc = ctx_wait_own(ctx)) return rc;             // a solve of the previous model may still be reading it
+  HostScope hs(ctx);
   WG_H2D(ctx->pldp_dev, &host, sizeof host);
   WG_HOST_WAIT();
   ctx->pldp_N = N;
@@ -1150,77 +1056,56 @@ int wg_pldp_configure_ctx(wg_ctx_t *ctx, int N, const double *iPu, const double 
 }
 
 int wg_pldp_solve_batch_dev_ctx(wg_ctx_t *ctx, int B, int mcap, const int *m, const double *D, const double *A, const double *b, const double *zmpref, const double *xkyk, const int *similar, const int *n_removed, const int *starting, int max_iter, wg_pldp_state_t *states, double *X, int *ret, int *n_iter, int *active, int *n_active, void *hip_stream) {
-  if (int rc = use_ctx(ctx)) return rc;
-  if (!ctx->pldp_N) return fail(WG_ERR_BAD_ARG, "wg_pldp_configure() has not been called on this context");
-  if (B < 0 || mcap < 1 || mcap > WG_PLDP_MMAX) return fail(WG_ERR_BAD_ARG, "need 1 <= mcap <= %d", WG_PLDP_MMAX);
-  if (!m || !D || !A || !b || !zmpref || !xkyk || !similar || !n_removed || !starting || !states || !X || !ret)
-    return fail(WG_ERR_BAD_ARG, "null argument");
+  if (int rc = pldp_check(ctx, B, mcap, m, D, A, b, zmpref, xkyk, similar, n_removed, starting, states, X, ret)) return rc;
   if (B == 0) return WG_OK;
   // like the dense QP kernel: A in LDS only while that does not cost a resident problem (8 per CU is the useful maximum)
   size_t lds = wg::PldpLds::bytes(mcap);
   const size_t lds_noa = wg::PldpLds::bytes(mcap, WG_PLDP_ACTIVE_CAP, false, false);
-  auto per_cu = [](size_t l) { const size_t k = (160 * 1024) / (l ? l : 1); return k > 8 ? (size_t)8 : k; };
-  int a_in_lds = per_cu(lds_noa) > per_cu(lds) ? 0 : 1;
-  if (const char *e = getenv("WG_PLDP_A_IN_LDS")) a_in_lds = atoi(e) != 0;   // tests force either path
+  const bool a_in_lds = env_flag("WG_PLDP_A_IN_LDS", per_cu_160k(lds_noa, 8) <= per_cu_160k(lds, 8));   // tests force either path
   if (!a_in_lds) lds = lds_noa;
-  if (lds > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute(a_in_lds ? reinterpret_cast<const void *>(wg_pldp_kernel<true>)
-                                         : reinterpret_cast<const void *>(wg_pldp_kernel<false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int grid = B;
-  if (a_in_lds)
-    hipLaunchKernelGGL(wg_pldp_kernel<true>, dim3(grid), dim3(64), lds, reinterpret_cast<hipStream_t>(hip_stream), B, mcap,
-                       ctx->pldp_dev, m, D, A, b, zmpref, xkyk, similar, n_removed, starting, max_iter, states, X, ret, n_iter,
-                       active, n_active);
-  else
-    hipLaunchKernelGGL(wg_pldp_kernel<false>, dim3(grid), dim3(64), lds, reinterpret_cast<hipStream_t>(hip_stream), B, mcap,
-                       ctx->pldp_dev, m, D, A, b, zmpref, xkyk, similar, n_removed, starting, max_iter, states, X, ret, n_iter,
-                       active, n_active);
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  const auto kern = a_in_lds ? wg_pldp_kernel<true> : wg_pldp_kernel<false>;     // A's place is a template argument
+  if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kern, dim3(B), dim3(64), lds, st, B, mcap, ctx->pldp_dev, m, D, A, b, zmpref, xkyk, similar, n_removed, starting, max_iter,
+                     states, X, ret, n_iter, active, n_active);
   HIP_TRY(hipGetLastError());
   std::lock_guard<std::mutex> launch_lk(ctx->launch_mu);
-  return slot_mark(ctx->aux_order, reinterpret_cast<hipStream_t>(hip_stream));
+  return slot_mark(ctx->aux_order, st);
 }
 
 int wg_pldp_solve_batch_ctx(wg_ctx_t *ctx, int B, int mcap, const int *m, const double *D, const double *A, const double *b, const double *zmpref, const double *xkyk, const int *similar, const int *n_removed, const int *starting, int max_iter, wg_pldp_state_t *states, double *X, int *ret, int *n_iter, int *active, int *n_active) {
-  if (int rc = use_ctx(ctx)) return rc;
-  if (!ctx->pldp_N) return fail(WG_ERR_BAD_ARG, "wg_pldp_configure() has not been called on this context");
-  if (B < 0 || mcap < 1 || mcap > WG_PLDP_MMAX) return fail(WG_ERR_BAD_ARG, "need 1 <= mcap <= %d", WG_PLDP_MMAX);
-  if (!m || !D || !A || !b || !zmpref || !xkyk || !similar || !n_removed || !starting || !states || !X || !ret)
-    return fail(WG_ERR_BAD_ARG, "null argument");
+  if (int rc = pldp_check(ctx, B, mcap, m, D, A, b, zmpref, xkyk, similar, n_removed, starting, states, X, ret)) return rc;
   if (B == 0) return WG_OK;
   std::lock_guard<std::mutex> lk(ctx->mu);
+  HostScope hs(ctx);
   const size_t sB = (size_t)B, n = 2 * (size_t)ctx->pldp_N;
-  const size_t aslot = (size_t)(mcap + 1) * n;
-  // one arena: doubles first, then the state structs (8-byte aligned), then ints
-  const size_t nd = sB * (n /*D*/ + aslot + mcap /*b*/ + n /*zmpref*/ + 6 + n /*X*/);
-  const size_t ni = sB * (1 /*m*/ + mcap /*similar*/ + 1 + 1 /*n_removed starting*/ + 1 + 1 /*ret n_iter*/ + mcap + 1 /*active n_active*/);
-  const size_t bytes = nd * 8 + sB * sizeof(wg_pldp_state_t) + ni * 4;
-  if (int rc = ctx->pldp_buf.reserve(bytes)) return rc;
-  double *dD = static_cast<double *>(ctx->pldp_buf.p), *dA = dD + sB * n, *db = dA + sB * aslot, *dz = db + sB * mcap,
-         *dx = dz + sB * n, *dX = dx + sB * 6;
-  wg_pldp_state_t *dst = reinterpret_cast<wg_pldp_state_t *>(dX + sB * n);
-  int *dm = reinterpret_cast<int *>(dst + sB), *dsim = dm + sB, *dnr = dsim + sB * mcap, *dstart = dnr + sB,
-      *dret = dstart + sB, *dit = dret + sB, *dact = dit + sB, *dnact = dact + sB * mcap;
-  WG_H2D(dD, D, sB * n * 8);
-  WG_H2D(dA, A, sB * aslot * 8);
-  WG_H2D(db, b, sB * mcap * 8);
-  WG_H2D(dz, zmpref, sB * n * 8);
-  WG_H2D(dx, xkyk, sB * 6 * 8);
-  WG_H2D(dst, states, sB * sizeof(wg_pldp_state_t));
-  WG_H2D(dm, m, sB * 4);
-  WG_H2D(dsim, similar, sB * mcap * 4);
-  WG_H2D(dnr, n_removed, sB * 4);
-  WG_H2D(dstart, starting, sB * 4);
-  WG_ZERO(dret, sB * (3 + mcap) * 4);
-  int rc = wg_pldp_solve_batch_dev_ctx(ctx, B, mcap, dm, dD, dA, db, dz, dx, dsim, dnr, dstart, max_iter, dst, dX, dret, dit, dact,
-                                   dnact, ctx->host_stream);
-  if (rc) return rc;
-  WG_D2H(states, dst, sB * sizeof(wg_pldp_state_t));
-  WG_D2H(X, dX, sB * n * 8);
-  WG_D2H(ret, dret, sB * 4);
-  if (n_iter) WG_D2H(n_iter, dit, sB * 4);
-  if (active) WG_D2H(active, dact, sB * mcap * 4);
-  if (n_active) WG_D2H(n_active, dnact, sB * 4);
+  Arena a(ctx->pldp_buf);
+  const auto sD = a.take<double>(sB * n), sA = a.take<double>(sB * (mcap + 1) * n), sb = a.take<double>(sB * mcap), sz = a.take<double>(sB * n),
+             sx = a.take<double>(sB * 6), sX = a.take<double>(sB * n);
+  const auto sst = a.take<wg_pldp_state_t>(sB);
+  const auto sm = a.take<int>(sB), ssim = a.take<int>(sB * mcap), snr = a.take<int>(sB), sstart = a.take<int>(sB);
+  const auto sret = a.take<int>(sB), sit = a.take<int>(sB), sact = a.take<int>(sB * mcap), snact = a.take<int>(sB);   // the outputs: last, zeroed
+  if (int rc = a.reserve()) return rc;
+  WG_H2D(a(sD), D, sD.bytes());
+  WG_H2D(a(sA), A, sA.bytes());
+  WG_H2D(a(sb), b, sb.bytes());
+  WG_H2D(a(sz), zmpref, sz.bytes());
+  WG_H2D(a(sx), xkyk, sx.bytes());
+  WG_H2D(a(sst), states, sst.bytes());
+  WG_H2D(a(sm), m, sm.bytes());
+  WG_H2D(a(ssim), similar, ssim.bytes());
+  WG_H2D(a(snr), n_removed, snr.bytes());
+  WG_H2D(a(sstart), starting, sstart.bytes());
+  WG_ZERO(a(sret), a.size - sret.off);
+  if (int rc = wg_pldp_solve_batch_dev_ctx(ctx, B, mcap, a(sm), a(sD), a(sA), a(sb), a(sz), a(sx), a(ssim), a(snr), a(sstart), max_iter, a(sst), a(sX),
+                                           a(sret), a(sit), a(sact), a(snact), hs.stream()))
+    return rc;
+  WG_D2H(states, a(sst), sst.bytes());
+  WG_D2H(X, a(sX), sX.bytes());
+  WG_D2H(ret, a(sret), sret.bytes());
+  if (n_iter) WG_D2H(n_iter, a(sit), sit.bytes());
+  if (active) WG_D2H(active, a(sact), sact.bytes());
+  if (n_active) WG_D2H(n_active, a(snact), snact.bytes());
   WG_HOST_WAIT();
   return WG_OK;
 }
@@ -1229,36 +1114,16 @@ int wg_pldp_solve_batch_ctx(wg_ctx_t *ctx, int B, int mcap, const int *m, const 
 
 // ---- Dimitrov-2008 tick around PLDP ------------------------------------------------------------------------------------
 
-__global__ void __launch_bounds__(64)
-wg_dimitrov_tick_kernel(int B, const wg::DimitrovConst *__restrict__ K, const wg_zmp_polytope_t *__restrict__ polys,
-                        wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int max_iter) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char dim_lds[];
-  const int N = K->N;
-  const int g = blockIdx.x;                       // one gait per block (grid == B), like the Herdt tick
-  // (a longest-solve-first start order as in the QL back-ends below was measured here and gave nothing: 5.19 against 5.20 M
-  // ticks/s -- PLDP's four iterations per tick leave nothing to order)
-  if (g < B) (void)wg::dimitrov_tick(*K, dim_lds, polys + (size_t)g * N, states + g, outs ? outs + g : nullptr, max_iter);
-}
-
-// modes QLD / QLDANDLQ: the same tick with the in-wave ql0002 as its back-end (wg_dimitrov_device.hpp, dimitrov_qld_tick)
-template <bool kLQ>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
-wg_dimitrov_qld_tick_kernel(int B, const wg::DimitrovConst *__restrict__ K, const wg_zmp_polytope_t *__restrict__ polys,
-                            wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, const int *__restrict__ order,
-                            int *__restrict__ iters_out) {
-  extern __shared__ __attribute__((aligned(16))) double dimq_lds[];
-  const int N = K->N;
-  const int g = order ? wg::uni(order[blockIdx.x]) : (int)blockIdx.x;     // longest-solve-first by the previous tick (scheduling only)
-  if (g < B) {
-    const int it = wg::dimitrov_qld_tick<kLQ>(*K, dimq_lds, polys + (size_t)g * N, states + g, outs ? outs + g : nullptr);
-    if (iters_out && (threadIdx.x & 63) == 0) iters_out[g] = it;
-  }
-}
-
 namespace {
 inline size_t dimitrov_lds_bytes() {
   return wg::PldpLds::bytes(WG_PLDP_MMAX, wg::kDimitrovActiveCap, true) + (4 * 2 * WG_PLDP_N + 8) * 8 +
          ((WG_PLDP_N + 1) * 4 + 15) / 16 * 16;
+}
+int dimitrov_check(wg_ctx *ctx, int B, const wg_zmp_polytope_t *polys, const wg_dimitrov_state_t *states) {
+  if (int rc = use_ctx(ctx)) return rc;
+  if (!ctx->dim_set) return fail(WG_ERR_BAD_ARG, "wg_dimitrov_configure() has not been called on this context");
+  if (B < 0 || !polys || !states) return fail(WG_ERR_BAD_ARG, "bad arguments");
+  return WG_OK;
 }
 }  // namespace
 
@@ -1286,6 +1151,7 @@ int wg_dimitrov_configure_ctx(wg_ctx_t *ctx, const wg_dimitrov_model_t *model) {
       return fail(WG_ERR_BAD_ARG, "the LQ factor or the inverse of Pu does not exist for this model");
     if (!ctx->dim_dev) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ctx->dim_dev), sizeof(wg::DimitrovConst)));
     if (int rc = ctx_wait_own(ctx)) return rc;           // a tick of the previous model may still be reading the constants
+    HostScope hs(ctx);
     WG_H2D(ctx->dim_dev, &(*ctx->dim_host), sizeof (*ctx->dim_host));
     WG_HOST_WAIT();
     ctx->dim_set = true;
@@ -1319,39 +1185,21 @@ int wg_dimitrov_get_qld_constants_ctx(wg_ctx_t *ctx, double *Q, double *OptB, do
 }
 
 int wg_dimitrov_tick_batch_dev_ctx(wg_ctx_t *ctx, int B, const wg_zmp_polytope_t *polys, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int max_iter, void *hip_stream) {
-  if (int rc = use_ctx(ctx)) return rc;
-  if (!ctx->dim_set) return fail(WG_ERR_BAD_ARG, "wg_dimitrov_configure() has not been called on this context");
-  if (B < 0 || !polys || !states) return fail(WG_ERR_BAD_ARG, "bad arguments");
+  if (int rc = dimitrov_check(ctx, B, polys, states)) return rc;
   if (B == 0) return WG_OK;
   hipStream_t stq = reinterpret_cast<hipStream_t>(hip_stream);
   std::lock_guard<std::mutex> launch_lk(ctx->launch_mu);
-  // more gaits than resident waves: longest-solve-first by the previous tick on the same state array (scheduling only)
-  int *order = nullptr, *iters_out = nullptr;
-  auto lpt_setup = [&](size_t lds_bytes, size_t wave_cap) -> int {
-    size_t per_cu = 128 / ((lds_bytes + 1279) / 1280);
-    if (per_cu > wave_cap) per_cu = wave_cap;
-    if (per_cu < 1) per_cu = 1;
-    // the order lives in a buffer of the context: not while another stream's launch of this context may still be reading it
-    bool lpt = (size_t)B > (size_t)ctx->num_cu * per_cu && !slot_pending_elsewhere(ctx->aux_order, stq);
-    if (const char *e = getenv("WG_QL_LPT")) lpt = lpt && atoi(e) != 0;
-    if (!lpt) return WG_OK;
-    const bool known = ctx->dlpt_key == states && ctx->dlpt_B == B && ctx->dlpt_buf.p;
-    if (int rc = ctx->dlpt_buf.reserve((size_t)B * 2 * sizeof(int))) return rc;
-    iters_out = static_cast<int *>(ctx->dlpt_buf.p);
-    if (known) {
-      order = iters_out + B;
-      hipLaunchKernelGGL(wg_lpt_order_kernel, dim3(1), dim3(1024), 0, stq, B, iters_out, order);
-    }
-    ctx->dlpt_key = states; ctx->dlpt_B = B;
-    return WG_OK;
-  };
-  if ((*ctx->dim_host).solver != WG_DIMITROV_PLDP) {
+  const int solver = ctx->dim_host->solver;
+  if (solver != WG_DIMITROV_PLDP) {                      // modes QLD / QLDANDLQ: the in-wave ql0002 as the back-end
     const size_t ldsq = wg::dimitrov_qld_lds_bytes();
-    if (int rc = lpt_setup(ldsq, 8)) return rc;            // eight gaits per CU (256 registers: two waves per SIMD)
-    if ((*ctx->dim_host).solver == WG_DIMITROV_QLDANDLQ)
-      hipLaunchKernelGGL(wg_dimitrov_qld_tick_kernel<true>, dim3(B), dim3(64), ldsq, stq, B, ctx->dim_dev, polys, states, outs, order, iters_out);
-    else
-      hipLaunchKernelGGL(wg_dimitrov_qld_tick_kernel<false>, dim3(B), dim3(64), ldsq, stq, B, ctx->dim_dev, polys, states, outs, order, iters_out);
+    // more gaits than resident waves (eight per CU: 256 registers, two waves per SIMD): longest-solve-first by the previous tick
+    // on the same state array (scheduling only).  The order lives in a buffer of the context: not while another stream's launch
+    // of this context may still be reading it
+    int *order = nullptr, *iters_out = nullptr;
+    if ((size_t)B > (size_t)ctx->num_cu * per_cu_granules(ldsq, 8) && !slot_pending_elsewhere(ctx->aux_order, stq) && env_flag("WG_QL_LPT", true))
+      if (int rc = lpt_prepare(ctx->dim_lpt, states, B, stq, &order, &iters_out)) return rc;
+    const auto kern = solver == WG_DIMITROV_QLDANDLQ ? wg_dimitrov_qld_tick_kernel<true> : wg_dimitrov_qld_tick_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3(B), dim3(64), ldsq, stq, B, ctx->dim_dev, polys, states, outs, order, iters_out);
     HIP_TRY(hipGetLastError());
     return slot_mark(ctx->aux_order, stq);
   }
@@ -1366,26 +1214,22 @@ int wg_dimitrov_tick_batch_dev_ctx(wg_ctx_t *ctx, int B, const wg_zmp_polytope_t
 }
 
 int wg_dimitrov_tick_batch_ctx(wg_ctx_t *ctx, int B, const wg_zmp_polytope_t *polys, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int max_iter) {
-  if (int rc = use_ctx(ctx)) return rc;
-  if (!ctx->dim_set) return fail(WG_ERR_BAD_ARG, "wg_dimitrov_configure() has not been called on this context");
-  if (B < 0 || !polys || !states) return fail(WG_ERR_BAD_ARG, "bad arguments");
+  if (int rc = dimitrov_check(ctx, B, polys, states)) return rc;
   if (B == 0) return WG_OK;
   std::lock_guard<std::mutex> lk(ctx->mu);
-  const size_t sB = (size_t)B, N = (size_t)(*ctx->dim_host).N;
-  const size_t pb = sB * N * sizeof(wg_zmp_polytope_t), sb = sB * sizeof(wg_dimitrov_state_t),
-               ob = outs ? sB * sizeof(wg_dimitrov_out_t) : 0;
-  if (int rc = ctx->dim_buf.reserve(pb + sb + ob)) return rc;
-  unsigned char *base = static_cast<unsigned char *>(ctx->dim_buf.p);
-  wg_zmp_polytope_t *dp = reinterpret_cast<wg_zmp_polytope_t *>(base);
-  wg_dimitrov_state_t *ds = reinterpret_cast<wg_dimitrov_state_t *>(base + pb);
-  wg_dimitrov_out_t *dout = outs ? reinterpret_cast<wg_dimitrov_out_t *>(base + pb + sb) : nullptr;
-  WG_H2D(dp, polys, pb);
-  WG_H2D(ds, states, sb);
-  if (dout) WG_ZERO(dout, ob);
-  int rc = wg_dimitrov_tick_batch_dev_ctx(ctx, B, dp, ds, dout, max_iter, ctx->host_stream);
-  if (rc) return rc;
-  WG_D2H(states, ds, sb);
-  if (dout) WG_D2H(outs, dout, ob);
+  HostScope hs(ctx);
+  const size_t sB = (size_t)B;
+  Arena a(ctx->dim_buf);
+  const auto sp = a.take<wg_zmp_polytope_t>(sB * (size_t)ctx->dim_host->N);
+  const auto ss = a.take<wg_dimitrov_state_t>(sB);
+  const auto so = a.take<wg_dimitrov_out_t>(outs ? sB : 0);
+  if (int rc = a.reserve()) return rc;
+  WG_H2D(a(sp), polys, sp.bytes());
+  WG_H2D(a(ss), states, ss.bytes());
+  if (outs) WG_ZERO(a(so), so.bytes());
+  if (int rc = wg_dimitrov_tick_batch_dev_ctx(ctx, B, a(sp), a(ss), a(so), max_iter, hs.stream())) return rc;
+  WG_D2H(states, a(ss), ss.bytes());
+  if (outs) WG_D2H(outs, a(so), so.bytes());
   WG_HOST_WAIT();
   return WG_OK;
 }
@@ -1393,6 +1237,22 @@ int wg_dimitrov_tick_batch_ctx(wg_ctx_t *ctx, int B, const wg_zmp_polytope_t *po
 }  // extern "C"
 
 // ---- Kajita stage-1 preview control -------------------------------------------------------------------------------------
+
+namespace {
+int preview_check(wg_ctx *ctx, int B, int L, const double *zmp_x, const double *zmp_y, const double *state) {
+  if (int rc = use_ctx(ctx)) return rc;
+  if (!ctx->prev_set) return fail(WG_ERR_BAD_ARG, "wg_preview_configure() has not been called on this context");
+  if (B < 0 || L < 0 || !zmp_x || !zmp_y || !state) return fail(WG_ERR_BAD_ARG, "bad arguments");
+  return WG_OK;
+}
+// the split-chain kernel's instantiations: T steps of the window per lane, eight lanes per gait-axis; [1]: the window is a whole
+// number of T (no tail test)
+constexpr int kSplitK = 8;
+typedef void (*SplitKernel)(int, int, wg::PreviewConst, const double *, const double *, const double *, double *, double *, double *, int);
+#define WG_SPLIT(T) {T, wg::wg_preview_split_kernel<T, kSplitK, true>, wg::wg_preview_split_kernel<T, kSplitK, false>}
+const struct { int T; SplitKernel full, part; } kSplitKernels[] = {WG_SPLIT(16), WG_SPLIT(24), WG_SPLIT(32), WG_SPLIT(40), WG_SPLIT(48)};
+#undef WG_SPLIT
+}  // namespace
 
 extern "C" {
 
@@ -1404,6 +1264,7 @@ int wg_preview_configure_ctx(wg_ctx_t *ctx, const wg_preview_gains_t *gains, con
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (!ctx->prev_F) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ctx->prev_F), sizeof(double) * WG_PREVIEW_NL_MAX));
   if (int rc = ctx_wait_own(ctx)) return rc;             // a run with the previous window may still be reading the gains
+  HostScope hs(ctx);
   WG_H2D(ctx->prev_F, F, sizeof(double) * gains->nl);
   WG_HOST_WAIT();
   const double T = gains->T;                                   // PreviewControl.cpp:203-214
@@ -1419,9 +1280,7 @@ int wg_preview_configure_ctx(wg_ctx_t *ctx, const wg_preview_gains_t *gains, con
 int wg_preview_window_ctx(wg_ctx_t *ctx) { return (ctx && ctx->prev_set) ? ctx->prev.nl : 0; }
 
 int wg_preview_run_batch_dev_ctx(wg_ctx_t *ctx, int B, int L, const double *zmp_x_tm, const double *zmp_y_tm, double *state, double *com_tm, double *zmp2_tm, int simulation, void *hip_stream) {
-  if (int rc = use_ctx(ctx)) return rc;
-  if (!ctx->prev_set) return fail(WG_ERR_BAD_ARG, "wg_preview_configure() has not been called on this context");
-  if (B < 0 || L < 0 || !zmp_x_tm || !zmp_y_tm || !state) return fail(WG_ERR_BAD_ARG, "bad arguments");
+  if (int rc = preview_check(ctx, B, L, zmp_x_tm, zmp_y_tm, state)) return rc;
   if (B == 0 || L == 0) return WG_OK;
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
   const char *force = getenv("WG_PREVIEW_KERNEL");            // "l2" / "ring" / "split": tests hold each to the oracle
@@ -1431,34 +1290,16 @@ int wg_preview_run_batch_dev_ctx(wg_ctx_t *ctx, int B, int L, const double *zmp_
   const bool ring = force ? force[0] == 'r' : (L >= 8 && (long long)B * 2 <= (long long)ctx->num_cu * 64 * 2);
   // The split-chain kernel (eight lanes per gait-axis, nothing re-read) covers the standard window sizes and wins at every
   // batch size measured; other windows, and runs too short to repay filling its rings, use the kernels below.
-  constexpr int kSplitK = 8;
-  int splitT = 0;                                              // smallest instantiated T with K T >= nl
-  for (int t : {16, 24, 32, 40, 48})
-    if (!splitT && kSplitK * t >= ctx->prev.nl) splitT = t;
+  SplitKernel split_kern = nullptr;                            // smallest instantiated T with K T >= nl
+  int splitT = 0;
+  for (const auto &s : kSplitKernels)
+    if (!splitT && kSplitK * s.T >= ctx->prev.nl) { splitT = s.T; split_kern = ctx->prev.nl % s.T == 0 ? s.full : s.part; }
   const bool can_split = splitT != 0 && ctx->prev.nl >= 64;
   const bool split = force ? (force[0] == 's' && can_split) : (can_split && L >= 4);
   if (split) {
     const int per_wave = 64 / kSplitK;
-    const dim3 grid((B + per_wave - 1) / per_wave, 2);
-    const size_t lds = (size_t)splitT * 64 * 8;
-    const bool full = ctx->prev.nl % splitT == 0;
-#define WG_SPLIT_LAUNCH(TT)                                                                                              \
-    do {                                                                                                                 \
-      if (full)                                                                                                          \
-        hipLaunchKernelGGL((wg::wg_preview_split_kernel<TT, kSplitK, true>), grid, dim3(64), lds, st, B, L, ctx->prev,      \
-                           ctx->prev_F, zmp_x_tm, zmp_y_tm, state, com_tm, zmp2_tm, simulation);                            \
-      else                                                                                                               \
-        hipLaunchKernelGGL((wg::wg_preview_split_kernel<TT, kSplitK, false>), grid, dim3(64), lds, st, B, L, ctx->prev,     \
-                           ctx->prev_F, zmp_x_tm, zmp_y_tm, state, com_tm, zmp2_tm, simulation);                            \
-    } while (0)
-    switch (splitT) {
-      case 16: WG_SPLIT_LAUNCH(16); break;
-      case 24: WG_SPLIT_LAUNCH(24); break;
-      case 32: WG_SPLIT_LAUNCH(32); break;
-      case 40: WG_SPLIT_LAUNCH(40); break;
-      default: WG_SPLIT_LAUNCH(48); break;
-    }
-#undef WG_SPLIT_LAUNCH
+    hipLaunchKernelGGL(split_kern, dim3((B + per_wave - 1) / per_wave, 2), dim3(64), (size_t)splitT * 64 * 8, st, B, L, ctx->prev, ctx->prev_F,
+                       zmp_x_tm, zmp_y_tm, state, com_tm, zmp2_tm, simulation);
   } else if (ring) {
     int R = ctx->prev.nl < 288 ? ctx->prev.nl : 288;                 // 288 x 512 B = 144 KB of the CU's 160 KB
     if (R < 1) R = 1;
@@ -1479,39 +1320,37 @@ int wg_preview_run_batch_dev_ctx(wg_ctx_t *ctx, int B, int L, const double *zmp_
 }
 
 int wg_preview_run_batch_ctx(wg_ctx_t *ctx, int B, int L, const double *zmp_x, const double *zmp_y, double *state, double *com, double *zmp2, int simulation) {
-  if (int rc = use_ctx(ctx)) return rc;
-  if (!ctx->prev_set) return fail(WG_ERR_BAD_ARG, "wg_preview_configure() has not been called on this context");
-  if (B < 0 || L < 0 || !zmp_x || !zmp_y || !state) return fail(WG_ERR_BAD_ARG, "bad arguments");
+  if (int rc = preview_check(ctx, B, L, zmp_x, zmp_y, state)) return rc;
   if (B == 0 || L == 0) return WG_OK;
   std::lock_guard<std::mutex> lk(ctx->mu);
+  HostScope hs(ctx);
   const size_t sB = (size_t)B, sL = (size_t)L, Lz = sL + ctx->prev.nl - 1;
   // arena: gait-major staging (largest user: com, B x L x 6), time-major zx, zy, com, zmp2, state
-  const size_t stage = sB * (sL * 6 > Lz ? sL * 6 : Lz);
-  const size_t nd = stage + 2 * sB * Lz + sB * sL * 6 + sB * sL * 2 + sB * 8;
-  if (int rc = ctx->prev_buf.reserve(nd * 8)) return rc;
-  double *d_stage = static_cast<double *>(ctx->prev_buf.p), *d_zx = d_stage + stage, *d_zy = d_zx + sB * Lz,
-         *d_com = d_zy + sB * Lz, *d_z2 = d_com + sB * sL * 6, *d_st = d_z2 + sB * sL * 2;
+  Arena a(ctx->prev_buf);
+  const auto s_stage = a.take<double>(sB * (sL * 6 > Lz ? sL * 6 : Lz)), s_zx = a.take<double>(sB * Lz), s_zy = a.take<double>(sB * Lz),
+             s_com = a.take<double>(sB * sL * 6), s_z2 = a.take<double>(sB * sL * 2), s_st = a.take<double>(sB * 8);
+  if (int rc = a.reserve()) return rc;
+  double *d_stage = a(s_stage);
   auto transpose = [&](int rows, int cols, const double *in, double *out) {
-    hipLaunchKernelGGL(wg::wg_transpose_kernel, dim3((cols + 31) / 32, (rows + 31) / 32), dim3(32, 8), 0, ctx->host_stream, rows,
-                       cols, in, out);
+    hipLaunchKernelGGL(wg::wg_transpose_kernel, dim3((cols + 31) / 32, (rows + 31) / 32), dim3(32, 8), 0, hs.stream(), rows, cols, in, out);
   };
   // everything below is in order on the context's stream: the staging buffer is reused only behind the transpose that read it
-  WG_H2D(d_stage, zmp_x, sB * Lz * 8);
-  transpose(B, (int)Lz, d_stage, d_zx);
-  WG_H2D(d_stage, zmp_y, sB * Lz * 8);
-  transpose(B, (int)Lz, d_stage, d_zy);
-  WG_H2D(d_st, state, sB * 8 * 8);
-  int rc = wg_preview_run_batch_dev_ctx(ctx, B, L, d_zx, d_zy, d_st, com ? d_com : nullptr, zmp2 ? d_z2 : nullptr, simulation,
-                                    ctx->host_stream);
-  if (rc) return rc;
-  WG_D2H(state, d_st, sB * 8 * 8);
+  WG_H2D(d_stage, zmp_x, s_zx.bytes());
+  transpose(B, (int)Lz, d_stage, a(s_zx));
+  WG_H2D(d_stage, zmp_y, s_zy.bytes());
+  transpose(B, (int)Lz, d_stage, a(s_zy));
+  WG_H2D(a(s_st), state, s_st.bytes());
+  if (int rc = wg_preview_run_batch_dev_ctx(ctx, B, L, a(s_zx), a(s_zy), a(s_st), com ? a(s_com) : nullptr, zmp2 ? a(s_z2) : nullptr, simulation,
+                                            hs.stream()))
+    return rc;
+  WG_D2H(state, a(s_st), s_st.bytes());
   if (com) {                                                   // [L*6][B] -> [B][L*6]
-    transpose(L * 6, B, d_com, d_stage);
-    WG_D2H(com, d_stage, sB * sL * 6 * 8);
+    transpose(L * 6, B, a(s_com), d_stage);
+    WG_D2H(com, d_stage, s_com.bytes());
   }
   if (zmp2) {
-    transpose(L * 2, B, d_z2, d_stage);
-    WG_D2H(zmp2, d_stage, sB * sL * 2 * 8);
+    transpose(L * 2, B, a(s_z2), d_stage);
+    WG_D2H(zmp2, d_stage, s_z2.bytes());
   }
   HIP_TRY(hipGetLastError());
   WG_HOST_WAIT();
@@ -1522,34 +1361,39 @@ int wg_preview_run_batch_ctx(wg_ctx_t *ctx, int B, int L, const double *zmp_x, c
 
 // ---- invariant Hessian block on the matrix cores (fleets with per-gait models) -----------------------------------------
 
+namespace {
+int gramian_check(wg_ctx *ctx, int B, int N, const double *T, const double *h, const double *Qb) {
+  if (int rc = use_ctx(ctx)) return rc;
+  if (B < 0 || N < 1 || N > 32 || !T || !h || !Qb) return fail(WG_ERR_BAD_ARG, "need B >= 0, 1 <= N <= 32, non-null arrays");
+  return WG_OK;
+}
+}  // namespace
+
 extern "C" {
 
 int wg_gramian_batch_dev_ctx(wg_ctx_t *ctx, int B, int N, const double *T, const double *h, double alpha, double beta, double gamma, int precision, double *Qb, void *hip_stream) {
-  if (int rc = use_ctx(ctx)) return rc;
-  if (B < 0 || N < 1 || N > 32 || !T || !h || !Qb) return fail(WG_ERR_BAD_ARG, "need B >= 0, 1 <= N <= 32, non-null arrays");
+  if (int rc = gramian_check(ctx, B, N, T, h, Qb)) return rc;
   if (precision != WG_GRAMIAN_F64 && precision != WG_GRAMIAN_F32) return fail(WG_ERR_BAD_ARG, "unknown precision %d", precision);
   if (B == 0) return WG_OK;
-  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  if (precision == WG_GRAMIAN_F32)
-    hipLaunchKernelGGL(wg::wg_gramian_kernel<true>, dim3(B), dim3(64), 0, st, B, N, T, h, alpha, beta, gamma, Qb);
-  else
-    hipLaunchKernelGGL(wg::wg_gramian_kernel<false>, dim3(B), dim3(64), 0, st, B, N, T, h, alpha, beta, gamma, Qb);
+  const auto kern = precision == WG_GRAMIAN_F32 ? wg::wg_gramian_kernel<true> : wg::wg_gramian_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3(B), dim3(64), 0, reinterpret_cast<hipStream_t>(hip_stream), B, N, T, h, alpha, beta, gamma, Qb);
   HIP_TRY(hipGetLastError());
   return WG_OK;
 }
 
 int wg_gramian_batch_ctx(wg_ctx_t *ctx, int B, int N, const double *T, const double *h, double alpha, double beta, double gamma, int precision, double *Qb) {
-  if (int rc = use_ctx(ctx)) return rc;
-  if (B < 0 || N < 1 || N > 32 || !T || !h || !Qb) return fail(WG_ERR_BAD_ARG, "need B >= 0, 1 <= N <= 32, non-null arrays");
+  if (int rc = gramian_check(ctx, B, N, T, h, Qb)) return rc;
   if (B == 0) return WG_OK;
   std::lock_guard<std::mutex> lk(ctx->mu);
-  const size_t sB = (size_t)B, nq = sB * N * N;
-  if (int rc = ctx->gram_buf.reserve((2 * sB + nq) * 8)) return rc;
-  double *dT = static_cast<double *>(ctx->gram_buf.p), *dh = dT + sB, *dQ = dh + sB;
-  WG_H2D(dT, T, sB * 8);
-  WG_H2D(dh, h, sB * 8);
-  if (int rc = wg_gramian_batch_dev_ctx(ctx, B, N, dT, dh, alpha, beta, gamma, precision, dQ, ctx->host_stream)) return rc;
-  WG_D2H(Qb, dQ, nq * 8);
+  HostScope hs(ctx);
+  const size_t sB = (size_t)B;
+  Arena a(ctx->gram_buf);
+  const auto sT = a.take<double>(sB), sh = a.take<double>(sB), sQ = a.take<double>(sB * N * N);
+  if (int rc = a.reserve()) return rc;
+  WG_H2D(a(sT), T, sT.bytes());
+  WG_H2D(a(sh), h, sh.bytes());
+  if (int rc = wg_gramian_batch_dev_ctx(ctx, B, N, a(sT), a(sh), alpha, beta, gamma, precision, a(sQ), hs.stream())) return rc;
+  WG_D2H(Qb, a(sQ), sQ.bytes());
   WG_HOST_WAIT();
   return WG_OK;
 }
@@ -1577,6 +1421,15 @@ int zd_make_const(const wg_zmpdisc_model_t *model, wg::ZdConst *K) {
   for (int i = 0; i < n + 1; i++) sum += K->win[i];
   for (int i = 0; i < n + 1; i++) K->win[i] /= sum;
   for (int i = n + 1; i < WG_ZD_WIN_MAX; i++) K->win[i] = 0.0;
+  return WG_OK;
+}
+
+// what the three entry points check alike: the context, the model (-> K), the sizes; `ptrs_ok`: the arrays each of them requires
+int zd_check(wg_ctx *ctx, const wg_zmpdisc_model_t *model, wg::ZdConst *K, int B, int smax, int lcap, bool ptrs_ok, const char *what) {
+  if (int rc = use_ctx(ctx)) return rc;
+  if (int rc = zd_make_const(model, K)) return rc;
+  if (B < 0 || smax < 2 || smax > WG_ZMPDISC_MAX_STEPS || lcap < 1 || !ptrs_ok)
+    return fail(WG_ERR_BAD_ARG, "need B >= 0, 2 <= smax <= %d, lcap >= 1, non-null %s", WG_ZMPDISC_MAX_STEPS, what);
   return WG_OK;
 }
 
@@ -1613,11 +1466,8 @@ int wg_zmpdisc_length(const wg_zmpdisc_model_t *model, const wg_rel_step_t *step
 }
 
 int wg_zmpdisc_batch_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap, double *zmp_x_tm, double *zmp_y_tm, int *length, void *hip_stream) {
-  if (int rc = use_ctx(ctx)) return rc;
   wg::ZdConst K;
-  if (int rc = zd_make_const(model, &K)) return rc;
-  if (B < 0 || smax < 2 || smax > WG_ZMPDISC_MAX_STEPS || lcap < 1 || !steps || !n_steps || !init_feet || !zmp_x_tm || !zmp_y_tm)
-    return fail(WG_ERR_BAD_ARG, "need B >= 0, 2 <= smax <= %d, lcap >= 1, non-null arrays", WG_ZMPDISC_MAX_STEPS);
+  if (int rc = zd_check(ctx, model, &K, B, smax, lcap, steps && n_steps && init_feet && zmp_x_tm && zmp_y_tm, "arrays")) return rc;
   if (B == 0) return WG_OK;
   wg::ZdOut O;
   memset(&O, 0, sizeof O);
@@ -1627,11 +1477,8 @@ int wg_zmpdisc_batch_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_model_t *model, int
 }
 
 int wg_zmpdisc_full_batch_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream) {
-  if (int rc = use_ctx(ctx)) return rc;
   wg::ZdConst K;
-  if (int rc = zd_make_const(model, &K)) return rc;
-  if (B < 0 || smax < 2 || smax > WG_ZMPDISC_MAX_STEPS || lcap < 1 || !steps || !n_steps || !init_feet)
-    return fail(WG_ERR_BAD_ARG, "need B >= 0, 2 <= smax <= %d, lcap >= 1, non-null inputs", WG_ZMPDISC_MAX_STEPS);
+  if (int rc = zd_check(ctx, model, &K, B, smax, lcap, steps && n_steps && init_feet, "inputs")) return rc;
   if ((zmp_x_tm == nullptr) != (zmp_y_tm == nullptr)) return fail(WG_ERR_BAD_ARG, "zmp_x_tm and zmp_y_tm go together");
   if (B == 0) return WG_OK;
   wg::ZdOut O;
@@ -1641,42 +1488,36 @@ int wg_zmpdisc_full_batch_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_model_t *model
 }
 
 int wg_zmpdisc_batch_ctx(wg_ctx_t *ctx, const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap, double *zmp, double *zmp_theta, int *zmp_type, double *left, int *left_type, double *right, int *right_type, int *length) {
-  if (int rc = use_ctx(ctx)) return rc;
   wg::ZdConst K;
-  if (int rc = zd_make_const(model, &K)) return rc;
-  if (B < 0 || smax < 2 || smax > WG_ZMPDISC_MAX_STEPS || lcap < 1 || !steps || !n_steps || !init_feet || !length)
-    return fail(WG_ERR_BAD_ARG, "need B >= 0, 2 <= smax <= %d, lcap >= 1, non-null arrays", WG_ZMPDISC_MAX_STEPS);
+  if (int rc = zd_check(ctx, model, &K, B, smax, lcap, steps && n_steps && init_feet && length, "arrays")) return rc;
   if (B == 0) return WG_OK;
   std::lock_guard<std::mutex> lk(ctx->mu);
+  std::vector<double> hd;                                      // host staging of the time-major arrays (outlive the copies into them)
+  std::vector<int> hi;
+  HostScope hs(ctx);
   const size_t sB = (size_t)B, sL = (size_t)lcap, row = sB * sL;
-  // arena (8-byte units): steps | init_feet | zx zy ztheta | left right (6 rows each) | ints: n_steps length ztype ltype rtype
-  const size_t n_step_d = (sB * smax * sizeof(wg_rel_step_t) + 7) / 8;
-  const size_t nd = n_step_d + sB * 6 + 3 * row + 12 * row, ni = 2 * sB + 3 * row;
-  if (int rc = ctx->zd_buf.reserve(nd * 8 + ni * 4 + 64)) return rc;
-  double *d0 = static_cast<double *>(ctx->zd_buf.p);
-  wg_rel_step_t *d_steps = reinterpret_cast<wg_rel_step_t *>(d0);
-  double *d_feet = d0 + n_step_d, *d_zx = d_feet + sB * 6, *d_zy = d_zx + row, *d_zt = d_zy + row, *d_l = d_zt + row,
-         *d_r = d_l + 6 * row;
-  int *d_ns = reinterpret_cast<int *>(d_r + 6 * row), *d_len = d_ns + sB, *d_zty = d_len + sB, *d_lty = d_zty + row,
-      *d_rty = d_lty + row;
-  WG_H2D(d_steps, steps, sB * smax * sizeof(wg_rel_step_t));
-  WG_H2D(d_feet, init_feet, sB * 6 * 8);
-  WG_H2D(d_ns, n_steps, sB * 4);
+  Arena a(ctx->zd_buf);
+  const auto s_steps = a.take<wg_rel_step_t>(sB * smax);
+  const auto s_feet = a.take<double>(sB * 6), s_zx = a.take<double>(row), s_zy = a.take<double>(row), s_zt = a.take<double>(row),
+             s_l = a.take<double>(6 * row), s_r = a.take<double>(6 * row);
+  const auto s_ns = a.take<int>(sB), s_len = a.take<int>(sB), s_zty = a.take<int>(row), s_lty = a.take<int>(row), s_rty = a.take<int>(row);
+  if (int rc = a.reserve()) return rc;
+  WG_H2D(a(s_steps), steps, s_steps.bytes());
+  WG_H2D(a(s_feet), init_feet, s_feet.bytes());
+  WG_H2D(a(s_ns), n_steps, s_ns.bytes());
   wg::ZdOut O;
   memset(&O, 0, sizeof O);
-  if (zmp) { O.zx = d_zx; O.zy = d_zy; }
-  if (zmp_theta) O.ztheta = d_zt;
-  if (zmp_type) O.ztype = d_zty;
-  if (left) O.left = d_l;
-  if (left_type) O.ltype = d_lty;
-  if (right) O.right = d_r;
-  if (right_type) O.rtype = d_rty;
-  if (int rc = zd_launch(K, B, smax, d_steps, d_ns, d_feet, lcap, O, d_len, ctx->host_stream)) return rc;
-  WG_D2H(length, d_len, sB * 4);
+  if (zmp) { O.zx = a(s_zx); O.zy = a(s_zy); }
+  if (zmp_theta) O.ztheta = a(s_zt);
+  if (zmp_type) O.ztype = a(s_zty);
+  if (left) O.left = a(s_l);
+  if (left_type) O.ltype = a(s_lty);
+  if (right) O.right = a(s_r);
+  if (right_type) O.rtype = a(s_rty);
+  if (int rc = zd_launch(K, B, smax, a(s_steps), a(s_ns), a(s_feet), lcap, O, a(s_len), hs.stream())) return rc;
+  WG_D2H(length, a(s_len), s_len.bytes());
   WG_HOST_WAIT();
   // time-major device arrays -> the caller's gait-major arrays, samples below each gait's length only
-  std::vector<double> hd;
-  std::vector<int> hi;
   auto fetch_d = [&](const double *dev, int comps, double *dst, int dst_stride, int dst_off) -> int {
     hd.resize(row * comps);
     WG_D2H(hd.data(), dev, row * comps * 8);
@@ -1696,15 +1537,15 @@ int wg_zmpdisc_batch_ctx(wg_ctx_t *ctx, const wg_zmpdisc_model_t *model, int B, 
     return WG_OK;
   };
   if (zmp) {
-    if (int rc = fetch_d(d_zx, 1, zmp, 2, 0)) return rc;
-    if (int rc = fetch_d(d_zy, 1, zmp, 2, 1)) return rc;
+    if (int rc = fetch_d(a(s_zx), 1, zmp, 2, 0)) return rc;
+    if (int rc = fetch_d(a(s_zy), 1, zmp, 2, 1)) return rc;
   }
-  if (zmp_theta) if (int rc = fetch_d(d_zt, 1, zmp_theta, 1, 0)) return rc;
-  if (left) if (int rc = fetch_d(d_l, 6, left, 6, 0)) return rc;
-  if (right) if (int rc = fetch_d(d_r, 6, right, 6, 0)) return rc;
-  if (zmp_type) if (int rc = fetch_i(d_zty, zmp_type)) return rc;
-  if (left_type) if (int rc = fetch_i(d_lty, left_type)) return rc;
-  if (right_type) if (int rc = fetch_i(d_rty, right_type)) return rc;
+  if (zmp_theta) if (int rc = fetch_d(a(s_zt), 1, zmp_theta, 1, 0)) return rc;
+  if (left) if (int rc = fetch_d(a(s_l), 6, left, 6, 0)) return rc;
+  if (right) if (int rc = fetch_d(a(s_r), 6, right, 6, 0)) return rc;
+  if (zmp_type) if (int rc = fetch_i(a(s_zty), zmp_type)) return rc;
+  if (left_type) if (int rc = fetch_i(a(s_lty), left_type)) return rc;
+  if (right_type) if (int rc = fetch_i(a(s_rty), right_type)) return rc;
   return WG_OK;
 }
 
@@ -1713,194 +1554,45 @@ int wg_zmpdisc_batch_ctx(wg_ctx_t *ctx, const wg_zmpdisc_model_t *model, int B, 
 // ---- the same entry points on the process-wide default context -----------------------------------------------------
 extern "C" {
 
-int wg_qp_solve_batch_dev(int B, int nmax, int mmax, const int *n, const int *m, const int *me, const double *C, const double *d, const double *A, const double *b, const double *xl, const double *xu, double eps, double *x, double *u, int *ifail, int *n_iter, int *iact, int *nact, int *hist, int hist_cap, int *hist_len, void *hip_stream) {
-  wg_ctx *c = nullptr;
-  if (int rc = default_ctx(&c)) return rc;
-  return wg_qp_solve_batch_dev_ctx(c, B, nmax, mmax, n, m, me, C, d, A, b, xl, xu, eps, x, u, ifail, n_iter, iact, nact, hist, hist_cap, hist_len, hip_stream);
-}
-
-int wg_qp_solve_batch(int B, int nmax, int mmax, const int *n, const int *m, const int *me, const double *C, const double *d, const double *A, const double *b, const double *xl, const double *xu, double eps, double *x, double *u, int *ifail, int *n_iter, int *iact, int *nact, int *hist, int hist_cap, int *hist_len) {
-  wg_ctx *c = nullptr;
-  if (int rc = default_ctx(&c)) return rc;
-  return wg_qp_solve_batch_ctx(c, B, nmax, mmax, n, m, me, C, d, A, b, xl, xu, eps, x, u, ifail, n_iter, iact, nact, hist, hist_cap, hist_len);
-}
-
-int wg_set_overlap_strict(int on) {
-  wg_ctx *c = nullptr;
-  if (int rc = default_ctx(&c)) return rc;
-  return wg_set_overlap_strict_ctx(c, on);
-}
-
-long long wg_overlap_serialised(void) {
-  wg_ctx *c = nullptr;
-  if (default_ctx(&c)) return -1;
-  return wg_overlap_serialised_ctx(c);
-}
-
-int wg_mpc_configure(const wg_model_t *model) {
-  wg_ctx *c = nullptr;
-  if (int rc = default_ctx(&c)) return rc;
-  return wg_mpc_configure_ctx(c, model);
-}
-
-int wg_mpc_reserve(int max_gaits) {
-  wg_ctx *c = nullptr;
-  if (int rc = default_ctx(&c)) return rc;
-  return wg_mpc_reserve_ctx(c, max_gaits);
-}
-
+int wg_qp_solve_batch_dev(int B, int nmax, int mmax, const int *n, const int *m, const int *me, const double *C, const double *d, const double *A, const double *b, const double *xl, const double *xu, double eps, double *x, double *u, int *ifail, int *n_iter, int *iact, int *nact, int *hist, int hist_cap, int *hist_len, void *hip_stream) { return on_default(&wg_qp_solve_batch_dev_ctx, B, nmax, mmax, n, m, me, C, d, A, b, xl, xu, eps, x, u, ifail, n_iter, iact, nact, hist, hist_cap, hist_len, hip_stream); }
+int wg_qp_solve_batch(int B, int nmax, int mmax, const int *n, const int *m, const int *me, const double *C, const double *d, const double *A, const double *b, const double *xl, const double *xu, double eps, double *x, double *u, int *ifail, int *n_iter, int *iact, int *nact, int *hist, int hist_cap, int *hist_len) { return on_default(&wg_qp_solve_batch_ctx, B, nmax, mmax, n, m, me, C, d, A, b, xl, xu, eps, x, u, ifail, n_iter, iact, nact, hist, hist_cap, hist_len); }
+int wg_set_overlap_strict(int on) { return on_default(&wg_set_overlap_strict_ctx, on); }
+long long wg_overlap_serialised(void) { return on_default(&wg_overlap_serialised_ctx); }
+int wg_mpc_configure(const wg_model_t *model) { return on_default(&wg_mpc_configure_ctx, model); }
+int wg_mpc_reserve(int max_gaits) { return on_default(&wg_mpc_reserve_ctx, max_gaits); }
 size_t wg_mpc_tick_lds_bytes(void) {                 // a query: does not create the default context
   std::lock_guard<std::mutex> lk(g_default_mu);
   return wg_mpc_tick_lds_bytes_ctx(g_default);
 }
 
-int wg_mpc_tick_batch_dev(int B, wg_gait_state_t *states, wg_tick_out_t *outs, int *diag, int advance_calls, int *hist, int hist_cap, int *hist_len, void *hip_stream) {
-  wg_ctx *c = nullptr;
-  if (int rc = default_ctx(&c)) return rc;
-  return wg_mpc_tick_batch_dev_ctx(c, B, states, outs, diag, advance_calls, hist, hist_cap, hist_len, hip_stream);
-}
-
-int wg_mpc_run_sched_dev(int B, wg_gait_state_t *states, int n_ticks, int advance_calls, const double *vref_sched, int period, wg_tick_out_t *outs, int *diag, void *hip_stream) {
-  wg_ctx *c = nullptr;
-  if (int rc = default_ctx(&c)) return rc;
-  return wg_mpc_run_sched_dev_ctx(c, B, states, n_ticks, advance_calls, vref_sched, period, outs, diag, hip_stream);
-}
-
-int wg_mpc_run_batch_dev(int B, wg_gait_state_t *states, int n_ticks, int advance_calls, wg_tick_out_t *outs, int *diag, void *hip_stream) {
-  wg_ctx *c = nullptr;
-  if (int rc = default_ctx(&c)) return rc;
-  return wg_mpc_run_batch_dev_ctx(c, B, states, n_ticks, advance_calls, outs, diag, hip_stream);
-}
-
-int wg_mpc_tick_batch(int B, wg_gait_state_t *states, wg_tick_out_t *outs, int *diag, int advance_calls, int *hist, int hist_cap, int *hist_len) {
-  wg_ctx *c = nullptr;
-  if (int rc = default_ctx(&c)) return rc;
-  return wg_mpc_tick_batch_ctx(c, B, states, outs, diag, advance_calls, hist, hist_cap, hist_len);
-}
-
-int wg_mpc_set_velref_dev(int B, wg_gait_state_t *states, const double *vref, void *hip_stream) {
-  wg_ctx *c = nullptr;
-  if (int rc = default_ctx(&c)) return rc;
-  return wg_mpc_set_velref_dev_ctx(c, B, states, vref, hip_stream);
-}
-
-int wg_pldp_configure(int N, const double *iPu, const double *Px, const double *Pu) {
-  wg_ctx *c = nullptr;
-  if (int rc = default_ctx(&c)) return rc;
-  return wg_pldp_configure_ctx(c, N, iPu, Px, Pu);
-}
-
-int wg_pldp_solve_batch_dev(int B, int mcap, const int *m, const double *D, const double *A, const double *b, const double *zmpref, const double *xkyk, const int *similar, const int *n_removed, const int *starting, int max_iter, wg_pldp_state_t *states, double *X, int *ret, int *n_iter, int *active, int *n_active, void *hip_stream) {
-  wg_ctx *c = nullptr;
-  if (int rc = default_ctx(&c)) return rc;
-  return wg_pldp_solve_batch_dev_ctx(c, B, mcap, m, D, A, b, zmpref, xkyk, similar, n_removed, starting, max_iter, states, X, ret, n_iter, active, n_active, hip_stream);
-}
-
-int wg_pldp_solve_batch(int B, int mcap, const int *m, const double *D, const double *A, const double *b, const double *zmpref, const double *xkyk, const int *similar, const int *n_removed, const int *starting, int max_iter, wg_pldp_state_t *states, double *X, int *ret, int *n_iter, int *active, int *n_active) {
-  wg_ctx *c = nullptr;
-  if (int rc = default_ctx(&c)) return rc;
-  return wg_pldp_solve_batch_ctx(c, B, mcap, m, D, A, b, zmpref, xkyk, similar, n_removed, starting, max_iter, states, X, ret, n_iter, active, n_active);
-}
-
-int wg_dimitrov_configure(const wg_dimitrov_model_t *model) {
-  wg_ctx *c = nullptr;
-  if (int rc = default_ctx(&c)) return rc;
-  return wg_dimitrov_configure_ctx(c, model);
-}
-
-int wg_dimitrov_get_constants(double *iLQ, double *OptB, double *OptC, double *Pu, double *iPu, double *Px) {
-  wg_ctx *c = nullptr;
-  if (int rc = default_ctx(&c)) return rc;
-  return wg_dimitrov_get_constants_ctx(c, iLQ, OptB, OptC, Pu, iPu, Px);
-}
-
-int wg_dimitrov_get_qld_constants(double *Q, double *OptB, double *OptC, double *PuT) {
-  wg_ctx *c = nullptr;
-  if (int rc = default_ctx(&c)) return rc;
-  return wg_dimitrov_get_qld_constants_ctx(c, Q, OptB, OptC, PuT);
-}
-
-int wg_dimitrov_tick_batch_dev(int B, const wg_zmp_polytope_t *polys, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int max_iter, void *hip_stream) {
-  wg_ctx *c = nullptr;
-  if (int rc = default_ctx(&c)) return rc;
-  return wg_dimitrov_tick_batch_dev_ctx(c, B, polys, states, outs, max_iter, hip_stream);
-}
-
-int wg_dimitrov_tick_batch(int B, const wg_zmp_polytope_t *polys, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int max_iter) {
-  wg_ctx *c = nullptr;
-  if (int rc = default_ctx(&c)) return rc;
-  return wg_dimitrov_tick_batch_ctx(c, B, polys, states, outs, max_iter);
-}
-
-int wg_mpc_tick_pinned(wg_gait_state_t *state, wg_tick_out_t *out, int *diag, int advance_calls) {
-  wg_ctx *c = nullptr;
-  if (int rc = default_ctx(&c)) return rc;
-  return wg_mpc_tick_pinned_ctx(c, state, out, diag, advance_calls);
-}
-
-int wg_mpc_assemble_batch_dev(int B, const wg_gait_state_t *states, int advance_calls, int nmax, int mmax, double *C, double *d, double *A, double *b, double *xl, double *xu, int *n, int *m, void *hip_stream) {
-  wg_ctx *c = nullptr;
-  if (int rc = default_ctx(&c)) return rc;
-  return wg_mpc_assemble_batch_dev_ctx(c, B, states, advance_calls, nmax, mmax, C, d, A, b, xl, xu, n, m, hip_stream);
-}
-
-int wg_mpc_assemble_batch(int B, const wg_gait_state_t *states, int advance_calls, int nmax, int mmax, double *C, double *d, double *A, double *b, double *xl, double *xu, int *n, int *m) {
-  wg_ctx *c = nullptr;
-  if (int rc = default_ctx(&c)) return rc;
-  return wg_mpc_assemble_batch_ctx(c, B, states, advance_calls, nmax, mmax, C, d, A, b, xl, xu, n, m);
-}
-
-int wg_preview_configure(const wg_preview_gains_t *gains, const double *F) {
-  wg_ctx *c = nullptr;
-  if (int rc = default_ctx(&c)) return rc;
-  return wg_preview_configure_ctx(c, gains, F);
-}
-
+int wg_mpc_tick_batch_dev(int B, wg_gait_state_t *states, wg_tick_out_t *outs, int *diag, int advance_calls, int *hist, int hist_cap, int *hist_len, void *hip_stream) { return on_default(&wg_mpc_tick_batch_dev_ctx, B, states, outs, diag, advance_calls, hist, hist_cap, hist_len, hip_stream); }
+int wg_mpc_run_sched_dev(int B, wg_gait_state_t *states, int n_ticks, int advance_calls, const double *vref_sched, int period, wg_tick_out_t *outs, int *diag, void *hip_stream) { return on_default(&wg_mpc_run_sched_dev_ctx, B, states, n_ticks, advance_calls, vref_sched, period, outs, diag, hip_stream); }
+int wg_mpc_run_batch_dev(int B, wg_gait_state_t *states, int n_ticks, int advance_calls, wg_tick_out_t *outs, int *diag, void *hip_stream) { return on_default(&wg_mpc_run_batch_dev_ctx, B, states, n_ticks, advance_calls, outs, diag, hip_stream); }
+int wg_mpc_tick_batch(int B, wg_gait_state_t *states, wg_tick_out_t *outs, int *diag, int advance_calls, int *hist, int hist_cap, int *hist_len) { return on_default(&wg_mpc_tick_batch_ctx, B, states, outs, diag, advance_calls, hist, hist_cap, hist_len); }
+int wg_mpc_set_velref_dev(int B, wg_gait_state_t *states, const double *vref, void *hip_stream) { return on_default(&wg_mpc_set_velref_dev_ctx, B, states, vref, hip_stream); }
+int wg_pldp_configure(int N, const double *iPu, const double *Px, const double *Pu) { return on_default(&wg_pldp_configure_ctx, N, iPu, Px, Pu); }
+int wg_pldp_solve_batch_dev(int B, int mcap, const int *m, const double *D, const double *A, const double *b, const double *zmpref, const double *xkyk, const int *similar, const int *n_removed, const int *starting, int max_iter, wg_pldp_state_t *states, double *X, int *ret, int *n_iter, int *active, int *n_active, void *hip_stream) { return on_default(&wg_pldp_solve_batch_dev_ctx, B, mcap, m, D, A, b, zmpref, xkyk, similar, n_removed, starting, max_iter, states, X, ret, n_iter, active, n_active, hip_stream); }
+int wg_pldp_solve_batch(int B, int mcap, const int *m, const double *D, const double *A, const double *b, const double *zmpref, const double *xkyk, const int *similar, const int *n_removed, const int *starting, int max_iter, wg_pldp_state_t *states, double *X, int *ret, int *n_iter, int *active, int *n_active) { return on_default(&wg_pldp_solve_batch_ctx, B, mcap, m, D, A, b, zmpref, xkyk, similar, n_removed, starting, max_iter, states, X, ret, n_iter, active, n_active); }
+int wg_dimitrov_configure(const wg_dimitrov_model_t *model) { return on_default(&wg_dimitrov_configure_ctx, model); }
+int wg_dimitrov_get_constants(double *iLQ, double *OptB, double *OptC, double *Pu, double *iPu, double *Px) { return on_default(&wg_dimitrov_get_constants_ctx, iLQ, OptB, OptC, Pu, iPu, Px); }
+int wg_dimitrov_get_qld_constants(double *Q, double *OptB, double *OptC, double *PuT) { return on_default(&wg_dimitrov_get_qld_constants_ctx, Q, OptB, OptC, PuT); }
+int wg_dimitrov_tick_batch_dev(int B, const wg_zmp_polytope_t *polys, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int max_iter, void *hip_stream) { return on_default(&wg_dimitrov_tick_batch_dev_ctx, B, polys, states, outs, max_iter, hip_stream); }
+int wg_dimitrov_tick_batch(int B, const wg_zmp_polytope_t *polys, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int max_iter) { return on_default(&wg_dimitrov_tick_batch_ctx, B, polys, states, outs, max_iter); }
+int wg_mpc_tick_pinned(wg_gait_state_t *state, wg_tick_out_t *out, int *diag, int advance_calls) { return on_default(&wg_mpc_tick_pinned_ctx, state, out, diag, advance_calls); }
+int wg_mpc_assemble_batch_dev(int B, const wg_gait_state_t *states, int advance_calls, int nmax, int mmax, double *C, double *d, double *A, double *b, double *xl, double *xu, int *n, int *m, void *hip_stream) { return on_default(&wg_mpc_assemble_batch_dev_ctx, B, states, advance_calls, nmax, mmax, C, d, A, b, xl, xu, n, m, hip_stream); }
+int wg_mpc_assemble_batch(int B, const wg_gait_state_t *states, int advance_calls, int nmax, int mmax, double *C, double *d, double *A, double *b, double *xl, double *xu, int *n, int *m) { return on_default(&wg_mpc_assemble_batch_ctx, B, states, advance_calls, nmax, mmax, C, d, A, b, xl, xu, n, m); }
+int wg_preview_configure(const wg_preview_gains_t *gains, const double *F) { return on_default(&wg_preview_configure_ctx, gains, F); }
 int wg_preview_window(void) {                        // a query: does not create the default context
   std::lock_guard<std::mutex> lk(g_default_mu);
   return wg_preview_window_ctx(g_default);
 }
 
-int wg_preview_run_batch_dev(int B, int L, const double *zmp_x_tm, const double *zmp_y_tm, double *state, double *com_tm, double *zmp2_tm, int simulation, void *hip_stream) {
-  wg_ctx *c = nullptr;
-  if (int rc = default_ctx(&c)) return rc;
-  return wg_preview_run_batch_dev_ctx(c, B, L, zmp_x_tm, zmp_y_tm, state, com_tm, zmp2_tm, simulation, hip_stream);
-}
-
-int wg_preview_run_batch(int B, int L, const double *zmp_x, const double *zmp_y, double *state, double *com, double *zmp2, int simulation) {
-  wg_ctx *c = nullptr;
-  if (int rc = default_ctx(&c)) return rc;
-  return wg_preview_run_batch_ctx(c, B, L, zmp_x, zmp_y, state, com, zmp2, simulation);
-}
-
-int wg_gramian_batch_dev(int B, int N, const double *T, const double *h, double alpha, double beta, double gamma, int precision, double *Qb, void *hip_stream) {
-  wg_ctx *c = nullptr;
-  if (int rc = default_ctx(&c)) return rc;
-  return wg_gramian_batch_dev_ctx(c, B, N, T, h, alpha, beta, gamma, precision, Qb, hip_stream);
-}
-
-int wg_gramian_batch(int B, int N, const double *T, const double *h, double alpha, double beta, double gamma, int precision, double *Qb) {
-  wg_ctx *c = nullptr;
-  if (int rc = default_ctx(&c)) return rc;
-  return wg_gramian_batch_ctx(c, B, N, T, h, alpha, beta, gamma, precision, Qb);
-}
-
-int wg_zmpdisc_batch_dev(const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap, double *zmp_x_tm, double *zmp_y_tm, int *length, void *hip_stream) {
-  wg_ctx *c = nullptr;
-  if (int rc = default_ctx(&c)) return rc;
-  return wg_zmpdisc_batch_dev_ctx(c, model, B, smax, steps, n_steps, init_feet, lcap, zmp_x_tm, zmp_y_tm, length, hip_stream);
-}
-
-int wg_zmpdisc_full_batch_dev(const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream) {
-  wg_ctx *c = nullptr;
-  if (int rc = default_ctx(&c)) return rc;
-  return wg_zmpdisc_full_batch_dev_ctx(c, model, B, smax, steps, n_steps, init_feet, lcap, zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, left_type_tm, right_tm, right_type_tm, length, hip_stream);
-}
-
-int wg_zmpdisc_batch(const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap, double *zmp, double *zmp_theta, int *zmp_type, double *left, int *left_type, double *right, int *right_type, int *length) {
-  wg_ctx *c = nullptr;
-  if (int rc = default_ctx(&c)) return rc;
-  return wg_zmpdisc_batch_ctx(c, model, B, smax, steps, n_steps, init_feet, lcap, zmp, zmp_theta, zmp_type, left, left_type, right, right_type, length);
-}
+int wg_preview_run_batch_dev(int B, int L, const double *zmp_x_tm, const double *zmp_y_tm, double *state, double *com_tm, double *zmp2_tm, int simulation, void *hip_stream) { return on_default(&wg_preview_run_batch_dev_ctx, B, L, zmp_x_tm, zmp_y_tm, state, com_tm, zmp2_tm, simulation, hip_stream); }
+int wg_preview_run_batch(int B, int L, const double *zmp_x, const double *zmp_y, double *state, double *com, double *zmp2, int simulation) { return on_default(&wg_preview_run_batch_ctx, B, L, zmp_x, zmp_y, state, com, zmp2, simulation); }
+int wg_gramian_batch_dev(int B, int N, const double *T, const double *h, double alpha, double beta, double gamma, int precision, double *Qb, void *hip_stream) { return on_default(&wg_gramian_batch_dev_ctx, B, N, T, h, alpha, beta, gamma, precision, Qb, hip_stream); }
+int wg_gramian_batch(int B, int N, const double *T, const double *h, double alpha, double beta, double gamma, int precision, double *Qb) { return on_default(&wg_gramian_batch_ctx, B, N, T, h, alpha, beta, gamma, precision, Qb); }
+int wg_zmpdisc_batch_dev(const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap, double *zmp_x_tm, double *zmp_y_tm, int *length, void *hip_stream) { return on_default(&wg_zmpdisc_batch_dev_ctx, model, B, smax, steps, n_steps, init_feet, lcap, zmp_x_tm, zmp_y_tm, length, hip_stream); }
+int wg_zmpdisc_full_batch_dev(const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream) { return on_default(&wg_zmpdisc_full_batch_dev_ctx, model, B, smax, steps, n_steps, init_feet, lcap, zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, left_type_tm, right_tm, right_type_tm, length, hip_stream); }
+int wg_zmpdisc_batch(const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap, double *zmp, double *zmp_theta, int *zmp_type, double *left, int *left_type, double *right, int *right_type, int *length) { return on_default(&wg_zmpdisc_batch_ctx, model, B, smax, steps, n_steps, init_feet, lcap, zmp, zmp_theta, zmp_type, left, left_type, right, right_type, length); }
 
 }  // extern "C"

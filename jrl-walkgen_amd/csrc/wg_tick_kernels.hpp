@@ -1,7 +1,8 @@
 // wg_tick_kernels.hpp -- the __global__ kernels of the Herdt-2010 tick (one launch per tick, many ticks per launch through a
 // device-wide queue, many ticks per launch with the hand-over kept inside one XCD) and their small helpers.  Included by
-// wg_capi.hip, which launches them; a translation unit of its own can instantiate ONE of them (tools/one_kernel.sh: resource
-// usage and ISA of a single kernel in seconds instead of the whole library).
+// wg_capi.hip, which launches them and holds no kernel itself (the other back-ends' kernels: wg_ql_kernels.hpp,
+// wg_pldp_kernels.hpp, wg_dimitrov_kernels.hpp, and the preview / Gramian / ZMP headers); a translation unit of its own can
+// instantiate ONE of them (tools/one_kernel.sh: resource usage and ISA of a single kernel in seconds instead of the whole library).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,5 +1,6 @@
 """Where a kernel saves / restores the exec mask (lane-dependent branches), by source line and loop depth: each site costs a
 scalar save, a branch and a restore on the spot (~27 cycles measured on the back substitution's path).
+csrc/wg_capi.hip is the translation unit to compile; the source lines reported are in the kernel headers it includes.
 usage: hipcc ... -gline-tables-only -S --cuda-device-only -o /tmp/k.s csrc/wg_capi.hip; python tools/exec_sites.py /tmp/k.s <mangled-kernel-prefix> [min-depth]"""
 import re, sys, collections
 L = open(sys.argv[1]).read().split('\n')

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Register / spill audit of the kernels in csrc/wg_capi.hip, from the compiler's own output (no GPU needed).
+"""Register / spill audit of every kernel of the library, from the compiler's own output (no GPU needed): csrc/wg_capi.hip is the
+translation unit (host code only); the kernels are in the csrc/wg_*_kernels.hpp and wg_*_device.hpp headers it includes.
 
     python tools/isa_audit.py [--out profiles/round3_resource_usage.txt] [--isa /tmp/wg_capi.s]
 

@@ -38,7 +38,8 @@ for k in names:
     summ[k] = json.load(open(os.path.join(d, "summary.json")))
     log = os.path.join(d, "trace.log")
     if k in ("gramian", "config5", "elem") and os.path.exists(log):
-        keep = [ln for ln in open(log) if ("TFLOP" in ln or "ticks/s" in ln or "same" in ln or "run" in ln) and "amdgpu.ids" not in ln]
+        keep = [ln for ln in open(log) if ("TFLOP" in ln or "ticks/s" in ln or "same" in ln or "run" in ln) and "amdgpu.ids" not in ln
+                and "Opened result file" not in ln]         # the profiler's own log lines (paths of the box it ran on)
         open(os.path.join(ROOT, "profiles", f"{tag}_{k}_probe_output.txt"), "w").writelines(keep)
 
 
