@@ -389,7 +389,7 @@ void wg_shutdown(void) {
 
 #ifdef WG_PROFILE
 // diagnostic build only: read-and-reset the in-kernel phase timers (shader cycles)
-int wg_prof_read(unsigned long long *out48) {          // 48 counters (wg_ql_device.hpp, g_prof)
+int wg_prof_read(unsigned long long *out48) {          // 48 counters (wg_ql_view.hpp, g_prof)
   if (hipMemcpyFromSymbol(out48, HIP_SYMBOL(wg::g_prof), 48 * sizeof(unsigned long long)) != hipSuccess) return -1;
   unsigned long long z[48] = {0};
   if (hipMemcpyToSymbol(HIP_SYMBOL(wg::g_prof), z, sizeof z) != hipSuccess) return -1;
@@ -541,8 +541,8 @@ inline bool tick_compact(const wg_model_t &m) {
 }
 // element view (-1: any horizon; 32: BASELINE config 5's horizon as a compile-time constant -- same LDS bytes, same slot, a fixed
 // layout): Z in a per-block slot of global memory instead of LDS (decided at compile time: mpc_tick<-1>, mpc_tick<32>)
-inline bool tick_elem(int view) { return view == -1 || view == 32 || view == 33; }   // 33: N = 32 with Z in registers
-inline int tick_waves_per_simd(int view) { return view == 33 ? WG_ZR_WPS : (tick_elem(view) ? WG_TICK32_WPE : WG_TICK_WPE_MAX); }
+inline bool tick_elem(int view) { return view == -1 || view == 32; }
+inline int tick_waves_per_simd(int view) { return tick_elem(view) ? WG_TICK32_WPE : WG_TICK_WPE_MAX; }
 inline bool tick_z_global(int view) { return tick_elem(view); }
 // compact view (N = 16): wa, b and the border block Gv in a per-block slot of global memory (decided at compile time: mpc_tick<16>)
 inline bool tick16_ext(int view) { return view == 16; }
@@ -561,7 +561,6 @@ inline size_t tick_lds_with_cap(const wg_model_t &m, int view, int r_cols) {
   // element view, short horizons: the pre-solve overlay does not fit over R; it gets its own bytes behind the tick's arrays
   if (view == -1 && wg::TickLds::elem_overlay_apart(m.N, sizeof(wg_gait_state_t)))
     tick = ((tick + 15) & ~(size_t)15) + wg::TickLds::elem_overlay_need(m.N, sizeof(wg_gait_state_t));
-  if (view == 33) tick += ((size_t)wg::kZrTile * wg::kZrTs + (size_t)wg::kZrTail * tick_max_n(m)) * 8;   // Z^T a tile + Z's tail rows (behind R)
   return ql + tick;
 }
 // Element view: how many columns of R the LDS holds (0: all of them).  R is the operand that decides the residency at N = 32
@@ -606,7 +605,7 @@ inline size_t tick_z_slot_doubles(const wg_model_t &m, int view) {
   if (view == 16) return (n + 2 * mm) + n * wg::kGvLd;       // wa | b | Gv
   // element view: Z | wa | b | Gv | rowA | rowB | rowK | gd | d | wd | wx | R in full (mpc_tick<-1>)
   // (the fixed N = 32 view keeps Z with leading dimension n: whole cache lines per column; slots are multiples of 64 bytes)
-  const size_t zd = (view == 32 || view == 33) ? n * n : n * (n | 1);
+  const size_t zd = view == 32 ? n * n : n * (n | 1);
   return (zd + (n + 2 * mm) + n * wg::kGvLdElem + 2 * mm + (mm + 1) / 2 + 2 + 4 * n + (n * (n + 1) / 2 + n) + 7) & ~(size_t)7;
 }
 inline size_t tick_lds_for(const wg_model_t &m, int view) { return tick_lds_with_cap(m, view, tick_elem_cap(m, view)); }
@@ -622,9 +621,6 @@ inline int tick_view(const wg_model_t &m) {
   // kernel there too (tests run both: same bytes)
   if (m.N == 32) {
     if (env_flag("WG_TICK_ELEM_GENERIC", false)) return -1;
-#ifdef WG_WITH_REGZ
-    if (env_flag("WG_TICK_REGZ", false)) return 33;      // experiment builds: Z in registers, four gaits per CU (mpc_tick<33>)
-#endif
     return 32;
   }
   return -1;

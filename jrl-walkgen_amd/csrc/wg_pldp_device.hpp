@@ -92,7 +92,7 @@ struct PldpLds {
 __device__ __forceinline__ int ltri(int i, int j) { return i * (i + 1) / 2 + j; }   // packed lower, j <= i
 
 // arg-min over the wave: smaller v wins, equal v -> smaller idx.  idx < 0 = no candidate (then idx stays < 0).
-// On the DPP path like wave_argmax_first (wg_ql_device.hpp); candidates must be finite.
+// On the DPP path like wave_argmax_first (wg_wave.hpp); candidates must be finite.
 __device__ __forceinline__ void wave_argmin_first(double &v, int &idx) {
   double nv = -v;                                   // exact, order-reversing; -(+-0) compares equal either way
   wave_argmax_first(nv, idx);

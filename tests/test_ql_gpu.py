@@ -161,7 +161,7 @@ def test_non_finite_iterates_end_the_way_the_reference_ends_them():
     round 5).  The reference does not notice: its running comparisons never skip a NaN, it adds and drops until maxit = 40 (m + n)
     and returns ifail = 1 with a NaN solution; the oracle follows it bit for bit.  A wave arg-max does not pick what those serial
     comparisons pick once NaNs compete -- the solver used to "converge" there with ifail = 0 -- so it takes NaN-exact forms of
-    the two selections when the iterate is not a number (wg_ql_device.hpp: scan_nan_exact, pick_drop_serial_reference).  Held here: ifail, the NaN solution's bits, the iteration count and the whole add / drop history
+    the two selections when the iterate is not a number (wg_ql_phases.hpp: scan_nan_exact, pick_drop_serial_reference).  Held here: ifail, the NaN solution's bits, the iteration count and the whole add / drop history
     (8 877 events) against the oracle, alone and inside a batch of ordinary QPs, through the fixed-size and the generic kernel."""
     wg = _wg()
     bad = [qpgen.herdt_like(np.random.default_rng(61000 + s), 16, 2) for s in (72, 1732, 3422, 3928, 4265, 5716, 5797)]
@@ -345,7 +345,7 @@ def test_two_host_threads_share_one_context():
 @pytest.mark.parametrize("log2_scale", [0, 380, 450, -380, -450])
 def test_sweep_norm_range_guard(log2_scale):
     """The sweep's norm chain takes a shorter instruction sequence when every operand is zero or within [2^-400, 2^400]
-    (wg_ql_device.hpp, givens_norm_fast / sweep_range_ok) and the reference-shaped one otherwise.  Constraint rows scaled by
+    (wg_ql_phases.hpp, givens_norm_fast / sweep_range_ok) and the reference-shaped one otherwise.  Constraint rows scaled by
     2^k put the operands (Z^T a) on either side of the guard, close to it and far from it; n > 64 takes the generic sweep."""
     wg = _wg()
     qps = []

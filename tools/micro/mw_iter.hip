@@ -2,7 +2,7 @@
 // workgroup of W waves per gait, Z (72 x 72, leading dimension 73: conflict-free column walks) in LDS, three gaits per CU
 // (53 KB of LDS each), the lane-parallel phases split over the waves, the two serial chains on waves 0 and 1 (side by side
 // when W >= 2), a workgroup barrier at every hand-over.  Same instruction shapes as the solver's phases -- the chain of
-// rotation norms IS the solver's (wg::givens_norm_fast from csrc/wg_ql_device.hpp), the rest restates their loops on LDS
+// rotation norms IS the solver's (wg::givens_norm_fast from csrc/wg_ql_phases.hpp), the rest restates their loops on LDS
 // operands -- on synthetic, well-conditioned data (rotations are exact Givens pairs, so Z stays orthogonal-ish for any
 // number of iterations).  What it leaves out makes it an OPTIMISTIC bound: the step products Z s, the drops (a second sweep
 // with rotations of R), the residual refresh, the tick around the solve (the 45 % "everything else" row of

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Per-phase attribution of the N = 16 tick's instruction streams and wait cycles (run on the GPU box via gpurun).
-# Builds lib/libwg_mpc_xr<k>.so = -DWG_REPEAT_PHASE=k (csrc/wg_ql_device.hpp: the idempotent phase k of every active-set
-# iteration is executed twice; k = 0: no phase repeated, same compiler barriers) must exist:
+# Builds lib/libwg_mpc_xr<k>.so = -DWG_REPEAT_PHASE=k (WG_REP of csrc/wg_ql_view.hpp, placed in ql_solve: the idempotent phase k
+# of every active-set iteration is executed twice; k = 0: no phase repeated, same compiler barriers) must exist:
 #   for k in 0 1 2 3 4 5 6 7 8 9 11; do make -C jrl-walkgen_amd lib/libwg_mpc_xr$k.so EXTRA=-DWG_REPEAT_PHASE=$k; done
 # (8: factor(), 9: the tick's QP assembly, 11: gradient + residuals of the residual refresh -- idempotent as well)
 # For each build: the multi-tick kernel's rate (no profiler), then ONE rocprofv3 --pmc pass of eight SQ counters.

@@ -178,7 +178,7 @@ from (`tools/csrc_hash.py`); `tests/test_docs_numbers.py` fails when that is not
 | `{tag}_fetchcal_*` | `tools/micro/fetchcal` (plain, then `tools/pmc_traffic.sh`) | FETCH_SIZE / WRITE_SIZE against known byte counts: 4 / 8 / 16 B per lane coalesced, the Z^T a column walk and the sweep's row walk of a 72 x 73 slot |
 | `{tag}_ticko_*` | the same with `--outs-on` | the timed launch stores every gait-tick's `wg_tick_out_t`: WRITE_SIZE of the `outs_on` leg (`current_tick_pmc.json` -> `run_kernel_outs`) |
 | `{tag}_b1_*` | `python3 tools/probe_b1.py` | one robot, one wave alone on a CU: the counters behind DESIGN 4.4 / 4.0 ("one robot") (`current_tick_pmc.json` -> `one_robot_kernel`) |
-| `round4_regz_*` | `bash tools/regz_probe.sh` (experiment builds, `-DWG_WITH_REGZ`; round 4) | the "Z on chip" experiment at N = 32 (docs/HISTORY.md 3.2): parity, rate at four and eight gaits per CU, all counters of the four-per-CU build |
+| `round4_regz_*` | `bash tools/regz_probe.sh` (experiment builds, `-DWG_WITH_REGZ`; round 4) | the "Z on chip" experiment at N = 32 (docs/HISTORY.md 3.2): parity, rate at four and eight gaits per CU, all counters of the four-per-CU build.  The experiment's code and its probe script were last present at commit `80f27a6` |
 | `round5_mw_barrier.txt`, `round5_mw_iter.txt` | `tools/micro/barrier`, `tools/micro/mw_iter` (round 5) | the multi-wave "Z in LDS" layout at N = 32 measured instead of built (DESIGN 4.3): cost of an `s_barrier` hand-over at three workgroups per CU; cycles per active-set iteration of a W-wave workgroup, per phase, against what the shipped kernel needs |
 | `{tag}_phase_attribution.txt` | `bash tools/phase_attribution.sh` + `python tools/phase_attribution.py`, then the timer table of `{tag}_tick_phase_timers.txt` | per-phase counters of the N = 16 run kernel (phases executed twice, differences against the plain build) and the shader-clock split of everything the counters cannot repeat |
 | `{tag}_phase_attribution_n32.txt` | `ATTR_DIR=attr32 PN=32 PB=8192 PT=50 PR=2 bash tools/phase_attribution.sh` + `... python tools/phase_attribution.py` | the same counter attribution for the N = 32 kernel `wg_mpc_run_xcd_kernel<32>` at the benchmark's residency (back substitution 12.1 %, norm chain 11.6 %, scan 11.0 %, Z^T a 10.4 %) |
