@@ -179,7 +179,10 @@ typedef struct wg_model {
   double hip_vmax;          /* |upperVelocityBound|                            :68   */
   double hip_amax;          /* 0.1                                             :71   */
   double feet_cross_max;    /* 5 deg in rad                                    :73   */
-  double step_period;       /* 0.8   SupportFSM, ZMPVelocityReferencedQP.cpp:76     */
+  double step_period;       /* 0.8   SupportFSM, ZMPVelocityReferencedQP.cpp:76.  The tick holds at most four previewed
+                             * steps: with k = ceil((step_period - T/10 - 1e-6) / T) previewed instants between two support
+                             * changes, wg_mpc_configure refuses (WG_ERR_BAD_ARG) a model with 1 + (N - 2) / k > 4
+                             * (T = 0.1: step_period <= 0.71 at N = 32, <= 0.31 at N = 16) */
   double ds_period;         /* 1e9                                             :77   */
   double dsss_period;       /* 0.8                                             :78   */
   double t_single;          /* 0.7   rigid-body-system.cpp:60                        */

@@ -1,6 +1,7 @@
 // wg_capi.hip -- C ABI (include/wg_mpc.h) over the HIP kernels: host code only (the kernels are in the headers).  gfx950 only.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -535,6 +536,18 @@ inline int tick_max_m(const wg_model_t &m) { return 1 + 4 * m.N + 5 * tick_smax(
 //    0  dense    G and A as LDS matrices: on request (WG_TICK_DENSE=1, while they fit the CU's 160 KiB) and for
 //                wg_mpc_assemble_batch, which writes the QP out
 // WG_TICK_VIEW=element sends N == 16 through the element view as well (tests).
+// The most steps a horizon can preview, from SupportFSM::set_support_state as wg_tick_device.hpp states it: a previewed support
+// changes at the first instant pi with time + 1e-6 + pi*T >= time_limit, and every change sets time_limit = time + pi*T +
+// step_period - T/10, so two changes are k = ceil((step_period - T/10 - 1e-6) / T) instants apart.  A change at pi = 1 is not
+// counted (`if (pi != 1) ++step_number`) and one at pi = 0 belongs to the current support: the earliest counted change is at
+// pi = 2, the most a horizon of N instants holds is 1 + floor((N - 2) / k).  The 1e-9 keeps k from being rounded UP past the
+// FSM's own figure (a smaller k only refuses more).  The kernels hold wg::kSMax steps: wg_mpc_configure refuses models beyond.
+inline int tick_max_prw_steps(const wg_model_t &m) {
+  const double q = (m.step_period - m.T / 10.0 - 1e-6) / m.T - 1e-9;
+  if (!(q == q)) return m.N;                                       // NaN: refuse
+  const int k = q <= 1.0 ? 1 : (q >= (double)m.N ? m.N : (int)ceil(q));
+  return 1 + (m.N - 2) / k;
+}
 inline bool tick_compact(const wg_model_t &m) {
   const char *v = getenv("WG_TICK_VIEW");
   return m.N == 16 && m.N * m.T <= 2.0 * m.step_period + 1e-12 && !env_flag("WG_TICK_DENSE", false) && !(v && *v);
@@ -712,6 +725,9 @@ int wg_mpc_configure_ctx(wg_ctx_t *ctx, const wg_model_t *model) {
   if (model->N < 2 || model->N > wg::kNMaxH) return fail(WG_ERR_BAD_ARG, "N=%d outside [2,%d]", model->N, wg::kNMaxH);
   if ((int)(model->T / model->Tctrl) != WG_SAMPLES_PER_TICK)
     return fail(WG_ERR_BAD_ARG, "T/Tctrl must be %d", WG_SAMPLES_PER_TICK);
+  if (tick_max_prw_steps(*model) > wg::kSMax)
+    return fail(WG_ERR_BAD_ARG, "step_period=%g: a horizon of N=%d instants of T=%g previews up to %d steps, the tick holds %d",
+                model->step_period, model->N, model->T, tick_max_prw_steps(*model), wg::kSMax);
   const size_t lds = TickPlan(*model).lds;
   if (lds > 160 * 1024) return fail(WG_ERR_TOO_LARGE, "tick needs %zu B of LDS > 160 KiB", lds);
   std::vector<double> qb;                              // Q_b from the matrix cores, when the model asks for it
@@ -746,7 +762,7 @@ int wg_mpc_configure_ctx(wg_ctx_t *ctx, const wg_model_t *model) {
 }
 
 size_t wg_mpc_tick_lds_bytes_for(const wg_model_t *model) {   // host arithmetic only: no device needed
-  if (!model || model->N < 2 || model->N > wg::kNMaxH) return 0;
+  if (!model || model->N < 2 || model->N > wg::kNMaxH || tick_max_prw_steps(*model) > wg::kSMax) return 0;
   return TickPlan(*model).lds;
 }
 

@@ -627,7 +627,8 @@ __device__ __forceinline__ TickDiag mpc_tick(const wg_model_t &m, const TickTabl
       }
     }
     int ns = L.sup[N].step_number;
-    constexpr int kSCap = (NH == 16) ? 2 : kSMax;   // compact kernel: N*T <= 2*step_period is checked at configure time
+    constexpr int kSCap = (NH == 16) ? 2 : kSMax;   // both bounds are checked at configure time: N*T <= 2*step_period for the
+                                                    // compact kernel, tick_max_prw_steps(model) <= kSMax for every model
     if (ns > kSCap) ns = kSCap;                     // cannot happen; keeps every index in range
 #ifdef WG_PROFILE
     tkb = clock64();

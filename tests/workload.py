@@ -174,23 +174,26 @@ def bench_plan_run(ctx, model, B, t_end, timed_from, bench, n_seg=None, vel_scal
     return [raw[k * sz:(k + 1) * sz] for k in range(B)], diag.cpu().numpy(), names
 
 
-def run_dev(wg, model, gaits, n_ticks, multi_tick=True, want_diag=True):
+def run_dev(wg, model, gaits, n_ticks, multi_tick=True, want_diag=True, vel=None, redraw=REDRAW):
     """the listed GLOBAL gait indices (any order) advanced n_ticks on the device through the unstaged plan, on the default
     stream: wg_mpc_set_velref_dev at every redraw, wg_mpc_tick_batch_dev for the first two ticks (for every tick without
-    multi_tick), wg_mpc_run_batch_dev up to the next redraw.  Returns (state bytes per gait as a uint8 array [B, size],
+    multi_tick), wg_mpc_run_batch_dev up to the next redraw.  vel ([n_seg, B, 3], redrawn every `redraw` ticks) replaces the
+    benchmark's references; `gaits` then only counts the gaits.  Returns (state bytes per gait as a uint8 array [B, size],
     diag [n_ticks, B, 6])"""
     import torch
     B = len(gaits)
     states = to_device(start_bytes(wg.gait_init, model), B)
-    n_seg = (n_ticks + REDRAW - 1) // REDRAW
-    vt = torch.from_numpy(np.stack([velocity(g, n_seg) for g in gaits], 1)).cuda()          # [seg, B, 3]
+    n_seg = (n_ticks + redraw - 1) // redraw
+    table = np.stack([velocity(g, n_seg) for g in gaits], 1) if vel is None else np.ascontiguousarray(vel, dtype=np.float64)
+    assert table.shape == (n_seg, B, 3), table.shape
+    vt = torch.from_numpy(table).cuda()                                                     # [seg, B, 3]
     diag = torch.zeros(n_ticks, B, 6, dtype=torch.int32, device="cuda")
     per_tick = int(round(model.T / model.Tctrl))
     t = 0
     while t < n_ticks:
-        if t % REDRAW == 0:
-            wg.mpc_set_velref_dev(B, states.data_ptr(), vt[t // REDRAW].data_ptr())
-        n = 1 if (t < 2 or not multi_tick) else min(n_ticks, (t // REDRAW + 1) * REDRAW) - t
+        if t % redraw == 0:
+            wg.mpc_set_velref_dev(B, states.data_ptr(), vt[t // redraw].data_ptr())
+        n = 1 if (t < 2 or not multi_tick) else min(n_ticks, (t // redraw + 1) * redraw) - t
         dp = diag[t].data_ptr() if want_diag else None
         if n == 1:
             wg.mpc_tick_batch_dev(B, states.data_ptr(), None, dp, advance_calls(t, per_tick))
