@@ -5,13 +5,16 @@
 // (Powell / Schittkowski dual active-set method; called from
 //  QPProblem::solve, src/ZMPRefTrajectoryGeneration/qp-problem.cpp:245-294.)
 //
-// The solver in four headers, included here in order (include this one):
+// The solver in five headers, included here in order (include this one):
 //   wg_wave.hpp        the one-wave rules (no barrier, lanes over independent outputs only, sums in the reference's order)
 //                      and the wave tools: WG_WSYNC, wg_lane, uni, rl, wg_kconst, the DPP reductions
 //   wg_ql_view.hpp     QlDims, QlView and its layouts, the Z / G / A / R accessors, the dense problem policies, QlResult,
-//                      QlResume, the WG_REP / PT_* instrumentation macros
+//                      QlResume, the WG_REP / WG_SINK macros of the attribution builds
+//   wg_prof.hpp        (included by wg_ql_view.hpp) the profile build's g_prof slots by name and its timer marks: PT_* for the
+//                      solver, TK_* for the tick, PT_LOCAL_* for a phase that times itself; nothing without WG_PROFILE
 //   wg_ql_phases.hpp   the phases of one active-set iteration (products with Z, back substitution, sweeps, scans, deletion)
-//   this file          the dispatch of the back substitution and the sweep by problem view, and ql_solve itself
+//   this file          the dispatch of the back substitution and the sweep by problem view, and ql_solve itself (ISA-sensitive: compare
+//                      every kernel before moving one of its blocks)
 // Compile with -ffp-contract=off: the reference build has no FMA contraction.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -41,6 +44,19 @@ namespace wg {
 #define WG_SWEEP(q, s, nu, nact, lane) \
   do { if (P::kNM > 0 || (!P::kRowOps && q.n <= 64)) sweep_flat<P::kFixedLdz>(q, s, nu, nact, lane PT_SW_ARG); else sweep<(P::kRowOps ? WG_ELEM_GRP : 8), P::kWideN>(q, s, nu, nact, lane); } while (0)
 
+// the reference's tests of one candidate row k in its order, :1256-1282 (cvmax starts at 0); reads wak, sum, temp of the scan body
+// it sits in and skips to its next row with `continue`.  A macro: as a function it changed the tick kernels' code
+#define QL_SCAN_ACCEPT                                                                        \
+  if (wak <= 0.0) continue;                                                                   \
+  double sumx = -sum * wak;                                                                   \
+  if (k + 1 <= me) sumx = fabs(sumx);                                                         \
+  if (sumx <= 0.0) continue;                                                                  \
+  if (bidx >= 0 && sumx <= bestv) continue;                                                   \
+  double tempa = temp + fabs(sum);                                                            \
+  if (tempa <= temp) continue;                                                                \
+  temp += onha * fabs(sum);                                                                   \
+  if (temp <= tempa) continue;                                                                \
+  bestv = sumx; bestres = sum; bestw = wak; bidx = k + 1
 template <class P>
 __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vsmall, int *hist, int hist_cap, QlResume *rs = nullptr) {
   // NaN iterates followed exactly (every policy of the shipped kernels; a policy may opt out for an A/B of what that costs)
@@ -108,7 +124,7 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
     fatal = uni(wave_min_int(fatal));
     if (fatal != 0x7fffffff) { info = -fatal; early_exit = true; }
   }
-  PT(0);
+  PT(PS_NORMS);
 
   if (!early_exit && !resuming) {
     // ---- make the Hessian numerically positive definite, :814-854 ----
@@ -134,7 +150,7 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
     }
     diag = uni(diag);
     bool need_shift = !(diag <= 0.0);                       // :844 `if (diag <= 0) goto L90`: a NaN shifts
-    PT(1);
+    PT(PS_DIAGCHK);
     bool factored = false;
     if constexpr (P::kHasFactor) {
       WG_REP(8)
@@ -198,7 +214,7 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
       need_shift = true;
     }
 
-    PT(2);
+    PT(PS_CHOL);
     // ---- Z = R^-1, :937-975 ----
     for (int i = lane; i < n; i += 64) {
       WG_UNROLL
@@ -226,7 +242,7 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
     }   // !factored
   }
 
-  PT(3);
+  PT(PS_INVERSE);
   // register rows of A (DenseRegProb) are loaded here, after the factorisation has given its registers back
   if constexpr (HasRegRows<P>::value) { if (!early_exit && !resuming) prob.load_rows(q, lane); }
   enum { ST_RESET, ST_RESID, ST_SCAN, ST_CONVERGED, ST_FINISH };
@@ -254,7 +270,7 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
         xmag = 0.0;
         vfact = 1.0;
         WG_WSYNC();
-        PT(24);
+        PT(PS_RESET_BODY);
       } else {                                              // :1031-1099
         iflag = 2;
         WG_REP(11) {                                        // gradient and residuals of the refresh: reads x, lam; writes ww, s
@@ -267,9 +283,7 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
             WG_UNROLL
             for (int j = 0; j < n; ++j) acc += Gm(i, j) * q.x[j];
           }
-#ifdef WG_PROFILE
-          q.ww[i] = acc; PT(27); acc = q.ww[i];
-#endif
+          PT_VIA(PS_RESID_GX, q.ww[i], acc);
           if constexpr (P::kCompact) acc = prob.grad_minus_active(q, ap, nact, i, acc);
           else {
             WG_UNROLL
@@ -299,7 +313,7 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
         }
         WG_WSYNC();
         }   // WG_REP(11)
-        PT(25);
+        PT(PS_RESID_GRAD);
       }
       if (nact > 0) {                                       // :1104-1170
         // forward substitution with R^T, column oriented (sums ascend in j)
@@ -315,7 +329,7 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
             if (i1 > j && i1 < nact) sum1 += Rp(j, i1) * sj;
           }
         }
-        PT(26);
+        PT(PS_RESID_FWD);
         if (P::kWideN || (P::kNM == 0 && n > 64 && n <= 128)) {
           double r0, r1;
           z_rows_times<(P::kRowOps ? WG_ELEM_GRP : 8)>(q, s, 0, nact, lane, r0, r1);
@@ -341,9 +355,9 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
         }
         WG_WSYNC();
       }
-      PT(4);
+      PT(PS_RESID);
       zt_times_ww<P::kNM, (P::kRowOps ? WG_ELEM_GRP : 8), P::kWideN>(q, s, lane);                           // :1175-1177
-      PT(5);
+      PT(PS_ZTWW_RESID);
       if (nact != n) {                                      // :1186-1201
         if (P::kWideN || (P::kNM == 0 && n > 64 && n <= 128)) {
           double r0, r1;
@@ -360,15 +374,15 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
         info = 0;
         WG_WSYNC();
       }
-      PT(6);
+      PT(PS_XSHIFT);
       if (nact != 0) {                                      // :1208-1217
         WG_BACKSUB(q, s, nact, lane);
         for (int k = lane; k < nact; k += 64) q.lam[k] += q.ww[k];
         WG_WSYNC();
       }
-      PT(7);
+      PT(PS_BACKSUB_RESID);
       { double sm = 0.0; WG_REP(6) { sm = uni(xmag_sum(q, prob, vfact, lane)); WG_SINK(sm); } xmag = maxd(xmag, sm); }
-      PT(8);
+      PT(PS_XMAG_RESID);
       if (iflag == itref) { st = ST_RESID; continue; }      // :1226
       // first inequality with a negative multiplier, :1233-1249 (`if (w[kdrop] >= zero) goto next`: a NaN multiplier IS dropped)
       int kd = 0x7fffffff;
@@ -470,16 +484,7 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
           const double wak = wak_p[pp], bk = bk_p[pp];
           double sum = -bk, temp = fabs(bk);
           prob.row_dot_both(q, kc, k0, ra_p[pp], rb_p[pp], rk_p[pp], q.x, sum, temp);
-          if (wak <= 0.0) continue;
-          double sumx = -sum * wak;
-          if (k + 1 <= me) sumx = fabs(sumx);
-          if (sumx <= 0.0) continue;
-          if (bidx >= 0 && sumx <= bestv) continue;
-          double tempa = temp + fabs(sum);
-          if (tempa <= temp) continue;
-          temp += onha * fabs(sum);
-          if (temp <= tempa) continue;
-          bestv = sumx; bestres = sum; bestw = wak; bidx = k + 1;
+          QL_SCAN_ACCEPT;
         }
       } else if constexpr (HasRegRows<P>::value) {
         // dense rows in registers: no memory access but x (LDS broadcasts, eight at a time); both of the lane's rows (lane,
@@ -508,16 +513,7 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
           const int k = pp == 0 ? ka : kb;
           const double wak = pp == 0 ? waka : wakb, sum = pp == 0 ? suma : sumb;
           double temp = pp == 0 ? tempa_ : tempb_;
-          if (wak <= 0.0) continue;
-          double sumx = -sum * wak;
-          if (k + 1 <= me) sumx = fabs(sumx);
-          if (sumx <= 0.0) continue;
-          if (bidx >= 0 && sumx <= bestv) continue;
-          double tempa = temp + fabs(sum);
-          if (tempa <= temp) continue;
-          temp += onha * fabs(sum);
-          if (temp <= tempa) continue;
-          bestv = sumx; bestres = sum; bestw = wak; bidx = k + 1;
+          QL_SCAN_ACCEPT;
         }
       } else
       // dense rows: ONE walk of the row for both sums (sum += x_i a_ki, temp += |x_i a_ki|, i ascending: the same values the
@@ -568,16 +564,7 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
             for (; i < n; ++i) { const double t = q.x[i] * Am(kc, i); sum += t; temp += fabs(t); }
           }
         }
-        if (wak <= 0.0) continue;
-        double sumx = -sum * wak;
-        if (k + 1 <= me) sumx = fabs(sumx);
-        if (sumx <= 0.0) continue;              // cvmax starts at 0 (:1256)
-        if (bidx >= 0 && sumx <= bestv) continue;
-        double tempa = temp + fabs(sum);
-        if (tempa <= temp) continue;
-        temp += onha * fabs(sum);
-        if (temp <= tempa) continue;
-        bestv = sumx; bestres = sum; bestw = wak; bidx = k + 1;
+        QL_SCAN_ACCEPT;
       }
       }
       if constexpr (P::kNM > 0) {                            // n <= 64: one bound pair per lane, selects instead of continues
@@ -625,7 +612,7 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
       }   // WG_REP(1)
       double cvmax = bestv;
       if (bidx >= 0) { res = bestres; knext = bidx; wsel = bestw; }
-      PT(9);
+      PT(PS_SCAN);
       info = 0;
       if (WG_UBOOL(cvmax <= wg_kconst(vsmall))) { st = ST_CONVERGED; continue; }  // :1336
 
@@ -661,7 +648,7 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
         for (int i = lane; i < n; i += 64) q.wx[i] = q.x[i];
         WG_WSYNC();
       }
-      PT(10);
+      PT(PS_FDIFF);
       ++iterc;                                              // :1415-1420
       if (iterc > maxit) { info = 1; st = ST_FINISH; continue; }
 
@@ -695,14 +682,14 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
         }
         WG_WSYNC();
       }
-      PT(11);
+      PT(PS_NEWNORMAL);
       double parnew = 0.0, parinc = 0.0, step = 0.0, sumy;
       int kdrop = -1;
       int route;   // 0 step, 1 dependent (multipliers needed), 2 dependent (multipliers in ww)
       if (nact == n) route = 1;                             // :1477
       else {
         WG_SWEEP(q, s, n, nact, lane);                         // :1480-1482
-        PT(12);
+        PT(PS_SWEEP);
         if (nact == 0) route = 0;                           // :1488
         else {                                              // :1491-1532
           double suma = 0.0, sumb = 0.0, sumc = 0.0;
@@ -759,7 +746,7 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
             if (knext <= m) sumc /= wsel;                    // wa[knext - 1]: the value the scan read
             if (WG_UBOOL(significant(sumc, fabs(suma)))) route = 0;
             else {                                          // :1538-1540
-              PT_COUNT(29);
+              PT_COUNT(PS_N_COORD);
               WG_BACKSUB(q, s, nact, lane);
               route = independent_coordinate(q, prob, knext, nact, vsmall, lane) ? 0 : 2;
             }
@@ -767,9 +754,9 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
         }
       }
       route = uni(route);
-      PT(13);
-      PT_COUNT(28);
-      if (route != 0) PT_COUNT(30);
+      PT(PS_ROUTE);
+      PT_COUNT(PS_N_ROUTE);
+      if (route != 0) PT_COUNT(PS_N_DEPENDENT);
       if (route != 0) {
         if (route == 1) WG_BACKSUB(q, s, nact, lane);
         kdrop = pick_drop<(P::kNM > 0), kNan>(q, nact, res, ratio, lane);
@@ -788,11 +775,11 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
           parinc = step / sumy;
           kdrop = -1;
           if (nact > 0) {
-            PT(14);
+            PT(PS_STEP_PRE);
             WG_REP(4) WG_BACKSUB(q, s, nact, lane);
-            PT(15);
+            PT(PS_BACKSUB_STEP);
             WG_REP(7) { kdrop = pick_drop<(P::kNM > 0), kNan>(q, nact, res, ratio, lane); WG_SINK(kdrop); WG_SINK(ratio); }
-            PT(16);
+            PT(PS_PICKDROP);
             if (kdrop >= 0) {                               // :1734-1743
               double temp = 1.0 - ratio / parinc;
               if (WG_UBOOL(temp <= 0.0)) kdrop = -1;
@@ -844,23 +831,17 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
         }
       }
 
-      PT(17);
+      PT(PS_STEP);
       // ---- add the new constraint, :1764-1771 ----
-      if (lane == 0) {
-        q.lam[nact] = parnew;
-        q.iact[nact] = knext;
-        int ia = knext - 1;
-        if (knext > mn) ia -= n;
-        q.wa[ia] = -wsel;                                   // = -wa[ia]: a store, not a read-modify-write
-      }
+      ql_activate(q, nact, knext, parnew, wsel, lane, n, mn);
       nact++;
       LOG_EVENT(knext);
       WG_WSYNC();
-      PT(18);
+      PT(PS_ADD);
       double sm = 0.0;
       WG_REP(6) { sm = uni(xmag_sum(q, prob, vfact, lane)); WG_SINK(sm); }   // :1776-1786
       xmag = maxd(xmag, sm);
-      PT(19);
+      PT(PS_XMAG_ADD);
       if (WG_UBOOL(sm < wg_kconst(xmagr) * xmag)) st = ST_RESET;
       else if (itref <= 0) st = ST_SCAN;
       else st = ST_RESID;
@@ -879,7 +860,7 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
   }
 #undef LOG_EVENT
 
-  PT(20);
+  PT(PS_TAIL);
   PT_FLUSH;
   if (cap_hit) {
     if (rs) {
@@ -890,11 +871,7 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
     out.ifail = kQlCapHit; out.n_iter = iterc; out.nact = nact;
     return out;
   }
-  // ---- ql0001 epilogue, :497-608 ----
-  out.ifail = 0;
-  if (info == 1) out.ifail = 1;
-  else if (info == 2) out.ifail = 2;
-  else if (info < 0) out.ifail = -info + 10;
+  out.ifail = ql_ifail_of(info);                          // ql0001 epilogue, :497-608
   out.n_iter = iterc;
   out.nact = nact;
   return out;

@@ -601,25 +601,18 @@ struct HerdtProb {
   __device__ __forceinline__ bool factor(const QlView &q, double vsmall, int lane) const {
     const int n = q.n;
     constexpr int M2 = 2 * NH;
-#ifdef WG_PROFILE
-    const unsigned long long fp0 = clock64();
-#endif
+    PT_LOCAL_BEGIN
     herdt_constant_blocks<NH>(q, R2, Z2, z2sign, lane);
     WG_WSYNC();
     const int nb = n - M2;                                  // border columns: 2 ns <= 4
-#ifdef WG_PROFILE
-    const unsigned long long fp1 = clock64();
-    if (lane == 0) atomicAdd(&g_prof[2], fp1 - fp0);       // slot "chol" (unused by the compact view): constant blocks into LDS
-#endif
+    PT_LOCAL(PS_CHOL);                                      // slot "chol" (unused by the compact view): constant blocks into LDS
     // rows of R, columns >= 2N only; straight-line per step count (a wave-uniform switch)
     bool ok = true;
     if (nb == 2) ok = herdt_border_rows<NH, 1>(q, gd, Gv, vsmall, lane);
     else if (nb == 4) ok = herdt_border_rows<NH, 2>(q, gd, Gv, vsmall, lane);
     if (!WG_UBOOL(ok)) return false;
     WG_WSYNC();
-#ifdef WG_PROFILE
-    if (lane == 0) atomicAdd(&g_prof[31], clock64() - fp1);   // border rows of R
-#endif
+    PT_LOCAL(PS_BORDER_ROWS);
     if (nb == 2) herdt_border_z<NH, 1>(q, lane);
     else if (nb == 4) herdt_border_z<NH, 2>(q, lane);
     WG_WSYNC();

@@ -527,7 +527,7 @@ __device__ __forceinline__ void sweep_flat(const QlView &q, double *s, int nu, i
     }
   }
   WG_WSYNC();
-  PT_SW(0);
+  PT_SW(PS_SW_NORMS);
   double myP = 0.0, myQ = 0.0, myN = 0.0;
   {
     const bool mine = lane > nact && lane < nu;
@@ -557,7 +557,7 @@ __device__ __forceinline__ void sweep_flat(const QlView &q, double *s, int nu, i
     if (rot) s[lane - 1] = myN;
   }
   WG_WSYNC();
-  PT_SW(1);
+  PT_SW(PS_SW_COEFF);
   {
     // phase 3: lane i carries row i of Z through the rotations.  Operands of rotation c -- Z(i, c-1) and the pair
     // (ga, gb) -- are fetched three rotations ahead into one of three register sets used in turn (an unroll by three, so
@@ -707,7 +707,7 @@ __device__ __forceinline__ void sweep_flat(const QlView &q, double *s, int nu, i
     if (any_skip) zp[0] = carry;                             // Z(i, nact)
   }
   WG_WSYNC();
-  PT_SW(2);
+  PT_SW(PS_SW_ROWS);
 }
 
 // qld.cpp:1861-1889.  Returns kdrop (0-based) or -1; ratio updated when found.
@@ -1283,6 +1283,26 @@ __device__ __forceinline__ bool chol_inverse_regs(const QlView &q, const P &prob
   }
   WG_WSYNC();
   return true;
+}
+
+// ---- blocks of ql_solve's main loop ----
+// add the new constraint, :1764-1771 (one lane)
+__device__ __forceinline__ void ql_activate(const QlView &q, int nact, int knext, double parnew, double wsel, int lane, int n, int mn) {
+  if (lane == 0) {
+    q.lam[nact] = parnew;
+    q.iact[nact] = knext;
+    int ia = knext - 1;
+    if (knext > mn) ia -= n;
+    q.wa[ia] = -wsel;                                   // = -wa[ia]: a store, not a read-modify-write
+  }
+}
+// ql0001 epilogue, :497-608: ql0002's info as the caller's ifail
+__device__ __forceinline__ int ql_ifail_of(int info) {
+  int ifail = 0;
+  if (info == 1) ifail = 1;
+  else if (info == 2) ifail = 2;
+  else if (info < 0) ifail = -info + 10;
+  return ifail;
 }
 
 }  // namespace wg

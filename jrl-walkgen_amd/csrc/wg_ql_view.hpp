@@ -1,7 +1,7 @@
 // wg_ql_view.hpp -- what a QL solve works on: the footprint of one QP (QlDims), the partition of a wave's LDS slice and its
 // global slots into the solver's arrays (QlView and its carve_* layouts), the accessors of Z, G, A and R, the dense problem
 // policies (DenseProbT, DenseRegProb) and the traits ql_solve asks a policy for, the result and resume records, and the
-// instrumentation macros of the attribution (WG_REP / WG_SINK) and profile (PT_*) builds.
+// instrumentation macros of the attribution builds (WG_REP / WG_SINK); those of the profile build are wg_prof.hpp's.
 //
 // Hessian G, Z (= R^-1, later rotated), packed R, the constraint matrix A and all vectors live in the wave's LDS slice unless
 // the layout says otherwise; leading dimensions are odd so that both row and column sweeps are bank-conflict free for 8-byte
@@ -12,6 +12,7 @@
 #include <type_traits>
 
 #include "wg_wave.hpp"
+#include "wg_prof.hpp"
 
 namespace wg {
 
@@ -230,31 +231,6 @@ template <class P> struct HasRegRows<P, typename std::enable_if<P::kRegRows>::ty
 #else
 #define WG_REP(id)
 #define WG_SINK(x) do {} while (0)
-#endif
-
-// ---- optional in-kernel phase timers (diagnostic build only: -DWG_PROFILE) ----
-#ifdef WG_PROFILE
-__device__ unsigned long long g_prof[48];               // 32..34: the sweep's three phases (norm chain, coefficients, row rotations)
-#define PT_DECL unsigned long long pt_acc[28] = {0}; unsigned long long pt_cnt[4] = {0}; unsigned long long pt_sw[3] = {0}; unsigned long long pt_last = clock64();
-#define PT(k) do { unsigned long long t_ = clock64(); pt_acc[k] += t_ - pt_last; pt_last = t_; } while (0)
-#define PT_FLUSH do { if ((threadIdx.x & 63) == 0) { for (int k_ = 0; k_ < 28; ++k_) if (k_ < 21 || k_ > 23) atomicAdd(&g_prof[k_], pt_acc[k_]); \
-                                                      for (int k_ = 0; k_ < 4; ++k_) atomicAdd(&g_prof[28 + k_], pt_cnt[k_]); \
-                                                      for (int k_ = 0; k_ < 3; ++k_) atomicAdd(&g_prof[32 + k_], pt_sw[k_]); } } while (0)
-#define PT_SW_PARAM , unsigned long long *ptsw = nullptr
-#define PT_SW_ARG , pt_sw
-#define PT_SW(k) do { if (ptsw) { unsigned long long t_ = clock64(); ptsw[k] += t_ - ptsw_last; ptsw_last = t_; } } while (0)
-#define PT_SW_BEGIN unsigned long long ptsw_last = clock64();
-// event counters 28..31: kept in registers and flushed once (a global atomic per event would show up in the phase it sits in)
-#define PT_COUNT(k) do { pt_cnt[(k) - 28]++; } while (0)
-#else
-#define PT_COUNT(k) do {} while (0)
-#define PT_SW_PARAM
-#define PT_SW_ARG
-#define PT_SW(k) do {} while (0)
-#define PT_SW_BEGIN
-#define PT_DECL
-#define PT(k) do {} while (0)
-#define PT_FLUSH do {} while (0)
 #endif
 
 // per-lane parameters of the active constraints, for problem views that supply a fast residual refresh

@@ -31,6 +31,14 @@ namespace wg {
 
 #define GmL(i, j) q.G[(i) + (j) * q.ldg]
 #define AmL(k, i) q.A[(k) + (i) * q.lda]
+// one wave copies a wg_gait_state_t in 8-byte lanes (`lane` is the caller's); _LD: relaxed atomic loads at `scope`, past a cache
+// that may hold a stale line.  Macros: as functions they changed the tick kernels' code
+#define WG_STATE_COPY(to, from)                                                                                       \
+  { double *dst = reinterpret_cast<double *>(to); const double *src = reinterpret_cast<const double *>(from);          \
+    for (int i = lane; i < (int)(sizeof(wg_gait_state_t) / 8); i += 64) dst[i] = src[i]; }
+#define WG_STATE_COPY_LD(to, from, scope)                                                                              \
+  { const double *src = reinterpret_cast<const double *>(from); double *dst = reinterpret_cast<double *>(to);           \
+    for (int i = lane; i < (int)(sizeof(wg_gait_state_t) / 8); i += 64) dst[i] = __hip_atomic_load(src + i, __ATOMIC_RELAXED, scope); }
 
 constexpr int kNMaxH = 32;   // largest horizon
 constexpr int kSMax = 4;     // largest number of previewed steps
@@ -571,23 +579,14 @@ __device__ __forceinline__ TickDiag mpc_tick(const wg_model_t &m, const TickTabl
     L.template carve<NH == 16>(lds_tick, N, (NH == 16) ? 2 : kSMax, kGvStride, reinterpret_cast<char *>(lds_ql), NH == 16,
                                (NH == 16) ? ext16 + kExtWab : nullptr);
   wg_gait_state_t *s = L.st;
-#ifdef WG_PROFILE
-  unsigned long long tk0 = clock64(), tk1 = 0, tk2 = 0, tk3 = 0, tka = 0, tkb = 0, tkc = 0, tkd = 0, tke = 0, tkf = 0, tkg = 0;
-#endif
+  TK_DECL
 
   // ---- state: HBM -> LDS (coalesced 8-byte lanes) ----
-  {
-    // agent-scope loads: in a multi-tick launch the previous tick of this gait may have run on another XCD
-    const double *src = reinterpret_cast<const double *>(gstate);
-    double *dst = reinterpret_cast<double *>(s);
-    for (int i = lane; i < (int)(sizeof(wg_gait_state_t) / 8); i += 64)
-      dst[i] = __hip_atomic_load(src + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  // agent-scope loads: in a multi-tick launch the previous tick of this gait may have run on another XCD
+  WG_STATE_COPY_LD(s, gstate, __HIP_MEMORY_SCOPE_AGENT);
   WG_WSYNC();
   const double time = s->clock;
-#ifdef WG_PROFILE
-  tka = clock64();
-#endif
+  TK(PS_TICK_LOAD);
 
   // ---- lane 0: support FSM, selection, orientations, polygon edges ----
   if (lane == 0) {
@@ -630,18 +629,14 @@ __device__ __forceinline__ TickDiag mpc_tick(const wg_model_t &m, const TickTabl
     constexpr int kSCap = (NH == 16) ? 2 : kSMax;   // both bounds are checked at configure time: N*T <= 2*step_period for the
                                                     // compact kernel, tick_max_prw_steps(model) <= kSMax for every model
     if (ns > kSCap) ns = kSCap;                     // cannot happen; keeps every index in range
-#ifdef WG_PROFILE
-    tkb = clock64();
-#endif
+    TK(PS_TICK_FSM);
     op_preview(m, s, time, ref, L.sup, L.sup_angles, L.trunk);
     *L.sup0 = L.sup[0];
     L.misc[0] = (double)ns;
     L.misc[1] = ref[0]; L.misc[2] = ref[1]; L.misc[3] = ref[2];
   }
   WG_WSYNC();
-#ifdef WG_PROFILE
-  tkc = clock64();
-#endif
+  TK(PS_TICK_ORIENT);
 
   // ---- lane-parallel part of the bookkeeping: one previewed instant per lane ----
   {
@@ -714,9 +709,7 @@ __device__ __forceinline__ TickDiag mpc_tick(const wg_model_t &m, const TickTabl
   }
   WG_WSYNC();
 
-#ifdef WG_PROFILE
-  tk1 = clock64();
-#endif
+  TK(PS_TICK_INSTANTS);
   const int ns = uni((int)L.misc[0]);     // the same in every lane: keep it (and n, m, every solver address) scalar
   const int n = 2 * N + 2 * ns;
   const int mq = 1 + 4 * N + 5 * ns;     // rows incl. the dummy row 0 (qp-problem.cpp:248)
@@ -896,19 +889,13 @@ __device__ __forceinline__ TickDiag mpc_tick(const wg_model_t &m, const TickTabl
   }   // WG_REP(9)
 
   // ---- QPProblem::solve -> ql0001_ (eps = 1e-8, qp-problem.cpp:260) ----
-#ifdef WG_PROFILE
-  tk2 = clock64();
-#endif
+  TK(PS_TICK_ASSEMBLY);
   QlResult qr;
   if constexpr (kCompactView) {
     if (lane == 0 && fabs(L.gd[n - 1]) == 0.0) L.gd[n - 1] = wg_kconst(1e-8);   // qld.cpp:442-444 (nmax == n)
     WG_WSYNC();
-    {
-      // the state's LDS copy sits on Z: park it in its HBM slot (L2) for the duration of the solve
-      double *dst = reinterpret_cast<double *>(gstate);
-      const double *src = reinterpret_cast<const double *>(s);
-      for (int i = lane; i < (int)(sizeof(wg_gait_state_t) / 8); i += 64) dst[i] = src[i];
-    }
+    // the state's LDS copy sits on Z: park it in its HBM slot (L2) for the duration of the solve
+    WG_STATE_COPY(gstate, s);
     HerdtProb<16> prob;
     prob.Qb = &tb->Qb[0][0]; prob.u = L.uvec; prob.Gv = L.Gv; prob.gd = L.gd;
     prob.rowA = L.rowA; prob.rowB = L.rowB; prob.rowK = L.rowK; prob.stepidx = L.stepidx; prob.V_f = L.V_f;
@@ -921,10 +908,7 @@ __device__ __forceinline__ TickDiag mpc_tick(const wg_model_t &m, const TickTabl
       // loads go -- agent-scope atomics: no stale L1 line of the tick's first read, no L1 invalidate that would hit the
       // other resident waves, and no L2 write-back: the same CU reads back what it wrote)
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-      const double *src = reinterpret_cast<const double *>(gstate);
-      double *dst = reinterpret_cast<double *>(s);
-      for (int i = lane; i < (int)(sizeof(wg_gait_state_t) / 8); i += 64)
-        dst[i] = __hip_atomic_load(src + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      WG_STATE_COPY_LD(s, gstate, __HIP_MEMORY_SCOPE_AGENT);
       WG_WSYNC();
     }
   } else if constexpr (kElem) {
@@ -932,9 +916,7 @@ __device__ __forceinline__ TickDiag mpc_tick(const wg_model_t &m, const TickTabl
     WG_WSYNC();
     {
       // the state's LDS copy sits on the solver's area: park it in its HBM slot (L2) for the duration of the solve
-      double *dst = reinterpret_cast<double *>(gstate);
-      const double *src = reinterpret_cast<const double *>(s);
-      for (int i = lane; i < (int)(sizeof(wg_gait_state_t) / 8); i += 64) dst[i] = src[i];
+      WG_STATE_COPY(gstate, s);
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // gd / d (global slot) written above are read by other lanes below
     }
     HerdtElemProbT<(NH == 32) ? 32 : -1> prob;
@@ -962,10 +944,7 @@ __device__ __forceinline__ TickDiag mpc_tick(const wg_model_t &m, const TickTabl
     {
       WG_WSYNC();
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-      const double *src = reinterpret_cast<const double *>(gstate);
-      double *dst = reinterpret_cast<double *>(s);
-      for (int i = lane; i < (int)(sizeof(wg_gait_state_t) / 8); i += 64)
-        dst[i] = __hip_atomic_load(src + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      WG_STATE_COPY_LD(s, gstate, __HIP_MEMORY_SCOPE_AGENT);
       WG_WSYNC();
     }
   } else {
@@ -987,9 +966,7 @@ __device__ __forceinline__ TickDiag mpc_tick(const wg_model_t &m, const TickTabl
     DenseProb prob;
     qr = ql_solve(q, prob, 1e-8, hist, hist_cap);
   }
-#ifdef WG_PROFILE
-  tk3 = clock64();
-#endif
+  TK_RESTART;
   if (hist_len && lane == 0) *hist_len = qr.hist_len;
   // A solve whose iterate became NaN: the reference does not notice (its running comparisons never skip a NaN), adds and drops until
   // maxit = 40 (m + n) and returns ifail = 1 with an all-NaN x, which the tick then integrates -- the gait is lost.  The views'
@@ -1067,9 +1044,7 @@ __device__ __forceinline__ TickDiag mpc_tick(const wg_model_t &m, const TickTabl
   }
   WG_WSYNC();
 
-#ifdef WG_PROFILE
-  tkd = clock64();
-#endif
+  TK(PS_TICK_COM);
   // ---- lane 0: trunk and feet (sequential in k) ----
   if (lane == 0) {
     const Sup cs = *L.sup0;
@@ -1102,12 +1077,9 @@ __device__ __forceinline__ TickDiag mpc_tick(const wg_model_t &m, const TickTabl
       for (int k = 0; k < K; k++)
         if (out) { out->com_yaw[k][0] = 0.0; out->com_yaw[k][1] = 0.0; }
     }
-
   }
   WG_WSYNC();
-#ifdef WG_PROFILE
-  tke = clock64();
-#endif
+  TK(PS_TICK_TRUNK);
 
   // ---- feet: one lane per 5 ms sample (interpolate_feet_positions, OnLineFootTrajectoryGeneration.cpp:235-346) ----
   {
@@ -1201,9 +1173,7 @@ __device__ __forceinline__ TickDiag mpc_tick(const wg_model_t &m, const TickTabl
       backl = outl; backr = outr;
     }
     WG_WSYNC();
-#ifdef WG_PROFILE
-    tkf = clock64();
-#endif
+    TK(PS_TICK_FEET);
     if (mine && out) { out->lf[lane] = outl; out->rf[lane] = outr; }
     if (lane == 0 && out) { out->lf_back = backl; out->rf_back = backr; }
     // the tail that rounds the struct up to whole cache lines: written (zeros) so that the last line leaves the L2 whole and the
@@ -1219,31 +1189,11 @@ __device__ __forceinline__ TickDiag mpc_tick(const wg_model_t &m, const TickTabl
     }
   }
   WG_WSYNC();
-#ifdef WG_PROFILE
-  tkg = clock64();
-#endif
+  TK(PS_TICK_QUEUE);
 
   // ---- state: LDS -> HBM ----
-  {
-    double *dst = reinterpret_cast<double *>(gstate);
-    const double *src = reinterpret_cast<const double *>(s);
-    for (int i = lane; i < (int)(sizeof(wg_gait_state_t) / 8); i += 64) dst[i] = src[i];
-  }
-#ifdef WG_PROFILE
-  if (lane == 0) {
-    atomicAdd(&g_prof[21], tk1 - tk0);                 // state load + lane-0 scalar part
-    atomicAdd(&g_prof[22], tk2 - tk1);                 // QP assembly
-    atomicAdd(&g_prof[23], clock64() - tk3);           // post-processing + state store
-    atomicAdd(&g_prof[35], tka - tk0);                 // of 21: state HBM -> LDS
-    atomicAdd(&g_prof[36], tkb - tka);                 //        lane 0: support FSM + preview of the support states
-    atomicAdd(&g_prof[37], tkc - tkb);                 //        lane 0: orientation preview
-    atomicAdd(&g_prof[38], tk1 - tkc);                 //        one instant per lane: selection, rotated references, hull edges
-    atomicAdd(&g_prof[39], tkd - tk3);                 // of 23: state fetched back, jerk, CoM samples, LIPM step
-    atomicAdd(&g_prof[40], tke - tkd);                 //        lane 0: trunk
-    atomicAdd(&g_prof[41], tkf - tke);                 //        feet: polynomials, one lane per sample
-    atomicAdd(&g_prof[42], tkg - tkf);                 //        samples into the state's queue (LDS)
-  }
-#endif
+  WG_STATE_COPY(gstate, s);
+  TK_FLUSH;
   TickDiag dg;
   dg.ifail = qr.ifail; dg.n_iter = qr.n_iter; dg.nact = qr.nact; dg.n = n; dg.m = mq; dg.ns = ns;
   return dg;

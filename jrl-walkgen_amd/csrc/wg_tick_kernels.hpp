@@ -55,6 +55,11 @@ constexpr bool wg_tick_is_elem(int NH) { return NH == -1 || NH == 32; }
     (p) = (decltype(p))gp_;                                                                       \
   } while (0)
 
+// the six ints a tick reports per gait (one lane)
+__device__ __forceinline__ void wg_diag_store(int *dq, const wg::TickDiag &dg) {
+  dq[0] = dg.ifail; dq[1] = dg.n_iter; dq[2] = dg.nact; dq[3] = dg.n; dq[4] = dg.m; dq[5] = dg.ns;
+}
+
 template <int NH>
 __global__ __launch_bounds__(64) WG_TICK_WAVES(NH) void wg_mpc_tick_kernel(int B, wg_model_t model, const wg::TickTables *__restrict__ tb,
                                                          wg_gait_state_t *__restrict__ states,
@@ -73,10 +78,7 @@ __global__ __launch_bounds__(64) WG_TICK_WAVES(NH) void wg_mpc_tick_kernel(int B
   if (g < B) {
     if (host_states) {
       // one-robot path (wg_mpc_tick_pinned): the caller's state lives in host-mapped memory; the tick works on a device copy
-      const double *src = reinterpret_cast<const double *>(host_states + g);
-      double *dst = reinterpret_cast<double *>(states + g);
-      for (int i = lane; i < (int)(sizeof(wg_gait_state_t) / 8); i += 64)
-        dst[i] = __hip_atomic_load(src + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      WG_STATE_COPY_LD(states + g, host_states + g, __HIP_MEMORY_SCOPE_SYSTEM);
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
       WG_WSYNC();
     }
@@ -94,8 +96,7 @@ __global__ __launch_bounds__(64) WG_TICK_WAVES(NH) void wg_mpc_tick_kernel(int B
                                    hist_cap, hist_len ? hist_len + g : nullptr,
                                    zscratch ? zscratch + (size_t)blockIdx.x * zslot : nullptr, elem_cap);
     if (diag && lane == 0) {
-      int *dq = diag + (size_t)g * 6;
-      dq[0] = dg.ifail; dq[1] = dg.n_iter; dq[2] = dg.nact; dq[3] = dg.n; dq[4] = dg.m; dq[5] = dg.ns;
+      wg_diag_store(diag + (size_t)g * 6, dg);
     }
     if (iters_out && lane == 0) iters_out[g] = dg.n_iter;
     WG_WSYNC();
@@ -103,9 +104,7 @@ __global__ __launch_bounds__(64) WG_TICK_WAVES(NH) void wg_mpc_tick_kernel(int B
       // state back to the caller's memory; outs / diag were written there directly.  Every store of this wave is performed
       // (system-scope release) before the completion counter moves: the host spins on it instead of synchronising.
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-      const double *src = reinterpret_cast<const double *>(states + g);
-      double *dst = reinterpret_cast<double *>(host_states + g);
-      for (int i = lane; i < (int)(sizeof(wg_gait_state_t) / 8); i += 64) dst[i] = src[i];
+      WG_STATE_COPY(host_states + g, states + g);
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
       WG_WSYNC();
       if (lane == 0) __hip_atomic_fetch_add(host_done, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -146,9 +145,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WG_TICK_WPE_
   const int g = blockIdx.x;
   if (g < B) {
     {
-      const double *src = reinterpret_cast<const double *>(states + g);
-      double *dst = reinterpret_cast<double *>(scratch + g);
-      for (int i = lane; i < (int)(sizeof(wg_gait_state_t) / 8); i += 64) dst[i] = src[i];
+      WG_STATE_COPY(scratch + g, states + g);
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
       WG_WSYNC();
     }
@@ -230,10 +227,7 @@ __global__ __launch_bounds__(64) WG_TICK_WAVES(NH) void wg_mpc_run_kernel(
     wg::TickDiag dg = wg::mpc_tick<NH>(model, tb, states + g, outs ? outs + (size_t)t * B + g : nullptr, wg_lds,
                                    reinterpret_cast<char *>(wg_lds) + ql_bytes, nullptr, 0, nullptr,
                                    zscratch ? zscratch + (size_t)blockIdx.x * zslot : nullptr, elem_cap);
-    if (diag && lane == 0) {
-      int *dq = diag + ((size_t)t * B + g) * 6;
-      dq[0] = dg.ifail; dq[1] = dg.n_iter; dq[2] = dg.nact; dq[3] = dg.n; dq[4] = dg.m; dq[5] = dg.ns;
-    }
+    if (diag && lane == 0) wg_diag_store(diag + ((size_t)t * B + g) * 6, dg);
     WG_WSYNC();
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");          // the state is in L2 before the gait is offered again
     if (lane == 0) {
@@ -378,7 +372,7 @@ __global__ __launch_bounds__(64) WG_TICK_WAVES(NH) void wg_mpc_run_xcd_kernel(
                                    zscratch ? zscratch + (size_t)blockIdx.x * zslot : nullptr, elem_cap);
     if (diag && lane == 0) {
       int *dq = diag + ((size_t)t * B + g) * 6;
-      dq[0] = dg.ifail; dq[1] = dg.n_iter; dq[2] = dg.nact; dq[3] = dg.n; dq[4] = dg.m; dq[5] = dg.ns;
+      wg_diag_store(dq, dg);
 #ifdef WG_XRUN_STATS
       // experiment build (tools/xrun_stats.py): when this tick ended (100 MHz counter), where it ran (block, XCD)
       dq[3] = (int)(unsigned)wall_clock64(); dq[4] = (int)blockIdx.x; dq[5] = xcc;
