@@ -602,20 +602,63 @@ int wg_zmpdisc_full_batch_dev(const wg_zmpdisc_model_t *model, int B, int smax, 
                               double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm,
                               int *right_type_tm, int *length, void *hip_stream);
 
-/* ZMP polytopes of a feet trajectory (host) ----------------------------------------------------------------------------
+/* ZMP polytopes of a feet trajectory ----------------------------------------------------------------------------------
  *
  * wg_foot_constraints replaces FootConstraintsAsLinearSystem::BuildLinearConstraintInequalities
  *     src/Mathematics/FootConstraintsAsLinearSystem.cpp:258-539   (+ ComputeLinearSystem :97-256,
  *     FindSimilarConstraints :55-92, ComputeConvexHull::DoComputeConvexHull src/Mathematics/ConvexHull.cpp:88-203):
  * one polytope per support phase of a 5 ms feet trajectory, A_j . zmp + B_j >= 0, with its validity interval -- the
  * queue ZMPConstrainedQPFastFormulation::BuildConstraintMatrices (:759-1022) walks to fill the wg_zmp_polytope_t of each
- * previewed instant.  Host code: it runs once per step sequence, not per tick.
+ * previewed instant.  Host code, one gait per call (the facade's one robot); a fleet whose feet are on the device builds its
+ * queues there with wg_foot_constraints_batch_dev below.
  *   n            samples;  time n;  left, right  n x 6 (x, y, z, theta, omega, omega2);  left_type n (stepType)
  *   sole_w, sole_h   getSoleSize outputs;  constraint_x, constraint_y  the security margins (ConstraintOnX / Y)
  *   polys, t_start, t_end   up to cap entries;  returns the number of polytopes (may exceed cap) or a negative code */
 int wg_foot_constraints(int n, const double *time, const double *left, const int *left_type, const double *right,
                         double sole_w, double sole_h, double constraint_x, double constraint_y, int cap,
                         wg_zmp_polytope_t *polys, double *t_start, double *t_end);
+
+/* Dimitrov-2008 fleets without the host between the feet trajectories and the tick -------------------------------------
+ *
+ * wg_foot_constraints_batch_dev is wg_foot_constraints for B gaits whose feet wg_zmpdisc_full_batch_dev left on the device
+ * (FootConstraintsAsLinearSystem.cpp:258-539, :97-256, :55-92, ConvexHull.cpp:88-203): per gait the bytes of the host call
+ * wg_foot_constraints(length[b], time, feet of gait b, ..., qcap, ...) -- same state machine, hull, half-plane forms and
+ * SimilarConstraints, entries [count, qcap) left untouched.  All pointers are DEVICE pointers.
+ *   length       B      samples of each gait as wg_zmpdisc_full_batch_dev wrote them; nothing past length[b] is read
+ *   time         lcap   ONE array shared by every gait
+ *   left_tm, right_tm  [lcap][6][B],  left_type_tm  [lcap][B]   (the layouts of wg_zmpdisc_full_batch_dev)
+ *   queues, t_start, t_end   [B][qcap]
+ *   count        B      polytopes of the gait (may exceed qcap, as the host call's return value may), or WG_ERR_BAD_ARG where
+ *                       the host call returns it (length[b] < 0 -- a gait wg_zmpdisc_* refused -- or > lcap; a support whose
+ *                       corners span no polygon: the queue entries of such a gait are unspecified)
+ * The time axis is split across blocks (chunks of wg_foot_constraints_chunk() samples, a kernel constant); the per-chunk
+ * counts live in a buffer of the context between the two passes, so launches of one context are ordered like tick launches. */
+int wg_foot_constraints_chunk(void);
+int wg_foot_constraints_batch_dev(int B, int lcap, const int *length, const double *time, const double *left_tm,
+                                  const int *left_type_tm, const double *right_tm, double sole_w, double sole_h,
+                                  double constraint_x, double constraint_y, int qcap, wg_zmp_polytope_t *queues,
+                                  double *t_start, double *t_end, int *count, void *hip_stream);
+/* The queue walk of one tick, BuildConstraintMatrices (ZMPConstrainedQPFastFormulation.cpp:785-796, 822-835), for B gaits:
+ * the first entry q with t_start[q] <= t0 <= t_end[q] is the start; for i = 0 .. N-1, q advances by one when
+ * t0 + i T > t_end[q] (the reference's StartingTime + i*T); polys[b][i] is a copy of entry q.  N and T are the configured
+ * Dimitrov model's (wg_dimitrov_configure).  Only the first min(count[b], qcap) entries of a queue exist.
+ * The reference gives up when t0 lies in no interval or the walk passes the last entry (:800-804, :830-833); a fleet launch
+ * cannot give up for one gait: such a gait gets its LAST polytope for the remaining instants (at rest on its final support,
+ * the convention of wg_zmpdisc_batch_dev past a gait's length) and ran_out[b] = 1, otherwise 0; count[b] <= 0: zeroed
+ * polytopes and ran_out[b] = 1.
+ *   polys  [B][N], what wg_dimitrov_tick_batch_dev reads;  ran_out  B or NULL */
+int wg_dimitrov_select_polys_dev(int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end,
+                                 const int *count, double t0, wg_zmp_polytope_t *polys, int *ran_out, void *hip_stream);
+/* n_ticks ticks of a fleet with nothing crossing the bus: for k = 0 .. n_ticks-1 { select at t; the launch of
+ * wg_dimitrov_tick_batch_dev; t += T }, t starting at t0 and accumulated by repeated addition like the loop of
+ * BuildZMPTrajectoryFromFootTrajectory (:1189-1192), all enqueued on hip_stream without a host synchronisation -- the bytes of
+ * a host loop of wg_dimitrov_select_polys_dev + wg_dimitrov_tick_batch_dev, in every solver mode.  The B x N selected
+ * polytopes live in a buffer of the context, sized on first use (growing never frees what a launch in flight may be reading,
+ * as for wg_mpc_reserve); walks of one context on different streams are ordered like tick launches.
+ *   outs     n_ticks x B, tick-major, or NULL;  ran_out  B: 1 once any tick of the gait ran out, or NULL */
+int wg_dimitrov_walk_dev(int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end,
+                         const int *count, double t0, int n_ticks, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs,
+                         int *ran_out, int max_iter, void *hip_stream);
 
 /* Invariant Hessian block on the matrix cores, batched over models -----------------------------------------------------
  *
@@ -680,6 +723,16 @@ int wg_dimitrov_tick_batch_dev_ctx(wg_ctx_t *ctx, int B, const wg_zmp_polytope_t
                                    wg_dimitrov_out_t *outs, int max_iter, void *hip_stream);
 int wg_dimitrov_tick_batch_ctx(wg_ctx_t *ctx, int B, const wg_zmp_polytope_t *polys, wg_dimitrov_state_t *states,
                                wg_dimitrov_out_t *outs, int max_iter);
+int wg_foot_constraints_batch_dev_ctx(wg_ctx_t *ctx, int B, int lcap, const int *length, const double *time,
+                                      const double *left_tm, const int *left_type_tm, const double *right_tm, double sole_w,
+                                      double sole_h, double constraint_x, double constraint_y, int qcap,
+                                      wg_zmp_polytope_t *queues, double *t_start, double *t_end, int *count, void *hip_stream);
+int wg_dimitrov_select_polys_dev_ctx(wg_ctx_t *ctx, int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start,
+                                     const double *t_end, const int *count, double t0, wg_zmp_polytope_t *polys, int *ran_out,
+                                     void *hip_stream);
+int wg_dimitrov_walk_dev_ctx(wg_ctx_t *ctx, int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start,
+                             const double *t_end, const int *count, double t0, int n_ticks, wg_dimitrov_state_t *states,
+                             wg_dimitrov_out_t *outs, int *ran_out, int max_iter, void *hip_stream);
 int wg_preview_configure_ctx(wg_ctx_t *ctx, const wg_preview_gains_t *gains, const double *F);
 int wg_preview_window_ctx(wg_ctx_t *ctx);
 int wg_preview_run_batch_dev_ctx(wg_ctx_t *ctx, int B, int L, const double *zmp_x_tm, const double *zmp_y_tm,

@@ -21,6 +21,7 @@
 #include "wg_preview_device.hpp"
 #include "wg_gramian_device.hpp"
 #include "wg_zmpdisc_device.hpp"
+#include "wg_footcons_device.hpp"
 #include "wg_ql_kernels.hpp"
 #include "wg_pldp_kernels.hpp"
 #include "wg_dimitrov_kernels.hpp"
@@ -149,6 +150,11 @@ struct wg_ctx {
   std::unique_ptr<wg::DimitrovConst> dim_host;
   bool dim_set = false;
   DevBuf dim_buf;
+  // Dimitrov fleets on the device: the per-chunk counts of wg_foot_constraints_batch_dev, and the B x N polytopes
+  // wg_dimitrov_walk_dev selects for the tick it launches next.  One launch at a time uses each: claimed and marked like the tick's
+  // buffers (fc_order, walk_order)
+  DevBuf fc_buf, walk_polys;
+  SlotOrder fc_order, walk_order;
   // preview control
   wg::PreviewConst prev;
   double *prev_F = nullptr;            // device copy of the window gains
@@ -164,10 +170,10 @@ struct wg_ctx {
     if (prev_F) (void)hipFree(prev_F);
     tables_dev = nullptr; model_dev = nullptr; pldp_dev = nullptr; dim_dev = nullptr; prev_F = nullptr;
     model_set = false; pldp_N = 0; dim_set = false; prev_set = false;
-    for (DevBuf *b : {&tick_state, &tick_out, &tick_aux, &run_buf, &tick_z, &asm_state, &qp_slot, &pldp_buf, &dim_buf, &prev_buf, &in, &out, &gram_buf, &zd_buf})
+    for (DevBuf *b : {&tick_state, &tick_out, &tick_aux, &run_buf, &tick_z, &asm_state, &qp_slot, &pldp_buf, &dim_buf, &fc_buf, &walk_polys, &prev_buf, &in, &out, &gram_buf, &zd_buf})
       b->release();
     for (Lpt *l : {&tick_lpt, &qp_lpt, &dim_lpt}) l->release();
-    for (SlotOrder *o : {&guard_order, &qp_order, &asm_order, &aux_order}) {
+    for (SlotOrder *o : {&guard_order, &qp_order, &asm_order, &aux_order, &fc_order, &walk_order}) {
       if (o->ev) (void)hipEventDestroy(o->ev);
       o->ev = nullptr; o->armed = false; o->stream = nullptr;
     }
@@ -245,7 +251,7 @@ int slot_claim(wg_ctx *ctx, wg_ctx::SlotOrder &o, hipStream_t st, const char *wh
 // the context's own streams) -- not for the device
 int ctx_wait_own(wg_ctx *ctx) {
   std::lock_guard<std::mutex> launch_lk(ctx->launch_mu);
-  for (wg_ctx::SlotOrder *o : {&ctx->guard_order, &ctx->qp_order, &ctx->asm_order, &ctx->aux_order})
+  for (wg_ctx::SlotOrder *o : {&ctx->guard_order, &ctx->qp_order, &ctx->asm_order, &ctx->aux_order, &ctx->fc_order, &ctx->walk_order})
     if (o->armed) HIP_TRY(hipEventSynchronize(o->ev));
   if (ctx->host_stream) HIP_TRY(hipStreamSynchronize(ctx->host_stream));
   if (ctx->pin_stream) HIP_TRY(hipStreamSynchronize(ctx->pin_stream));
@@ -1137,6 +1143,32 @@ int dimitrov_check(wg_ctx *ctx, int B, const wg_zmp_polytope_t *polys, const wg_
   if (B < 0 || !polys || !states) return fail(WG_ERR_BAD_ARG, "bad arguments");
   return WG_OK;
 }
+
+// the tick launch of wg_dimitrov_tick_batch_dev and of every tick of wg_dimitrov_walk_dev; with ctx->launch_mu held
+int dimitrov_tick_launch(wg_ctx *ctx, int B, const wg_zmp_polytope_t *polys, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int max_iter, hipStream_t stq) {
+  const int solver = ctx->dim_host->solver;
+  if (solver != WG_DIMITROV_PLDP) {                      // modes QLD / QLDANDLQ: the in-wave ql0002 as the back-end
+    const size_t ldsq = wg::dimitrov_qld_lds_bytes();
+    // more gaits than resident waves (eight per CU: 256 registers, two waves per SIMD): longest-solve-first by the previous tick
+    // on the same state array (scheduling only).  The order lives in a buffer of the context: not while another stream's launch
+    // of this context may still be reading it
+    int *order = nullptr, *iters_out = nullptr;
+    if ((size_t)B > (size_t)ctx->num_cu * per_cu_granules(ldsq, 8) && !slot_pending_elsewhere(ctx->aux_order, stq) && env_flag("WG_QL_LPT", true))
+      if (int rc = lpt_prepare(ctx->dim_lpt, states, B, stq, &order, &iters_out)) return rc;
+    const auto kern = solver == WG_DIMITROV_QLDANDLQ ? wg_dimitrov_qld_tick_kernel<true> : wg_dimitrov_qld_tick_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3(B), dim3(64), ldsq, stq, B, ctx->dim_dev, polys, states, outs, order, iters_out);
+    HIP_TRY(hipGetLastError());
+    return slot_mark(ctx->aux_order, stq);
+  }
+  const size_t lds = dimitrov_lds_bytes();
+  if (lds > 64 * 1024)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(wg_dimitrov_tick_kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const int grid = B;
+  hipLaunchKernelGGL(wg_dimitrov_tick_kernel, dim3(grid), dim3(64), lds, stq, B, ctx->dim_dev, polys, states, outs, max_iter);
+  HIP_TRY(hipGetLastError());
+  return slot_mark(ctx->aux_order, stq);
+}
 }  // namespace
 
 extern "C" {
@@ -1199,30 +1231,8 @@ int wg_dimitrov_get_qld_constants_ctx(wg_ctx_t *ctx, double *Q, double *OptB, do
 int wg_dimitrov_tick_batch_dev_ctx(wg_ctx_t *ctx, int B, const wg_zmp_polytope_t *polys, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int max_iter, void *hip_stream) {
   if (int rc = dimitrov_check(ctx, B, polys, states)) return rc;
   if (B == 0) return WG_OK;
-  hipStream_t stq = reinterpret_cast<hipStream_t>(hip_stream);
   std::lock_guard<std::mutex> launch_lk(ctx->launch_mu);
-  const int solver = ctx->dim_host->solver;
-  if (solver != WG_DIMITROV_PLDP) {                      // modes QLD / QLDANDLQ: the in-wave ql0002 as the back-end
-    const size_t ldsq = wg::dimitrov_qld_lds_bytes();
-    // more gaits than resident waves (eight per CU: 256 registers, two waves per SIMD): longest-solve-first by the previous tick
-    // on the same state array (scheduling only).  The order lives in a buffer of the context: not while another stream's launch
-    // of this context may still be reading it
-    int *order = nullptr, *iters_out = nullptr;
-    if ((size_t)B > (size_t)ctx->num_cu * per_cu_granules(ldsq, 8) && !slot_pending_elsewhere(ctx->aux_order, stq) && env_flag("WG_QL_LPT", true))
-      if (int rc = lpt_prepare(ctx->dim_lpt, states, B, stq, &order, &iters_out)) return rc;
-    const auto kern = solver == WG_DIMITROV_QLDANDLQ ? wg_dimitrov_qld_tick_kernel<true> : wg_dimitrov_qld_tick_kernel<false>;
-    hipLaunchKernelGGL(kern, dim3(B), dim3(64), ldsq, stq, B, ctx->dim_dev, polys, states, outs, order, iters_out);
-    HIP_TRY(hipGetLastError());
-    return slot_mark(ctx->aux_order, stq);
-  }
-  const size_t lds = dimitrov_lds_bytes();
-  if (lds > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(wg_dimitrov_tick_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int grid = B;
-  hipLaunchKernelGGL(wg_dimitrov_tick_kernel, dim3(grid), dim3(64), lds, stq, B, ctx->dim_dev, polys, states, outs, max_iter);
-  HIP_TRY(hipGetLastError());
-  return slot_mark(ctx->aux_order, stq);
+  return dimitrov_tick_launch(ctx, B, polys, states, outs, max_iter, reinterpret_cast<hipStream_t>(hip_stream));
 }
 
 int wg_dimitrov_tick_batch_ctx(wg_ctx_t *ctx, int B, const wg_zmp_polytope_t *polys, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int max_iter) {
@@ -1244,6 +1254,90 @@ int wg_dimitrov_tick_batch_ctx(wg_ctx_t *ctx, int B, const wg_zmp_polytope_t *po
   if (outs) WG_D2H(outs, a(so), so.bytes());
   WG_HOST_WAIT();
   return WG_OK;
+}
+
+}  // extern "C"
+
+// ---- Dimitrov fleets on the device: polytope queues, the queue walk of a tick, n ticks on a stream --------------------------
+
+namespace {
+int select_check(wg_ctx *ctx, int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count) {
+  if (int rc = use_ctx(ctx)) return rc;
+  if (!ctx->dim_set) return fail(WG_ERR_BAD_ARG, "wg_dimitrov_configure() has not been called on this context");
+  if (B < 0 || qcap < 1 || !queues || !t_start || !t_end || !count) return fail(WG_ERR_BAD_ARG, "need B >= 0, qcap >= 1, non-null queues, intervals and counts");
+  return WG_OK;
+}
+void select_launch(wg_ctx *ctx, int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count, double t0, wg_zmp_polytope_t *polys, int *ran_out, int sticky, hipStream_t st) {
+  hipLaunchKernelGGL(wg::wg_dimitrov_select_kernel, dim3((B + 3) / 4), dim3(256), 0, st, B, qcap, queues, t_start, t_end, count, t0,
+                     ctx->dim_host->N, ctx->dim_host->T, polys, ran_out, sticky);
+}
+}  // namespace
+
+extern "C" {
+
+int wg_foot_constraints_chunk(void) { return wg::kFcChunk; }
+
+int wg_foot_constraints_batch_dev_ctx(wg_ctx_t *ctx, int B, int lcap, const int *length, const double *time, const double *left_tm, const int *left_type_tm, const double *right_tm, double sole_w, double sole_h, double constraint_x, double constraint_y, int qcap, wg_zmp_polytope_t *queues, double *t_start, double *t_end, int *count, void *hip_stream) {
+  if (int rc = use_ctx(ctx)) return rc;
+  if (B < 0 || qcap < 0) return fail(WG_ERR_BAD_ARG, "need B >= 0, qcap >= 0");
+  if (B == 0) return WG_OK;
+  if (qcap > 0 && (!queues || !t_start || !t_end)) return fail(WG_ERR_BAD_ARG, "need non-null queues and intervals for qcap > 0");
+  if (lcap < 1 || !length || !time || !left_tm || !left_type_tm || !right_tm || !count)
+    return fail(WG_ERR_BAD_ARG, "need lcap >= 1, non-null lengths, times, feet arrays and counts");
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  double hw = sole_w * 0.5, hh = sole_h * 0.5;
+  hh -= constraint_y;
+  hw -= constraint_x;
+  const wg::FcIn I{B, lcap, length, time, left_tm, right_tm, left_type_tm, hw, hh};
+  const wg::FcOut Q{qcap, queues, t_start, t_end, count};
+  const int chunks = (lcap + wg::kFcChunk - 1) / wg::kFcChunk;
+  if (chunks > 65535) return fail(WG_ERR_TOO_LARGE, "lcap = %d: more than 65535 chunks of %d samples", lcap, wg::kFcChunk);
+  // the per-chunk counts live in a buffer of the context between the two passes: one launch at a time uses it
+  std::lock_guard<std::mutex> launch_lk(ctx->launch_mu);
+  if (int rc = slot_claim(ctx, ctx->fc_order, st, "foot-constraints")) return rc;
+  if (int rc = ctx->fc_buf.reserve((size_t)chunks * (size_t)B * sizeof(int))) return rc;
+  int *cnt = static_cast<int *>(ctx->fc_buf.p);
+  const dim3 grid((B + 63) / 64, chunks);
+  HIP_TRY(hipMemsetAsync(count, 0, (size_t)B * sizeof(int), st));
+  hipLaunchKernelGGL(wg::wg_footcons_kernel<false>, grid, dim3(64), 0, st, I, Q, cnt);
+  hipLaunchKernelGGL(wg::wg_footcons_kernel<true>, grid, dim3(64), 0, st, I, Q, cnt);
+  HIP_TRY(hipGetLastError());
+  return slot_mark(ctx->fc_order, st);
+}
+
+int wg_dimitrov_select_polys_dev_ctx(wg_ctx_t *ctx, int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count, double t0, wg_zmp_polytope_t *polys, int *ran_out, void *hip_stream) {
+  if (int rc = select_check(ctx, B, qcap, queues, t_start, t_end, count)) return rc;
+  if (!polys) return fail(WG_ERR_BAD_ARG, "null polys");
+  if (B == 0) return WG_OK;
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  std::lock_guard<std::mutex> launch_lk(ctx->launch_mu);
+  select_launch(ctx, B, qcap, queues, t_start, t_end, count, t0, polys, ran_out, 0, st);
+  HIP_TRY(hipGetLastError());
+  return slot_mark(ctx->aux_order, st);                   // N and T are the configured model's: a re-configuration waits for it
+}
+
+int wg_dimitrov_walk_dev_ctx(wg_ctx_t *ctx, int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count, double t0, int n_ticks, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int *ran_out, int max_iter, void *hip_stream) {
+  if (int rc = select_check(ctx, B, qcap, queues, t_start, t_end, count)) return rc;
+  if (n_ticks < 0 || !states) return fail(WG_ERR_BAD_ARG, "need n_ticks >= 0 and non-null states");
+  if (B == 0 || n_ticks == 0) return WG_OK;
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  const size_t N = (size_t)ctx->dim_host->N;
+  const double T = ctx->dim_host->T;
+  std::lock_guard<std::mutex> launch_lk(ctx->launch_mu);
+  // the selected polytopes live in a buffer of the context, rewritten tick by tick: behind the previous walk, whatever stream
+  // that was on; growing retires the old allocation, which a launch in flight may still be reading (DevBuf)
+  if (int rc = slot_claim(ctx, ctx->walk_order, st, "Dimitrov walk")) return rc;
+  if (int rc = ctx->walk_polys.reserve((size_t)B * N * sizeof(wg_zmp_polytope_t))) return rc;
+  wg_zmp_polytope_t *polys = static_cast<wg_zmp_polytope_t *>(ctx->walk_polys.p);
+  if (ran_out) HIP_TRY(hipMemsetAsync(ran_out, 0, (size_t)B * sizeof(int), st));
+  double t = t0;
+  for (int k = 0; k < n_ticks; k++) {
+    select_launch(ctx, B, qcap, queues, t_start, t_end, count, t, polys, ran_out, 1, st);
+    HIP_TRY(hipGetLastError());
+    if (int rc = dimitrov_tick_launch(ctx, B, polys, states, outs ? outs + (size_t)k * (size_t)B : nullptr, max_iter, st)) return rc;
+    t += T;                                               // BuildZMPTrajectoryFromFootTrajectory's own accumulation (:1189-1192)
+  }
+  return slot_mark(ctx->walk_order, st);
 }
 
 }  // extern "C"
@@ -1590,6 +1684,9 @@ int wg_dimitrov_get_constants(double *iLQ, double *OptB, double *OptC, double *P
 int wg_dimitrov_get_qld_constants(double *Q, double *OptB, double *OptC, double *PuT) { return on_default(&wg_dimitrov_get_qld_constants_ctx, Q, OptB, OptC, PuT); }
 int wg_dimitrov_tick_batch_dev(int B, const wg_zmp_polytope_t *polys, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int max_iter, void *hip_stream) { return on_default(&wg_dimitrov_tick_batch_dev_ctx, B, polys, states, outs, max_iter, hip_stream); }
 int wg_dimitrov_tick_batch(int B, const wg_zmp_polytope_t *polys, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int max_iter) { return on_default(&wg_dimitrov_tick_batch_ctx, B, polys, states, outs, max_iter); }
+int wg_foot_constraints_batch_dev(int B, int lcap, const int *length, const double *time, const double *left_tm, const int *left_type_tm, const double *right_tm, double sole_w, double sole_h, double constraint_x, double constraint_y, int qcap, wg_zmp_polytope_t *queues, double *t_start, double *t_end, int *count, void *hip_stream) { return on_default(&wg_foot_constraints_batch_dev_ctx, B, lcap, length, time, left_tm, left_type_tm, right_tm, sole_w, sole_h, constraint_x, constraint_y, qcap, queues, t_start, t_end, count, hip_stream); }
+int wg_dimitrov_select_polys_dev(int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count, double t0, wg_zmp_polytope_t *polys, int *ran_out, void *hip_stream) { return on_default(&wg_dimitrov_select_polys_dev_ctx, B, qcap, queues, t_start, t_end, count, t0, polys, ran_out, hip_stream); }
+int wg_dimitrov_walk_dev(int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count, double t0, int n_ticks, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int *ran_out, int max_iter, void *hip_stream) { return on_default(&wg_dimitrov_walk_dev_ctx, B, qcap, queues, t_start, t_end, count, t0, n_ticks, states, outs, ran_out, max_iter, hip_stream); }
 int wg_mpc_tick_pinned(wg_gait_state_t *state, wg_tick_out_t *out, int *diag, int advance_calls) { return on_default(&wg_mpc_tick_pinned_ctx, state, out, diag, advance_calls); }
 int wg_mpc_assemble_batch_dev(int B, const wg_gait_state_t *states, int advance_calls, int nmax, int mmax, double *C, double *d, double *A, double *b, double *xl, double *xu, int *n, int *m, void *hip_stream) { return on_default(&wg_mpc_assemble_batch_dev_ctx, B, states, advance_calls, nmax, mmax, C, d, A, b, xl, xu, n, m, hip_stream); }
 int wg_mpc_assemble_batch(int B, const wg_gait_state_t *states, int advance_calls, int nmax, int mmax, double *C, double *d, double *A, double *b, double *xl, double *xu, int *n, int *m) { return on_default(&wg_mpc_assemble_batch_ctx, B, states, advance_calls, nmax, mmax, C, d, A, b, xl, xu, n, m); }

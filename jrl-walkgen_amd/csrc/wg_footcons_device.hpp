@@ -1,0 +1,336 @@
+// wg_footcons_device.hpp -- the Dimitrov-2008 pipeline between the feet trajectories and the tick, on the device:
+//
+//   wg_footcons_kernel<false / true>   polytope queues of B feet trajectories (wg_foot_constraints_batch_dev)
+//       FootConstraintsAsLinearSystem::BuildLinearConstraintInequalities  src/Mathematics/FootConstraintsAsLinearSystem.cpp:258-539
+//       ComputeLinearSystem :97-256, FindSimilarConstraints :55-92, ComputeConvexHull::DoComputeConvexHull ConvexHull.cpp:88-203
+//   wg_dimitrov_select_kernel          the queue walk of one tick (wg_dimitrov_select_polys_dev, wg_dimitrov_walk_dev)
+//       ZMPConstrainedQPFastFormulation::BuildConstraintMatrices  ZMPConstrainedQPFastFormulation.cpp:785-796, 822-835
+//
+// Queues.  The host version (wg_footcons.cpp) walks one gait sample by sample.  Here the inputs are the time-major arrays
+// wg_zmpdisc_full_batch_dev writes ([sample][component][gait]): lanes are gaits, so that every row a wave reads is one 512-byte
+// line, and the time axis is split across blocks -- grid = (gait groups of 64) x (chunks of kFcChunk samples) -- because one
+// lane walking all 2-3 k samples of its gait is 64 waves on 1024 SIMDs with one dependent load after the other.  What makes
+// the split possible: the support state of a sample depends on that sample alone (left stepType, left z, right z), except
+// when none of the reference's three tests holds (a z exactly at the lifting threshold), where it keeps its predecessor's.
+//   pass 1 (kBuild = false)  every lane classifies the samples of its chunk (independent loads, 2 bits each, kept in two
+//                            registers), classifies the sample before the chunk for the boundary test (walking back while
+//                            that one inherits) and counts the support changes: cnt[chunk][gait], and their sum into count[gait];
+//   pass 2 (kBuild = true)   the counts of the earlier chunks give the queue position of the chunk's first polytope; the lane
+//                            walks its codes again and builds a polytope at every change.  The hull (Graham scan over the 8
+//                            sole corners, in the reference's std::set order) runs in that one lane on points kept in LDS laid
+//                            out [slot][lane] (runtime-indexed, so not in registers; conflict-free).
+// Every entry of the queue has exactly one writer: polytope q and t_start[q] the lane that finds change q, t_end[q] the lane
+// that finds change q + 1, the last t_end the lane whose chunk holds the gait's last sample.  Nothing past length[b] is read.
+// Same operation order as wg_footcons.cpp; the library is built with -ffp-contract=off, / and sqrt are IEEE on both sides and
+// sin / cos are include/wg_trig.h: the same bytes.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "../../include/wg_mpc.h"
+#ifndef WG_TRIG_FN
+#define WG_TRIG_FN __host__ __device__ static inline
+#endif
+#include "../../include/wg_trig.h"
+
+namespace wg {
+
+constexpr int kFcChunk = 64;             // samples per (gait, chunk) lane: 2 bits of support state each in two 64-bit registers
+constexpr int kFcSlots = 17;             // hull scratch per lane: 9 points (corners, then the hull) + 8 (the ordered candidates)
+constexpr double kFcPi = 3.14159265358979323846;
+enum { kFcInherit = 0, kFcRight = 1, kFcLeft = 2, kFcDouble = 3 };   // 1..3: the reference's states
+
+struct FcIn {
+  int B, lcap;
+  const int *length;                     // B
+  const double *time;                    // lcap, shared
+  const double *left, *right;            // [lcap][6][B]
+  const int *ltype;                      // [lcap][B]
+  double hw, hh;                         // half sole minus the margins
+};
+struct FcOut {
+  int qcap;
+  wg_zmp_polytope_t *queues;             // [B][qcap]
+  double *t_start, *t_end;               // [B][qcap]
+  int *count;                            // B, zeroed before pass 1
+};
+
+// the state the reference's three tests give sample (stepType, left z, right z), or kFcInherit when none of them holds
+__device__ __forceinline__ int fc_classify(int ltype, double lz, double rz) {
+  const double lifting = 0.00001;
+  if (ltype >= 10) return kFcDouble;
+  if (lz > lifting) return kFcLeft;      // the reference's state 2: the LEFT foot is in the air
+  if (rz > lifting) return kFcRight;
+  if (rz < lifting && lz < lifting) return kFcDouble;
+  return kFcInherit;
+}
+
+// one lane's hull scratch: point s at [2 s + {0, 1}][lane]
+struct FcPts {
+  double *base;
+  __device__ __forceinline__ double &x(int s) const { return base[(2 * s) * 64]; }
+  __device__ __forceinline__ double &y(int s) const { return base[(2 * s + 1) * 64]; }
+};
+
+__device__ __forceinline__ double fc_cross(double ox, double oy, double ax, double ay, double bx, double by) {
+  const double x1 = ax - ox, x2 = bx - ox, y1 = ay - oy, y2 = by - oy;
+  return x1 * y2 - x2 * y1;
+}
+
+// sole_corners of wg_footcons.cpp into slots s0 .. s0 + 3 (counter-clockwise)
+__device__ inline void fc_corners(const FcPts &P, int s0, double fx, double fy, double theta, double hw, double hh) {
+  const double s = wg_sin(theta * kFcPi / 180.0), c = wg_cos(theta * kFcPi / 180.0);
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    const double sx = j < 2 ? 1.0 : -1.0, sy = (j == 1 || j == 2) ? 1.0 : -1.0;
+    P.x(s0 + j) = fx + (sx * hw * c - sy * hh * s);
+    P.y(s0 + j) = fy + (sx * hw * s + sy * hh * c);
+  }
+}
+
+// graham_hull of wg_footcons.cpp: the 8 points in slots 0..7 -> the hull in slots 0.. (returned size; 0: fewer than two
+// directions).  Slots 9..16 hold the candidates in ascending polar angle about the lowest point.
+__device__ inline int fc_hull8(const FcPts &P) {
+  const int O = 9;
+  double p0x = P.x(0), p0y = P.y(0);
+  for (int i = 0; i < 8; i++)
+    if (P.y(i) < p0y) { p0x = P.x(i); p0y = P.y(i); }
+  int no = 0;
+  for (int i = 0; i < 8; i++) {
+    const double px = P.x(i), py = P.y(i);
+    bool insert = true;
+    for (int k = 0; k < no;) {
+      const double kx = P.x(O + k), ky = P.y(O + k);
+      if (fc_cross(p0x, p0y, kx, ky, px, py) == 0.0) {
+        const double dk = sqrt((kx - p0x) * (kx - p0x) + (ky - p0y) * (ky - p0y));
+        const double dp = sqrt((px - p0x) * (px - p0x) + (py - p0y) * (py - p0y));
+        if (dk <= dp) {
+          for (int q = k; q < no - 1; q++) { P.x(O + q) = P.x(O + q + 1); P.y(O + q) = P.y(O + q + 1); }
+          no--;
+          continue;
+        }
+        insert = false;
+      }
+      k++;
+    }
+    if (!insert) continue;
+    int pos = 0;
+    bool equivalent = false;
+    for (; pos < no; pos++) {
+      const double kx = P.x(O + pos), ky = P.y(O + pos);
+      if (fc_cross(p0x, p0y, px, py, kx, ky) > 0.0) break;            // p orders before the candidate
+      if (!(fc_cross(p0x, p0y, kx, ky, px, py) > 0.0)) equivalent = true;
+    }
+    if (!equivalent) {
+      for (int q = no; q > pos; q--) { P.x(O + q) = P.x(O + q - 1); P.y(O + q) = P.y(O + q - 1); }
+      P.x(O + pos) = px; P.y(O + pos) = py;
+      no++;
+    }
+  }
+  if (no < 2) return 0;
+  int nh = 0;
+  P.x(nh) = p0x; P.y(nh) = p0y; nh++;
+  P.x(nh) = P.x(O); P.y(nh) = P.y(O); nh++;
+  P.x(nh) = P.x(O + 1); P.y(nh) = P.y(O + 1); nh++;
+  for (int it = 2; it < no; it++) {
+    const double ix = P.x(O + it), iy = P.y(O + it);
+    while (nh >= 2 && !(fc_cross(P.x(nh - 2), P.y(nh - 2), P.x(nh - 1), P.y(nh - 1), ix, iy) > 0.0)) nh--;
+    P.x(nh) = ix; P.y(nh) = iy; nh++;
+  }
+  return nh;
+}
+
+// half_plane of wg_footcons.cpp: the half plane left of the edge p -> q as a x + c y + b >= 0, offset taken at (ax_, ay_)
+__device__ __forceinline__ void fc_half_plane(double px, double py, double qx, double qy, double ax_, double ay_, double &a,
+                                              double &c, double &b) {
+  if (fabs(qx - px) > 1e-7) {
+    double x1, y1, x2, y2, lmul = -1.0;
+    if (qx < px) {
+      lmul = 1.0;
+      x1 = qx; y1 = qy; x2 = px; y2 = py;
+    } else {
+      x1 = px; y1 = py; x2 = qx; y2 = qy;
+    }
+    a = (y2 - y1) / (x2 - x1);
+    b = (ay_ - a * ax_);
+    a = lmul * a;
+    b = lmul * b;
+    c = -lmul;
+  } else {
+    c = 0.0;
+    a = -1.0;
+    b = qx;
+    if (qy < py) {
+      a = -a;
+      b = -b;
+    }
+  }
+}
+
+// polytope_of of wg_footcons.cpp on the hull in slots 0..n-1, written straight to the queue entry (every byte of it); the rows'
+// (a, c) go through slots 9.. for FindSimilarConstraints.  false: the reference's "not a polytope" (n < 2 or n > 8)
+__device__ inline bool fc_polytope(const FcPts &P, int n, wg_zmp_polytope_t *out) {
+  if (n < 2 || n > WG_POLY_MAX_ROWS) return false;
+  const int O = 9;
+  double cx = 0.0, cy = 0.0;
+  for (int i = 0; i < WG_POLY_MAX_ROWS; i++) {
+    double a = 0.0, c = 0.0, b = 0.0;
+    if (i < n) {
+      cx += P.x(i);
+      cy += P.y(i);
+      if (i < n - 1)
+        fc_half_plane(P.x(i), P.y(i), P.x(i + 1), P.y(i + 1), P.x(i), P.y(i), a, c, b);     // offset at the edge's first point
+      else
+        fc_half_plane(P.x(n - 1), P.y(n - 1), P.x(0), P.y(0), P.x(0), P.y(0), a, c, b);    // closing edge: at its last point
+      P.x(O + i) = a; P.y(O + i) = c;
+    }
+    out->A[i][0] = a; out->A[i][1] = c; out->B[i] = b;
+  }
+  out->nrows = n;
+  out->pad_ = 0;
+  out->centre[0] = cx / (double)n;
+  out->centre[1] = cy / (double)n;
+  const int half = n == 4 ? 2 : (n == 6 ? 3 : 0);         // FindSimilarConstraints knows rectangles and hexagons
+  for (int k = 0; k < WG_POLY_MAX_ROWS; k++) {
+    int sim = 0;
+    if (k >= half && k < 2 * half && P.x(O + k - half) == -P.x(O + k) && P.y(O + k - half) == -P.y(O + k)) sim = -half;
+    out->similar[k] = sim;
+  }
+  return true;
+}
+
+template <bool kBuild>
+__global__ void __launch_bounds__(64)
+wg_footcons_kernel(FcIn I, FcOut Q, int *__restrict__ cnt /* [chunks][B] */) {
+  __shared__ double fc_lds[kBuild ? kFcSlots * 2 * 64 : 1];
+  const int lane = threadIdx.x, b = blockIdx.x * 64 + lane, chunk = blockIdx.y;
+  if (b >= I.B) return;
+  const size_t sB = (size_t)I.B;
+  const int len = I.length[b], i0 = chunk * kFcChunk;
+  if (len < 0 || len > I.lcap) {                          // a gait wg_zmpdisc_* refused (or a length the arrays cannot hold): the
+    if (!kBuild) {                                        // host call's answer to n < 0
+      cnt[(size_t)chunk * sB + b] = 0;
+      if (chunk == 0) Q.count[b] = WG_ERR_BAD_ARG;
+    }
+    return;
+  }
+  const int n = len - i0 < kFcChunk ? len - i0 : kFcChunk;         // samples of this chunk (<= 0: past the gait's end)
+  int own = 0;
+  if (kBuild) {
+    own = n > 0 ? cnt[(size_t)chunk * sB + b] : 0;
+    if (own == 0 && !(n > 0 && i0 + n == len)) return;    // no change in this chunk, and not the one that closes the queue
+  }
+  // support state of every sample of the chunk, 2 bits each: the loads do not depend on one another
+  unsigned long long code_lo = 0, code_hi = 0;
+  if (!kBuild || own > 0) {
+#pragma unroll 8
+    for (int k = 0; k < kFcChunk; k++) {
+      unsigned long long s = 0;
+      if (k < n) {
+        const size_t i = (size_t)(i0 + k);
+        s = (unsigned long long)fc_classify(I.ltype[i * sB + b], I.left[(i * 6 + 2) * sB + b], I.right[(i * 6 + 2) * sB + b]);
+      }
+      if (k < 32) code_lo |= s << (2 * k);
+      else code_hi |= s << (2 * (k - 32));
+    }
+  }
+  // the state before the chunk: its predecessor's, walking back while that one inherits; sample 0 inherits DOUBLE_SUPPORT
+  int state = kFcDouble;
+  if (n > 0 && i0 > 0 && (!kBuild || own > 0)) {
+    for (int j = i0 - 1; j >= 0; j--) {
+      const size_t i = (size_t)j;
+      const int s = fc_classify(I.ltype[i * sB + b], I.left[(i * 6 + 2) * sB + b], I.right[(i * 6 + 2) * sB + b]);
+      if (s != kFcInherit) { state = s; break; }
+    }
+  }
+  int q = 0;                                              // queue position of this chunk's first change
+  if (kBuild)
+    for (int c = 0; c < chunk; c++) q += cnt[(size_t)c * sB + b];
+  const FcPts P{fc_lds + lane};
+  int found = 0;
+  for (int k = 0; k < n; k++) {
+    if (kBuild && found == own) break;
+    const int s = (int)(((k < 32 ? code_lo >> (2 * k) : code_hi >> (2 * (k - 32)))) & 3);
+    const int next = s == kFcInherit ? state : s;
+    const bool fresh = (i0 + k == 0) || next != state;
+    state = next;
+    if (!fresh) continue;
+    if (kBuild) {
+      const size_t i = (size_t)(i0 + k);
+      const double t = I.time[i];
+      if (q > 0 && q - 1 < Q.qcap) Q.t_end[(size_t)b * Q.qcap + q - 1] = t;
+      if (q < Q.qcap) {
+        const double *L = I.left + i * 6 * sB + b, *R = I.right + i * 6 * sB + b;
+        const double lx = L[0], ly = L[sB], lz = L[2 * sB], lth = L[3 * sB], rx = R[0], ry = R[sB], rz = R[2 * sB], rth = R[3 * sB];
+        int nh = 4;
+        if (state == kFcDouble) {
+          fc_corners(P, 0, lx, ly, lth, I.hw, I.hh);
+          fc_corners(P, 4, rx, ry, rth, I.hw, I.hh);
+          nh = fc_hull8(P);
+        } else if (lz < rz) {
+          fc_corners(P, 0, lx, ly, lth, I.hw, I.hh);
+        } else {
+          fc_corners(P, 0, rx, ry, rth, I.hw, I.hh);
+        }
+        if (!fc_polytope(P, nh, Q.queues + (size_t)b * Q.qcap + q)) atomicMin(Q.count + b, WG_ERR_BAD_ARG);
+        Q.t_start[(size_t)b * Q.qcap + q] = t;
+      }
+      q++;
+    }
+    found++;
+  }
+  if (!kBuild) {
+    cnt[(size_t)chunk * sB + b] = found;
+    if (found) atomicAdd(Q.count + b, found);
+  } else if (n > 0 && i0 + n == len && q > 0 && q - 1 < Q.qcap) {
+    Q.t_end[(size_t)b * Q.qcap + q - 1] = I.time[len - 1];             // the last polytope holds until the last sample
+  }
+}
+
+// ---- the queue walk of one tick ------------------------------------------------------------------------------------------
+// One wave per gait, four to a block.  The first entry whose interval holds t0 is found by all lanes at once (ballot); the walk
+// over the N previewed instants is a chain of N compares on wave-uniform operands, lane i keeps instant i's entry; then the
+// N x 248 bytes are copied as 8-byte words, lane after lane: the stores of a wave are whole lines, the loads 248-byte runs.
+// A gait whose t0 lies in no interval, or whose walk passes its last entry, keeps its LAST polytope (at rest on its final support,
+// the convention of wg_zmpdisc_batch_dev past a gait's length) and is reported in ran_out; no entries: zeros.
+constexpr int kPolyWords = (int)(sizeof(wg_zmp_polytope_t) / 8);
+static_assert(sizeof(wg_zmp_polytope_t) == 248 && kPolyWords * 8 == (int)sizeof(wg_zmp_polytope_t), "wg_zmp_polytope_t: 31 words");
+
+__global__ void __launch_bounds__(256)
+wg_dimitrov_select_kernel(int B, int qcap, const wg_zmp_polytope_t *__restrict__ queues, const double *__restrict__ t_start,
+                          const double *__restrict__ t_end, const int *__restrict__ count, double t0, int N, double T,
+                          wg_zmp_polytope_t *__restrict__ polys, int *ran_out, int sticky) {
+  const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= B) return;
+  const int cb = count[b], k = cb < qcap ? cb : qcap;
+  const double *ts = t_start + (size_t)b * qcap, *te = t_end + (size_t)b * qcap;
+  int q = k, ran = 0, mine = 0;
+  for (int base = 0; base < k && q == k; base += 64) {
+    const int c = base + lane;
+    const bool hit = c < k && ts[c] <= t0 && t0 <= te[c];
+    const unsigned long long m = __ballot(hit);
+    if (m) q = base + __ffsll((long long)m) - 1;
+  }
+  if (k <= 0 || q == k) {
+    ran = 1;
+    mine = k - 1;
+  } else {
+    for (int i = 0; i < N; i++) {
+      if (t0 + i * T > te[q]) {                           // the reference's StartingTime + i * T against EndingTime
+        q++;
+        if (q == k) { q = k - 1; ran = 1; }
+      }
+      if (lane == i) mine = q;
+    }
+  }
+  const unsigned long long *src = reinterpret_cast<const unsigned long long *>(queues + (size_t)b * qcap);
+  unsigned long long *dst = reinterpret_cast<unsigned long long *>(polys + (size_t)b * N);
+  const int words = N * kPolyWords;
+  for (int base = 0; base < words; base += 64) {          // wave-uniform trip count: every lane takes part in the shuffle
+    const int w = base + lane, inst = (w < words ? w : words - 1) / kPolyWords, word = w - inst * kPolyWords;
+    const int e = __shfl(mine, inst);
+    if (w < words) dst[w] = k > 0 ? src[(size_t)e * kPolyWords + word] : 0ull;
+  }
+  if (ran_out && lane == 0 && (ran || !sticky)) ran_out[b] = ran;
+}
+
+}  // namespace wg

@@ -124,6 +124,12 @@ def lib():
         _lib.wg_zmpdisc_full_batch_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + \
             [C.c_void_p] * 10
         _lib.wg_foot_constraints.argtypes = [C.c_int] + [C.c_void_p] * 4 + [C.c_double] * 4 + [C.c_int] + [C.c_void_p] * 3
+        if hasattr(_lib, "wg_foot_constraints_batch_dev"):   # absent from older experiment builds (WG_LIB_PATH, A/B runs)
+            _lib.wg_foot_constraints_batch_dev.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_double] * 4 + [C.c_int] + \
+                [C.c_void_p] * 5
+            _lib.wg_dimitrov_select_polys_dev.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_double] + [C.c_void_p] * 3
+            _lib.wg_dimitrov_walk_dev.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_double, C.c_int] + \
+                [C.c_void_p] * 3 + [C.c_int, C.c_void_p]
         # contexts: NAME_ctx(ctx, args...) for every entry point NAME(args...) that keeps or stages device-side state
         _lib.wg_ctx_create.argtypes = [C.c_int, C.c_void_p]
         _lib.wg_ctx_destroy.argtypes = [C.c_void_p]
@@ -151,7 +157,8 @@ CTX_ENTRY_POINTS = ("wg_set_overlap_strict", "wg_overlap_serialised", "wg_qp_sol
                     "wg_pldp_solve_batch", "wg_pldp_solve_batch_dev", "wg_dimitrov_configure", "wg_dimitrov_get_constants", "wg_dimitrov_get_qld_constants",
                     "wg_dimitrov_tick_batch", "wg_dimitrov_tick_batch_dev", "wg_preview_configure", "wg_preview_window",
                     "wg_preview_run_batch", "wg_preview_run_batch_dev", "wg_gramian_batch", "wg_gramian_batch_dev",
-                    "wg_zmpdisc_batch", "wg_zmpdisc_batch_dev", "wg_zmpdisc_full_batch_dev")
+                    "wg_zmpdisc_batch", "wg_zmpdisc_batch_dev", "wg_zmpdisc_full_batch_dev", "wg_foot_constraints_batch_dev",
+                    "wg_dimitrov_select_polys_dev", "wg_dimitrov_walk_dev")
 
 
 class Context:
@@ -633,6 +640,40 @@ def foot_constraints(time, left, left_type, right, sole_w, sole_h, constraint_x,
     if k > cap:
         raise WgError("foot_constraints: %d polytopes, capacity %d" % (k, cap))
     return polys, ts[:k], te[:k], k
+
+
+# ---- Dimitrov fleets on the device: raw device pointers (ints, e.g. torch tensor.data_ptr()) and a stream ----
+def foot_constraints_chunk():
+    """samples per time chunk of wg_foot_constraints_batch_dev's kernels"""
+    return int(lib().wg_foot_constraints_chunk())
+
+
+def foot_constraints_batch_dev(B, lcap, length_ptr, time_ptr, left_tm_ptr, left_type_tm_ptr, right_tm_ptr, sole_w, sole_h,
+                               constraint_x, constraint_y, qcap, queues_ptr, t_start_ptr, t_end_ptr, count_ptr, stream=None):
+    """wg_foot_constraints for B gaits whose feet wg_zmpdisc_full_batch_dev left on the device: queues / t_start / t_end
+    [B][qcap], count [B]."""
+    _check(lib().wg_foot_constraints_batch_dev(int(B), int(lcap), length_ptr, time_ptr, left_tm_ptr, left_type_tm_ptr,
+                                               right_tm_ptr, float(sole_w), float(sole_h), float(constraint_x),
+                                               float(constraint_y), int(qcap), queues_ptr, t_start_ptr, t_end_ptr, count_ptr,
+                                               stream))
+
+
+def dimitrov_select_polys_dev(B, qcap, queues_ptr, t_start_ptr, t_end_ptr, count_ptr, t0, polys_ptr, ran_out_ptr=None,
+                              stream=None):
+    """the queue walk of one tick: polys [B][N] for wg_dimitrov_tick_batch_dev, ran_out [B] or None"""
+    _check(lib().wg_dimitrov_select_polys_dev(int(B), int(qcap), queues_ptr, t_start_ptr, t_end_ptr, count_ptr, float(t0),
+                                              polys_ptr, ran_out_ptr, stream))
+
+
+def dimitrov_tick_batch_dev(B, polys_ptr, states_ptr, outs_ptr=None, max_iter=0, stream=None):
+    _check(lib().wg_dimitrov_tick_batch_dev(int(B), polys_ptr, states_ptr, outs_ptr, int(max_iter), stream))
+
+
+def dimitrov_walk_dev(B, qcap, queues_ptr, t_start_ptr, t_end_ptr, count_ptr, t0, n_ticks, states_ptr, outs_ptr=None,
+                      ran_out_ptr=None, max_iter=0, stream=None):
+    """n_ticks x { select at t; tick; t += T } on one stream; outs [n_ticks][B] or None, ran_out [B] or None"""
+    _check(lib().wg_dimitrov_walk_dev(int(B), int(qcap), queues_ptr, t_start_ptr, t_end_ptr, count_ptr, float(t0), int(n_ticks),
+                                      states_ptr, outs_ptr, ran_out_ptr, int(max_iter), stream))
 
 
 # ---- invariant Hessian block on the matrix cores ----
