@@ -404,7 +404,13 @@ int wg_riccati_gains(double T, double zc, double Q, double R, int Nl, int mode, 
  *   states   B          hot-start state, read and updated (m_PreviouslyActivatedConstraints, m_PreviousZMPSolution)
  *   X        B x 2N     solution;   ret B: 0, WG_PLDP_NAN (reference returns -1), WG_PLDP_NEG_ALPHA (reference calls
  *                       exit(0)), WG_PLDP_CAPACITY (more than WG_PLDP_ACTIVE_CAP active rows; E E' is singular long
- *                       before that), WG_PLDP_BAD_INPUT (a positive or out-of-range SimilarConstraint offset)
+ *                       before that; or a hot-start row prev_active[i] - n_removed[b] >= m[b], which the reference would
+ *                       index its constraint matrix with: refused like a full factor), WG_PLDP_BAD_INPUT (a positive or
+ *                       out-of-range SimilarConstraint offset).  A hot start refused with WG_PLDP_CAPACITY solves nothing:
+ *                       n_iter = 0, X is the initial solution (ComputeInitialSolution on the state as it came in), the
+ *                       state's n_prev is cleared, its prev_zmp and internal_time stay as they were
+ *                       (WG_PLDP_NAN: a non-finite X[0] or X[N]; the state's members and prev_zmp are stored as the
+ *                       reference stores them before it tests, internal_time does not advance)
  *   n_iter   B          m_ItNb;  active B x mcap / n_active B: m_ActivatedConstraints in activation order (or NULL) */
 #define WG_PLDP_N 16
 #define WG_PLDP_MMAX (8 * WG_PLDP_N)

@@ -141,6 +141,14 @@ static void initial_solution(pldp_work_t *w, const wg_pldp_state_t *st, const do
   }
 }
 
+void wgo_pldp_initial_solution(const wgo_pldp_model_t *M, const wg_pldp_state_t *st, const double *zmpref, const double *xkyk,
+                               int starting, double *X) {
+  static pldp_work_t work;
+  work.M = M;
+  initial_solution(&work, st, zmpref, xkyk, starting);
+  for (int i = 0; i < 2 * M->N; i++) X[i] = work.Vk[i];
+}
+
 /* ComputeProjectedDescentDirection with Forward/BackwardSubstitution, PLDPSolver.cpp:342-532 */
 static void projected_direction(pldp_work_t *w) {
   const int n = 2 * w->M->N, S = w->nact, ld = WG_PLDP_MMAX;

@@ -261,6 +261,14 @@ def pldp_solve(M, st, D, m, A, b, zmpref, xkyk, similar, n_removed, starting, ma
     return dict(ret=rc, X=X, n_iter=nit.value, active=act[:nact.value].copy())
 
 
+def pldp_initial_solution(M, st, zmpref, xkyk, starting):
+    """ComputeInitialSolution alone: where a solve on this state starts (what a refused solve leaves in X)"""
+    X = np.zeros(2 * M.N)
+    oracle().wgo_pldp_initial_solution(C.byref(M), C.byref(st), _d(np.ascontiguousarray(zmpref, dtype=np.float64)),
+                                       _d(np.ascontiguousarray(xkyk, dtype=np.float64)), C.c_int(1 if starting else 0), _d(X))
+    return X
+
+
 # ---- ZMPDiscretization / FootConstraintsAsLinearSystem restatement (oracle/zmpdisc_oracle.c) ----
 def zmpdisc(model, steps, init_feet, n_steps=None, lib=None):
     """wgo_zmpdisc for one gait: dict(zmp [L,2], zmp_theta, zmp_type, left [L,6], left_type, right, right_type, time)."""
