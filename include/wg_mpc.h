@@ -608,6 +608,75 @@ int wg_zmpdisc_full_batch_dev(const wg_zmpdisc_model_t *model, int B, int smax, 
                               double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm,
                               int *right_type_tm, int *length, void *hip_stream);
 
+/* The same walk on line: steps as they arrive --------------------------------------------------------------------------
+ *
+ * The reference's on-line use of ZMPDiscretization -- InitOnLine (:319-513), OnLineAddFoot (:573-1020) per step,
+ * EndPhaseOfTheWalking (:1129-1300) -- for B gaits whose steps are decided while they walk.  wg_zmpdisc_begin_dev runs
+ * InitOnLine on the first n_steps[b] >= 2 steps and writes samples [0, length[b]); every wg_zmpdisc_append_dev runs
+ * OnLineAddFoot on n_steps[b] >= 0 further steps and writes from the gait's sample count on; wg_zmpdisc_end_dev runs
+ * EndPhaseOfTheWalking.  The walk only pushes samples, and its filter reads back into samples already filtered, so a sample
+ * once written is final and begin, any appends, end leave every output byte wg_zmpdisc_full_batch_dev leaves for the
+ * concatenated sequence.  Cost: each step is walked once, however the calls are cut.
+ *   state      B        one wg_zmpdisc_state_t per gait, device memory, written by begin (no need to clear it for begin;
+ *                       append / end on a blob that begin never wrote is only recognised if the memory was zeroed)
+ *   steps      B x smax the steps of THIS call (begin: the walk's first ones; append: the further ones, from index 0),
+ *                       gait b uses the first n_steps[b] <= smax; append: 1 <= smax <= WG_ZMPDISC_MAX_STEPS, and
+ *                       n_steps[b] == 0 means the gait sits the call out: none of its bytes, length[b] included, is touched
+ *   outputs    the layouts of wg_zmpdisc_full_batch_dev (time-major, row stride B), any of them NULL, zmp_x_tm and zmp_y_tm
+ *              together; pass the same set to every call of a walk.  With the queue present the filter's look-back is read
+ *              from the gait's own rows of it (the reference's deque); without, from the tail kept in the state.
+ *   lcap       rows the outputs hold; may grow from call to call (wg_zmpdisc_length_after sizes it)
+ *   length     B, may be NULL: samples of the gait after the call, or a negative code
+ *   select     wg_zmpdisc_end_dev only, B or NULL: gaits with select[b] == 0 sit the call out untouched and walk on; NULL ends
+ *              every gait.  After its end phase a gait's queue rows [length[b], lcap) repeat its last value, the rule of
+ *              wg_zmpdisc_batch_dev.
+ * Errors are per gait and sticky: WG_ZMPDISC_BAD_INPUT (n_steps out of range, a phase that does not fit its own sample count,
+ * append or end on a gait that has ended or never began) or WG_ZMPDISC_CAPACITY (the call's samples do not fit lcap) is
+ * decided before the call's first sample; the call then writes nothing for the gait but the code, to length[b] and to the
+ * state, where every later call finds it and reports it again.  A neighbour never notices.  A walk has no bound on its
+ * number of steps, only zd_length's 2^24 samples.  All three are asynchronous on hip_stream and keep nothing in the context.
+ * These entry points were added without a change of wg_abi_version() (no existing signature changed): a caller that must
+ * run against older libraries detects them by symbol (dlsym) or, at compile time, by WG_ZMPDISC_STATE_BYTES. */
+#define WG_ZMPDISC_TAIL_MAX 52        /* most filter taps a model may have (T >= 1 ms) */
+typedef struct wg_zmpdisc_state {
+  double support[6];                  /* m_CurrentSupportFootPosition rows 0, 1 */
+  double prev_support[2];             /* translation of m_PrevCurrentSupportFootPosition */
+  double prev_rel[2];                 /* m_vdiffsupppre */
+  double ang_support, ang_zmp;        /* m_AngleDiffToSupportFootTheta, m_AngleDiffFromZMPThetaToSupportFootTheta */
+  double left[6], right[6];           /* back() of the feet queues: x, y, z, theta, omega, omega2 */
+  double zmp_last[3];                 /* FinalZMPPositions.back(): px, py, theta */
+  double zmp_first[2];                /* FinalZMPPositions[0] */
+  wg_rel_step_t last_step;            /* m_RelativeFootPositions.front(): the step given last */
+  double tail[WG_ZMPDISC_TAIL_MAX][2];/* the last filtered samples, newest first; kept only while the queue outputs are NULL */
+  int left_type, right_type;          /* stepType of the feet above */
+  int n_samples;                      /* samples written: the walk's clock, in periods T */
+  int n_steps;                        /* steps given */
+  int ended;                          /* EndPhaseOfTheWalking has run */
+  int error;                          /* 0 or the sticky code */
+  int begun, pad_;                    /* set by wg_zmpdisc_begin_dev */
+} wg_zmpdisc_state_t;
+#define WG_ZMPDISC_STATE_BYTES 1144
+#ifdef __cplusplus
+static_assert(sizeof(wg_zmpdisc_state_t) == WG_ZMPDISC_STATE_BYTES, "wg_zmpdisc_state_t is part of the ABI");
+#else
+_Static_assert(sizeof(wg_zmpdisc_state_t) == WG_ZMPDISC_STATE_BYTES, "wg_zmpdisc_state_t is part of the ABI");
+#endif
+/* samples of a walk after the first n_steps >= 2 steps of a sequence, and after its end phase if `ended`: the prefix sums
+ * of wg_zmpdisc_length (host arithmetic; ended != 0 and n_steps <= WG_ZMPDISC_MAX_STEPS: wg_zmpdisc_length itself), or a
+ * negative code */
+int wg_zmpdisc_length_after(const wg_zmpdisc_model_t *model, const wg_rel_step_t *steps, int n_steps, int ended);
+int wg_zmpdisc_begin_dev(const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps,
+                         const double *init_feet, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm,
+                         int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm,
+                         wg_zmpdisc_state_t *state, int *length, void *hip_stream);
+int wg_zmpdisc_append_dev(const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps,
+                          int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm,
+                          double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm,
+                          wg_zmpdisc_state_t *state, int *length, void *hip_stream);
+int wg_zmpdisc_end_dev(const wg_zmpdisc_model_t *model, int B, const int *select, int lcap, double *zmp_x_tm,
+                       double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm,
+                       double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream);
+
 /* ZMP polytopes of a feet trajectory ----------------------------------------------------------------------------------
  *
  * wg_foot_constraints replaces FootConstraintsAsLinearSystem::BuildLinearConstraintInequalities
@@ -760,6 +829,18 @@ int wg_zmpdisc_full_batch_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_model_t *model
 int wg_zmpdisc_batch_ctx(wg_ctx_t *ctx, const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps,
                          const int *n_steps, const double *init_feet, int lcap, double *zmp, double *zmp_theta,
                          int *zmp_type, double *left, int *left_type, double *right, int *right_type, int *length);
+int wg_zmpdisc_begin_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps,
+                             const int *n_steps, const double *init_feet, int lcap, double *zmp_x_tm, double *zmp_y_tm,
+                             double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm,
+                             int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream);
+int wg_zmpdisc_append_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps,
+                              const int *n_steps, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm,
+                              int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm,
+                              wg_zmpdisc_state_t *state, int *length, void *hip_stream);
+int wg_zmpdisc_end_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_model_t *model, int B, const int *select, int lcap,
+                           double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm,
+                           int *left_type_tm, double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length,
+                           void *hip_stream);
 
 #ifdef __cplusplus
 }

@@ -1550,6 +1550,29 @@ int zd_launch(const wg::ZdConst &K, int B, int smax, const wg_rel_step_t *steps,
   HIP_TRY(hipGetLastError());
   return WG_OK;
 }
+
+// begin / append / end of an on-line walk: the checks they share, then one launch of the resumable kernel
+int zd_online(wg_ctx *ctx, int op, const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps,
+              const double *init_feet, const int *select, int lcap, const wg::ZdOut &O, wg_zmpdisc_state_t *state, int *length,
+              void *hip_stream) {
+  wg::ZdConst K;
+  if (int rc = use_ctx(ctx)) return rc;
+  if (int rc = zd_make_const(model, &K)) return rc;
+  const int smin = op == wg::ZD_OP_BEGIN ? 2 : 1;
+  const bool steps_ok = op == wg::ZD_OP_END || (steps && n_steps && smax >= smin && smax <= WG_ZMPDISC_MAX_STEPS);
+  if (B < 0 || lcap < 1 || !state || !steps_ok || (op == wg::ZD_OP_BEGIN && !init_feet))
+    return fail(WG_ERR_BAD_ARG, "need B >= 0, %d <= smax <= %d, lcap >= 1, non-null inputs and state", smin, WG_ZMPDISC_MAX_STEPS);
+  if ((O.zx == nullptr) != (O.zy == nullptr)) return fail(WG_ERR_BAD_ARG, "zmp_x_tm and zmp_y_tm go together");
+  if (B == 0) return WG_OK;
+  const size_t lds = (size_t)K.nwin * 3 * 2 * 64 * 8;
+  if (lds > 64 * 1024)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(wg::wg_zmpdisc_online_kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(wg::wg_zmpdisc_online_kernel, dim3((B + 63) / 64), dim3(64), lds, reinterpret_cast<hipStream_t>(hip_stream),
+                     K, op, B, smax, steps, n_steps, init_feet, select, lcap, O, state, length);
+  HIP_TRY(hipGetLastError());
+  return WG_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1591,6 +1614,26 @@ int wg_zmpdisc_full_batch_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_model_t *model
   O.zx = zmp_x_tm; O.zy = zmp_y_tm; O.ztheta = zmp_theta_tm; O.ztype = zmp_type_tm;
   O.left = left_tm; O.ltype = left_type_tm; O.right = right_tm; O.rtype = right_type_tm;
   return zd_launch(K, B, smax, steps, n_steps, init_feet, lcap, O, length, reinterpret_cast<hipStream_t>(hip_stream));
+}
+
+int wg_zmpdisc_length_after(const wg_zmpdisc_model_t *model, const wg_rel_step_t *steps, int n_steps, int ended) {
+  if (!model || !steps) return WG_ZMPDISC_BAD_INPUT;
+  return wg::zd_length_after(*model, steps, n_steps, ended);
+}
+
+int wg_zmpdisc_begin_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream) {
+  const wg::ZdOut O{zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, right_tm, left_type_tm, right_type_tm};
+  return zd_online(ctx, wg::ZD_OP_BEGIN, model, B, smax, steps, n_steps, init_feet, nullptr, lcap, O, state, length, hip_stream);
+}
+
+int wg_zmpdisc_append_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream) {
+  const wg::ZdOut O{zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, right_tm, left_type_tm, right_type_tm};
+  return zd_online(ctx, wg::ZD_OP_APPEND, model, B, smax, steps, n_steps, nullptr, nullptr, lcap, O, state, length, hip_stream);
+}
+
+int wg_zmpdisc_end_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_model_t *model, int B, const int *select, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream) {
+  const wg::ZdOut O{zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, right_tm, left_type_tm, right_type_tm};
+  return zd_online(ctx, wg::ZD_OP_END, model, B, 0, nullptr, nullptr, nullptr, select, lcap, O, state, length, hip_stream);
 }
 
 int wg_zmpdisc_batch_ctx(wg_ctx_t *ctx, const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap, double *zmp, double *zmp_theta, int *zmp_type, double *left, int *left_type, double *right, int *right_type, int *length) {
@@ -1702,6 +1745,9 @@ int wg_gramian_batch_dev(int B, int N, const double *T, const double *h, double 
 int wg_gramian_batch(int B, int N, const double *T, const double *h, double alpha, double beta, double gamma, int precision, double *Qb) { return on_default(&wg_gramian_batch_ctx, B, N, T, h, alpha, beta, gamma, precision, Qb); }
 int wg_zmpdisc_batch_dev(const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap, double *zmp_x_tm, double *zmp_y_tm, int *length, void *hip_stream) { return on_default(&wg_zmpdisc_batch_dev_ctx, model, B, smax, steps, n_steps, init_feet, lcap, zmp_x_tm, zmp_y_tm, length, hip_stream); }
 int wg_zmpdisc_full_batch_dev(const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream) { return on_default(&wg_zmpdisc_full_batch_dev_ctx, model, B, smax, steps, n_steps, init_feet, lcap, zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, left_type_tm, right_tm, right_type_tm, length, hip_stream); }
+int wg_zmpdisc_begin_dev(const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream) { return on_default(&wg_zmpdisc_begin_dev_ctx, model, B, smax, steps, n_steps, init_feet, lcap, zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, left_type_tm, right_tm, right_type_tm, state, length, hip_stream); }
+int wg_zmpdisc_append_dev(const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream) { return on_default(&wg_zmpdisc_append_dev_ctx, model, B, smax, steps, n_steps, lcap, zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, left_type_tm, right_tm, right_type_tm, state, length, hip_stream); }
+int wg_zmpdisc_end_dev(const wg_zmpdisc_model_t *model, int B, const int *select, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream) { return on_default(&wg_zmpdisc_end_dev_ctx, model, B, select, lcap, zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, left_type_tm, right_tm, right_type_tm, state, length, hip_stream); }
 int wg_zmpdisc_batch(const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap, double *zmp, double *zmp_theta, int *zmp_type, double *left, int *left_type, double *right, int *right_type, int *length) { return on_default(&wg_zmpdisc_batch_ctx, model, B, smax, steps, n_steps, init_feet, lcap, zmp, zmp_theta, zmp_type, left, left_type, right, right_type, length); }
 
 }  // extern "C"

@@ -15,6 +15,15 @@
 // Per lane the last nwin unfiltered and 2 nwin filtered samples live in LDS rings laid out [slot][axis][lane]
 // (lane-contiguous: conflict-free).  Operation order follows the oracle restatement (oracle/zmpdisc_oracle.c) line by
 // line; sin / cos come from include/wg_trig.h like in the tick kernel.
+//
+// The walk is one function template, zd_walk<RES>.  RES = false is the whole-sequence kernel (InitOnLine, every
+// OnLineAddFoot, EndPhaseOfTheWalking in one launch; nothing kept).  RES = true is the on-line form of the reference's public
+// API: one launch runs InitOnLine + some steps (ZD_OP_BEGIN), some more OnLineAddFoot (ZD_OP_APPEND) or
+// EndPhaseOfTheWalking (ZD_OP_END) and carries what the walk keeps between phases in a wg_zmpdisc_state_t per gait.  The
+// walk only ever pushes samples and FilterOutValues reads at most nwin filtered samples back, so a resumed launch refills
+// the filtered ring from the gait's own rows of zmp_x_tm / zmp_y_tm (the reference's deque) -- or, when the caller does not
+// ask for the queue, from the tail the previous launch left in the state.  Everything resumable sits under
+// `if constexpr (RES)`: the whole-sequence instantiation carries none of it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -28,6 +37,7 @@ namespace wg {
 
 #define WG_ZD_WIN_MAX 52                 // (nwin + 2 nwin) x 2 axes x 64 lanes x 8 B = 3 KB x nwin <= 160 KB
 #define WG_ZD_PI 3.14159265358979323846
+static_assert(WG_ZD_WIN_MAX <= WG_ZMPDISC_TAIL_MAX, "wg_zmpdisc_state_t::tail holds one filter window");
 
 constexpr int kZdWinStd = 11;            // floor(0.05 / T) + 1 taps at the reference's T = 5 ms (ZMPDiscretization.cpp:240-262)
 struct ZdConst {
@@ -121,6 +131,55 @@ __host__ __device__ inline int zd_length(const wg_zmpdisc_model_t &M, const wg_r
   return n > (1 << 24) ? WG_ZMPDISC_BAD_INPUT : (int)n;
 }
 
+// host + device: samples of the phases, one by one (the terms of zd_length's sum), or a negative code
+__host__ __device__ inline int zd_init_samples(const wg_zmpdisc_model_t &M) {
+  if (!(M.T > 0)) return WG_ZMPDISC_BAD_INPUT;
+  const int n = (int)(2 * M.preview_time / M.T);
+  return n < 3 || n > (1 << 24) ? WG_ZMPDISC_BAD_INPUT : n;
+}
+__host__ __device__ inline int zd_step_samples(const wg_zmpdisc_model_t &M, const wg_rel_step_t &s) {
+  double d = M.t_double, ss = M.t_single;
+  if (s.ds_time != 0.0) {
+    d = s.ds_time;
+    ss = s.ss_time;
+  }
+  const double a = round((d + ss) / M.T), a1 = round(d / M.T), a2 = round(ss / M.T);
+  if (!(a >= 1.0 && a < 1048576.0) || a1 < 1.0 || a1 + a2 > a) return WG_ZMPDISC_BAD_INPUT;
+  return (int)a;
+}
+__host__ __device__ inline int zd_end_samples(const wg_zmpdisc_model_t &M) {
+  const double e = round(M.t_double / (2 * M.T)), r = 3.0 * M.preview_time / M.T;
+  if (!(e >= 1.0 && e < 1048576.0) || !(r >= 0.0 && r < 16777216.0)) return WG_ZMPDISC_BAD_INPUT;
+  return (int)e + (int)r;
+}
+// samples `n` further steps add to a walk that holds `have`, or a negative code; the total stays within zd_length's 2^24
+__host__ __device__ inline int zd_steps_samples(const wg_zmpdisc_model_t &M, const wg_rel_step_t *steps, int n, int have) {
+  long long tot = have;
+  for (int i = 0; i < n; i++) {
+    const int a = zd_step_samples(M, steps[i]);
+    if (a < 0) return a;
+    tot += a;
+    if (tot > (1 << 24)) return WG_ZMPDISC_BAD_INPUT;
+  }
+  return (int)(tot - have);
+}
+// samples after the first n_steps >= 2 steps of a sequence (InitOnLine on them), and after EndPhaseOfTheWalking if `ended`:
+// the prefix sums of zd_length.  An on-line walk has no bound on its number of steps, only on its samples.
+__host__ __device__ inline int zd_length_after(const wg_zmpdisc_model_t &M, const wg_rel_step_t *steps, int n_steps, int ended) {
+  if (n_steps < 2) return WG_ZMPDISC_BAD_INPUT;
+  const int n0 = zd_init_samples(M);
+  if (n0 < 0) return n0;
+  const int ns = zd_steps_samples(M, steps + 1, n_steps - 1, n0);
+  if (ns < 0) return ns;
+  long long n = (long long)n0 + ns;
+  if (ended) {
+    const int e = zd_end_samples(M);
+    if (e < 0) return e;
+    n += e;
+  }
+  return n > (1 << 24) ? WG_ZMPDISC_BAD_INPUT : (int)n;
+}
+
 // per-lane view of the two LDS rings
 struct ZdRings {
   double *z, *f;      // base of this lane's column in the unfiltered / filtered ring
@@ -133,9 +192,18 @@ struct ZdRings {
 // generated; the filter / output loop is common.
 enum { ZD_INIT = 0, ZD_STEP = 1, ZD_END = 2 };
 
-__global__ void __launch_bounds__(64)
-wg_zmpdisc_kernel(ZdConst K, int B, int smax, const wg_rel_step_t *__restrict__ steps, const int *__restrict__ n_steps,
-                  const double *__restrict__ init_feet, int lcap, ZdOut O, int *__restrict__ length) {
+// what a resumable launch does (the reference's three on-line entry points)
+enum { ZD_OP_BEGIN = 0, ZD_OP_APPEND = 1, ZD_OP_END = 2 };
+#define WG_ZD_STATE_MAGIC 0x5a4d5044     // wg_zmpdisc_state_t::begun once InitOnLine has run on it
+
+// RES = false: `op`, `select` and `state` are unused.  RES = true: `steps` holds only the steps of this launch (ZD_OP_BEGIN:
+// the first n_steps[g] >= 2 of the walk; ZD_OP_APPEND: n_steps[g] >= 0 further ones), `select` (ZD_OP_END, may be NULL)
+// names the gaits that end.  A gait that sits a launch out (0 steps, not selected) returns before it touches anything.
+template <bool RES>
+__device__ __forceinline__ void zd_walk(const ZdConst &K, int op, int B, int smax, const wg_rel_step_t *__restrict__ steps,
+                                        const int *__restrict__ n_steps, const double *__restrict__ init_feet,
+                                        const int *__restrict__ select, int lcap, const ZdOut &O,
+                                        wg_zmpdisc_state_t *__restrict__ state, int *__restrict__ length) {
   extern __shared__ __attribute__((aligned(16))) double zd_lds[];
   const int lane = threadIdx.x;
   const int g = blockIdx.x * 64 + lane;
@@ -143,11 +211,49 @@ wg_zmpdisc_kernel(ZdConst K, int B, int smax, const wg_rel_step_t *__restrict__ 
   const wg_zmpdisc_model_t &M = K.M;
   const size_t sB = (size_t)B;
   const wg_rel_step_t *st = steps + (size_t)g * smax;
-  const int S = n_steps[g];
-  int Ltot = (S <= smax) ? zd_length(M, st, S) : WG_ZMPDISC_BAD_INPUT;
-  if (Ltot > lcap) Ltot = WG_ZMPDISC_CAPACITY;
-  if (length) length[g] = Ltot;
-  if (Ltot < 0) return;
+  int S = 0;                                        // RES = false / ZD_OP_BEGIN: steps of the sequence, the first one included
+  int nz0 = 0;                                      // RES: samples the walk holds when this launch starts
+  wg_zmpdisc_state_t *sp = nullptr;
+  if constexpr (!RES) {
+    S = n_steps[g];
+    int Ltot = (S <= smax) ? zd_length(M, st, S) : WG_ZMPDISC_BAD_INPUT;
+    if (Ltot > lcap) Ltot = WG_ZMPDISC_CAPACITY;
+    if (length) length[g] = Ltot;
+    if (Ltot < 0) return;
+  } else {
+    // every refusal is decided here, before the first sample: a refused launch writes the code and nothing else
+    sp = state + g;
+    int code;
+    if (op == ZD_OP_BEGIN) {
+      S = n_steps[g];
+      code = (S >= 2 && S <= smax) ? zd_length_after(M, st, S, 0) : WG_ZMPDISC_BAD_INPUT;
+      if (code > lcap) code = WG_ZMPDISC_CAPACITY;
+      if (code < 0) {
+        sp->begun = WG_ZD_STATE_MAGIC; sp->error = code; sp->ended = 0; sp->n_samples = 0; sp->n_steps = 0;
+      }
+    } else {
+      S = op == ZD_OP_APPEND ? n_steps[g] : (select ? (select[g] != 0) : 1);
+      if (S == 0) return;
+      const bool begun = sp->begun == WG_ZD_STATE_MAGIC;
+      code = !begun ? WG_ZMPDISC_BAD_INPUT : sp->error;
+      if (code == 0 && sp->ended) code = WG_ZMPDISC_BAD_INPUT;
+      if (code == 0) {
+        nz0 = sp->n_samples;
+        if (op == ZD_OP_END) {
+          code = zd_end_samples(M);
+          if (code >= 0 && (long long)nz0 + code > (1 << 24)) code = WG_ZMPDISC_BAD_INPUT;
+        } else {
+          code = (S > 0 && S <= smax) ? zd_steps_samples(M, st, S, nz0) : WG_ZMPDISC_BAD_INPUT;
+        }
+        if (code >= 0 && nz0 + code > lcap) code = WG_ZMPDISC_CAPACITY;
+      }
+      if (code < 0) sp->error = code;
+    }
+    if (code < 0) {
+      if (length) length[g] = code;
+      return;
+    }
+  }
 
   const bool want_feet = O.left || O.right || O.ltype || O.rtype;   // otherwise only each phase's last sample is evaluated
   ZdRings R;
@@ -161,11 +267,15 @@ wg_zmpdisc_kernel(ZdConst K, int B, int smax, const wg_rel_step_t *__restrict__ 
   double p02 = 0.0, p12 = 0.0;                                               // translation of m_PrevCurrentSupportFootPosition
   double vpre0, vpre1, ang_support, ang_zmp;
   ZdFoot cl, cr;                                                             // back() of the final feet deques
+  wg_rel_step_t rel0;
+  const bool fresh = !RES || op == ZD_OP_BEGIN;                              // otherwise all of this comes from the state below
+  if (fresh) {
   cl.x = init_feet[(size_t)g * 6 + 0]; cl.y = init_feet[(size_t)g * 6 + 1]; cl.theta = init_feet[(size_t)g * 6 + 2];
   cr.x = init_feet[(size_t)g * 6 + 3]; cr.y = init_feet[(size_t)g * 6 + 4]; cr.theta = init_feet[(size_t)g * 6 + 5];
   cl.z = cl.omega = cl.omega2 = 0.0; cr.z = cr.omega = cr.omega2 = 0.0;
   cl.type = cr.type = 0;
-  wg_rel_step_t rel0 = st[0];
+  rel0 = st[0];
+  }
   double bpx = 0.0, bpy = 0.0, btheta = 0.0;        // FinalZMPPositions.back()
   double f0x = 0.0, f0y = 0.0;                      // FinalZMPPositions[0]
   int nz = 0;                                       // FinalZMPPositions.size()
@@ -214,15 +324,50 @@ wg_zmpdisc_kernel(ZdConst K, int B, int smax, const wg_rel_step_t *__restrict__ 
     if (tbase) tbase[l * sB + g] = f.type;
   };
 
-  {
+  if (fresh) {
     int who;
     bookkeeping((cr.theta + cl.theta) / 2.0, who);
   }
 
   // ---- phases -----------------------------------------------------------------------------------------------------------
-  const int n_phases = S + 1;                       // rest, S - 1 steps, end
-  for (int ph = 0; ph < n_phases; ph++) {
-    const int kind = ph == 0 ? ZD_INIT : (ph == n_phases - 1 ? ZD_END : ZD_STEP);
+  // phase ph is the rest (ph == 0), the end (ph == ph_end) or OnLineAddFoot on st[ph - st_off]
+  int ph_first = 0, ph_stop = S + 1, ph_end = S;    // rest, S - 1 steps, end
+  int st_off = 0;
+  if constexpr (RES) {
+    if (op == ZD_OP_BEGIN) {
+      ph_end = -1; ph_stop = S;                     // rest, S - 1 steps
+    } else {
+      // the walk so far: what the phases above leave behind, and the filter's look-back
+      s00 = sp->support[0]; s01 = sp->support[1]; s02 = sp->support[2];
+      s10 = sp->support[3]; s11 = sp->support[4]; s12 = sp->support[5];
+      p02 = sp->prev_support[0]; p12 = sp->prev_support[1];
+      vpre0 = sp->prev_rel[0]; vpre1 = sp->prev_rel[1];
+      ang_support = sp->ang_support; ang_zmp = sp->ang_zmp;
+      cl.x = sp->left[0]; cl.y = sp->left[1]; cl.z = sp->left[2]; cl.theta = sp->left[3]; cl.omega = sp->left[4]; cl.omega2 = sp->left[5];
+      cr.x = sp->right[0]; cr.y = sp->right[1]; cr.z = sp->right[2]; cr.theta = sp->right[3]; cr.omega = sp->right[4]; cr.omega2 = sp->right[5];
+      cl.type = sp->left_type; cr.type = sp->right_type;
+      rel0 = sp->last_step;
+      bpx = sp->zmp_last[0]; bpy = sp->zmp_last[1]; btheta = sp->zmp_last[2];
+      f0x = sp->zmp_first[0]; f0y = sp->zmp_first[1];
+      nz = nz0;
+      fslot = nz % R.nf;
+      const int back = nz < R.nwin ? nz : R.nwin;   // FilterOutValues reads no further back than its window
+      int slot = fslot;
+      for (int k = 0; k < back; k++) {              // k-th sample before the next one
+        slot = slot == 0 ? R.nf - 1 : slot - 1;
+        const size_t l = (size_t)(nz - 1 - k);
+        R.F(slot, 0) = O.zx ? O.zx[l * sB + g] : sp->tail[k][0];
+        R.F(slot, 1) = O.zx ? O.zy[l * sB + g] : sp->tail[k][1];
+      }
+      if (op == ZD_OP_APPEND) {
+        st_off = 1; ph_first = 1; ph_stop = S + 1; ph_end = -1;   // OnLineAddFoot on steps[0 .. S)
+      } else {
+        ph_first = 1; ph_stop = 2; ph_end = 1;
+      }
+    }
+  }
+  for (int ph = ph_first; ph < ph_stop; ph++) {
+    const int kind = ph == 0 ? ZD_INIT : (ph == ph_end ? ZD_END : ZD_STEP);
     int nZ, n1 = 0, n2 = 0, t1 = 0, who = 1, n_end = 0;
     double px0 = 0, py0 = 0, theta0 = 0, dx = 0, dy = 0, w0 = 0, w1 = 0, mod_sst = 0, fin0 = 0, fin1 = 0;
     int type_ss = 0;
@@ -233,7 +378,7 @@ wg_zmpdisc_kernel(ZdConst K, int B, int smax, const wg_rel_step_t *__restrict__ 
       fin0 = M.zmp_neutral[0]; fin1 = M.zmp_neutral[1];
       dsl.type = dsr.type = 10;
     } else if (kind == ZD_STEP) {
-      const wg_rel_step_t rel1 = st[ph];
+      const wg_rel_step_t rel1 = st[ph - st_off];
       double lTdble = M.t_double, lTsingle = M.t_single;
       if (rel1.ds_time != 0.0) {
         lTdble = rel1.ds_time;
@@ -459,11 +604,54 @@ wg_zmpdisc_kernel(ZdConst K, int B, int smax, const wg_rel_step_t *__restrict__ 
       nz++;
     }
   }
+  if constexpr (RES) {
+    sp->support[0] = s00; sp->support[1] = s01; sp->support[2] = s02;
+    sp->support[3] = s10; sp->support[4] = s11; sp->support[5] = s12;
+    sp->prev_support[0] = p02; sp->prev_support[1] = p12;
+    sp->prev_rel[0] = vpre0; sp->prev_rel[1] = vpre1;
+    sp->ang_support = ang_support; sp->ang_zmp = ang_zmp;
+    sp->left[0] = cl.x; sp->left[1] = cl.y; sp->left[2] = cl.z; sp->left[3] = cl.theta; sp->left[4] = cl.omega; sp->left[5] = cl.omega2;
+    sp->right[0] = cr.x; sp->right[1] = cr.y; sp->right[2] = cr.z; sp->right[3] = cr.theta; sp->right[4] = cr.omega; sp->right[5] = cr.omega2;
+    sp->left_type = cl.type; sp->right_type = cr.type;
+    sp->last_step = rel0;
+    sp->zmp_last[0] = bpx; sp->zmp_last[1] = bpy; sp->zmp_last[2] = btheta;
+    sp->zmp_first[0] = f0x; sp->zmp_first[1] = f0y;
+    if (!O.zx) {                                    // no queue to read the look-back from next time
+      const int back = nz < R.nwin ? nz : R.nwin;
+      int slot = fslot;
+      for (int k = 0; k < back; k++) {
+        slot = slot == 0 ? R.nf - 1 : slot - 1;
+        sp->tail[k][0] = R.F(slot, 0); sp->tail[k][1] = R.F(slot, 1);
+      }
+    }
+    sp->n_samples = nz;
+    sp->n_steps = op == ZD_OP_BEGIN ? S : sp->n_steps + (op == ZD_OP_APPEND ? S : 0);
+    sp->ended = op == ZD_OP_END;
+    sp->error = 0;
+    sp->begun = WG_ZD_STATE_MAGIC;
+    if (length) length[g] = nz;
+    if (op != ZD_OP_END) return;
+  }
   // a gait at rest after its last sample: lets one preview launch cover a ragged batch
   for (size_t l = (size_t)nz; l < (size_t)lcap; l++) {
     if (O.zx) O.zx[l * sB + g] = bpx;
     if (O.zy) O.zy[l * sB + g] = bpy;
   }
+}
+
+__global__ void __launch_bounds__(64)
+wg_zmpdisc_kernel(ZdConst K, int B, int smax, const wg_rel_step_t *__restrict__ steps, const int *__restrict__ n_steps,
+                  const double *__restrict__ init_feet, int lcap, ZdOut O, int *__restrict__ length) {
+  zd_walk<false>(K, 0, B, smax, steps, n_steps, init_feet, nullptr, lcap, O, nullptr, length);
+}
+
+// BEGIN / APPEND / END of an on-line walk; `state` [B], one blob per gait
+__global__ void __launch_bounds__(64)
+wg_zmpdisc_online_kernel(ZdConst K, int op, int B, int smax, const wg_rel_step_t *__restrict__ steps,
+                         const int *__restrict__ n_steps, const double *__restrict__ init_feet,
+                         const int *__restrict__ select, int lcap, ZdOut O, wg_zmpdisc_state_t *__restrict__ state,
+                         int *__restrict__ length) {
+  zd_walk<true>(K, op, B, smax, steps, n_steps, init_feet, select, lcap, O, state, length);
 }
 
 }  // namespace wg

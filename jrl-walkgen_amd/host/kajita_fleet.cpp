@@ -3,7 +3,12 @@
 // nothing leaves the device in between.  Gait 0 walks TestKajita2003's StraightWalking sequence and is checked against
 // the host-pointer entry points on the same input (bit for bit); the others vary step length and heading.
 //
-//   kajita_fleet [--batch B] [--steps S]
+// With --online K the same walks are fed K steps per call instead: wg_zmpdisc_begin_dev on the first two steps, then
+// { wg_zmpdisc_append_dev on the next K; wg_preview_run_batch_dev on the rows that became safe } until the steps run out,
+// wg_zmpdisc_end_dev and the remaining rows.  Every step is walked once, and the CoM trajectories -- hence the checksum
+// (FNV-1a, 64 bit, over all of them) that both modes print -- are those of the whole-sequence mode.
+//
+//   kajita_fleet [--batch B] [--steps S] [--online K]
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -19,10 +24,11 @@
 #define CHECK_WG(e) do { int r_ = (e); if (r_ != WG_OK) { fprintf(stderr, "FAILED: %s: %s\n", #e, wg_last_error()); return 1; } } while (0)
 
 int main(int argc, char **argv) {
-  int B = 4096, S = 16;
+  int B = 4096, S = 16, K = 0;
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--batch") && i + 1 < argc) B = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--steps") && i + 1 < argc) S = atoi(argv[++i]);
+    else if (!strcmp(argv[i], "--online") && i + 1 < argc) { K = atoi(argv[++i]); if (K < 1 || K > WG_ZMPDISC_MAX_STEPS) { fprintf(stderr, "FAILED: need 1 <= --online K <= %d\n", WG_ZMPDISC_MAX_STEPS); return 1; } }
   }
   if (B < 1 || S < 2 || S > WG_ZMPDISC_MAX_STEPS) { fprintf(stderr, "FAILED: need B >= 1, 2 <= steps <= %d\n", WG_ZMPDISC_MAX_STEPS); return 1; }
   CHECK_WG(wg_init(0));
@@ -72,6 +78,27 @@ int main(int argc, char **argv) {
   CHECK_HIP(hipMemcpy(d_steps, steps.data(), sizeof(wg_rel_step_t) * steps.size(), hipMemcpyHostToDevice));
   CHECK_HIP(hipMemcpy(d_ns, n_steps.data(), sizeof(int) * B, hipMemcpyHostToDevice));
   CHECK_HIP(hipMemcpy(d_feet, feet.data(), sizeof(double) * feet.size(), hipMemcpyHostToDevice));
+  // --online: the walk's state blobs, and the steps after the first two regrouped call by call, [call][B][K]
+  const int n_calls = K ? (S - 2 + K - 1) / K : 0;
+  wg_zmpdisc_state_t *d_walk = nullptr; wg_rel_step_t *d_chunks = nullptr; int *d_cns = nullptr;
+  if (K) {
+    std::vector<wg_rel_step_t> chunks((size_t)n_calls * B * K);
+    std::vector<int> cns((size_t)n_calls * B);
+    memset(chunks.data(), 0, sizeof(wg_rel_step_t) * chunks.size());
+    for (int c = 0; c < n_calls; ++c)
+      for (int g = 0; g < B; ++g) {
+        const int first = 2 + c * K, n = S - first < K ? S - first : K;
+        cns[(size_t)c * B + g] = n;
+        for (int i = 0; i < n; ++i) chunks[((size_t)c * B + g) * K + i] = steps[(size_t)g * S + first + i];
+      }
+    CHECK_HIP(hipMalloc((void **)&d_walk, sizeof(wg_zmpdisc_state_t) * B));
+    CHECK_HIP(hipMalloc((void **)&d_chunks, sizeof(wg_rel_step_t) * (chunks.size() ? chunks.size() : 1)));
+    CHECK_HIP(hipMalloc((void **)&d_cns, sizeof(int) * (cns.size() ? cns.size() : 1)));
+    CHECK_HIP(hipMemcpy(d_chunks, chunks.data(), sizeof(wg_rel_step_t) * chunks.size(), hipMemcpyHostToDevice));
+    CHECK_HIP(hipMemcpy(d_cns, cns.data(), sizeof(int) * cns.size(), hipMemcpyHostToDevice));
+    std::vector<int> two(B, 2);
+    CHECK_HIP(hipMemcpy(d_ns, two.data(), sizeof(int) * B, hipMemcpyHostToDevice));
+  }
   hipStream_t st;
   CHECK_HIP(hipStreamCreate(&st));
   double sec = 0.0;
@@ -79,10 +106,44 @@ int main(int argc, char **argv) {
     CHECK_HIP(hipMemsetAsync(d_state, 0, sizeof(double) * 8 * B, st));
     CHECK_HIP(hipStreamSynchronize(st));
     const auto t0 = std::chrono::steady_clock::now();
-    CHECK_WG(wg_zmpdisc_batch_dev(&zm, B, S, d_steps, d_ns, d_feet, L, d_zx, d_zy, d_len, st));
-    CHECK_WG(wg_preview_run_batch_dev(B, Lrun, d_zx, d_zy, d_state, d_com, nullptr, 1, st));
+    if (!K) {
+      CHECK_WG(wg_zmpdisc_batch_dev(&zm, B, S, d_steps, d_ns, d_feet, L, d_zx, d_zy, d_len, st));
+      CHECK_WG(wg_preview_run_batch_dev(B, Lrun, d_zx, d_zy, d_state, d_com, nullptr, 1, st));
+    } else {
+      // every gait has the same support times, hence the same sample count after each call: the host knows it without
+      // reading `length` back.  Rows [done, done + n) are safe once the queue holds done + n + nl - 1 samples.
+      int done = 0;
+      auto preview_upto = [&](int have) -> int {
+        const int n = have - nl + 1 - done;
+        if (n <= 0) return WG_OK;
+        const int rc = wg_preview_run_batch_dev(B, n, d_zx + (size_t)done * B, d_zy + (size_t)done * B, d_state,
+                                                d_com + (size_t)done * 6 * B, nullptr, 1, st);
+        done += n;
+        return rc;
+      };
+      CHECK_WG(wg_zmpdisc_begin_dev(&zm, B, S, d_steps, d_ns, d_feet, L, d_zx, d_zy, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                    nullptr, d_walk, d_len, st));
+      CHECK_WG(preview_upto(wg_zmpdisc_length_after(&zm, steps.data(), 2, 0)));
+      for (int c = 0; c < n_calls; ++c) {
+        CHECK_WG(wg_zmpdisc_append_dev(&zm, B, K, d_chunks + (size_t)c * B * K, d_cns + (size_t)c * B, L, d_zx, d_zy, nullptr,
+                                       nullptr, nullptr, nullptr, nullptr, nullptr, d_walk, d_len, st));
+        const int upto = 2 + (c + 1) * K < S ? 2 + (c + 1) * K : S;
+        CHECK_WG(preview_upto(wg_zmpdisc_length_after(&zm, steps.data(), upto, 0)));
+      }
+      CHECK_WG(wg_zmpdisc_end_dev(&zm, B, nullptr, L, d_zx, d_zy, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, d_walk,
+                                  d_len, st));
+      CHECK_WG(preview_upto(L));
+      if (done != Lrun) { fprintf(stderr, "FAILED: previewed %d rows of %d\n", done, Lrun); return 1; }
+    }
     CHECK_HIP(hipStreamSynchronize(st));
     sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  }
+  if (K) {                                                     // every gait must have arrived at the whole sequence's length
+    std::vector<int> len_h(B);
+    CHECK_HIP(hipMemcpy(len_h.data(), d_len, sizeof(int) * B, hipMemcpyDeviceToHost));
+    for (int g = 0; g < B; ++g)
+      if (len_h[g] != L) { fprintf(stderr, "FAILED: gait %d ended with length %d, not %d\n", g, len_h[g], L); return 1; }
+    CHECK_HIP(hipMemcpy(d_ns, n_steps.data(), sizeof(int) * B, hipMemcpyHostToDevice));
   }
   // gait 0 against the host-pointer entry points
   std::vector<double> zmp((size_t)L * 2), com_h((size_t)Lrun * 6), state_h(8, 0.0), zx(L), zy(L);
@@ -98,8 +159,12 @@ int main(int argc, char **argv) {
       if (com_d[((size_t)l * 6 + c) * B] != com_h[(size_t)l * 6 + c]) { fprintf(stderr, "FAILED: device chain differs from the host entry points at step %d\n", l); return 1; }
   double far = 0.0;
   for (int g = 0; g < B; ++g) { const double x = com_d[((size_t)(Lrun - 1) * 6) * B + g]; far = x > far ? x : far; }
+  unsigned long long sum = 1469598103934665603ull;
+  const unsigned char *bytes = reinterpret_cast<const unsigned char *>(com_d.data());
+  for (size_t i = 0; i < com_d.size() * sizeof(double); ++i) sum = (sum ^ bytes[i]) * 1099511628211ull;
   printf("kajita_fleet: %d walks of %d steps (%d samples each) in %.2f ms = %.0f walks/s; gait 0 ends at x = %.4f m (%d samples), "
-         "farthest %.2f m; device chain == host entry points\n", B, S, L, sec * 1e3, B / sec, com_h[(size_t)(Lrun - 1) * 6], len0, far);
+         "farthest %.2f m; device chain == host entry points; checksum %016llx\n", B, S, L, sec * 1e3, B / sec,
+         com_h[(size_t)(Lrun - 1) * 6], len0, far, sum);
   wg_shutdown();
   return 0;
 }

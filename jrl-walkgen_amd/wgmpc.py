@@ -123,6 +123,12 @@ def lib():
             [C.c_void_p] * 4
         _lib.wg_zmpdisc_full_batch_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + \
             [C.c_void_p] * 10
+        if hasattr(_lib, "wg_zmpdisc_begin_dev"):           # absent from older experiment builds (WG_LIB_PATH, A/B runs)
+            _lib.wg_zmpdisc_length_after.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+            _lib.wg_zmpdisc_begin_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + \
+                [C.c_void_p] * 11
+            _lib.wg_zmpdisc_append_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 11
+            _lib.wg_zmpdisc_end_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 11
         _lib.wg_foot_constraints.argtypes = [C.c_int] + [C.c_void_p] * 4 + [C.c_double] * 4 + [C.c_int] + [C.c_void_p] * 3
         if hasattr(_lib, "wg_foot_constraints_batch_dev"):   # absent from older experiment builds (WG_LIB_PATH, A/B runs)
             _lib.wg_foot_constraints_batch_dev.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_double] * 4 + [C.c_int] + \
@@ -158,6 +164,7 @@ CTX_ENTRY_POINTS = ("wg_set_overlap_strict", "wg_overlap_serialised", "wg_qp_sol
                     "wg_dimitrov_tick_batch", "wg_dimitrov_tick_batch_dev", "wg_preview_configure", "wg_preview_window",
                     "wg_preview_run_batch", "wg_preview_run_batch_dev", "wg_gramian_batch", "wg_gramian_batch_dev",
                     "wg_zmpdisc_batch", "wg_zmpdisc_batch_dev", "wg_zmpdisc_full_batch_dev", "wg_foot_constraints_batch_dev",
+                    "wg_zmpdisc_begin_dev", "wg_zmpdisc_append_dev", "wg_zmpdisc_end_dev",
                     "wg_dimitrov_select_polys_dev", "wg_dimitrov_walk_dev")
 
 
@@ -625,6 +632,52 @@ def zmpdisc_batch_dev(model, B, smax, steps_ptr, n_steps_ptr, init_feet_ptr, lca
                       stream=None):
     _check(lib().wg_zmpdisc_batch_dev(C.byref(model), int(B), int(smax), steps_ptr, n_steps_ptr, init_feet_ptr, int(lcap),
                                       zx_tm_ptr, zy_tm_ptr, length_ptr, stream))
+
+
+# ---- the same walk on line: begin, any number of appends, end (include/wg_mpc.h, "steps as they arrive") ----
+ZMPDISC_TAIL_MAX = 52
+
+
+class ZmpDiscState(C.Structure):        # wg_zmpdisc_state_t
+    _fields_ = [("support", C.c_double * 6), ("prev_support", C.c_double * 2), ("prev_rel", C.c_double * 2),
+                ("ang_support", C.c_double), ("ang_zmp", C.c_double), ("left", C.c_double * 6), ("right", C.c_double * 6),
+                ("zmp_last", C.c_double * 3), ("zmp_first", C.c_double * 2), ("last_step", RelStep),
+                ("tail", C.c_double * 2 * ZMPDISC_TAIL_MAX)] + \
+               [(k, C.c_int) for k in ("left_type", "right_type", "n_samples", "n_steps", "ended", "error", "begun", "pad_")]
+
+
+ZMPDISC_STATE_BYTES = 1144
+ZMPDISC_OUTPUTS = ("zmp_x", "zmp_y", "zmp_theta", "zmp_type", "left", "left_type", "right", "right_type")
+
+
+def zmpdisc_length_after(model, steps, n_steps, ended=False):
+    """samples after the first n_steps steps of `steps` (and after the end phase if `ended`), or a negative code"""
+    return int(lib().wg_zmpdisc_length_after(C.byref(model), C.addressof(steps), int(n_steps), int(bool(ended))))
+
+
+def _zd_outs(outs):
+    assert set(outs) <= set(ZMPDISC_OUTPUTS), outs
+    return [outs.get(k) for k in ZMPDISC_OUTPUTS]
+
+
+def zmpdisc_begin_dev(model, B, smax, steps_ptr, n_steps_ptr, init_feet_ptr, lcap, outs, state_ptr, length_ptr=None,
+                      stream=None):
+    """InitOnLine on the first n_steps[b] >= 2 steps.  `outs`: device pointers by name (ZMPDISC_OUTPUTS, time-major as
+    wg_zmpdisc_full_batch_dev writes them), absent = not wanted; the same set goes to every call of the walk."""
+    _check(lib().wg_zmpdisc_begin_dev(C.byref(model), int(B), int(smax), steps_ptr, n_steps_ptr, init_feet_ptr, int(lcap),
+                                      *_zd_outs(outs), state_ptr, length_ptr, stream))
+
+
+def zmpdisc_append_dev(model, B, smax, steps_ptr, n_steps_ptr, lcap, outs, state_ptr, length_ptr=None, stream=None):
+    """OnLineAddFoot on n_steps[b] >= 0 further steps (`steps`: those of this call, [B][smax]); 0 = the gait sits it out"""
+    _check(lib().wg_zmpdisc_append_dev(C.byref(model), int(B), int(smax), steps_ptr, n_steps_ptr, int(lcap), *_zd_outs(outs),
+                                       state_ptr, length_ptr, stream))
+
+
+def zmpdisc_end_dev(model, B, lcap, outs, state_ptr, length_ptr=None, select_ptr=None, stream=None):
+    """EndPhaseOfTheWalking for every gait, or for those with select[b] != 0"""
+    _check(lib().wg_zmpdisc_end_dev(C.byref(model), int(B), select_ptr, int(lcap), *_zd_outs(outs), state_ptr, length_ptr,
+                                    stream))
 
 
 def foot_constraints(time, left, left_type, right, sole_w, sole_h, constraint_x, constraint_y, cap=256):
