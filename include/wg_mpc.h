@@ -713,6 +713,35 @@ int wg_foot_constraints_batch_dev(int B, int lcap, const int *length, const doub
                                   const int *left_type_tm, const double *right_tm, double sole_w, double sole_h,
                                   double constraint_x, double constraint_y, int qcap, wg_zmp_polytope_t *queues,
                                   double *t_start, double *t_end, int *count, void *hip_stream);
+/* The same queues on line: grown with the feet trajectories (wg_zmpdisc_begin_dev / _append_dev / _end_dev), each sample
+ * classified and each polytope built once.  The reference has no counterpart (InitOnLine / OnLineAddFoot / OnLine /
+ * EndPhaseOfTheWalking of ZMPConstrainedQPFastFormulation are empty bodies, ZMPConstrainedQPFastFormulation.cpp:1544-1595): the
+ * contract is equality with wg_foot_constraints_batch_dev.  Layouts and arguments are that call's; per gait
+ *   done[b]   B, in/out   samples already turned into queue entries by earlier calls.  done[b] == 0 starts a queue: count[b] is
+ *                         ignored on input and restarts at 0.  The call consumes samples [done[b], length[b]) and sets
+ *                         done[b] = length[b].
+ * CONTRACT: after the call, count[b] and the first min(count[b], qcap) entries of queues, t_start, t_end are exactly what
+ * wg_foot_constraints_batch_dev writes for length[b] samples; entries [count[b], qcap) are not touched; the last entry's t_end
+ * is time[length[b] - 1].  This holds after every call, however the trajectory is cut.  So an entry is final once written,
+ * except the last entry's t_end: the next call overwrites that once, with the time of the first new support change or with
+ * the new last sample's time (every entry still has exactly one writer per call).  count[b] may exceed qcap as it may in the
+ * batch call: positions >= qcap are counted and not stored, and the entry at position qcap - 1 still gets its t_end from the
+ * later call that finds the change closing it.
+ *   length[b] == done[b]    the gait sits the call out: none of its bytes is touched.
+ *   refused, with count[b] = WG_ERR_BAD_ARG, done[b] unchanged and no queue byte written:  length[b] < 0 (a gait
+ *       wg_zmpdisc_* refused);  length[b] > lcap;  done[b] < 0;  done[b] > length[b];  done[b] < first_sample;  done[b] > 0
+ *       with count[b] < 0 -- errors are sticky through count[b] < 0.  A support whose corners span no polygon gives
+ *       WG_ERR_BAD_ARG as in the batch call.  A neighbour never notices.
+ *   first_sample   a HOST-side lower bound on every done[b] (0 is always valid): the chunks of the time axis that lie wholly
+ *       below it are not launched, so that a long walk does not pay a grid over its past.
+ * The feet arrays hold the whole walk from sample 0 (the convention of the wg_zmpdisc on-line calls: lcap / qcap are sized by
+ * the caller for the walk; no ring buffer): the support state before a gait's first new sample is read back from them, nothing
+ * else is carried from call to call.  Nothing at or past length[b] is read.  Launches are ordered per context exactly like the
+ * batch call's (the same buffer of the context).  Added without a change of wg_abi_version(): detect by symbol. */
+int wg_foot_constraints_append_dev(int B, int lcap, int first_sample, int *done, const int *length, const double *time,
+                                   const double *left_tm, const int *left_type_tm, const double *right_tm, double sole_w,
+                                   double sole_h, double constraint_x, double constraint_y, int qcap,
+                                   wg_zmp_polytope_t *queues, double *t_start, double *t_end, int *count, void *hip_stream);
 /* The queue walk of one tick, BuildConstraintMatrices (ZMPConstrainedQPFastFormulation.cpp:785-796, 822-835), for B gaits:
  * the first entry q with t_start[q] <= t0 <= t_end[q] is the start; for i = 0 .. N-1, q advances by one when
  * t0 + i T > t_end[q] (the reference's StartingTime + i*T); polys[b][i] is a copy of entry q.  N and T are the configured
@@ -730,10 +759,26 @@ int wg_dimitrov_select_polys_dev(int B, int qcap, const wg_zmp_polytope_t *queue
  * a host loop of wg_dimitrov_select_polys_dev + wg_dimitrov_tick_batch_dev, in every solver mode.  The B x N selected
  * polytopes live in a buffer of the context, sized on first use (growing never frees what a launch in flight may be reading,
  * as for wg_mpc_reserve); walks of one context on different streams are ordered like tick launches.
- *   outs     n_ticks x B, tick-major, or NULL;  ran_out  B: 1 once any tick of the gait ran out, or NULL */
+ *   outs     n_ticks x B, tick-major, or NULL;  ran_out  B: 1 once any tick of the gait ran out, or NULL.  ran_out is CLEARED
+ *            by every walk call: a caller that walks in pieces (below) ORs it across its calls. */
 int wg_dimitrov_walk_dev(int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end,
                          const int *count, double t0, int n_ticks, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs,
                          int *ran_out, int max_iter, void *hip_stream);
+/* Continuing a walk (host arithmetic on the configured model's N and T; no launch).
+ * wg_dimitrov_walk_time(t0, n_ticks) is the t at which tick n_ticks of a walk started at t0 selects: the walk's own repeated
+ * addition of T, so the walks (t0, n1) and (wg_dimitrov_walk_time(t0, n1), n2) on the same states are the walk (t0, n1 + n2) bit
+ * for bit (the product t0 + n T is another number).  NaN without a configured model.
+ * wg_dimitrov_walk_safe_ticks(t0, t_have) is the largest n such that every tick k < n, at t = wg_dimitrov_walk_time(t0, k), has
+ * t + (N - 1) T <= t_have -- the select kernel's own expression t0 + i * T at its last instant.  With t_have = time[length - 1]
+ * of a gait that is still walking (the smallest over the fleet), such a tick selects from the provisional queue
+ * wg_foot_constraints_append_dev has left what it will select from the final one: every entry but the last is final; the last
+ * one's t_end is provisional, equals t_have and only grows; the tick's start test t_start <= t <= t_end and its N advance
+ * tests t + i T > t_end compare against it only with instants <= t_have, which no later, larger t_end answers differently; and
+ * a walk that never passes the last entry never sees the entries later calls add behind it.  A gait whose walk has ended
+ * (wg_zmpdisc_end_dev, then one more wg_foot_constraints_append_dev) has a final queue and constrains nothing.  Negative code:
+ * no configured model, or a t0 / t_have that is not finite. */
+double wg_dimitrov_walk_time(double t0, int n_ticks);
+int wg_dimitrov_walk_safe_ticks(double t0, double t_have);
 
 /* Invariant Hessian block on the matrix cores, batched over models -----------------------------------------------------
  *
@@ -802,6 +847,13 @@ int wg_foot_constraints_batch_dev_ctx(wg_ctx_t *ctx, int B, int lcap, const int 
                                       const double *left_tm, const int *left_type_tm, const double *right_tm, double sole_w,
                                       double sole_h, double constraint_x, double constraint_y, int qcap,
                                       wg_zmp_polytope_t *queues, double *t_start, double *t_end, int *count, void *hip_stream);
+int wg_foot_constraints_append_dev_ctx(wg_ctx_t *ctx, int B, int lcap, int first_sample, int *done, const int *length,
+                                       const double *time, const double *left_tm, const int *left_type_tm,
+                                       const double *right_tm, double sole_w, double sole_h, double constraint_x,
+                                       double constraint_y, int qcap, wg_zmp_polytope_t *queues, double *t_start,
+                                       double *t_end, int *count, void *hip_stream);
+double wg_dimitrov_walk_time_ctx(wg_ctx_t *ctx, double t0, int n_ticks);
+int wg_dimitrov_walk_safe_ticks_ctx(wg_ctx_t *ctx, double t0, double t_have);
 int wg_dimitrov_select_polys_dev_ctx(wg_ctx_t *ctx, int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start,
                                      const double *t_end, const int *count, double t0, wg_zmp_polytope_t *polys, int *ran_out,
                                      void *hip_stream);

@@ -1,11 +1,13 @@
 // wg_capi.hip -- C ABI (include/wg_mpc.h) over the HIP kernels: host code only (the kernels are in the headers).  gfx950 only.
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -150,7 +152,8 @@ struct wg_ctx {
   std::unique_ptr<wg::DimitrovConst> dim_host;
   bool dim_set = false;
   DevBuf dim_buf;
-  // Dimitrov fleets on the device: the per-chunk counts of wg_foot_constraints_batch_dev, and the B x N polytopes
+  // Dimitrov fleets on the device: the per-chunk counts of wg_foot_constraints_batch_dev / _append_dev (the latter keeps each
+  // gait's done and count as they were on entry behind them), and the B x N polytopes
   // wg_dimitrov_walk_dev selects for the tick it launches next.  One launch at a time uses each: claimed and marked like the tick's
   // buffers (fc_order, walk_order)
   DevBuf fc_buf, walk_polys;
@@ -1299,8 +1302,42 @@ int wg_foot_constraints_batch_dev_ctx(wg_ctx_t *ctx, int B, int lcap, const int 
   int *cnt = static_cast<int *>(ctx->fc_buf.p);
   const dim3 grid((B + 63) / 64, chunks);
   HIP_TRY(hipMemsetAsync(count, 0, (size_t)B * sizeof(int), st));
-  hipLaunchKernelGGL(wg::wg_footcons_kernel<false>, grid, dim3(64), 0, st, I, Q, cnt);
-  hipLaunchKernelGGL(wg::wg_footcons_kernel<true>, grid, dim3(64), 0, st, I, Q, cnt);
+  hipLaunchKernelGGL((wg::wg_footcons_kernel<false, false>), grid, dim3(64), 0, st, I, Q, cnt, wg::FcRes{});
+  hipLaunchKernelGGL((wg::wg_footcons_kernel<true, false>), grid, dim3(64), 0, st, I, Q, cnt, wg::FcRes{});
+  HIP_TRY(hipGetLastError());
+  return slot_mark(ctx->fc_order, st);
+}
+
+int wg_foot_constraints_append_dev_ctx(wg_ctx_t *ctx, int B, int lcap, int first_sample, int *done, const int *length, const double *time, const double *left_tm, const int *left_type_tm, const double *right_tm, double sole_w, double sole_h, double constraint_x, double constraint_y, int qcap, wg_zmp_polytope_t *queues, double *t_start, double *t_end, int *count, void *hip_stream) {
+  if (int rc = use_ctx(ctx)) return rc;
+  if (B < 0 || qcap < 0 || first_sample < 0) return fail(WG_ERR_BAD_ARG, "need B >= 0, qcap >= 0, first_sample >= 0");
+  if (B == 0) return WG_OK;
+  if (qcap > 0 && (!queues || !t_start || !t_end)) return fail(WG_ERR_BAD_ARG, "need non-null queues and intervals for qcap > 0");
+  if (lcap < 1 || !done || !length || !time || !left_tm || !left_type_tm || !right_tm || !count)
+    return fail(WG_ERR_BAD_ARG, "need lcap >= 1, non-null done, lengths, times, feet arrays and counts");
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  double hw = sole_w * 0.5, hh = sole_h * 0.5;
+  hh -= constraint_y;
+  hw -= constraint_x;
+  const wg::FcIn I{B, lcap, length, time, left_tm, right_tm, left_type_tm, hw, hh};
+  const wg::FcOut Q{qcap, queues, t_start, t_end, count};
+  // chunks that lie wholly below first_sample hold no new sample of any gait: not launched (a gait whose done[b] is below it
+  // is refused on the device).  first_sample >= lcap: every gait sits out or is refused, the first kernel alone says so
+  const int chunk0 = first_sample / wg::kFcChunk, chunks = (lcap + wg::kFcChunk - 1) / wg::kFcChunk - chunk0;
+  if (chunks > 65535) return fail(WG_ERR_TOO_LARGE, "lcap = %d, first_sample = %d: more than 65535 chunks of %d samples", lcap, first_sample, wg::kFcChunk);
+  // the per-chunk counts, and done[b] / count[b] as they were on entry, live in the buffer of the batch call: ordered like it
+  std::lock_guard<std::mutex> launch_lk(ctx->launch_mu);
+  if (int rc = slot_claim(ctx, ctx->fc_order, st, "foot-constraints")) return rc;
+  const size_t sB = (size_t)B, n_cnt = (size_t)(chunks > 0 ? chunks : 0) * sB;
+  if (int rc = ctx->fc_buf.reserve((n_cnt + 2 * sB) * sizeof(int))) return rc;
+  int *cnt = static_cast<int *>(ctx->fc_buf.p), *from = cnt + n_cnt, *base = from + sB;
+  hipLaunchKernelGGL(wg::wg_footcons_resume_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, lcap, first_sample, length, done, count, from, base);
+  if (chunks > 0) {
+    const wg::FcRes Z{from, base, done, chunk0};
+    const dim3 grid((B + 63) / 64, chunks);
+    hipLaunchKernelGGL((wg::wg_footcons_kernel<false, true>), grid, dim3(64), 0, st, I, Q, cnt, Z);
+    hipLaunchKernelGGL((wg::wg_footcons_kernel<true, true>), grid, dim3(64), 0, st, I, Q, cnt, Z);
+  }
   HIP_TRY(hipGetLastError());
   return slot_mark(ctx->fc_order, st);
 }
@@ -1338,6 +1375,28 @@ int wg_dimitrov_walk_dev_ctx(wg_ctx_t *ctx, int B, int qcap, const wg_zmp_polyto
     t += T;                                               // BuildZMPTrajectoryFromFootTrajectory's own accumulation (:1189-1192)
   }
   return slot_mark(ctx->walk_order, st);
+}
+
+// the clock of wg_dimitrov_walk_dev_ctx above, on the host: the same repeated addition of the configured T
+double wg_dimitrov_walk_time_ctx(wg_ctx_t *ctx, double t0, int n_ticks) {
+  if (!ctx || !ctx->dim_set) {
+    (void)fail(WG_ERR_BAD_ARG, "wg_dimitrov_configure() has not been called on this context");
+    return std::numeric_limits<double>::quiet_NaN();
+  }
+  const double T = ctx->dim_host->T;
+  double t = t0;
+  for (int k = 0; k < n_ticks; k++) t += T;
+  return t;
+}
+
+int wg_dimitrov_walk_safe_ticks_ctx(wg_ctx_t *ctx, double t0, double t_have) {
+  if (!ctx || !ctx->dim_set) return fail(WG_ERR_BAD_ARG, "wg_dimitrov_configure() has not been called on this context");
+  if (!std::isfinite(t0) || !std::isfinite(t_have)) return fail(WG_ERR_BAD_ARG, "need finite t0 and t_have");
+  const int i = ctx->dim_host->N - 1;
+  const double T = ctx->dim_host->T;
+  int n = 0;
+  for (double t = t0; n < INT_MAX && t + i * T <= t_have; t += T) n++;       // the select kernel's t0 + i * T at its last instant
+  return n;
 }
 
 }  // extern "C"
@@ -1729,6 +1788,9 @@ int wg_dimitrov_tick_batch_dev(int B, const wg_zmp_polytope_t *polys, wg_dimitro
 int wg_dimitrov_tick_batch(int B, const wg_zmp_polytope_t *polys, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int max_iter) { return on_default(&wg_dimitrov_tick_batch_ctx, B, polys, states, outs, max_iter); }
 int wg_foot_constraints_batch_dev(int B, int lcap, const int *length, const double *time, const double *left_tm, const int *left_type_tm, const double *right_tm, double sole_w, double sole_h, double constraint_x, double constraint_y, int qcap, wg_zmp_polytope_t *queues, double *t_start, double *t_end, int *count, void *hip_stream) { return on_default(&wg_foot_constraints_batch_dev_ctx, B, lcap, length, time, left_tm, left_type_tm, right_tm, sole_w, sole_h, constraint_x, constraint_y, qcap, queues, t_start, t_end, count, hip_stream); }
 int wg_dimitrov_select_polys_dev(int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count, double t0, wg_zmp_polytope_t *polys, int *ran_out, void *hip_stream) { return on_default(&wg_dimitrov_select_polys_dev_ctx, B, qcap, queues, t_start, t_end, count, t0, polys, ran_out, hip_stream); }
+int wg_foot_constraints_append_dev(int B, int lcap, int first_sample, int *done, const int *length, const double *time, const double *left_tm, const int *left_type_tm, const double *right_tm, double sole_w, double sole_h, double constraint_x, double constraint_y, int qcap, wg_zmp_polytope_t *queues, double *t_start, double *t_end, int *count, void *hip_stream) { return on_default(&wg_foot_constraints_append_dev_ctx, B, lcap, first_sample, done, length, time, left_tm, left_type_tm, right_tm, sole_w, sole_h, constraint_x, constraint_y, qcap, queues, t_start, t_end, count, hip_stream); }
+double wg_dimitrov_walk_time(double t0, int n_ticks) { return on_default(&wg_dimitrov_walk_time_ctx, t0, n_ticks); }
+int wg_dimitrov_walk_safe_ticks(double t0, double t_have) { return on_default(&wg_dimitrov_walk_safe_ticks_ctx, t0, t_have); }
 int wg_dimitrov_walk_dev(int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count, double t0, int n_ticks, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int *ran_out, int max_iter, void *hip_stream) { return on_default(&wg_dimitrov_walk_dev_ctx, B, qcap, queues, t_start, t_end, count, t0, n_ticks, states, outs, ran_out, max_iter, hip_stream); }
 int wg_mpc_tick_pinned(wg_gait_state_t *state, wg_tick_out_t *out, int *diag, int advance_calls) { return on_default(&wg_mpc_tick_pinned_ctx, state, out, diag, advance_calls); }
 int wg_mpc_assemble_batch_dev(int B, const wg_gait_state_t *states, int advance_calls, int nmax, int mmax, double *C, double *d, double *A, double *b, double *xl, double *xu, int *n, int *m, void *hip_stream) { return on_default(&wg_mpc_assemble_batch_dev_ctx, B, states, advance_calls, nmax, mmax, C, d, A, b, xl, xu, n, m, hip_stream); }

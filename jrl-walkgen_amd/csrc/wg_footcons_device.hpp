@@ -1,6 +1,8 @@
 // wg_footcons_device.hpp -- the Dimitrov-2008 pipeline between the feet trajectories and the tick, on the device:
 //
-//   wg_footcons_kernel<false / true>   polytope queues of B feet trajectories (wg_foot_constraints_batch_dev)
+//   wg_footcons_kernel<kBuild, kRes>   polytope queues of B feet trajectories: <false / true, false> the whole trajectories
+//                                      (wg_foot_constraints_batch_dev), <false / true, true> behind wg_footcons_resume_kernel the
+//                                      samples that arrived since the last call (wg_foot_constraints_append_dev)
 //       FootConstraintsAsLinearSystem::BuildLinearConstraintInequalities  src/Mathematics/FootConstraintsAsLinearSystem.cpp:258-539
 //       ComputeLinearSystem :97-256, FindSimilarConstraints :55-92, ComputeConvexHull::DoComputeConvexHull ConvexHull.cpp:88-203
 //   wg_dimitrov_select_kernel          the queue walk of one tick (wg_dimitrov_select_polys_dev, wg_dimitrov_walk_dev)
@@ -21,6 +23,10 @@
 //                            out [slot][lane] (runtime-indexed, so not in registers; conflict-free).
 // Every entry of the queue has exactly one writer: polytope q and t_start[q] the lane that finds change q, t_end[q] the lane
 // that finds change q + 1, the last t_end the lane whose chunk holds the gait's last sample.  Nothing past length[b] is read.
+// Resumed (kRes): the same two passes over the samples [done[b], length[b]) alone.  An entry is final once written, except the last
+// one's t_end, which the next call overwrites once -- with the time of the first new change (the lane that finds it, as above) or
+// with the new last sample's.  count[b] on entry is the queue position of the first new change; pass 1's atomics change it, so
+// wg_footcons_resume_kernel leaves it, and done[b], behind the per-chunk counts where both passes read them.
 // Same operation order as wg_footcons.cpp; the library is built with -ffp-contract=off, / and sqrt are IEEE on both sides and
 // sin / cos are include/wg_trig.h: the same bytes.
 #pragma once
@@ -198,15 +204,56 @@ __device__ inline bool fc_polytope(const FcPts &P, int n, wg_zmp_polytope_t *out
   return true;
 }
 
-template <bool kBuild>
+// what a resumed call (wg_foot_constraints_append_dev) adds: where each gait resumes, snapshot by wg_footcons_resume_kernel before
+// pass 1's atomics change count[b]
+struct FcRes {
+  const int *from;                       // B: the first new sample (done[b] on entry), or -1: the gait sits out or was refused
+  const int *base;                       // B: count[b] on entry (0 for a gait that starts), the queue position of the first new change
+  int *done;                             // B, in/out: length[b] after the call
+  int chunk0;                            // the launch's first chunk (first_sample / kFcChunk): blockIdx.y counts from there
+};
+
+// Before the two passes of a resumed call, one lane per gait: refuse or admit, and keep done[b] / count[b] as they were on entry
+// where both passes read them (neither is read again: pass 1 adds to count[b], pass 2's closing lane writes done[b]).
+__global__ void __launch_bounds__(256)
+wg_footcons_resume_kernel(int B, int lcap, int first_sample, const int *__restrict__ length, const int *__restrict__ done,
+                          int *__restrict__ count, int *__restrict__ from, int *__restrict__ base) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  const int len = length[b], d = done[b];
+  const int c = d > 0 ? count[b] : 0;                     // a gait that starts ignores what count[b] holds
+  int f = -1;
+  if (len < 0 || len > lcap || d < 0 || d > len || d < first_sample || c < 0) {
+    count[b] = WG_ERR_BAD_ARG;                            // refused (an earlier error included: sticky); done[b] and the queue stay
+  } else if (d < len) {
+    f = d;
+    if (d == 0) count[b] = 0;
+  }                                                       // else length[b] == done[b]: sits the call out, nothing is touched
+  from[b] = f;
+  base[b] = c;
+}
+
+// kRes = false: the whole trajectory, wg_foot_constraints_batch_dev (Z is not read).  kRes = true: the samples from Z.from[b] on.
+// The chunks stay ABSOLUTE (chunk c is samples [c kFcChunk, (c + 1) kFcChunk) of every gait), so the rows a wave reads are whole
+// lines however the lanes' resume points differ; a lane skips the samples of its chunk below its own.  The state before a lane's
+// first new sample is found like the state before a chunk, walking back while the predecessor inherits -- across the resume point
+// and across chunks: the feet arrays hold the whole walk, nothing is carried from call to call but done[b] and count[b].
+template <bool kBuild, bool kRes>
 __global__ void __launch_bounds__(64)
-wg_footcons_kernel(FcIn I, FcOut Q, int *__restrict__ cnt /* [chunks][B] */) {
+wg_footcons_kernel(FcIn I, FcOut Q, int *__restrict__ cnt /* [chunks][B] */, FcRes Z) {
   __shared__ double fc_lds[kBuild ? kFcSlots * 2 * 64 : 1];
-  const int lane = threadIdx.x, b = blockIdx.x * 64 + lane, chunk = blockIdx.y;
+  const int lane = threadIdx.x, b = blockIdx.x * 64 + lane;
+  int chunk = blockIdx.y, crel = blockIdx.y;              // absolute, and as cnt is indexed
+  if constexpr (kRes) chunk += Z.chunk0;
   if (b >= I.B) return;
   const size_t sB = (size_t)I.B;
   const int len = I.length[b], i0 = chunk * kFcChunk;
-  if (len < 0 || len > I.lcap) {                          // a gait wg_zmpdisc_* refused (or a length the arrays cannot hold): the
+  int from = 0, cfirst = 0;                               // the first new sample, and its chunk as cnt is indexed
+  if constexpr (kRes) {
+    from = Z.from[b];
+    if (from < 0) return;                                 // sits out or refused: wg_footcons_resume_kernel has said so
+    cfirst = from / kFcChunk - Z.chunk0;
+  } else if (len < 0 || len > I.lcap) {                   // a gait wg_zmpdisc_* refused (or a length the arrays cannot hold): the
     if (!kBuild) {                                        // host call's answer to n < 0
       cnt[(size_t)chunk * sB + b] = 0;
       if (chunk == 0) Q.count[b] = WG_ERR_BAD_ARG;
@@ -214,9 +261,12 @@ wg_footcons_kernel(FcIn I, FcOut Q, int *__restrict__ cnt /* [chunks][B] */) {
     return;
   }
   const int n = len - i0 < kFcChunk ? len - i0 : kFcChunk;         // samples of this chunk (<= 0: past the gait's end)
+  const int k0 = kRes && from > i0 ? from - i0 : 0;                // the first of them that is new
+  if constexpr (kRes)
+    if (n <= k0) return;                                  // nothing new here (neither pass reads cnt of such a chunk)
   int own = 0;
   if (kBuild) {
-    own = n > 0 ? cnt[(size_t)chunk * sB + b] : 0;
+    own = n > 0 ? cnt[(size_t)crel * sB + b] : 0;
     if (own == 0 && !(n > 0 && i0 + n == len)) return;    // no change in this chunk, and not the one that closes the queue
   }
   // support state of every sample of the chunk, 2 bits each: the loads do not depend on one another
@@ -225,7 +275,7 @@ wg_footcons_kernel(FcIn I, FcOut Q, int *__restrict__ cnt /* [chunks][B] */) {
 #pragma unroll 8
     for (int k = 0; k < kFcChunk; k++) {
       unsigned long long s = 0;
-      if (k < n) {
+      if (k < n && (!kRes || k >= k0)) {
         const size_t i = (size_t)(i0 + k);
         s = (unsigned long long)fc_classify(I.ltype[i * sB + b], I.left[(i * 6 + 2) * sB + b], I.right[(i * 6 + 2) * sB + b]);
       }
@@ -233,21 +283,23 @@ wg_footcons_kernel(FcIn I, FcOut Q, int *__restrict__ cnt /* [chunks][B] */) {
       else code_hi |= s << (2 * (k - 32));
     }
   }
-  // the state before the chunk: its predecessor's, walking back while that one inherits; sample 0 inherits DOUBLE_SUPPORT
+  // the state before the first new sample: its predecessor's, walking back while that one inherits; sample 0 inherits DOUBLE_SUPPORT
   int state = kFcDouble;
-  if (n > 0 && i0 > 0 && (!kBuild || own > 0)) {
-    for (int j = i0 - 1; j >= 0; j--) {
+  if (n > 0 && i0 + k0 > 0 && (!kBuild || own > 0)) {
+    for (int j = i0 + k0 - 1; j >= 0; j--) {
       const size_t i = (size_t)j;
       const int s = fc_classify(I.ltype[i * sB + b], I.left[(i * 6 + 2) * sB + b], I.right[(i * 6 + 2) * sB + b]);
       if (s != kFcInherit) { state = s; break; }
     }
   }
   int q = 0;                                              // queue position of this chunk's first change
-  if (kBuild)
-    for (int c = 0; c < chunk; c++) q += cnt[(size_t)c * sB + b];
+  if (kBuild) {
+    if constexpr (kRes) q = Z.base[b];
+    for (int c = cfirst; c < crel; c++) q += cnt[(size_t)c * sB + b];
+  }
   const FcPts P{fc_lds + lane};
   int found = 0;
-  for (int k = 0; k < n; k++) {
+  for (int k = k0; k < n; k++) {
     if (kBuild && found == own) break;
     const int s = (int)(((k < 32 ? code_lo >> (2 * k) : code_hi >> (2 * (k - 32)))) & 3);
     const int next = s == kFcInherit ? state : s;
@@ -257,7 +309,7 @@ wg_footcons_kernel(FcIn I, FcOut Q, int *__restrict__ cnt /* [chunks][B] */) {
     if (kBuild) {
       const size_t i = (size_t)(i0 + k);
       const double t = I.time[i];
-      if (q > 0 && q - 1 < Q.qcap) Q.t_end[(size_t)b * Q.qcap + q - 1] = t;
+      if (q > 0 && q - 1 < Q.qcap) Q.t_end[(size_t)b * Q.qcap + q - 1] = t;       // resumed: may be an earlier call's last entry
       if (q < Q.qcap) {
         const double *L = I.left + i * 6 * sB + b, *R = I.right + i * 6 * sB + b;
         const double lx = L[0], ly = L[sB], lz = L[2 * sB], lth = L[3 * sB], rx = R[0], ry = R[sB], rz = R[2 * sB], rth = R[3 * sB];
@@ -279,10 +331,11 @@ wg_footcons_kernel(FcIn I, FcOut Q, int *__restrict__ cnt /* [chunks][B] */) {
     found++;
   }
   if (!kBuild) {
-    cnt[(size_t)chunk * sB + b] = found;
+    cnt[(size_t)crel * sB + b] = found;
     if (found) atomicAdd(Q.count + b, found);
-  } else if (n > 0 && i0 + n == len && q > 0 && q - 1 < Q.qcap) {
-    Q.t_end[(size_t)b * Q.qcap + q - 1] = I.time[len - 1];             // the last polytope holds until the last sample
+  } else if (n > 0 && i0 + n == len) {                    // the lane whose chunk holds the gait's last sample
+    if (q > 0 && q - 1 < Q.qcap) Q.t_end[(size_t)b * Q.qcap + q - 1] = I.time[len - 1];    // the last polytope holds until then
+    if constexpr (kRes) Z.done[b] = len;
   }
 }
 

@@ -3,7 +3,14 @@
 // queues) -> wg_dimitrov_walk_dev (n ticks: queue walk + fused tick), nothing leaves the device in between.  The Dimitrov twin of
 // kajita_fleet.cpp.  Prints one line with walks/s, ticks/s and a checksum (FNV-1a, 64 bit) of the final states.
 //
-//   dimitrov_fleet [--batch B] [--steps S] [--ticks K] [--solver 0|1|2] [--fleet FILE]
+// With --online K the same walks are fed K steps per call instead, the twin of kajita_fleet --online: wg_zmpdisc_begin_dev on the
+// first two steps (feet outputs only), then { wg_zmpdisc_append_dev on the next K; wg_foot_constraints_append_dev;
+// wg_dimitrov_walk_dev on the ticks that became safe (wg_dimitrov_walk_safe_ticks, chained by wg_dimitrov_walk_time) } until the
+// steps run out -- a gait of a ragged fleet whose steps have run out is ended (wg_zmpdisc_end_dev with `select`) while the others
+// walk on -- then a last append of the queues and the remaining ticks.  Every sample is classified once, and the final states --
+// hence the checksum -- are those of the whole-sequence mode.  ("the walk alone" is then the sum of the walk pieces, by events.)
+//
+//   dimitrov_fleet [--batch B] [--steps S] [--ticks K] [--solver 0|1|2] [--fleet FILE] [--online K]
 //
 // --fleet FILE runs a fleet somebody else drew instead of the built-in one (tests/test_dimitrov_walk_gpu.py compares the
 // checksum with its own run of the same fleet): int32 B, int32 smax, wg_zmpdisc_model_t, B x smax wg_rel_step_t, B int32
@@ -24,7 +31,7 @@
 #define CHECK_WG(e) do { int r_ = (e); if (r_ != WG_OK) { fprintf(stderr, "FAILED: %s: %s\n", #e, wg_last_error()); return 1; } } while (0)
 
 int main(int argc, char **argv) {
-  int B = 4096, S = 8, K = 40, solver = WG_DIMITROV_PLDP;
+  int B = 4096, S = 8, K = 40, solver = WG_DIMITROV_PLDP, online = 0;
   const char *fleet = nullptr;
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--batch") && i + 1 < argc) B = atoi(argv[++i]);
@@ -32,6 +39,7 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[i], "--ticks") && i + 1 < argc) K = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--solver") && i + 1 < argc) solver = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--fleet") && i + 1 < argc) fleet = argv[++i];
+    else if (!strcmp(argv[i], "--online") && i + 1 < argc) { online = atoi(argv[++i]); if (online < 1 || online > WG_ZMPDISC_MAX_STEPS) { fprintf(stderr, "FAILED: need 1 <= --online K <= %d\n", WG_ZMPDISC_MAX_STEPS); return 1; } }
   }
   wg_zmpdisc_model_t zm;
   wg_zmpdisc_defaults(&zm);
@@ -112,12 +120,127 @@ int main(int argc, char **argv) {
   std::vector<wg_dimitrov_state_t> states(B);
   memset(states.data(), 0, sizeof(wg_dimitrov_state_t) * B);
   for (int g = 0; g < B; ++g) states[g].starting = 1;
+  // --online: the walk's state blobs, the steps after the first two regrouped call by call, [call][B][online], what each call
+  // leaves of every gait (host arithmetic: nothing is read back while the fleet walks), and each walk piece's ran_out
+  int S_max = 0;
+  for (int g = 0; g < B; ++g) S_max = n_steps[g] > S_max ? n_steps[g] : S_max;
+  const int n_calls = online ? (S_max - 2 + online - 1) / online : 0;
+  wg_zmpdisc_state_t *d_walk = nullptr; wg_rel_step_t *d_chunks = nullptr; int *d_cns = nullptr, *d_two = nullptr, *d_sel = nullptr, *d_done = nullptr;
+  std::vector<int> cns((size_t)n_calls * B), sel((size_t)(n_calls + 1) * B, 0), len_after((size_t)(n_calls + 1) * B), len_ended(B);
+  std::vector<int> ran_pieces;
+  std::vector<hipEvent_t> ev;
+  if (online) {
+    std::vector<wg_rel_step_t> chunks((size_t)n_calls * B * online);
+    memset(chunks.data(), 0, sizeof(wg_rel_step_t) * chunks.size());
+    for (int g = 0; g < B; ++g) {
+      if (n_steps[g] < 2) { fprintf(stderr, "FAILED: gait %d: --online needs two steps to begin with\n", g); return 1; }
+      const wg_rel_step_t *sg = &steps[(size_t)g * S];
+      len_ended[g] = wg_zmpdisc_length_after(&zm, sg, n_steps[g], 1);
+      for (int c = 0; c <= n_calls; ++c) {                     // call 0 is the begin; sel: the gait is ended behind call c
+        const int given = 2 + c * online < n_steps[g] ? 2 + c * online : n_steps[g];
+        len_after[(size_t)c * B + g] = wg_zmpdisc_length_after(&zm, sg, given, 0);
+        sel[(size_t)c * B + g] = given == n_steps[g] && (c == 0 || 2 + (c - 1) * online < n_steps[g]);
+      }
+      for (int c = 0; c < n_calls; ++c) {
+        const int first = 2 + c * online, left = n_steps[g] - first, n = left < 0 ? 0 : (left < online ? left : online);
+        cns[(size_t)c * B + g] = n;
+        for (int i = 0; i < n; ++i) chunks[((size_t)c * B + g) * online + i] = sg[first + i];
+      }
+    }
+    std::vector<int> two(B, 2);
+    CHECK_HIP(hipMalloc((void **)&d_walk, sizeof(wg_zmpdisc_state_t) * B));
+    CHECK_HIP(hipMalloc((void **)&d_chunks, sizeof(wg_rel_step_t) * (chunks.size() ? chunks.size() : 1)));
+    CHECK_HIP(hipMalloc((void **)&d_cns, sizeof(int) * (cns.size() ? cns.size() : 1)));
+    CHECK_HIP(hipMalloc((void **)&d_sel, sizeof(int) * sel.size()));
+    CHECK_HIP(hipMalloc((void **)&d_two, sizeof(int) * B));
+    CHECK_HIP(hipMalloc((void **)&d_done, sizeof(int) * B));
+    CHECK_HIP(hipMemcpy(d_chunks, chunks.data(), sizeof(wg_rel_step_t) * chunks.size(), hipMemcpyHostToDevice));
+    CHECK_HIP(hipMemcpy(d_cns, cns.data(), sizeof(int) * cns.size(), hipMemcpyHostToDevice));
+    CHECK_HIP(hipMemcpy(d_sel, sel.data(), sizeof(int) * sel.size(), hipMemcpyHostToDevice));
+    CHECK_HIP(hipMemcpy(d_two, two.data(), sizeof(int) * B, hipMemcpyHostToDevice));
+    ran_pieces.reserve((size_t)(2 * n_calls + 3) * B);        // never reallocated: pieces are copied into it asynchronously
+  }
   hipStream_t st;
   CHECK_HIP(hipStreamCreate(&st));
   double sec = 0.0, sec_walk = 0.0;
   for (int rep = 0; rep < 2; ++rep) {                          // the second pass is the timed one
     CHECK_HIP(hipMemcpyAsync(d_states, states.data(), sizeof(wg_dimitrov_state_t) * B, hipMemcpyHostToDevice, st));
     CHECK_HIP(hipStreamSynchronize(st));
+    if (online) {
+      // what the host knows of the fleet: every gait's samples (cur), which have ended, the samples the queues hold (done)
+      std::vector<int> cur(B, 0), done(B, 0);
+      std::vector<char> ended(B, 0);
+      double t = 0.0;
+      int ticks = 0;
+      ran_pieces.clear();
+      for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+      ev.clear();
+      // the queues up to the feet's new lengths, then the ticks that became safe: those whose N instants lie at or before the
+      // last sample of the shortest gait still walking (a gait that has ended has its final queue)
+      auto grow_and_walk = [&]() -> int {
+        int first = done[0], have = -1;
+        for (int g = 0; g < B; ++g) {
+          first = done[g] < first ? done[g] : first;
+          if (!ended[g] && (have < 0 || cur[g] < have)) have = cur[g];
+          done[g] = cur[g];
+        }
+        if (int rc = wg_foot_constraints_append_dev(B, lcap, first, d_done, d_len, d_time, d_left, d_lty, d_right, 0.24, 0.138, 0.02,
+                                                    0.02, qcap, d_queues, d_ts, d_te, d_count, st)) return rc;
+        int n = K - ticks;
+        if (have > 0) {
+          const int safe = wg_dimitrov_walk_safe_ticks(t, time[have - 1]);
+          if (safe < 0) return safe;
+          n = safe < n ? safe : n;
+        }
+        if (n <= 0) return WG_OK;
+        hipEvent_t e0, e1;
+        if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return WG_ERR_HIP;
+        ev.push_back(e0); ev.push_back(e1);
+        (void)hipEventRecord(e0, st);
+        if (int rc = wg_dimitrov_walk_dev(B, qcap, d_queues, d_ts, d_te, d_count, t, n, d_states, nullptr, d_ran, 0, st)) return rc;
+        (void)hipEventRecord(e1, st);
+        ran_pieces.resize(ran_pieces.size() + B);             // ran_out is cleared by every walk: kept piece by piece, ORed below
+        if (hipMemcpyAsync(ran_pieces.data() + ran_pieces.size() - B, d_ran, sizeof(int) * B, hipMemcpyDeviceToHost, st) != hipSuccess) return WG_ERR_HIP;
+        t = wg_dimitrov_walk_time(t, n);
+        ticks += n;
+        return WG_OK;
+      };
+      auto end_those_out_of_steps = [&](int c) -> int {
+        bool any = false;
+        for (int g = 0; g < B; ++g)
+          if (sel[(size_t)c * B + g]) { any = true; ended[g] = 1; cur[g] = len_ended[g]; }
+        if (!any) return WG_OK;
+        if (int rc = wg_zmpdisc_end_dev(&zm, B, d_sel + (size_t)c * B, lcap, nullptr, nullptr, nullptr, nullptr, d_left, d_lty, d_right,
+                                        nullptr, d_walk, d_len, st)) return rc;
+        return grow_and_walk();
+      };
+      CHECK_HIP(hipMemsetAsync(d_done, 0, sizeof(int) * B, st));
+      CHECK_HIP(hipStreamSynchronize(st));
+      const auto t0 = std::chrono::steady_clock::now();
+      CHECK_WG(wg_zmpdisc_begin_dev(&zm, B, S, d_steps, d_two, d_feet, lcap, nullptr, nullptr, nullptr, nullptr, d_left, d_lty, d_right,
+                                    nullptr, d_walk, d_len, st));
+      for (int g = 0; g < B; ++g) cur[g] = len_after[g];
+      CHECK_WG(grow_and_walk());
+      CHECK_WG(end_those_out_of_steps(0));
+      for (int c = 0; c < n_calls; ++c) {
+        CHECK_WG(wg_zmpdisc_append_dev(&zm, B, online, d_chunks + (size_t)c * B * online, d_cns + (size_t)c * B, lcap, nullptr, nullptr,
+                                       nullptr, nullptr, d_left, d_lty, d_right, nullptr, d_walk, d_len, st));
+        for (int g = 0; g < B; ++g)
+          if (!ended[g]) cur[g] = len_after[(size_t)(c + 1) * B + g];
+        CHECK_WG(grow_and_walk());
+        CHECK_WG(end_those_out_of_steps(c + 1));
+      }
+      CHECK_HIP(hipStreamSynchronize(st));
+      sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+      if (ticks != K) { fprintf(stderr, "FAILED: walked %d ticks of %d\n", ticks, K); return 1; }
+      sec_walk = 0.0;
+      for (size_t i = 0; i + 1 < ev.size(); i += 2) { float ms = 0.f; CHECK_HIP(hipEventElapsedTime(&ms, ev[i], ev[i + 1])); sec_walk += ms * 1e-3; }
+      std::vector<int> len_h(B);
+      CHECK_HIP(hipMemcpy(len_h.data(), d_len, sizeof(int) * B, hipMemcpyDeviceToHost));
+      for (int g = 0; g < B; ++g)                              // every gait must have arrived at the whole sequence's length
+        if (len_h[g] != len_ended[g] || !ended[g]) { fprintf(stderr, "FAILED: gait %d ended with length %d, not %d\n", g, len_h[g], len_ended[g]); return 1; }
+      continue;
+    }
     const auto t0 = std::chrono::steady_clock::now();
     CHECK_WG(wg_zmpdisc_full_batch_dev(&zm, B, S, d_steps, d_ns, d_feet, lcap, nullptr, nullptr, nullptr, nullptr, d_left, d_lty, d_right,
                                        nullptr, d_len, st));
@@ -135,6 +258,7 @@ int main(int argc, char **argv) {
   CHECK_HIP(hipMemcpy(states.data(), d_states, sizeof(wg_dimitrov_state_t) * B, hipMemcpyDeviceToHost));
   CHECK_HIP(hipMemcpy(count.data(), d_count, sizeof(int) * B, hipMemcpyDeviceToHost));
   CHECK_HIP(hipMemcpy(ran.data(), d_ran, sizeof(int) * B, hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < ran_pieces.size(); ++i) ran[i % B] |= ran_pieces[i];
   int n_ran = 0, max_count = 0;
   for (int g = 0; g < B; ++g) {
     if (count[g] < 1 || count[g] > qcap) { fprintf(stderr, "FAILED: gait %d: %d polytopes (capacity %d)\n", g, count[g], qcap); return 1; }

@@ -136,6 +136,12 @@ def lib():
             _lib.wg_dimitrov_select_polys_dev.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_double] + [C.c_void_p] * 3
             _lib.wg_dimitrov_walk_dev.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_double, C.c_int] + \
                 [C.c_void_p] * 3 + [C.c_int, C.c_void_p]
+        if hasattr(_lib, "wg_foot_constraints_append_dev"):  # absent from older experiment builds (WG_LIB_PATH, A/B runs)
+            _lib.wg_foot_constraints_append_dev.argtypes = [C.c_int] * 3 + [C.c_void_p] * 6 + [C.c_double] * 4 + [C.c_int] + \
+                [C.c_void_p] * 5
+            _lib.wg_dimitrov_walk_time.argtypes = [C.c_double, C.c_int]
+            _lib.wg_dimitrov_walk_time.restype = C.c_double
+            _lib.wg_dimitrov_walk_safe_ticks.argtypes = [C.c_double, C.c_double]
         # contexts: NAME_ctx(ctx, args...) for every entry point NAME(args...) that keeps or stages device-side state
         _lib.wg_ctx_create.argtypes = [C.c_int, C.c_void_p]
         _lib.wg_ctx_destroy.argtypes = [C.c_void_p]
@@ -165,7 +171,8 @@ CTX_ENTRY_POINTS = ("wg_set_overlap_strict", "wg_overlap_serialised", "wg_qp_sol
                     "wg_preview_run_batch", "wg_preview_run_batch_dev", "wg_gramian_batch", "wg_gramian_batch_dev",
                     "wg_zmpdisc_batch", "wg_zmpdisc_batch_dev", "wg_zmpdisc_full_batch_dev", "wg_foot_constraints_batch_dev",
                     "wg_zmpdisc_begin_dev", "wg_zmpdisc_append_dev", "wg_zmpdisc_end_dev",
-                    "wg_dimitrov_select_polys_dev", "wg_dimitrov_walk_dev")
+                    "wg_dimitrov_select_polys_dev", "wg_dimitrov_walk_dev", "wg_foot_constraints_append_dev",
+                    "wg_dimitrov_walk_time", "wg_dimitrov_walk_safe_ticks")
 
 
 class Context:
@@ -711,6 +718,17 @@ def foot_constraints_batch_dev(B, lcap, length_ptr, time_ptr, left_tm_ptr, left_
                                                stream))
 
 
+def foot_constraints_append_dev(B, lcap, first_sample, done_ptr, length_ptr, time_ptr, left_tm_ptr, left_type_tm_ptr, right_tm_ptr,
+                                sole_w, sole_h, constraint_x, constraint_y, qcap, queues_ptr, t_start_ptr, t_end_ptr, count_ptr,
+                                stream=None):
+    """the same queues grown on line: samples [done[b], length[b]) of every gait are added, done[b] = length[b] afterwards;
+    first_sample is a host-side lower bound on every done[b] (0 is always valid)"""
+    _check(lib().wg_foot_constraints_append_dev(int(B), int(lcap), int(first_sample), done_ptr, length_ptr, time_ptr, left_tm_ptr,
+                                                left_type_tm_ptr, right_tm_ptr, float(sole_w), float(sole_h), float(constraint_x),
+                                                float(constraint_y), int(qcap), queues_ptr, t_start_ptr, t_end_ptr, count_ptr,
+                                                stream))
+
+
 def dimitrov_select_polys_dev(B, qcap, queues_ptr, t_start_ptr, t_end_ptr, count_ptr, t0, polys_ptr, ran_out_ptr=None,
                               stream=None):
     """the queue walk of one tick: polys [B][N] for wg_dimitrov_tick_batch_dev, ran_out [B] or None"""
@@ -727,6 +745,21 @@ def dimitrov_walk_dev(B, qcap, queues_ptr, t_start_ptr, t_end_ptr, count_ptr, t0
     """n_ticks x { select at t; tick; t += T } on one stream; outs [n_ticks][B] or None, ran_out [B] or None"""
     _check(lib().wg_dimitrov_walk_dev(int(B), int(qcap), queues_ptr, t_start_ptr, t_end_ptr, count_ptr, float(t0), int(n_ticks),
                                       states_ptr, outs_ptr, ran_out_ptr, int(max_iter), stream))
+
+
+def dimitrov_walk_time(t0, n_ticks):
+    """the t at which tick n_ticks of a walk started at t0 selects (the walk's own repeated addition of the configured T)"""
+    t = float(lib().wg_dimitrov_walk_time(float(t0), int(n_ticks)))
+    if t != t:
+        raise WgError("dimitrov_walk_time: " + lib().wg_last_error().decode())
+    return t
+
+
+def dimitrov_walk_safe_ticks(t0, t_have):
+    """ticks from t0 on whose N previewed instants all lie at or before t_have"""
+    n = int(lib().wg_dimitrov_walk_safe_ticks(float(t0), float(t_have)))
+    _check(min(n, 0))
+    return n
 
 
 # ---- invariant Hessian block on the matrix cores ----
