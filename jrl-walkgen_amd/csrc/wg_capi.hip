@@ -1274,6 +1274,38 @@ void select_launch(wg_ctx *ctx, int B, int qcap, const wg_zmp_polytope_t *queues
   hipLaunchKernelGGL(wg::wg_dimitrov_select_kernel, dim3((B + 3) / 4), dim3(256), 0, st, B, qcap, queues, t_start, t_end, count, t0,
                      ctx->dim_host->N, ctx->dim_host->T, polys, ran_out, sticky);
 }
+
+// What wg_foot_constraints_batch_dev (res = false: first_sample 0, no done) and _append_dev (res = true) share: the checks, the
+// half sole, the kernels' arguments, the chunks from first_sample's on, the claim of the context's buffer -- the per-chunk counts
+// live there between the two passes (and two ints per gait behind them for a resumed call): one launch at a time uses it --
+// and the mark behind the launches, which `passes` issues.
+template <class Passes>
+int footcons_launch(wg_ctx *ctx, bool res, int B, int lcap, int first_sample, const int *done, const int *length, const double *time, const double *left_tm, const int *left_type_tm, const double *right_tm, double sole_w, double sole_h, double constraint_x, double constraint_y, int qcap, wg_zmp_polytope_t *queues, double *t_start, double *t_end, int *count, void *hip_stream, Passes passes) {
+  if (int rc = use_ctx(ctx)) return rc;
+  if (B < 0 || qcap < 0 || first_sample < 0) return fail(WG_ERR_BAD_ARG, res ? "need B >= 0, qcap >= 0, first_sample >= 0" : "need B >= 0, qcap >= 0");
+  if (B == 0) return WG_OK;
+  if (qcap > 0 && (!queues || !t_start || !t_end)) return fail(WG_ERR_BAD_ARG, "need non-null queues and intervals for qcap > 0");
+  if (lcap < 1 || (res && !done) || !length || !time || !left_tm || !left_type_tm || !right_tm || !count)
+    return fail(WG_ERR_BAD_ARG, "need lcap >= 1, non-null %slengths, times, feet arrays and counts", res ? "done, " : "");
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  double hw = sole_w * 0.5, hh = sole_h * 0.5;
+  hh -= constraint_y;
+  hw -= constraint_x;
+  const wg::FcIn I{B, lcap, length, time, left_tm, right_tm, left_type_tm, hw, hh};
+  const wg::FcOut Q{qcap, queues, t_start, t_end, count};
+  const int chunk0 = first_sample / wg::kFcChunk, chunks = (lcap + wg::kFcChunk - 1) / wg::kFcChunk - chunk0;
+  if (chunks > 65535) {
+    if (res) return fail(WG_ERR_TOO_LARGE, "lcap = %d, first_sample = %d: more than 65535 chunks of %d samples", lcap, first_sample, wg::kFcChunk);
+    return fail(WG_ERR_TOO_LARGE, "lcap = %d: more than 65535 chunks of %d samples", lcap, wg::kFcChunk);
+  }
+  std::lock_guard<std::mutex> launch_lk(ctx->launch_mu);
+  if (int rc = slot_claim(ctx, ctx->fc_order, st, "foot-constraints")) return rc;
+  const size_t sB = (size_t)B, n_cnt = (size_t)(chunks > 0 ? chunks : 0) * sB;
+  if (int rc = ctx->fc_buf.reserve((n_cnt + (res ? 2 * sB : 0)) * sizeof(int))) return rc;
+  if (int rc = passes(I, Q, static_cast<int *>(ctx->fc_buf.p), n_cnt, chunk0, chunks, st)) return rc;
+  HIP_TRY(hipGetLastError());
+  return slot_mark(ctx->fc_order, st);
+}
 }  // namespace
 
 extern "C" {
@@ -1281,65 +1313,32 @@ extern "C" {
 int wg_foot_constraints_chunk(void) { return wg::kFcChunk; }
 
 int wg_foot_constraints_batch_dev_ctx(wg_ctx_t *ctx, int B, int lcap, const int *length, const double *time, const double *left_tm, const int *left_type_tm, const double *right_tm, double sole_w, double sole_h, double constraint_x, double constraint_y, int qcap, wg_zmp_polytope_t *queues, double *t_start, double *t_end, int *count, void *hip_stream) {
-  if (int rc = use_ctx(ctx)) return rc;
-  if (B < 0 || qcap < 0) return fail(WG_ERR_BAD_ARG, "need B >= 0, qcap >= 0");
-  if (B == 0) return WG_OK;
-  if (qcap > 0 && (!queues || !t_start || !t_end)) return fail(WG_ERR_BAD_ARG, "need non-null queues and intervals for qcap > 0");
-  if (lcap < 1 || !length || !time || !left_tm || !left_type_tm || !right_tm || !count)
-    return fail(WG_ERR_BAD_ARG, "need lcap >= 1, non-null lengths, times, feet arrays and counts");
-  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  double hw = sole_w * 0.5, hh = sole_h * 0.5;
-  hh -= constraint_y;
-  hw -= constraint_x;
-  const wg::FcIn I{B, lcap, length, time, left_tm, right_tm, left_type_tm, hw, hh};
-  const wg::FcOut Q{qcap, queues, t_start, t_end, count};
-  const int chunks = (lcap + wg::kFcChunk - 1) / wg::kFcChunk;
-  if (chunks > 65535) return fail(WG_ERR_TOO_LARGE, "lcap = %d: more than 65535 chunks of %d samples", lcap, wg::kFcChunk);
-  // the per-chunk counts live in a buffer of the context between the two passes: one launch at a time uses it
-  std::lock_guard<std::mutex> launch_lk(ctx->launch_mu);
-  if (int rc = slot_claim(ctx, ctx->fc_order, st, "foot-constraints")) return rc;
-  if (int rc = ctx->fc_buf.reserve((size_t)chunks * (size_t)B * sizeof(int))) return rc;
-  int *cnt = static_cast<int *>(ctx->fc_buf.p);
-  const dim3 grid((B + 63) / 64, chunks);
-  HIP_TRY(hipMemsetAsync(count, 0, (size_t)B * sizeof(int), st));
-  hipLaunchKernelGGL((wg::wg_footcons_kernel<false, false>), grid, dim3(64), 0, st, I, Q, cnt, wg::FcRes{});
-  hipLaunchKernelGGL((wg::wg_footcons_kernel<true, false>), grid, dim3(64), 0, st, I, Q, cnt, wg::FcRes{});
-  HIP_TRY(hipGetLastError());
-  return slot_mark(ctx->fc_order, st);
+  return footcons_launch(ctx, false, B, lcap, 0, nullptr, length, time, left_tm, left_type_tm, right_tm, sole_w, sole_h, constraint_x, constraint_y, qcap, queues, t_start, t_end, count, hip_stream,
+                         [&](const wg::FcIn &I, const wg::FcOut &Q, int *cnt, size_t, int, int chunks, hipStream_t st) -> int {
+    const dim3 grid((B + 63) / 64, chunks);
+    HIP_TRY(hipMemsetAsync(count, 0, (size_t)B * sizeof(int), st));
+    hipLaunchKernelGGL((wg::wg_footcons_kernel<false, false>), grid, dim3(64), 0, st, I, Q, cnt, wg::FcRes{});
+    hipLaunchKernelGGL((wg::wg_footcons_kernel<true, false>), grid, dim3(64), 0, st, I, Q, cnt, wg::FcRes{});
+    return WG_OK;
+  });
 }
 
 int wg_foot_constraints_append_dev_ctx(wg_ctx_t *ctx, int B, int lcap, int first_sample, int *done, const int *length, const double *time, const double *left_tm, const int *left_type_tm, const double *right_tm, double sole_w, double sole_h, double constraint_x, double constraint_y, int qcap, wg_zmp_polytope_t *queues, double *t_start, double *t_end, int *count, void *hip_stream) {
-  if (int rc = use_ctx(ctx)) return rc;
-  if (B < 0 || qcap < 0 || first_sample < 0) return fail(WG_ERR_BAD_ARG, "need B >= 0, qcap >= 0, first_sample >= 0");
-  if (B == 0) return WG_OK;
-  if (qcap > 0 && (!queues || !t_start || !t_end)) return fail(WG_ERR_BAD_ARG, "need non-null queues and intervals for qcap > 0");
-  if (lcap < 1 || !done || !length || !time || !left_tm || !left_type_tm || !right_tm || !count)
-    return fail(WG_ERR_BAD_ARG, "need lcap >= 1, non-null done, lengths, times, feet arrays and counts");
-  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  double hw = sole_w * 0.5, hh = sole_h * 0.5;
-  hh -= constraint_y;
-  hw -= constraint_x;
-  const wg::FcIn I{B, lcap, length, time, left_tm, right_tm, left_type_tm, hw, hh};
-  const wg::FcOut Q{qcap, queues, t_start, t_end, count};
   // chunks that lie wholly below first_sample hold no new sample of any gait: not launched (a gait whose done[b] is below it
-  // is refused on the device).  first_sample >= lcap: every gait sits out or is refused, the first kernel alone says so
-  const int chunk0 = first_sample / wg::kFcChunk, chunks = (lcap + wg::kFcChunk - 1) / wg::kFcChunk - chunk0;
-  if (chunks > 65535) return fail(WG_ERR_TOO_LARGE, "lcap = %d, first_sample = %d: more than 65535 chunks of %d samples", lcap, first_sample, wg::kFcChunk);
-  // the per-chunk counts, and done[b] / count[b] as they were on entry, live in the buffer of the batch call: ordered like it
-  std::lock_guard<std::mutex> launch_lk(ctx->launch_mu);
-  if (int rc = slot_claim(ctx, ctx->fc_order, st, "foot-constraints")) return rc;
-  const size_t sB = (size_t)B, n_cnt = (size_t)(chunks > 0 ? chunks : 0) * sB;
-  if (int rc = ctx->fc_buf.reserve((n_cnt + 2 * sB) * sizeof(int))) return rc;
-  int *cnt = static_cast<int *>(ctx->fc_buf.p), *from = cnt + n_cnt, *base = from + sB;
-  hipLaunchKernelGGL(wg::wg_footcons_resume_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, lcap, first_sample, length, done, count, from, base);
-  if (chunks > 0) {
-    const wg::FcRes Z{from, base, done, chunk0};
-    const dim3 grid((B + 63) / 64, chunks);
-    hipLaunchKernelGGL((wg::wg_footcons_kernel<false, true>), grid, dim3(64), 0, st, I, Q, cnt, Z);
-    hipLaunchKernelGGL((wg::wg_footcons_kernel<true, true>), grid, dim3(64), 0, st, I, Q, cnt, Z);
-  }
-  HIP_TRY(hipGetLastError());
-  return slot_mark(ctx->fc_order, st);
+  // is refused on the device).  first_sample >= lcap: every gait sits out or is refused, the first kernel alone says so.
+  // done[b] / count[b] as they were on entry live behind the per-chunk counts
+  return footcons_launch(ctx, true, B, lcap, first_sample, done, length, time, left_tm, left_type_tm, right_tm, sole_w, sole_h, constraint_x, constraint_y, qcap, queues, t_start, t_end, count, hip_stream,
+                         [&](const wg::FcIn &I, const wg::FcOut &Q, int *cnt, size_t n_cnt, int chunk0, int chunks, hipStream_t st) -> int {
+    int *from = cnt + n_cnt, *base = from + (size_t)B;
+    hipLaunchKernelGGL(wg::wg_footcons_resume_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, lcap, first_sample, length, done, count, from, base);
+    if (chunks > 0) {
+      const wg::FcRes Z{from, base, done, chunk0};
+      const dim3 grid((B + 63) / 64, chunks);
+      hipLaunchKernelGGL((wg::wg_footcons_kernel<false, true>), grid, dim3(64), 0, st, I, Q, cnt, Z);
+      hipLaunchKernelGGL((wg::wg_footcons_kernel<true, true>), grid, dim3(64), 0, st, I, Q, cnt, Z);
+    }
+    return WG_OK;
+  });
 }
 
 int wg_dimitrov_select_polys_dev_ctx(wg_ctx_t *ctx, int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count, double t0, wg_zmp_polytope_t *polys, int *ran_out, void *hip_stream) {

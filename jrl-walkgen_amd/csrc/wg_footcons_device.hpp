@@ -8,7 +8,7 @@
 //   wg_dimitrov_select_kernel          the queue walk of one tick (wg_dimitrov_select_polys_dev, wg_dimitrov_walk_dev)
 //       ZMPConstrainedQPFastFormulation::BuildConstraintMatrices  ZMPConstrainedQPFastFormulation.cpp:785-796, 822-835
 //
-// Queues.  The host version (wg_footcons.cpp) walks one gait sample by sample.  Here the inputs are the time-major arrays
+// Queues.  The host call (wg_footcons.cpp) walks one gait sample by sample.  Here the inputs are the time-major arrays
 // wg_zmpdisc_full_batch_dev writes ([sample][component][gait]): lanes are gaits, so that every row a wave reads is one 512-byte
 // line, and the time axis is split across blocks -- grid = (gait groups of 64) x (chunks of kFcChunk samples) -- because one
 // lane walking all 2-3 k samples of its gait is 64 waves on 1024 SIMDs with one dependent load after the other.  What makes
@@ -27,23 +27,16 @@
 // one's t_end, which the next call overwrites once -- with the time of the first new change (the lane that finds it, as above) or
 // with the new last sample's.  count[b] on entry is the queue position of the first new change; pass 1's atomics change it, so
 // wg_footcons_resume_kernel leaves it, and done[b], behind the per-chunk counts where both passes read them.
-// Same operation order as wg_footcons.cpp; the library is built with -ffp-contract=off, / and sqrt are IEEE on both sides and
-// sin / cos are include/wg_trig.h: the same bytes.
+// The geometry -- classification, corners, hull, half planes, the polytope fill -- is wg_footcons_geom.hpp, which the host call
+// compiles too: the same bytes.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "../../include/wg_mpc.h"
-#ifndef WG_TRIG_FN
-#define WG_TRIG_FN __host__ __device__ static inline
-#endif
-#include "../../include/wg_trig.h"
+#include "wg_footcons_geom.hpp"
 
 namespace wg {
 
 constexpr int kFcChunk = 64;             // samples per (gait, chunk) lane: 2 bits of support state each in two 64-bit registers
-constexpr int kFcSlots = 17;             // hull scratch per lane: 9 points (corners, then the hull) + 8 (the ordered candidates)
-constexpr double kFcPi = 3.14159265358979323846;
-enum { kFcInherit = 0, kFcRight = 1, kFcLeft = 2, kFcDouble = 3 };   // 1..3: the reference's states
 
 struct FcIn {
   int B, lcap;
@@ -59,150 +52,6 @@ struct FcOut {
   double *t_start, *t_end;               // [B][qcap]
   int *count;                            // B, zeroed before pass 1
 };
-
-// the state the reference's three tests give sample (stepType, left z, right z), or kFcInherit when none of them holds
-__device__ __forceinline__ int fc_classify(int ltype, double lz, double rz) {
-  const double lifting = 0.00001;
-  if (ltype >= 10) return kFcDouble;
-  if (lz > lifting) return kFcLeft;      // the reference's state 2: the LEFT foot is in the air
-  if (rz > lifting) return kFcRight;
-  if (rz < lifting && lz < lifting) return kFcDouble;
-  return kFcInherit;
-}
-
-// one lane's hull scratch: point s at [2 s + {0, 1}][lane]
-struct FcPts {
-  double *base;
-  __device__ __forceinline__ double &x(int s) const { return base[(2 * s) * 64]; }
-  __device__ __forceinline__ double &y(int s) const { return base[(2 * s + 1) * 64]; }
-};
-
-__device__ __forceinline__ double fc_cross(double ox, double oy, double ax, double ay, double bx, double by) {
-  const double x1 = ax - ox, x2 = bx - ox, y1 = ay - oy, y2 = by - oy;
-  return x1 * y2 - x2 * y1;
-}
-
-// sole_corners of wg_footcons.cpp into slots s0 .. s0 + 3 (counter-clockwise)
-__device__ inline void fc_corners(const FcPts &P, int s0, double fx, double fy, double theta, double hw, double hh) {
-  const double s = wg_sin(theta * kFcPi / 180.0), c = wg_cos(theta * kFcPi / 180.0);
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    const double sx = j < 2 ? 1.0 : -1.0, sy = (j == 1 || j == 2) ? 1.0 : -1.0;
-    P.x(s0 + j) = fx + (sx * hw * c - sy * hh * s);
-    P.y(s0 + j) = fy + (sx * hw * s + sy * hh * c);
-  }
-}
-
-// graham_hull of wg_footcons.cpp: the 8 points in slots 0..7 -> the hull in slots 0.. (returned size; 0: fewer than two
-// directions).  Slots 9..16 hold the candidates in ascending polar angle about the lowest point.
-__device__ inline int fc_hull8(const FcPts &P) {
-  const int O = 9;
-  double p0x = P.x(0), p0y = P.y(0);
-  for (int i = 0; i < 8; i++)
-    if (P.y(i) < p0y) { p0x = P.x(i); p0y = P.y(i); }
-  int no = 0;
-  for (int i = 0; i < 8; i++) {
-    const double px = P.x(i), py = P.y(i);
-    bool insert = true;
-    for (int k = 0; k < no;) {
-      const double kx = P.x(O + k), ky = P.y(O + k);
-      if (fc_cross(p0x, p0y, kx, ky, px, py) == 0.0) {
-        const double dk = sqrt((kx - p0x) * (kx - p0x) + (ky - p0y) * (ky - p0y));
-        const double dp = sqrt((px - p0x) * (px - p0x) + (py - p0y) * (py - p0y));
-        if (dk <= dp) {
-          for (int q = k; q < no - 1; q++) { P.x(O + q) = P.x(O + q + 1); P.y(O + q) = P.y(O + q + 1); }
-          no--;
-          continue;
-        }
-        insert = false;
-      }
-      k++;
-    }
-    if (!insert) continue;
-    int pos = 0;
-    bool equivalent = false;
-    for (; pos < no; pos++) {
-      const double kx = P.x(O + pos), ky = P.y(O + pos);
-      if (fc_cross(p0x, p0y, px, py, kx, ky) > 0.0) break;            // p orders before the candidate
-      if (!(fc_cross(p0x, p0y, kx, ky, px, py) > 0.0)) equivalent = true;
-    }
-    if (!equivalent) {
-      for (int q = no; q > pos; q--) { P.x(O + q) = P.x(O + q - 1); P.y(O + q) = P.y(O + q - 1); }
-      P.x(O + pos) = px; P.y(O + pos) = py;
-      no++;
-    }
-  }
-  if (no < 2) return 0;
-  int nh = 0;
-  P.x(nh) = p0x; P.y(nh) = p0y; nh++;
-  P.x(nh) = P.x(O); P.y(nh) = P.y(O); nh++;
-  P.x(nh) = P.x(O + 1); P.y(nh) = P.y(O + 1); nh++;
-  for (int it = 2; it < no; it++) {
-    const double ix = P.x(O + it), iy = P.y(O + it);
-    while (nh >= 2 && !(fc_cross(P.x(nh - 2), P.y(nh - 2), P.x(nh - 1), P.y(nh - 1), ix, iy) > 0.0)) nh--;
-    P.x(nh) = ix; P.y(nh) = iy; nh++;
-  }
-  return nh;
-}
-
-// half_plane of wg_footcons.cpp: the half plane left of the edge p -> q as a x + c y + b >= 0, offset taken at (ax_, ay_)
-__device__ __forceinline__ void fc_half_plane(double px, double py, double qx, double qy, double ax_, double ay_, double &a,
-                                              double &c, double &b) {
-  if (fabs(qx - px) > 1e-7) {
-    double x1, y1, x2, y2, lmul = -1.0;
-    if (qx < px) {
-      lmul = 1.0;
-      x1 = qx; y1 = qy; x2 = px; y2 = py;
-    } else {
-      x1 = px; y1 = py; x2 = qx; y2 = qy;
-    }
-    a = (y2 - y1) / (x2 - x1);
-    b = (ay_ - a * ax_);
-    a = lmul * a;
-    b = lmul * b;
-    c = -lmul;
-  } else {
-    c = 0.0;
-    a = -1.0;
-    b = qx;
-    if (qy < py) {
-      a = -a;
-      b = -b;
-    }
-  }
-}
-
-// polytope_of of wg_footcons.cpp on the hull in slots 0..n-1, written straight to the queue entry (every byte of it); the rows'
-// (a, c) go through slots 9.. for FindSimilarConstraints.  false: the reference's "not a polytope" (n < 2 or n > 8)
-__device__ inline bool fc_polytope(const FcPts &P, int n, wg_zmp_polytope_t *out) {
-  if (n < 2 || n > WG_POLY_MAX_ROWS) return false;
-  const int O = 9;
-  double cx = 0.0, cy = 0.0;
-  for (int i = 0; i < WG_POLY_MAX_ROWS; i++) {
-    double a = 0.0, c = 0.0, b = 0.0;
-    if (i < n) {
-      cx += P.x(i);
-      cy += P.y(i);
-      if (i < n - 1)
-        fc_half_plane(P.x(i), P.y(i), P.x(i + 1), P.y(i + 1), P.x(i), P.y(i), a, c, b);     // offset at the edge's first point
-      else
-        fc_half_plane(P.x(n - 1), P.y(n - 1), P.x(0), P.y(0), P.x(0), P.y(0), a, c, b);    // closing edge: at its last point
-      P.x(O + i) = a; P.y(O + i) = c;
-    }
-    out->A[i][0] = a; out->A[i][1] = c; out->B[i] = b;
-  }
-  out->nrows = n;
-  out->pad_ = 0;
-  out->centre[0] = cx / (double)n;
-  out->centre[1] = cy / (double)n;
-  const int half = n == 4 ? 2 : (n == 6 ? 3 : 0);         // FindSimilarConstraints knows rectangles and hexagons
-  for (int k = 0; k < WG_POLY_MAX_ROWS; k++) {
-    int sim = 0;
-    if (k >= half && k < 2 * half && P.x(O + k - half) == -P.x(O + k) && P.y(O + k - half) == -P.y(O + k)) sim = -half;
-    out->similar[k] = sim;
-  }
-  return true;
-}
 
 // what a resumed call (wg_foot_constraints_append_dev) adds: where each gait resumes, snapshot by wg_footcons_resume_kernel before
 // pass 1's atomics change count[b]
@@ -297,7 +146,7 @@ wg_footcons_kernel(FcIn I, FcOut Q, int *__restrict__ cnt /* [chunks][B] */, FcR
     if constexpr (kRes) q = Z.base[b];
     for (int c = cfirst; c < crel; c++) q += cnt[(size_t)c * sB + b];
   }
-  const FcPts P{fc_lds + lane};
+  const FcPts<64> P{fc_lds + lane};
   int found = 0;
   for (int k = k0; k < n; k++) {
     if (kBuild && found == own) break;

@@ -15,20 +15,14 @@
 // --fleet FILE runs a fleet somebody else drew instead of the built-in one (tests/test_dimitrov_walk_gpu.py compares the
 // checksum with its own run of the same fleet): int32 B, int32 smax, wg_zmpdisc_model_t, B x smax wg_rel_step_t, B int32
 // n_steps, B x 6 doubles init_feet, in the machine's byte order.
-#include <hip/hip_runtime.h>
-
 #include <chrono>
-#include <cstdint>
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <random>
-#include <vector>
 
-#include "../../include/wg_mpc.h"
+#include "wg_fleet.hpp"
 
-#define CHECK_HIP(e) do { hipError_t r_ = (e); if (r_ != hipSuccess) { fprintf(stderr, "FAILED: %s: %s\n", #e, hipGetErrorString(r_)); return 1; } } while (0)
-#define CHECK_WG(e) do { int r_ = (e); if (r_ != WG_OK) { fprintf(stderr, "FAILED: %s: %s\n", #e, wg_last_error()); return 1; } } while (0)
+using wg_fleet::dev_alloc;
+using wg_fleet::dev_upload;
 
 int main(int argc, char **argv) {
   int B = 4096, S = 8, K = 40, solver = WG_DIMITROV_PLDP, online = 0;
@@ -99,67 +93,42 @@ int main(int argc, char **argv) {
   wg_rel_step_t *d_steps; int *d_ns, *d_len, *d_lty, *d_count, *d_ran; double *d_feet, *d_time, *d_left, *d_right, *d_ts, *d_te;
   wg_zmp_polytope_t *d_queues; wg_dimitrov_state_t *d_states;
   const size_t row = (size_t)lcap * B, nq = (size_t)B * qcap;
-  CHECK_HIP(hipMalloc((void **)&d_steps, sizeof(wg_rel_step_t) * steps.size()));
-  CHECK_HIP(hipMalloc((void **)&d_ns, sizeof(int) * B));
-  CHECK_HIP(hipMalloc((void **)&d_len, sizeof(int) * B));
-  CHECK_HIP(hipMalloc((void **)&d_count, sizeof(int) * B));
-  CHECK_HIP(hipMalloc((void **)&d_ran, sizeof(int) * B));
-  CHECK_HIP(hipMalloc((void **)&d_lty, sizeof(int) * row));
-  CHECK_HIP(hipMalloc((void **)&d_feet, sizeof(double) * feet.size()));
-  CHECK_HIP(hipMalloc((void **)&d_time, sizeof(double) * lcap));
-  CHECK_HIP(hipMalloc((void **)&d_left, sizeof(double) * 6 * row));
-  CHECK_HIP(hipMalloc((void **)&d_right, sizeof(double) * 6 * row));
-  CHECK_HIP(hipMalloc((void **)&d_ts, sizeof(double) * nq));
-  CHECK_HIP(hipMalloc((void **)&d_te, sizeof(double) * nq));
-  CHECK_HIP(hipMalloc((void **)&d_queues, sizeof(wg_zmp_polytope_t) * nq));
-  CHECK_HIP(hipMalloc((void **)&d_states, sizeof(wg_dimitrov_state_t) * B));
-  CHECK_HIP(hipMemcpy(d_steps, steps.data(), sizeof(wg_rel_step_t) * steps.size(), hipMemcpyHostToDevice));
-  CHECK_HIP(hipMemcpy(d_ns, n_steps.data(), sizeof(int) * B, hipMemcpyHostToDevice));
-  CHECK_HIP(hipMemcpy(d_feet, feet.data(), sizeof(double) * feet.size(), hipMemcpyHostToDevice));
-  CHECK_HIP(hipMemcpy(d_time, time.data(), sizeof(double) * lcap, hipMemcpyHostToDevice));
+  CHECK_HIP(dev_upload(&d_steps, steps));
+  CHECK_HIP(dev_upload(&d_ns, n_steps));
+  CHECK_HIP(dev_upload(&d_feet, feet));
+  CHECK_HIP(dev_upload(&d_time, time));
+  CHECK_HIP(dev_alloc(&d_len, B));
+  CHECK_HIP(dev_alloc(&d_count, B));
+  CHECK_HIP(dev_alloc(&d_ran, B));
+  CHECK_HIP(dev_alloc(&d_lty, row));
+  CHECK_HIP(dev_alloc(&d_left, 6 * row));
+  CHECK_HIP(dev_alloc(&d_right, 6 * row));
+  CHECK_HIP(dev_alloc(&d_ts, nq));
+  CHECK_HIP(dev_alloc(&d_te, nq));
+  CHECK_HIP(dev_alloc(&d_queues, nq));
+  CHECK_HIP(dev_alloc(&d_states, B));
   std::vector<wg_dimitrov_state_t> states(B);
   memset(states.data(), 0, sizeof(wg_dimitrov_state_t) * B);
   for (int g = 0; g < B; ++g) states[g].starting = 1;
-  // --online: the walk's state blobs, the steps after the first two regrouped call by call, [call][B][online], what each call
-  // leaves of every gait (host arithmetic: nothing is read back while the fleet walks), and each walk piece's ran_out
-  int S_max = 0;
-  for (int g = 0; g < B; ++g) S_max = n_steps[g] > S_max ? n_steps[g] : S_max;
-  const int n_calls = online ? (S_max - 2 + online - 1) / online : 0;
+  // --online: the walk's state blobs, the feeding plan (the steps after the first two regrouped call by call, what each call
+  // leaves of every gait, which gaits end behind it), and each walk piece's ran_out
+  wg_fleet::OnlinePlan plan;
   wg_zmpdisc_state_t *d_walk = nullptr; wg_rel_step_t *d_chunks = nullptr; int *d_cns = nullptr, *d_two = nullptr, *d_sel = nullptr, *d_done = nullptr;
-  std::vector<int> cns((size_t)n_calls * B), sel((size_t)(n_calls + 1) * B, 0), len_after((size_t)(n_calls + 1) * B), len_ended(B);
   std::vector<int> ran_pieces;
   std::vector<hipEvent_t> ev;
   if (online) {
-    std::vector<wg_rel_step_t> chunks((size_t)n_calls * B * online);
-    memset(chunks.data(), 0, sizeof(wg_rel_step_t) * chunks.size());
-    for (int g = 0; g < B; ++g) {
-      if (n_steps[g] < 2) { fprintf(stderr, "FAILED: gait %d: --online needs two steps to begin with\n", g); return 1; }
-      const wg_rel_step_t *sg = &steps[(size_t)g * S];
-      len_ended[g] = wg_zmpdisc_length_after(&zm, sg, n_steps[g], 1);
-      for (int c = 0; c <= n_calls; ++c) {                     // call 0 is the begin; sel: the gait is ended behind call c
-        const int given = 2 + c * online < n_steps[g] ? 2 + c * online : n_steps[g];
-        len_after[(size_t)c * B + g] = wg_zmpdisc_length_after(&zm, sg, given, 0);
-        sel[(size_t)c * B + g] = given == n_steps[g] && (c == 0 || 2 + (c - 1) * online < n_steps[g]);
-      }
-      for (int c = 0; c < n_calls; ++c) {
-        const int first = 2 + c * online, left = n_steps[g] - first, n = left < 0 ? 0 : (left < online ? left : online);
-        cns[(size_t)c * B + g] = n;
-        for (int i = 0; i < n; ++i) chunks[((size_t)c * B + g) * online + i] = sg[first + i];
-      }
-    }
-    std::vector<int> two(B, 2);
-    CHECK_HIP(hipMalloc((void **)&d_walk, sizeof(wg_zmpdisc_state_t) * B));
-    CHECK_HIP(hipMalloc((void **)&d_chunks, sizeof(wg_rel_step_t) * (chunks.size() ? chunks.size() : 1)));
-    CHECK_HIP(hipMalloc((void **)&d_cns, sizeof(int) * (cns.size() ? cns.size() : 1)));
-    CHECK_HIP(hipMalloc((void **)&d_sel, sizeof(int) * sel.size()));
-    CHECK_HIP(hipMalloc((void **)&d_two, sizeof(int) * B));
-    CHECK_HIP(hipMalloc((void **)&d_done, sizeof(int) * B));
-    CHECK_HIP(hipMemcpy(d_chunks, chunks.data(), sizeof(wg_rel_step_t) * chunks.size(), hipMemcpyHostToDevice));
-    CHECK_HIP(hipMemcpy(d_cns, cns.data(), sizeof(int) * cns.size(), hipMemcpyHostToDevice));
-    CHECK_HIP(hipMemcpy(d_sel, sel.data(), sizeof(int) * sel.size(), hipMemcpyHostToDevice));
-    CHECK_HIP(hipMemcpy(d_two, two.data(), sizeof(int) * B, hipMemcpyHostToDevice));
-    ran_pieces.reserve((size_t)(2 * n_calls + 3) * B);        // never reallocated: pieces are copied into it asynchronously
+    const int bad = wg_fleet::online_plan(zm, steps, n_steps, B, S, online, &plan);
+    if (bad >= 0) { fprintf(stderr, "FAILED: gait %d: --online needs two steps to begin with\n", bad); return 1; }
+    CHECK_HIP(dev_alloc(&d_walk, B));
+    CHECK_HIP(dev_upload(&d_chunks, plan.chunks));
+    CHECK_HIP(dev_upload(&d_cns, plan.cns));
+    CHECK_HIP(dev_upload(&d_sel, plan.sel));
+    CHECK_HIP(dev_upload(&d_two, std::vector<int>(B, 2)));
+    CHECK_HIP(dev_alloc(&d_done, B));
+    ran_pieces.reserve((size_t)(2 * plan.n_calls + 3) * B);   // never reallocated: pieces are copied into it asynchronously
   }
+  const int n_calls = plan.n_calls;
+  const std::vector<int> &sel = plan.sel, &len_after = plan.len_after, &len_ended = plan.len_ended;
   hipStream_t st;
   CHECK_HIP(hipStreamCreate(&st));
   double sec = 0.0, sec_walk = 0.0;
@@ -265,9 +234,7 @@ int main(int argc, char **argv) {
     n_ran += ran[g];
     max_count = count[g] > max_count ? count[g] : max_count;
   }
-  uint64_t h = 1469598103934665603ull;
-  const unsigned char *p = reinterpret_cast<const unsigned char *>(states.data());
-  for (size_t i = 0; i < sizeof(wg_dimitrov_state_t) * B; ++i) { h ^= p[i]; h *= 1099511628211ull; }
+  const uint64_t h = wg_fleet::fnv1a64(states.data(), sizeof(wg_dimitrov_state_t) * B);
   double far = 0.0;
   for (int g = 0; g < B; ++g) far = states[g].xk[0] > far ? states[g].xk[0] : far;
   printf("dimitrov_fleet: %d walks (<= %d steps, <= %d samples, <= %d polytopes) x %d ticks in %.2f ms = %.0f walks/s; the walk alone "

@@ -28,10 +28,9 @@
 #include <vector>
 
 #include "../../include/wg_mpc.h"
+#include "wg_fleet.hpp"
 #include "wg_rendezvous.hpp"
 
-#define CHECK_HIP(e) do { hipError_t r_ = (e); if (r_ != hipSuccess) { fprintf(stderr, "FAILED: %s: %s\n", #e, hipGetErrorString(r_)); return 1; } } while (0)
-#define CHECK_WG(e) do { int r_ = (e); if (r_ != WG_OK) { fprintf(stderr, "FAILED: %s: %s\n", #e, wg_last_error()); return 1; } } while (0)
 #define CHECK_NCCL(e) do { ncclResult_t r_ = (e); if (r_ != ncclSuccess) { fprintf(stderr, "FAILED: %s: %s\n", #e, ncclGetErrorString(r_)); return 1; } } while (0)
 
 static int env_int(const char *k, int dflt) { const char *e = getenv(k); return e ? atoi(e) : dflt; }

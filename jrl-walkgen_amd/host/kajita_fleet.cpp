@@ -9,19 +9,14 @@
 // (FNV-1a, 64 bit, over all of them) that both modes print -- are those of the whole-sequence mode.
 //
 //   kajita_fleet [--batch B] [--steps S] [--online K]
-#include <hip/hip_runtime.h>
-
 #include <chrono>
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <random>
-#include <vector>
 
-#include "../../include/wg_mpc.h"
+#include "wg_fleet.hpp"
 
-#define CHECK_HIP(e) do { hipError_t r_ = (e); if (r_ != hipSuccess) { fprintf(stderr, "FAILED: %s: %s\n", #e, hipGetErrorString(r_)); return 1; } } while (0)
-#define CHECK_WG(e) do { int r_ = (e); if (r_ != WG_OK) { fprintf(stderr, "FAILED: %s: %s\n", #e, wg_last_error()); return 1; } } while (0)
+using wg_fleet::dev_alloc;
+using wg_fleet::dev_upload;
 
 int main(int argc, char **argv) {
   int B = 4096, S = 16, K = 0;
@@ -67,38 +62,26 @@ int main(int argc, char **argv) {
   const int Lrun = L - nl + 1;
 
   wg_rel_step_t *d_steps; int *d_ns, *d_len; double *d_feet, *d_zx, *d_zy, *d_state, *d_com;
-  CHECK_HIP(hipMalloc((void **)&d_steps, sizeof(wg_rel_step_t) * steps.size()));
-  CHECK_HIP(hipMalloc((void **)&d_ns, sizeof(int) * B));
-  CHECK_HIP(hipMalloc((void **)&d_len, sizeof(int) * B));
-  CHECK_HIP(hipMalloc((void **)&d_feet, sizeof(double) * feet.size()));
-  CHECK_HIP(hipMalloc((void **)&d_zx, sizeof(double) * (size_t)L * B));
-  CHECK_HIP(hipMalloc((void **)&d_zy, sizeof(double) * (size_t)L * B));
-  CHECK_HIP(hipMalloc((void **)&d_state, sizeof(double) * 8 * B));
-  CHECK_HIP(hipMalloc((void **)&d_com, sizeof(double) * (size_t)Lrun * 6 * B));
-  CHECK_HIP(hipMemcpy(d_steps, steps.data(), sizeof(wg_rel_step_t) * steps.size(), hipMemcpyHostToDevice));
-  CHECK_HIP(hipMemcpy(d_ns, n_steps.data(), sizeof(int) * B, hipMemcpyHostToDevice));
-  CHECK_HIP(hipMemcpy(d_feet, feet.data(), sizeof(double) * feet.size(), hipMemcpyHostToDevice));
-  // --online: the walk's state blobs, and the steps after the first two regrouped call by call, [call][B][K]
-  const int n_calls = K ? (S - 2 + K - 1) / K : 0;
+  CHECK_HIP(dev_upload(&d_steps, steps));
+  CHECK_HIP(dev_upload(&d_ns, n_steps));
+  CHECK_HIP(dev_upload(&d_feet, feet));
+  CHECK_HIP(dev_alloc(&d_len, B));
+  CHECK_HIP(dev_alloc(&d_zx, (size_t)L * B));
+  CHECK_HIP(dev_alloc(&d_zy, (size_t)L * B));
+  CHECK_HIP(dev_alloc(&d_state, (size_t)8 * B));
+  CHECK_HIP(dev_alloc(&d_com, (size_t)Lrun * 6 * B));
+  // --online: the walk's state blobs and the feeding plan.  Every gait has the same n_steps: nothing ends early
+  wg_fleet::OnlinePlan plan;
   wg_zmpdisc_state_t *d_walk = nullptr; wg_rel_step_t *d_chunks = nullptr; int *d_cns = nullptr;
   if (K) {
-    std::vector<wg_rel_step_t> chunks((size_t)n_calls * B * K);
-    std::vector<int> cns((size_t)n_calls * B);
-    memset(chunks.data(), 0, sizeof(wg_rel_step_t) * chunks.size());
-    for (int c = 0; c < n_calls; ++c)
-      for (int g = 0; g < B; ++g) {
-        const int first = 2 + c * K, n = S - first < K ? S - first : K;
-        cns[(size_t)c * B + g] = n;
-        for (int i = 0; i < n; ++i) chunks[((size_t)c * B + g) * K + i] = steps[(size_t)g * S + first + i];
-      }
-    CHECK_HIP(hipMalloc((void **)&d_walk, sizeof(wg_zmpdisc_state_t) * B));
-    CHECK_HIP(hipMalloc((void **)&d_chunks, sizeof(wg_rel_step_t) * (chunks.size() ? chunks.size() : 1)));
-    CHECK_HIP(hipMalloc((void **)&d_cns, sizeof(int) * (cns.size() ? cns.size() : 1)));
-    CHECK_HIP(hipMemcpy(d_chunks, chunks.data(), sizeof(wg_rel_step_t) * chunks.size(), hipMemcpyHostToDevice));
-    CHECK_HIP(hipMemcpy(d_cns, cns.data(), sizeof(int) * cns.size(), hipMemcpyHostToDevice));
-    std::vector<int> two(B, 2);
+    if (wg_fleet::online_plan(zm, steps, n_steps, B, S, K, &plan) >= 0) return 1;    // S >= 2: cannot be
+    CHECK_HIP(dev_alloc(&d_walk, B));
+    CHECK_HIP(dev_upload(&d_chunks, plan.chunks));
+    CHECK_HIP(dev_upload(&d_cns, plan.cns));
+    const std::vector<int> two(B, 2);                         // the begin call takes two steps of every gait
     CHECK_HIP(hipMemcpy(d_ns, two.data(), sizeof(int) * B, hipMemcpyHostToDevice));
   }
+  const int n_calls = plan.n_calls;
   hipStream_t st;
   CHECK_HIP(hipStreamCreate(&st));
   double sec = 0.0;
@@ -123,12 +106,11 @@ int main(int argc, char **argv) {
       };
       CHECK_WG(wg_zmpdisc_begin_dev(&zm, B, S, d_steps, d_ns, d_feet, L, d_zx, d_zy, nullptr, nullptr, nullptr, nullptr, nullptr,
                                     nullptr, d_walk, d_len, st));
-      CHECK_WG(preview_upto(wg_zmpdisc_length_after(&zm, steps.data(), 2, 0)));
+      CHECK_WG(preview_upto(plan.len_after[0]));
       for (int c = 0; c < n_calls; ++c) {
         CHECK_WG(wg_zmpdisc_append_dev(&zm, B, K, d_chunks + (size_t)c * B * K, d_cns + (size_t)c * B, L, d_zx, d_zy, nullptr,
                                        nullptr, nullptr, nullptr, nullptr, nullptr, d_walk, d_len, st));
-        const int upto = 2 + (c + 1) * K < S ? 2 + (c + 1) * K : S;
-        CHECK_WG(preview_upto(wg_zmpdisc_length_after(&zm, steps.data(), upto, 0)));
+        CHECK_WG(preview_upto(plan.len_after[(size_t)(c + 1) * B]));
       }
       CHECK_WG(wg_zmpdisc_end_dev(&zm, B, nullptr, L, d_zx, d_zy, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, d_walk,
                                   d_len, st));
@@ -159,9 +141,7 @@ int main(int argc, char **argv) {
       if (com_d[((size_t)l * 6 + c) * B] != com_h[(size_t)l * 6 + c]) { fprintf(stderr, "FAILED: device chain differs from the host entry points at step %d\n", l); return 1; }
   double far = 0.0;
   for (int g = 0; g < B; ++g) { const double x = com_d[((size_t)(Lrun - 1) * 6) * B + g]; far = x > far ? x : far; }
-  unsigned long long sum = 1469598103934665603ull;
-  const unsigned char *bytes = reinterpret_cast<const unsigned char *>(com_d.data());
-  for (size_t i = 0; i < com_d.size() * sizeof(double); ++i) sum = (sum ^ bytes[i]) * 1099511628211ull;
+  const unsigned long long sum = wg_fleet::fnv1a64(com_d.data(), com_d.size() * sizeof(double));
   printf("kajita_fleet: %d walks of %d steps (%d samples each) in %.2f ms = %.0f walks/s; gait 0 ends at x = %.4f m (%d samples), "
          "farthest %.2f m; device chain == host entry points; checksum %016llx\n", B, S, L, sec * 1e3, B / sec,
          com_h[(size_t)(Lrun - 1) * 6], len0, far, sum);

@@ -175,11 +175,8 @@ def test_every_cut_equals_the_oracle_and_the_batch_call(fleet1, B, first):
 
 
 # ---- 3. hand-made support codes --------------------------------------------------------------------------------------------
-@gpu
-def test_hand_made_support_codes():
-    import torch
-    wg.init(0)
-    assert wg.foot_constraints_chunk() == CH
+def hand_made_gaits():
+    """(B, lcap, calls, lf [lcap][6][B], rf, lty [lcap][B]): four gaits given by their support codes, and three calls' lengths"""
     B, lcap = 4, 3 * CH
     DS, LA, RA, INH = 0, 1, 2, 3                       # double support, left / right foot in the air, "none of the three tests"
     st = [[DS] * lcap for _ in range(B)]
@@ -204,6 +201,15 @@ def test_hand_made_support_codes():
             lf[i, 3, b] = rf[i, 3, b] = 3.0 * (b == 2)
             lf[i, 2, b] = {DS: 0.0, LA: 0.03, RA: 0.0, INH: 0.00001}[st[b][i]]
             rf[i, 2, b] = {DS: 0.0, LA: 0.0, RA: 0.02, INH: 0.0}[st[b][i]]
+    return B, lcap, calls, lf, rf, lty
+
+
+@gpu
+def test_hand_made_support_codes():
+    import torch
+    wg.init(0)
+    assert wg.foot_constraints_chunk() == CH
+    B, lcap, calls, lf, rf, lty = hand_made_gaits()
     T = 0.005
     F = dict(B=B, lcap=lcap, lf=torch.from_numpy(lf).cuda(), rf=torch.from_numpy(rf).cuda(), lty=torch.from_numpy(lty).cuda(),
              time=torch.from_numpy(times(lcap, T)).cuda())
