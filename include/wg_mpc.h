@@ -677,6 +677,40 @@ int wg_zmpdisc_end_dev(const wg_zmpdisc_model_t *model, int B, const int *select
                        double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm,
                        double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream);
 
+/* The preview that follows such a walk: every gait advances over exactly the rows its own queue has made safe -------------
+ *
+ * wg_preview_follow_dev is wg_preview_run_batch_dev with a range per gait, driven by the `length` array the wg_zmpdisc
+ * on-line calls leave on the device: the host does no arithmetic on lengths and reads nothing back, whatever the gaits'
+ * step counts and support times are, and whenever each of them begins, is fed or ends.  All pointers are DEVICE pointers,
+ * the layouts are those of wg_preview_run_batch_dev with ABSOLUTE rows:
+ *   zmp_*_tm [lcap][B]                 the gait's queue from sample 0 (the convention of the wg_zmpdisc on-line calls)
+ *   com_tm   [lcap - nl + 1][6][B],  zmp2_tm [lcap - nl + 1][2][B]    may be NULL each; step l of gait b goes to row l
+ *   state    [B][8]
+ *   length   B         samples gait b holds
+ *   done     B, in/out steps gait b has behind it; done[b] == 0 starts a walk from whatever state[b] holds
+ * With nl the configured window, safe[b] = max(0, length[b] - nl + 1) are the steps whose window [l, l + nl) lies inside the
+ * samples the gait holds -- a sample once written is final, so these steps are final whether or not the gait has ended, and
+ * this is where the reference stops as well (PreviewControl.cpp:341-344).  The call runs steps [done[b], safe[b]) from state[b],
+ * writes state[b] back and sets done[b] = safe[b]; a resumed gait refills its window from rows [done[b], done[b] + nl) of its
+ * own queue.
+ *   done[b] == safe[b]                  the gait sits the call out: none of its bytes is touched.
+ *   length[b] < 0 (a gait wg_zmpdisc_* refused) or done[b] < 0    the gait sits out as well: errors are sticky through done[b] < 0.
+ *   length[b] > lcap or done[b] > safe[b]    refused: done[b] = WG_ERR_BAD_ARG and nothing else of the gait is written.
+ * A neighbour never notices a refused or sitting-out gait.  Nothing at or past row length[b] of a gait is read: those rows are
+ * unwritten memory while the gait walks.
+ * CONTRACT: after any sequence of follow calls interleaved with calls that grow `length`, state[b] and rows [0, done[b]) of
+ * com_tm and zmp2_tm are byte for byte what ONE wg_preview_run_batch_dev with L = done[b] over the gait's final queue leaves,
+ * however the growth was cut; rows >= done[b] are untouched.  (Running an ended gait past length - nl + 1 -- the at-rest rows
+ * of the batch pipeline -- stays with the batch call.)
+ * Host-side errors (WG_ERR_BAD_ARG, nothing launched): no wg_preview_configure, B < 0, lcap < nl, a NULL length, done, queue or
+ * state.  B == 0 is WG_OK.  Asynchronous on hip_stream; keeps nothing in the context.
+ * Cost: both axes of a gait run in one wave, which reads done[b] before its step loop and stores it behind it, four gaits (windows
+ * of 64 .. 384 samples) or 32 gaits (other windows) to the wave; a wave takes as long as its longest gait, so an evenly fed
+ * fleet loses nothing against the batch call and a lone long gait costs its wave.
+ * Added without a change of wg_abi_version(): detect by symbol. */
+int wg_preview_follow_dev(int B, int lcap, const int *length, int *done, const double *zmp_x_tm, const double *zmp_y_tm,
+                          double *state, double *com_tm, double *zmp2_tm, int simulation, void *hip_stream);
+
 /* ZMP polytopes of a feet trajectory ----------------------------------------------------------------------------------
  *
  * wg_foot_constraints replaces FootConstraintsAsLinearSystem::BuildLinearConstraintInequalities
@@ -864,6 +898,9 @@ int wg_preview_configure_ctx(wg_ctx_t *ctx, const wg_preview_gains_t *gains, con
 int wg_preview_window_ctx(wg_ctx_t *ctx);
 int wg_preview_run_batch_dev_ctx(wg_ctx_t *ctx, int B, int L, const double *zmp_x_tm, const double *zmp_y_tm,
                                  double *state, double *com_tm, double *zmp2_tm, int simulation, void *hip_stream);
+int wg_preview_follow_dev_ctx(wg_ctx_t *ctx, int B, int lcap, const int *length, int *done, const double *zmp_x_tm,
+                              const double *zmp_y_tm, double *state, double *com_tm, double *zmp2_tm, int simulation,
+                              void *hip_stream);
 int wg_preview_run_batch_ctx(wg_ctx_t *ctx, int B, int L, const double *zmp_x, const double *zmp_y, double *state,
                              double *com, double *zmp2, int simulation);
 int wg_gramian_batch_dev_ctx(wg_ctx_t *ctx, int B, int N, const double *T, const double *h, double alpha,

@@ -1416,6 +1416,11 @@ typedef void (*SplitKernel)(int, int, wg::PreviewConst, const double *, const do
 #define WG_SPLIT(T) {T, wg::wg_preview_split_kernel<T, kSplitK, true>, wg::wg_preview_split_kernel<T, kSplitK, false>}
 const struct { int T; SplitKernel full, part; } kSplitKernels[] = {WG_SPLIT(16), WG_SPLIT(24), WG_SPLIT(32), WG_SPLIT(40), WG_SPLIT(48)};
 #undef WG_SPLIT
+// ... and their follow forms (wg_preview_follow_dev): four gaits x two axes per wave
+typedef void (*FollowSplitKernel)(int, int, const int *, int *, wg::PreviewConst, const double *, const double *, const double *, double *, double *, double *, int);
+#define WG_SPLIT(T) {T, wg::wg_preview_follow_split_kernel<T, kSplitK, true>, wg::wg_preview_follow_split_kernel<T, kSplitK, false>}
+const struct { int T; FollowSplitKernel full, part; } kFollowSplitKernels[] = {WG_SPLIT(16), WG_SPLIT(24), WG_SPLIT(32), WG_SPLIT(40), WG_SPLIT(48)};
+#undef WG_SPLIT
 }  // namespace
 
 extern "C" {
@@ -1477,6 +1482,31 @@ int wg_preview_run_batch_dev_ctx(wg_ctx_t *ctx, int B, int L, const double *zmp_
     const int threads = B >= 4096 ? 256 : 64;                  // small batches: more blocks, one wave each
     hipLaunchKernelGGL(wg::wg_preview_kernel, dim3((B + threads - 1) / threads, 2), dim3(threads), 0, st, B, L, ctx->prev,
                        ctx->prev_F, zmp_x_tm, zmp_y_tm, state, com_tm, zmp2_tm, simulation);
+  }
+  HIP_TRY(hipGetLastError());
+  std::lock_guard<std::mutex> launch_lk(ctx->launch_mu);
+  return slot_mark(ctx->aux_order, st);
+}
+
+int wg_preview_follow_dev_ctx(wg_ctx_t *ctx, int B, int lcap, const int *length, int *done, const double *zmp_x_tm, const double *zmp_y_tm, double *state, double *com_tm, double *zmp2_tm, int simulation, void *hip_stream) {
+  if (int rc = preview_check(ctx, B, lcap, zmp_x_tm, zmp_y_tm, state)) return rc;
+  if (!length || !done) return fail(WG_ERR_BAD_ARG, "null length or done");
+  if (lcap < ctx->prev.nl) return fail(WG_ERR_BAD_ARG, "lcap=%d holds no window of nl=%d samples", lcap, ctx->prev.nl);
+  if (B == 0) return WG_OK;
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  const char *force = getenv("WG_PREVIEW_KERNEL");            // "l2" / "split" as in the batch call; "ring" has no follow form: l2
+  FollowSplitKernel split_kern = nullptr;                      // the batch call's T / FULL selection
+  int splitT = 0;
+  for (const auto &s : kFollowSplitKernels)
+    if (!splitT && kSplitK * s.T >= ctx->prev.nl) { splitT = s.T; split_kern = ctx->prev.nl % s.T == 0 ? s.full : s.part; }
+  const bool can_split = splitT != 0 && ctx->prev.nl >= 64;
+  if (force ? (force[0] == 's' && can_split) : can_split) {
+    const int per_wave = 64 / kSplitK / 2;                     // both axes of a gait in one wave
+    hipLaunchKernelGGL(split_kern, dim3((B + per_wave - 1) / per_wave), dim3(64), (size_t)splitT * 64 * 8, st, B, lcap, length, done, ctx->prev,
+                       ctx->prev_F, zmp_x_tm, zmp_y_tm, state, com_tm, zmp2_tm, simulation);
+  } else {
+    hipLaunchKernelGGL(wg::wg_preview_follow_kernel, dim3((B + 31) / 32), dim3(64), 0, st, B, lcap, length, done, ctx->prev, ctx->prev_F,
+                       zmp_x_tm, zmp_y_tm, state, com_tm, zmp2_tm, simulation);
   }
   HIP_TRY(hipGetLastError());
   std::lock_guard<std::mutex> launch_lk(ctx->launch_mu);
@@ -1801,6 +1831,7 @@ int wg_preview_window(void) {                        // a query: does not create
 }
 
 int wg_preview_run_batch_dev(int B, int L, const double *zmp_x_tm, const double *zmp_y_tm, double *state, double *com_tm, double *zmp2_tm, int simulation, void *hip_stream) { return on_default(&wg_preview_run_batch_dev_ctx, B, L, zmp_x_tm, zmp_y_tm, state, com_tm, zmp2_tm, simulation, hip_stream); }
+int wg_preview_follow_dev(int B, int lcap, const int *length, int *done, const double *zmp_x_tm, const double *zmp_y_tm, double *state, double *com_tm, double *zmp2_tm, int simulation, void *hip_stream) { return on_default(&wg_preview_follow_dev_ctx, B, lcap, length, done, zmp_x_tm, zmp_y_tm, state, com_tm, zmp2_tm, simulation, hip_stream); }
 int wg_preview_run_batch(int B, int L, const double *zmp_x, const double *zmp_y, double *state, double *com, double *zmp2, int simulation) { return on_default(&wg_preview_run_batch_ctx, B, L, zmp_x, zmp_y, state, com, zmp2, simulation); }
 int wg_gramian_batch_dev(int B, int N, const double *T, const double *h, double alpha, double beta, double gamma, int precision, double *Qb, void *hip_stream) { return on_default(&wg_gramian_batch_dev_ctx, B, N, T, h, alpha, beta, gamma, precision, Qb, hip_stream); }
 int wg_gramian_batch(int B, int N, const double *T, const double *h, double alpha, double beta, double gamma, int precision, double *Qb) { return on_default(&wg_gramian_batch_ctx, B, N, T, h, alpha, beta, gamma, precision, Qb); }

@@ -16,6 +16,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "wg_wave.hpp"
+
 namespace wg {
 
 struct PreviewConst {
@@ -26,22 +28,67 @@ struct PreviewConst {
   int nl;
 };
 
+// The follow forms (RAGGED, wg_preview_follow_dev): every gait advances over the rows its own queue has made safe.
+//   length [B]   samples gait b holds (what the wg_zmpdisc on-line calls leave); safe = max(0, length - nl + 1)
+//   done   [B]   steps gait b has behind it; the launch runs steps [done, safe) and stores done = safe
+// with ABSOLUTE rows: zx, zy [lcap][B] from the gait's sample 0, com [lcap - nl + 1][6][B], zmp2 [lcap - nl + 1][2][B].
+// length < 0 or done < 0: the gait sits out; length > lcap or done > safe: done = WG_ERR_BAD_ARG (-2) and nothing else.  A gait
+// without a step to run reads nothing of its queue and stores nothing, and no lane reads a row >= length[b] of its gait: those
+// rows are unwritten memory while the gait walks.
+// Both axes of a gait sit in ONE wave, which reads done[b] before its step loop and stores it behind it: were the axes
+// two blocks, as in the batch forms, one could store done[b] before the other has read it.
+struct PreviewRange {
+  const double *z;          // row done[b] of the gait's queue: the row of the call's first step
+  size_t row0;              // done[b]
+  int n;                    // steps to run, 0: the gait sits out or is refused
+  int Lz;                   // rows from z on that the gait holds: n + nl - 1, or 0
+  bool refused;
+};
+__device__ __forceinline__ PreviewRange pv_range(bool valid, int g, int B, int nl, int lcap, const double *z, const int *length,
+                                                 const int *done) {
+  const int len = valid ? length[g] : -1, dn = valid ? done[g] : -1;
+  const int safe = len >= nl ? len - nl + 1 : 0;
+  const bool sits = len < 0 || dn < 0;
+  PreviewRange r;
+  r.refused = !sits && (len > lcap || dn > safe);
+  r.n = (sits || r.refused) ? 0 : safe - dn;
+  r.row0 = r.n > 0 ? (size_t)dn : 0;
+  r.z = z + r.row0 * (size_t)B;
+  r.Lz = r.n > 0 ? len - dn : 0;
+  return r;
+}
+// the one lane of a gait that answers for done[b]
+__device__ __forceinline__ void pv_range_store(const PreviewRange &r, int g, int *done) {
+  if (r.refused) done[g] = -2;                                       // WG_ERR_BAD_ARG
+  else if (r.n > 0) done[g] = (int)r.row0 + r.n;
+}
+
 // zx, zy:  [(L + nl - 1)][B]   time-major ZMP references (entry t of gait g at t*B + g)
 // state:   [B][8]              x[3], y[3], sxzmp, syzmp  (read, advanced L steps, written back)
 // com:     [L][6][B] or NULL   x[0..2], y[0..2] after each step
 // zmp2:    [L][2][B] or NULL   zmpx2, zmpy2 of each step
-__global__ void __launch_bounds__(256)
-wg_preview_kernel(int B, int L, PreviewConst K, const double *__restrict__ F, const double *__restrict__ zx,
-                  const double *__restrict__ zy, double *__restrict__ state, double *__restrict__ com,
-                  double *__restrict__ zmp2, int simulation) {
-  const int g = blockIdx.x * blockDim.x + threadIdx.x;
-  const int axis = blockIdx.y;
+// RAGGED: one wave per block, lanes 0..31 the x axes of 32 gaits, lanes 32..63 their y axes; L is not used.  The step loop has
+// a bound per lane here (no lane talks to another), so a lane's loads are those of its own steps and nothing else.
+template <bool RAGGED>
+__device__ __forceinline__ void pv_l2_body(int B, int L, const PreviewConst &K, const double *__restrict__ F,
+                                           const double *__restrict__ zx, const double *__restrict__ zy, double *__restrict__ state,
+                                           double *__restrict__ com, double *__restrict__ zmp2, int simulation, int lcap,
+                                           const int *length, int *done) {
+  const int g = RAGGED ? blockIdx.x * 32 + (threadIdx.x & 31) : blockIdx.x * blockDim.x + threadIdx.x;
+  const int axis = RAGGED ? threadIdx.x >> 5 : blockIdx.y;
   if (g >= B) return;
   const double *__restrict__ z = axis ? zy : zx;
-  double *st = state + (size_t)g * 8;
-  double x0 = st[3 * axis], x1 = st[3 * axis + 1], x2 = st[3 * axis + 2], s = st[6 + axis];
   const size_t sB = (size_t)B;
   const int nl = K.nl;
+  PreviewRange rg;
+  if constexpr (RAGGED) {
+    rg = pv_range(true, g, B, nl, lcap, z, length, done);
+    z = rg.z; L = rg.n;
+    if (com) com += rg.row0 * 6 * sB;
+    if (zmp2) zmp2 += rg.row0 * 2 * sB;
+  }
+  double *st = state + (size_t)g * 8;
+  double x0 = st[3 * axis], x1 = st[3 * axis + 1], x2 = st[3 * axis + 2], s = st[6 + axis];
   for (int l = 0; l < L; ++l) {
     // r = MAL_RET_A_by_B(m_Kx, x): 1x3 by 3x1, products summed k ascending from 0.0 (:338)
     double r = 0.0;
@@ -72,7 +119,26 @@ wg_preview_kernel(int B, int L, PreviewConst K, const double *__restrict__ F, co
     }
     if (zmp2) zmp2[((size_t)l * 2 + axis) * sB + g] = p;
   }
-  st[3 * axis] = x0; st[3 * axis + 1] = x1; st[3 * axis + 2] = x2; st[6 + axis] = s;
+  if constexpr (RAGGED) {
+    if (L > 0) { st[3 * axis] = x0; st[3 * axis + 1] = x1; st[3 * axis + 2] = x2; st[6 + axis] = s; }
+    if (axis == 0) pv_range_store(rg, g, done);
+  } else {
+    st[3 * axis] = x0; st[3 * axis + 1] = x1; st[3 * axis + 2] = x2; st[6 + axis] = s;
+  }
+}
+
+__global__ void __launch_bounds__(256)
+wg_preview_kernel(int B, int L, PreviewConst K, const double *__restrict__ F, const double *__restrict__ zx,
+                  const double *__restrict__ zy, double *__restrict__ state, double *__restrict__ com,
+                  double *__restrict__ zmp2, int simulation) {
+  pv_l2_body<false>(B, L, K, F, zx, zy, state, com, zmp2, simulation, 0, nullptr, nullptr);
+}
+
+__global__ void __launch_bounds__(64)
+wg_preview_follow_kernel(int B, int lcap, const int *__restrict__ length, int *__restrict__ done, PreviewConst K,
+                         const double *__restrict__ F, const double *__restrict__ zx, const double *__restrict__ zy,
+                         double *__restrict__ state, double *__restrict__ com, double *__restrict__ zmp2, int simulation) {
+  pv_l2_body<true>(B, 0, K, F, zx, zy, state, com, zmp2, simulation, lcap, length, done);
 }
 
 // The same iteration with the preview window staged in LDS.  wg_preview_kernel re-reads the whole window from L2 at every
@@ -172,26 +238,40 @@ __device__ __forceinline__ double pv_dpp(double v) {
   return __hiloint2double(hi, lo);
 }
 
-template <int T, int K, bool FULL>     // FULL: nl is a multiple of T, the last used lane has T taps like the others
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
-wg_preview_split_kernel(int B, int L, PreviewConst Kc, const double *__restrict__ F, const double *__restrict__ zx,
-                        const double *__restrict__ zy, double *__restrict__ state, double *__restrict__ com,
-                        double *__restrict__ zmp2, int simulation) {
+// RAGGED (the follow form): the eight groups of a wave are four gaits x two axes, each with its own number of steps n.  The
+// step loop stays wave-uniform -- it runs the largest n of the wave, a wave reduction -- and a group that has finished keeps
+// its lanes in it, so that the row shifts keep their meaning: only its state update and its stores are predicated, and its
+// loads are off (every load is guarded by the gait's own row count Lz, which is 0 for a group without a step).  A wave takes
+// as long as its longest gait: an evenly fed fleet loses nothing, a lone long gait costs its wave.
+template <int T, int K, bool FULL, bool RAGGED>     // FULL: nl is a multiple of T, the last used lane has T taps like the others
+__device__ __forceinline__ void pv_split_body(int B, int L, const PreviewConst &Kc, const double *__restrict__ F,
+                                              const double *__restrict__ zx, const double *__restrict__ zy,
+                                              double *__restrict__ state, double *__restrict__ com, double *__restrict__ zmp2,
+                                              int simulation, int lcap, const int *length, int *done) {
   static_assert(K == 8, "the DPP controls below are written for groups of eight lanes");
   extern __shared__ __attribute__((aligned(16))) double pv_ring[];      // [T][64]
   constexpr int G = 64 / K;
   const int lane = threadIdx.x;
   const int k = lane & (K - 1);
-  const int g0 = blockIdx.x * G + lane / K;
+  const int g0 = RAGGED ? blockIdx.x * (G / 2) + lane / (2 * K) : blockIdx.x * G + lane / K;
   const bool valid = g0 < B;
   const int g = valid ? g0 : B - 1;                                     // surplus groups shadow the last gait (no stores)
-  const int axis = blockIdx.y;
+  const int axis = RAGGED ? (lane / K) & 1 : blockIdx.y;
   const double *__restrict__ z = axis ? zy : zx;
   const size_t sB = (size_t)B;
   const int nl = Kc.nl;
   const int Ku = (nl + T - 1) / T;                                      // lanes of the group that hold taps, 1..K
   const int Tl = nl - (Ku - 1) * T;                                     // taps of the last of them, 1..T
-  const int Lz = L + nl - 1;
+  int Lz = L + nl - 1;
+  int n = L;                                                            // steps of this lane's gait
+  PreviewRange rg;
+  if constexpr (RAGGED) {
+    rg = pv_range(valid, g, B, nl, lcap, z, length, done);
+    z = rg.z; Lz = rg.Lz; n = rg.n;
+    L = wave_max_int(n);
+    if (com) com += rg.row0 * 6 * sB;
+    if (zmp2) zmp2 += rg.row0 * 2 * sB;
+  }
   const bool last = k == Ku - 1, first = k == 0;
   double Fk[T];
 #pragma unroll
@@ -258,7 +338,7 @@ wg_preview_split_kernel(int B, int L, PreviewConst Kc, const double *__restrict_
     const double n0 = a0 + u * Kc.B0, n1 = a1 + u * Kc.B1, n2 = a2 + u * Kc.B2;
     double pz = 0.0;
     pz += 1.0 * n0; pz += 0.0 * n1; pz += Kc.C2 * n2;
-    if (first) {                                                        // only lane 0 carries the gait's state
+    if (first && (!RAGGED || l < n)) {                                  // only lane 0 carries the gait's state
       x0 = n0; x1 = n1; x2 = n2;
       if (simulation) s += (zold - pz);
       if (valid) {
@@ -280,10 +360,28 @@ wg_preview_split_kernel(int B, int L, PreviewConst Kc, const double *__restrict_
     pv_ring[wslot * 64 + lane] = incoming;
     head = head + 1 == T ? 0 : head + 1;
   }
-  if (valid && first) {
+  if (valid && first && (!RAGGED || n > 0)) {
     double *so = state + (size_t)g * 8;
     so[3 * axis] = x0; so[3 * axis + 1] = x1; so[3 * axis + 2] = x2; so[6 + axis] = s;
   }
+  if constexpr (RAGGED)
+    if (valid && first && axis == 0) pv_range_store(rg, g, done);
+}
+
+template <int T, int K, bool FULL>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
+wg_preview_split_kernel(int B, int L, PreviewConst Kc, const double *__restrict__ F, const double *__restrict__ zx,
+                        const double *__restrict__ zy, double *__restrict__ state, double *__restrict__ com,
+                        double *__restrict__ zmp2, int simulation) {
+  pv_split_body<T, K, FULL, false>(B, L, Kc, F, zx, zy, state, com, zmp2, simulation, 0, nullptr, nullptr);
+}
+
+template <int T, int K, bool FULL>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
+wg_preview_follow_split_kernel(int B, int lcap, const int *__restrict__ length, int *__restrict__ done, PreviewConst Kc,
+                               const double *__restrict__ F, const double *__restrict__ zx, const double *__restrict__ zy,
+                               double *__restrict__ state, double *__restrict__ com, double *__restrict__ zmp2, int simulation) {
+  pv_split_body<T, K, FULL, true>(B, 0, Kc, F, zx, zy, state, com, zmp2, simulation, lcap, length, done);
 }
 
 // [B][cols] (gait-major) <-> [cols][B] (time-major) on the device, for the host-pointer entry point

@@ -8,7 +8,14 @@
 // wg_zmpdisc_end_dev and the remaining rows.  Every step is walked once, and the CoM trajectories -- hence the checksum
 // (FNV-1a, 64 bit, over all of them) that both modes print -- are those of the whole-sequence mode.
 //
-//   kajita_fleet [--batch B] [--steps S] [--online K]
+// With --ragged gait g walks its own number of steps, between S/2 and S.  Whole-sequence mode: wg_zmpdisc_batch_dev, then ONE
+// wg_preview_run_batch_dev over the longest gait.  With --online K the feeding plan runs out early for some gaits: they are
+// ended (wg_zmpdisc_end_dev with `select`) behind the call that gave them their last step while the others walk on, and the
+// preview is wg_preview_follow_dev behind every zmpdisc call, fed by the `length` array those calls leave on the device -- the
+// host does no arithmetic on sample counts and reads nothing back.  Both modes print one checksum over each gait's OWN rows
+// [0, len_g - nl + 1) of the CoM trajectories (the rows past them exist only in the whole-sequence mode): the same one.
+//
+//   kajita_fleet [--batch B] [--steps S] [--online K] [--ragged]
 #include <chrono>
 #include <cstdlib>
 #include <random>
@@ -20,9 +27,11 @@ using wg_fleet::dev_upload;
 
 int main(int argc, char **argv) {
   int B = 4096, S = 16, K = 0;
+  bool ragged = false;
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--batch") && i + 1 < argc) B = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--steps") && i + 1 < argc) S = atoi(argv[++i]);
+    else if (!strcmp(argv[i], "--ragged")) ragged = true;
     else if (!strcmp(argv[i], "--online") && i + 1 < argc) { K = atoi(argv[++i]); if (K < 1 || K > WG_ZMPDISC_MAX_STEPS) { fprintf(stderr, "FAILED: need 1 <= --online K <= %d\n", WG_ZMPDISC_MAX_STEPS); return 1; } }
   }
   if (B < 1 || S < 2 || S > WG_ZMPDISC_MAX_STEPS) { fprintf(stderr, "FAILED: need B >= 1, 2 <= steps <= %d\n", WG_ZMPDISC_MAX_STEPS); return 1; }
@@ -41,13 +50,17 @@ int main(int argc, char **argv) {
   std::vector<int> n_steps(B, S);
   std::vector<double> feet((size_t)B * 6);
   for (int g = 0; g < B; ++g) {
+    if (ragged) {                                              // S/2 .. S steps, at least the two the begin call takes
+      const int lo = S / 2 > 2 ? S / 2 : 2;
+      n_steps[g] = lo + (int)(std::mt19937_64(7700 + g)() % (unsigned)(S - lo + 1));
+    }
     std::mt19937_64 rng(20100 + g);
     std::uniform_real_distribution<double> len(0.1, 0.25), turn(-5.0, 5.0);
     double side = (g & 1) ? 1.0 : -1.0;
     for (int i = 0; i < S; ++i) {
       wg_rel_step_t &s = steps[(size_t)g * S + i];
       memset(&s, 0, sizeof s);
-      const bool ends = i == 0 || i == S - 1;
+      const bool ends = i == 0 || i == n_steps[g] - 1;
       s.sx = ends ? 0.0 : (g == 0 ? 0.2 : len(rng));
       s.sy = side * (i == 0 ? 0.105 : 0.21);
       s.theta = (ends || g == 0) ? 0.0 : turn(rng);
@@ -57,11 +70,18 @@ int main(int argc, char **argv) {
     const double f[6] = {0.0094903, 0.095, 0.0, 0.0094903, -0.095, 0.0};
     memcpy(&feet[(size_t)g * 6], f, sizeof f);
   }
-  const int L = wg_zmpdisc_length(&zm, steps.data(), S);
-  if (L < nl) { fprintf(stderr, "FAILED: sequence of %d samples\n", L); return 1; }
+  // samples of every gait, L those of the longest (without --ragged: of all)
+  std::vector<int> len_g(B);
+  int L = 0, Lmin = 1 << 30;
+  for (int g = 0; g < B; ++g) {
+    len_g[g] = wg_zmpdisc_length(&zm, &steps[(size_t)g * S], n_steps[g]);
+    if (len_g[g] < nl) { fprintf(stderr, "FAILED: sequence of %d samples\n", len_g[g]); return 1; }
+    L = len_g[g] > L ? len_g[g] : L;
+    Lmin = len_g[g] < Lmin ? len_g[g] : Lmin;
+  }
   const int Lrun = L - nl + 1;
 
-  wg_rel_step_t *d_steps; int *d_ns, *d_len; double *d_feet, *d_zx, *d_zy, *d_state, *d_com;
+  wg_rel_step_t *d_steps; int *d_ns, *d_len, *d_done = nullptr, *d_sel = nullptr; double *d_feet, *d_zx, *d_zy, *d_state, *d_com;
   CHECK_HIP(dev_upload(&d_steps, steps));
   CHECK_HIP(dev_upload(&d_ns, n_steps));
   CHECK_HIP(dev_upload(&d_feet, feet));
@@ -70,7 +90,7 @@ int main(int argc, char **argv) {
   CHECK_HIP(dev_alloc(&d_zy, (size_t)L * B));
   CHECK_HIP(dev_alloc(&d_state, (size_t)8 * B));
   CHECK_HIP(dev_alloc(&d_com, (size_t)Lrun * 6 * B));
-  // --online: the walk's state blobs and the feeding plan.  Every gait has the same n_steps: nothing ends early
+  // --online: the walk's state blobs and the feeding plan.  Without --ragged every gait has the same n_steps: nothing ends early
   wg_fleet::OnlinePlan plan;
   wg_zmpdisc_state_t *d_walk = nullptr; wg_rel_step_t *d_chunks = nullptr; int *d_cns = nullptr;
   if (K) {
@@ -78,6 +98,10 @@ int main(int argc, char **argv) {
     CHECK_HIP(dev_alloc(&d_walk, B));
     CHECK_HIP(dev_upload(&d_chunks, plan.chunks));
     CHECK_HIP(dev_upload(&d_cns, plan.cns));
+    if (ragged) {
+      CHECK_HIP(dev_upload(&d_sel, plan.sel));
+      CHECK_HIP(dev_alloc(&d_done, B));
+    }
     const std::vector<int> two(B, 2);                         // the begin call takes two steps of every gait
     CHECK_HIP(hipMemcpy(d_ns, two.data(), sizeof(int) * B, hipMemcpyHostToDevice));
   }
@@ -92,6 +116,29 @@ int main(int argc, char **argv) {
     if (!K) {
       CHECK_WG(wg_zmpdisc_batch_dev(&zm, B, S, d_steps, d_ns, d_feet, L, d_zx, d_zy, d_len, st));
       CHECK_WG(wg_preview_run_batch_dev(B, Lrun, d_zx, d_zy, d_state, d_com, nullptr, 1, st));
+    } else if (ragged) {
+      // the plan says which STEPS each call gives and which gaits it ends; how many samples that makes is the device's business
+      CHECK_HIP(hipMemsetAsync(d_done, 0, sizeof(int) * B, st));
+      auto follow = [&]() { return wg_preview_follow_dev(B, L, d_len, d_done, d_zx, d_zy, d_state, d_com, nullptr, 1, st); };
+      auto end_selected = [&](int c) -> int {                  // the gaits whose steps ran out with call c
+        const int *sel = &plan.sel[(size_t)c * B];
+        bool any = false;
+        for (int g = 0; g < B; ++g) any = any || sel[g];
+        if (!any) return WG_OK;
+        const int rc = wg_zmpdisc_end_dev(&zm, B, d_sel + (size_t)c * B, L, d_zx, d_zy, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                          nullptr, d_walk, d_len, st);
+        return rc != WG_OK ? rc : follow();
+      };
+      CHECK_WG(wg_zmpdisc_begin_dev(&zm, B, S, d_steps, d_ns, d_feet, L, d_zx, d_zy, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                    nullptr, d_walk, d_len, st));
+      CHECK_WG(follow());
+      CHECK_WG(end_selected(0));
+      for (int c = 0; c < n_calls; ++c) {
+        CHECK_WG(wg_zmpdisc_append_dev(&zm, B, K, d_chunks + (size_t)c * B * K, d_cns + (size_t)c * B, L, d_zx, d_zy, nullptr,
+                                       nullptr, nullptr, nullptr, nullptr, nullptr, d_walk, d_len, st));
+        CHECK_WG(follow());
+        CHECK_WG(end_selected(c + 1));
+      }
     } else {
       // every gait has the same support times, hence the same sample count after each call: the host knows it without
       // reading `length` back.  Rows [done, done + n) are safe once the queue holds done + n + nl - 1 samples.
@@ -124,27 +171,53 @@ int main(int argc, char **argv) {
     std::vector<int> len_h(B);
     CHECK_HIP(hipMemcpy(len_h.data(), d_len, sizeof(int) * B, hipMemcpyDeviceToHost));
     for (int g = 0; g < B; ++g)
-      if (len_h[g] != L) { fprintf(stderr, "FAILED: gait %d ended with length %d, not %d\n", g, len_h[g], L); return 1; }
+      if (len_h[g] != len_g[g]) { fprintf(stderr, "FAILED: gait %d ended with length %d, not %d\n", g, len_h[g], len_g[g]); return 1; }
     CHECK_HIP(hipMemcpy(d_ns, n_steps.data(), sizeof(int) * B, hipMemcpyHostToDevice));
+    if (ragged) {                                              // ... and the preview at its last safe row
+      CHECK_HIP(hipMemcpy(len_h.data(), d_done, sizeof(int) * B, hipMemcpyDeviceToHost));
+      for (int g = 0; g < B; ++g)
+        if (len_h[g] != len_g[g] - nl + 1) { fprintf(stderr, "FAILED: gait %d previewed %d rows of %d\n", g, len_h[g], len_g[g] - nl + 1); return 1; }
+    }
   }
   // gait 0 against the host-pointer entry points
-  std::vector<double> zmp((size_t)L * 2), com_h((size_t)Lrun * 6), state_h(8, 0.0), zx(L), zy(L);
+  const int L0 = len_g[0], Lrun0 = L0 - nl + 1;
+  std::vector<double> zmp((size_t)L0 * 2), com_h((size_t)Lrun0 * 6), state_h(8, 0.0), zx(L0), zy(L0);
   int len0 = 0;
-  CHECK_WG(wg_zmpdisc_batch(&zm, 1, S, steps.data(), n_steps.data(), feet.data(), L, zmp.data(), nullptr, nullptr, nullptr, nullptr,
+  CHECK_WG(wg_zmpdisc_batch(&zm, 1, S, steps.data(), n_steps.data(), feet.data(), L0, zmp.data(), nullptr, nullptr, nullptr, nullptr,
                             nullptr, nullptr, &len0));
-  for (int l = 0; l < L; ++l) { zx[l] = zmp[2 * l]; zy[l] = zmp[2 * l + 1]; }
-  CHECK_WG(wg_preview_run_batch(1, Lrun, zx.data(), zy.data(), state_h.data(), com_h.data(), nullptr, 1));
+  for (int l = 0; l < L0; ++l) { zx[l] = zmp[2 * l]; zy[l] = zmp[2 * l + 1]; }
+  CHECK_WG(wg_preview_run_batch(1, Lrun0, zx.data(), zy.data(), state_h.data(), com_h.data(), nullptr, 1));
   std::vector<double> com_d((size_t)Lrun * 6 * B);
   CHECK_HIP(hipMemcpy(com_d.data(), d_com, sizeof(double) * com_d.size(), hipMemcpyDeviceToHost));
-  for (int l = 0; l < Lrun; ++l)
+  for (int l = 0; l < Lrun0; ++l)
     for (int c = 0; c < 6; ++c)
       if (com_d[((size_t)l * 6 + c) * B] != com_h[(size_t)l * 6 + c]) { fprintf(stderr, "FAILED: device chain differs from the host entry points at step %d\n", l); return 1; }
+  if (ragged) {                                                // each gait's own rows, gait by gait
+    std::vector<double> own;
+    double far = 0.0;
+    int n_min = S, n_max = 0;
+    for (int g = 0; g < B; ++g) {
+      const int rows = len_g[g] - nl + 1;
+      for (int l = 0; l < rows; ++l)
+        for (int c = 0; c < 6; ++c) own.push_back(com_d[((size_t)l * 6 + c) * B + g]);
+      const double x = com_d[((size_t)(rows - 1) * 6) * B + g];
+      far = x > far ? x : far;
+      n_min = n_steps[g] < n_min ? n_steps[g] : n_min;
+      n_max = n_steps[g] > n_max ? n_steps[g] : n_max;
+    }
+    const unsigned long long sum = wg_fleet::fnv1a64(own.data(), own.size() * sizeof(double));
+    printf("kajita_fleet: %d ragged walks of %d..%d steps (%d..%d samples) in %.2f ms = %.0f walks/s; gait 0 ends at x = %.4f m (%d samples), "
+           "farthest %.2f m; device chain == host entry points; checksum %016llx\n", B, n_min, n_max, Lmin, L, sec * 1e3, B / sec,
+           com_h[(size_t)(Lrun0 - 1) * 6], len0, far, sum);
+    wg_shutdown();
+    return 0;
+  }
   double far = 0.0;
   for (int g = 0; g < B; ++g) { const double x = com_d[((size_t)(Lrun - 1) * 6) * B + g]; far = x > far ? x : far; }
   const unsigned long long sum = wg_fleet::fnv1a64(com_d.data(), com_d.size() * sizeof(double));
   printf("kajita_fleet: %d walks of %d steps (%d samples each) in %.2f ms = %.0f walks/s; gait 0 ends at x = %.4f m (%d samples), "
          "farthest %.2f m; device chain == host entry points; checksum %016llx\n", B, S, L, sec * 1e3, B / sec,
-         com_h[(size_t)(Lrun - 1) * 6], len0, far, sum);
+         com_h[(size_t)(Lrun0 - 1) * 6], len0, far, sum);
   wg_shutdown();
   return 0;
 }

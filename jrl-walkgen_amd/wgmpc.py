@@ -115,6 +115,8 @@ def lib():
         _lib.wg_gramian_batch_dev.argtypes = _lib.wg_gramian_batch.argtypes + [C.c_void_p]
         _lib.wg_preview_run_batch.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int]
         _lib.wg_preview_run_batch_dev.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]
+        if hasattr(_lib, "wg_preview_follow_dev"):          # absent from older experiment builds (WG_LIB_PATH, A/B runs)
+            _lib.wg_preview_follow_dev.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p]
         _lib.wg_zmpdisc_defaults.argtypes = [C.c_void_p]
         _lib.wg_zmpdisc_length.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         _lib.wg_zmpdisc_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + \
@@ -172,7 +174,7 @@ CTX_ENTRY_POINTS = ("wg_set_overlap_strict", "wg_overlap_serialised", "wg_qp_sol
                     "wg_zmpdisc_batch", "wg_zmpdisc_batch_dev", "wg_zmpdisc_full_batch_dev", "wg_foot_constraints_batch_dev",
                     "wg_zmpdisc_begin_dev", "wg_zmpdisc_append_dev", "wg_zmpdisc_end_dev",
                     "wg_dimitrov_select_polys_dev", "wg_dimitrov_walk_dev", "wg_foot_constraints_append_dev",
-                    "wg_dimitrov_walk_time", "wg_dimitrov_walk_safe_ticks")
+                    "wg_dimitrov_walk_time", "wg_dimitrov_walk_safe_ticks", "wg_preview_follow_dev")
 
 
 class Context:
@@ -581,6 +583,13 @@ def preview_run_batch_dev(B, L, zx_tm_ptr, zy_tm_ptr, state_ptr, com_tm_ptr=None
                           stream=None):
     _check(lib().wg_preview_run_batch_dev(B, L, zx_tm_ptr, zy_tm_ptr, state_ptr, com_tm_ptr, zmp2_tm_ptr,
                                           int(bool(simulation)), stream))
+
+
+def preview_follow_dev(B, lcap, length_ptr, done_ptr, zx_tm_ptr, zy_tm_ptr, state_ptr, com_tm_ptr=None, zmp2_tm_ptr=None,
+                       simulation=True, stream=None):
+    """every gait over the rows its own queue has made safe: steps [done[b], length[b] - nl + 1), absolute rows (wg_mpc.h)"""
+    _check(lib().wg_preview_follow_dev(B, lcap, length_ptr, done_ptr, zx_tm_ptr, zy_tm_ptr, state_ptr, com_tm_ptr, zmp2_tm_ptr,
+                                       int(bool(simulation)), stream))
 
 
 # ---- Kajita stage-1 inputs: ZMPDiscretization, batched; FootConstraintsAsLinearSystem (host) ----
