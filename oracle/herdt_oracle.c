@@ -432,6 +432,28 @@ static void poly3_set(double *c, double FT, double FP, double p0, double v0) {
   }
 }
 
+/* probe: the statics above, callable (tests/test_ref_parts_oracle.py holds them to the compiled reference).  Case i sets the
+ * polynomial of `degree` as the tick does -- 3: poly3_set(FT, FP, p0, v0); 4: poly4_set(FT, FP) with FP the middle position;
+ * 5: poly5_set(FT, FP, p0, v0, a0) -- and evaluates it at t[i][0 .. nt): value, first and second derivative [n][nt] each.
+ * Returns 0, or -2 on an unknown degree. */
+int wgo_probe_tick_poly(int degree, int n, const double *FT, const double *FP, const double *p0, const double *v0,
+                        const double *a0, int nt, const double *t, double *val, double *d1, double *d2) {
+  if (degree < 3 || degree > 5) return -2;
+  for (int i = 0; i < n; i++) {
+    double c[6];
+    if (degree == 3) poly3_set(c, FT[i], FP[i], p0[i], v0[i]);
+    if (degree == 4) poly4_set(c, FT[i], FP[i]);
+    if (degree == 5) poly5_set(c, FT[i], FP[i], p0[i], v0[i], a0[i]);
+    for (int k = 0; k < nt; k++) {
+      const double tk = t[(size_t)i * nt + k];
+      val[(size_t)i * nt + k] = poly_eval(c, degree, tk);
+      d1[(size_t)i * nt + k] = poly_d1(c, degree, tk);
+      d2[(size_t)i * nt + k] = poly_d2(c, degree, tk);
+    }
+  }
+  return 0;
+}
+
 /* ---------------------------------------------------------------------- */
 /* the tick                                                                */
 /* ---------------------------------------------------------------------- */

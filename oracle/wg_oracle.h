@@ -117,6 +117,17 @@ int wgo_steps_last_support(int keep, double ss, double ds, wg_rel_step_t *out, i
 int wgo_steps_arc(double x, double y, double arc_deg, int support_foot, double ss, double ds, wg_rel_step_t *out, int *n,
                   int cap, int *keep);
 
+/* ---- probes: the static pieces that restate the reference's ConvexHull.cpp / Polynome.cpp / PolynomeFoot.cpp, callable, so
+ * that tests can hold them to those files compiled (oracle/_ref/libwalkgen_parts_ref.so).  Each calls the static the oracle itself
+ * uses; points are (x, y) pairs.  See zmpdisc_oracle.c / herdt_oracle.c for the array shapes. */
+void wgo_probe_foot_corners(int n, const double *feet_xytheta, double sole_w, double sole_h, double constraint_x,
+                            double constraint_y, double *xy);
+int wgo_probe_convex_hull(int n_sets, int n_pts, const double *xy, double *hull, int *count);
+void wgo_probe_linear_system(int n_sets, int stride, const double *hull, const int *count, wg_zmp_polytope_t *polys, int *rc);
+int wgo_probe_zd_poly(int degree, int n, const double *FT, const double *FP, int nt, const double *t, double *val);
+int wgo_probe_tick_poly(int degree, int n, const double *FT, const double *FP, const double *p0, const double *v0,
+                        const double *a0, int nt, const double *t, double *val, double *d1, double *d2);
+
 #ifdef __cplusplus
 }
 #endif

@@ -774,15 +774,21 @@ static void foot_corners(double lx, double ly, double theta_deg, double hw, doub
   }
 }
 
+/* the half extents of the sole less the margins, :270-292: halved, then reduced */
+static void sole_half(double sole_w, double sole_h, double cx, double cy, double *hw, double *hh) {
+  *hw = sole_w * 0.5;
+  *hh = sole_h * 0.5;
+  *hh -= cy;
+  *hw -= cx;
+}
+
 /* BuildLinearConstraintInequalities, :258-539; arguments as wg_foot_constraints */
 int wgo_foot_constraints(int n, const double *time, const double *left, const int *left_type, const double *right,
                          double sole_w, double sole_h, double cx, double cy, int cap, wg_zmp_polytope_t *polys,
                          double *t_start, double *t_end) {
-  double lhw = sole_w * 0.5, lhh = sole_h * 0.5, rhw = sole_w * 0.5, rhh = sole_h * 0.5;
-  lhh -= cy;
-  rhh -= cy;
-  lhw -= cx;
-  rhw -= cx;
+  double lhw, lhh, rhw, rhh;
+  sole_half(sole_w, sole_h, cx, cy, &lhw, &lhh);
+  sole_half(sole_w, sole_h, cx, cy, &rhw, &rhh);
   int state = 0, count = 0;
   for (int i = 0; i < n; i++) {
     const double *L = left + 6 * (size_t)i, *R = right + 6 * (size_t)i;
@@ -835,6 +841,75 @@ int wgo_foot_constraints(int n, const double *time, const double *left, const in
     if (i == n - 1 && count > 0 && count - 1 < cap) t_end[count - 1] = time[i];
   }
   return count;
+}
+
+/* ---- probes: the statics above, callable (tests/test_ref_parts_*.py hold them to the compiled reference) -------------------
+ * Points are (x, y) pairs, x = col, y = row.  Nothing is computed here. */
+
+/* the four corners of n feet (x, y, theta in degrees) [n][3] as wgo_foot_constraints forms them -> xy [n][4][2] */
+void wgo_probe_foot_corners(int n, const double *feet, double sole_w, double sole_h, double cx, double cy, double *xy) {
+  double hw, hh;
+  sole_half(sole_w, sole_h, cx, cy, &hw, &hh);
+  for (int i = 0; i < n; i++) {
+    chpt_t c[4];
+    foot_corners(feet[3 * i], feet[3 * i + 1], feet[3 * i + 2], hw, hh, c);
+    for (int j = 0; j < 4; j++) {
+      xy[8 * i + 2 * j] = c[j].col;
+      xy[8 * i + 2 * j + 1] = c[j].row;
+    }
+  }
+}
+
+/* convex_hull of n_sets point sets of n_pts <= 16 points each, xy [n_sets][n_pts][2] -> hull [n_sets][n_pts + 1][2] (zero past the
+ * count) and count [n_sets] (-1: fewer than two directions).  Returns 0, or -2 on bad sizes. */
+int wgo_probe_convex_hull(int n_sets, int n_pts, const double *xy, double *hull, int *count) {
+  if (n_sets < 0 || n_pts < 1 || n_pts > 16) return -2;
+  for (int s = 0; s < n_sets; s++) {
+    chpt_t pts[16], h[17];
+    for (int i = 0; i < n_pts; i++) {
+      pts[i].col = xy[2 * ((size_t)s * n_pts + i)];
+      pts[i].row = xy[2 * ((size_t)s * n_pts + i) + 1];
+    }
+    int nh = convex_hull(pts, n_pts, h);
+    count[s] = nh;
+    for (int i = 0; i <= n_pts; i++) {
+      hull[2 * ((size_t)s * (n_pts + 1) + i)] = i < nh ? h[i].col : 0.0;
+      hull[2 * ((size_t)s * (n_pts + 1) + i) + 1] = i < nh ? h[i].row : 0.0;
+    }
+  }
+  return 0;
+}
+
+/* linear_system of n_sets hulls, hull [n_sets][stride][2] with count [n_sets] vertices -> P [n_sets]; rc [n_sets] is its return
+ * value (P[s] is left untouched where it refuses) */
+void wgo_probe_linear_system(int n_sets, int stride, const double *hull, const int *count, wg_zmp_polytope_t *P, int *rc) {
+  for (int s = 0; s < n_sets; s++) {
+    chpt_t h[WG_POLY_MAX_ROWS];
+    int n = count[s];
+    if (n < 0 || n > WG_POLY_MAX_ROWS || n > stride) {
+      rc[s] = -1;
+      continue;
+    }
+    for (int i = 0; i < n; i++) {
+      h[i].col = hull[2 * ((size_t)s * stride + i)];
+      h[i].row = hull[2 * ((size_t)s * stride + i) + 1];
+    }
+    rc[s] = linear_system(h, n, &P[s]);
+  }
+}
+
+/* the feet queue's polynomials: poly<degree>_set(FT[i], FP[i]) (degree 4: FP is the middle position), then poly_eval at
+ * t[i][0 .. nt) -> val [n][nt].  Returns 0, or -2 on an unknown degree. */
+int wgo_probe_zd_poly(int degree, int n, const double *FT, const double *FP, int nt, const double *t, double *val) {
+  if (degree < 3 || degree > 5) return -2;
+  for (int i = 0; i < n; i++) {
+    poly_t p;
+    if (degree == 3) poly3_set(&p, FT[i], FP[i]);
+    if (degree == 4) poly4_set(&p, FT[i], FP[i]);
+    if (degree == 5) poly5_set(&p, FT[i], FP[i]);
+    for (int k = 0; k < nt; k++) val[(size_t)i * nt + k] = poly_eval(&p, t[(size_t)i * nt + k]);
+  }
+  return 0;
 }
 
 /* ---- StepStackHandler: the step generators behind ":supportfoot", ":arc", ":lastsupport" ------------------------------

@@ -19,6 +19,12 @@
         that hold the outputs of ZMPDiscretization (tests/TestObject.cpp:344-385): time (1), left foot x y z (11-13),
         theta omega omega2 (20-22), right foot (23-25, 32-34), world-frame ZMP reference (35-36), as data, plus the
         step sequences of tests/TestKajita2003.cpp:95-152 (inputs).
+  ref_parts.npz : the fixed-seed cases of tests/test_ref_parts_gpu.py and what the COMPILED reference gives on them
+        (oracle/_ref/libwalkgen_parts_ref.so: ConvexHull.cpp, Polynome.cpp, PolynomeFoot.cpp behind oracle/ref_parts_shim.cpp):
+        - the first rows of every stance family of tests/refparts.py (inputs), their eight corners as the wg_trig.h oracle
+          forms them (inputs of the hull) and ComputeConvexHull::DoComputeConvexHull's vertex list and count (recorded output);
+        - Polynome4(t_single, step_height).Compute(k T) for the three models of refparts.SWING_MODELS (recorded output).
+        `python make_golden.py ref_parts` writes this file alone.
 """
 import os
 import sys
@@ -96,7 +102,26 @@ def overdriven_tick_qp(gait=18, tick_wanted=87, B=32, scale=3.0):
                 xl=np.full(n, -1e8), xu=np.full(n, 1e8))
 
 
+def ref_parts():
+    import refparts as rp
+    _, per = rp.fleet_deal()
+    out = dict(families=np.array(rp.FAMILIES), swing_models=np.array(rp.SWING_MODELS))
+    st = np.concatenate([rp.stances(f, per) for f in rp.FAMILIES])
+    xy = rp.corners(rp.ptrig(), st)
+    hull, count = rp.ref_hull(xy)
+    assert (count >= 3).all() and (count <= 8).all() and not hull[:, 8].any()
+    out.update(hull_stances=st, hull_family=np.repeat(np.arange(len(rp.FAMILIES), dtype=np.uint8), per), hull_corners=xy,
+               hull_vertices=hull[:, :8], hull_count=count)
+    for i, (T, t_single, step_height) in enumerate(rp.SWING_MODELS):
+        out["swing_z_%d" % i] = rp.ref_swing_z(t_single, step_height, T, int(round(1.0 / T)))
+    path = os.path.join(HERE, "ref_parts.npz")
+    np.savez_compressed(path, **out)
+    print("wrote %s: %d stances per family, %d bytes" % (path, per, os.path.getsize(path)))
+    assert os.path.getsize(path) < 1 << 20
+
+
 def main():
+    ref_parts()
     preview_ini()
     kajita_datrefs()
     datref = np.loadtxt(REF)
@@ -158,4 +183,7 @@ def save_ql_golden(recs):
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["ref_parts"]:
+        ref_parts()
+    else:
+        main()

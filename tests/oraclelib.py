@@ -4,6 +4,9 @@
   * `oracle/_ref/libqld_ref.so`  -- the reference's own qld.cpp, compiled by
                                     oracle/Makefile (present where the
                                     reference tree was available at build time)
+  * `oracle/_ref/libwalkgen_parts_ref.so` -- the reference's own ConvexHull.cpp,
+                                    Polynome.cpp and PolynomeFoot.cpp behind
+                                    oracle/ref_parts_shim.cpp (likewise)
 """
 import ctypes as C
 import os
@@ -15,6 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORACLE_DIR = os.path.join(ROOT, "oracle")
 ORACLE_SO = os.path.join(ORACLE_DIR, "libwg_oracle.so")
 REF_SO = os.path.join(ORACLE_DIR, "_ref", "libqld_ref.so")
+REF_PARTS_SO = os.path.join(ORACLE_DIR, "_ref", "libwalkgen_parts_ref.so")
 REF_SYM = "_Z7ql0001_PiS_S_S_S_S_PdS0_S0_S0_S0_S0_S0_S0_S_S_S_S0_S_S_S_S0_"
 
 _dp = C.POINTER(C.c_double)
@@ -39,6 +43,7 @@ def build_oracle():
 
 _oracle = None
 _ref = None
+_ref_parts = None
 
 
 def oracle():
@@ -57,6 +62,18 @@ def ref():
     if _ref is None:
         _ref = C.CDLL(REF_SO)
     return _ref
+
+
+def have_ref_parts():
+    return os.path.exists(REF_PARTS_SO)
+
+
+def ref_parts():
+    """the reference's hull and foot polynomials, compiled (entry points: oracle/ref_parts_shim.cpp)"""
+    global _ref_parts
+    if _ref_parts is None:
+        _ref_parts = C.CDLL(REF_PARTS_SO)
+    return _ref_parts
 
 
 def oracle_ql(q, eps=1e-8, hist_cap=4096):
