@@ -814,6 +814,55 @@ int wg_dimitrov_walk_dev(int B, int qcap, const wg_zmp_polytope_t *queues, const
 double wg_dimitrov_walk_time(double t0, int n_ticks);
 int wg_dimitrov_walk_safe_ticks(double t0, double t_have);
 
+/* The walk that follows each gait's own queue: a clock and a tick count per gait ------------------------------------------
+ *
+ * wg_dimitrov_follow_dev is wg_dimitrov_walk_dev with a range per gait, driven by the arrays the on-line calls leave on the
+ * device: the host keeps no mirror of the gaits' sample counts, takes no minimum over them and reads nothing back, whatever
+ * the gaits' step counts are and whenever each of them began, is fed or ends.  All pointers are DEVICE pointers.
+ *   queues, t_start, t_end, count   [B][qcap] and B, as in wg_dimitrov_walk_dev (what wg_foot_constraints_append_dev grows)
+ *   time     lcap             the array wg_foot_constraints_append_dev was given
+ *   have     B                samples gait b's queue covers: that call's `done` array
+ *   walk     B or NULL        the wg_zmpdisc state blobs: tell a gait whose walk has ended, and whose queue is therefore final
+ *   flags    WG_DIMITROV_FOLLOW_ALL_FINAL: every queue is final (walk is not read)
+ *   clock    B, in/out        the t at which the gait's next tick selects
+ *   ticks    B, in/out        ticks the gait has behind it; 0 starts a walk from whatever states[b] holds
+ *   outs     [tick_cap][B] or NULL, ABSOLUTE rows: tick k of gait b goes to outs[k * B + b]
+ *   ran_out  B or NULL        ORed: set where a tick of the gait ran out, NEVER cleared by this call (clear it before the walk)
+ * The call runs max_ticks rounds.  In each round, for every gait b, with N and T the configured Dimitrov model's:
+ *   final(b) = flags & WG_DIMITROV_FOLLOW_ALL_FINAL, or walk != NULL && walk[b].ended && !walk[b].error &&
+ *              walk[b].n_samples == have[b]          (ended, and the queue has consumed the end phase)
+ *   go(b)    = ticks[b] < tick_cap && (final(b) || clock[b] + (N - 1) * T <= time[have[b] - 1])
+ *              -- the select kernel's own expression t0 + i * T at i = N - 1, the one wg_dimitrov_walk_safe_ticks uses.
+ * A gait that goes selects at t = clock[b] (the bytes wg_dimitrov_select_polys_dev gives for t0 = clock[b]), runs the tick of
+ * wg_dimitrov_tick_batch_dev on states[b], writes its out struct to row ticks[b], then clock[b] += T and ticks[b] += 1: the
+ * walk's repeated addition, clock[b] == wg_dimitrov_walk_time(clock0[b], ticks[b]) bit for bit.  Of a gait that does not go the
+ * round touches no byte.
+ *   sits the whole call out, nothing touched:  ticks[b] < 0 (errors are sticky through it), count[b] <= 0 (a gait
+ *       wg_zmpdisc_* or the queue calls refused, or no queue yet), have[b] <= 0, or no round with go(b).
+ *   refused (tested behind those three):  ticks[b] > tick_cap, have[b] > lcap, a clock[b] that is not finite:
+ *       ticks[b] = WG_ERR_BAD_ARG and nothing else of the gait is written.  A neighbour never notices.
+ * CONTRACT: after any sequence of follow calls interleaved with calls that grow `have`, and for any cut into max_ticks,
+ * states[b], rows [0, ticks[b]) of outs and ran_out[b] (as an OR) are byte for byte what ONE wg_dimitrov_walk_dev(t0 = the gait's
+ * initial clock, n_ticks = ticks[b]) over the gait's FINAL queue leaves for that gait; rows >= ticks[b] are untouched.
+ * Why, per gait (the argument of wg_dimitrov_walk_safe_ticks with t_have = time[have[b] - 1] of this gait alone): every entry of
+ * the gait's provisional queue but the last is final; the last one's t_end is provisional, equals time[have[b] - 1] and only grows;
+ * a tick that goes compares it -- in the start test t_start <= t <= t_end and the N advance tests t + i T > t_end -- only with
+ * instants <= time[have[b] - 1], which no later, larger t_end answers differently; and a walk that never passes the last entry
+ * never sees the entries later calls add behind it.  A gait that is final has nothing provisional.  No gait's decision reads
+ * anything of another gait.
+ * Host-side errors (WG_ERR_BAD_ARG, nothing launched): no wg_dimitrov_configure; B < 0, qcap < 1, lcap < 1, tick_cap < 0,
+ * max_ticks < 0; a NULL among queues, t_start, t_end, count, time, have, clock, ticks, states; unknown flag bits.  B == 0 or
+ * max_ticks == 0 is WG_OK.  Asynchronous on hip_stream: 2 max_ticks launches, a round in which no gait goes included (the host
+ * does not know).  The selected polytopes and one int per gait (the row its tick writes, or -1) live in the context's walk buffer:
+ * follow calls and walks of one context are ordered like walks.  In the QL modes the longest-solve-first start order stays
+ * scheduling only; a gait that sits a round out keeps its previous iteration count.
+ * Added without a change of wg_abi_version(): detect by symbol. */
+#define WG_DIMITROV_FOLLOW_ALL_FINAL 1
+int wg_dimitrov_follow_dev(int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end,
+                           const int *count, int lcap, const double *time, const int *have,
+                           const wg_zmpdisc_state_t *walk, int flags, double *clock, int *ticks, int tick_cap, int max_ticks,
+                           wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int *ran_out, int max_iter, void *hip_stream);
+
 /* Invariant Hessian block on the matrix cores, batched over models -----------------------------------------------------
  *
  * wg_gramian_batch computes, for B models that differ in QP sampling period T[b] and CoM height h[b],
@@ -894,6 +943,11 @@ int wg_dimitrov_select_polys_dev_ctx(wg_ctx_t *ctx, int B, int qcap, const wg_zm
 int wg_dimitrov_walk_dev_ctx(wg_ctx_t *ctx, int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start,
                              const double *t_end, const int *count, double t0, int n_ticks, wg_dimitrov_state_t *states,
                              wg_dimitrov_out_t *outs, int *ran_out, int max_iter, void *hip_stream);
+int wg_dimitrov_follow_dev_ctx(wg_ctx_t *ctx, int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start,
+                               const double *t_end, const int *count, int lcap, const double *time, const int *have,
+                               const wg_zmpdisc_state_t *walk, int flags, double *clock, int *ticks, int tick_cap,
+                               int max_ticks, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int *ran_out, int max_iter,
+                               void *hip_stream);
 int wg_preview_configure_ctx(wg_ctx_t *ctx, const wg_preview_gains_t *gains, const double *F);
 int wg_preview_window_ctx(wg_ctx_t *ctx);
 int wg_preview_run_batch_dev_ctx(wg_ctx_t *ctx, int B, int L, const double *zmp_x_tm, const double *zmp_y_tm,

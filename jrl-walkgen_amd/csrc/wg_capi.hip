@@ -154,8 +154,8 @@ struct wg_ctx {
   DevBuf dim_buf;
   // Dimitrov fleets on the device: the per-chunk counts of wg_foot_constraints_batch_dev / _append_dev (the latter keeps each
   // gait's done and count as they were on entry behind them), and the B x N polytopes
-  // wg_dimitrov_walk_dev selects for the tick it launches next.  One launch at a time uses each: claimed and marked like the tick's
-  // buffers (fc_order, walk_order)
+  // wg_dimitrov_walk_dev / _follow_dev select for the tick they launch next (follow: and the row each gait's tick writes, behind
+  // them).  One launch at a time uses each: claimed and marked like the tick's buffers (fc_order, walk_order)
   DevBuf fc_buf, walk_polys;
   SlotOrder fc_order, walk_order;
   // preview control
@@ -1147,8 +1147,9 @@ int dimitrov_check(wg_ctx *ctx, int B, const wg_zmp_polytope_t *polys, const wg_
   return WG_OK;
 }
 
-// the tick launch of wg_dimitrov_tick_batch_dev and of every tick of wg_dimitrov_walk_dev; with ctx->launch_mu held
-int dimitrov_tick_launch(wg_ctx *ctx, int B, const wg_zmp_polytope_t *polys, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int max_iter, hipStream_t stq) {
+// the tick launch of wg_dimitrov_tick_batch_dev and of every tick of wg_dimitrov_walk_dev; with ctx->launch_mu held.  With `row`
+// (wg_dimitrov_follow_dev): the follow wrappers of the same ticks -- gait g writes row row[g] of outs, or sits the launch out
+int dimitrov_tick_launch(wg_ctx *ctx, int B, const wg_zmp_polytope_t *polys, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int max_iter, hipStream_t stq, const int *row = nullptr) {
   const int solver = ctx->dim_host->solver;
   if (solver != WG_DIMITROV_PLDP) {                      // modes QLD / QLDANDLQ: the in-wave ql0002 as the back-end
     const size_t ldsq = wg::dimitrov_qld_lds_bytes();
@@ -1156,19 +1157,29 @@ int dimitrov_tick_launch(wg_ctx *ctx, int B, const wg_zmp_polytope_t *polys, wg_
     // on the same state array (scheduling only).  The order lives in a buffer of the context: not while another stream's launch
     // of this context may still be reading it
     int *order = nullptr, *iters_out = nullptr;
-    if ((size_t)B > (size_t)ctx->num_cu * per_cu_granules(ldsq, 8) && !slot_pending_elsewhere(ctx->aux_order, stq) && env_flag("WG_QL_LPT", true))
+    if ((size_t)B > (size_t)ctx->num_cu * per_cu_granules(ldsq, 8) && !slot_pending_elsewhere(ctx->aux_order, stq) && env_flag("WG_QL_LPT", true)) {
+      // a follow launch writes the counts of the gaits that go only: the others keep their last one, which a fresh buffer has not
+      const bool fresh = row && !(ctx->dim_lpt.key == states && ctx->dim_lpt.B == B && ctx->dim_lpt.buf.p);
       if (int rc = lpt_prepare(ctx->dim_lpt, states, B, stq, &order, &iters_out)) return rc;
-    const auto kern = solver == WG_DIMITROV_QLDANDLQ ? wg_dimitrov_qld_tick_kernel<true> : wg_dimitrov_qld_tick_kernel<false>;
-    hipLaunchKernelGGL(kern, dim3(B), dim3(64), ldsq, stq, B, ctx->dim_dev, polys, states, outs, order, iters_out);
+      if (fresh) HIP_TRY(hipMemsetAsync(iters_out, 0, (size_t)B * sizeof(int), stq));
+    }
+    if (row) {
+      const auto kern = solver == WG_DIMITROV_QLDANDLQ ? wg_dimitrov_qld_follow_tick_kernel<true> : wg_dimitrov_qld_follow_tick_kernel<false>;
+      hipLaunchKernelGGL(kern, dim3(B), dim3(64), ldsq, stq, B, ctx->dim_dev, polys, states, outs, row, order, iters_out);
+    } else {
+      const auto kern = solver == WG_DIMITROV_QLDANDLQ ? wg_dimitrov_qld_tick_kernel<true> : wg_dimitrov_qld_tick_kernel<false>;
+      hipLaunchKernelGGL(kern, dim3(B), dim3(64), ldsq, stq, B, ctx->dim_dev, polys, states, outs, order, iters_out);
+    }
     HIP_TRY(hipGetLastError());
     return slot_mark(ctx->aux_order, stq);
   }
   const size_t lds = dimitrov_lds_bytes();
   if (lds > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(wg_dimitrov_tick_kernel),
+    HIP_TRY(hipFuncSetAttribute(row ? reinterpret_cast<const void *>(wg_dimitrov_follow_tick_kernel) : reinterpret_cast<const void *>(wg_dimitrov_tick_kernel),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   const int grid = B;
-  hipLaunchKernelGGL(wg_dimitrov_tick_kernel, dim3(grid), dim3(64), lds, stq, B, ctx->dim_dev, polys, states, outs, max_iter);
+  if (row) hipLaunchKernelGGL(wg_dimitrov_follow_tick_kernel, dim3(grid), dim3(64), lds, stq, B, ctx->dim_dev, polys, states, outs, row, max_iter);
+  else hipLaunchKernelGGL(wg_dimitrov_tick_kernel, dim3(grid), dim3(64), lds, stq, B, ctx->dim_dev, polys, states, outs, max_iter);
   HIP_TRY(hipGetLastError());
   return slot_mark(ctx->aux_order, stq);
 }
@@ -1372,6 +1383,33 @@ int wg_dimitrov_walk_dev_ctx(wg_ctx_t *ctx, int B, int qcap, const wg_zmp_polyto
     HIP_TRY(hipGetLastError());
     if (int rc = dimitrov_tick_launch(ctx, B, polys, states, outs ? outs + (size_t)k * (size_t)B : nullptr, max_iter, st)) return rc;
     t += T;                                               // BuildZMPTrajectoryFromFootTrajectory's own accumulation (:1189-1192)
+  }
+  return slot_mark(ctx->walk_order, st);
+}
+
+// The walk with a clock and a tick count per gait: max_ticks rounds of { follow select, follow tick }.  The select launch decides,
+// per gait, whether the gait's own queue covers the tick at the gait's own clock, and leaves the row its tick writes (or -1) in an
+// int per gait behind the selected polytopes -- the context's walk buffer, claimed and marked like a walk's.
+int wg_dimitrov_follow_dev_ctx(wg_ctx_t *ctx, int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count, int lcap, const double *time, const int *have, const wg_zmpdisc_state_t *walk, int flags, double *clock, int *ticks, int tick_cap, int max_ticks, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int *ran_out, int max_iter, void *hip_stream) {
+  if (int rc = select_check(ctx, B, qcap, queues, t_start, t_end, count)) return rc;
+  if (lcap < 1 || tick_cap < 0 || max_ticks < 0 || !time || !have || !clock || !ticks || !states)
+    return fail(WG_ERR_BAD_ARG, "need lcap >= 1, tick_cap >= 0, max_ticks >= 0, non-null time, have, clock, ticks and states");
+  if (flags & ~WG_DIMITROV_FOLLOW_ALL_FINAL) return fail(WG_ERR_BAD_ARG, "flags = %#x: WG_DIMITROV_FOLLOW_ALL_FINAL (1) is the only flag", flags);
+  if (B == 0 || max_ticks == 0) return WG_OK;
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  const int N = ctx->dim_host->N;
+  const double T = ctx->dim_host->T;
+  std::lock_guard<std::mutex> launch_lk(ctx->launch_mu);
+  if (int rc = slot_claim(ctx, ctx->walk_order, st, "Dimitrov walk")) return rc;
+  Arena a(ctx->walk_polys);
+  const auto sp = a.take<wg_zmp_polytope_t>((size_t)B * (size_t)N);
+  const auto sr = a.take<int>((size_t)B);
+  if (int rc = a.reserve()) return rc;
+  for (int k = 0; k < max_ticks; k++) {
+    hipLaunchKernelGGL(wg::wg_dimitrov_follow_select_kernel, dim3((B + 3) / 4), dim3(256), 0, st, B, qcap, queues, t_start, t_end, count,
+                       lcap, time, have, walk, flags & WG_DIMITROV_FOLLOW_ALL_FINAL, clock, ticks, tick_cap, N, T, a(sp), ran_out, a(sr));
+    HIP_TRY(hipGetLastError());
+    if (int rc = dimitrov_tick_launch(ctx, B, a(sp), states, outs, max_iter, st, a(sr))) return rc;
   }
   return slot_mark(ctx->walk_order, st);
 }
@@ -1831,6 +1869,7 @@ int wg_preview_window(void) {                        // a query: does not create
 }
 
 int wg_preview_run_batch_dev(int B, int L, const double *zmp_x_tm, const double *zmp_y_tm, double *state, double *com_tm, double *zmp2_tm, int simulation, void *hip_stream) { return on_default(&wg_preview_run_batch_dev_ctx, B, L, zmp_x_tm, zmp_y_tm, state, com_tm, zmp2_tm, simulation, hip_stream); }
+int wg_dimitrov_follow_dev(int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count, int lcap, const double *time, const int *have, const wg_zmpdisc_state_t *walk, int flags, double *clock, int *ticks, int tick_cap, int max_ticks, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int *ran_out, int max_iter, void *hip_stream) { return on_default(&wg_dimitrov_follow_dev_ctx, B, qcap, queues, t_start, t_end, count, lcap, time, have, walk, flags, clock, ticks, tick_cap, max_ticks, states, outs, ran_out, max_iter, hip_stream); }
 int wg_preview_follow_dev(int B, int lcap, const int *length, int *done, const double *zmp_x_tm, const double *zmp_y_tm, double *state, double *com_tm, double *zmp2_tm, int simulation, void *hip_stream) { return on_default(&wg_preview_follow_dev_ctx, B, lcap, length, done, zmp_x_tm, zmp_y_tm, state, com_tm, zmp2_tm, simulation, hip_stream); }
 int wg_preview_run_batch(int B, int L, const double *zmp_x, const double *zmp_y, double *state, double *com, double *zmp2, int simulation) { return on_default(&wg_preview_run_batch_ctx, B, L, zmp_x, zmp_y, state, com, zmp2, simulation); }
 int wg_gramian_batch_dev(int B, int N, const double *T, const double *h, double alpha, double beta, double gamma, int precision, double *Qb, void *hip_stream) { return on_default(&wg_gramian_batch_dev_ctx, B, N, T, h, alpha, beta, gamma, precision, Qb, hip_stream); }

@@ -155,7 +155,8 @@ struct DimitrovHost {
 constexpr int kDimitrovActiveCap = 40;   // E E' is singular beyond 2N = 32 active rows
 
 // one gait, one tick.  LDS: the structured PLDP work area (mcap = 8N) + 4 * 2N doubles (D, zmpref, NewX, X) + 8 (xk).
-__device__ int dimitrov_tick(const DimitrovConst &K, unsigned char *lds, const wg_zmp_polytope_t *__restrict__ polys,
+// (inlined by name: two kernels call it -- the tick's and its follow wrapper -- and each must keep the tick in its own body)
+__device__ __forceinline__ int dimitrov_tick(const DimitrovConst &K, unsigned char *lds, const wg_zmp_polytope_t *__restrict__ polys,
                              wg_dimitrov_state_t *st, wg_dimitrov_out_t *out, int max_iter) {   // returns PLDP's iteration count
   const int lane = threadIdx.x;
   const int N = K.N, n = 2 * N, mcap = WG_POLY_MAX_ROWS * N;
@@ -357,7 +358,7 @@ __host__ __device__ inline size_t dimitrov_qld_lds_bytes() {
 }
 
 template <bool kLQ>                                          // returns ql0002's iteration count (the launcher's start order, nothing else)
-__device__ int dimitrov_qld_tick(const DimitrovConst &K, double *lds, const wg_zmp_polytope_t *__restrict__ polys,
+__device__ __forceinline__ int dimitrov_qld_tick(const DimitrovConst &K, double *lds, const wg_zmp_polytope_t *__restrict__ polys,
                                  wg_dimitrov_state_t *st, wg_dimitrov_out_t *out) {
   const int lane = wg_lane();
   const int N = K.N, n = 2 * N, mcap = WG_PLDP_MMAX;

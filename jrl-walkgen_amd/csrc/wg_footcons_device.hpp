@@ -6,6 +6,7 @@
 //       FootConstraintsAsLinearSystem::BuildLinearConstraintInequalities  src/Mathematics/FootConstraintsAsLinearSystem.cpp:258-539
 //       ComputeLinearSystem :97-256, FindSimilarConstraints :55-92, ComputeConvexHull::DoComputeConvexHull ConvexHull.cpp:88-203
 //   wg_dimitrov_select_kernel          the queue walk of one tick (wg_dimitrov_select_polys_dev, wg_dimitrov_walk_dev)
+//   wg_dimitrov_follow_select_kernel   the same per gait, at the gait's own clock, where its own queue allows (wg_dimitrov_follow_dev)
 //       ZMPConstrainedQPFastFormulation::BuildConstraintMatrices  ZMPConstrainedQPFastFormulation.cpp:785-796, 822-835
 //
 // Queues.  The host call (wg_footcons.cpp) walks one gait sample by sample.  Here the inputs are the time-major arrays
@@ -197,13 +198,11 @@ wg_footcons_kernel(FcIn I, FcOut Q, int *__restrict__ cnt /* [chunks][B] */, FcR
 constexpr int kPolyWords = (int)(sizeof(wg_zmp_polytope_t) / 8);
 static_assert(sizeof(wg_zmp_polytope_t) == 248 && kPolyWords * 8 == (int)sizeof(wg_zmp_polytope_t), "wg_zmp_polytope_t: 31 words");
 
-__global__ void __launch_bounds__(256)
-wg_dimitrov_select_kernel(int B, int qcap, const wg_zmp_polytope_t *__restrict__ queues, const double *__restrict__ t_start,
-                          const double *__restrict__ t_end, const int *__restrict__ count, double t0, int N, double T,
-                          wg_zmp_polytope_t *__restrict__ polys, int *ran_out, int sticky) {
-  const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (b >= B) return;
-  const int cb = count[b], k = cb < qcap ? cb : qcap;
+// the search, the walk and the copies of gait b at t0, by its wave: what wg_dimitrov_select_kernel and the follow form below share
+__device__ __forceinline__ void dimitrov_select_gait(int lane, int b, int cb, int qcap, const wg_zmp_polytope_t *__restrict__ queues,
+                                                     const double *__restrict__ t_start, const double *__restrict__ t_end, double t0,
+                                                     int N, double T, wg_zmp_polytope_t *__restrict__ polys, int *ran_out, int sticky) {
+  const int k = cb < qcap ? cb : qcap;
   const double *ts = t_start + (size_t)b * qcap, *te = t_end + (size_t)b * qcap;
   int q = k, ran = 0, mine = 0;
   for (int base = 0; base < k && q == k; base += 64) {
@@ -233,6 +232,56 @@ wg_dimitrov_select_kernel(int B, int qcap, const wg_zmp_polytope_t *__restrict__
     if (w < words) dst[w] = k > 0 ? src[(size_t)e * kPolyWords + word] : 0ull;
   }
   if (ran_out && lane == 0 && (ran || !sticky)) ran_out[b] = ran;
+}
+
+__global__ void __launch_bounds__(256)
+wg_dimitrov_select_kernel(int B, int qcap, const wg_zmp_polytope_t *__restrict__ queues, const double *__restrict__ t_start,
+                          const double *__restrict__ t_end, const int *__restrict__ count, double t0, int N, double T,
+                          wg_zmp_polytope_t *__restrict__ polys, int *ran_out, int sticky) {
+  const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= B) return;
+  dimitrov_select_gait(lane, b, count[b], qcap, queues, t_start, t_end, t0, N, T, polys, ran_out, sticky);
+}
+
+// ---- the queue walk of one round of wg_dimitrov_follow_dev ------------------------------------------------------------------
+// The same layout, with a clock and a tick count per gait.  Every operand of the decision is wave-uniform (the wave's own gait):
+// the wave reads ticks[b], count[b], have[b], clock[b], the time of its last sample and, unless every queue is final, three ints
+// of its walk's state, and either goes -- selects at t = clock[b], leaves the row of outs its tick writes in row[b], advances
+// clock[b] by the walk's own addition and ticks[b] by one -- or leaves row[b] = -1 and touches nothing else of the gait (a refusal
+// writes ticks[b] as well).  An idle gait costs these loads and one store.
+//   sits out   ticks[b] < 0 (sticky), count[b] <= 0, have[b] <= 0, ticks[b] == tick_cap, or a queue that is neither final nor
+//              covers the tick's last instant: clock[b] + (N - 1) T <= time[have[b] - 1], the expression t0 + i * T of the walk
+//              above at i = N - 1
+//   refused    (tested behind the first three) ticks[b] > tick_cap, have[b] > lcap, a clock that is not finite
+__global__ void __launch_bounds__(256)
+wg_dimitrov_follow_select_kernel(int B, int qcap, const wg_zmp_polytope_t *__restrict__ queues, const double *__restrict__ t_start,
+                                 const double *__restrict__ t_end, const int *__restrict__ count, int lcap,
+                                 const double *__restrict__ time, const int *__restrict__ have,
+                                 const wg_zmpdisc_state_t *__restrict__ walk, int all_final, double *clock, int *ticks, int tick_cap,
+                                 int N, double T, wg_zmp_polytope_t *__restrict__ polys, int *ran_out, int *__restrict__ row) {
+  const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= B) return;
+  const int tk = ticks[b], cb = count[b], hv = have[b];
+  int r = -1;
+  if (tk >= 0 && cb > 0 && hv > 0) {
+    const double t = clock[b];
+    if (tk > tick_cap || hv > lcap || !(fabs(t) <= 1.7976931348623157e308)) {
+      if (lane == 0) ticks[b] = WG_ERR_BAD_ARG;
+    } else if (tk < tick_cap) {
+      bool go = all_final != 0;
+      if (!go && walk) go = walk[b].ended && !walk[b].error && walk[b].n_samples == hv;
+      if (!go) go = t + (N - 1) * T <= time[hv - 1];
+      if (go) {
+        dimitrov_select_gait(lane, b, cb, qcap, queues, t_start, t_end, t, N, T, polys, ran_out, 1);
+        r = tk;
+        if (lane == 0) {
+          clock[b] = t + T;
+          ticks[b] = tk + 1;
+        }
+      }
+    }
+  }
+  if (lane == 0) row[b] = r;
 }
 
 }  // namespace wg

@@ -10,7 +10,15 @@
 // walk on -- then a last append of the queues and the remaining ticks.  Every sample is classified once, and the final states --
 // hence the checksum -- are those of the whole-sequence mode.  ("the walk alone" is then the sum of the walk pieces, by events.)
 //
-//   dimitrov_fleet [--batch B] [--steps S] [--ticks K] [--solver 0|1|2] [--fleet FILE] [--online K]
+// With --online K --follow the walk pieces are ONE wg_dimitrov_follow_dev behind every feeding instead: every gait has its own clock
+// and tick count on the device and ticks where its own queue allows (`have` = the done array of wg_foot_constraints_append_dev,
+// `walk` = the state blobs, tick_cap = --ticks).  The host does no arithmetic on lengths for walking -- no minimum over the gaits
+// still walking, no wg_dimitrov_walk_safe_ticks, no wg_dimitrov_walk_time: it sizes the call's rounds from the steps it has just
+// fed (the longest duration any gait was given, over the tick period, plus one; behind an end call: --ticks).  ran_out is cleared
+// once and ORed on the device.  The final states, hence the checksum, are again those of the whole-sequence mode.
+// With --ragged gait g of the built-in fleet walks its own number of steps, between S/2 and S (as kajita_fleet --ragged).
+//
+//   dimitrov_fleet [--batch B] [--steps S] [--ticks K] [--solver 0|1|2] [--fleet FILE] [--online K [--follow]] [--ragged]
 //
 // --fleet FILE runs a fleet somebody else drew instead of the built-in one (tests/test_dimitrov_walk_gpu.py compares the
 // checksum with its own run of the same fleet): int32 B, int32 smax, wg_zmpdisc_model_t, B x smax wg_rel_step_t, B int32
@@ -26,6 +34,7 @@ using wg_fleet::dev_upload;
 
 int main(int argc, char **argv) {
   int B = 4096, S = 8, K = 40, solver = WG_DIMITROV_PLDP, online = 0;
+  bool follow = false, ragged = false;
   const char *fleet = nullptr;
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--batch") && i + 1 < argc) B = atoi(argv[++i]);
@@ -33,8 +42,11 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[i], "--ticks") && i + 1 < argc) K = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--solver") && i + 1 < argc) solver = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--fleet") && i + 1 < argc) fleet = argv[++i];
+    else if (!strcmp(argv[i], "--follow")) follow = true;
+    else if (!strcmp(argv[i], "--ragged")) ragged = true;
     else if (!strcmp(argv[i], "--online") && i + 1 < argc) { online = atoi(argv[++i]); if (online < 1 || online > WG_ZMPDISC_MAX_STEPS) { fprintf(stderr, "FAILED: need 1 <= --online K <= %d\n", WG_ZMPDISC_MAX_STEPS); return 1; } }
   }
+  if (follow && !online) { fprintf(stderr, "FAILED: --follow needs --online K\n"); return 1; }
   wg_zmpdisc_model_t zm;
   wg_zmpdisc_defaults(&zm);
   zm.t_single = 0.7; zm.t_double = 0.13;                       // phase boundaries off the 0.1 s grid of the previewed instants
@@ -57,13 +69,17 @@ int main(int argc, char **argv) {
     if (B < 1 || S < 2 || S > WG_ZMPDISC_MAX_STEPS) { fprintf(stderr, "FAILED: need B >= 1, 2 <= steps <= %d\n", WG_ZMPDISC_MAX_STEPS); return 1; }
     steps.resize((size_t)B * S); n_steps.assign(B, S); feet.resize((size_t)B * 6);
     for (int g = 0; g < B; ++g) {                               // straight walks of varying step length: axis-aligned soles
+      if (ragged) {                                             // S/2 .. S steps, at least the two the begin call takes
+        const int lo = S / 2 > 2 ? S / 2 : 2;
+        n_steps[g] = lo + (int)(std::mt19937_64(7700 + g)() % (unsigned)(S - lo + 1));
+      }
       std::mt19937_64 rng(20080 + g);
       std::uniform_real_distribution<double> len(0.1, 0.25);
       double side = (g & 1) ? 1.0 : -1.0;
       for (int i = 0; i < S; ++i) {
         wg_rel_step_t &s = steps[(size_t)g * S + i];
         memset(&s, 0, sizeof s);
-        const bool ends = i == 0 || i == S - 1;
+        const bool ends = i == 0 || i == n_steps[g] - 1;
         s.sx = ends ? 0.0 : len(rng);
         s.sy = side * (i == 0 ? 0.105 : 0.21);
         s.ss_time = zm.t_single; s.ds_time = 0.0; s.step_type = 1;
@@ -127,6 +143,27 @@ int main(int argc, char **argv) {
     CHECK_HIP(dev_alloc(&d_done, B));
     ran_pieces.reserve((size_t)(2 * plan.n_calls + 3) * B);   // never reallocated: pieces are copied into it asynchronously
   }
+  // --follow: a clock and a tick count per gait, and the rounds of the follow call behind each feeding: the longest duration any
+  // gait was fed (begin: the rest phase and the second step; the first step is where the walk stands), in ticks, plus one
+  double *d_clock = nullptr; int *d_ticks = nullptr;
+  std::vector<int> rounds;
+  if (follow) {
+    CHECK_HIP(dev_alloc(&d_clock, B));
+    CHECK_HIP(dev_alloc(&d_ticks, B));
+    auto dur = [&](const wg_rel_step_t &s) { return s.ds_time != 0.0 ? s.ds_time + s.ss_time : zm.t_double + zm.t_single; };
+    rounds.assign(plan.n_calls + 1, 0);
+    for (int c = 0; c <= plan.n_calls; ++c) {
+      double longest = 0.0;
+      for (int g = 0; g < B; ++g) {
+        double d = 0.0;
+        if (c == 0) d = 2 * zm.preview_time + dur(steps[(size_t)g * S + 1]);
+        else for (int i = 0; i < plan.cns[(size_t)(c - 1) * B + g]; ++i) d += dur(plan.chunks[((size_t)(c - 1) * B + g) * online + i]);
+        longest = d > longest ? d : longest;
+      }
+      const double r = longest / dm.T + 1.0;
+      rounds[c] = r < (double)K ? (int)r : K;
+    }
+  }
   const int n_calls = plan.n_calls;
   const std::vector<int> &sel = plan.sel, &len_after = plan.len_after, &len_ended = plan.len_ended;
   hipStream_t st;
@@ -142,6 +179,7 @@ int main(int argc, char **argv) {
       double t = 0.0;
       int ticks = 0;
       ran_pieces.clear();
+      int max_ticks = 0;                                       // --follow: the rounds of the next follow call
       for (hipEvent_t e : ev) (void)hipEventDestroy(e);
       ev.clear();
       // the queues up to the feet's new lengths, then the ticks that became safe: those whose N instants lie at or before the
@@ -155,6 +193,16 @@ int main(int argc, char **argv) {
         }
         if (int rc = wg_foot_constraints_append_dev(B, lcap, first, d_done, d_len, d_time, d_left, d_lty, d_right, 0.24, 0.138, 0.02,
                                                     0.02, qcap, d_queues, d_ts, d_te, d_count, st)) return rc;
+        if (follow) {                                          // every gait over the ticks its own queue has made safe
+          hipEvent_t e0, e1;
+          if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return WG_ERR_HIP;
+          ev.push_back(e0); ev.push_back(e1);
+          (void)hipEventRecord(e0, st);
+          if (int rc = wg_dimitrov_follow_dev(B, qcap, d_queues, d_ts, d_te, d_count, lcap, d_time, d_done, d_walk, 0, d_clock, d_ticks,
+                                              K, max_ticks, d_states, nullptr, d_ran, 0, st)) return rc;
+          (void)hipEventRecord(e1, st);
+          return WG_OK;
+        }
         int n = K - ticks;
         if (have > 0) {
           const int safe = wg_dimitrov_walk_safe_ticks(t, time[have - 1]);
@@ -179,16 +227,23 @@ int main(int argc, char **argv) {
         for (int g = 0; g < B; ++g)
           if (sel[(size_t)c * B + g]) { any = true; ended[g] = 1; cur[g] = len_ended[g]; }
         if (!any) return WG_OK;
+        max_ticks = K;                                         // an ended gait's queue is final: whatever it has left
         if (int rc = wg_zmpdisc_end_dev(&zm, B, d_sel + (size_t)c * B, lcap, nullptr, nullptr, nullptr, nullptr, d_left, d_lty, d_right,
                                         nullptr, d_walk, d_len, st)) return rc;
         return grow_and_walk();
       };
       CHECK_HIP(hipMemsetAsync(d_done, 0, sizeof(int) * B, st));
+      if (follow) {
+        CHECK_HIP(hipMemsetAsync(d_clock, 0, sizeof(double) * B, st));
+        CHECK_HIP(hipMemsetAsync(d_ticks, 0, sizeof(int) * B, st));
+        CHECK_HIP(hipMemsetAsync(d_ran, 0, sizeof(int) * B, st));       // ORed by the follow calls, never cleared
+      }
       CHECK_HIP(hipStreamSynchronize(st));
       const auto t0 = std::chrono::steady_clock::now();
       CHECK_WG(wg_zmpdisc_begin_dev(&zm, B, S, d_steps, d_two, d_feet, lcap, nullptr, nullptr, nullptr, nullptr, d_left, d_lty, d_right,
                                     nullptr, d_walk, d_len, st));
       for (int g = 0; g < B; ++g) cur[g] = len_after[g];
+      if (follow) max_ticks = rounds[0];
       CHECK_WG(grow_and_walk());
       CHECK_WG(end_those_out_of_steps(0));
       for (int c = 0; c < n_calls; ++c) {
@@ -196,12 +251,18 @@ int main(int argc, char **argv) {
                                        nullptr, nullptr, d_left, d_lty, d_right, nullptr, d_walk, d_len, st));
         for (int g = 0; g < B; ++g)
           if (!ended[g]) cur[g] = len_after[(size_t)(c + 1) * B + g];
+        if (follow) max_ticks = rounds[c + 1];
         CHECK_WG(grow_and_walk());
         CHECK_WG(end_those_out_of_steps(c + 1));
       }
       CHECK_HIP(hipStreamSynchronize(st));
       sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-      if (ticks != K) { fprintf(stderr, "FAILED: walked %d ticks of %d\n", ticks, K); return 1; }
+      if (follow) {
+        std::vector<int> ticks_h(B);
+        CHECK_HIP(hipMemcpy(ticks_h.data(), d_ticks, sizeof(int) * B, hipMemcpyDeviceToHost));
+        for (int g = 0; g < B; ++g)
+          if (ticks_h[g] != K) { fprintf(stderr, "FAILED: gait %d walked %d ticks of %d\n", g, ticks_h[g], K); return 1; }
+      } else if (ticks != K) { fprintf(stderr, "FAILED: walked %d ticks of %d\n", ticks, K); return 1; }
       sec_walk = 0.0;
       for (size_t i = 0; i + 1 < ev.size(); i += 2) { float ms = 0.f; CHECK_HIP(hipEventElapsedTime(&ms, ev[i], ev[i + 1])); sec_walk += ms * 1e-3; }
       std::vector<int> len_h(B);

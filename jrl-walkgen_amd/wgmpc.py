@@ -144,6 +144,9 @@ def lib():
             _lib.wg_dimitrov_walk_time.argtypes = [C.c_double, C.c_int]
             _lib.wg_dimitrov_walk_time.restype = C.c_double
             _lib.wg_dimitrov_walk_safe_ticks.argtypes = [C.c_double, C.c_double]
+        if hasattr(_lib, "wg_dimitrov_follow_dev"):          # absent from older experiment builds (WG_LIB_PATH, A/B runs)
+            _lib.wg_dimitrov_follow_dev.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int] + \
+                [C.c_void_p] * 2 + [C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p]
         # contexts: NAME_ctx(ctx, args...) for every entry point NAME(args...) that keeps or stages device-side state
         _lib.wg_ctx_create.argtypes = [C.c_int, C.c_void_p]
         _lib.wg_ctx_destroy.argtypes = [C.c_void_p]
@@ -174,7 +177,7 @@ CTX_ENTRY_POINTS = ("wg_set_overlap_strict", "wg_overlap_serialised", "wg_qp_sol
                     "wg_zmpdisc_batch", "wg_zmpdisc_batch_dev", "wg_zmpdisc_full_batch_dev", "wg_foot_constraints_batch_dev",
                     "wg_zmpdisc_begin_dev", "wg_zmpdisc_append_dev", "wg_zmpdisc_end_dev",
                     "wg_dimitrov_select_polys_dev", "wg_dimitrov_walk_dev", "wg_foot_constraints_append_dev",
-                    "wg_dimitrov_walk_time", "wg_dimitrov_walk_safe_ticks", "wg_preview_follow_dev")
+                    "wg_dimitrov_walk_time", "wg_dimitrov_walk_safe_ticks", "wg_preview_follow_dev", "wg_dimitrov_follow_dev")
 
 
 class Context:
@@ -754,6 +757,37 @@ def dimitrov_walk_dev(B, qcap, queues_ptr, t_start_ptr, t_end_ptr, count_ptr, t0
     """n_ticks x { select at t; tick; t += T } on one stream; outs [n_ticks][B] or None, ran_out [B] or None"""
     _check(lib().wg_dimitrov_walk_dev(int(B), int(qcap), queues_ptr, t_start_ptr, t_end_ptr, count_ptr, float(t0), int(n_ticks),
                                       states_ptr, outs_ptr, ran_out_ptr, int(max_iter), stream))
+
+
+DIMITROV_FOLLOW_ALL_FINAL = 1
+
+
+def _dimitrov_follow_args(B, qcap, queues_ptr, t_start_ptr, t_end_ptr, count_ptr, lcap, time_ptr, have_ptr, walk_ptr, flags,
+                          clock_ptr, ticks_ptr, tick_cap, max_ticks, states_ptr, outs_ptr, ran_out_ptr, max_iter, stream):
+    return (int(B), int(qcap), queues_ptr, t_start_ptr, t_end_ptr, count_ptr, int(lcap), time_ptr, have_ptr, walk_ptr, int(flags),
+            clock_ptr, ticks_ptr, int(tick_cap), int(max_ticks), states_ptr, outs_ptr, ran_out_ptr, int(max_iter), stream)
+
+
+def dimitrov_follow_dev(B, qcap, queues_ptr, t_start_ptr, t_end_ptr, count_ptr, lcap, time_ptr, have_ptr, walk_ptr, flags,
+                        clock_ptr, ticks_ptr, tick_cap, max_ticks, states_ptr, outs_ptr=None, ran_out_ptr=None, max_iter=0,
+                        stream=None):
+    """max_ticks rounds of { select; tick } in which gait b ticks at its own clock[b] while its own queue covers the tick
+    (or is final: walk[b] ended, or DIMITROV_FOLLOW_ALL_FINAL) and ticks[b] < tick_cap; outs [tick_cap][B], absolute rows;
+    ran_out is ORed, never cleared (wg_mpc.h)"""
+    _check(lib().wg_dimitrov_follow_dev(*_dimitrov_follow_args(B, qcap, queues_ptr, t_start_ptr, t_end_ptr, count_ptr, lcap,
+                                                               time_ptr, have_ptr, walk_ptr, flags, clock_ptr, ticks_ptr, tick_cap,
+                                                               max_ticks, states_ptr, outs_ptr, ran_out_ptr, max_iter, stream)))
+
+
+def dimitrov_follow_dev_ctx(ctx, B, qcap, queues_ptr, t_start_ptr, t_end_ptr, count_ptr, lcap, time_ptr, have_ptr, walk_ptr, flags,
+                            clock_ptr, ticks_ptr, tick_cap, max_ticks, states_ptr, outs_ptr=None, ran_out_ptr=None, max_iter=0,
+                            stream=None):
+    """the same on a Context (or a raw wg_ctx_t handle)"""
+    h = ctx.handle if isinstance(ctx, Context) else ctx
+    _check(lib().wg_dimitrov_follow_dev_ctx(h, *_dimitrov_follow_args(B, qcap, queues_ptr, t_start_ptr, t_end_ptr, count_ptr, lcap,
+                                                                      time_ptr, have_ptr, walk_ptr, flags, clock_ptr, ticks_ptr,
+                                                                      tick_cap, max_ticks, states_ptr, outs_ptr, ran_out_ptr,
+                                                                      max_iter, stream)))
 
 
 def dimitrov_walk_time(t0, n_ticks):
