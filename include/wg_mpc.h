@@ -677,6 +677,64 @@ int wg_zmpdisc_end_dev(const wg_zmpdisc_model_t *model, int B, const int *select
                        double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm,
                        double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream);
 
+/* Where the steps come from: the step stack on the device ---------------------------------------------------------------
+ *
+ * The generators of the reference's StepStackHandler for B gaits at once, in the layout wg_zmpdisc_full_batch_dev,
+ * wg_zmpdisc_begin_dev and wg_zmpdisc_append_dev read: a fleet whose commands live in device memory (a planner's output, a
+ * policy's tensor) goes from a few numbers per gait to its CoM on one stream.  One call turns every gait's command list into
+ * the steps of THIS call, written from index 0 of the gait's row, and their count n_steps[b] -- the arguments of the zmpdisc
+ * call behind it.  Every step carries step_type 0, pad_ 0 and the call's ss_time, ds_time.
+ *   op                    arguments                reference (src/StepStackHandler.cpp)            step                  keep
+ *   WG_STEP_NONE                                                                                   none                  unchanged
+ *   WG_STEP_SUPPORT_FOOT  foot                     PrepareForSupportFoot :754-764                  (0, foot 0.095, 0)    unchanged
+ *   WG_STEP_ARC           a = x, y, arc_deg; foot  CreateArcInStepStack :299-457                   the arc's steps       the foot it ends on
+ *   WG_STEP_LAST_SUPPORT                           FinishOnTheLastCorrectSupportFoot :872-882      (0, keep 0.19, 0)     unchanged
+ *   WG_STEP_ADD           a = sx, sy, theta        AddStepInTheStack :850-863 (the call's times)   (sx, sy, theta)       unchanged
+ *   WG_STEP_ONLINE        a = x, y, theta          AddStandardOnLineStep(true, ..) :791-832        (x, y + keep 0.19, theta)  -keep
+ *   WG_STEP_ONLINE_IDLE                            AddStandardOnLineStep(false, ..) :791-832       (0, keep 0.19, 0)     -keep
+ * keep is m_KeepLastCorrectSupportFoot (+1 / -1; a fresh stack holds {1, 0, 0, 0}); it is carried by the stack alone, so a
+ * command list gives the same steps however it is cut into calls.  Angles are degrees.  An arc of radius R = |(x, y)| turns
+ * by arc_deg in steps of 0.15 m along it, plus one shorter step where they do not divide it; its direction is the sign of y,
+ * x < 0 walks it backwards.  x = y = 0 and arc_deg = 0 give no step and keep = foot, as in the reference.  The arguments an
+ * op does not take are ignored, but a[] must be finite.
+ *   cmds     B x ccap   gait b's list is its first n_cmds[b]
+ *   stack    B, in/out  keep, the sticky error, n_given (steps given so far, accumulated), pad_
+ *   steps    B x smax   bytes of a row past n_steps[b] are untouched
+ *   n_cmds[b] == 0      n_steps[b] = 0 and the stack is untouched: the gait sits out the append that follows
+ * Refusals are per gait, decided before the gait's first write and sticky in stack[b].error: a refused call sets
+ * n_steps[b] = 0 and stack[b].error and writes nothing else of the gait, and every later call finds the code and does the
+ * same.  wg_zmpdisc_begin_dev then refuses the gait with its own sticky code (n_steps < 2) and wg_zmpdisc_append_dev lets it
+ * sit out; a neighbour never notices.  The first command, in order, that offends decides the code:
+ *   WG_STEPS_BAD_INPUT  an unknown op; a foot that is not +1 / -1 where the op takes one; a non-finite a[]; arc_deg < 0 (a
+ *                       declared refusal: the reference pushes one step for it that no generator here restates -- the way
+ *                       to walk an arc the other way is the sign of y); a radius that overflows; n_cmds[b] outside
+ *                       [0, ccap]; a stack whose keep is not +1 / -1 (never initialised)
+ *   WG_STEPS_CAPACITY   the commands give more than smax steps (an arc's count is known before its first step)
+ * Host-side errors (WG_ERR_BAD_ARG, nothing launched): a NULL array, B < 0, ccap < 1, smax outside
+ * [1, WG_ZMPDISC_MAX_STEPS], non-finite ss or ds.  B == 0 is WG_OK.  Asynchronous on hip_stream; keeps nothing in the context.
+ * wg_steps_plan is the same arithmetic for one gait on the host (the same bytes; returns WG_OK with the verdict in
+ * stack->error and *n_steps, or WG_ERR_BAD_ARG); wg_steps_count is the number of steps a list gives, for sizing buffers
+ * together with wg_zmpdisc_length_after -- a walk's length depends only on the count and the times -- or a code
+ * (WG_STEPS_CAPACITY: more than WG_ZMPDISC_MAX_STEPS, what no call can hold).
+ * Added without a change of wg_abi_version(): detect by symbol. */
+enum { WG_STEP_NONE = 0, WG_STEP_SUPPORT_FOOT, WG_STEP_ARC, WG_STEP_LAST_SUPPORT, WG_STEP_ADD, WG_STEP_ONLINE, WG_STEP_ONLINE_IDLE };
+typedef struct wg_step_cmd {
+  int op, foot;                       /* foot = +1 / -1 where the op takes one */
+  double a[3];
+} wg_step_cmd_t;
+typedef struct wg_step_stack {
+  int keep;                           /* m_KeepLastCorrectSupportFoot (starts at 1) */
+  int error;                          /* 0 or the sticky code */
+  int n_given, pad_;                  /* steps given so far */
+} wg_step_stack_t;
+#define WG_STEPS_BAD_INPUT (-1)
+#define WG_STEPS_CAPACITY (-2)
+int wg_steps_count(const wg_step_cmd_t *cmds, int n_cmds);
+int wg_steps_plan(const wg_step_cmd_t *cmds, int n_cmds, double ss, double ds, wg_step_stack_t *stack, int smax,
+                  wg_rel_step_t *steps, int *n_steps);
+int wg_steps_plan_dev(int B, int ccap, const wg_step_cmd_t *cmds, const int *n_cmds, double ss, double ds,
+                      wg_step_stack_t *stack, int smax, wg_rel_step_t *steps, int *n_steps, void *hip_stream);
+
 /* The preview that follows such a walk: every gait advances over exactly the rows its own queue has made safe -------------
  *
  * wg_preview_follow_dev is wg_preview_run_batch_dev with a range per gait, driven by the `length` array the wg_zmpdisc
@@ -984,6 +1042,8 @@ int wg_zmpdisc_end_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_model_t *model, int B
                            double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm,
                            int *left_type_tm, double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length,
                            void *hip_stream);
+int wg_steps_plan_dev_ctx(wg_ctx_t *ctx, int B, int ccap, const wg_step_cmd_t *cmds, const int *n_cmds, double ss, double ds,
+                          wg_step_stack_t *stack, int smax, wg_rel_step_t *steps, int *n_steps, void *hip_stream);
 
 #ifdef __cplusplus
 }

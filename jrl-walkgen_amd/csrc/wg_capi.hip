@@ -27,6 +27,7 @@
 #include "wg_ql_kernels.hpp"
 #include "wg_pldp_kernels.hpp"
 #include "wg_dimitrov_kernels.hpp"
+#include "wg_steps_kernels.hpp"
 
 
 namespace {
@@ -1762,6 +1763,18 @@ int wg_zmpdisc_end_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_model_t *model, int B
   return zd_online(ctx, wg::ZD_OP_END, model, B, 0, nullptr, nullptr, nullptr, select, lcap, O, state, length, hip_stream);
 }
 
+// the step stack on the device: one wave per gait (wg_steps_kernels.hpp); the host twins are wg_steps.cpp
+int wg_steps_plan_dev_ctx(wg_ctx_t *ctx, int B, int ccap, const wg_step_cmd_t *cmds, const int *n_cmds, double ss, double ds, wg_step_stack_t *stack, int smax, wg_rel_step_t *steps, int *n_steps, void *hip_stream) {
+  if (int rc = use_ctx(ctx)) return rc;
+  if (B < 0 || ccap < 1 || smax < 1 || smax > WG_ZMPDISC_MAX_STEPS || !cmds || !n_cmds || !stack || !steps || !n_steps || !wg::sp_finite(ss) || !wg::sp_finite(ds))
+    return fail(WG_ERR_BAD_ARG, "need B >= 0, ccap >= 1, 1 <= smax <= %d, finite times, non-null arrays", WG_ZMPDISC_MAX_STEPS);
+  if (B == 0) return WG_OK;
+  hipLaunchKernelGGL(wg::wg_steps_plan_kernel, dim3((B + wg::kSpWaves - 1) / wg::kSpWaves), dim3(64 * wg::kSpWaves), 0,
+                     reinterpret_cast<hipStream_t>(hip_stream), B, ccap, cmds, n_cmds, ss, ds, stack, smax, steps, n_steps);
+  HIP_TRY(hipGetLastError());
+  return WG_OK;
+}
+
 int wg_zmpdisc_batch_ctx(wg_ctx_t *ctx, const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap, double *zmp, double *zmp_theta, int *zmp_type, double *left, int *left_type, double *right, int *right_type, int *length) {
   wg::ZdConst K;
   if (int rc = zd_check(ctx, model, &K, B, smax, lcap, steps && n_steps && init_feet && length, "arrays")) return rc;
@@ -1879,6 +1892,7 @@ int wg_zmpdisc_full_batch_dev(const wg_zmpdisc_model_t *model, int B, int smax, 
 int wg_zmpdisc_begin_dev(const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream) { return on_default(&wg_zmpdisc_begin_dev_ctx, model, B, smax, steps, n_steps, init_feet, lcap, zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, left_type_tm, right_tm, right_type_tm, state, length, hip_stream); }
 int wg_zmpdisc_append_dev(const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream) { return on_default(&wg_zmpdisc_append_dev_ctx, model, B, smax, steps, n_steps, lcap, zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, left_type_tm, right_tm, right_type_tm, state, length, hip_stream); }
 int wg_zmpdisc_end_dev(const wg_zmpdisc_model_t *model, int B, const int *select, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream) { return on_default(&wg_zmpdisc_end_dev_ctx, model, B, select, lcap, zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, left_type_tm, right_tm, right_type_tm, state, length, hip_stream); }
+int wg_steps_plan_dev(int B, int ccap, const wg_step_cmd_t *cmds, const int *n_cmds, double ss, double ds, wg_step_stack_t *stack, int smax, wg_rel_step_t *steps, int *n_steps, void *hip_stream) { return on_default(&wg_steps_plan_dev_ctx, B, ccap, cmds, n_cmds, ss, ds, stack, smax, steps, n_steps, hip_stream); }
 int wg_zmpdisc_batch(const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap, double *zmp, double *zmp_theta, int *zmp_type, double *left, int *left_type, double *right, int *right_type, int *length) { return on_default(&wg_zmpdisc_batch_ctx, model, B, smax, steps, n_steps, init_feet, lcap, zmp, zmp_theta, zmp_type, left, left_type, right, right_type, length); }
 
 }  // extern "C"

@@ -18,7 +18,14 @@
 // once and ORed on the device.  The final states, hence the checksum, are again those of the whole-sequence mode.
 // With --ragged gait g of the built-in fleet walks its own number of steps, between S/2 and S (as kajita_fleet --ragged).
 //
+// With --plan the built-in fleet's steps are decided on the device instead (the twin of kajita_fleet --plan): the only step input
+// uploaded is a command list per gait (wg_fleet::command_plan), and wg_steps_plan_dev writes the steps into the array wg_zmpdisc_*
+// reads, on the same stream -- the whole list in front of wg_zmpdisc_full_batch_dev, or with --online K the support foot and the
+// arc in front of wg_zmpdisc_begin_dev and K commands in front of every wg_zmpdisc_append_dev.  --plan-host is its host-fed twin:
+// the same lists through wg_steps_plan and the upload path.  Both print the same checksum.
+//
 //   dimitrov_fleet [--batch B] [--steps S] [--ticks K] [--solver 0|1|2] [--fleet FILE] [--online K [--follow]] [--ragged]
+//                  [--plan | --plan-host]
 //
 // --fleet FILE runs a fleet somebody else drew instead of the built-in one (tests/test_dimitrov_walk_gpu.py compares the
 // checksum with its own run of the same fleet): int32 B, int32 smax, wg_zmpdisc_model_t, B x smax wg_rel_step_t, B int32
@@ -35,6 +42,7 @@ using wg_fleet::dev_upload;
 int main(int argc, char **argv) {
   int B = 4096, S = 8, K = 40, solver = WG_DIMITROV_PLDP, online = 0;
   bool follow = false, ragged = false;
+  int planned = 0;                                            // 1: --plan (steps planned on the device), 2: --plan-host
   const char *fleet = nullptr;
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--batch") && i + 1 < argc) B = atoi(argv[++i]);
@@ -44,9 +52,14 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[i], "--fleet") && i + 1 < argc) fleet = argv[++i];
     else if (!strcmp(argv[i], "--follow")) follow = true;
     else if (!strcmp(argv[i], "--ragged")) ragged = true;
+    else if (!strcmp(argv[i], "--plan")) planned = 1;
+    else if (!strcmp(argv[i], "--plan-host")) planned = 2;
     else if (!strcmp(argv[i], "--online") && i + 1 < argc) { online = atoi(argv[++i]); if (online < 1 || online > WG_ZMPDISC_MAX_STEPS) { fprintf(stderr, "FAILED: need 1 <= --online K <= %d\n", WG_ZMPDISC_MAX_STEPS); return 1; } }
   }
   if (follow && !online) { fprintf(stderr, "FAILED: --follow needs --online K\n"); return 1; }
+  if (planned && (ragged || fleet || S < 4)) { fprintf(stderr, "FAILED: --plan needs steps >= 4, no --ragged and no --fleet\n"); return 1; }
+  const bool on_device = planned == 1;
+  wg_fleet::CommandPlan cp;
   wg_zmpdisc_model_t zm;
   wg_zmpdisc_defaults(&zm);
   zm.t_single = 0.7; zm.t_double = 0.13;                       // phase boundaries off the 0.1 s grid of the previewed instants
@@ -88,6 +101,13 @@ int main(int argc, char **argv) {
       const double f[6] = {0.0, 0.095, 0.0, 0.0, -0.095, 0.0};
       memcpy(&feet[(size_t)g * 6], f, sizeof f);
     }
+    // --plan, --plan-host: the steps come from command lists instead.  On the host they are the twin's input, and with --plan what
+    // the buffers are sized by (counts and times only) -- none of them is uploaded then
+    if (planned && (wg_fleet::command_plan(B, S, online, &cp) >= 0 ||
+                    wg_fleet::command_steps(cp, B, S, zm.t_single, zm.t_double, on_device, &steps, &n_steps) >= 0)) {
+      fprintf(stderr, "FAILED: the command lists do not give %d steps\n", S);
+      return 1;
+    }
   }
   if (K < 1) { fprintf(stderr, "FAILED: need ticks >= 1\n"); return 1; }
   CHECK_WG(wg_init(0));
@@ -109,8 +129,19 @@ int main(int argc, char **argv) {
   wg_rel_step_t *d_steps; int *d_ns, *d_len, *d_lty, *d_count, *d_ran; double *d_feet, *d_time, *d_left, *d_right, *d_ts, *d_te;
   wg_zmp_polytope_t *d_queues; wg_dimitrov_state_t *d_states;
   const size_t row = (size_t)lcap * B, nq = (size_t)B * qcap;
-  CHECK_HIP(dev_upload(&d_steps, steps));
-  CHECK_HIP(dev_upload(&d_ns, n_steps));
+  wg_step_cmd_t *d_cmds = nullptr, *d_later = nullptr; wg_step_stack_t *d_stack = nullptr; int *d_ncmds = nullptr, *d_nlater = nullptr;
+  const std::vector<wg_step_stack_t> fresh(B, wg_step_stack_t{1, 0, 0, 0});
+  if (on_device) {                                            // the steps' array is only written by the device
+    CHECK_HIP(dev_alloc(&d_steps, steps.size()));
+    CHECK_HIP(hipMemset(d_steps, 0, sizeof(wg_rel_step_t) * steps.size()));
+    CHECK_HIP(dev_alloc(&d_ns, B));
+    CHECK_HIP(dev_upload(&d_cmds, cp.whole));
+    CHECK_HIP(dev_upload(&d_ncmds, online ? std::vector<int>(B, 2) : cp.n_whole));
+    CHECK_HIP(dev_alloc(&d_stack, B));
+  } else {
+    CHECK_HIP(dev_upload(&d_steps, steps));
+    CHECK_HIP(dev_upload(&d_ns, n_steps));
+  }
   CHECK_HIP(dev_upload(&d_feet, feet));
   CHECK_HIP(dev_upload(&d_time, time));
   CHECK_HIP(dev_alloc(&d_len, B));
@@ -133,11 +164,19 @@ int main(int argc, char **argv) {
   std::vector<int> ran_pieces;
   std::vector<hipEvent_t> ev;
   if (online) {
-    const int bad = wg_fleet::online_plan(zm, steps, n_steps, B, S, online, &plan);
+    const int bad = wg_fleet::online_plan(zm, steps, n_steps, B, S, online, &plan, on_device ? &cp.first_steps : nullptr);
     if (bad >= 0) { fprintf(stderr, "FAILED: gait %d: --online needs two steps to begin with\n", bad); return 1; }
     CHECK_HIP(dev_alloc(&d_walk, B));
-    CHECK_HIP(dev_upload(&d_chunks, plan.chunks));
-    CHECK_HIP(dev_upload(&d_cns, plan.cns));
+    if (on_device) {                                          // one call's steps and counts, written in front of every append
+      CHECK_HIP(dev_alloc(&d_chunks, (size_t)B * online));
+      CHECK_HIP(dev_alloc(&d_cns, B));
+      CHECK_HIP(dev_upload(&d_later, cp.later));
+      CHECK_HIP(dev_upload(&d_nlater, cp.n_later));
+      if (plan.n_calls != cp.n_calls) { fprintf(stderr, "FAILED: %d calls planned, %d lists\n", plan.n_calls, cp.n_calls); return 1; }
+    } else {
+      CHECK_HIP(dev_upload(&d_chunks, plan.chunks));
+      CHECK_HIP(dev_upload(&d_cns, plan.cns));
+    }
     CHECK_HIP(dev_upload(&d_sel, plan.sel));
     CHECK_HIP(dev_upload(&d_two, std::vector<int>(B, 2)));
     CHECK_HIP(dev_alloc(&d_done, B));
@@ -156,8 +195,13 @@ int main(int argc, char **argv) {
       double longest = 0.0;
       for (int g = 0; g < B; ++g) {
         double d = 0.0;
-        if (c == 0) d = 2 * zm.preview_time + dur(steps[(size_t)g * S + 1]);
-        else for (int i = 0; i < plan.cns[(size_t)(c - 1) * B + g]; ++i) d += dur(plan.chunks[((size_t)(c - 1) * B + g) * online + i]);
+        const int first = on_device ? cp.first_steps[g] : 2;   // the steps the begin call takes
+        if (c == 0) {
+          for (int i = 1; i < first; ++i) d += dur(steps[(size_t)g * S + i]);
+          d = 2 * zm.preview_time + d;
+        } else if (on_device) {
+          for (int i = 0; i < plan.cns[(size_t)(c - 1) * B + g]; ++i) d += dur(steps[(size_t)g * S + first + (c - 1) * online + i]);
+        } else for (int i = 0; i < plan.cns[(size_t)(c - 1) * B + g]; ++i) d += dur(plan.chunks[((size_t)(c - 1) * B + g) * online + i]);
         longest = d > longest ? d : longest;
       }
       const double r = longest / dm.T + 1.0;
@@ -171,6 +215,7 @@ int main(int argc, char **argv) {
   double sec = 0.0, sec_walk = 0.0;
   for (int rep = 0; rep < 2; ++rep) {                          // the second pass is the timed one
     CHECK_HIP(hipMemcpyAsync(d_states, states.data(), sizeof(wg_dimitrov_state_t) * B, hipMemcpyHostToDevice, st));
+    if (on_device) CHECK_HIP(hipMemcpyAsync(d_stack, fresh.data(), sizeof(wg_step_stack_t) * B, hipMemcpyHostToDevice, st));
     CHECK_HIP(hipStreamSynchronize(st));
     if (online) {
       // what the host knows of the fleet: every gait's samples (cur), which have ended, the samples the queues hold (done)
@@ -240,14 +285,19 @@ int main(int argc, char **argv) {
       }
       CHECK_HIP(hipStreamSynchronize(st));
       const auto t0 = std::chrono::steady_clock::now();
-      CHECK_WG(wg_zmpdisc_begin_dev(&zm, B, S, d_steps, d_two, d_feet, lcap, nullptr, nullptr, nullptr, nullptr, d_left, d_lty, d_right,
+      // --plan: the support foot and the arc become the steps the begin call takes
+      if (on_device) CHECK_WG(wg_steps_plan_dev(B, cp.ccap, d_cmds, d_ncmds, zm.t_single, zm.t_double, d_stack, S, d_steps, d_ns, st));
+      CHECK_WG(wg_zmpdisc_begin_dev(&zm, B, S, d_steps, on_device ? d_ns : d_two, d_feet, lcap, nullptr, nullptr, nullptr, nullptr, d_left, d_lty, d_right,
                                     nullptr, d_walk, d_len, st));
       for (int g = 0; g < B; ++g) cur[g] = len_after[g];
       if (follow) max_ticks = rounds[0];
       CHECK_WG(grow_and_walk());
       CHECK_WG(end_those_out_of_steps(0));
       for (int c = 0; c < n_calls; ++c) {
-        CHECK_WG(wg_zmpdisc_append_dev(&zm, B, online, d_chunks + (size_t)c * B * online, d_cns + (size_t)c * B, lcap, nullptr, nullptr,
+        const size_t at = on_device ? 0 : (size_t)c * B;       // --plan: call c's steps are planned into the one chunk
+        if (on_device) CHECK_WG(wg_steps_plan_dev(B, online, d_later + (size_t)c * B * online, d_nlater + (size_t)c * B, zm.t_single,
+                                                  zm.t_double, d_stack, online, d_chunks, d_cns, st));
+        CHECK_WG(wg_zmpdisc_append_dev(&zm, B, online, d_chunks + at * online, d_cns + at, lcap, nullptr, nullptr,
                                        nullptr, nullptr, d_left, d_lty, d_right, nullptr, d_walk, d_len, st));
         for (int g = 0; g < B; ++g)
           if (!ended[g]) cur[g] = len_after[(size_t)(c + 1) * B + g];
@@ -272,6 +322,7 @@ int main(int argc, char **argv) {
       continue;
     }
     const auto t0 = std::chrono::steady_clock::now();
+    if (on_device) CHECK_WG(wg_steps_plan_dev(B, cp.ccap, d_cmds, d_ncmds, zm.t_single, zm.t_double, d_stack, S, d_steps, d_ns, st));
     CHECK_WG(wg_zmpdisc_full_batch_dev(&zm, B, S, d_steps, d_ns, d_feet, lcap, nullptr, nullptr, nullptr, nullptr, d_left, d_lty, d_right,
                                        nullptr, d_len, st));
     CHECK_WG(wg_foot_constraints_batch_dev(B, lcap, d_len, d_time, d_left, d_lty, d_right, 0.24, 0.138, 0.02, 0.02, qcap, d_queues, d_ts,

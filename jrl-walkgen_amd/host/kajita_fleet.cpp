@@ -15,7 +15,15 @@
 // host does no arithmetic on sample counts and reads nothing back.  Both modes print one checksum over each gait's OWN rows
 // [0, len_g - nl + 1) of the CoM trajectories (the rows past them exist only in the whole-sequence mode): the same one.
 //
-//   kajita_fleet [--batch B] [--steps S] [--online K] [--ragged]
+// With --plan the steps are decided on the device: the only step input uploaded is a command list per gait (support foot, an arc
+// of the gait's own radius and angle, on-line steps, last support: wg_fleet::command_plan), and wg_steps_plan_dev writes the steps
+// into the array wg_zmpdisc_* reads, on the same stream -- the whole list in front of wg_zmpdisc_batch_dev, or with --online K the
+// first two commands in front of wg_zmpdisc_begin_dev and K in front of every wg_zmpdisc_append_dev, the preview following each
+// gait's own queue as with --ragged (the arcs differ, so the gaits' sample counts do between the calls).  Buffers are sized with
+// wg_steps_count and wg_zmpdisc_length_after.  --plan-host is its host-fed twin: the same lists through wg_steps_plan and the
+// upload path above, with or without --online K.  Both print the same checksum.
+//
+//   kajita_fleet [--batch B] [--steps S] [--online K] [--ragged] [--plan | --plan-host]
 #include <chrono>
 #include <cstdlib>
 #include <random>
@@ -28,13 +36,18 @@ using wg_fleet::dev_upload;
 int main(int argc, char **argv) {
   int B = 4096, S = 16, K = 0;
   bool ragged = false;
+  int planned = 0;                                            // 1: --plan (steps planned on the device), 2: --plan-host
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--batch") && i + 1 < argc) B = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--steps") && i + 1 < argc) S = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--ragged")) ragged = true;
+    else if (!strcmp(argv[i], "--plan")) planned = 1;
+    else if (!strcmp(argv[i], "--plan-host")) planned = 2;
     else if (!strcmp(argv[i], "--online") && i + 1 < argc) { K = atoi(argv[++i]); if (K < 1 || K > WG_ZMPDISC_MAX_STEPS) { fprintf(stderr, "FAILED: need 1 <= --online K <= %d\n", WG_ZMPDISC_MAX_STEPS); return 1; } }
   }
   if (B < 1 || S < 2 || S > WG_ZMPDISC_MAX_STEPS) { fprintf(stderr, "FAILED: need B >= 1, 2 <= steps <= %d\n", WG_ZMPDISC_MAX_STEPS); return 1; }
+  if (planned && (ragged || S < 4)) { fprintf(stderr, "FAILED: --plan needs steps >= 4 and no --ragged\n"); return 1; }
+  const bool on_device = planned == 1;
   CHECK_WG(wg_init(0));
   wg_zmpdisc_model_t zm;
   wg_zmpdisc_defaults(&zm);                                   // 5 ms, 1.6 s preview, 0.78 / 0.02 s supports, 0.07 m step height
@@ -70,6 +83,15 @@ int main(int argc, char **argv) {
     const double f[6] = {0.0094903, 0.095, 0.0, 0.0094903, -0.095, 0.0};
     memcpy(&feet[(size_t)g * 6], f, sizeof f);
   }
+  // --plan, --plan-host: the steps come from command lists.  On the host they are the twin's input, and with --plan what the
+  // buffers are sized by and gait 0 is checked against -- none of them is uploaded then
+  wg_fleet::CommandPlan cp;
+  if (planned) {
+    if (wg_fleet::command_plan(B, S, K, &cp) >= 0 || wg_fleet::command_steps(cp, B, S, zm.t_single, zm.t_double, on_device, &steps, &n_steps) >= 0) {
+      fprintf(stderr, "FAILED: the command lists do not give %d steps\n", S);
+      return 1;
+    }
+  }
   // samples of every gait, L those of the longest (without --ragged: of all)
   std::vector<int> len_g(B);
   int L = 0, Lmin = 1 << 30;
@@ -82,8 +104,19 @@ int main(int argc, char **argv) {
   const int Lrun = L - nl + 1;
 
   wg_rel_step_t *d_steps; int *d_ns, *d_len, *d_done = nullptr, *d_sel = nullptr; double *d_feet, *d_zx, *d_zy, *d_state, *d_com;
-  CHECK_HIP(dev_upload(&d_steps, steps));
-  CHECK_HIP(dev_upload(&d_ns, n_steps));
+  wg_step_cmd_t *d_cmds = nullptr, *d_later = nullptr; wg_step_stack_t *d_stack = nullptr; int *d_ncmds = nullptr, *d_nlater = nullptr;
+  const std::vector<wg_step_stack_t> fresh(B, wg_step_stack_t{1, 0, 0, 0});
+  if (on_device) {                                            // the steps' array is only written by the device
+    CHECK_HIP(dev_alloc(&d_steps, steps.size()));
+    CHECK_HIP(hipMemset(d_steps, 0, sizeof(wg_rel_step_t) * steps.size()));
+    CHECK_HIP(dev_alloc(&d_ns, B));
+    CHECK_HIP(dev_upload(&d_cmds, cp.whole));
+    CHECK_HIP(dev_upload(&d_ncmds, K ? std::vector<int>(B, 2) : cp.n_whole));
+    CHECK_HIP(dev_alloc(&d_stack, B));
+  } else {
+    CHECK_HIP(dev_upload(&d_steps, steps));
+    CHECK_HIP(dev_upload(&d_ns, n_steps));
+  }
   CHECK_HIP(dev_upload(&d_feet, feet));
   CHECK_HIP(dev_alloc(&d_len, B));
   CHECK_HIP(dev_alloc(&d_zx, (size_t)L * B));
@@ -94,16 +127,26 @@ int main(int argc, char **argv) {
   wg_fleet::OnlinePlan plan;
   wg_zmpdisc_state_t *d_walk = nullptr; wg_rel_step_t *d_chunks = nullptr; int *d_cns = nullptr;
   if (K) {
-    if (wg_fleet::online_plan(zm, steps, n_steps, B, S, K, &plan) >= 0) return 1;    // S >= 2: cannot be
+    if (wg_fleet::online_plan(zm, steps, n_steps, B, S, K, &plan, on_device ? &cp.first_steps : nullptr) >= 0) return 1;    // S >= 2: cannot be
     CHECK_HIP(dev_alloc(&d_walk, B));
-    CHECK_HIP(dev_upload(&d_chunks, plan.chunks));
-    CHECK_HIP(dev_upload(&d_cns, plan.cns));
-    if (ragged) {
+    if (on_device) {                                          // one call's steps and counts, written in front of every append
+      CHECK_HIP(dev_alloc(&d_chunks, (size_t)B * K));
+      CHECK_HIP(dev_alloc(&d_cns, B));
+      CHECK_HIP(dev_upload(&d_later, cp.later));
+      CHECK_HIP(dev_upload(&d_nlater, cp.n_later));
+      if (plan.n_calls != cp.n_calls) { fprintf(stderr, "FAILED: %d calls planned, %d lists\n", plan.n_calls, cp.n_calls); return 1; }
+    } else {
+      CHECK_HIP(dev_upload(&d_chunks, plan.chunks));
+      CHECK_HIP(dev_upload(&d_cns, plan.cns));
+    }
+    if (ragged || on_device) {
       CHECK_HIP(dev_upload(&d_sel, plan.sel));
       CHECK_HIP(dev_alloc(&d_done, B));
     }
-    const std::vector<int> two(B, 2);                         // the begin call takes two steps of every gait
-    CHECK_HIP(hipMemcpy(d_ns, two.data(), sizeof(int) * B, hipMemcpyHostToDevice));
+    if (!on_device) {
+      const std::vector<int> two(B, 2);                       // the begin call takes two steps of every gait
+      CHECK_HIP(hipMemcpy(d_ns, two.data(), sizeof(int) * B, hipMemcpyHostToDevice));
+    }
   }
   const int n_calls = plan.n_calls;
   hipStream_t st;
@@ -111,12 +154,15 @@ int main(int argc, char **argv) {
   double sec = 0.0;
   for (int rep = 0; rep < 2; ++rep) {                          // the second pass is the timed one
     CHECK_HIP(hipMemsetAsync(d_state, 0, sizeof(double) * 8 * B, st));
+    if (on_device) CHECK_HIP(hipMemcpyAsync(d_stack, fresh.data(), sizeof(wg_step_stack_t) * B, hipMemcpyHostToDevice, st));
     CHECK_HIP(hipStreamSynchronize(st));
     const auto t0 = std::chrono::steady_clock::now();
+    // --plan: the steps of the call that follows, from the commands: the whole list, or the support foot and the arc
+    if (on_device) CHECK_WG(wg_steps_plan_dev(B, cp.ccap, d_cmds, d_ncmds, zm.t_single, zm.t_double, d_stack, S, d_steps, d_ns, st));
     if (!K) {
       CHECK_WG(wg_zmpdisc_batch_dev(&zm, B, S, d_steps, d_ns, d_feet, L, d_zx, d_zy, d_len, st));
       CHECK_WG(wg_preview_run_batch_dev(B, Lrun, d_zx, d_zy, d_state, d_com, nullptr, 1, st));
-    } else if (ragged) {
+    } else if (ragged || on_device) {
       // the plan says which STEPS each call gives and which gaits it ends; how many samples that makes is the device's business
       CHECK_HIP(hipMemsetAsync(d_done, 0, sizeof(int) * B, st));
       auto follow = [&]() { return wg_preview_follow_dev(B, L, d_len, d_done, d_zx, d_zy, d_state, d_com, nullptr, 1, st); };
@@ -134,7 +180,10 @@ int main(int argc, char **argv) {
       CHECK_WG(follow());
       CHECK_WG(end_selected(0));
       for (int c = 0; c < n_calls; ++c) {
-        CHECK_WG(wg_zmpdisc_append_dev(&zm, B, K, d_chunks + (size_t)c * B * K, d_cns + (size_t)c * B, L, d_zx, d_zy, nullptr,
+        const size_t at = on_device ? 0 : (size_t)c * B;       // --plan: call c's steps are planned into the one chunk
+        if (on_device) CHECK_WG(wg_steps_plan_dev(B, K, d_later + (size_t)c * B * K, d_nlater + (size_t)c * B, zm.t_single, zm.t_double,
+                                                  d_stack, K, d_chunks, d_cns, st));
+        CHECK_WG(wg_zmpdisc_append_dev(&zm, B, K, d_chunks + at * K, d_cns + at, L, d_zx, d_zy, nullptr,
                                        nullptr, nullptr, nullptr, nullptr, nullptr, d_walk, d_len, st));
         CHECK_WG(follow());
         CHECK_WG(end_selected(c + 1));
@@ -173,7 +222,7 @@ int main(int argc, char **argv) {
     for (int g = 0; g < B; ++g)
       if (len_h[g] != len_g[g]) { fprintf(stderr, "FAILED: gait %d ended with length %d, not %d\n", g, len_h[g], len_g[g]); return 1; }
     CHECK_HIP(hipMemcpy(d_ns, n_steps.data(), sizeof(int) * B, hipMemcpyHostToDevice));
-    if (ragged) {                                              // ... and the preview at its last safe row
+    if (ragged || on_device) {                                 // ... and the preview at its last safe row
       CHECK_HIP(hipMemcpy(len_h.data(), d_done, sizeof(int) * B, hipMemcpyDeviceToHost));
       for (int g = 0; g < B; ++g)
         if (len_h[g] != len_g[g] - nl + 1) { fprintf(stderr, "FAILED: gait %d previewed %d rows of %d\n", g, len_h[g], len_g[g] - nl + 1); return 1; }

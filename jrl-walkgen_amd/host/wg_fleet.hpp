@@ -1,5 +1,5 @@
 // wg_fleet.hpp -- what the fleet programs (kajita_fleet, dimitrov_fleet, fleet_bench, latency_b1) share: the error-exit macros,
-// checked device allocations, the checksum, and the feeding plan of the --online modes.  Header-only host code: no kernels, and
+// checked device allocations, the checksum, the feeding plan of the --online modes and the command lists of the --plan modes.  Header-only host code: no kernels, and
 // nothing here touches the GPU before the program calls it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -50,9 +50,37 @@ struct OnlinePlan {
 };
 
 // steps [B][S], n_steps [B].  Returns -1, or the first gait with fewer than the two steps the begin call needs.
+// `first`: [B] or null -- the steps the begin call takes of each gait where that is not two of every one (--plan: the support
+// foot and the arc); only the times of `steps` are read then.
 inline int online_plan(const wg_zmpdisc_model_t &zm, const std::vector<wg_rel_step_t> &steps, const std::vector<int> &n_steps, int B,
-                       int S, int K, OnlinePlan *plan) {
+                       int S, int K, OnlinePlan *plan, const std::vector<int> *first = nullptr) {
   OnlinePlan &p = *plan;
+  if (first) {
+    int n_calls = 0;
+    for (int g = 0; g < B; ++g) {
+      const int f = (*first)[g], c = (n_steps[g] - f + K - 1) / K;
+      if (f < 2 || f > n_steps[g]) return g;
+      n_calls = c > n_calls ? c : n_calls;
+    }
+    p.n_calls = n_calls;
+    p.chunks.clear();                                      // the steps are planned on the device: none to regroup
+    p.cns.assign((size_t)n_calls * B, 0);
+    p.len_after.assign((size_t)(n_calls + 1) * B, 0);
+    p.len_ended.assign(B, 0);
+    p.sel.assign((size_t)(n_calls + 1) * B, 0);
+    for (int g = 0; g < B; ++g) {
+      const wg_rel_step_t *sg = &steps[(size_t)g * S];
+      const int f = (*first)[g];
+      p.len_ended[g] = wg_zmpdisc_length_after(&zm, sg, n_steps[g], 1);
+      for (int c = 0; c <= n_calls; ++c) {
+        const int given = f + c * K < n_steps[g] ? f + c * K : n_steps[g];
+        p.len_after[(size_t)c * B + g] = wg_zmpdisc_length_after(&zm, sg, given, 0);
+        p.sel[(size_t)c * B + g] = given == n_steps[g] && (c == 0 || f + (c - 1) * K < n_steps[g]);
+        if (c < n_calls) p.cns[(size_t)c * B + g] = (f + (c + 1) * K < n_steps[g] ? f + (c + 1) * K : n_steps[g]) - given;
+      }
+    }
+    return -1;
+  }
   int S_max = 0;
   for (int g = 0; g < B; ++g) S_max = n_steps[g] > S_max ? n_steps[g] : S_max;
   const int n_calls = p.n_calls = S_max > 2 ? (S_max - 2 + K - 1) / K : 0;
@@ -76,6 +104,76 @@ inline int online_plan(const wg_zmpdisc_model_t &zm, const std::vector<wg_rel_st
       p.cns[(size_t)c * B + g] = n;
       for (int i = 0; i < n; ++i) p.chunks[((size_t)c * B + g) * K + i] = sg[first + i];
     }
+  }
+  return -1;
+}
+
+// The command lists of the --plan modes: what a fleet that decides its steps while it walks would hold in device memory.  Gait g
+// starts on the foot of its parity, turns on an arc whose radius and angle are its own (1 .. 5 steps), walks on with on-line steps
+// and finishes on the last correct support foot: S steps for every gait, from S + 1 - (arc steps) commands.  Whole-sequence mode
+// gives the whole list in one call; on line the first two commands go in front of wg_zmpdisc_begin_dev and the rest, one step
+// each, K per append.
+struct CommandPlan {
+  int ccap = 0, n_calls = 0;
+  std::vector<wg_step_cmd_t> whole;      // [B][ccap]
+  std::vector<int> n_whole;              // [B]
+  std::vector<int> first_steps;          // [B]: steps the support foot and the arc give
+  std::vector<wg_step_cmd_t> later;      // [n_calls][B][K]: the commands behind those two, regrouped call by call
+  std::vector<int> n_later;              // [n_calls][B]
+};
+
+// Returns -1, or the first gait whose list does not give S steps (cannot be for 4 <= S <= WG_ZMPDISC_MAX_STEPS).  K == 0: no cuts.
+inline int command_plan(int B, int S, int K, CommandPlan *plan) {
+  CommandPlan &p = *plan;
+  p.ccap = S;
+  p.whole.assign((size_t)B * S, wg_step_cmd_t{WG_STEP_NONE, 0, {0.0, 0.0, 0.0}});
+  p.n_whole.assign(B, 0);
+  p.first_steps.assign(B, 0);
+  int most = 0;
+  for (int g = 0; g < B; ++g) {
+    wg_step_cmd_t *c = &p.whole[(size_t)g * S];
+    const int foot = (g & 1) ? 1 : -1, most_arc = S - 3 < 5 ? S - 3 : 5, n_arc = 1 + g % most_arc;
+    const double R = 0.4 + 0.05 * (g % 17), deg = (n_arc - 0.5) * 0.15 / R * 180.0 / 3.14159265358979323846;
+    int n = 0;
+    c[n++] = wg_step_cmd_t{WG_STEP_SUPPORT_FOOT, foot, {0.0, 0.0, 0.0}};
+    c[n++] = wg_step_cmd_t{WG_STEP_ARC, -foot, {0.0, (g & 2) ? -R : R, deg}};   // n_arc - 1 whole steps and the shorter last one
+    p.first_steps[g] = wg_steps_count(c, 2);
+    if (p.first_steps[g] != 1 + n_arc) return g;
+    for (int i = 0; i < S - 2 - n_arc; ++i) c[n++] = wg_step_cmd_t{WG_STEP_ONLINE, 0, {0.1 + 0.01 * (g % 10), 0.0, (g % 7) - 3.0}};
+    c[n++] = wg_step_cmd_t{WG_STEP_LAST_SUPPORT, 0, {0.0, 0.0, 0.0}};
+    p.n_whole[g] = n;
+    if (wg_steps_count(c, n) != S) return g;
+    most = n - 2 > most ? n - 2 : most;
+  }
+  p.n_calls = K ? (most + K - 1) / K : 0;
+  p.later.assign((size_t)p.n_calls * B * (K ? K : 1), wg_step_cmd_t{WG_STEP_NONE, 0, {0.0, 0.0, 0.0}});
+  p.n_later.assign((size_t)p.n_calls * B, 0);
+  for (int g = 0; K && g < B; ++g)
+    for (int i = 2; i < p.n_whole[g]; ++i) {
+      const int call = (i - 2) / K;
+      p.later[((size_t)call * B + g) * K + p.n_later[(size_t)call * B + g]++] = p.whole[(size_t)g * S + i];
+    }
+  return -1;
+}
+
+// Such a fleet seen from the host.  --plan-host feeds these steps through the upload path: every byte wg_steps_plan_dev would
+// write.  --plan (times_only) uploads none of them and only sizes its buffers: wg_steps_count steps per gait that carry the
+// call's times and nothing else -- a walk's length depends only on the count and the times (wg_zmpdisc_length_after) -- but for
+// gait 0, whose steps the programs check their device chain against.  Returns -1, or the first gait that does not give S steps.
+inline int command_steps(const CommandPlan &p, int B, int S, double ss, double ds, bool times_only, std::vector<wg_rel_step_t> *steps,
+                         std::vector<int> *n_steps) {
+  for (int g = 0; g < B; ++g) {
+    wg_rel_step_t *sg = &(*steps)[(size_t)g * S];
+    if (times_only && g > 0) {
+      const int n = (*n_steps)[g] = wg_steps_count(&p.whole[(size_t)g * S], p.n_whole[g]);
+      if (n != S) return g;
+      for (int i = 0; i < n; ++i) sg[i] = wg_rel_step_t{0.0, 0.0, 0.0, ss, ds, 0, 0};
+      continue;
+    }
+    wg_step_stack_t stack = {1, 0, 0, 0};
+    if (wg_steps_plan(&p.whole[(size_t)g * S], p.n_whole[g], ss, ds, &stack, S, sg, &(*n_steps)[g]) != WG_OK || stack.error ||
+        (*n_steps)[g] != S)
+      return g;
   }
   return -1;
 }

@@ -147,6 +147,11 @@ def lib():
         if hasattr(_lib, "wg_dimitrov_follow_dev"):          # absent from older experiment builds (WG_LIB_PATH, A/B runs)
             _lib.wg_dimitrov_follow_dev.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int] + \
                 [C.c_void_p] * 2 + [C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p]
+        if hasattr(_lib, "wg_steps_plan_dev"):               # absent from older experiment builds (WG_LIB_PATH, A/B runs)
+            _lib.wg_steps_count.argtypes = [C.c_void_p, C.c_int]
+            _lib.wg_steps_plan.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+            _lib.wg_steps_plan_dev.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_int,
+                                               C.c_void_p, C.c_void_p, C.c_void_p]
         # contexts: NAME_ctx(ctx, args...) for every entry point NAME(args...) that keeps or stages device-side state
         _lib.wg_ctx_create.argtypes = [C.c_int, C.c_void_p]
         _lib.wg_ctx_destroy.argtypes = [C.c_void_p]
@@ -177,7 +182,8 @@ CTX_ENTRY_POINTS = ("wg_set_overlap_strict", "wg_overlap_serialised", "wg_qp_sol
                     "wg_zmpdisc_batch", "wg_zmpdisc_batch_dev", "wg_zmpdisc_full_batch_dev", "wg_foot_constraints_batch_dev",
                     "wg_zmpdisc_begin_dev", "wg_zmpdisc_append_dev", "wg_zmpdisc_end_dev",
                     "wg_dimitrov_select_polys_dev", "wg_dimitrov_walk_dev", "wg_foot_constraints_append_dev",
-                    "wg_dimitrov_walk_time", "wg_dimitrov_walk_safe_ticks", "wg_preview_follow_dev", "wg_dimitrov_follow_dev")
+                    "wg_dimitrov_walk_time", "wg_dimitrov_walk_safe_ticks", "wg_preview_follow_dev", "wg_dimitrov_follow_dev",
+                    "wg_steps_plan_dev")
 
 
 class Context:
@@ -697,6 +703,55 @@ def zmpdisc_end_dev(model, B, lcap, outs, state_ptr, length_ptr=None, select_ptr
     """EndPhaseOfTheWalking for every gait, or for those with select[b] != 0"""
     _check(lib().wg_zmpdisc_end_dev(C.byref(model), int(B), select_ptr, int(lcap), *_zd_outs(outs), state_ptr, length_ptr,
                                     stream))
+
+
+# ---- the step stack: command lists -> the steps the zmpdisc calls read (include/wg_mpc.h, "Where the steps come from") ----
+STEP_NONE, STEP_SUPPORT_FOOT, STEP_ARC, STEP_LAST_SUPPORT, STEP_ADD, STEP_ONLINE, STEP_ONLINE_IDLE = range(7)
+STEPS_BAD_INPUT, STEPS_CAPACITY = -1, -2
+
+
+class StepCmd(C.Structure):             # wg_step_cmd_t
+    _fields_ = [("op", C.c_int), ("foot", C.c_int), ("a", C.c_double * 3)]
+
+
+class StepStack(C.Structure):           # wg_step_stack_t
+    _fields_ = [(k, C.c_int) for k in ("keep", "error", "n_given", "pad_")]
+
+
+def step_cmds(cmds):
+    """(StepCmd * n) from [(op, foot, a0, a1, a2)]"""
+    arr = (StepCmd * max(len(cmds), 1))()
+    for i, (op, foot, a0, a1, a2) in enumerate(cmds):
+        arr[i] = StepCmd(int(op), int(foot), (a0, a1, a2))
+    return arr
+
+
+def steps_count(cmds, n_cmds=None):
+    """steps a command list gives (host arithmetic), or STEPS_BAD_INPUT / STEPS_CAPACITY"""
+    return int(lib().wg_steps_count(C.addressof(cmds), len(cmds) if n_cmds is None else int(n_cmds)))
+
+
+def steps_plan(cmds, n_cmds, ss, ds, stack, smax, steps=None):
+    """wg_steps_plan for one gait: (steps (RelStep * smax), n_steps); the verdict is in stack.error.  `steps`: an array to write
+    into (bytes past the count stay as they are)."""
+    steps = (RelStep * int(smax))() if steps is None else steps
+    n = C.c_int(-7)
+    _check(lib().wg_steps_plan(C.addressof(cmds), int(n_cmds), float(ss), float(ds), C.addressof(stack), int(smax),
+                               C.addressof(steps), C.addressof(n)))
+    return steps, n.value
+
+
+def steps_plan_dev(B, ccap, cmds_ptr, n_cmds_ptr, ss, ds, stack_ptr, smax, steps_ptr, n_steps_ptr, stream=None):
+    """the same for B gaits on the device: cmds [B][ccap], n_cmds [B], stack [B] in/out, steps [B][smax], n_steps [B]"""
+    _check(lib().wg_steps_plan_dev(int(B), int(ccap), cmds_ptr, n_cmds_ptr, float(ss), float(ds), stack_ptr, int(smax), steps_ptr,
+                                   n_steps_ptr, stream))
+
+
+def steps_plan_dev_ctx(ctx, B, ccap, cmds_ptr, n_cmds_ptr, ss, ds, stack_ptr, smax, steps_ptr, n_steps_ptr, stream=None):
+    """the same on a Context (or a raw wg_ctx_t handle)"""
+    h = ctx.handle if isinstance(ctx, Context) else ctx
+    _check(lib().wg_steps_plan_dev_ctx(h, int(B), int(ccap), cmds_ptr, n_cmds_ptr, float(ss), float(ds), stack_ptr, int(smax),
+                                       steps_ptr, n_steps_ptr, stream))
 
 
 def foot_constraints(time, left, left_type, right, sole_w, sole_h, constraint_x, constraint_y, cap=256):
