@@ -365,7 +365,9 @@ size_t wg_mpc_tick_lds_bytes_for(const wg_model_t *model);
  * it builds the cart-table system for sampling period T and CoM height zc (g = 9.81) -- 3 states for
  * WITH_INITIALPOS, the 4-state error system for WITHOUT_INITIALPOS -- and returns
  *     WITHOUT_INITIALPOS: K = {Ks, Kx[0], Kx[1], Kx[2]};  WITH_INITIALPOS: K = {Kx[0] (= Ks), Kx[1], Kx[2], 0}.
- * The reference passes Q = 1, R = 1e-6 (WITHOUT) or 1e-5 (WITH), Nl = (int)(preview time / T). */
+ * The reference passes Q = 1, R = 1e-6 (WITHOUT) or 1e-5 (WITH), Nl = (int)(preview time / T).
+ * For a fleet with a CoM height per gait, wg_riccati_gains_batch_dev (below, "Fleets with a CoM height per gait") makes the
+ * gains of every gait on the device, from the same arithmetic and to the same bits. */
 #define WG_RICCATI_WITH_INITIALPOS 0
 #define WG_RICCATI_WITHOUT_INITIALPOS 1
 int wg_riccati_solve(int n, const double *A, const double *b, const double *c, double Q, double R, int Nl, int mode,
@@ -769,6 +771,55 @@ int wg_steps_plan_dev(int B, int ccap, const wg_step_cmd_t *cmds, const int *n_c
 int wg_preview_follow_dev(int B, int lcap, const int *length, int *done, const double *zmp_x_tm, const double *zmp_y_tm,
                           double *state, double *com_tm, double *zmp2_tm, int simulation, void *hip_stream);
 
+/* Fleets with a CoM height per gait: gains made on the device, preview with gains per gait ---------------------------------
+ *
+ * A context holds ONE set of gains (wg_preview_configure).  A fleet whose gaits differ in CoM height -- robots of different
+ * size, a load sweep, the reference's :comheight per robot -- has a set per gait; these calls make the B sets on the device
+ * and walk the fleet with them in one launch.  T, nl, Q and R stay fleet-wide: the window length fixes the kernel's shape.
+ *
+ * wg_riccati_gains_batch_dev runs wg_riccati_gains(T, zc[b], Q, R, Nl, mode, ...) for every gait b, one lane per gait, from the
+ * text the host call is compiled from (csrc/wg_riccati_math.hpp): K, F and the code are the host call's, bit for bit.
+ * All pointers are DEVICE pointers:
+ *   zc      [B]        CoM heights
+ *   K_tm    [4][B]     entry i of gait b at i*B + b; the four numbers wg_riccati_gains returns in K, in its layout per mode
+ *                      (WITHOUT_INITIALPOS: Ks, Kx[0], Kx[1], Kx[2] -- what wg_preview_fleet_t takes as it stands)
+ *   F_tm    [Nl][B]    time-major, what the fleet preview calls below read; may be NULL when Nl == 0
+ *   status  [B]        what the host call returns for the gait: WG_OK, or WG_ERR_BAD_ARG for a height that is not finite or a
+ *                      solve that does not converge.  Such a gait gets zeros in its K and F columns (never NaN); its
+ *                      neighbours are not touched by it.
+ * Host-side errors (WG_ERR_BAD_ARG, before any device call): B < 0, T <= 0, R <= 0, an unknown mode, Nl < 0 or
+ * Nl > WG_PREVIEW_NL_MAX, a NULL zc, K_tm, status or (Nl > 0) F_tm.  B == 0 is WG_OK.  Asynchronous on hip_stream; keeps nothing
+ * in the context.  wg_riccati_gains_batch is the same with HOST pointers, gait-major (K [B][4], F [B][Nl]), staged through the
+ * context's stream like the other host forms; it returns when the results are in place.
+ *
+ * wg_preview_run_fleet_dev and wg_preview_follow_fleet_dev are wg_preview_run_batch_dev and wg_preview_follow_dev with the
+ * gains of `fleet` instead of the context's: array shapes, length / done semantics, sitting out and refusals are those calls'
+ * word for word, with nl = fleet->nl.  Gait b runs with A, B of fleet->T, C = [1, 0, -zc[b] / 9.81], Ks = K_tm[b],
+ * Kx[i] = K_tm[(i + 1) * B + b] and F[i] = F_tm[i * B + b], and gives byte for byte what a context configured with those
+ * gains gives for it.  The arrays of `fleet` are DEVICE arrays, the struct itself is read on the host during the call.
+ * They read nothing of the context's configured gains and write nothing to them (no wg_preview_configure is needed).
+ * Windows of 64 .. 384 samples run eight lanes per gait and axis, each lane with its own gait's taps in registers; other
+ * windows run one lane per gait and axis.
+ * Host-side errors (WG_ERR_BAD_ARG, before any device call): a NULL fleet or a NULL array in it, nl < 1 or
+ * nl > WG_PREVIEW_NL_MAX, T <= 0, B < 0, L < 0, a NULL queue or state; follow: a NULL length or done, lcap < nl.
+ * Added without a change of wg_abi_version(): detect by symbol. */
+typedef struct wg_preview_fleet {
+  double T;
+  int nl, pad_;
+  const double *zc;   /* [B]      device */
+  const double *K_tm; /* [4][B]   device: Ks, Kx[0], Kx[1], Kx[2] */
+  const double *F_tm; /* [nl][B]  device */
+} wg_preview_fleet_t;
+int wg_riccati_gains_batch_dev(int B, double T, const double *zc, double Q, double R, int Nl, int mode, double *K_tm,
+                               double *F_tm, int *status, void *hip_stream);
+int wg_riccati_gains_batch(int B, double T, const double *zc, double Q, double R, int Nl, int mode, double *K, double *F,
+                           int *status);
+int wg_preview_run_fleet_dev(int B, int L, const wg_preview_fleet_t *fleet, const double *zmp_x_tm, const double *zmp_y_tm,
+                             double *state, double *com_tm, double *zmp2_tm, int simulation, void *hip_stream);
+int wg_preview_follow_fleet_dev(int B, int lcap, const int *length, int *done, const wg_preview_fleet_t *fleet,
+                                const double *zmp_x_tm, const double *zmp_y_tm, double *state, double *com_tm,
+                                double *zmp2_tm, int simulation, void *hip_stream);
+
 /* ZMP polytopes of a feet trajectory ----------------------------------------------------------------------------------
  *
  * wg_foot_constraints replaces FootConstraintsAsLinearSystem::BuildLinearConstraintInequalities
@@ -1044,6 +1095,16 @@ int wg_zmpdisc_end_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_model_t *model, int B
                            void *hip_stream);
 int wg_steps_plan_dev_ctx(wg_ctx_t *ctx, int B, int ccap, const wg_step_cmd_t *cmds, const int *n_cmds, double ss, double ds,
                           wg_step_stack_t *stack, int smax, wg_rel_step_t *steps, int *n_steps, void *hip_stream);
+int wg_riccati_gains_batch_dev_ctx(wg_ctx_t *ctx, int B, double T, const double *zc, double Q, double R, int Nl, int mode,
+                                   double *K_tm, double *F_tm, int *status, void *hip_stream);
+int wg_riccati_gains_batch_ctx(wg_ctx_t *ctx, int B, double T, const double *zc, double Q, double R, int Nl, int mode,
+                               double *K, double *F, int *status);
+int wg_preview_run_fleet_dev_ctx(wg_ctx_t *ctx, int B, int L, const wg_preview_fleet_t *fleet, const double *zmp_x_tm,
+                                 const double *zmp_y_tm, double *state, double *com_tm, double *zmp2_tm, int simulation,
+                                 void *hip_stream);
+int wg_preview_follow_fleet_dev_ctx(wg_ctx_t *ctx, int B, int lcap, const int *length, int *done,
+                                    const wg_preview_fleet_t *fleet, const double *zmp_x_tm, const double *zmp_y_tm,
+                                    double *state, double *com_tm, double *zmp2_tm, int simulation, void *hip_stream);
 
 #ifdef __cplusplus
 }

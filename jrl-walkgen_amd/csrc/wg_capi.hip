@@ -28,6 +28,7 @@
 #include "wg_pldp_kernels.hpp"
 #include "wg_dimitrov_kernels.hpp"
 #include "wg_steps_kernels.hpp"
+#include "wg_riccati_kernels.hpp"
 
 
 namespace {
@@ -1592,6 +1593,142 @@ int wg_preview_run_batch_ctx(wg_ctx_t *ctx, int B, int L, const double *zmp_x, c
 
 }  // extern "C"
 
+// ---- Kajita fleets with a CoM height per gait: gains made on the device, preview with gains per gait --------------------------
+
+namespace {
+// everything the fleet calls refuse is refused here, before a context or the device is touched
+int riccati_batch_check(int B, double T, const double *zc, double R, int Nl, int mode, const double *K, const double *F, const int *status) {
+  if (B < 0 || !(T > 0.0) || !(R > 0.0) || Nl < 0 || Nl > WG_PREVIEW_NL_MAX || (mode != WG_RICCATI_WITH_INITIALPOS && mode != WG_RICCATI_WITHOUT_INITIALPOS))
+    return fail(WG_ERR_BAD_ARG, "need B >= 0, T > 0, R > 0, 0 <= Nl <= %d and a known mode", WG_PREVIEW_NL_MAX);
+  if (!zc || !K || !status || (Nl > 0 && !F)) return fail(WG_ERR_BAD_ARG, "null argument");
+  return WG_OK;
+}
+int preview_fleet_check(int B, int L, const wg_preview_fleet_t *fleet, const double *zmp_x, const double *zmp_y, const double *state) {
+  if (!fleet || !fleet->zc || !fleet->K_tm || !fleet->F_tm) return fail(WG_ERR_BAD_ARG, "null fleet, or a null array in it");
+  if (fleet->nl < 1 || fleet->nl > WG_PREVIEW_NL_MAX) return fail(WG_ERR_BAD_ARG, "need 1 <= nl <= %d", WG_PREVIEW_NL_MAX);
+  if (!(fleet->T > 0.0)) return fail(WG_ERR_BAD_ARG, "sampling period must be positive");
+  if (B < 0 || L < 0 || !zmp_x || !zmp_y || !state) return fail(WG_ERR_BAD_ARG, "bad arguments");
+  return WG_OK;
+}
+int preview_follow_fleet_check(int B, int lcap, const int *length, const int *done, const wg_preview_fleet_t *fleet, const double *zmp_x, const double *zmp_y, const double *state) {
+  if (int rc = preview_fleet_check(B, lcap, fleet, zmp_x, zmp_y, state)) return rc;
+  if (!length || !done) return fail(WG_ERR_BAD_ARG, "null length or done");
+  if (lcap < fleet->nl) return fail(WG_ERR_BAD_ARG, "lcap=%d holds no window of nl=%d samples", lcap, fleet->nl);
+  return WG_OK;
+}
+// A and B of the fleet-wide T, as wg_preview_configure fills them (PreviewControl.cpp:203-214); what depends on the height is
+// read per gait in the kernel
+wg::PreviewConst preview_fleet_const(const wg_preview_fleet_t *fleet) {
+  wg::PreviewConst k;
+  memset(&k, 0, sizeof k);
+  const double T = fleet->T;
+  k.A01 = T; k.A02 = T * T / 2.0; k.A12 = T;
+  k.B0 = T * T * T / 6.0; k.B1 = T * T / 2.0; k.B2 = T;
+  k.nl = fleet->nl;
+  return k;
+}
+typedef void (*FleetSplitKernel)(int, int, wg::PreviewConst, wg::PreviewFleetDev, const double *, const double *, const double *, double *, double *, double *, int);
+#define WG_SPLIT(T) {T, wg::wg_preview_fleet_split_kernel<T, kSplitK, true>, wg::wg_preview_fleet_split_kernel<T, kSplitK, false>}
+const struct { int T; FleetSplitKernel full, part; } kFleetSplitKernels[] = {WG_SPLIT(16), WG_SPLIT(24), WG_SPLIT(32), WG_SPLIT(40), WG_SPLIT(48)};
+#undef WG_SPLIT
+typedef void (*FollowFleetSplitKernel)(int, int, const int *, int *, wg::PreviewConst, wg::PreviewFleetDev, const double *, const double *, const double *, double *, double *, double *, int);
+#define WG_SPLIT(T) {T, wg::wg_preview_follow_fleet_split_kernel<T, kSplitK, true>, wg::wg_preview_follow_fleet_split_kernel<T, kSplitK, false>}
+const struct { int T; FollowFleetSplitKernel full, part; } kFollowFleetSplitKernels[] = {WG_SPLIT(16), WG_SPLIT(24), WG_SPLIT(32), WG_SPLIT(40), WG_SPLIT(48)};
+#undef WG_SPLIT
+}  // namespace
+
+extern "C" {
+
+// one lane per model (wg_riccati_kernels.hpp); the host twin is wg_riccati_gains (wg_riccati.cpp), the arithmetic wg_riccati_math.hpp
+int wg_riccati_gains_batch_dev_ctx(wg_ctx_t *ctx, int B, double T, const double *zc, double Q, double R, int Nl, int mode, double *K_tm, double *F_tm, int *status, void *hip_stream) {
+  if (int rc = riccati_batch_check(B, T, zc, R, Nl, mode, K_tm, F_tm, status)) return rc;
+  if (int rc = use_ctx(ctx)) return rc;
+  if (B == 0) return WG_OK;
+  hipLaunchKernelGGL(wg::wg_riccati_gains_kernel, dim3((B + 63) / 64), dim3(64), 0, reinterpret_cast<hipStream_t>(hip_stream), B, T, zc, Q, R, Nl,
+                     mode, K_tm, F_tm, status);
+  HIP_TRY(hipGetLastError());
+  return WG_OK;
+}
+
+// host pointers, gait-major: K [B][4], F [B][Nl]
+int wg_riccati_gains_batch_ctx(wg_ctx_t *ctx, int B, double T, const double *zc, double Q, double R, int Nl, int mode, double *K, double *F, int *status) {
+  if (int rc = riccati_batch_check(B, T, zc, R, Nl, mode, K, F, status)) return rc;
+  if (int rc = use_ctx(ctx)) return rc;
+  if (B == 0) return WG_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HostScope hs(ctx);
+  const size_t sB = (size_t)B, sN = (size_t)Nl;
+  Arena a(ctx->prev_buf);
+  const auto s_zc = a.take<double>(sB), s_K = a.take<double>(4 * sB), s_F = a.take<double>(sN * sB), s_stage = a.take<double>(sB * (sN > 4 ? sN : 4));
+  const auto s_st = a.take<int>(sB);
+  if (int rc = a.reserve()) return rc;
+  auto transpose = [&](int rows, int cols, const double *in, double *out) {
+    hipLaunchKernelGGL(wg::wg_transpose_kernel, dim3((cols + 31) / 32, (rows + 31) / 32), dim3(32, 8), 0, hs.stream(), rows, cols, in, out);
+  };
+  WG_H2D(a(s_zc), zc, s_zc.bytes());
+  if (int rc = wg_riccati_gains_batch_dev_ctx(ctx, B, T, a(s_zc), Q, R, Nl, mode, a(s_K), a(s_F), a(s_st), hs.stream())) return rc;
+  transpose(4, B, a(s_K), a(s_stage));                         // [4][B] -> [B][4]; the staging buffer is reused behind the copy that reads it
+  WG_D2H(K, a(s_stage), s_K.bytes());
+  if (Nl > 0) {
+    transpose(Nl, B, a(s_F), a(s_stage));
+    WG_D2H(F, a(s_stage), s_F.bytes());
+  }
+  WG_D2H(status, a(s_st), s_st.bytes());
+  HIP_TRY(hipGetLastError());
+  WG_HOST_WAIT();
+  return WG_OK;
+}
+
+// wg_preview_run_batch_dev with the gains of `fleet` per gait: reads nothing of the context's configured gains
+int wg_preview_run_fleet_dev_ctx(wg_ctx_t *ctx, int B, int L, const wg_preview_fleet_t *fleet, const double *zmp_x_tm, const double *zmp_y_tm, double *state, double *com_tm, double *zmp2_tm, int simulation, void *hip_stream) {
+  if (int rc = preview_fleet_check(B, L, fleet, zmp_x_tm, zmp_y_tm, state)) return rc;
+  if (int rc = use_ctx(ctx)) return rc;
+  if (B == 0 || L == 0) return WG_OK;
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  const wg::PreviewConst K = preview_fleet_const(fleet);
+  const wg::PreviewFleetDev fl = {fleet->zc, fleet->K_tm};
+  FleetSplitKernel split_kern = nullptr;                       // the batch call's T / FULL selection
+  int splitT = 0;
+  for (const auto &s : kFleetSplitKernels)
+    if (!splitT && kSplitK * s.T >= K.nl) { splitT = s.T; split_kern = K.nl % s.T == 0 ? s.full : s.part; }
+  if (splitT != 0 && K.nl >= 64) {                             // windows of 64 .. 384 samples, whatever L
+    const int per_wave = 64 / kSplitK;
+    hipLaunchKernelGGL(split_kern, dim3((B + per_wave - 1) / per_wave, 2), dim3(64), (size_t)splitT * 64 * 8, st, B, L, K, fl, fleet->F_tm,
+                       zmp_x_tm, zmp_y_tm, state, com_tm, zmp2_tm, simulation);
+  } else {
+    const int threads = B >= 4096 ? 256 : 64;
+    hipLaunchKernelGGL(wg::wg_preview_fleet_kernel, dim3((B + threads - 1) / threads, 2), dim3(threads), 0, st, B, L, K, fl, fleet->F_tm,
+                       zmp_x_tm, zmp_y_tm, state, com_tm, zmp2_tm, simulation);
+  }
+  HIP_TRY(hipGetLastError());
+  return WG_OK;
+}
+
+int wg_preview_follow_fleet_dev_ctx(wg_ctx_t *ctx, int B, int lcap, const int *length, int *done, const wg_preview_fleet_t *fleet, const double *zmp_x_tm, const double *zmp_y_tm, double *state, double *com_tm, double *zmp2_tm, int simulation, void *hip_stream) {
+  if (int rc = preview_follow_fleet_check(B, lcap, length, done, fleet, zmp_x_tm, zmp_y_tm, state)) return rc;
+  if (int rc = use_ctx(ctx)) return rc;
+  if (B == 0) return WG_OK;
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  const wg::PreviewConst K = preview_fleet_const(fleet);
+  const wg::PreviewFleetDev fl = {fleet->zc, fleet->K_tm};
+  FollowFleetSplitKernel split_kern = nullptr;
+  int splitT = 0;
+  for (const auto &s : kFollowFleetSplitKernels)
+    if (!splitT && kSplitK * s.T >= K.nl) { splitT = s.T; split_kern = K.nl % s.T == 0 ? s.full : s.part; }
+  if (splitT != 0 && K.nl >= 64) {
+    const int per_wave = 64 / kSplitK / 2;                     // both axes of a gait in one wave
+    hipLaunchKernelGGL(split_kern, dim3((B + per_wave - 1) / per_wave), dim3(64), (size_t)splitT * 64 * 8, st, B, lcap, length, done, K, fl,
+                       fleet->F_tm, zmp_x_tm, zmp_y_tm, state, com_tm, zmp2_tm, simulation);
+  } else {
+    hipLaunchKernelGGL(wg::wg_preview_follow_fleet_kernel, dim3((B + 31) / 32), dim3(64), 0, st, B, lcap, length, done, K, fl, fleet->F_tm,
+                       zmp_x_tm, zmp_y_tm, state, com_tm, zmp2_tm, simulation);
+  }
+  HIP_TRY(hipGetLastError());
+  return WG_OK;
+}
+
+}  // extern "C"
+
 // ---- invariant Hessian block on the matrix cores (fleets with per-gait models) -----------------------------------------
 
 namespace {
@@ -1885,6 +2022,23 @@ int wg_preview_run_batch_dev(int B, int L, const double *zmp_x_tm, const double 
 int wg_dimitrov_follow_dev(int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count, int lcap, const double *time, const int *have, const wg_zmpdisc_state_t *walk, int flags, double *clock, int *ticks, int tick_cap, int max_ticks, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int *ran_out, int max_iter, void *hip_stream) { return on_default(&wg_dimitrov_follow_dev_ctx, B, qcap, queues, t_start, t_end, count, lcap, time, have, walk, flags, clock, ticks, tick_cap, max_ticks, states, outs, ran_out, max_iter, hip_stream); }
 int wg_preview_follow_dev(int B, int lcap, const int *length, int *done, const double *zmp_x_tm, const double *zmp_y_tm, double *state, double *com_tm, double *zmp2_tm, int simulation, void *hip_stream) { return on_default(&wg_preview_follow_dev_ctx, B, lcap, length, done, zmp_x_tm, zmp_y_tm, state, com_tm, zmp2_tm, simulation, hip_stream); }
 int wg_preview_run_batch(int B, int L, const double *zmp_x, const double *zmp_y, double *state, double *com, double *zmp2, int simulation) { return on_default(&wg_preview_run_batch_ctx, B, L, zmp_x, zmp_y, state, com, zmp2, simulation); }
+// the fleet calls refuse their arguments before the default context (and with it the device) is looked for
+int wg_riccati_gains_batch_dev(int B, double T, const double *zc, double Q, double R, int Nl, int mode, double *K_tm, double *F_tm, int *status, void *hip_stream) {
+  if (int rc = riccati_batch_check(B, T, zc, R, Nl, mode, K_tm, F_tm, status)) return rc;
+  return on_default(&wg_riccati_gains_batch_dev_ctx, B, T, zc, Q, R, Nl, mode, K_tm, F_tm, status, hip_stream);
+}
+int wg_riccati_gains_batch(int B, double T, const double *zc, double Q, double R, int Nl, int mode, double *K, double *F, int *status) {
+  if (int rc = riccati_batch_check(B, T, zc, R, Nl, mode, K, F, status)) return rc;
+  return on_default(&wg_riccati_gains_batch_ctx, B, T, zc, Q, R, Nl, mode, K, F, status);
+}
+int wg_preview_run_fleet_dev(int B, int L, const wg_preview_fleet_t *fleet, const double *zmp_x_tm, const double *zmp_y_tm, double *state, double *com_tm, double *zmp2_tm, int simulation, void *hip_stream) {
+  if (int rc = preview_fleet_check(B, L, fleet, zmp_x_tm, zmp_y_tm, state)) return rc;
+  return on_default(&wg_preview_run_fleet_dev_ctx, B, L, fleet, zmp_x_tm, zmp_y_tm, state, com_tm, zmp2_tm, simulation, hip_stream);
+}
+int wg_preview_follow_fleet_dev(int B, int lcap, const int *length, int *done, const wg_preview_fleet_t *fleet, const double *zmp_x_tm, const double *zmp_y_tm, double *state, double *com_tm, double *zmp2_tm, int simulation, void *hip_stream) {
+  if (int rc = preview_follow_fleet_check(B, lcap, length, done, fleet, zmp_x_tm, zmp_y_tm, state)) return rc;
+  return on_default(&wg_preview_follow_fleet_dev_ctx, B, lcap, length, done, fleet, zmp_x_tm, zmp_y_tm, state, com_tm, zmp2_tm, simulation, hip_stream);
+}
 int wg_gramian_batch_dev(int B, int N, const double *T, const double *h, double alpha, double beta, double gamma, int precision, double *Qb, void *hip_stream) { return on_default(&wg_gramian_batch_dev_ctx, B, N, T, h, alpha, beta, gamma, precision, Qb, hip_stream); }
 int wg_gramian_batch(int B, int N, const double *T, const double *h, double alpha, double beta, double gamma, int precision, double *Qb) { return on_default(&wg_gramian_batch_ctx, B, N, T, h, alpha, beta, gamma, precision, Qb); }
 int wg_zmpdisc_batch_dev(const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap, double *zmp_x_tm, double *zmp_y_tm, int *length, void *hip_stream) { return on_default(&wg_zmpdisc_batch_dev_ctx, model, B, smax, steps, n_steps, init_feet, lcap, zmp_x_tm, zmp_y_tm, length, hip_stream); }

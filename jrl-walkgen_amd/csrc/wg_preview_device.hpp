@@ -28,6 +28,34 @@ struct PreviewConst {
   int nl;
 };
 
+// The fleet forms (FLEET, wg_preview_run_fleet_dev / wg_preview_follow_fleet_dev): a CoM height, and so a set of gains, per gait.
+// A and B come from the fleet-wide T as before (PreviewConst, with nl); what depends on the height is read per gait:
+//   zc    [B]        C2 = -zc[g] / 9.81, the expression wg_preview_configure fills PreviewConst with
+//   K_tm  [4][B]     Ks, Kx0, Kx1, Kx2
+//   F     [nl][B]    time-major like the ZMP references: tap i of gait g at i*B + g, a wave's loads are whole rows
+// The step arithmetic below is one text for both: FLEET changes where Kx, Ks, C2 and F[i] come from and nothing else.
+struct PreviewFleetDev {
+  const double *zc, *K_tm;
+};
+// the constants of gait g: the launch's own (not FLEET: `own` is never touched), or `own` filled from them and the fleet's arrays
+template <bool FLEET>
+__device__ __forceinline__ const PreviewConst &pv_gains(const PreviewConst &K, PreviewConst &own, const PreviewFleetDev &fl, int g, int B) {
+  if constexpr (FLEET) {
+    const size_t sB = (size_t)B;
+    own = K;
+    own.C2 = -fl.zc[g] / 9.81;
+    own.Ks = fl.K_tm[g]; own.Kx0 = fl.K_tm[sB + g]; own.Kx1 = fl.K_tm[2 * sB + g]; own.Kx2 = fl.K_tm[3 * sB + g];
+    return own;
+  } else {
+    return K;
+  }
+}
+template <bool FLEET>
+__device__ __forceinline__ double pv_tap(const double *__restrict__ F, int i, int g, size_t sB) {
+  if constexpr (FLEET) return F[(size_t)i * sB + g];
+  else return F[i];
+}
+
 // The follow forms (RAGGED, wg_preview_follow_dev): every gait advances over the rows its own queue has made safe.
 //   length [B]   samples gait b holds (what the wg_zmpdisc on-line calls leave); safe = max(0, length - nl + 1)
 //   done   [B]   steps gait b has behind it; the launch runs steps [done, safe) and stores done = safe
@@ -69,14 +97,16 @@ __device__ __forceinline__ void pv_range_store(const PreviewRange &r, int g, int
 // zmp2:    [L][2][B] or NULL   zmpx2, zmpy2 of each step
 // RAGGED: one wave per block, lanes 0..31 the x axes of 32 gaits, lanes 32..63 their y axes; L is not used.  The step loop has
 // a bound per lane here (no lane talks to another), so a lane's loads are those of its own steps and nothing else.
-template <bool RAGGED>
-__device__ __forceinline__ void pv_l2_body(int B, int L, const PreviewConst &K, const double *__restrict__ F,
+template <bool RAGGED, bool FLEET = false>
+__device__ __forceinline__ void pv_l2_body(int B, int L, const PreviewConst &Kc, const double *__restrict__ F,
                                            const double *__restrict__ zx, const double *__restrict__ zy, double *__restrict__ state,
                                            double *__restrict__ com, double *__restrict__ zmp2, int simulation, int lcap,
-                                           const int *length, int *done) {
+                                           const int *length, int *done, const PreviewFleetDev fl = PreviewFleetDev()) {
   const int g = RAGGED ? blockIdx.x * 32 + (threadIdx.x & 31) : blockIdx.x * blockDim.x + threadIdx.x;
   const int axis = RAGGED ? threadIdx.x >> 5 : blockIdx.y;
   if (g >= B) return;
+  PreviewConst Kg;
+  const PreviewConst &K = pv_gains<FLEET>(Kc, Kg, fl, g, B);
   const double *__restrict__ z = axis ? zy : zx;
   const size_t sB = (size_t)B;
   const int nl = K.nl;
@@ -100,10 +130,13 @@ __device__ __forceinline__ void pv_l2_body(int B, int L, const PreviewConst &K, 
       const double z0 = zl[(size_t)(i + 0) * sB], z1 = zl[(size_t)(i + 1) * sB], z2 = zl[(size_t)(i + 2) * sB],
                    z3 = zl[(size_t)(i + 3) * sB], z4 = zl[(size_t)(i + 4) * sB], z5 = zl[(size_t)(i + 5) * sB],
                    z6 = zl[(size_t)(i + 6) * sB], z7 = zl[(size_t)(i + 7) * sB];
-      u += F[i + 0] * z0; u += F[i + 1] * z1; u += F[i + 2] * z2; u += F[i + 3] * z3;
-      u += F[i + 4] * z4; u += F[i + 5] * z5; u += F[i + 6] * z6; u += F[i + 7] * z7;
+      const double f0 = pv_tap<FLEET>(F, i + 0, g, sB), f1 = pv_tap<FLEET>(F, i + 1, g, sB), f2 = pv_tap<FLEET>(F, i + 2, g, sB),
+                   f3 = pv_tap<FLEET>(F, i + 3, g, sB), f4 = pv_tap<FLEET>(F, i + 4, g, sB), f5 = pv_tap<FLEET>(F, i + 5, g, sB),
+                   f6 = pv_tap<FLEET>(F, i + 6, g, sB), f7 = pv_tap<FLEET>(F, i + 7, g, sB);
+      u += f0 * z0; u += f1 * z1; u += f2 * z2; u += f3 * z3;
+      u += f4 * z4; u += f5 * z5; u += f6 * z6; u += f7 * z7;
     }
-    for (; i < nl; ++i) u += F[i] * zl[(size_t)i * sB];
+    for (; i < nl; ++i) u += pv_tap<FLEET>(F, i, g, sB) * zl[(size_t)i * sB];
     // x = MAL_RET_A_by_B(m_A, x) + ux * m_B  (:355): every product of the 3x3 by 3x1 prod is formed, zeros included
     double a0 = 0.0, a1 = 0.0, a2 = 0.0;
     a0 += 1.0 * x0; a0 += K.A01 * x1; a0 += K.A02 * x2;
@@ -139,6 +172,21 @@ wg_preview_follow_kernel(int B, int lcap, const int *__restrict__ length, int *_
                          const double *__restrict__ F, const double *__restrict__ zx, const double *__restrict__ zy,
                          double *__restrict__ state, double *__restrict__ com, double *__restrict__ zmp2, int simulation) {
   pv_l2_body<true>(B, 0, K, F, zx, zy, state, com, zmp2, simulation, lcap, length, done);
+}
+
+__global__ void __launch_bounds__(256)
+wg_preview_fleet_kernel(int B, int L, PreviewConst K, PreviewFleetDev fl, const double *__restrict__ F, const double *__restrict__ zx,
+                        const double *__restrict__ zy, double *__restrict__ state, double *__restrict__ com,
+                        double *__restrict__ zmp2, int simulation) {
+  pv_l2_body<false, true>(B, L, K, F, zx, zy, state, com, zmp2, simulation, 0, nullptr, nullptr, fl);
+}
+
+__global__ void __launch_bounds__(64)
+wg_preview_follow_fleet_kernel(int B, int lcap, const int *__restrict__ length, int *__restrict__ done, PreviewConst K,
+                               PreviewFleetDev fl, const double *__restrict__ F, const double *__restrict__ zx,
+                               const double *__restrict__ zy, double *__restrict__ state, double *__restrict__ com,
+                               double *__restrict__ zmp2, int simulation) {
+  pv_l2_body<true, true>(B, 0, K, F, zx, zy, state, com, zmp2, simulation, lcap, length, done, fl);
 }
 
 // The same iteration with the preview window staged in LDS.  wg_preview_kernel re-reads the whole window from L2 at every
@@ -243,11 +291,14 @@ __device__ __forceinline__ double pv_dpp(double v) {
 // its lanes in it, so that the row shifts keep their meaning: only its state update and its stores are predicated, and its
 // loads are off (every load is guarded by the gait's own row count Lz, which is 0 for a group without a step).  A wave takes
 // as long as its longest gait: an evenly fed fleet loses nothing, a lone long gait costs its wave.
-template <int T, int K, bool FULL, bool RAGGED>     // FULL: nl is a multiple of T, the last used lane has T taps like the others
-__device__ __forceinline__ void pv_split_body(int B, int L, const PreviewConst &Kc, const double *__restrict__ F,
+// FLEET: the taps a lane keeps in registers are its gait's own (F [nl][B], loaded once per launch like the shared ones); a
+// surplus or sitting-out group loads gains like any other, through the gait index g that shadows B - 1 where the group has none.
+template <int T, int K, bool FULL, bool RAGGED, bool FLEET = false>     // FULL: nl is a multiple of T, the last used lane has T taps like the others
+__device__ __forceinline__ void pv_split_body(int B, int L, const PreviewConst &Kin, const double *__restrict__ F,
                                               const double *__restrict__ zx, const double *__restrict__ zy,
                                               double *__restrict__ state, double *__restrict__ com, double *__restrict__ zmp2,
-                                              int simulation, int lcap, const int *length, int *done) {
+                                              int simulation, int lcap, const int *length, int *done,
+                                              const PreviewFleetDev fl = PreviewFleetDev()) {
   static_assert(K == 8, "the DPP controls below are written for groups of eight lanes");
   extern __shared__ __attribute__((aligned(16))) double pv_ring[];      // [T][64]
   constexpr int G = 64 / K;
@@ -259,6 +310,8 @@ __device__ __forceinline__ void pv_split_body(int B, int L, const PreviewConst &
   const int axis = RAGGED ? (lane / K) & 1 : blockIdx.y;
   const double *__restrict__ z = axis ? zy : zx;
   const size_t sB = (size_t)B;
+  PreviewConst Kg;
+  const PreviewConst &Kc = pv_gains<FLEET>(Kin, Kg, fl, g, B);
   const int nl = Kc.nl;
   const int Ku = (nl + T - 1) / T;                                      // lanes of the group that hold taps, 1..K
   const int Tl = nl - (Ku - 1) * T;                                     // taps of the last of them, 1..T
@@ -277,7 +330,7 @@ __device__ __forceinline__ void pv_split_body(int B, int L, const PreviewConst &
 #pragma unroll
   for (int t = 0; t < T; ++t) {
     const int i = k * T + t;
-    Fk[t] = i < nl ? F[i] : 0.0;
+    Fk[t] = i < nl ? pv_tap<FLEET>(F, i, g, sB) : 0.0;
     pv_ring[t * 64 + lane] = (i < nl && i < Lz) ? z[(size_t)i * sB + g] : 0.0;
   }
   const double *st = state + (size_t)g * 8;
@@ -382,6 +435,23 @@ wg_preview_follow_split_kernel(int B, int lcap, const int *__restrict__ length, 
                                const double *__restrict__ F, const double *__restrict__ zx, const double *__restrict__ zy,
                                double *__restrict__ state, double *__restrict__ com, double *__restrict__ zmp2, int simulation) {
   pv_split_body<T, K, FULL, true>(B, 0, Kc, F, zx, zy, state, com, zmp2, simulation, lcap, length, done);
+}
+
+template <int T, int K, bool FULL>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
+wg_preview_fleet_split_kernel(int B, int L, PreviewConst Kc, PreviewFleetDev fl, const double *__restrict__ F,
+                              const double *__restrict__ zx, const double *__restrict__ zy, double *__restrict__ state,
+                              double *__restrict__ com, double *__restrict__ zmp2, int simulation) {
+  pv_split_body<T, K, FULL, false, true>(B, L, Kc, F, zx, zy, state, com, zmp2, simulation, 0, nullptr, nullptr, fl);
+}
+
+template <int T, int K, bool FULL>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
+wg_preview_follow_fleet_split_kernel(int B, int lcap, const int *__restrict__ length, int *__restrict__ done, PreviewConst Kc,
+                                     PreviewFleetDev fl, const double *__restrict__ F, const double *__restrict__ zx,
+                                     const double *__restrict__ zy, double *__restrict__ state, double *__restrict__ com,
+                                     double *__restrict__ zmp2, int simulation) {
+  pv_split_body<T, K, FULL, true, true>(B, 0, Kc, F, zx, zy, state, com, zmp2, simulation, lcap, length, done, fl);
 }
 
 // [B][cols] (gait-major) <-> [cols][B] (time-major) on the device, for the host-pointer entry point

@@ -23,7 +23,13 @@
 // wg_steps_count and wg_zmpdisc_length_after.  --plan-host is its host-fed twin: the same lists through wg_steps_plan and the
 // upload path above, with or without --online K.  Both print the same checksum.
 //
-//   kajita_fleet [--batch B] [--steps S] [--online K] [--ragged] [--plan | --plan-host]
+// With --heights LO:HI gait b walks at its own CoM height, zc = LO + (HI - LO) b / (B - 1): its gains are made on the device
+// (wg_riccati_gains_batch_dev, one lane per gait, on the same stream in front of the walk) and every preview call above is its
+// fleet form (wg_preview_run_fleet_dev, wg_preview_follow_fleet_dev), which reads the gains per gait; the context's configured
+// gains play no part.  Works with every mode above.  At the end every gait's status must be 0, and gait 0 AND gait B - 1 are
+// checked against the one-gait host path configured with that gait's own wg_riccati_gains.
+//
+//   kajita_fleet [--batch B] [--steps S] [--online K] [--ragged] [--plan | --plan-host] [--heights LO:HI]
 #include <chrono>
 #include <cstdlib>
 #include <random>
@@ -35,7 +41,8 @@ using wg_fleet::dev_upload;
 
 int main(int argc, char **argv) {
   int B = 4096, S = 16, K = 0;
-  bool ragged = false;
+  bool ragged = false, heights = false;
+  double zc_lo = 0.8078, zc_hi = 0.8078;
   int planned = 0;                                            // 1: --plan (steps planned on the device), 2: --plan-host
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--batch") && i + 1 < argc) B = atoi(argv[++i]);
@@ -43,6 +50,10 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[i], "--ragged")) ragged = true;
     else if (!strcmp(argv[i], "--plan")) planned = 1;
     else if (!strcmp(argv[i], "--plan-host")) planned = 2;
+    else if (!strcmp(argv[i], "--heights") && i + 1 < argc) {
+      heights = sscanf(argv[++i], "%lf:%lf", &zc_lo, &zc_hi) == 2;
+      if (!heights || !(zc_lo > 0.0) || !(zc_hi >= zc_lo) || !(zc_hi < 1e3)) { fprintf(stderr, "FAILED: need --heights LO:HI with 0 < LO <= HI\n"); return 1; }
+    }
     else if (!strcmp(argv[i], "--online") && i + 1 < argc) { K = atoi(argv[++i]); if (K < 1 || K > WG_ZMPDISC_MAX_STEPS) { fprintf(stderr, "FAILED: need 1 <= --online K <= %d\n", WG_ZMPDISC_MAX_STEPS); return 1; } }
   }
   if (B < 1 || S < 2 || S > WG_ZMPDISC_MAX_STEPS) { fprintf(stderr, "FAILED: need B >= 1, 2 <= steps <= %d\n", WG_ZMPDISC_MAX_STEPS); return 1; }
@@ -58,6 +69,10 @@ int main(int argc, char **argv) {
   CHECK_WG(wg_riccati_gains(zm.T, 0.8078, 1.0, 1e-6, nl, WG_RICCATI_WITHOUT_INITIALPOS, Kg, F.data()));
   wg_preview_gains_t pg = {zm.T, 0.8078, Kg[0], {Kg[1], Kg[2], Kg[3]}, nl, 0};
   CHECK_WG(wg_preview_configure(&pg, F.data()));
+  // --heights: a CoM height per gait; K_tm, F_tm and the status are written by the device in front of every walk
+  std::vector<double> zc(B, 0.8078);
+  if (heights)
+    for (int g = 0; g < B; ++g) zc[g] = B > 1 ? zc_lo + (zc_hi - zc_lo) * g / (B - 1) : zc_lo;
 
   std::vector<wg_rel_step_t> steps((size_t)B * S);
   std::vector<int> n_steps(B, S);
@@ -91,6 +106,15 @@ int main(int argc, char **argv) {
       fprintf(stderr, "FAILED: the command lists do not give %d steps\n", S);
       return 1;
     }
+    if (heights && on_device && B > 1) {                      // --heights checks gait B - 1 as well: its steps from the host twin, like gait 0's
+      const size_t g = (size_t)B - 1;
+      wg_step_stack_t stack = {1, 0, 0, 0};
+      if (wg_steps_plan(&cp.whole[g * cp.ccap], cp.n_whole[g], zm.t_single, zm.t_double, &stack, S, &steps[g * S], &n_steps[g]) != WG_OK ||
+          stack.error || n_steps[g] != S) {
+        fprintf(stderr, "FAILED: the command list of gait %zu does not give %d steps\n", g, S);
+        return 1;
+      }
+    }
   }
   // samples of every gait, L those of the longest (without --ragged: of all)
   std::vector<int> len_g(B);
@@ -123,6 +147,19 @@ int main(int argc, char **argv) {
   CHECK_HIP(dev_alloc(&d_zy, (size_t)L * B));
   CHECK_HIP(dev_alloc(&d_state, (size_t)8 * B));
   CHECK_HIP(dev_alloc(&d_com, (size_t)Lrun * 6 * B));
+  double *d_zc = nullptr, *d_Ktm = nullptr, *d_Ftm = nullptr; int *d_status = nullptr;
+  if (heights) {
+    CHECK_HIP(dev_upload(&d_zc, zc));
+    CHECK_HIP(dev_alloc(&d_Ktm, (size_t)4 * B));
+    CHECK_HIP(dev_alloc(&d_Ftm, (size_t)nl * B));
+    CHECK_HIP(dev_alloc(&d_status, B));
+  }
+  const wg_preview_fleet_t fleet = {zm.T, nl, 0, d_zc, d_Ktm, d_Ftm};
+  // the preview calls of every mode below: the context's gains, or with --heights each gait's own
+  auto preview_batch = [&](int n, const double *zx_, const double *zy_, double *com_, hipStream_t s_) {
+    return heights ? wg_preview_run_fleet_dev(B, n, &fleet, zx_, zy_, d_state, com_, nullptr, 1, s_)
+                   : wg_preview_run_batch_dev(B, n, zx_, zy_, d_state, com_, nullptr, 1, s_);
+  };
   // --online: the walk's state blobs and the feeding plan.  Without --ragged every gait has the same n_steps: nothing ends early
   wg_fleet::OnlinePlan plan;
   wg_zmpdisc_state_t *d_walk = nullptr; wg_rel_step_t *d_chunks = nullptr; int *d_cns = nullptr;
@@ -157,15 +194,19 @@ int main(int argc, char **argv) {
     if (on_device) CHECK_HIP(hipMemcpyAsync(d_stack, fresh.data(), sizeof(wg_step_stack_t) * B, hipMemcpyHostToDevice, st));
     CHECK_HIP(hipStreamSynchronize(st));
     const auto t0 = std::chrono::steady_clock::now();
+    if (heights) CHECK_WG(wg_riccati_gains_batch_dev(B, zm.T, d_zc, 1.0, 1e-6, nl, WG_RICCATI_WITHOUT_INITIALPOS, d_Ktm, d_Ftm, d_status, st));
     // --plan: the steps of the call that follows, from the commands: the whole list, or the support foot and the arc
     if (on_device) CHECK_WG(wg_steps_plan_dev(B, cp.ccap, d_cmds, d_ncmds, zm.t_single, zm.t_double, d_stack, S, d_steps, d_ns, st));
     if (!K) {
       CHECK_WG(wg_zmpdisc_batch_dev(&zm, B, S, d_steps, d_ns, d_feet, L, d_zx, d_zy, d_len, st));
-      CHECK_WG(wg_preview_run_batch_dev(B, Lrun, d_zx, d_zy, d_state, d_com, nullptr, 1, st));
+      CHECK_WG(preview_batch(Lrun, d_zx, d_zy, d_com, st));
     } else if (ragged || on_device) {
       // the plan says which STEPS each call gives and which gaits it ends; how many samples that makes is the device's business
       CHECK_HIP(hipMemsetAsync(d_done, 0, sizeof(int) * B, st));
-      auto follow = [&]() { return wg_preview_follow_dev(B, L, d_len, d_done, d_zx, d_zy, d_state, d_com, nullptr, 1, st); };
+      auto follow = [&]() {
+        return heights ? wg_preview_follow_fleet_dev(B, L, d_len, d_done, &fleet, d_zx, d_zy, d_state, d_com, nullptr, 1, st)
+                       : wg_preview_follow_dev(B, L, d_len, d_done, d_zx, d_zy, d_state, d_com, nullptr, 1, st);
+      };
       auto end_selected = [&](int c) -> int {                  // the gaits whose steps ran out with call c
         const int *sel = &plan.sel[(size_t)c * B];
         bool any = false;
@@ -195,8 +236,7 @@ int main(int argc, char **argv) {
       auto preview_upto = [&](int have) -> int {
         const int n = have - nl + 1 - done;
         if (n <= 0) return WG_OK;
-        const int rc = wg_preview_run_batch_dev(B, n, d_zx + (size_t)done * B, d_zy + (size_t)done * B, d_state,
-                                                d_com + (size_t)done * 6 * B, nullptr, 1, st);
+        const int rc = preview_batch(n, d_zx + (size_t)done * B, d_zy + (size_t)done * B, d_com + (size_t)done * 6 * B, st);
         done += n;
         return rc;
       };
@@ -228,19 +268,44 @@ int main(int argc, char **argv) {
         if (len_h[g] != len_g[g] - nl + 1) { fprintf(stderr, "FAILED: gait %d previewed %d rows of %d\n", g, len_h[g], len_g[g] - nl + 1); return 1; }
     }
   }
-  // gait 0 against the host-pointer entry points
-  const int L0 = len_g[0], Lrun0 = L0 - nl + 1;
-  std::vector<double> zmp((size_t)L0 * 2), com_h((size_t)Lrun0 * 6), state_h(8, 0.0), zx(L0), zy(L0);
-  int len0 = 0;
-  CHECK_WG(wg_zmpdisc_batch(&zm, 1, S, steps.data(), n_steps.data(), feet.data(), L0, zmp.data(), nullptr, nullptr, nullptr, nullptr,
-                            nullptr, nullptr, &len0));
-  for (int l = 0; l < L0; ++l) { zx[l] = zmp[2 * l]; zy[l] = zmp[2 * l + 1]; }
-  CHECK_WG(wg_preview_run_batch(1, Lrun0, zx.data(), zy.data(), state_h.data(), com_h.data(), nullptr, 1));
+  if (heights) {                                               // every gait's gains were made
+    std::vector<int> status(B);
+    CHECK_HIP(hipMemcpy(status.data(), d_status, sizeof(int) * B, hipMemcpyDeviceToHost));
+    for (int g = 0; g < B; ++g)
+      if (status[g] != WG_OK) { fprintf(stderr, "FAILED: the gains of gait %d (zc = %g): status %d\n", g, zc[g], status[g]); return 1; }
+  }
   std::vector<double> com_d((size_t)Lrun * 6 * B);
   CHECK_HIP(hipMemcpy(com_d.data(), d_com, sizeof(double) * com_d.size(), hipMemcpyDeviceToHost));
-  for (int l = 0; l < Lrun0; ++l)
-    for (int c = 0; c < 6; ++c)
-      if (com_d[((size_t)l * 6 + c) * B] != com_h[(size_t)l * 6 + c]) { fprintf(stderr, "FAILED: device chain differs from the host entry points at step %d\n", l); return 1; }
+  // a gait against the host-pointer entry points, one gait at a time (with --heights: configured with its own wg_riccati_gains)
+  std::vector<double> com_h;
+  int len0 = 0;
+  auto check_gait = [&](int g) -> int {
+    if (heights) {
+      CHECK_WG(wg_riccati_gains(zm.T, zc[g], 1.0, 1e-6, nl, WG_RICCATI_WITHOUT_INITIALPOS, Kg, F.data()));
+      const wg_preview_gains_t own = {zm.T, zc[g], Kg[0], {Kg[1], Kg[2], Kg[3]}, nl, 0};
+      CHECK_WG(wg_preview_configure(&own, F.data()));
+    }
+    const int Lg = len_g[g], Lrun_g = Lg - nl + 1;
+    std::vector<double> zmp((size_t)Lg * 2), state_h(8, 0.0), zx(Lg), zy(Lg);
+    com_h.assign((size_t)Lrun_g * 6, 0.0);
+    CHECK_WG(wg_zmpdisc_batch(&zm, 1, S, &steps[(size_t)g * S], &n_steps[g], &feet[(size_t)g * 6], Lg, zmp.data(), nullptr, nullptr, nullptr,
+                              nullptr, nullptr, nullptr, &len0));
+    for (int l = 0; l < Lg; ++l) { zx[l] = zmp[2 * l]; zy[l] = zmp[2 * l + 1]; }
+    CHECK_WG(wg_preview_run_batch(1, Lrun_g, zx.data(), zy.data(), state_h.data(), com_h.data(), nullptr, 1));
+    for (int l = 0; l < Lrun_g; ++l)
+      for (int c = 0; c < 6; ++c)
+        if (com_d[((size_t)l * 6 + c) * B + g] != com_h[(size_t)l * 6 + c]) {
+          fprintf(stderr, "FAILED: device chain of gait %d differs from the host entry points at step %d\n", g, l);
+          return 1;
+        }
+    return 0;
+  };
+  if (heights && B > 1 && check_gait(B - 1)) return 1;
+  if (check_gait(0)) return 1;                                 // last: com_h and len0 below are gait 0's
+  if (heights)
+    printf("kajita_fleet: CoM heights %.4f .. %.4f m, the gains of %d gaits made on the device, all status 0; gaits 0 and %d == host entry "
+           "points with their own gains\n", zc[0], zc[B - 1], B, B - 1);
+  const int Lrun0 = len_g[0] - nl + 1;
   if (ragged) {                                                // each gait's own rows, gait by gait
     std::vector<double> own;
     double far = 0.0;

@@ -117,6 +117,12 @@ def lib():
         _lib.wg_preview_run_batch_dev.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]
         if hasattr(_lib, "wg_preview_follow_dev"):          # absent from older experiment builds (WG_LIB_PATH, A/B runs)
             _lib.wg_preview_follow_dev.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p]
+        if hasattr(_lib, "wg_riccati_gains_batch_dev"):     # absent from older experiment builds (WG_LIB_PATH, A/B runs)
+            _lib.wg_riccati_gains_batch.argtypes = [C.c_int, C.c_double, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_int] + \
+                [C.c_void_p] * 3
+            _lib.wg_riccati_gains_batch_dev.argtypes = _lib.wg_riccati_gains_batch.argtypes + [C.c_void_p]
+            _lib.wg_preview_run_fleet_dev.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p]
+            _lib.wg_preview_follow_fleet_dev.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 8 + [C.c_int, C.c_void_p]
         _lib.wg_zmpdisc_defaults.argtypes = [C.c_void_p]
         _lib.wg_zmpdisc_length.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         _lib.wg_zmpdisc_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + \
@@ -183,7 +189,8 @@ CTX_ENTRY_POINTS = ("wg_set_overlap_strict", "wg_overlap_serialised", "wg_qp_sol
                     "wg_zmpdisc_begin_dev", "wg_zmpdisc_append_dev", "wg_zmpdisc_end_dev",
                     "wg_dimitrov_select_polys_dev", "wg_dimitrov_walk_dev", "wg_foot_constraints_append_dev",
                     "wg_dimitrov_walk_time", "wg_dimitrov_walk_safe_ticks", "wg_preview_follow_dev", "wg_dimitrov_follow_dev",
-                    "wg_steps_plan_dev")
+                    "wg_steps_plan_dev", "wg_riccati_gains_batch", "wg_riccati_gains_batch_dev", "wg_preview_run_fleet_dev",
+                    "wg_preview_follow_fleet_dev")
 
 
 class Context:
@@ -599,6 +606,51 @@ def preview_follow_dev(B, lcap, length_ptr, done_ptr, zx_tm_ptr, zy_tm_ptr, stat
     """every gait over the rows its own queue has made safe: steps [done[b], length[b] - nl + 1), absolute rows (wg_mpc.h)"""
     _check(lib().wg_preview_follow_dev(B, lcap, length_ptr, done_ptr, zx_tm_ptr, zy_tm_ptr, state_ptr, com_tm_ptr, zmp2_tm_ptr,
                                        int(bool(simulation)), stream))
+
+
+# ---- Kajita fleets with a CoM height per gait: gains made on the device, preview with gains per gait ----
+class PreviewFleet(C.Structure):        # wg_preview_fleet_t
+    _fields_ = [("T", C.c_double), ("nl", C.c_int), ("pad_", C.c_int), ("zc", C.c_void_p), ("K_tm", C.c_void_p),
+                ("F_tm", C.c_void_p)]
+
+
+def preview_fleet(T, nl, zc_ptr, K_tm_ptr, F_tm_ptr):
+    """wg_preview_fleet_t over device arrays zc [B], K_tm [4][B] (Ks, Kx0..2), F_tm [nl][B]"""
+    f = PreviewFleet()
+    f.T, f.nl, f.pad_, f.zc, f.K_tm, f.F_tm = float(T), int(nl), 0, zc_ptr, K_tm_ptr, F_tm_ptr
+    return f
+
+
+def riccati_gains_batch(T, zc, Q, R, Nl, mode):
+    """wg_riccati_gains for every height of zc [B], on the device -> (K [B, 4], F [B, Nl], status [B]); host-pointer entry point."""
+    zc = np.ascontiguousarray(zc, dtype=np.float64)
+    B = zc.shape[0]
+    K = np.zeros((B, 4))
+    F = np.zeros((B, int(Nl)))
+    status = np.zeros(B, dtype=np.int32)
+    _check(lib().wg_riccati_gains_batch(B, float(T), _hp(zc), float(Q), float(R), int(Nl), int(mode), _hp(K),
+                                        _hp(F) if Nl > 0 else None, _hp(status)))
+    return K, F, status
+
+
+def riccati_gains_batch_dev(B, T, zc_ptr, Q, R, Nl, mode, K_tm_ptr, F_tm_ptr, status_ptr, stream=None):
+    """one lane per gait: K_tm [4][B], F_tm [Nl][B] time-major, status [B] (all device pointers)"""
+    _check(lib().wg_riccati_gains_batch_dev(B, float(T), zc_ptr, float(Q), float(R), int(Nl), int(mode), K_tm_ptr, F_tm_ptr,
+                                            status_ptr, stream))
+
+
+def preview_run_fleet_dev(B, L, fleet, zx_tm_ptr, zy_tm_ptr, state_ptr, com_tm_ptr=None, zmp2_tm_ptr=None, simulation=True,
+                          stream=None):
+    """wg_preview_run_batch_dev with the gains of `fleet` (a PreviewFleet) per gait instead of the context's"""
+    _check(lib().wg_preview_run_fleet_dev(B, L, C.addressof(fleet), zx_tm_ptr, zy_tm_ptr, state_ptr, com_tm_ptr, zmp2_tm_ptr,
+                                          int(bool(simulation)), stream))
+
+
+def preview_follow_fleet_dev(B, lcap, length_ptr, done_ptr, fleet, zx_tm_ptr, zy_tm_ptr, state_ptr, com_tm_ptr=None,
+                             zmp2_tm_ptr=None, simulation=True, stream=None):
+    """wg_preview_follow_dev with the gains of `fleet` (a PreviewFleet) per gait instead of the context's"""
+    _check(lib().wg_preview_follow_fleet_dev(B, lcap, length_ptr, done_ptr, C.addressof(fleet), zx_tm_ptr, zy_tm_ptr, state_ptr,
+                                             com_tm_ptr, zmp2_tm_ptr, int(bool(simulation)), stream))
 
 
 # ---- Kajita stage-1 inputs: ZMPDiscretization, batched; FootConstraintsAsLinearSystem (host) ----

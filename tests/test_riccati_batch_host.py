@@ -1,0 +1,104 @@
+"""The fleet forms of the Kajita gains and preview (wg_riccati_gains_batch*, wg_preview_run_fleet_dev, wg_preview_follow_fleet_dev),
+host side: the symbols exist, every argument they refuse is refused before a device is looked for, and the host call
+wg_riccati_gains -- whose arithmetic the fleet kernel shares through csrc/wg_riccati_math.hpp -- still returns the bits it
+returned before that text was shared (tests/golden/riccati_host_bits.npz, recorded by tools/record_riccati_host_bits.py).
+Runs without a GPU; the kernels are held to the host call in test_riccati_batch_gpu.py."""
+import ctypes as C
+import importlib
+import os
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+wg = importlib.import_module("jrl-walkgen_amd")
+
+BAD_ARG = -2
+NL_MAX = 4096                                   # WG_PREVIEW_NL_MAX
+NEW = ("wg_riccati_gains_batch_dev", "wg_riccati_gains_batch", "wg_preview_run_fleet_dev", "wg_preview_follow_fleet_dev")
+
+
+def test_symbols_and_abi():
+    lib = wg.lib()
+    for name in NEW:
+        assert hasattr(lib, name) and hasattr(lib, name + "_ctx"), name
+        assert name in wg.CTX_ENTRY_POINTS
+    assert lib.wg_abi_version() == 5
+    assert C.sizeof(wg.PreviewFleet) == 40
+    hdr = open(os.path.join(ROOT, "include", "wg_mpc.h")).read()
+    assert "typedef struct wg_preview_fleet {" in hdr and "} wg_preview_fleet_t;" in hdr
+
+
+def test_host_gains_keep_their_bits():
+    """the guard of the refactor: 8 cases recorded from the library before the arithmetic moved into the shared header"""
+    gold = np.load(os.path.join(ROOT, "tests", "golden", "riccati_host_bits.npz"))
+    cases, K0, F0 = gold["cases"], gold["K"], gold["F"]
+    assert cases.shape == (8, 3) and K0.shape == (8, 4) and F0.shape == (8, 320) and K0.dtype == F0.dtype == np.uint64
+    assert {(T, zc, int(m)) for T, zc, m in cases} == {(T, zc, m) for T in (0.005, 0.01) for zc in (0.6, 0.814) for m in (0, 1)}
+    for (T, zc, mode), k0, f0 in zip(cases, K0, F0):
+        mode = int(mode)
+        K, F = wg.riccati_gains(T, zc, 1.0, 1e-6 if mode == 1 else 1e-5, 320, mode)
+        assert np.array_equal(K.view(np.uint64), k0), (T, zc, mode)
+        assert np.array_equal(F.view(np.uint64), f0), (T, zc, mode)
+        assert np.isfinite(F).all() and F[0] != 0.0
+
+
+def _riccati_args():
+    """arguments in order (host arrays stand in for device arrays: a refusal never looks at them)"""
+    B, Nl = 3, 8
+    keep = [np.full(B, 0.8), np.zeros((4, B)), np.zeros((Nl, B)), np.zeros(B, np.int32)]
+    p = [a.ctypes.data for a in keep]
+    return keep, [B, 0.005, p[0], 1.0, 1e-6, Nl, 1, p[1], p[2], p[3]]
+
+
+def _with(args, **kw):
+    a = list(args)
+    for k, v in kw.items():
+        a[int(k[1:])] = v
+    return a
+
+
+def test_riccati_batch_refusals_need_no_device():
+    lib = wg.lib()
+    keep, args = _riccati_args()
+    bad = [dict(a0=-1), dict(a1=0.0), dict(a1=-0.005), dict(a1=float("nan")), dict(a4=0.0), dict(a4=-1e-6), dict(a6=2), dict(a6=-1),
+           dict(a5=-1), dict(a5=NL_MAX + 1), dict(a2=None), dict(a7=None), dict(a8=None), dict(a9=None)]
+    for kw in bad:
+        a = _with(args, **kw)
+        assert lib.wg_riccati_gains_batch_dev(*a, None) == BAD_ARG, kw
+        assert lib.wg_riccati_gains_batch(*a) == BAD_ARG, kw
+        assert lib.wg_riccati_gains_batch_dev_ctx(None, *a, None) == BAD_ARG, kw
+        assert lib.wg_riccati_gains_batch_ctx(None, *a) == BAD_ARG, kw
+    assert lib.wg_last_error()
+    assert all((k == k.flat[0]).all() for k in keep)                          # nothing was written
+
+
+def _fleet_args(nl=8):
+    B = 3
+    keep = [np.full(B, 0.8), np.zeros((4, B)), np.zeros((nl, B)), np.zeros((nl + 4, B)), np.zeros((nl + 4, B)), np.zeros((B, 8)),
+            np.full(B, nl + 2, np.int32), np.zeros(B, np.int32)]
+    fleet = wg.preview_fleet(0.005, nl, keep[0].ctypes.data, keep[1].ctypes.data, keep[2].ctypes.data)
+    return keep, fleet
+
+
+def test_preview_fleet_refusals_need_no_device():
+    lib = wg.lib()
+    nl = 8
+    keep, fleet = _fleet_args(nl)
+    zx, zy, st, ln, dn = (a.ctypes.data for a in keep[3:])
+    fp = C.addressof(fleet)
+    run = [3, 5, fp, zx, zy, st, None, None, 1]
+    follow = [3, nl + 4, ln, dn, fp, zx, zy, st, None, None, 1]
+    for kw in (dict(a0=-1), dict(a1=-1), dict(a2=None), dict(a3=None), dict(a4=None), dict(a5=None)):
+        assert lib.wg_preview_run_fleet_dev(*_with(run, **kw), None) == BAD_ARG, kw
+        assert lib.wg_preview_run_fleet_dev_ctx(None, *_with(run, **kw), None) == BAD_ARG, kw
+    for kw in (dict(a0=-1), dict(a1=nl - 1), dict(a2=None), dict(a3=None), dict(a4=None), dict(a5=None), dict(a6=None), dict(a7=None)):
+        assert lib.wg_preview_follow_fleet_dev(*_with(follow, **kw), None) == BAD_ARG, kw
+        assert lib.wg_preview_follow_fleet_dev_ctx(None, *_with(follow, **kw), None) == BAD_ARG, kw
+    # what the struct itself can have wrong: a null array, a window out of range, a sampling period that is not positive
+    for field, value in (("zc", None), ("K_tm", None), ("F_tm", None), ("nl", 0), ("nl", NL_MAX + 1), ("T", 0.0), ("T", -0.005)):
+        _, f2 = _fleet_args(nl)
+        f2.zc, f2.K_tm, f2.F_tm = fleet.zc, fleet.K_tm, fleet.F_tm
+        setattr(f2, field, value)
+        assert lib.wg_preview_run_fleet_dev(*_with(run, a2=C.addressof(f2)), None) == BAD_ARG, field
+        assert lib.wg_preview_follow_fleet_dev(*_with(follow, a4=C.addressof(f2)), None) == BAD_ARG, field
+    assert all((k == k.flat[0]).all() for k in keep)
