@@ -400,6 +400,9 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
     }
 
     if (st == ST_SCAN) {
+      // the common path -- an add that neither resets nor refreshes is followed by the next scan -- closes here with ONE taken
+      // branch, without passing the dispatch on `st` at the head of the loop (the lane index is made opaque again, as there)
+      next_scan: asm volatile("" : "+v"(lane));
       // ---- most violated normalised constraint, :1255-1331 ----
       // bestw: the weight wa[.] of the lane's candidate as the scan read it.  The winner's is kept (wsel): the linear-dependence
       // test divides by it and the activation stores its negative -- wa may live in global memory (L2), where reading it again on
@@ -704,7 +707,12 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
             WG_WSYNC();
             // three ordered sums of NM terms: lane 0 adds the first vector, lane 1 the second, lane 2 the third (the
             // scratch vectors are contiguous) -- one 8-cycle add chain per lane instead of three interleaved ones in all
-            const double *src = q.sc0 + (lane < 3 ? lane : 0) * (int)(q.sc1 - q.sc0);
+            // the lane's vector through ONE typed address register with constant offsets (as in sweep_flat): as a plain pointer
+            // every pair of loads got an address of its own, a v_add each, because the scratch vectors lie beyond the reach
+            // of a two-entry load's offsets
+            typedef __attribute__((address_space(3))) double lds_f64;
+            const lds_f64 *src = (const lds_f64 *)(q.sc0 + (lane < 3 ? lane : 0) * (int)(q.sc1 - q.sc0));
+            asm volatile("" : "+v"(src));
             double acc = 0.0;
 #pragma unroll
             for (int i0 = 0; i0 < NM; i0 += kOsChunk) {
@@ -848,6 +856,7 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
       // R's LDS part is full (its columns and the working column hold nact finished columns): stop BETWEEN two iterations,
       // the loop's state goes to the caller, who moves R and resumes (or, without rs, repeats the solve from the start)
       if (q.nact_cap > 0 && nact > q.nact_cap) { cap_hit = true; break; }
+      if (st == ST_SCAN) goto next_scan;
       continue;
     }
 

@@ -850,6 +850,26 @@ __device__ __forceinline__ int pick_drop_serial_reference(const QlView &q, int n
   return kdrop;
 }
 
+// Smallest 32-bit unsigned value of the wave, wave-uniform: the six steps of wg_wave.hpp's reductions (row_shr 1, 2, 4, 8, then
+// row_bcast 15 and 31 fold the rows into lane 63) with the minimum taken BY the DPP instruction -- v_min_u32 is VOP2, a lane
+// without a source keeps its value because destination and second operand are one register -- two instructions per step (the
+// s_nop 1 is the two wait states between a VALU write and a DPP read of the same register, which the compiler does not count
+// inside an asm statement) where update_dpp + min compiles to four: copy, s_nop, v_mov_dpp, v_min.  All 64 lanes must be active.
+// The statement also hides the DPP from the compiler's hazard recogniser, and only the hazard above is padded by hand: a VALU
+// write of EXEC right in front of it (v_cmpx, v_readlane into EXEC) would need five wait states before a DPP and would get two.
+// Its callers sit in wave-uniform code behind a ballot, where EXEC is written by scalar instructions if at all; a caller inside
+// divergent code generated with v_cmpx has to pad for itself.
+__device__ __forceinline__ unsigned wave_min_u32(unsigned v) {
+  asm("s_nop 1\n\tv_min_u32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 1\n\tv_min_u32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 1\n\tv_min_u32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 1\n\tv_min_u32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 1\n\tv_min_u32_dpp %0, %0, %0 row_bcast:15 row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 1\n\tv_min_u32_dpp %0, %0, %0 row_bcast:31 row_mask:0xf bank_mask:0xf"
+      : "+v"(v));
+  return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
+}
+
 template <bool kOnePass = false, bool kNan = false>       // kOnePass: nact <= 64 known at compile time (n <= 64); kNan: see above
 __device__ __forceinline__ int pick_drop(const QlView &q, int nact, double res, double &ratio, int lane) {
   double best = 0.0, bestt = 0.0;
@@ -868,6 +888,24 @@ __device__ __forceinline__ int pick_drop(const QlView &q, int nact, double res, 
     if constexpr (kNan) {
       const bool bw = !wg_sane(w), bl = !wg_sane(lamv);    // plain values: the || below have nothing to short-circuit
       bad = bad || (in && (bw || bl));
+      if (__ballot(bad) != 0ull) return uni(pick_drop_serial_reference(q, nact, res, ratio));
+      // Every operand is an ordinary number here, so a candidate's quotient is one too, or an infinity (res * w < 0 leaves no
+      // zero divisor): the smallest |temp| is the smallest bit pattern of |temp| read as an unsigned integer, and equal
+      // magnitudes are equal patterns.  Two 32-bit minima on the DPP path (high words, then the low words of the lanes that
+      // hold the smallest high word) and the first lane of one ballot -- the candidate's index IS its lane -- instead of a
+      // 64-bit floating-point maximum and an index minimum: 30 vector instructions for 75, the same lane for the same operands.
+      // This selection exists in the kNan form only, because only there the operands are known to be ordinary numbers: a build
+      // with WG_TICK_NAN_EXACT = 0 or WG_NAN_REGIME = 0 (the A/B builds) takes the 64-bit reduction below, so an A/B of the
+      // NaN regime also switches the ratio test's selection.
+      const unsigned hi = cand ? ((unsigned)__double2hiint(temp) & 0x7fffffffu) : 0xffffffffu;
+      const unsigned lo = (unsigned)__double2loint(temp);
+      const unsigned mh = wave_min_u32(hi);
+      const unsigned ml = wave_min_u32(hi == mh ? lo : 0xffffffffu);
+      const unsigned long long win = __ballot(cand && hi == mh && lo == ml);
+      if (win == 0ull) return -1;
+      const int idx = __ffsll((long long)win) - 1;
+      ratio = rl(temp, idx);
+      return idx;
     }
     best = cand ? -fabs(temp) : 0.0; bestt = cand ? temp : 0.0; bidx = cand ? lane : -1;
   } else

@@ -147,7 +147,7 @@ def block_current():
         if f32:
             L.append(f"N = 32, B = 8192: {f32[0]['a']:.2f} ms + {f32[0]['b']:.3f} ms × T, steady {M(f32[0]['steady'])}.")
         L.append("")
-    L.append(f"**Resources** (`{tag}_resource_usage.txt`: the compiler's table, spill code placed by loop depth — 1 = per tick, 2 = per active-set iteration, ≥ 3 = inner loops):")
+    L.append(f"**Resources** (`{tag}_resource_usage.txt`: the compiler's table, spill code placed by loop depth — 1 = per tick, 2 = the solver's dispatch loop (reset, refresh, convergence), 3 = the common path scan … add of an active-set iteration, which closes on itself inside that loop, ≥ 4 = inner loops; tables filed before the common path closed on itself had the whole iteration at depth 2 and the inner loops at ≥ 3, so their \"≥ 3\" figures compare with \"≥ 4\" here, not with this table's \"≥ 3\"):")
     L.append("")
     L.append("| kernel | VGPR | spilled VGPR | spilled SGPR | scratch per lane | waves / SIMD | `scratch_` instructions | SGPR-spill reloads |")
     L.append("|---|---|---|---|---|---|---|---|")

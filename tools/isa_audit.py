@@ -149,7 +149,10 @@ def main():
     dm = demangle([n for _, n in starts])
     out.append("")
     out.append("# where the spill code sits: instructions by loop-nesting depth (0 = straight-line, 1 = outermost loop, ...)")
-    out.append("#   multi-tick kernels: depth 1 = per tick, depth 2 = per active-set iteration, depth >= 3 = inner loops of the phases")
+    out.append("#   multi-tick kernels: depth 1 = per tick, depth 2 = the solver's dispatch loop (reset, refresh, convergence), depth 3 = the")
+    out.append("#   common path scan .. add of an active-set iteration, a loop of its own inside the dispatch loop, depth >= 4 = inner loops of")
+    out.append("#   the phases.  Audits filed before the common path closed on itself had the whole iteration at depth 2 and the inner loops")
+    out.append("#   at depth >= 3: their 'depth >= 3' rows are this table's 'depth >= 4', their 'depth 2' this table's 2 and 3 together.")
     for k, (i0, name) in enumerate(starts):
         pretty = dm[name]
         if not any(w in pretty for w in want):
