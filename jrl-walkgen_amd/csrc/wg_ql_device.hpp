@@ -429,14 +429,31 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
         const bool has_foot = lane < 5 * prob.ns;
         const int kf = has_foot ? 1 + 4 * NH + lane : 0;
         const double wakf = q.wa[kf], bkf = q.b[kf];
+        // ... and so is every other operand of what follows the CoP row's jerk terms: its two step-column terms, the four terms of
+        // the foot-placement row and the bound pair of variable `lane`.  Requested one by one where they are used, each was an
+        // exposed round trip per iteration (six to LDS, and one to L2 for the bound's weight: wa lives in global memory here).
+        // A CoP row of the current support phase (fj < 0) has no step-column entry: its lanes take x[0] with a zero coefficient
+        // instead of branching around the two terms.  Their products are +-0.0 (x holds ordinary numbers on this path): a non-zero
+        // sum and asum >= +0.0 are unchanged, and a zero sum of either sign gives sumx = -(+-0) wak, which is not > 0: no
+        // candidate either way, and only a candidate's sum is ever used
+        const bool has_step = prob.fj >= 0;
+        const double xsa = q.x[has_step ? 2 * NH + prob.fj : 0], xsb = q.x[has_step ? 2 * NH + prob.ns + prob.fj : 0];
+        const auto fr = prob.foot_row();
+        double xfr[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) xfr[e] = q.x[fr.c[e]];
+        const bool bin = lane < n;
+        const int bkc = bin ? lane : n - 1;
+        const double bw = q.wa[m + bkc], bxk = q.x[bkc];
         {
           const int k = lane + 1;                     // the lane's CoP row
           const double wak = q.wa[k], bk = prob.bcop;
           double sum = -bk, asum = fabs(bk);
           prob.cop_row_dot(xs, sum, asum);
-          if (prob.fj >= 0) {
-            double t = q.x[2 * NH + prob.fj] * prob.fa(); sum += t; asum += fabs(t);
-            t = q.x[2 * NH + prob.ns + prob.fj] * prob.fb(); sum += t; asum += fabs(t);
+          {
+            const double ca = has_step ? prob.fa() : 0.0, cb = has_step ? prob.fb() : 0.0;
+            double t = xsa * ca; sum += t; asum += fabs(t);
+            t = xsb * cb; sum += t; asum += fabs(t);
           }
           const double sumx = -sum * wak;
           {                                           // the reference's tests in its order, as one predicate and three selects
@@ -452,14 +469,23 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
           const int k = kf;
           const double wak = wakf, bk = bkf;
           double sum = -bk, asum = fabs(bk);
-          const auto fr = prob.foot_row();
 #pragma unroll
-          for (int e = 0; e < 4; ++e) { const double t = q.x[fr.c[e]] * fr.v[e]; sum += t; asum += fabs(t); }
+          for (int e = 0; e < 4; ++e) { const double t = xfr[e] * fr.v[e]; sum += t; asum += fabs(t); }
           const double sumx = -sum * wak;
           const double tempa = asum + fabs(sum);
           const double temp2 = asum + onha * fabs(sum);
           const bool take = has_foot & (wak > 0.0) & !(sumx <= 0.0) & !((bidx >= 0) & (sumx <= bestv)) & !(tempa <= asum) & !(temp2 <= tempa);
           bestv = take ? sumx : bestv; bestres = take ? sum : bestres; bestw = take ? wak : bestw; bidx = take ? k + 1 : bidx;
+        }
+        {
+          // the bound pair of variable `lane` (the n <= 64 form below, on the operands requested above); the code of an upper bound
+          // is the lower one's plus n: an addend chosen by a select, not two assignments under exec masks
+          const double s1 = prob.xl(q, bkc) - bxk;
+          const bool upper = s1 < 0.0;
+          const double sum = upper ? bxk - prob.xu(q, bkc) : s1;
+          const bool take = bin & !(bw <= 0.0) & !(s1 == 0.0) & !(sum <= 0.0) & !((bidx >= 0) & (sum <= bestv));
+          bestv = take ? sum : bestv; bestres = take ? -sum : bestres; bestw = take ? bw : bestw;
+          bidx = take ? bkc + 1 + m + (upper ? n : 0) : bidx;
         }
       } else {
       if constexpr (P::kRowOps) {
@@ -570,7 +596,8 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
         QL_SCAN_ACCEPT;
       }
       }
-      if constexpr (P::kNM > 0) {                            // n <= 64: one bound pair per lane, selects instead of continues
+      if constexpr (P::kCompact) {                           // done above, with the rows
+      } else if constexpr (P::kNM > 0) {                     // n <= 64: one bound pair per lane, selects instead of continues
         const bool in = lane < n;
         const int kc = in ? lane : n - 1;
         const double w = q.wa[m + kc], xk = q.x[kc];
@@ -595,6 +622,17 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
         // order key: general rows 1..m, then bounds by variable; lower/upper of one
         // variable never compete.  knext codes > mn (upper) must sort by variable.
         int key = bidx < 0 ? -1 : (bidx > mn ? bidx - n : bidx);
+        if constexpr (P::kCompact) {
+          // the compact view's selection on the bit patterns of the (positive) candidate values: scan_select_lane
+          const int src = scan_select_lane(bestv, key);
+          if (src < 0) { bestv = 0.0; bidx = -1; }
+          else {
+            bestv = rl(bestv, src);
+            bestres = rl(bestres, src);
+            bestw = rl(bestw, src);
+            bidx = __builtin_amdgcn_readlane(bidx, src);
+          }
+        } else {
         double v = bestv;
         int kk = key;
         wave_argmax_first(v, kk);
@@ -609,6 +647,7 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
           bestres = rl(bestres, src);
           bestw = rl(bestw, src);
           bidx = __builtin_amdgcn_readlane(bidx, src);
+        }
         }
       }
       WG_SINK(bestv); WG_SINK(bestres); WG_SINK(bestw); WG_SINK(bidx);
@@ -699,10 +738,15 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
           WG_REP(5) {
           if constexpr (P::kNM > 0) {
             constexpr int NM = P::kNM;
-            if (lane < NM) {
-              const bool in = lane < n;
-              const double zi = in ? Zm(lane, nact) : 0.0, wi = in ? q.ww[lane] : 0.0;
-              q.sc0[lane] = wi * zi; q.sc1[lane] = fabs(wi * zi); q.sc2[lane] = zi * zi;
+            {
+              // lanes past NM shadow lane NM - 1 (same value to the same address); loads from clamped addresses, selected values:
+              // a load or a store under a lane-dependent condition is an exec-mask save / restore, here in every iteration
+              const int il = lane < NM ? lane : NM - 1;
+              const bool in = il < n;
+              const int ic = in ? il : n - 1;
+              const double zv = Zm(ic, nact), wv = q.ww[ic];
+              const double zi = in ? zv : 0.0, wi = in ? wv : 0.0;
+              q.sc0[il] = wi * zi; q.sc1[il] = fabs(wi * zi); q.sc2[il] = zi * zi;
             }
             WG_WSYNC();
             // three ordered sums of NM terms: lane 0 adds the first vector, lane 1 the second, lane 2 the third (the

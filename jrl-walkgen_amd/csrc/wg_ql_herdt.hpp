@@ -622,8 +622,10 @@ struct HerdtProb {
   // ------------------------------------------------------------------ s = Z' * (row rk of A), :2071-2085
   __device__ __forceinline__ void zt_row(const QlView &q, double *s, int rk, int lane) const {
     const int n = q.n;
-    if (lane < n) {
-      const int i = lane;
+    {
+      // lanes past n shadow lane n - 1 (same loads, same sums, the same value to the same address): no exec-mask save / restore
+      // around the body
+      const int i = lane < n ? lane : n - 1;
       const double *zc = q.Z + i * q.ldz;            // column i of Z is contiguous
       double acc = 0.0;
       if (rk >= 1 && rk <= 4 * NH) {
@@ -645,7 +647,17 @@ struct HerdtProb {
           for (int c = 0; c < kZtChunk; ++c) acc += zz[c] * wv[c];
         }
       }
-      for (int j = 2 * NH; j < n; ++j) acc += zc[j] * q.ww[j];
+      // the step columns' rows 2 NH .. n - 1: n - 2 NH = 2 ns is 0, 2 or 4 (kNM = 2 NH + 4).  The four operand pairs are requested
+      // together (entries past n lie inside the column of Z and inside ww: read, never used), then one wave-uniform test per
+      // previewed step: the counted loop it replaces waited for an LDS round trip per term
+      constexpr int kTail = kNM - 2 * NH;
+      static_assert(kTail == 4, "two entries per previewed step, at most two steps");
+      double zt[kTail], wt[kTail];
+#pragma unroll
+      for (int c = 0; c < kTail; ++c) { zt[c] = zc[2 * NH + c]; wt[c] = q.ww[2 * NH + c]; }
+      const int nb = n - 2 * NH;
+      if (nb >= 2) { acc += zt[0] * wt[0]; acc += zt[1] * wt[1]; }
+      if (nb >= 4) { acc += zt[2] * wt[2]; acc += zt[3] * wt[3]; }
       s[i] = acc;
     }
     WG_WSYNC();

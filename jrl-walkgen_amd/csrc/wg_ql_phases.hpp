@@ -869,8 +869,46 @@ __device__ __forceinline__ unsigned wave_min_u32(unsigned v) {
       : "+v"(v));
   return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
 }
+// Largest 32-bit unsigned value of the wave, wave-uniform: wave_min_u32 with v_max_u32 -- the same six steps, the same padding,
+// the same conditions on its callers (all 64 lanes active, wave-uniform code).
+__device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
+  asm("s_nop 1\n\tv_max_u32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 1\n\tv_max_u32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 1\n\tv_max_u32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 1\n\tv_max_u32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 1\n\tv_max_u32_dpp %0, %0, %0 row_bcast:15 row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 1\n\tv_max_u32_dpp %0, %0, %0 row_bcast:31 row_mask:0xf bank_mask:0xf"
+      : "+v"(v));
+  return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
+}
 
-template <bool kOnePass = false, bool kNan = false>       // kOnePass: nact <= 64 known at compile time (n <= 64); kNan: see above
+// The violation scan's selection among the lanes' candidates -- the largest value, the smallest order key among equal values --
+// for candidates whose values are POSITIVE (every test of the scan that admits a candidate has `value <= 0` as a reason to skip)
+// or a NaN, which takes part in no maximum (wave_argmax_first's v_max_f64 and its `v == vmax` leave a NaN out the same way).
+// Positive doubles order as their bit patterns read as unsigned integers and equal values are equal patterns, so the maximum is
+// two 32-bit maxima on the DPP path (high words, then the low words of the lanes that hold the largest high word), as in the
+// ratio test above; the lanes that hold it come from one ballot, and only when there are several of them -- equal violations
+// of two rows, rare -- does the smallest key need a reduction of its own.  A third of the vector instructions of the 64-bit
+// maximum plus index minimum; the same lane for the same operands.  Returns the winning lane, or -1 without a candidate.
+__device__ __forceinline__ int scan_select_lane(double v, int key) {
+  const bool cand = key >= 0 && v > 0.0;
+  const unsigned hi = cand ? (unsigned)__double2hiint(v) : 0u;
+  const unsigned mh = wave_max_u32(hi);
+  const bool top = cand && hi == mh;
+  const unsigned lo = top ? (unsigned)__double2loint(v) : 0u;
+  const unsigned ml = wave_max_u32(lo);
+  const bool winl = top && lo == ml;
+  const unsigned long long win = __ballot(winl);
+  if (win == 0ull) return -1;
+  int src = __ffsll((long long)win) - 1;
+  if ((win & (win - 1ull)) != 0ull) {                       // several lanes hold the maximum: the smallest key among them
+    const unsigned kmin = wave_min_u32(winl ? (unsigned)key : 0xffffffffu);
+    src = __ffsll((long long)__ballot(winl && (unsigned)key == kmin)) - 1;
+  }
+  return src;
+}
+
+template <bool kOnePass = false, bool kNan = false>      // kOnePass: nact <= 64 known at compile time (n <= 64); kNan: see above
 __device__ __forceinline__ int pick_drop(const QlView &q, int nact, double res, double &ratio, int lane) {
   double best = 0.0, bestt = 0.0;
   int bidx = -1;

@@ -91,7 +91,7 @@ if os.path.exists(TIMERS):
     tsum = sum(v for _, v in rows)
     print()
     print("# the lump by shader-clock timers (%s; %.0f timer cycles per gait-tick in all, %.0f of them in the rows below = %.1f %% there," %
-          (os.path.relpath(TIMERS, ROOT), tot_t, tsum, 100 * tsum / tot_t))
+          ("tools/probe_tick_phases.py", tot_t, tsum, 100 * tsum / tot_t))
     print("# against %.1f %% by the counters: the timers' own reads weigh on short phases); share = row / sum of these rows x %.1f %%" % (lump, lump))
     print("%-112s %10s %8s" % ("phase (not repeatable: timed)", "timer cyc", "time %"))
     for name, v in sorted(rows, key=lambda r: -r[1]):

@@ -39,7 +39,7 @@ for k in names:
     log = os.path.join(d, "trace.log")
     if k in ("gramian", "config5", "elem") and os.path.exists(log):
         keep = [ln for ln in open(log) if ("TFLOP" in ln or "ticks/s" in ln or "same" in ln or "run" in ln) and "amdgpu.ids" not in ln
-                and "Opened result file" not in ln]         # the profiler's own log lines (paths of the box it ran on)
+                and "Opened result file" not in ln and "simple_timer.cpp" not in ln]   # the profiler's own log lines (paths of the box it ran on)
         open(os.path.join(ROOT, "profiles", f"{tag}_{k}_probe_output.txt"), "w").writelines(keep)
 
 
