@@ -972,6 +972,76 @@ int wg_dimitrov_follow_dev(int B, int qcap, const wg_zmp_polytope_t *queues, con
                            const wg_zmpdisc_state_t *walk, int flags, double *clock, int *ticks, int tick_cap, int max_ticks,
                            wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int *ran_out, int max_iter, void *hip_stream);
 
+/* Dimitrov-2008 fleets with a model per gait ------------------------------------------------------------------------------
+ *
+ * wg_dimitrov_configure gives a context one model.  A fleet whose gaits differ in CoM height or in the cost weights alpha,
+ * beta -- robots of different size, a load sweep, a Monte-Carlo run over the weights -- carries its models as BLOCKS instead:
+ * one opaque block of wg_dimitrov_constants_bytes() bytes (a multiple of 128) per model, the constants InitConstants leaves
+ * behind (what wg_dimitrov_configure uploads) and zeros behind them, so that blocks compare as bytes.  The arithmetic is one
+ * text (csrc/wg_dimitrov_math.hpp) compiled for the host and for the device: host blocks and device blocks are the same bytes.
+ *
+ * wg_dimitrov_constants(model, block): host arithmetic, no device call.  WG_ERR_BAD_ARG and an ALL-ZERO block for a model that
+ *   does not exist: N outside 1 .. WG_PLDP_N, an unknown solver, T <= 0, a T, height, alpha or beta that is not finite, an LQ
+ *   factor or an inverse of Pu that does not exist.  (T / Tctrl is not tested: Tctrl only spaces the samples of an out struct.)
+ * wg_dimitrov_constants_unpack(block, ...): host arithmetic on a HOST copy of a block -- the arrays of
+ *   wg_dimitrov_get_constants (iLQ, OptB, OptC, Pu, iPu, Px), of wg_dimitrov_get_qld_constants (Q, OptBq, OptCq, PuT) and
+ *   iPuPx (2N x 6, PLDPSolver::PrecomputeiPuPx), at the sizes of the block's own N; model, if not NULL, gets N, solver, T,
+ *   Tctrl and com_height (the weights are not kept: zeros).  Any pointer but block may be NULL.  WG_ERR_BAD_ARG for a failed
+ *   (all-zero) block.
+ * wg_dimitrov_constants_batch_dev(M, base, com_height, alpha, beta, blocks, status, hip_stream): M models on the device, one
+ *   wavefront per model.
+ *     base        read on the HOST: N, solver, T and Tctrl of every model, and the value of each per-model array that is NULL
+ *     com_height, alpha, beta   DEVICE arrays of M doubles, or NULL
+ *     blocks      M blocks, DEVICE;   status  M ints, DEVICE
+ *   status[m] is WG_OK or WG_ERR_BAD_ARG, exactly what wg_dimitrov_constants returns for model m (a height or weight that is
+ *   not finite included); a failed model gets an all-zero block, never a NaN, and no model touches a byte of another's.
+ *   Asynchronous on hip_stream; keeps nothing in the context.  wg_dimitrov_constants_batch is the same call with HOST
+ *   pointers, staged through the context's stream like the other host forms.
+ *
+ * The fleet descriptor: blocks points to M blocks and model_of to an int per gait, both on the DEVICE; the struct itself is read
+ * on the host.  N, solver and T are fleet-wide (the select kernels and the kernel shapes are): a block made for another N is
+ * refused like a failed one.
+ *
+ * wg_dimitrov_tick_fleet_dev / _walk_fleet_dev / _follow_fleet_dev are wg_dimitrov_tick_batch_dev / _walk_dev / _follow_dev
+ * with the fleet after B: gait g runs with blocks[model_of[g]].  They read nothing of the context's configured Dimitrov model
+ * (no wg_dimitrov_configure is needed) and use the context's walk buffers, launch ordering and longest-solve-first order
+ * exactly as their twins do, through the same launcher.
+ * CONTRACT: gait g of a fleet launch leaves, byte for byte, the state, outs rows, ran_out, clocks and tick counts that a context
+ * configured with model model_of[g] leaves for it through the twin call.
+ * A gait whose model_of[g] is outside [0, M), or whose block is a failed one, is refused: each of its ticks writes
+ * ret = WG_PLDP_BAD_INPUT and n_iter = 0 into its out struct (if any) and nothing else -- no byte of its state changes, in a
+ * walk or a follow call it sits every round's tick out (the follow select kernel, which knows no models, still counts the round
+ * in clock[g] and ticks[g]), and no other gait notices.
+ * Host-side refusals (WG_ERR_BAD_ARG before any device call): a NULL fleet, blocks, model_of or base; M < 1; B < 0; N outside
+ * 1 .. WG_PLDP_N; an unknown solver; T <= 0; and whatever the twin call refuses.  B == 0 is WG_OK.
+ * Added without a change of wg_abi_version(): detect by symbol. */
+typedef struct wg_dimitrov_fleet {
+  int N, solver, M, pad_;
+  double T, Tctrl;
+  const void *blocks;
+  const int *model_of;
+} wg_dimitrov_fleet_t;
+size_t wg_dimitrov_constants_bytes(void);
+int wg_dimitrov_constants(const wg_dimitrov_model_t *model, void *block);
+int wg_dimitrov_constants_unpack(const void *block, wg_dimitrov_model_t *model, double *iLQ, double *OptB, double *OptC,
+                                 double *Pu, double *iPu, double *Px, double *Q, double *OptBq, double *OptCq, double *PuT,
+                                 double *iPuPx);
+int wg_dimitrov_constants_batch_dev(int M, const wg_dimitrov_model_t *base, const double *com_height, const double *alpha,
+                                    const double *beta, void *blocks, int *status, void *hip_stream);
+int wg_dimitrov_constants_batch(int M, const wg_dimitrov_model_t *base, const double *com_height, const double *alpha,
+                                const double *beta, void *blocks, int *status);
+int wg_dimitrov_tick_fleet_dev(int B, const wg_dimitrov_fleet_t *fleet, const wg_zmp_polytope_t *polys,
+                               wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int max_iter, void *hip_stream);
+int wg_dimitrov_walk_fleet_dev(int B, const wg_dimitrov_fleet_t *fleet, int qcap, const wg_zmp_polytope_t *queues,
+                               const double *t_start, const double *t_end, const int *count, double t0, int n_ticks,
+                               wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int *ran_out, int max_iter,
+                               void *hip_stream);
+int wg_dimitrov_follow_fleet_dev(int B, const wg_dimitrov_fleet_t *fleet, int qcap, const wg_zmp_polytope_t *queues,
+                                 const double *t_start, const double *t_end, const int *count, int lcap, const double *time,
+                                 const int *have, const wg_zmpdisc_state_t *walk, int flags, double *clock, int *ticks,
+                                 int tick_cap, int max_ticks, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs,
+                                 int *ran_out, int max_iter, void *hip_stream);
+
 /* Invariant Hessian block on the matrix cores, batched over models -----------------------------------------------------
  *
  * wg_gramian_batch computes, for B models that differ in QP sampling period T[b] and CoM height h[b],
@@ -1105,6 +1175,22 @@ int wg_preview_run_fleet_dev_ctx(wg_ctx_t *ctx, int B, int L, const wg_preview_f
 int wg_preview_follow_fleet_dev_ctx(wg_ctx_t *ctx, int B, int lcap, const int *length, int *done,
                                     const wg_preview_fleet_t *fleet, const double *zmp_x_tm, const double *zmp_y_tm,
                                     double *state, double *com_tm, double *zmp2_tm, int simulation, void *hip_stream);
+int wg_dimitrov_constants_batch_dev_ctx(wg_ctx_t *ctx, int M, const wg_dimitrov_model_t *base, const double *com_height,
+                                        const double *alpha, const double *beta, void *blocks, int *status, void *hip_stream);
+int wg_dimitrov_constants_batch_ctx(wg_ctx_t *ctx, int M, const wg_dimitrov_model_t *base, const double *com_height,
+                                    const double *alpha, const double *beta, void *blocks, int *status);
+int wg_dimitrov_tick_fleet_dev_ctx(wg_ctx_t *ctx, int B, const wg_dimitrov_fleet_t *fleet, const wg_zmp_polytope_t *polys,
+                                   wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int max_iter, void *hip_stream);
+int wg_dimitrov_walk_fleet_dev_ctx(wg_ctx_t *ctx, int B, const wg_dimitrov_fleet_t *fleet, int qcap,
+                                   const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end,
+                                   const int *count, double t0, int n_ticks, wg_dimitrov_state_t *states,
+                                   wg_dimitrov_out_t *outs, int *ran_out, int max_iter, void *hip_stream);
+int wg_dimitrov_follow_fleet_dev_ctx(wg_ctx_t *ctx, int B, const wg_dimitrov_fleet_t *fleet, int qcap,
+                                     const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end,
+                                     const int *count, int lcap, const double *time, const int *have,
+                                     const wg_zmpdisc_state_t *walk, int flags, double *clock, int *ticks, int tick_cap,
+                                     int max_ticks, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int *ran_out,
+                                     int max_iter, void *hip_stream);
 
 #ifdef __cplusplus
 }

@@ -1151,8 +1151,11 @@ int dimitrov_check(wg_ctx *ctx, int B, const wg_zmp_polytope_t *polys, const wg_
 
 // the tick launch of wg_dimitrov_tick_batch_dev and of every tick of wg_dimitrov_walk_dev; with ctx->launch_mu held.  With `row`
 // (wg_dimitrov_follow_dev): the follow wrappers of the same ticks -- gait g writes row row[g] of outs, or sits the launch out
-int dimitrov_tick_launch(wg_ctx *ctx, int B, const wg_zmp_polytope_t *polys, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int max_iter, hipStream_t stq, const int *row = nullptr) {
-  const int solver = ctx->dim_host->solver;
+// With `fl` (the wg_dimitrov_*_fleet_dev calls): the fleet twins of the same kernels -- gait g binds blocks[model_of[g]] where the
+// others bind the context's one model, of which nothing is read.
+int dimitrov_tick_launch(wg_ctx *ctx, int B, const wg_zmp_polytope_t *polys, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int max_iter, hipStream_t stq, const int *row = nullptr, const wg_dimitrov_fleet_t *fl = nullptr) {
+  const int solver = fl ? fl->solver : ctx->dim_host->solver;
+  const unsigned char *blocks = fl ? static_cast<const unsigned char *>(fl->blocks) : nullptr;
   if (solver != WG_DIMITROV_PLDP) {                      // modes QLD / QLDANDLQ: the in-wave ql0002 as the back-end
     const size_t ldsq = wg::dimitrov_qld_lds_bytes();
     // more gaits than resident waves (eight per CU: 256 registers, two waves per SIMD): longest-solve-first by the previous tick
@@ -1165,7 +1168,13 @@ int dimitrov_tick_launch(wg_ctx *ctx, int B, const wg_zmp_polytope_t *polys, wg_
       if (int rc = lpt_prepare(ctx->dim_lpt, states, B, stq, &order, &iters_out)) return rc;
       if (fresh) HIP_TRY(hipMemsetAsync(iters_out, 0, (size_t)B * sizeof(int), stq));
     }
-    if (row) {
+    if (fl && row) {
+      const auto kern = solver == WG_DIMITROV_QLDANDLQ ? wg_dimitrov_qld_fleet_follow_tick_kernel<true> : wg_dimitrov_qld_fleet_follow_tick_kernel<false>;
+      hipLaunchKernelGGL(kern, dim3(B), dim3(64), ldsq, stq, B, fl->N, fl->M, blocks, fl->model_of, polys, states, outs, row, order, iters_out);
+    } else if (fl) {
+      const auto kern = solver == WG_DIMITROV_QLDANDLQ ? wg_dimitrov_qld_fleet_tick_kernel<true> : wg_dimitrov_qld_fleet_tick_kernel<false>;
+      hipLaunchKernelGGL(kern, dim3(B), dim3(64), ldsq, stq, B, fl->N, fl->M, blocks, fl->model_of, polys, states, outs, order, iters_out);
+    } else if (row) {
       const auto kern = solver == WG_DIMITROV_QLDANDLQ ? wg_dimitrov_qld_follow_tick_kernel<true> : wg_dimitrov_qld_follow_tick_kernel<false>;
       hipLaunchKernelGGL(kern, dim3(B), dim3(64), ldsq, stq, B, ctx->dim_dev, polys, states, outs, row, order, iters_out);
     } else {
@@ -1177,10 +1186,13 @@ int dimitrov_tick_launch(wg_ctx *ctx, int B, const wg_zmp_polytope_t *polys, wg_
   }
   const size_t lds = dimitrov_lds_bytes();
   if (lds > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute(row ? reinterpret_cast<const void *>(wg_dimitrov_follow_tick_kernel) : reinterpret_cast<const void *>(wg_dimitrov_tick_kernel),
+    HIP_TRY(hipFuncSetAttribute(fl ? (row ? reinterpret_cast<const void *>(wg_dimitrov_fleet_follow_tick_kernel) : reinterpret_cast<const void *>(wg_dimitrov_fleet_tick_kernel))
+                                   : (row ? reinterpret_cast<const void *>(wg_dimitrov_follow_tick_kernel) : reinterpret_cast<const void *>(wg_dimitrov_tick_kernel)),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   const int grid = B;
-  if (row) hipLaunchKernelGGL(wg_dimitrov_follow_tick_kernel, dim3(grid), dim3(64), lds, stq, B, ctx->dim_dev, polys, states, outs, row, max_iter);
+  if (fl && row) hipLaunchKernelGGL(wg_dimitrov_fleet_follow_tick_kernel, dim3(grid), dim3(64), lds, stq, B, fl->N, fl->M, blocks, fl->model_of, polys, states, outs, row, max_iter);
+  else if (fl) hipLaunchKernelGGL(wg_dimitrov_fleet_tick_kernel, dim3(grid), dim3(64), lds, stq, B, fl->N, fl->M, blocks, fl->model_of, polys, states, outs, max_iter);
+  else if (row) hipLaunchKernelGGL(wg_dimitrov_follow_tick_kernel, dim3(grid), dim3(64), lds, stq, B, ctx->dim_dev, polys, states, outs, row, max_iter);
   else hipLaunchKernelGGL(wg_dimitrov_tick_kernel, dim3(grid), dim3(64), lds, stq, B, ctx->dim_dev, polys, states, outs, max_iter);
   HIP_TRY(hipGetLastError());
   return slot_mark(ctx->aux_order, stq);
@@ -1277,15 +1289,68 @@ int wg_dimitrov_tick_batch_ctx(wg_ctx_t *ctx, int B, const wg_zmp_polytope_t *po
 // ---- Dimitrov fleets on the device: polytope queues, the queue walk of a tick, n ticks on a stream --------------------------
 
 namespace {
-int select_check(wg_ctx *ctx, int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count) {
-  if (int rc = use_ctx(ctx)) return rc;
-  if (!ctx->dim_set) return fail(WG_ERR_BAD_ARG, "wg_dimitrov_configure() has not been called on this context");
+int queue_check(int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count) {
   if (B < 0 || qcap < 1 || !queues || !t_start || !t_end || !count) return fail(WG_ERR_BAD_ARG, "need B >= 0, qcap >= 1, non-null queues, intervals and counts");
   return WG_OK;
 }
-void select_launch(wg_ctx *ctx, int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count, double t0, wg_zmp_polytope_t *polys, int *ran_out, int sticky, hipStream_t st) {
+int select_check(wg_ctx *ctx, int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count) {
+  if (int rc = use_ctx(ctx)) return rc;
+  if (!ctx->dim_set) return fail(WG_ERR_BAD_ARG, "wg_dimitrov_configure() has not been called on this context");
+  return queue_check(B, qcap, queues, t_start, t_end, count);
+}
+void select_launch(int N, double T, int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count, double t0, wg_zmp_polytope_t *polys, int *ran_out, int sticky, hipStream_t st) {
   hipLaunchKernelGGL(wg::wg_dimitrov_select_kernel, dim3((B + 3) / 4), dim3(256), 0, st, B, qcap, queues, t_start, t_end, count, t0,
-                     ctx->dim_host->N, ctx->dim_host->T, polys, ran_out, sticky);
+                     N, T, polys, ran_out, sticky);
+}
+
+// the launches of wg_dimitrov_walk_dev (fl == nullptr: N, T and the ticks' model are the context's) and of
+// wg_dimitrov_walk_fleet_dev (the fleet's); the arguments are checked
+int dimitrov_walk_launch(wg_ctx *ctx, const wg_dimitrov_fleet_t *fl, int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count, double t0, int n_ticks, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int *ran_out, int max_iter, void *hip_stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  const int Ni = fl ? fl->N : ctx->dim_host->N;
+  const size_t N = (size_t)Ni;
+  const double T = fl ? fl->T : ctx->dim_host->T;
+  std::lock_guard<std::mutex> launch_lk(ctx->launch_mu);
+  // the selected polytopes live in a buffer of the context, rewritten tick by tick: behind the previous walk, whatever stream
+  // that was on; growing retires the old allocation, which a launch in flight may still be reading (DevBuf)
+  if (int rc = slot_claim(ctx, ctx->walk_order, st, "Dimitrov walk")) return rc;
+  if (int rc = ctx->walk_polys.reserve((size_t)B * N * sizeof(wg_zmp_polytope_t))) return rc;
+  wg_zmp_polytope_t *polys = static_cast<wg_zmp_polytope_t *>(ctx->walk_polys.p);
+  if (ran_out) HIP_TRY(hipMemsetAsync(ran_out, 0, (size_t)B * sizeof(int), st));
+  double t = t0;
+  for (int k = 0; k < n_ticks; k++) {
+    select_launch(Ni, T, B, qcap, queues, t_start, t_end, count, t, polys, ran_out, 1, st);
+    HIP_TRY(hipGetLastError());
+    if (int rc = dimitrov_tick_launch(ctx, B, polys, states, outs ? outs + (size_t)k * (size_t)B : nullptr, max_iter, st, nullptr, fl)) return rc;
+    t += T;                                               // BuildZMPTrajectoryFromFootTrajectory's own accumulation (:1189-1192)
+  }
+  return slot_mark(ctx->walk_order, st);
+}
+
+// likewise wg_dimitrov_follow_dev and wg_dimitrov_follow_fleet_dev
+int dimitrov_follow_launch(wg_ctx *ctx, const wg_dimitrov_fleet_t *fl, int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count, int lcap, const double *time, const int *have, const wg_zmpdisc_state_t *walk, int flags, double *clock, int *ticks, int tick_cap, int max_ticks, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int *ran_out, int max_iter, void *hip_stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  const int N = fl ? fl->N : ctx->dim_host->N;
+  const double T = fl ? fl->T : ctx->dim_host->T;
+  std::lock_guard<std::mutex> launch_lk(ctx->launch_mu);
+  if (int rc = slot_claim(ctx, ctx->walk_order, st, "Dimitrov walk")) return rc;
+  Arena a(ctx->walk_polys);
+  const auto sp = a.take<wg_zmp_polytope_t>((size_t)B * (size_t)N);
+  const auto sr = a.take<int>((size_t)B);
+  if (int rc = a.reserve()) return rc;
+  for (int k = 0; k < max_ticks; k++) {
+    hipLaunchKernelGGL(wg::wg_dimitrov_follow_select_kernel, dim3((B + 3) / 4), dim3(256), 0, st, B, qcap, queues, t_start, t_end, count,
+                       lcap, time, have, walk, flags & WG_DIMITROV_FOLLOW_ALL_FINAL, clock, ticks, tick_cap, N, T, a(sp), ran_out, a(sr));
+    HIP_TRY(hipGetLastError());
+    if (int rc = dimitrov_tick_launch(ctx, B, a(sp), states, outs, max_iter, st, a(sr), fl)) return rc;
+  }
+  return slot_mark(ctx->walk_order, st);
+}
+int follow_args_check(int lcap, const double *time, const int *have, int flags, const double *clock, const int *ticks, int tick_cap, int max_ticks, const wg_dimitrov_state_t *states) {
+  if (lcap < 1 || tick_cap < 0 || max_ticks < 0 || !time || !have || !clock || !ticks || !states)
+    return fail(WG_ERR_BAD_ARG, "need lcap >= 1, tick_cap >= 0, max_ticks >= 0, non-null time, have, clock, ticks and states");
+  if (flags & ~WG_DIMITROV_FOLLOW_ALL_FINAL) return fail(WG_ERR_BAD_ARG, "flags = %#x: WG_DIMITROV_FOLLOW_ALL_FINAL (1) is the only flag", flags);
+  return WG_OK;
 }
 
 // What wg_foot_constraints_batch_dev (res = false: first_sample 0, no done) and _append_dev (res = true) share: the checks, the
@@ -1360,7 +1425,7 @@ int wg_dimitrov_select_polys_dev_ctx(wg_ctx_t *ctx, int B, int qcap, const wg_zm
   if (B == 0) return WG_OK;
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
   std::lock_guard<std::mutex> launch_lk(ctx->launch_mu);
-  select_launch(ctx, B, qcap, queues, t_start, t_end, count, t0, polys, ran_out, 0, st);
+  select_launch(ctx->dim_host->N, ctx->dim_host->T, B, qcap, queues, t_start, t_end, count, t0, polys, ran_out, 0, st);
   HIP_TRY(hipGetLastError());
   return slot_mark(ctx->aux_order, st);                   // N and T are the configured model's: a re-configuration waits for it
 }
@@ -1369,24 +1434,7 @@ int wg_dimitrov_walk_dev_ctx(wg_ctx_t *ctx, int B, int qcap, const wg_zmp_polyto
   if (int rc = select_check(ctx, B, qcap, queues, t_start, t_end, count)) return rc;
   if (n_ticks < 0 || !states) return fail(WG_ERR_BAD_ARG, "need n_ticks >= 0 and non-null states");
   if (B == 0 || n_ticks == 0) return WG_OK;
-  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  const size_t N = (size_t)ctx->dim_host->N;
-  const double T = ctx->dim_host->T;
-  std::lock_guard<std::mutex> launch_lk(ctx->launch_mu);
-  // the selected polytopes live in a buffer of the context, rewritten tick by tick: behind the previous walk, whatever stream
-  // that was on; growing retires the old allocation, which a launch in flight may still be reading (DevBuf)
-  if (int rc = slot_claim(ctx, ctx->walk_order, st, "Dimitrov walk")) return rc;
-  if (int rc = ctx->walk_polys.reserve((size_t)B * N * sizeof(wg_zmp_polytope_t))) return rc;
-  wg_zmp_polytope_t *polys = static_cast<wg_zmp_polytope_t *>(ctx->walk_polys.p);
-  if (ran_out) HIP_TRY(hipMemsetAsync(ran_out, 0, (size_t)B * sizeof(int), st));
-  double t = t0;
-  for (int k = 0; k < n_ticks; k++) {
-    select_launch(ctx, B, qcap, queues, t_start, t_end, count, t, polys, ran_out, 1, st);
-    HIP_TRY(hipGetLastError());
-    if (int rc = dimitrov_tick_launch(ctx, B, polys, states, outs ? outs + (size_t)k * (size_t)B : nullptr, max_iter, st)) return rc;
-    t += T;                                               // BuildZMPTrajectoryFromFootTrajectory's own accumulation (:1189-1192)
-  }
-  return slot_mark(ctx->walk_order, st);
+  return dimitrov_walk_launch(ctx, nullptr, B, qcap, queues, t_start, t_end, count, t0, n_ticks, states, outs, ran_out, max_iter, hip_stream);
 }
 
 // The walk with a clock and a tick count per gait: max_ticks rounds of { follow select, follow tick }.  The select launch decides,
@@ -1394,26 +1442,9 @@ int wg_dimitrov_walk_dev_ctx(wg_ctx_t *ctx, int B, int qcap, const wg_zmp_polyto
 // int per gait behind the selected polytopes -- the context's walk buffer, claimed and marked like a walk's.
 int wg_dimitrov_follow_dev_ctx(wg_ctx_t *ctx, int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count, int lcap, const double *time, const int *have, const wg_zmpdisc_state_t *walk, int flags, double *clock, int *ticks, int tick_cap, int max_ticks, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int *ran_out, int max_iter, void *hip_stream) {
   if (int rc = select_check(ctx, B, qcap, queues, t_start, t_end, count)) return rc;
-  if (lcap < 1 || tick_cap < 0 || max_ticks < 0 || !time || !have || !clock || !ticks || !states)
-    return fail(WG_ERR_BAD_ARG, "need lcap >= 1, tick_cap >= 0, max_ticks >= 0, non-null time, have, clock, ticks and states");
-  if (flags & ~WG_DIMITROV_FOLLOW_ALL_FINAL) return fail(WG_ERR_BAD_ARG, "flags = %#x: WG_DIMITROV_FOLLOW_ALL_FINAL (1) is the only flag", flags);
+  if (int rc = follow_args_check(lcap, time, have, flags, clock, ticks, tick_cap, max_ticks, states)) return rc;
   if (B == 0 || max_ticks == 0) return WG_OK;
-  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  const int N = ctx->dim_host->N;
-  const double T = ctx->dim_host->T;
-  std::lock_guard<std::mutex> launch_lk(ctx->launch_mu);
-  if (int rc = slot_claim(ctx, ctx->walk_order, st, "Dimitrov walk")) return rc;
-  Arena a(ctx->walk_polys);
-  const auto sp = a.take<wg_zmp_polytope_t>((size_t)B * (size_t)N);
-  const auto sr = a.take<int>((size_t)B);
-  if (int rc = a.reserve()) return rc;
-  for (int k = 0; k < max_ticks; k++) {
-    hipLaunchKernelGGL(wg::wg_dimitrov_follow_select_kernel, dim3((B + 3) / 4), dim3(256), 0, st, B, qcap, queues, t_start, t_end, count,
-                       lcap, time, have, walk, flags & WG_DIMITROV_FOLLOW_ALL_FINAL, clock, ticks, tick_cap, N, T, a(sp), ran_out, a(sr));
-    HIP_TRY(hipGetLastError());
-    if (int rc = dimitrov_tick_launch(ctx, B, a(sp), states, outs, max_iter, st, a(sr))) return rc;
-  }
-  return slot_mark(ctx->walk_order, st);
+  return dimitrov_follow_launch(ctx, nullptr, B, qcap, queues, t_start, t_end, count, lcap, time, have, walk, flags, clock, ticks, tick_cap, max_ticks, states, outs, ran_out, max_iter, hip_stream);
 }
 
 // the clock of wg_dimitrov_walk_dev_ctx above, on the host: the same repeated addition of the configured T
@@ -1436,6 +1467,142 @@ int wg_dimitrov_walk_safe_ticks_ctx(wg_ctx_t *ctx, double t0, double t_have) {
   int n = 0;
   for (double t = t0; n < INT_MAX && t + i * T <= t_have; t += T) n++;       // the select kernel's t0 + i * T at its last instant
   return n;
+}
+
+}  // extern "C"
+
+// ---- Dimitrov fleets with a model per gait: the constants as blocks, made on the host or on the device; the fleet launches ----
+
+namespace {
+int dimitrov_base_check(int N, int solver, double T) {
+  if (N < 1 || N > WG_PLDP_N) return fail(WG_ERR_BAD_ARG, "N=%d outside [1,%d]", N, WG_PLDP_N);
+  if (solver != WG_DIMITROV_PLDP && solver != WG_DIMITROV_QLD && solver != WG_DIMITROV_QLDANDLQ)
+    return fail(WG_ERR_BAD_ARG, "solver = %d: WG_DIMITROV_PLDP (0), WG_DIMITROV_QLD (1) or WG_DIMITROV_QLDANDLQ (2)", solver);
+  if (!(T > 0.0) || !std::isfinite(T)) return fail(WG_ERR_BAD_ARG, "need a finite T > 0");
+  return WG_OK;
+}
+int dimitrov_constants_batch_check(int M, const wg_dimitrov_model_t *base, const void *blocks, const int *status) {
+  if (M < 1 || !base || !blocks || !status) return fail(WG_ERR_BAD_ARG, "need M >= 1, non-null base, blocks and status");
+  return dimitrov_base_check(base->N, base->solver, base->T);
+}
+int dimitrov_fleet_check(int B, const wg_dimitrov_fleet_t *fl) {
+  if (!fl) return fail(WG_ERR_BAD_ARG, "null fleet");
+  if (B < 0 || fl->M < 1 || !fl->blocks || !fl->model_of) return fail(WG_ERR_BAD_ARG, "need B >= 0, fleet M >= 1, non-null fleet blocks and model_of");
+  return dimitrov_base_check(fl->N, fl->solver, fl->T);
+}
+// the fleet calls refuse their arguments before a context (and with it the device) is looked for
+int dimitrov_tick_fleet_check(int B, const wg_dimitrov_fleet_t *fl, const wg_zmp_polytope_t *polys, const wg_dimitrov_state_t *states) {
+  if (int rc = dimitrov_fleet_check(B, fl)) return rc;
+  if (!polys || !states) return fail(WG_ERR_BAD_ARG, "need non-null polys and states");
+  return WG_OK;
+}
+int dimitrov_walk_fleet_check(int B, const wg_dimitrov_fleet_t *fl, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count, int n_ticks, const wg_dimitrov_state_t *states) {
+  if (int rc = dimitrov_fleet_check(B, fl)) return rc;
+  if (int rc = queue_check(B, qcap, queues, t_start, t_end, count)) return rc;
+  if (n_ticks < 0 || !states) return fail(WG_ERR_BAD_ARG, "need n_ticks >= 0 and non-null states");
+  return WG_OK;
+}
+int dimitrov_follow_fleet_check(int B, const wg_dimitrov_fleet_t *fl, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count, int lcap, const double *time, const int *have, int flags, const double *clock, const int *ticks, int tick_cap, int max_ticks, const wg_dimitrov_state_t *states) {
+  if (int rc = dimitrov_fleet_check(B, fl)) return rc;
+  if (int rc = queue_check(B, qcap, queues, t_start, t_end, count)) return rc;
+  return follow_args_check(lcap, time, have, flags, clock, ticks, tick_cap, max_ticks, states);
+}
+}  // namespace
+
+extern "C" {
+
+size_t wg_dimitrov_constants_bytes(void) { return wg::kDimitrovBlockBytes; }
+
+// host arithmetic (wg_dimitrov_math.hpp through DimitrovHost::build, as wg_dimitrov_configure runs it); no device call
+int wg_dimitrov_constants(const wg_dimitrov_model_t *model, void *block) {
+  if (!block) return fail(WG_ERR_BAD_ARG, "null block");
+  memset(block, 0, wg::kDimitrovBlockBytes);
+  if (!model) return fail(WG_ERR_BAD_ARG, "null model");
+  if (int rc = dimitrov_base_check(model->N, model->solver, model->T)) return rc;
+  std::unique_ptr<wg::DimitrovConst> K(new wg::DimitrovConst);
+  if (!wg::DimitrovHost::build(*model, *K))
+    return fail(WG_ERR_BAD_ARG, "a height or weight is not finite, or the LQ factor or the inverse of Pu does not exist for this model");
+  memcpy(block, K.get(), sizeof *K);
+  return WG_OK;
+}
+
+int wg_dimitrov_constants_unpack(const void *block, wg_dimitrov_model_t *model, double *iLQ, double *OptB, double *OptC, double *Pu, double *iPu, double *Px, double *Q, double *OptBq, double *OptCq, double *PuT, double *iPuPx) {
+  if (!block) return fail(WG_ERR_BAD_ARG, "null block");
+  const wg::DimitrovConst &K = *static_cast<const wg::DimitrovConst *>(block);
+  if (K.N < 1 || K.N > WG_PLDP_N) return fail(WG_ERR_BAD_ARG, "not a block of a model that exists (N = %d)", K.N);
+  const size_t N = (size_t)K.N, n = 2 * N;
+  if (model) {                                           // the weights are not kept in a block: reported as zeros
+    memset(model, 0, sizeof *model);
+    model->N = K.N; model->solver = K.solver; model->T = K.T; model->Tctrl = K.Tctrl; model->com_height = K.h;
+  }
+  if (iLQ) memcpy(iLQ, K.iLQ, 8 * n * n);
+  if (OptB) memcpy(OptB, K.OptB, 8 * n * 6);
+  if (OptC) memcpy(OptC, K.OptC, 8 * n * n);
+  if (Pu) memcpy(Pu, K.pldp.Pu, 8 * N * N);
+  if (iPu) memcpy(iPu, K.pldp.iPu, 8 * N * N);
+  if (Px) memcpy(Px, K.pldp.Px, 8 * N * 3);
+  if (Q) memcpy(Q, K.Qq, 8 * n * n);
+  if (OptBq) memcpy(OptBq, K.OptBq, 8 * n * 6);
+  if (OptCq) memcpy(OptCq, K.OptCq, 8 * n * n);
+  if (PuT) memcpy(PuT, K.PuTq, 8 * N * N);
+  if (iPuPx) memcpy(iPuPx, K.pldp.iPuPx, 8 * n * 6);
+  return WG_OK;
+}
+
+// one wave per model (wg_dimitrov_kernels.hpp); the host twin is wg_dimitrov_constants, the arithmetic wg_dimitrov_math.hpp
+int wg_dimitrov_constants_batch_dev_ctx(wg_ctx_t *ctx, int M, const wg_dimitrov_model_t *base, const double *com_height, const double *alpha, const double *beta, void *blocks, int *status, void *hip_stream) {
+  if (int rc = dimitrov_constants_batch_check(M, base, blocks, status)) return rc;
+  if (int rc = use_ctx(ctx)) return rc;
+  hipLaunchKernelGGL(wg_dimitrov_constants_kernel, dim3((M + kDimConstWaves - 1) / kDimConstWaves), dim3(64 * kDimConstWaves), 0,
+                     reinterpret_cast<hipStream_t>(hip_stream), M, *base, com_height, alpha, beta, static_cast<unsigned char *>(blocks), status);
+  HIP_TRY(hipGetLastError());
+  return WG_OK;
+}
+
+// host pointers
+int wg_dimitrov_constants_batch_ctx(wg_ctx_t *ctx, int M, const wg_dimitrov_model_t *base, const double *com_height, const double *alpha, const double *beta, void *blocks, int *status) {
+  if (int rc = dimitrov_constants_batch_check(M, base, blocks, status)) return rc;
+  if (int rc = use_ctx(ctx)) return rc;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HostScope hs(ctx);
+  const size_t sM = (size_t)M;
+  Arena a(ctx->dim_buf);
+  const auto sh = a.take<double>(com_height ? sM : 0), sa = a.take<double>(alpha ? sM : 0), sb = a.take<double>(beta ? sM : 0);
+  const auto sk = a.take<unsigned char>(sM * wg::kDimitrovBlockBytes);
+  const auto ss = a.take<int>(sM);
+  if (int rc = a.reserve()) return rc;
+  if (com_height) WG_H2D(a(sh), com_height, sh.bytes());
+  if (alpha) WG_H2D(a(sa), alpha, sa.bytes());
+  if (beta) WG_H2D(a(sb), beta, sb.bytes());
+  if (int rc = wg_dimitrov_constants_batch_dev_ctx(ctx, M, base, com_height ? a(sh) : nullptr, alpha ? a(sa) : nullptr, beta ? a(sb) : nullptr, a(sk), a(ss), hs.stream())) return rc;
+  WG_D2H(blocks, a(sk), sk.bytes());
+  WG_D2H(status, a(ss), ss.bytes());
+  WG_HOST_WAIT();
+  return WG_OK;
+}
+
+// the launches of wg_dimitrov_tick_batch_dev, wg_dimitrov_walk_dev and wg_dimitrov_follow_dev with blocks[model_of[g]] as gait g's
+// model: the same launcher code, the context's buffers and orders; nothing of the context's configured model is read
+int wg_dimitrov_tick_fleet_dev_ctx(wg_ctx_t *ctx, int B, const wg_dimitrov_fleet_t *fleet, const wg_zmp_polytope_t *polys, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int max_iter, void *hip_stream) {
+  if (int rc = dimitrov_tick_fleet_check(B, fleet, polys, states)) return rc;
+  if (int rc = use_ctx(ctx)) return rc;
+  if (B == 0) return WG_OK;
+  std::lock_guard<std::mutex> launch_lk(ctx->launch_mu);
+  return dimitrov_tick_launch(ctx, B, polys, states, outs, max_iter, reinterpret_cast<hipStream_t>(hip_stream), nullptr, fleet);
+}
+
+int wg_dimitrov_walk_fleet_dev_ctx(wg_ctx_t *ctx, int B, const wg_dimitrov_fleet_t *fleet, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count, double t0, int n_ticks, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int *ran_out, int max_iter, void *hip_stream) {
+  if (int rc = dimitrov_walk_fleet_check(B, fleet, qcap, queues, t_start, t_end, count, n_ticks, states)) return rc;
+  if (int rc = use_ctx(ctx)) return rc;
+  if (B == 0 || n_ticks == 0) return WG_OK;
+  return dimitrov_walk_launch(ctx, fleet, B, qcap, queues, t_start, t_end, count, t0, n_ticks, states, outs, ran_out, max_iter, hip_stream);
+}
+
+int wg_dimitrov_follow_fleet_dev_ctx(wg_ctx_t *ctx, int B, const wg_dimitrov_fleet_t *fleet, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count, int lcap, const double *time, const int *have, const wg_zmpdisc_state_t *walk, int flags, double *clock, int *ticks, int tick_cap, int max_ticks, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int *ran_out, int max_iter, void *hip_stream) {
+  if (int rc = dimitrov_follow_fleet_check(B, fleet, qcap, queues, t_start, t_end, count, lcap, time, have, flags, clock, ticks, tick_cap, max_ticks, states)) return rc;
+  if (int rc = use_ctx(ctx)) return rc;
+  if (B == 0 || max_ticks == 0) return WG_OK;
+  return dimitrov_follow_launch(ctx, fleet, B, qcap, queues, t_start, t_end, count, lcap, time, have, walk, flags, clock, ticks, tick_cap, max_ticks, states, outs, ran_out, max_iter, hip_stream);
 }
 
 }  // extern "C"
@@ -2038,6 +2205,26 @@ int wg_preview_run_fleet_dev(int B, int L, const wg_preview_fleet_t *fleet, cons
 int wg_preview_follow_fleet_dev(int B, int lcap, const int *length, int *done, const wg_preview_fleet_t *fleet, const double *zmp_x_tm, const double *zmp_y_tm, double *state, double *com_tm, double *zmp2_tm, int simulation, void *hip_stream) {
   if (int rc = preview_follow_fleet_check(B, lcap, length, done, fleet, zmp_x_tm, zmp_y_tm, state)) return rc;
   return on_default(&wg_preview_follow_fleet_dev_ctx, B, lcap, length, done, fleet, zmp_x_tm, zmp_y_tm, state, com_tm, zmp2_tm, simulation, hip_stream);
+}
+int wg_dimitrov_constants_batch_dev(int M, const wg_dimitrov_model_t *base, const double *com_height, const double *alpha, const double *beta, void *blocks, int *status, void *hip_stream) {
+  if (int rc = dimitrov_constants_batch_check(M, base, blocks, status)) return rc;
+  return on_default(&wg_dimitrov_constants_batch_dev_ctx, M, base, com_height, alpha, beta, blocks, status, hip_stream);
+}
+int wg_dimitrov_constants_batch(int M, const wg_dimitrov_model_t *base, const double *com_height, const double *alpha, const double *beta, void *blocks, int *status) {
+  if (int rc = dimitrov_constants_batch_check(M, base, blocks, status)) return rc;
+  return on_default(&wg_dimitrov_constants_batch_ctx, M, base, com_height, alpha, beta, blocks, status);
+}
+int wg_dimitrov_tick_fleet_dev(int B, const wg_dimitrov_fleet_t *fleet, const wg_zmp_polytope_t *polys, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int max_iter, void *hip_stream) {
+  if (int rc = dimitrov_tick_fleet_check(B, fleet, polys, states)) return rc;
+  return on_default(&wg_dimitrov_tick_fleet_dev_ctx, B, fleet, polys, states, outs, max_iter, hip_stream);
+}
+int wg_dimitrov_walk_fleet_dev(int B, const wg_dimitrov_fleet_t *fleet, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count, double t0, int n_ticks, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int *ran_out, int max_iter, void *hip_stream) {
+  if (int rc = dimitrov_walk_fleet_check(B, fleet, qcap, queues, t_start, t_end, count, n_ticks, states)) return rc;
+  return on_default(&wg_dimitrov_walk_fleet_dev_ctx, B, fleet, qcap, queues, t_start, t_end, count, t0, n_ticks, states, outs, ran_out, max_iter, hip_stream);
+}
+int wg_dimitrov_follow_fleet_dev(int B, const wg_dimitrov_fleet_t *fleet, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count, int lcap, const double *time, const int *have, const wg_zmpdisc_state_t *walk, int flags, double *clock, int *ticks, int tick_cap, int max_ticks, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int *ran_out, int max_iter, void *hip_stream) {
+  if (int rc = dimitrov_follow_fleet_check(B, fleet, qcap, queues, t_start, t_end, count, lcap, time, have, flags, clock, ticks, tick_cap, max_ticks, states)) return rc;
+  return on_default(&wg_dimitrov_follow_fleet_dev_ctx, B, fleet, qcap, queues, t_start, t_end, count, lcap, time, have, walk, flags, clock, ticks, tick_cap, max_ticks, states, outs, ran_out, max_iter, hip_stream);
 }
 int wg_gramian_batch_dev(int B, int N, const double *T, const double *h, double alpha, double beta, double gamma, int precision, double *Qb, void *hip_stream) { return on_default(&wg_gramian_batch_dev_ctx, B, N, T, h, alpha, beta, gamma, precision, Qb, hip_stream); }
 int wg_gramian_batch(int B, int N, const double *T, const double *h, double alpha, double beta, double gamma, int precision, double *Qb) { return on_default(&wg_gramian_batch_ctx, B, N, T, h, alpha, beta, gamma, precision, Qb); }

@@ -4,6 +4,9 @@
 // src/PreviewControl/LinearizedInvertedPendulum2D.cpp:157-264 with the same operation order; lanes run over
 // independent outputs only.
 #pragma once
+#include <memory>
+
+#include "wg_dimitrov_math.hpp"
 #include "wg_pldp_device.hpp"
 
 namespace wg {
@@ -19,136 +22,16 @@ struct DimitrovConst {           // device-resident (wg_dimitrov_configure)
   double Qq[2 * WG_PLDP_N * 2 * WG_PLDP_N], OptBq[2 * WG_PLDP_N * 6], OptCq[2 * WG_PLDP_N * 2 * WG_PLDP_N], PuTq[WG_PLDP_N * WG_PLDP_N];
 };
 
-// host: the constants of InitConstants (ZMPConstrainedQPFastFormulation.cpp:158-246, 384-560, 597-690), row-major.
-// Matrix products are plain i-j-k loops with k ascending (what ublas prod does on dense matrices).
+// one model's block of wg_dimitrov_constants*: a DimitrovConst and zeros up to a multiple of 128 bytes
+constexpr size_t kDimitrovBlockBytes = (sizeof(DimitrovConst) + 127) & ~(size_t)127;
+
+// host: the constants of InitConstants (ZMPConstrainedQPFastFormulation.cpp:158-246, 384-560, 597-690), row-major -- the text of
+// wg_dimitrov_math.hpp run by one lane
 struct DimitrovHost {
-  static void matmul(const double *A, const double *B, double *C, int r, int inner, int c) {
-    for (int i = 0; i < r; i++)
-      for (int j = 0; j < c; j++) {
-        double s = 0.0;
-        for (int k = 0; k < inner; k++) s += A[i * inner + k] * B[k * c + j];
-        C[i * c + j] = s;
-      }
-  }
-  // false if the LQ factor or the inverse of Pu does not exist
+  // false, with K as it was, if a height or weight is not finite or the LQ factor or the inverse of Pu does not exist
   static bool build(const wg_dimitrov_model_t &m, DimitrovConst &K) {
-    const unsigned N = (unsigned)m.N, n = 2 * N;
-    const double T = m.T;
-    std::vector<double> PPu(n * n, 0.0), VPu(n * n, 0.0), PPx(n * 6, 0.0), VPx(n * 6, 0.0), Px(N * 3);
-    for (unsigned i = 0; i < N; i++) {                                 // :165-211
-      VPx[i * 6 + 1] = 1.0; VPx[i * 6 + 2] = (i + 1) * T;
-      VPx[(i + N) * 6 + 4] = 1.0; VPx[(i + N) * 6 + 5] = (i + 1) * T;
-      PPx[i * 6 + 0] = 1.0; PPx[i * 6 + 1] = (i + 1) * T; PPx[i * 6 + 2] = (i + 1) * (i + 1) * T * T * 0.5;
-      PPx[(i + N) * 6 + 3] = 1.0; PPx[(i + N) * 6 + 4] = (i + 1) * T; PPx[(i + N) * 6 + 5] = (i + 1) * (i + 1) * T * T * 0.5;
-      for (unsigned j = 0; j <= i; j++) {
-        const double v = (2 * (i - j) + 1) * T * T * 0.5;
-        const double p = (1 + 3 * (i - j) + 3 * (i - j) * (i - j)) * T * T * T / 6.0;
-        VPu[i * n + j] = v; VPu[(i + N) * n + j + N] = v;
-        PPu[i * n + j] = p; PPu[(i + N) * n + j + N] = p;
-      }
-    }
-    for (unsigned li = 0; li < N; li++) {                              // :214-220
-      Px[li * 3 + 0] = 1.0;
-      Px[li * 3 + 1] = (double)(1.0 + li) * T;
-      Px[li * 3 + 2] = (li + 1.0) * (li + 1.0) * T * T * 0.5 - m.com_height / 9.81;
-    }
-    auto transpose = [](const std::vector<double> &A, int r, int c) {
-      std::vector<double> t((size_t)r * c);
-      for (int i = 0; i < r; i++) for (int j = 0; j < c; j++) t[(size_t)j * r + i] = A[(size_t)i * c + j];
-      return t;
-    };
-    const std::vector<double> PPuT = transpose(PPu, n, n), VPuT = transpose(VPu, n, n);
-    // OptA = Id + beta PPu'PPu + alpha VPu'   (the reference scales VPu', not VPu'VPu: :524-527)
-    std::vector<double> tmp(n * n), OptA(n * n);
-    matmul(PPuT.data(), PPu.data(), tmp.data(), n, n, n);
-    for (unsigned i = 0; i < n; i++)
-      for (unsigned j = 0; j < n; j++)
-        OptA[i * n + j] = ((i == j ? 1.0 : 0.0) + m.beta * tmp[i * n + j]) + m.alpha * VPuT[i * n + j];
-    // linear part: OptB = alpha VPu'VPx + beta PPu'PPx ; OptC = beta PPu'   (:545-556)
-    std::vector<double> l1(n * 6), OptB(n * 6), OptC(n * n);
-    matmul(PPuT.data(), PPx.data(), l1.data(), n, n, 6);
-    matmul(VPuT.data(), VPx.data(), OptB.data(), n, n, 6);
-    for (unsigned i = 0; i < n * 6; i++) OptB[i] = m.alpha * OptB[i] + m.beta * l1[i];
-    for (unsigned i = 0; i < n * n; i++) OptC[i] = m.beta * PPuT[i];
-    // LQ factor of the leading N x N block and its inverse, OptCholesky::ComputeNormalCholeskyOnANormal /
-    // ComputeInverseCholeskyNormal (OptCholesky.cpp:225-302): only the lower triangle of OptA is read  (:384-420)
-    std::vector<double> LQ(N * N, 0.0), iLQ1(N * N, 0.0);
-    for (unsigned li = 0; li < N; li++)
-      for (unsigned lj = 0; lj <= li; lj++) {
-        double r = OptA[li * n + lj];
-        for (unsigned lk = 0; lk < lj; lk++) r = r - LQ[li * N + lk] * LQ[lj * N + lk];
-        if (lj != li) LQ[li * N + lj] = r / LQ[lj * N + lj];
-        else { if (!(r > 0.0)) return false; LQ[li * N + lj] = sqrt(r); }
-      }
-    for (int lj = (int)N - 1; lj >= 0; lj--) {
-      const double d = 1 / LQ[lj * N + lj];
-      iLQ1[lj * N + lj] = d;
-      for (int li = lj + 1; li < (int)N; li++) {
-        double r = 0.0;
-        for (int lk = lj + 1; lk < (int)N; lk++) r = r + iLQ1[li * N + lk] * LQ[lk * N + lj];
-        iLQ1[li * N + lj] = -d * r;
-      }
-    }
-    std::vector<double> iLQ(n * n, 0.0);                               // :448-461
-    for (unsigned i = 0; i < N; i++)
-      for (unsigned j = 0; j < N; j++) { iLQ[i * n + j] = iLQ1[i * N + j]; iLQ[(i + N) * n + j + N] = iLQ1[i * N + j]; }
-    std::vector<double> OptB2(n * 6), OptC2(n * n);                    // :464-467
-    matmul(iLQ.data(), OptB.data(), OptB2.data(), n, n, 6);
-    matmul(iLQ.data(), OptC.data(), OptC2.data(), n, n, n);
-    // constraint side: Pu' (transposed storage), m_Pu = iLQ Pu', iPu = inverse  (:597-690)
-    std::vector<double> PuT(N * N, 0.0), Pu(N * N), iPu(N * N);
-    for (unsigned i = 0; i < N; i++)
-      for (unsigned k = 0; k <= i; k++)
-        PuT[k * N + i] = ((1 + 3 * (i - k) + 3 * (i - k) * (i - k)) * T * T * T / 6.0 - T * m.com_height / 9.81);
-    for (unsigned i = 0; i < N; i++)
-      for (unsigned j = 0; j < N; j++) {
-        double s = 0;
-        for (unsigned k = 0; k < N; k++) s += iLQ[i * n + k] * PuT[k * N + j];
-        Pu[i * N + j] = s;
-      }
-    {  // MAL_INVERSE (jrl-mal -> LAPACK, unpinned): Gauss-Jordan with partial pivoting
-      std::vector<double> a(Pu), inv(N * N, 0.0);
-      for (unsigned i = 0; i < N; i++) inv[i * N + i] = 1.0;
-      for (unsigned c = 0; c < N; c++) {
-        unsigned p = c; double best = fabs(a[c * N + c]);
-        for (unsigned r = c + 1; r < N; r++) if (fabs(a[r * N + c]) > best) { best = fabs(a[r * N + c]); p = r; }
-        if (!(best > 0.0)) return false;
-        if (p != c) for (unsigned j = 0; j < N; j++) { std::swap(a[c * N + j], a[p * N + j]); std::swap(inv[c * N + j], inv[p * N + j]); }
-        const double d = a[c * N + c];
-        for (unsigned j = 0; j < N; j++) { a[c * N + j] /= d; inv[c * N + j] /= d; }
-        for (unsigned r = 0; r < N; r++) {
-          if (r == c) continue;
-          const double f = a[r * N + c];
-          if (f == 0.0) continue;
-          for (unsigned j = 0; j < N; j++) { a[r * N + j] -= f * a[c * N + j]; inv[r * N + j] -= f * inv[c * N + j]; }
-        }
-      }
-      iPu = inv;
-    }
-    memset(&K, 0, sizeof K);
-    K.N = (int)N; K.T = T; K.Tctrl = m.Tctrl; K.h = m.com_height; K.solver = m.solver;
-    // mode QLD: BuildingConstantPartOfTheObjectiveFunctionQLD (:382-389) stores m_Q[i 2N + j] = OptA(j, i), which ql0001_ reads as
-    // the column-major matrix C(j, i) = OptA(j, i); OptB / OptC stay as built; Pu' is the raw table
-    for (unsigned i = 0; i < n; i++)
-      for (unsigned j = 0; j < n; j++) K.Qq[i * n + j] = OptA[j * n + i];
-    memcpy(K.OptBq, OptB.data(), sizeof(double) * n * 6);
-    memcpy(K.OptCq, OptC.data(), sizeof(double) * n * n);
-    memcpy(K.PuTq, PuT.data(), sizeof(double) * N * N);
-    memcpy(K.OptB, OptB2.data(), sizeof(double) * n * 6);
-    memcpy(K.OptC, OptC2.data(), sizeof(double) * n * n);
-    memcpy(K.iLQ, iLQ.data(), sizeof(double) * n * n);
-    K.pldp.N = (int)N;
-    memcpy(K.pldp.iPu, iPu.data(), sizeof(double) * N * N);
-    memcpy(K.pldp.Pu, Pu.data(), sizeof(double) * N * N);
-    memcpy(K.pldp.Px, Px.data(), sizeof(double) * N * 3);
-    for (unsigned i = 0; i < N; i++)                                   // PLDPSolver::PrecomputeiPuPx
-      for (unsigned j = 0; j < 3; j++) {
-        double s = 0.0;
-        for (unsigned k = 0; k < N; k++) s += iPu[k * N + i] * Px[k * 3 + j];
-        K.pldp.iPuPx[i * 6 + j] = s;
-        K.pldp.iPuPx[(i + N) * 6 + j + 3] = s;
-      }
-    return true;
+    std::unique_ptr<DmWork> W(new DmWork);
+    return dm_build(DmHostExec{}, m, *W, K);
   }
 };
 

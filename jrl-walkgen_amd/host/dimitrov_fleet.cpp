@@ -24,8 +24,14 @@
 // arc in front of wg_zmpdisc_begin_dev and K commands in front of every wg_zmpdisc_append_dev.  --plan-host is its host-fed twin:
 // the same lists through wg_steps_plan and the upload path.  Both print the same checksum.
 //
+// With --heights LO:HI gait g walks at its own CoM height, h = LO + (HI - LO) g / (B - 1): a model per gait.  The constants are made
+// on the device (wg_dimitrov_constants_batch_dev on the walk's stream, in front of every pass) and every walk or follow call is
+// its fleet form (wg_dimitrov_walk_fleet_dev / wg_dimitrov_follow_fleet_dev, model_of[g] = g), in every mode above.  The program
+// checks every model's status and holds gaits 0 and B - 1 to a context configured with their own model: one wg_dimitrov_walk_dev
+// over the gait's final queue.  LO = HI = 0.80 prints the checksum of the run without the option.
+//
 //   dimitrov_fleet [--batch B] [--steps S] [--ticks K] [--solver 0|1|2] [--fleet FILE] [--online K [--follow]] [--ragged]
-//                  [--plan | --plan-host]
+//                  [--plan | --plan-host] [--heights LO:HI]
 //
 // --fleet FILE runs a fleet somebody else drew instead of the built-in one (tests/test_dimitrov_walk_gpu.py compares the
 // checksum with its own run of the same fleet): int32 B, int32 smax, wg_zmpdisc_model_t, B x smax wg_rel_step_t, B int32
@@ -41,7 +47,8 @@ using wg_fleet::dev_upload;
 
 int main(int argc, char **argv) {
   int B = 4096, S = 8, K = 40, solver = WG_DIMITROV_PLDP, online = 0;
-  bool follow = false, ragged = false;
+  bool follow = false, ragged = false, heights = false;
+  double h_lo = 0.0, h_hi = 0.0;
   int planned = 0;                                            // 1: --plan (steps planned on the device), 2: --plan-host
   const char *fleet = nullptr;
   for (int i = 1; i < argc; ++i) {
@@ -54,6 +61,10 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[i], "--ragged")) ragged = true;
     else if (!strcmp(argv[i], "--plan")) planned = 1;
     else if (!strcmp(argv[i], "--plan-host")) planned = 2;
+    else if (!strcmp(argv[i], "--heights") && i + 1 < argc) {
+      heights = sscanf(argv[++i], "%lf:%lf", &h_lo, &h_hi) == 2;
+      if (!heights || !(h_lo > 0.0) || !(h_hi >= h_lo) || !(h_hi < 1e3)) { fprintf(stderr, "FAILED: need --heights LO:HI with 0 < LO <= HI\n"); return 1; }
+    }
     else if (!strcmp(argv[i], "--online") && i + 1 < argc) { online = atoi(argv[++i]); if (online < 1 || online > WG_ZMPDISC_MAX_STEPS) { fprintf(stderr, "FAILED: need 1 <= --online K <= %d\n", WG_ZMPDISC_MAX_STEPS); return 1; } }
   }
   if (follow && !online) { fprintf(stderr, "FAILED: --follow needs --online K\n"); return 1; }
@@ -154,6 +165,24 @@ int main(int argc, char **argv) {
   CHECK_HIP(dev_alloc(&d_te, nq));
   CHECK_HIP(dev_alloc(&d_queues, nq));
   CHECK_HIP(dev_alloc(&d_states, B));
+  // --heights: a model per gait; the blocks and the status are written by the device in front of every pass
+  double *d_h = nullptr; unsigned char *d_blocks = nullptr; int *d_status = nullptr, *d_model_of = nullptr;
+  std::vector<double> h_of(B, dm.com_height);
+  wg_dimitrov_fleet_t dfl{dm.N, dm.solver, B, 0, dm.T, dm.Tctrl, nullptr, nullptr};
+  if (heights) {
+    std::vector<int> ident(B);
+    for (int g = 0; g < B; ++g) { h_of[g] = B > 1 ? h_lo + (h_hi - h_lo) * g / (B - 1) : h_lo; ident[g] = g; }
+    CHECK_HIP(dev_upload(&d_h, h_of));
+    CHECK_HIP(dev_upload(&d_model_of, ident));
+    CHECK_HIP(dev_alloc(&d_blocks, (size_t)B * wg_dimitrov_constants_bytes()));
+    CHECK_HIP(dev_alloc(&d_status, B));
+    dfl.blocks = d_blocks; dfl.model_of = d_model_of;
+  }
+  // the walk and follow calls of every mode below: the configured model, or with --heights each gait's own
+  auto walk = [&](double t_, int n_, hipStream_t s_) {
+    return heights ? wg_dimitrov_walk_fleet_dev(B, &dfl, qcap, d_queues, d_ts, d_te, d_count, t_, n_, d_states, nullptr, d_ran, 0, s_)
+                   : wg_dimitrov_walk_dev(B, qcap, d_queues, d_ts, d_te, d_count, t_, n_, d_states, nullptr, d_ran, 0, s_);
+  };
   std::vector<wg_dimitrov_state_t> states(B);
   memset(states.data(), 0, sizeof(wg_dimitrov_state_t) * B);
   for (int g = 0; g < B; ++g) states[g].starting = 1;
@@ -216,6 +245,7 @@ int main(int argc, char **argv) {
   for (int rep = 0; rep < 2; ++rep) {                          // the second pass is the timed one
     CHECK_HIP(hipMemcpyAsync(d_states, states.data(), sizeof(wg_dimitrov_state_t) * B, hipMemcpyHostToDevice, st));
     if (on_device) CHECK_HIP(hipMemcpyAsync(d_stack, fresh.data(), sizeof(wg_step_stack_t) * B, hipMemcpyHostToDevice, st));
+    if (heights) CHECK_WG(wg_dimitrov_constants_batch_dev(B, &dm, d_h, nullptr, nullptr, d_blocks, d_status, st));
     CHECK_HIP(hipStreamSynchronize(st));
     if (online) {
       // what the host knows of the fleet: every gait's samples (cur), which have ended, the samples the queues hold (done)
@@ -243,8 +273,10 @@ int main(int argc, char **argv) {
           if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return WG_ERR_HIP;
           ev.push_back(e0); ev.push_back(e1);
           (void)hipEventRecord(e0, st);
-          if (int rc = wg_dimitrov_follow_dev(B, qcap, d_queues, d_ts, d_te, d_count, lcap, d_time, d_done, d_walk, 0, d_clock, d_ticks,
-                                              K, max_ticks, d_states, nullptr, d_ran, 0, st)) return rc;
+          if (int rc = heights ? wg_dimitrov_follow_fleet_dev(B, &dfl, qcap, d_queues, d_ts, d_te, d_count, lcap, d_time, d_done, d_walk, 0,
+                                                              d_clock, d_ticks, K, max_ticks, d_states, nullptr, d_ran, 0, st)
+                               : wg_dimitrov_follow_dev(B, qcap, d_queues, d_ts, d_te, d_count, lcap, d_time, d_done, d_walk, 0, d_clock, d_ticks,
+                                                        K, max_ticks, d_states, nullptr, d_ran, 0, st)) return rc;
           (void)hipEventRecord(e1, st);
           return WG_OK;
         }
@@ -259,7 +291,7 @@ int main(int argc, char **argv) {
         if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return WG_ERR_HIP;
         ev.push_back(e0); ev.push_back(e1);
         (void)hipEventRecord(e0, st);
-        if (int rc = wg_dimitrov_walk_dev(B, qcap, d_queues, d_ts, d_te, d_count, t, n, d_states, nullptr, d_ran, 0, st)) return rc;
+        if (int rc = walk(t, n, st)) return rc;
         (void)hipEventRecord(e1, st);
         ran_pieces.resize(ran_pieces.size() + B);             // ran_out is cleared by every walk: kept piece by piece, ORed below
         if (hipMemcpyAsync(ran_pieces.data() + ran_pieces.size() - B, d_ran, sizeof(int) * B, hipMemcpyDeviceToHost, st) != hipSuccess) return WG_ERR_HIP;
@@ -329,7 +361,7 @@ int main(int argc, char **argv) {
                                            d_te, d_count, st));
     CHECK_HIP(hipStreamSynchronize(st));
     const auto t1 = std::chrono::steady_clock::now();
-    CHECK_WG(wg_dimitrov_walk_dev(B, qcap, d_queues, d_ts, d_te, d_count, 0.0, K, d_states, nullptr, d_ran, 0, st));
+    CHECK_WG(walk(0.0, K, st));
     CHECK_HIP(hipStreamSynchronize(st));
     const auto t2 = std::chrono::steady_clock::now();
     sec = std::chrono::duration<double>(t2 - t0).count();
@@ -345,6 +377,31 @@ int main(int argc, char **argv) {
     if (count[g] < 1 || count[g] > qcap) { fprintf(stderr, "FAILED: gait %d: %d polytopes (capacity %d)\n", g, count[g], qcap); return 1; }
     n_ran += ran[g];
     max_count = count[g] > max_count ? count[g] : max_count;
+  }
+  if (heights) {
+    std::vector<int> status(B);
+    CHECK_HIP(hipMemcpy(status.data(), d_status, sizeof(int) * B, hipMemcpyDeviceToHost));
+    for (int g = 0; g < B; ++g)
+      if (status[g] != WG_OK) { fprintf(stderr, "FAILED: model %d (height %.4f): status %d\n", g, h_of[g], status[g]); return 1; }
+    // gaits 0 and B - 1 once more, each alone: the default context configured with the gait's own model, one walk over its final queue
+    wg_dimitrov_state_t *d_one;
+    CHECK_HIP(dev_alloc(&d_one, 1));
+    for (int g : {0, B - 1}) {
+      wg_dimitrov_model_t own = dm;
+      own.com_height = h_of[g];
+      CHECK_WG(wg_dimitrov_configure(&own));
+      wg_dimitrov_state_t one;
+      memset(&one, 0, sizeof one);
+      one.starting = 1;
+      CHECK_HIP(hipMemcpy(d_one, &one, sizeof one, hipMemcpyHostToDevice));
+      CHECK_WG(wg_dimitrov_walk_dev(1, qcap, d_queues + (size_t)g * qcap, d_ts + (size_t)g * qcap, d_te + (size_t)g * qcap, d_count + g, 0.0, K,
+                                    d_one, nullptr, nullptr, 0, st));
+      CHECK_HIP(hipStreamSynchronize(st));
+      CHECK_HIP(hipMemcpy(&one, d_one, sizeof one, hipMemcpyDeviceToHost));
+      if (memcmp(&one, &states[g], sizeof one)) { fprintf(stderr, "FAILED: gait %d differs from a context configured with its own model\n", g); return 1; }
+    }
+    printf("dimitrov_fleet: CoM heights %.4f .. %.4f m, the constants of %d models made on the device, all status 0; gaits 0 and %d == a "
+           "context configured with their own model\n", h_lo, h_hi, B, B - 1);
   }
   const uint64_t h = wg_fleet::fnv1a64(states.data(), sizeof(wg_dimitrov_state_t) * B);
   double far = 0.0;

@@ -153,6 +153,18 @@ def lib():
         if hasattr(_lib, "wg_dimitrov_follow_dev"):          # absent from older experiment builds (WG_LIB_PATH, A/B runs)
             _lib.wg_dimitrov_follow_dev.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int] + \
                 [C.c_void_p] * 2 + [C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p]
+        if hasattr(_lib, "wg_dimitrov_constants_batch_dev"):  # absent from older experiment builds (WG_LIB_PATH, A/B runs)
+            _lib.wg_dimitrov_constants_bytes.restype = C.c_size_t
+            _lib.wg_dimitrov_constants_bytes.argtypes = []
+            _lib.wg_dimitrov_constants.argtypes = [C.c_void_p, C.c_void_p]
+            _lib.wg_dimitrov_constants_unpack.argtypes = [C.c_void_p] * 13
+            _lib.wg_dimitrov_constants_batch.argtypes = [C.c_int] + [C.c_void_p] * 6
+            _lib.wg_dimitrov_constants_batch_dev.argtypes = _lib.wg_dimitrov_constants_batch.argtypes + [C.c_void_p]
+            _lib.wg_dimitrov_tick_fleet_dev.argtypes = [C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p]
+            _lib.wg_dimitrov_walk_fleet_dev.argtypes = [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_double, C.c_int] + \
+                [C.c_void_p] * 3 + [C.c_int, C.c_void_p]
+            _lib.wg_dimitrov_follow_fleet_dev.argtypes = [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + \
+                [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 2 + [C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p]
         if hasattr(_lib, "wg_steps_plan_dev"):               # absent from older experiment builds (WG_LIB_PATH, A/B runs)
             _lib.wg_steps_count.argtypes = [C.c_void_p, C.c_int]
             _lib.wg_steps_plan.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
@@ -190,7 +202,8 @@ CTX_ENTRY_POINTS = ("wg_set_overlap_strict", "wg_overlap_serialised", "wg_qp_sol
                     "wg_dimitrov_select_polys_dev", "wg_dimitrov_walk_dev", "wg_foot_constraints_append_dev",
                     "wg_dimitrov_walk_time", "wg_dimitrov_walk_safe_ticks", "wg_preview_follow_dev", "wg_dimitrov_follow_dev",
                     "wg_steps_plan_dev", "wg_riccati_gains_batch", "wg_riccati_gains_batch_dev", "wg_preview_run_fleet_dev",
-                    "wg_preview_follow_fleet_dev")
+                    "wg_preview_follow_fleet_dev", "wg_dimitrov_constants_batch", "wg_dimitrov_constants_batch_dev",
+                    "wg_dimitrov_tick_fleet_dev", "wg_dimitrov_walk_fleet_dev", "wg_dimitrov_follow_fleet_dev")
 
 
 class Context:
@@ -895,6 +908,80 @@ def dimitrov_follow_dev_ctx(ctx, B, qcap, queues_ptr, t_start_ptr, t_end_ptr, co
                                                                       time_ptr, have_ptr, walk_ptr, flags, clock_ptr, ticks_ptr,
                                                                       tick_cap, max_ticks, states_ptr, outs_ptr, ran_out_ptr,
                                                                       max_iter, stream)))
+
+
+# ---- Dimitrov fleets with a model per gait: the constants as blocks, the fleet launches (wg_mpc.h) ----
+class DimitrovFleet(C.Structure):       # wg_dimitrov_fleet_t
+    _fields_ = [("N", C.c_int), ("solver", C.c_int), ("M", C.c_int), ("pad_", C.c_int), ("T", C.c_double), ("Tctrl", C.c_double),
+                ("blocks", C.c_void_p), ("model_of", C.c_void_p)]
+
+
+DIMITROV_BLOCK_ARRAYS = ("iLQ", "OptB", "OptC", "Pu", "iPu", "Px", "Q", "OptBq", "OptCq", "PuT", "iPuPx")
+
+
+def dimitrov_constants_bytes():
+    return int(lib().wg_dimitrov_constants_bytes())
+
+
+def dimitrov_constants_block(model):
+    """(rc, block): the model's block as a uint8 array, made on the host; all zeros when rc != 0"""
+    blk = np.zeros(dimitrov_constants_bytes(), dtype=np.uint8)
+    return int(lib().wg_dimitrov_constants(C.byref(model), _hp(blk))), blk
+
+
+def dimitrov_constants_unpack(block):
+    """the arrays of a host copy of a block, by the names of DIMITROV_BLOCK_ARRAYS, and `model` (N, solver, T, Tctrl, com_height)"""
+    blk = np.ascontiguousarray(block, dtype=np.uint8)
+    N = int(blk[:4].view(np.int32)[0])
+    n = 2 * N
+    shapes = dict(iLQ=(n, n), OptB=(n, 6), OptC=(n, n), Pu=(N, N), iPu=(N, N), Px=(N, 3), Q=(n, n), OptBq=(n, 6), OptCq=(n, n),
+                  PuT=(N, N), iPuPx=(n, 6))
+    out = {k: np.zeros(shapes[k] if N > 0 else (0, 0)) for k in DIMITROV_BLOCK_ARRAYS}
+    m = DimitrovModel()
+    _check(lib().wg_dimitrov_constants_unpack(_hp(blk), C.addressof(m), *[_hp(out[k]) for k in DIMITROV_BLOCK_ARRAYS]))
+    out["model"] = m
+    return out
+
+
+def dimitrov_constants_batch(base, M, com_height=None, alpha=None, beta=None):
+    """(blocks [M][bytes] uint8, status [M]) of M models through the device, host arrays in and out"""
+    arr = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (com_height, alpha, beta)]
+    blocks = np.zeros((M, dimitrov_constants_bytes()), dtype=np.uint8)
+    status = np.zeros(M, dtype=np.int32)
+    _check(lib().wg_dimitrov_constants_batch(int(M), C.byref(base), _hp(arr[0]), _hp(arr[1]), _hp(arr[2]), _hp(blocks), _hp(status)))
+    return blocks, status
+
+
+def dimitrov_constants_batch_dev(M, base, com_height_ptr, alpha_ptr, beta_ptr, blocks_ptr, status_ptr, stream=None):
+    """M blocks and M status ints on the device; a per-model array that is None takes its value from base"""
+    _check(lib().wg_dimitrov_constants_batch_dev(int(M), C.byref(base), com_height_ptr, alpha_ptr, beta_ptr, blocks_ptr, status_ptr,
+                                                 stream))
+
+
+def dimitrov_fleet(base, M, blocks_ptr, model_of_ptr):
+    """the descriptor of the fleet launches: N, solver, T, Tctrl of `base`, M blocks and an int per gait on the device"""
+    return DimitrovFleet(int(base.N), int(base.solver), int(M), 0, float(base.T), float(base.Tctrl), blocks_ptr, model_of_ptr)
+
+
+def dimitrov_tick_fleet_dev(B, fleet, polys_ptr, states_ptr, outs_ptr=None, max_iter=0, stream=None):
+    """dimitrov_tick_batch_dev with blocks[model_of[g]] as gait g's model; no configured model is read"""
+    _check(lib().wg_dimitrov_tick_fleet_dev(int(B), C.byref(fleet), polys_ptr, states_ptr, outs_ptr, int(max_iter), stream))
+
+
+def dimitrov_walk_fleet_dev(B, fleet, qcap, queues_ptr, t_start_ptr, t_end_ptr, count_ptr, t0, n_ticks, states_ptr, outs_ptr=None,
+                            ran_out_ptr=None, max_iter=0, stream=None):
+    """dimitrov_walk_dev with a model per gait"""
+    _check(lib().wg_dimitrov_walk_fleet_dev(int(B), C.byref(fleet), int(qcap), queues_ptr, t_start_ptr, t_end_ptr, count_ptr,
+                                            float(t0), int(n_ticks), states_ptr, outs_ptr, ran_out_ptr, int(max_iter), stream))
+
+
+def dimitrov_follow_fleet_dev(B, fleet, qcap, queues_ptr, t_start_ptr, t_end_ptr, count_ptr, lcap, time_ptr, have_ptr, walk_ptr,
+                              flags, clock_ptr, ticks_ptr, tick_cap, max_ticks, states_ptr, outs_ptr=None, ran_out_ptr=None,
+                              max_iter=0, stream=None):
+    """dimitrov_follow_dev with a model per gait"""
+    a = _dimitrov_follow_args(B, qcap, queues_ptr, t_start_ptr, t_end_ptr, count_ptr, lcap, time_ptr, have_ptr, walk_ptr, flags,
+                              clock_ptr, ticks_ptr, tick_cap, max_ticks, states_ptr, outs_ptr, ran_out_ptr, max_iter, stream)
+    _check(lib().wg_dimitrov_follow_fleet_dev(a[0], C.byref(fleet), *a[1:]))
 
 
 def dimitrov_walk_time(t0, n_ticks):

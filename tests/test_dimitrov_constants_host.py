@@ -1,0 +1,164 @@
+"""The Dimitrov-2008 constants as blocks (wg_dimitrov_constants, wg_dimitrov_constants_unpack), host side.  The arithmetic of
+InitConstants is one text, csrc/wg_dimitrov_math.hpp, which wg_dimitrov_configure, wg_dimitrov_constants and the constants kernel
+share: the host call must still give the bits DimitrovHost::build gave before that text was shared
+(tests/golden/dimitrov_host_bits.npz, recorded by tools/record_dimitrov_host_bits.py from the parent's header), and agree with the
+numpy model of InitConstants.  Runs without a GPU; the kernel is held to the host call in test_dimitrov_constants_gpu.py."""
+import ctypes as C
+import hashlib
+import importlib
+import os
+
+import numpy as np
+
+import dimitrov as dv
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+wg = importlib.import_module("jrl-walkgen_amd")
+
+BAD_ARG = -2
+NEW = ("wg_dimitrov_constants_batch_dev", "wg_dimitrov_constants_batch", "wg_dimitrov_tick_fleet_dev", "wg_dimitrov_walk_fleet_dev",
+       "wg_dimitrov_follow_fleet_dev")
+ARRAYS = wg.DIMITROV_BLOCK_ARRAYS if hasattr(wg, "DIMITROV_BLOCK_ARRAYS") else ()
+
+
+def _model(N, T, Tctrl, h, a, b, solver=0):
+    m = wg.dimitrov_defaults()
+    m.N, m.T, m.Tctrl, m.com_height, m.alpha, m.beta, m.solver = int(N), T, Tctrl, h, a, b, solver
+    return m
+
+
+def test_symbols_and_abi():
+    lib = wg.lib()
+    for name in NEW:
+        assert hasattr(lib, name) and hasattr(lib, name + "_ctx"), name
+        assert name in wg.CTX_ENTRY_POINTS
+    for name in ("wg_dimitrov_constants_bytes", "wg_dimitrov_constants", "wg_dimitrov_constants_unpack"):
+        assert hasattr(lib, name), name
+    assert lib.wg_abi_version() == 5
+    assert C.sizeof(wg.DimitrovFleet) == 48
+    nbytes = wg.dimitrov_constants_bytes()
+    assert nbytes % 128 == 0 and nbytes > 8 * (3 * 32 * 32 + 2 * 32 * 6)
+    hdr = open(os.path.join(ROOT, "include", "wg_mpc.h")).read()
+    assert "typedef struct wg_dimitrov_fleet {" in hdr and "} wg_dimitrov_fleet_t;" in hdr
+
+
+def test_the_fixture_holds_the_models_the_issue_lists():
+    gold = np.load(os.path.join(ROOT, "tests", "golden", "dimitrov_host_bits.npz"))
+    models = [tuple(m) for m in gold["models"]]
+    assert models[0] == (16, 0.1, 0.005, 0.80, 200.0, 1000.0)                     # the defaults
+    want = {(N, T, T / 20, h, a, b) for N in (1, 2, 7, 15, 16) for h in (0.6, 0.8, 0.95)
+            for a, b in ((200.0, 1000.0), (1.0, 1.0), (1e4, 10.0)) for T in (0.05, 0.1)}
+    assert set(models[1:]) == want and len(models) == 91
+    assert gold["ok"].all() and len(gold["full"]) == 3 and gold["sha256"].shape == (91, 11, 32)
+
+
+def test_host_blocks_keep_the_parents_bits():
+    """every array of every model: in full for three models, by sha256 for the rest; in every solver mode (which only labels a block)"""
+    gold = np.load(os.path.join(ROOT, "tests", "golden", "dimitrov_host_bits.npz"))
+    full = [int(i) for i in gold["full"]]
+    for i, row in enumerate(gold["models"]):
+        rc, blk = wg.dimitrov_constants_block(_model(*row, solver=i % 3))
+        assert rc == 0, row
+        K = wg.dimitrov_constants_unpack(blk)
+        assert (K["model"].N, K["model"].solver, K["model"].T, K["model"].Tctrl, K["model"].com_height) == \
+            (int(row[0]), i % 3, row[1], row[2], row[3])
+        for j, name in enumerate(ARRAYS):
+            got = np.ascontiguousarray(K[name], dtype="<f8")
+            assert hashlib.sha256(got.tobytes()).digest() == gold["sha256"][i, j].tobytes(), (row, name)
+            if i in full:
+                assert np.array_equal(got.view(np.uint64), gold["m%d_%s" % (i, name)]), (row, name)
+
+
+def test_blocks_compare_as_bytes_and_pad_with_zeros():
+    m = _model(7, 0.1, 0.005, 0.8, 200.0, 1000.0)
+    junk = np.full(wg.dimitrov_constants_bytes(), 0xA5, dtype=np.uint8)
+    assert wg.lib().wg_dimitrov_constants(C.byref(m), junk.ctypes.data_as(C.c_void_p)) == 0
+    rc, blk = wg.dimitrov_constants_block(m)
+    assert rc == 0 and np.array_equal(junk, blk)                                  # whatever the block held before
+    # NULL pointers are passed over by the unpack call; a full unpack accounts for every non-zero double of the block
+    assert wg.lib().wg_dimitrov_constants_unpack(blk.ctypes.data_as(C.c_void_p), *([None] * 12)) == 0
+    K = wg.dimitrov_constants_unpack(blk)
+    # (behind the block's own 32 bytes of N, solver, T, Tctrl, h; the one word more is the PLDP table's copy of N)
+    assert np.count_nonzero(blk.view(np.float64)[4:]) == sum(np.count_nonzero(K[k]) for k in ARRAYS) + 1
+
+
+def test_constants_match_the_numpy_model():
+    """the tolerance of test_dimitrov_gpu.py::test_constants_match_the_numpy_model_of_initconstants"""
+    for row in ((16, 0.1, 0.005, 0.80, 200.0, 1000.0), (7, 0.05, 0.0025, 0.6, 1.0, 1.0), (15, 0.1, 0.005, 0.95, 1e4, 10.0),
+                (1, 0.1, 0.005, 0.8, 200.0, 1000.0), (2, 0.05, 0.0025, 0.95, 200.0, 1000.0)):
+        rc, blk = wg.dimitrov_constants_block(_model(*row))
+        assert rc == 0
+        K = wg.dimitrov_constants_unpack(blk)
+        N = row[0]
+        dm = dv.Dimitrov(N, row[1], row[3], row[4], row[5])
+        for name, want in (("iLQ", dm.iLQ), ("OptB", dm.OptB), ("OptC", dm.OptC), ("Pu", dm.Pu), ("iPu", dm.iPu), ("Px", dm.Px)):
+            np.testing.assert_allclose(K[name], want, rtol=1e-9, atol=1e-12 * np.abs(want).max(), err_msg="%s %s" % (row, name))
+        ipupx = dm.iPu.T @ dm.Px                                                  # PLDPSolver::PrecomputeiPuPx
+        want = np.zeros((2 * N, 6))
+        want[:N, :3] = ipupx
+        want[N:, 3:] = ipupx
+        np.testing.assert_allclose(K["iPuPx"], want, rtol=1e-9, atol=1e-12 * np.abs(want).max(), err_msg="%s iPuPx" % (row,))
+        assert np.array_equal(K["PuT"], np.triu(K["PuT"])) and np.array_equal(K["Q"].T[:N, :N], K["Q"].T[N:, N:])
+
+
+def test_models_that_do_not_exist_give_bad_arg_and_zeros():
+    nan, inf = float("nan"), float("inf")
+    bad = [dict(com_height=nan), dict(com_height=inf), dict(alpha=nan), dict(beta=-inf), dict(beta=-1e9),      # -1e9: no LQ factor
+           dict(N=0), dict(N=17), dict(solver=3), dict(solver=-1), dict(T=0.0), dict(T=-0.1), dict(T=nan)]
+    for kw in bad:
+        m = wg.dimitrov_defaults()
+        for k, v in kw.items():
+            setattr(m, k, v)
+        junk = np.full(wg.dimitrov_constants_bytes(), 0xA5, dtype=np.uint8)
+        assert wg.lib().wg_dimitrov_constants(C.byref(m), junk.ctypes.data_as(C.c_void_p)) == BAD_ARG, kw
+        assert not junk.any(), kw
+        assert wg.lib().wg_dimitrov_constants_unpack(junk.ctypes.data_as(C.c_void_p), *([None] * 12)) == BAD_ARG, kw
+    assert wg.lib().wg_last_error()
+    assert wg.lib().wg_dimitrov_constants(None, junk.ctypes.data_as(C.c_void_p)) == BAD_ARG
+    assert wg.lib().wg_dimitrov_constants(C.byref(wg.dimitrov_defaults()), None) == BAD_ARG
+    assert wg.lib().wg_dimitrov_constants_unpack(None, *([None] * 12)) == BAD_ARG
+
+
+def test_batch_and_fleet_refusals_need_no_device():
+    """the calls that launch refuse their arguments before a device is looked for (host arrays stand in for device arrays)"""
+    lib = wg.lib()
+    M, B = 3, 4
+    nb = wg.dimitrov_constants_bytes()
+    keep = [np.full(M, 0.8), np.full((M, nb), 0xA5, np.uint8), np.full(M, -77, np.int32), np.zeros(B, np.int32), np.zeros(4096)]
+    p = [k.ctypes.data for k in keep]
+    base = wg.dimitrov_defaults()
+    bad_bases = []
+    for field, value in (("N", 0), ("N", 17), ("solver", 3), ("T", 0.0), ("T", -0.1)):
+        b2 = wg.dimitrov_defaults()
+        setattr(b2, field, value)
+        bad_bases.append(b2)
+    for a in ([0, C.addressof(base), p[0], None, None, p[1], p[2]], [M, None, p[0], None, None, p[1], p[2]],
+              [M, C.addressof(base), p[0], None, None, None, p[2]], [M, C.addressof(base), p[0], None, None, p[1], None]) + \
+            tuple([M, C.addressof(b2), p[0], None, None, p[1], p[2]] for b2 in bad_bases):
+        assert lib.wg_dimitrov_constants_batch_dev(*a, None) == BAD_ARG, a
+        assert lib.wg_dimitrov_constants_batch(*a) == BAD_ARG, a
+        assert lib.wg_dimitrov_constants_batch_dev_ctx(None, *a, None) == BAD_ARG, a
+    fleet = wg.dimitrov_fleet(base, M, p[1], p[3])
+    bad_fleets = [None]
+    for field, value in (("N", 0), ("N", 17), ("solver", 3), ("T", 0.0), ("M", 0), ("blocks", None), ("model_of", None)):
+        f2 = wg.DimitrovFleet.from_buffer_copy(fleet)
+        setattr(f2, field, value)
+        bad_fleets.append(f2)
+    q = (8, p[4], p[4], p[4], p[3])                                               # qcap, queues, t_start, t_end, count
+    fo = (4, p[4], p[3], None, 1, p[4], p[3], 4, 1, p[4], None, None, 0, None)    # lcap .. hip_stream of the follow call
+    for f2 in bad_fleets:
+        a = None if f2 is None else C.addressof(f2)
+        assert lib.wg_dimitrov_tick_fleet_dev(B, a, p[4], p[4], None, 0, None) == BAD_ARG
+        assert lib.wg_dimitrov_walk_fleet_dev(B, a, *q, 0.0, 1, p[4], None, None, 0, None) == BAD_ARG
+        assert lib.wg_dimitrov_follow_fleet_dev(B, a, *q, *fo) == BAD_ARG
+    fp = C.addressof(fleet)
+    assert lib.wg_dimitrov_tick_fleet_dev(-1, fp, p[4], p[4], None, 0, None) == BAD_ARG
+    assert lib.wg_dimitrov_tick_fleet_dev(B, fp, None, p[4], None, 0, None) == BAD_ARG
+    assert lib.wg_dimitrov_tick_fleet_dev(B, fp, p[4], None, None, 0, None) == BAD_ARG
+    assert lib.wg_dimitrov_walk_fleet_dev(B, fp, 0, *q[1:], 0.0, 1, p[4], None, None, 0, None) == BAD_ARG
+    assert lib.wg_dimitrov_walk_fleet_dev(B, fp, *q, 0.0, -1, p[4], None, None, 0, None) == BAD_ARG
+    assert lib.wg_dimitrov_follow_fleet_dev(B, fp, *q, 0, *fo[1:]) == BAD_ARG
+    assert lib.wg_dimitrov_follow_fleet_dev(B, fp, *q, *fo[:4], 2, *fo[5:]) == BAD_ARG
+    assert lib.wg_dimitrov_tick_fleet_dev_ctx(None, B, fp, p[4], p[4], None, 0, None) == BAD_ARG
+    assert lib.wg_last_error()
+    assert (keep[1] == 0xA5).all() and (keep[2] == -77).all()                     # nothing was written

@@ -1,0 +1,501 @@
+"""Dimitrov-2008 fleets with a model per gait: wg_dimitrov_tick_fleet_dev, wg_dimitrov_walk_fleet_dev and
+wg_dimitrov_follow_fleet_dev through the C ABI, in the three solver modes.  Gait g of a fleet launch runs with
+blocks[model_of[g]] (made by wg_dimitrov_constants_batch_dev) and must leave, byte for byte, what a context configured with that
+model leaves for it through the twin call: the references are five contexts, one per model, each ticking / walking / following
+its own subset of the fleet.  One gait at h = 0.6 is held to the CPU oracle as well, so the chain is not only HIP against HIP."""
+import ctypes as C
+import importlib
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import dimitrov as dv  # noqa: E402
+import oraclelib as ol  # noqa: E402
+from test_dimitrov_gpu import _fill  # noqa: E402
+from test_dimitrov_walk_gpu import (BF, FILL_I, OSZ, PSZ, QCAP, SMAX, SOLE, SSZ, _stream, device_feet, device_queues, fleet70,  # noqa: E402
+                                    fresh_states, times, to_dev)
+from test_dimitrov_follow_gpu import CANARY, FINAL, arrays, host  # noqa: E402
+from test_dimitrov_follow_host import N_TICKS, feeding  # noqa: E402
+from test_footcons_online_gpu import new_queues, poison_past_length  # noqa: E402
+from test_zmpdisc_online_gpu import Fleet, Walk  # noqa: E402
+
+wg = importlib.import_module("jrl-walkgen_amd")
+pytestmark = pytest.mark.gpu
+
+SOLVERS = pytest.mark.parametrize("solver", [0, 1, 2], ids=["PLDP", "QLD", "QLDANDLQ"])
+BAD_INPUT = -4                                  # WG_PLDP_BAD_INPUT
+N, TICKS = 16, 12
+HEIGHTS = np.array([0.6, 0.7, 0.8, 0.9, 0.95])
+ALPHAS = np.array([200.0, 1.0, 1e3, 50.0, 200.0])
+BETAS = np.array([1000.0, 1.0, 10.0, 500.0, 2000.0])
+M5 = len(HEIGHTS)
+MODEL_OF = np.array([(7 * g + g // 5) % M5 for g in range(BF)], np.int32)       # scattered: every model, no runs
+MODEL_OF[0] = 0                                                               # gait 0, h = 0.6: the one the oracle follows
+
+
+def model_of_fleet(m, solver):
+    mod = wg.dimitrov_defaults()
+    mod.solver, mod.com_height, mod.alpha, mod.beta = solver, HEIGHTS[m], ALPHAS[m], BETAS[m]
+    return mod
+
+
+def fleet_of(solver, models=range(M5), model_of=MODEL_OF, extra_failed=False):
+    """blocks of the given models made on the device (a failed one behind them on request), model_of on the device, the descriptor;
+    the tensors ride along so that they outlive the launches"""
+    import torch
+    wg.init(0)
+    idx = list(models)
+    h, a, b = HEIGHTS[idx].copy(), ALPHAS[idx].copy(), BETAS[idx].copy()
+    if extra_failed:
+        h, a, b = np.append(h, 0.8), np.append(a, 200.0), np.append(b, -1e9)
+    M = len(h)
+    base = wg.dimitrov_defaults()
+    base.solver = solver
+    dev = [torch.from_numpy(x).cuda() for x in (h, a, b)]
+    blocks = torch.full((M, wg.dimitrov_constants_bytes()), 0x5A, dtype=torch.uint8, device="cuda")
+    status = torch.zeros(M, dtype=torch.int32, device="cuda")
+    wg.dimitrov_constants_batch_dev(M, base, dev[0].data_ptr(), dev[1].data_ptr(), dev[2].data_ptr(), blocks.data_ptr(),
+                                    status.data_ptr(), _stream())
+    assert list(status.cpu().numpy()) == [0] * len(idx) + ([-2] if extra_failed else [])
+    mo = torch.from_numpy(np.ascontiguousarray(model_of, np.int32)).cuda()
+    return dict(M=M, blocks=blocks, mo=mo, fleet=wg.dimitrov_fleet(base, M, blocks.data_ptr(), mo.data_ptr()))
+
+
+class Contexts:
+    """one context per model, each configured with its own"""
+
+    def __init__(self, solver, models=range(M5)):
+        self.ctx = []
+        for m in models:
+            c = wg.Context(0)
+            mod = model_of_fleet(m, solver)
+            assert c.call("wg_dimitrov_configure", C.byref(mod)) == 0
+            self.ctx.append(c)
+
+    def __enter__(self):
+        return self.ctx
+
+    def __exit__(self, *a):
+        for c in self.ctx:
+            c.close()
+
+
+_plans = {}
+
+
+def plan_polys():
+    """the polytopes of TICKS ticks of BF gaits on the plans of tests/footplans.py, [tick] -> bytes of [BF][N] polytopes; once"""
+    if not _plans:
+        plans = [dv.plan(np.random.default_rng(500 + g), n_steps=3 + g % 6) for g in range(BF)]
+        offs = [(5 * g) % 11 for g in range(BF)]
+        ticks = []
+        for it in range(TICKS):
+            polys = (wg.ZmpPolytope * (BF * N))()
+            for g in range(BF):
+                for i, p in enumerate(dv.polys_at(plans[g], it + offs[g], N)):
+                    _fill(polys[g * N + i], p)
+            ticks.append(np.frombuffer(polys, dtype=np.uint8).reshape(BF, N * PSZ).copy())
+        _plans["ticks"] = ticks
+    return _plans["ticks"]
+
+
+def start_states():
+    st = fresh_states(BF)
+    for g in range(BF):
+        st[g].xk[0] = 0.002 * g; st[g].xk[4] = 0.001 * (g % 5 - 2)
+    return np.frombuffer(st, dtype=np.uint8).reshape(BF, SSZ).copy()
+
+
+def tick_loop_fleet(fl, n_ticks=TICKS, snaps=None):
+    """n_ticks fleet ticks with hot starts: (states [BF][SSZ], outs [n_ticks][BF][OSZ]) on the host; a list given as `snaps`
+    receives the states behind every tick as well"""
+    import torch
+    st = torch.from_numpy(start_states()).cuda()
+    outs = torch.full((n_ticks, BF, OSZ), CANARY, dtype=torch.uint8, device="cuda")
+    after = []
+    for k in range(n_ticks):
+        polys = torch.from_numpy(plan_polys()[k]).cuda()
+        wg.dimitrov_tick_fleet_dev(BF, fl["fleet"], polys.data_ptr(), st.data_ptr(), outs[k].data_ptr(), 0, _stream())
+        if snaps is not None:
+            after.append(st.clone())
+    torch.cuda.synchronize()
+    if snaps is not None:
+        snaps.extend(s.cpu().numpy() for s in after)
+    return st.cpu().numpy(), outs.cpu().numpy()
+
+
+def tick_loop_contexts(ctxs, model_of, n_ticks=TICKS):
+    """the same ticks, context m ticking the gaits of model m through wg_dimitrov_tick_batch_dev: the same two arrays"""
+    import torch
+    st0 = start_states()
+    st_all = np.zeros_like(st0); outs_all = np.zeros((n_ticks, BF, OSZ), np.uint8)
+    for m, c in enumerate(ctxs):
+        idx = np.flatnonzero(model_of == m)
+        if not len(idx):
+            continue
+        st = torch.from_numpy(st0[idx]).cuda()
+        outs = torch.full((n_ticks, len(idx), OSZ), CANARY, dtype=torch.uint8, device="cuda")
+        for k in range(n_ticks):
+            polys = torch.from_numpy(plan_polys()[k][idx]).cuda()
+            assert c.call("wg_dimitrov_tick_batch_dev", len(idx), polys.data_ptr(), st.data_ptr(), outs[k].data_ptr(), 0, _stream()) == 0
+        torch.cuda.synchronize()
+        st_all[idx] = st.cpu().numpy(); outs_all[:, idx] = outs.cpu().numpy()
+    return st_all, outs_all
+
+
+_refs = {}
+
+
+def tick_reference(solver):
+    if solver not in _refs:
+        with Contexts(solver) as ctxs:
+            st, outs = tick_loop_contexts(ctxs, MODEL_OF)
+        st.setflags(write=False); outs.setflags(write=False)
+        _refs[solver] = (st, outs)
+    return _refs[solver]
+
+
+def out_of(row):
+    return wg.DimitrovOut.from_buffer_copy(row.tobytes())
+
+
+# ---- the tick ----------------------------------------------------------------------------------------------------------------
+@SOLVERS
+def test_fleet_ticks_equal_five_configured_contexts(solver):
+    st_ref, outs_ref = tick_reference(solver)
+    st, outs = tick_loop_fleet(fleet_of(solver))
+    assert np.array_equal(outs, outs_ref) and np.array_equal(st, st_ref)
+    rets = {out_of(outs[k, g]).ret for k in (0, TICKS - 1) for g in range(BF)}
+    assert (0 in rets) if solver != 1 else (2 in rets)                # mode QLD is the reference's: ifail = 2 on the first tick
+    if solver != 1:                                                   # the models matter: the same plan under two models
+        g, rolled = 5, np.roll(MODEL_OF, 1)
+        assert MODEL_OF[g] != rolled[g] and not np.array_equal(st[g], start_states()[g])
+        assert not np.array_equal(tick_loop_fleet(fleet_of(solver, model_of=rolled))[0][g], st[g])
+
+
+@SOLVERS
+def test_one_model_equals_one_configured_context(solver):
+    zeros = np.zeros(BF, np.int32)
+    with Contexts(solver, models=[3]) as ctxs:
+        st_ref, outs_ref = tick_loop_contexts(ctxs, zeros)
+    st, outs = tick_loop_fleet(fleet_of(solver, models=[3], model_of=zeros))
+    assert np.array_equal(outs, outs_ref) and np.array_equal(st, st_ref)
+
+
+def test_one_gait_at_a_height_of_0_6_against_the_cpu_oracle():
+    """gait 0 (model 0: h = 0.6) of the PLDP fleet, tick by tick against oracle/pldp_oracle.c fed with the constants of the HOST
+    block of that model, the way test_dimitrov_gpu.py::test_fused_tick_bit_exact_over_gaits holds the configured tick"""
+    assert MODEL_OF[0] == 0 and HEIGHTS[0] == 0.6
+    mod = model_of_fleet(0, 0)
+    rc, blk = wg.dimitrov_constants_block(mod)
+    assert rc == 0
+    K = wg.dimitrov_constants_unpack(blk)
+    Mo = ol.pldp_setup(N, K["iPu"], K["Px"], K["Pu"])
+    lib = ol.oracle()
+    dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))  # noqa: E731
+    snaps = []
+    st, outs = tick_loop_fleet(fleet_of(0), snaps=snaps)
+    assert len(snaps) == TICKS and np.array_equal(snaps[-1], st)
+    so = wg.DimitrovState.from_buffer_copy(start_states()[0].tobytes())
+    solved = 0
+    for k in range(TICKS):
+        polys = (wg.ZmpPolytope * N).from_buffer_copy(plan_polys()[k][0].tobytes())
+        oo = wg.DimitrovOut()
+        rc = lib.wgo_dimitrov_tick(C.byref(Mo), dp(K["OptB"]), dp(K["OptC"]), dp(K["iLQ"]), C.c_double(mod.T), C.c_double(mod.Tctrl),
+                                   C.c_double(mod.com_height), C.byref(polys), C.byref(so), C.byref(oo), C.c_int(0))
+        got = out_of(outs[k, 0])
+        assert got.ret == rc, (k, got.ret, rc)
+        assert snaps[k][0].tobytes() == bytes(so), (k, "state")           # the state behind every tick, a failed one included
+        if rc != 0:                                                       # the oracle's gait stops here, as in the test cited
+            assert (got.jerk_x, got.n_iter, got.n_active) == (oo.jerk_x, oo.n_iter, oo.n_active), k
+            break
+        assert bytes(got) == bytes(oo), k
+        solved += 1
+    assert solved >= 8
+
+
+@SOLVERS
+def test_refused_gaits_keep_their_state_and_no_neighbour_notices(solver):
+    """model_of of -1, of M, and of a failed block"""
+    st_ref, outs_ref = tick_reference(solver)
+    refused = REFUSED
+    st, outs = tick_loop_fleet(refusing_fleet(solver), n_ticks=3)
+    s0 = start_states()
+    for g in range(BF):
+        if g in refused:
+            assert np.array_equal(st[g], s0[g]), g
+            for k in range(3):
+                o = out_of(outs[k, g])
+                assert o.ret == BAD_INPUT and o.n_iter == 0, (k, g)
+        else:
+            assert np.array_equal(outs[:, g], outs_ref[:3, g]), g
+    keep = [g for g in range(BF) if g not in refused]
+    st3 = tick_loop_fleet(fleet_of(solver), n_ticks=3)[0]             # the run without them: three ticks of the good fleet
+    assert np.array_equal(st[keep], st3[keep])
+
+
+# ---- the walk ----------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def aligned():
+    """fleet70(0.7, 0.13), axis-aligned, through wg_zmpdisc_full_batch_dev -> wg_foot_constraints_batch_dev: the queues, and what a
+    follow call over them needs beside them"""
+    wg.init(0)
+    F = device_feet(fleet70(0.7, 0.13, aligned=range(BF)))
+    return dict(Q=device_queues(F), time=F["time"], ln=F["ln"], refs={})
+
+
+@pytest.fixture(scope="module")
+def queues(aligned):
+    return aligned["Q"]
+
+
+def subset(Q, idx):
+    import torch
+    t = torch.from_numpy(np.asarray(idx, np.int64)).cuda()
+    return dict(B=len(idx), qcap=Q["qcap"], queues=Q["queues"][t].contiguous(), ts=Q["ts"][t].contiguous(), te=Q["te"][t].contiguous(),
+                count=Q["count"][t].contiguous())
+
+
+WALK_TICKS = 40                                                       # (the first ticks see the start's double support only)
+REFUSED = {3: -1, 17: M5 + 1, 40: M5}                                 # of M5 + 1 blocks, 0 .. M5 - 1 good and the last a failed one
+_walks = {}
+
+
+def refusing_fleet(solver):
+    """the fleet of fleet_of(solver) with a failed block behind the good ones and the gaits of REFUSED bound to no good block"""
+    mo = MODEL_OF.copy()
+    for g, v in REFUSED.items():
+        mo[g] = v
+    fl = fleet_of(solver, model_of=mo, extra_failed=True)
+    assert fl["M"] == M5 + 1
+    return fl
+
+
+def assert_refused_rows(rows, what):
+    """the out structs of a refused gait: ret and n_iter written, every other byte the pre-fill's"""
+    ret, nit = wg.DimitrovOut.ret, wg.DimitrovOut.n_iter
+    written = np.zeros(OSZ, bool)
+    written[ret.offset:ret.offset + ret.size] = True; written[nit.offset:nit.offset + nit.size] = True
+    for k, row in enumerate(rows):
+        o = out_of(row)
+        assert o.ret == BAD_INPUT and o.n_iter == 0, (what, k)
+        assert (row[~written] == CANARY).all(), (what, k)
+
+
+def walk_fleet(Q, fl, n=WALK_TICKS):
+    """ONE wg_dimitrov_walk_fleet_dev from fresh states at t0 = 0, outs pre-filled with the canary: (states, outs, ran_out)"""
+    import torch
+    st = to_dev(fresh_states(BF))
+    outs = torch.full((n, BF, OSZ), CANARY, dtype=torch.uint8, device="cuda")
+    ran = torch.full((BF,), FILL_I, dtype=torch.int32, device="cuda")
+    wg.dimitrov_walk_fleet_dev(BF, fl["fleet"], QCAP, Q["queues"].data_ptr(), Q["ts"].data_ptr(), Q["te"].data_ptr(), Q["count"].data_ptr(),
+                               0.0, n, st.data_ptr(), outs.data_ptr(), ran.data_ptr(), 0, _stream())
+    torch.cuda.synchronize()
+    return st.cpu().numpy().reshape(BF, SSZ), outs.cpu().numpy(), ran.cpu().numpy()
+
+
+def good_walk(Q, solver):
+    if solver not in _walks:
+        _walks[solver] = walk_fleet(Q, fleet_of(solver))
+        for a in _walks[solver]:
+            a.setflags(write=False)
+    return _walks[solver]
+
+
+@SOLVERS
+def test_walk_fleet_equals_the_per_model_walks(queues, solver):
+    import torch
+    Q, n = queues, WALK_TICKS
+    st, outs, ran = good_walk(Q, solver)
+    assert not ran.any()
+    with Contexts(solver) as ctxs:
+        for m, c in enumerate(ctxs):
+            idx = np.flatnonzero(MODEL_OF == m)
+            q = subset(Q, idx)
+            s = to_dev(fresh_states(len(idx)))
+            o = torch.full((n, len(idx), OSZ), CANARY, dtype=torch.uint8, device="cuda")
+            r = torch.full((len(idx),), FILL_I, dtype=torch.int32, device="cuda")
+            assert c.call("wg_dimitrov_walk_dev", len(idx), QCAP, q["queues"].data_ptr(), q["ts"].data_ptr(), q["te"].data_ptr(),
+                          q["count"].data_ptr(), 0.0, n, s.data_ptr(), o.data_ptr(), r.data_ptr(), 0, _stream()) == 0
+            torch.cuda.synchronize()
+            assert np.array_equal(st[idx], s.cpu().numpy().reshape(len(idx), SSZ)), m
+            assert np.array_equal(outs[:, idx], o.cpu().numpy()), m
+            assert np.array_equal(ran[idx], r.cpu().numpy()), m
+    if solver != 1:                                                   # every gait went its own way
+        assert len({st[g].tobytes() for g in range(BF)}) == BF
+
+
+@SOLVERS
+def test_refused_gaits_sit_every_tick_of_a_walk_out(queues, solver):
+    """model_of of -1, of M + 1 and of a failed block in ONE wg_dimitrov_walk_fleet_dev: the refused gaits keep their states, every
+    row of theirs says so and holds nothing else; the others leave the bytes of the walk without them"""
+    st_ref, outs_ref, ran_ref = good_walk(queues, solver)
+    st, outs, ran = walk_fleet(queues, refusing_fleet(solver))
+    fresh = np.frombuffer(fresh_states(BF), dtype=np.uint8).reshape(BF, SSZ)
+    for g in REFUSED:
+        assert np.array_equal(st[g], fresh[g]), g
+        assert_refused_rows(outs[:, g], ("walk", g))
+    keep = [g for g in range(BF) if g not in REFUSED]
+    assert np.array_equal(st[keep], st_ref[keep]) and np.array_equal(outs[:, keep], outs_ref[:, keep])
+    assert np.array_equal(ran[keep], ran_ref[keep])
+
+
+# ---- the follow --------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def ragged():
+    """fleet70(0.7, 0.13): ragged step counts, rotated soles; its final queues, and the on-line machinery of the follow tests"""
+    import torch
+    wg.init(0)
+    fl = fleet70(0.7, 0.13)
+    zm, steps, n_steps, init = fl
+    f = Fleet(zm, steps, n_steps, init, SMAX, check_oracle=False)
+    time = torch.from_numpy(times(f.lcap, zm.T)).cuda()
+    F = dict(B=f.B, lcap=f.lcap, ln=f.full["length"], time=time, lf=f.full["left"], lty=f.full["left_type"], rf=f.full["right"])
+    return dict(fl=fl, f=f, time=time, ln=f.full["length"], Q=device_queues(F), refs={})
+
+
+def follow_reference(fleet, solver, n_ticks=N_TICKS):
+    """every model's own context following its own gaits over their final queues through wg_dimitrov_follow_dev, n_ticks ticks in one
+    call: dict(st, outs, ran, clock) of the whole fleet on the host; once per solver and tick count"""
+    import torch
+    if (solver, n_ticks) not in fleet["refs"]:
+        Qfull = fleet["Q"]
+        ref = dict(st=np.zeros((BF, SSZ), np.uint8), outs=np.zeros((n_ticks, BF, OSZ), np.uint8), ran=np.zeros(BF, np.int32),
+                   clock=np.zeros(BF))
+        with Contexts(solver) as ctxs:
+            for m, c in enumerate(ctxs):
+                idx = np.flatnonzero(MODEL_OF == m)
+                q = subset(Qfull, idx)
+                have = fleet["ln"][torch.from_numpy(idx).cuda()].contiguous()
+                A = arrays(len(idx), n_ticks)
+                wg.dimitrov_follow_dev_ctx(c, len(idx), QCAP, q["queues"].data_ptr(), q["ts"].data_ptr(), q["te"].data_ptr(),
+                                           q["count"].data_ptr(), int(fleet["time"].shape[0]), fleet["time"].data_ptr(), have.data_ptr(),
+                                           None, FINAL, A["clock"].data_ptr(), A["ticks"].data_ptr(), n_ticks, n_ticks, A["st"].data_ptr(),
+                                           A["outs"].data_ptr(), A["ran"].data_ptr(), 0, _stream())
+                h = host(A)
+                assert (h["ticks"] == n_ticks).all()
+                ref["st"][idx], ref["outs"][:, idx], ref["ran"][idx], ref["clock"][idx] = h["st"], h["outs"], h["ran"], h["clock"]
+        for a in ref.values():
+            a.setflags(write=False)
+        fleet["refs"][solver, n_ticks] = ref
+    return fleet["refs"][solver, n_ticks]
+
+
+def follow_fleet(fl, Q, A, time_t, have_t, max_ticks, flags=0, walk=None):
+    wg.dimitrov_follow_fleet_dev(A["B"], fl["fleet"], Q["qcap"], Q["queues"].data_ptr(), Q["ts"].data_ptr(), Q["te"].data_ptr(),
+                                 Q["count"].data_ptr(), int(time_t.shape[0]), time_t.data_ptr(), have_t.data_ptr(),
+                                 None if walk is None else walk.data_ptr(), flags, A["clock"].data_ptr(), A["ticks"].data_ptr(),
+                                 A["tick_cap"], max_ticks, A["st"].data_ptr(), A["outs"].data_ptr(), A["ran"].data_ptr(), 0, _stream())
+
+
+@SOLVERS
+def test_follow_fleet_over_final_queues_equals_the_per_model_follows(aligned, solver):
+    """the three modes (QLD's follow twin runs here alone, on the walk test's axis-aligned fleet: over the ragged one's rotated soles
+    mode QLD takes 70 ms a tick): final queues followed in two calls, a model per gait, against every model's own context; then the
+    same with refused gaits among them -- model_of of -1, of M + 1, of a failed block -- whose rounds the select kernel counts while
+    their ticks write ret and n_iter and nothing else"""
+    n_ticks = WALK_TICKS
+    ref = follow_reference(aligned, solver, n_ticks)
+    t_end = 0.0
+    for _ in range(n_ticks):
+        t_end += wg.dimitrov_defaults().T                             # the walk's own repeated addition of the fleet's T
+    runs = {}
+    for name, fl in (("good", fleet_of(solver)), ("refusing", refusing_fleet(solver))):
+        A = arrays(BF, n_ticks)
+        for n in (15, n_ticks):                                       # fifteen ticks, then what the rows still hold
+            follow_fleet(fl, aligned["Q"], A, aligned["time"], aligned["ln"], n, flags=FINAL)
+        runs[name] = h = host(A)
+        assert (h["ticks"] == n_ticks).all() and (h["clock"] == t_end).all() and np.array_equal(h["clock"], ref["clock"]), name
+    h = runs["good"]
+    assert np.array_equal(h["st"], ref["st"]) and np.array_equal(h["outs"], ref["outs"]) and np.array_equal(h["ran"], ref["ran"])
+    walked = good_walk(aligned["Q"], solver)                          # and ONE wg_dimitrov_walk_fleet_dev over the same queues
+    assert np.array_equal(h["st"], walked[0]) and np.array_equal(h["outs"], walked[1])
+    rets = {out_of(h["outs"][k, g]).ret for k in (0, n_ticks - 1) for g in range(BF)}
+    assert (0 in rets) if solver != 1 else (2 in rets)                # mode QLD is the reference's: ifail = 2 on the first tick
+    h = runs["refusing"]
+    fresh = np.frombuffer(fresh_states(BF), dtype=np.uint8).reshape(BF, SSZ)
+    for g in REFUSED:
+        assert np.array_equal(h["st"][g], fresh[g]), g
+        assert_refused_rows(h["outs"][:, g], ("follow", g))
+    keep = [g for g in range(BF) if g not in REFUSED]
+    assert np.array_equal(h["st"][keep], ref["st"][keep]) and np.array_equal(h["outs"][:, keep], ref["outs"][:, keep])
+    assert np.array_equal(h["ran"][keep], ref["ran"][keep])
+
+
+@pytest.mark.parametrize("solver", [0, 2], ids=["PLDP", "QLDANDLQ"])
+def test_follow_fleet_fed_on_line_equals_the_per_model_follows(ragged, solver):
+    """the ragged fleet fed on line, cut into rounds two ways (one and three steps per call), a model per gait; the reference: every
+    model's own context following its own gaits over their final queues.  (The modes of the twin's on-line test; QLD's follow
+    kernel is held by the test above -- these 60 ticks over rotated soles take 11 s in mode QLD.)"""
+    f = ragged["f"]
+    ref = follow_reference(ragged, solver)
+    ref_st, ref_outs, ref_ran, ref_clock = ref["st"], ref["outs"], ref["ran"], ref["clock"]
+    fl = fleet_of(solver)
+    for K in (1, 3):
+        calls = feeding(ragged["fl"], K)
+        w = Walk(f, ("left", "left_type", "right", "right_type"))
+        Q = new_queues(BF)
+        A = arrays(BF, N_TICKS)
+        done = np.zeros(BF, np.int32)
+        seen = set()
+        for i, (what, arg, lens_want, _) in enumerate(calls):
+            lens = w.begin(arg) if what == "begin" else (w.append(arg) if what == "append" else w.end(arg))
+            assert np.array_equal(lens, lens_want), (i, what)
+            poison_past_length(w, lens)
+            wg.foot_constraints_append_dev(BF, w.lcap, int(done.min()), Q["done"].data_ptr(), w.buf["length"].data_ptr(),
+                                           ragged["time"].data_ptr(), w.buf["left"].data_ptr(), w.buf["left_type"].data_ptr(),
+                                           w.buf["right"].data_ptr(), *SOLE, QCAP, Q["queues"].data_ptr(), Q["ts"].data_ptr(),
+                                           Q["te"].data_ptr(), Q["count"].data_ptr(), _stream())
+            done = lens.copy()
+            follow_fleet(fl, Q, A, ragged["time"], Q["done"], N_TICKS, walk=w.state)
+            seen.add(tuple(host(A)["ticks"]))
+        h = host(A)
+        assert len(seen) > 2                                              # the gaits did advance raggedly, call by call
+        assert (h["ticks"] == N_TICKS).all() and np.array_equal(h["clock"], ref_clock), K
+        assert np.array_equal(h["st"], ref_st) and np.array_equal(h["outs"], ref_outs) and np.array_equal(h["ran"], ref_ran), K
+
+
+# ---- arguments ---------------------------------------------------------------------------------------------------------------
+def test_host_side_refusals_and_an_empty_fleet(queues):
+    import torch
+    lib = wg.lib()
+    Q = queues
+    fl = fleet_of(0)
+    st = to_dev(fresh_states(BF))
+    before = st.clone()
+    polys = torch.from_numpy(plan_polys()[0]).cuda()
+    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    fp = C.addressof(fl["fleet"])
+    qa = (QCAP, p(Q["queues"]), p(Q["ts"]), p(Q["te"]), p(Q["count"]))
+    A = arrays(BF, 4)
+    fa = (4, p(Q["ts"]), p(Q["count"]), None, FINAL, p(A["clock"]), p(A["ticks"]), 4, 1, p(st), None, None, 0, None)
+    bad_fleets = []
+    for field, value in (("N", 0), ("N", 17), ("solver", 3), ("solver", -1), ("T", 0.0), ("T", -0.1), ("M", 0), ("blocks", None),
+                         ("model_of", None)):
+        f2 = wg.DimitrovFleet.from_buffer_copy(fl["fleet"])
+        setattr(f2, field, value)
+        bad_fleets.append(f2)
+    for f2 in [None] + bad_fleets:
+        a = None if f2 is None else C.addressof(f2)
+        assert lib.wg_dimitrov_tick_fleet_dev(BF, a, p(polys), p(st), None, 0, None) == -2
+        assert lib.wg_dimitrov_walk_fleet_dev(BF, a, *qa, 0.0, 1, p(st), None, None, 0, None) == -2
+        assert lib.wg_dimitrov_follow_fleet_dev(BF, a, *qa, *fa) == -2
+    assert lib.wg_dimitrov_tick_fleet_dev(-1, fp, p(polys), p(st), None, 0, None) == -2
+    assert lib.wg_dimitrov_tick_fleet_dev(BF, fp, None, p(st), None, 0, None) == -2
+    assert lib.wg_dimitrov_tick_fleet_dev(BF, fp, p(polys), None, None, 0, None) == -2
+    assert lib.wg_dimitrov_walk_fleet_dev(-1, fp, *qa, 0.0, 1, p(st), None, None, 0, None) == -2
+    assert lib.wg_dimitrov_walk_fleet_dev(BF, fp, 0, *qa[1:], 0.0, 1, p(st), None, None, 0, None) == -2
+    assert lib.wg_dimitrov_walk_fleet_dev(BF, fp, *qa, 0.0, -1, p(st), None, None, 0, None) == -2
+    assert lib.wg_dimitrov_walk_fleet_dev(BF, fp, *qa, 0.0, 1, None, None, None, 0, None) == -2
+    assert lib.wg_dimitrov_follow_fleet_dev(BF, fp, *qa, 0, *fa[1:]) == -2
+    assert lib.wg_dimitrov_follow_fleet_dev(BF, fp, *qa, *fa[:4], 2, *fa[5:]) == -2
+    assert lib.wg_dimitrov_tick_fleet_dev_ctx(None, BF, fp, p(polys), p(st), None, 0, None) == -2
+    # B == 0 is WG_OK and launches nothing
+    assert lib.wg_dimitrov_tick_fleet_dev(0, fp, p(polys), p(st), None, 0, None) == 0
+    assert lib.wg_dimitrov_walk_fleet_dev(0, fp, *qa, 0.0, 1, p(st), None, None, 0, None) == 0
+    assert lib.wg_dimitrov_follow_fleet_dev(0, fp, *qa, *fa) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(st, before)
