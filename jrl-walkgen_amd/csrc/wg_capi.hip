@@ -755,6 +755,14 @@ int wg_mpc_configure_ctx(wg_ctx_t *ctx, const wg_model_t *model) {
   wg::build_tables(*model, host_tables, qb.empty() ? nullptr : qb.data());
   if (!host_tables.blocks_ok && !qb.empty())
     return fail(WG_ERR_BAD_ARG, "the matrix-core Gramian is not positive definite enough for ql0002's factorisation");
+  // the compact view's decision-only sums (tests and A/B; read here, once per configuration): unset = guarded by certificates,
+  // "ordered" = the reference's order throughout, "doubt" = every dependence test falls back and every solve is run twice
+  if (const char *e = getenv("WG_QL_SUMS")) {
+    const std::string v(e);
+    if (v == "ordered") host_tables.ql_sums = wg::kSumsOrdered;
+    else if (v == "doubt") host_tables.ql_sums = wg::kSumsDoubt;
+    else if (!v.empty() && v != "guarded") return fail(WG_ERR_BAD_ARG, "WG_QL_SUMS=%s: ordered, doubt or unset", e);
+  }
   if (!ctx->tables_dev) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ctx->tables_dev), sizeof(wg::TickTables)));
   if (!ctx->model_dev) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ctx->model_dev), sizeof(wg_model_t)));
   // a launch of an earlier configuration may still be reading the tables: this context's own launches, on whatever stream they

@@ -13,6 +13,7 @@
 //   wg_prof.hpp        (included by wg_ql_view.hpp) the profile build's g_prof slots by name and its timer marks: PT_* for the
 //                      solver, TK_* for the tick, PT_LOCAL_* for a phase that times itself; nothing without WG_PROFILE
 //   wg_ql_phases.hpp   the phases of one active-set iteration (products with Z, back substitution, sweeps, scans, deletion)
+//   wg_ql_guard.hpp    the certificates of the compact view's decision-only sums, one text for host and device
 //   this file          the dispatch of the back substitution and the sweep by problem view, and ql_solve itself (ISA-sensitive: compare
 //                      every kernel before moving one of its blocks)
 // Compile with -ffp-contract=off: the reference build has no FMA contraction.
@@ -24,6 +25,10 @@
 #include "wg_wave.hpp"
 #include "wg_ql_view.hpp"
 #include "wg_ql_phases.hpp"
+// the certificates of the guarded sums, the host's text compiled for the device: constants materialised where they are used
+#define WG_GUARD_FN __device__ __forceinline__
+#define WG_GUARD_K(c) ::wg::wg_kconst(c)
+#include "wg_ql_guard.hpp"
 
 namespace wg {
 
@@ -61,6 +66,17 @@ template <class P>
 __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vsmall, int *hist, int hist_cap, QlResume *rs = nullptr) {
   // NaN iterates followed exactly (every policy of the shipped kernels; a policy may opt out for an A/B of what that costs)
   constexpr bool kNan = P::kNanExact && (WG_NAN_REGIME != 0);
+  // Guarded sums (the compact view; wg_ql_guard.hpp): the sums that only decide a branch -- the three of the
+  // linear-dependence test, lql's magnitude sum -- are added as a tree over the lanes while a certificate can vouch for the
+  // decision.  A doubt at the dependence test forms that iteration's sums in the reference's order on the spot (the test keeps no
+  // state); a doubt at the magnitude test cannot be settled there (the exact running maximum is not known), so the solve leaves
+  // with kQlDoubt -- a code no caller of the tick ever sees -- and ql_solve_guarded starts it again from its set-up with every sum
+  // in the reference's order (sums_mode = kSumsOrdered: one mode word, wave-uniform).
+  // kSumsDoubt (tests): the dependence certificate always doubts, and the finished solve is doubted as a whole -- the second pass
+  // starts from the dirtiest state a first pass can leave.
+  constexpr bool kGuard = GuardedSumsOf<P>::value;
+  [[maybe_unused]] int gmode = kSumsOrdered;
+  if constexpr (kGuard) gmode = uni(prob.sums_mode);
   int lane = wg_lane();
   const int n = q.n, m = q.m, me = q.me, mn = q.mn;
   QlResult out;
@@ -99,6 +115,18 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
   do {                                                                    \
     if (lane == 0 && hist && out.hist_len < hist_cap) hist[out.hist_len] = (code); \
     out.hist_len++;                                                       \
+  } while (0)
+  // guarded sums only: leave with kQlDoubt, the caller (ql_solve_guarded) runs the solve again from its set-up with every sum in
+  // the reference's order.  What this pass changed and the set-up does not rewrite is put back here: a shifted Hessian diagonal (wd
+  // still holds the caller's); wa, R, Z, the iterate, the multipliers and the history are rewritten from their first entry on
+#define QL_RERUN_ORDERED                                                              \
+  do {                                                                                \
+    PT_COUNT2(PS_N_RERUN);                                                            \
+    for (int i = lane; i < n; i += 64) prob.setGd(q, i, q.wd[i]);                     \
+    WG_WSYNC();                                                                       \
+    PT_FLUSH;                                                                         \
+    out.ifail = kQlDoubt; out.n_iter = iterc; out.nact = nact;                        \
+    return out;                                                                       \
   } while (0)
 
   // ---- reciprocal lengths of the constraint normals, :769-807 ----
@@ -381,6 +409,13 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
         WG_WSYNC();
       }
       PT(PS_BACKSUB_RESID);
+      if constexpr (kGuard) {
+        // nothing is decided here: the running maximum follows the tree sums while they are ordinary numbers
+        double sm = 0.0;
+        WG_REP(6) { sm = uni(xmag_sum_guarded(q, prob, vfact, lane, gmode == kSumsOrdered)); WG_SINK(sm); }
+        if (gmode != kSumsOrdered && WG_UBOOL(x_suspect || !guard_xmag_update(sm))) QL_RERUN_ORDERED;
+        xmag = maxd(xmag, sm);
+      } else
       { double sm = 0.0; WG_REP(6) { sm = uni(xmag_sum(q, prob, vfact, lane)); WG_SINK(sm); } xmag = maxd(xmag, sm); }
       PT(PS_XMAG_RESID);
       if (iflag == itref) { st = ST_RESID; continue; }      // :1226
@@ -735,8 +770,49 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
         if (nact == 0) route = 0;                           // :1488
         else {                                              // :1491-1532
           double suma = 0.0, sumb = 0.0, sumc = 0.0;
+          bool step_certain = false;                         // guarded sums: the certificate has decided route 0
           WG_REP(5) {
-          if constexpr (P::kNM > 0) {
+          if constexpr (kGuard) {
+            constexpr int NM = P::kNM;
+            static_assert(NM > 32 && NM <= 48, "three entries per lane of a 16-lane row");
+            {
+              // the three product vectors, written as before (lanes past NM shadow lane NM - 1, entries from n on are zeros)
+              const int il = lane < NM ? lane : NM - 1;
+              const bool in = il < n;
+              const int ic = in ? il : n - 1;
+              const double zv = Zm(ic, nact), wv = q.ww[ic];
+              const double zi = in ? zv : 0.0, wi = in ? wv : 0.0;
+              q.sc0[il] = wi * zi; q.sc1[il] = fabs(wi * zi); q.sc2[il] = zi * zi;
+            }
+            WG_WSYNC();
+            if (gmode == kSumsGuarded && !x_suspect) {
+              // the three sums side by side, one per row of 16 lanes (row 3 shadows row 2): lane j of row s adds entries j, j + 16
+              // and j + 32 of vector s, then the row is folded as a balanced tree on the DPP path (guard_rows_sum is this order on
+              // the host).  The values may differ from the reference's in their last bits -- they are handed to the certificate
+              // and to nothing else
+              const int row = (lane >> 4) < 3 ? (lane >> 4) : 2, j = lane & 15;
+              const int j2 = j + 32 < NM ? j + 32 : NM - 1;      // in bounds for every lane; past NM the value is dropped
+              const double *vec = q.sc0 + row * (int)(q.sc1 - q.sc0);
+              const double t0 = vec[j], t1 = vec[j + 16], t2 = vec[j2];
+              double v = (t0 + t1) + (j + 32 < NM ? t2 : 0.0);
+              v += dpp_zero<0x111, 0xf>(v);                       // row_shr:1, 2, 4, 8: lane 15 of a row holds its sum
+              v += dpp_zero<0x112, 0xf>(v);
+              v += dpp_zero<0x114, 0xf>(v);
+              v += dpp_zero<0x118, 0xf>(v);
+              suma = rl(v, 15); sumb = rl(v, 31); sumc = rl(v, 47);
+              step_certain = WG_UBOOL(guard_route0(suma, sumb, sumc, knext <= m, wsel, wg_kconst(vsmall)));
+            }
+            if (!step_certain) {
+              // doubt (or the reference's order asked for): the parent's three chains as rolled loops, lanes 0 .. 2
+              if (gmode != kSumsOrdered) PT_COUNT2(PS_N_FALLBACK);
+              const double *src = q.sc0 + (lane < 3 ? lane : 0) * (int)(q.sc1 - q.sc0);
+              double acc = 0.0;
+#pragma nounroll
+              for (int i = 0; i < NM; ++i) acc += src[i];
+              suma = rl(acc, 0); sumb = rl(acc, 1); sumc = rl(acc, 2);
+            }
+            WG_WSYNC();
+          } else if constexpr (P::kNM > 0) {
             constexpr int NM = P::kNM;
             {
               // lanes past NM shadow lane NM - 1 (same value to the same address); loads from clamped addresses, selected values:
@@ -792,7 +868,8 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
           }
           WG_SINK(suma); WG_SINK(sumb); WG_SINK(sumc);
           }   // WG_REP(5)
-          if (WG_UBOOL(!significant(sumb, fabs(suma)) || !(sumb > wg_kconst(vsmall)))) route = 1;
+          if (kGuard && step_certain) route = 0;
+          else if (WG_UBOOL(!significant(sumb, fabs(suma)) || !(sumb > wg_kconst(vsmall)))) route = 1;
           else {
             sumc = sqrt(sumc);
             if (knext <= m) sumc /= wsel;                    // wa[knext - 1]: the value the scan read
@@ -891,12 +968,28 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
       WG_WSYNC();
       PT(PS_ADD);
       double sm = 0.0;
+      if constexpr (kGuard) {
+        WG_REP(6) { sm = uni(xmag_sum_guarded(q, prob, vfact, lane, gmode == kSumsOrdered)); WG_SINK(sm); }   // :1776-1786
+        xmag = maxd(xmag, sm);
+        PT(PS_XMAG_ADD);
+        bool reset;
+        if (gmode == kSumsOrdered) reset = WG_UBOOL(sm < wg_kconst(xmagr) * xmag);
+        else {
+          const int verdict = x_suspect ? (int)kGuardDoubt : uni(guard_xmag(sm, xmag));
+          if (verdict == kGuardDoubt) QL_RERUN_ORDERED;
+          reset = verdict == kGuardReset;
+        }
+        if (reset) st = ST_RESET;
+        else if (itref <= 0) st = ST_SCAN;
+        else st = ST_RESID;
+      } else {
       WG_REP(6) { sm = uni(xmag_sum(q, prob, vfact, lane)); WG_SINK(sm); }   // :1776-1786
       xmag = maxd(xmag, sm);
       PT(PS_XMAG_ADD);
       if (WG_UBOOL(sm < wg_kconst(xmagr) * xmag)) st = ST_RESET;
       else if (itref <= 0) st = ST_SCAN;
       else st = ST_RESID;
+      }
       // R's LDS part is full (its columns and the working column hold nact finished columns): stop BETWEEN two iterations,
       // the loop's state goes to the caller, who moves R and resumes (or, without rs, repeats the solve from the start)
       if (q.nact_cap > 0 && nact > q.nact_cap) { cap_hit = true; break; }
@@ -911,6 +1004,8 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
       st = ST_FINISH;
     }
   }
+  if constexpr (kGuard) { if (gmode == kSumsDoubt && !early_exit && !cap_hit) QL_RERUN_ORDERED; }   // tests: the whole solve doubted once
+#undef QL_RERUN_ORDERED
 #undef LOG_EVENT
 
   PT(PS_TAIL);
@@ -928,6 +1023,20 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
   out.n_iter = iterc;
   out.nact = nact;
   return out;
+}
+
+// ql_solve for a policy with guarded sums: a solve that leaves in doubt (kQlDoubt) is run again from its set-up in the reference's
+// order -- once: the second pass has no certificate left to doubt.  One call site in a loop, so the solver is compiled once.
+template <class P>
+__device__ __forceinline__ QlResult ql_solve_guarded(const QlView &q, P &prob, double vsmall, int *hist, int hist_cap) {
+  static_assert(GuardedSumsOf<P>::value, "for policies with kGuardedSums");
+  QlResult r;
+  for (;;) {
+    r = ql_solve(q, prob, vsmall, hist, hist_cap);
+    if (!WG_UBOOL(r.ifail == kQlDoubt)) break;
+    prob.sums_mode = kSumsOrdered;
+  }
+  return r;
 }
 
 }  // namespace wg

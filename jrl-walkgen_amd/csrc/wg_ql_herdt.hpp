@@ -243,6 +243,7 @@ struct HerdtProb {
   static constexpr int kCopRows = 4 * NH;      // rows 1 .. 4N (lane k - 1 keeps row k's coefficients), then the foot-placement rows
   static constexpr bool kWideN = false;
   static constexpr int kFixedLdz = kNM | 1;    // Z in LDS, leading dimension of carve_fixed<kNM, ...>
+  static constexpr bool kGuardedSums = true;   // the decision-only sums as trees over the lanes, under wg_ql_guard.hpp's certificates
   static_assert(4 * NH == 64, "one CoP row per lane needs 4N == 64");
   // ---- LDS / global tables (wave-uniform pointers) ----
   const double *Qb;       // global (L1/L2-resident constant of the model), NH x kQbLd
@@ -257,6 +258,7 @@ struct HerdtProb {
   double diag_b;          // the constant block's contribution to ql0002's diagonal test
   int blocks_ok;
   int ns;
+  int sums_mode;          // kSumsGuarded / kSumsOrdered / kSumsDoubt (TickTables::ql_sums: the host's WG_QL_SUMS at configure time)
   // ---- per-lane registers: the lane's own constraint rows ----
   double ax[NH], ay[NH];  // CoP row (lane+1): x- and y-jerk parts
   int fj;                 // its two foot-variable entries sit in columns 2N+fj, 2N+ns+fj (fj < 0: none); their values fa(), fb()

@@ -460,6 +460,24 @@ __device__ __forceinline__ double ordered_sum_lds(double term, double *scratch, 
   return sum;
 }
 
+// The same sum in the same order as a rolled loop: the cold form behind the guarded sums (wg_ql_guard.hpp), run when a
+// certificate doubts or when the knob asks for the reference's order throughout.  Code that never runs still costs the
+// 256-register kernel, so the fallbacks stay small.
+template <int NM>
+__device__ __forceinline__ double ordered_sum_lds_rolled(double term, double *scratch, int cnt, int lane) {
+  {
+    const double v = (lane < cnt) ? term : 0.0;
+    const double vl = rl(v, NM - 1);                        // lanes past NM shadow lane NM - 1
+    scratch[lane < NM ? lane : NM - 1] = lane < NM ? v : vl;
+  }
+  WG_WSYNC();
+  double sum = 0.0;
+#pragma nounroll
+  for (int i = 0; i < NM; ++i) sum += scratch[i];           // entries >= cnt are +0.0: they leave the sum unchanged
+  WG_WSYNC();
+  return sum;
+}
+
 // Givens sweep (qld.cpp:1992-2030) for n <= 64, written without data-dependent control flow: on a single
 // resident wave every taken branch costs tens of cycles, so predicates become selects, inactive lanes shadow
 // lane n-1 (same addresses, same values), and LDS operands are fetched one or two steps ahead of the
@@ -997,6 +1015,19 @@ __device__ __forceinline__ double xmag_sum(const QlView &q, const P &prob, doubl
   }
   for (; i < n; ++i) sum += q.sc3[i];
   return sum;
+}
+
+// The same terms for a policy with guarded sums (GuardedSumsOf; n <= kNM <= 64, one term per lane): added as a balanced tree over
+// the lanes -- NOT the reference's order: the caller holds the result to wg_ql_guard.hpp's certificates -- or, `ordered`
+// (wave-uniform), in index order by the rolled loop.
+template <class P>
+__device__ __forceinline__ double xmag_sum_guarded(const QlView &q, const P &prob, double vfact, int lane, bool ordered) {
+  const int n = q.n;
+  const int il = lane < n ? lane : n - 1;                   // surplus lanes compute lane n - 1's term and drop it
+  const double xi = q.x[il];
+  const double term = fabs(xi) * vfact * (fabs(q.d[il]) + fabs(prob.Gd(q, il) * xi));
+  if (ordered) return ordered_sum_lds_rolled<P::kNM>(term, q.sc3, n, lane);
+  return wave_sum_tree(lane < n ? term : 0.0);
 }
 
 // qld.cpp:1992-2030.  Three phases: (1) the chain of rotation norms; (2) ga/gb of every rotation, one lane

@@ -238,6 +238,13 @@ struct NoActiveParams {};
 template <class P, class = void> struct ActiveParamsOf { typedef NoActiveParams type; };
 template <class P> struct ActiveParamsOf<P, typename std::enable_if<P::kCompact>::type> { typedef typename P::ActiveParams type; };
 
+// decision-only sums under certificates (wg_ql_guard.hpp): a policy that declares kGuardedSums carries `sums_mode`
+// (kSumsGuarded / kSumsOrdered / kSumsDoubt); every other policy keeps the reference's order and compiles none of it
+template <class P, class = void> struct GuardedSumsOf { static constexpr bool value = false; };
+template <class P> struct GuardedSumsOf<P, typename std::enable_if<P::kGuardedSums>::type> { static constexpr bool value = true; };
+enum : int { kSumsGuarded = 0, kSumsOrdered = 1, kSumsDoubt = 2 };
+constexpr int kQlDoubt = -7778;                            // QlResult::ifail of a guarded solve that must be run again (ql_solve_guarded)
+
 struct QlResult {
   int ifail, n_iter, nact, hist_len;
 };

@@ -55,7 +55,8 @@ struct TickTables {
   double R2[2 * kNMaxH * (2 * kNMaxH + 1) / 2];   // packed Cholesky factor of blockdiag(Qb, Qb), qld.cpp:859-890
   double Z2[4 * kNMaxH * kNMaxH];                 // its inverse, column-major ld 2N, qld.cpp:937-975
   double diag_b;                                  // diagonal test over the constant block, qld.cpp:814-843
-  int blocks_ok, pad_;
+  int blocks_ok;
+  int ql_sums;                                    // the compact view's decision-only sums (wg_ql_view.hpp: kSumsGuarded / Ordered / Doubt)
   // Z2 is blockdiag(Zb, Zb) with zeros in between, but the recurrence leaves SIGNED zeros in the upper-right block
   // (-(x * 0) / r); bit i + j*N = sign of Z2(i, N + j).  The kernel fetches only Zb and re-creates the rest from this.
   unsigned long long z2_cross_sign[(kNMaxH * kNMaxH + 63) / 64];
@@ -114,7 +115,7 @@ inline void build_tables(const wg_model_t &m, TickTables &t, const double *qb_ov
     }
     t.diag_b = diag;
     t.blocks_ok = (diag <= 0.0) ? 1 : 0;
-    t.pad_ = 0;
+    t.ql_sums = 0;                                // guarded; wg_mpc_configure reads the knob
     auto R = [&](int i, int j) -> double & { return t.R2[(size_t)j * (j + 1) / 2 + i]; };
     for (int j = 0; j < M && t.blocks_ok; ++j) {
       double temp = 0.0;
@@ -900,8 +901,9 @@ __device__ __forceinline__ TickDiag mpc_tick(const wg_model_t &m, const TickTabl
     prob.Qb = &tb->Qb[0][0]; prob.u = L.uvec; prob.Gv = L.Gv; prob.gd = L.gd;
     prob.rowA = L.rowA; prob.rowB = L.rowB; prob.rowK = L.rowK; prob.stepidx = L.stepidx; prob.V_f = L.V_f;
     prob.R2 = tb->R2; prob.Z2 = tb->Z2; prob.z2sign = tb->z2_cross_sign; prob.diag_b = tb->diag_b; prob.blocks_ok = tb->blocks_ok; prob.ns = ns;
+    prob.sums_mode = tb->ql_sums;
     prob.load_rows(lane, q.b);
-    qr = ql_solve(q, prob, 1e-8, hist, hist_cap);
+    qr = ql_solve_guarded(q, prob, 1e-8, hist, hist_cap);
     {
       WG_WSYNC();
       // the stores above completed long ago (the release only waits for them: they are in L2 then, which is where the

@@ -9,7 +9,9 @@
 //   * lanes parallelise over *independent outputs* only (rows of Z, columns of
 //     R, constraint rows of A); every inner sum runs sequentially inside one
 //     lane in the reference's order, so every double is bit-identical to the
-//     CPU solver and the active-set add/drop sequence is reproduced exactly;
+//     CPU solver and the active-set add/drop sequence is reproduced exactly
+//     (one stated exception: sums that only decide a branch, under the
+//     certificates of wg_ql_guard.hpp -- wave_sum_tree below);
 //   * order-insensitive reductions (max, arg-max with first-index tie-break,
 //     "any") use wave shuffles;
 //   * the long scalar chains (Givens sweep norms, triangular solves) are
@@ -120,6 +122,25 @@ __device__ __forceinline__ int wave_max_int(int v) {
   { const int o = dpp_keep<0x142>(v); v = o > v ? o : v; }
   { const int o = dpp_keep<0x143>(v); v = o > v ? o : v; }
   return __builtin_amdgcn_readlane(v, 63);
+}
+// Sum of v over the 64 lanes as a balanced binary tree on the same data path (neighbours, pairs of pairs ... inside each row of
+// 16, then rows 0 + 1 and 2 + 3, then the halves): lanes without a partner add +0.0 (bound_ctrl / a masked row keeps `old` = 0).
+// NOT the reference's order of addition: only for the sums whose value decides a branch under a certificate (wg_ql_guard.hpp,
+// whose guard_tree_sum is this order on the host).  Six dependent adds instead of a chain of n; result wave-uniform.
+template <int CTRL, int ROWS>
+__device__ __forceinline__ double dpp_zero(double v) {
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROWS, 0xf, true);
+  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROWS, 0xf, true);
+  return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ double wave_sum_tree(double v) {
+  v += dpp_zero<0x111, 0xf>(v);   // row_shr:1
+  v += dpp_zero<0x112, 0xf>(v);   // row_shr:2
+  v += dpp_zero<0x114, 0xf>(v);   // row_shr:4
+  v += dpp_zero<0x118, 0xf>(v);   // row_shr:8: lane 15 of every row holds the row's sum
+  v += dpp_zero<0x142, 0xa>(v);   // row_bcast:15 into rows 1 and 3
+  v += dpp_zero<0x143, 0xc>(v);   // row_bcast:31 into rows 2 and 3
+  return rl(v, 63);
 }
 // arg-max over the wave: larger v wins, equal v -> smaller idx.  idx < 0 = no candidate (then idx stays < 0).
 // Candidates must be finite.  Result is wave-uniform.
