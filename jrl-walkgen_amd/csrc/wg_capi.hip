@@ -763,6 +763,14 @@ int wg_mpc_configure_ctx(wg_ctx_t *ctx, const wg_model_t *model) {
     else if (v == "doubt") host_tables.ql_sums = wg::kSumsDoubt;
     else if (!v.empty() && v != "guarded") return fail(WG_ERR_BAD_ARG, "WG_QL_SUMS=%s: ordered, doubt or unset", e);
   }
+  // the compact view's norm chain of a sweep (tests and A/B; in bits 8 - 9 of the same word): unset or "seeded" = from seeds,
+  // checked once; "exact" = the exact chain throughout; "doubt" = the check reports a mismatch in every sweep
+  if (const char *e = getenv("WG_QL_NORMS")) {
+    const std::string v(e);
+    if (v == "exact") host_tables.ql_sums |= wg::kNormsExact;
+    else if (v == "doubt") host_tables.ql_sums |= wg::kNormsDoubt;
+    else if (!v.empty() && v != "seeded") return fail(WG_ERR_BAD_ARG, "WG_QL_NORMS=%s: seeded, exact, doubt or unset", e);
+  }
   if (!ctx->tables_dev) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ctx->tables_dev), sizeof(wg::TickTables)));
   if (!ctx->model_dev) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ctx->model_dev), sizeof(wg_model_t)));
   // a launch of an earlier configuration may still be reading the tables: this context's own launches, on whatever stream they

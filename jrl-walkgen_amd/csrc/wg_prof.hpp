@@ -24,7 +24,9 @@ enum ProfSlot : int {   // the numbers are the interface: tools/probe_phases.py 
   PS_TICK_COM = 39, PS_TICK_TRUNK = 40, PS_TICK_FEET = 41, PS_TICK_QUEUE = 42,
   // guarded sums (PT_COUNT2): local fallbacks at the dependence test, solves run again in the reference's order
   PS_N_FALLBACK = 43, PS_N_RERUN = 44,
-  PS_COUNT = 48            // 45 - 47: free
+  // the seeded norm chain (PT_SW_COUNT): sweeps of sweep_flat, those that took the seeded chain, those of them that fell back
+  PS_N_SWEEPS = 45, PS_N_SEEDED = 46, PS_N_SEED_FALLBACK = 47,
+  PS_COUNT = 48
 };
 
 #ifdef WG_PROFILE
@@ -32,7 +34,7 @@ __device__ unsigned long long g_prof[PS_COUNT];
 
 // ---- the solver's timers: what PT_DECL declares is what a phase function receives ----
 struct PtState {
-  unsigned long long acc[28] = {0}, cnt[4] = {0}, sw[3] = {0}, cnt2[2] = {0};
+  unsigned long long acc[28] = {0}, cnt[4] = {0}, sw[6] = {0}, cnt2[2] = {0};   // sw: three timers, then PS_N_SWEEPS ..
   unsigned long long last = clock64();
 };
 #define PT_DECL PtState pt;
@@ -44,11 +46,13 @@ struct PtState {
 #define PT_FLUSH do { if ((threadIdx.x & 63) == 0) { for (int k_ = 0; k_ < 28; ++k_) if (k_ < PS_TICK_PRE || k_ > PS_TICK_POST) atomicAdd(&g_prof[k_], pt.acc[k_]); \
                                                       for (int k_ = 0; k_ < 4; ++k_) atomicAdd(&g_prof[PS_N_ROUTE + k_], pt.cnt[k_]); \
                                                       for (int k_ = 0; k_ < 3; ++k_) atomicAdd(&g_prof[PS_SW_NORMS + k_], pt.sw[k_]); \
-                                                      for (int k_ = 0; k_ < 2; ++k_) atomicAdd(&g_prof[PS_N_FALLBACK + k_], pt.cnt2[k_]); } } while (0)
+                                                      for (int k_ = 0; k_ < 2; ++k_) atomicAdd(&g_prof[PS_N_FALLBACK + k_], pt.cnt2[k_]); \
+                                                      for (int k_ = 0; k_ < 3; ++k_) atomicAdd(&g_prof[PS_N_SWEEPS + k_], pt.sw[3 + k_]); } } while (0)
 #define PT_SW_PARAM , unsigned long long *ptsw = nullptr
 #define PT_SW_ARG , pt.sw
 #define PT_SW(k) do { if (ptsw) { unsigned long long t_ = clock64(); ptsw[(k) - PS_SW_NORMS] += t_ - ptsw_last; ptsw_last = t_; } } while (0)
 #define PT_SW_BEGIN unsigned long long ptsw_last = clock64();
+#define PT_SW_COUNT(k) do { if (ptsw) ptsw[3 + (k) - PS_N_SWEEPS]++; } while (0)
 // event counters 28..31: kept in registers and flushed once (a global atomic per event would show up in the phase it sits in)
 #define PT_COUNT(k) do { pt.cnt[(k) - PS_N_ROUTE]++; } while (0)
 #define PT_COUNT2(k) do { pt.cnt2[(k) - PS_N_FALLBACK]++; } while (0)
@@ -82,6 +86,7 @@ struct TkState {
 #define PT_SW_ARG
 #define PT_SW(k) do {} while (0)
 #define PT_SW_BEGIN
+#define PT_SW_COUNT(k) do {} while (0)
 #define PT_COUNT(k) do {} while (0)
 #define PT_COUNT2(k) do {} while (0)
 #define PT_LOCAL_BEGIN

@@ -47,7 +47,7 @@ namespace wg {
 // one row of Z per lane (n <= 64): the branch-free, prefetching form -- the compact view always, the dense view by size (the
 // element view is built for n > 64: it keeps the one form it needs, its kernel is large enough as it is)
 #define WG_SWEEP(q, s, nu, nact, lane) \
-  do { if (P::kNM > 0 || (!P::kRowOps && q.n <= 64)) sweep_flat<P::kFixedLdz>(q, s, nu, nact, lane PT_SW_ARG); else sweep<(P::kRowOps ? WG_ELEM_GRP : 8), P::kWideN>(q, s, nu, nact, lane); } while (0)
+  do { if (P::kNM > 0 || (!P::kRowOps && q.n <= 64)) sweep_flat<P::kFixedLdz, SeededNormsOf<P>::value>(q, s, nu, nact, lane, nmode PT_SW_ARG); else sweep<(P::kRowOps ? WG_ELEM_GRP : 8), P::kWideN>(q, s, nu, nact, lane); } while (0)
 
 // the reference's tests of one candidate row k in its order, :1256-1282 (cvmax starts at 0); reads wak, sum, temp of the scan body
 // it sits in and skips to its next row with `continue`.  A macro: as a function it changed the tick kernels' code
@@ -76,7 +76,10 @@ __device__ __forceinline__ QlResult ql_solve(const QlView &q, P &prob, double vs
   // starts from the dirtiest state a first pass can leave.
   constexpr bool kGuard = GuardedSumsOf<P>::value;
   [[maybe_unused]] int gmode = kSumsOrdered;
-  if constexpr (kGuard) gmode = uni(prob.sums_mode);
+  if constexpr (kGuard) gmode = uni(prob.sums_mode) & kSumsMask;
+  // the sweep's norm chain (the compact view; wg_ql_norms.hpp): seeded and checked, exact throughout, or doubted in every sweep
+  [[maybe_unused]] int nmode = kNormsExact;
+  if constexpr (SeededNormsOf<P>::value) nmode = uni(prob.sums_mode) & kNormsMask;
   int lane = wg_lane();
   const int n = q.n, m = q.m, me = q.me, mn = q.mn;
   QlResult out;
@@ -1034,7 +1037,7 @@ __device__ __forceinline__ QlResult ql_solve_guarded(const QlView &q, P &prob, d
   for (;;) {
     r = ql_solve(q, prob, vsmall, hist, hist_cap);
     if (!WG_UBOOL(r.ifail == kQlDoubt)) break;
-    prob.sums_mode = kSumsOrdered;
+    prob.sums_mode = (prob.sums_mode & ~kSumsMask) | kSumsOrdered;   // the other bits of the word (the norms' mode) stay
   }
   return r;
 }

@@ -244,6 +244,7 @@ struct HerdtProb {
   static constexpr bool kWideN = false;
   static constexpr int kFixedLdz = kNM | 1;    // Z in LDS, leading dimension of carve_fixed<kNM, ...>
   static constexpr bool kGuardedSums = true;   // the decision-only sums as trees over the lanes, under wg_ql_guard.hpp's certificates
+  static constexpr bool kSeededNorms = true;   // the sweep's norm chain from lane-parallel seeds, checked once (wg_ql_norms.hpp)
   static_assert(4 * NH == 64, "one CoP row per lane needs 4N == 64");
   // ---- LDS / global tables (wave-uniform pointers) ----
   const double *Qb;       // global (L1/L2-resident constant of the model), NH x kQbLd
@@ -258,7 +259,8 @@ struct HerdtProb {
   double diag_b;          // the constant block's contribution to ql0002's diagonal test
   int blocks_ok;
   int ns;
-  int sums_mode;          // kSumsGuarded / kSumsOrdered / kSumsDoubt (TickTables::ql_sums: the host's WG_QL_SUMS at configure time)
+  int sums_mode;          // kSumsGuarded / kSumsOrdered / kSumsDoubt (TickTables::ql_sums: the host's WG_QL_SUMS at configure time),
+                          // and in bits 8 - 9 kNormsSeeded / kNormsExact / kNormsDoubt (WG_QL_NORMS)
   // ---- per-lane registers: the lane's own constraint rows ----
   double ax[NH], ay[NH];  // CoP row (lane+1): x- and y-jerk parts
   int fj;                 // its two foot-variable entries sit in columns 2N+fj, 2N+ns+fj (fj < 0: none); their values fa(), fb()

@@ -74,6 +74,13 @@ __device__ __forceinline__ double givens_norm_fast(double p, double qq) {
   const double x = 1.0 + d * d;
   return t * sqrt_1to2(x);
 }
+}  // namespace wg
+// the same chain from seeds made ahead of it and checked once against givens_norm_fast: one text for host and device
+#define WG_NORMS_FN __device__ __forceinline__
+#define WG_NORMS_RSQ(x) __builtin_amdgcn_rsq(x)
+#define WG_NORMS_EXACT(p, q) ::wg::givens_norm_fast(p, q)
+#include "wg_ql_norms.hpp"
+namespace wg {
 // every entry of s[lo, hi) is zero or has its magnitude in [2^-400, 2^400] (then every norm of a sweep over them, being at
 // least its larger operand and at most sqrt(n) times the largest entry, is zero or in [2^-400, 2^404]); wave-uniform
 template <bool kOnePass = false>                          // kOnePass: hi - lo <= 64 (the caller's n <= 64)
@@ -485,17 +492,92 @@ __device__ __forceinline__ double ordered_sum_lds_rolled(double term, double *sc
 //   phase 1  chain of rotation norms (all lanes redundantly; s[c-1] prefetched); lane c records its rotation;
 //   phase 2  lane c turns (p, q, norm) into (ga, gb) and publishes the pair in LDS;
 //   phase 3  lane i carries row i of Z through the rotations.
-template <int kLdzC = 0>                                     // > 0: Z lives in LDS with this leading dimension (every compile-time-bounded view)
-__device__ __forceinline__ void sweep_flat(const QlView &q, double *s, int nu, int nact, int lane PT_SW_PARAM) {
+//   phase 1, seeded (kSeeded: the compact N = 16 view; wg_ql_norms.hpp): from the last non-zero entry of s on the chain runs from
+//            seeds -- 1/t and 1/sqrt(x) of every rotation, made lane-parallel from a scan of the squares and handed over through
+//            sc0 / sc1 (dead until phase 2 writes the pairs there) -- in 11 dependent instructions per rotation instead of 23;
+//            afterwards lane c recomputes its rotation in the exact form from the operands phase 2 loads anyway and compares
+//            bits.  One ballot; on a mismatch (or nmode == kNormsDoubt) the exact code below runs as if nothing had happened:
+//            a flag and a forward edge.  nmode == kNormsExact: the exact code alone.
+template <int kLdzC = 0, bool kSeeded = false>               // kLdzC > 0: Z lives in LDS with this leading dimension (every compile-time-bounded view)
+__device__ __forceinline__ void sweep_flat(const QlView &q, double *s, int nu, int nact, int lane, [[maybe_unused]] int nmode = kNormsExact PT_SW_PARAM) {
   const int n = q.n;
   if (nu - 1 <= nact) return;
   PT_SW_BEGIN
+  PT_SW_COUNT(PS_N_SWEEPS);
   // Phase 1 leaves ONE value per rotation behind -- `cur` as it leaves rotation c, in chain[c - 1] -- from which lane c
   // rebuilds its rotation afterwards: q = the value that entered (chain[c], or s[nu-1] for the first one), p = s[c-1]
   // (untouched until phase 2), norm = chain[c-1] when q != 0 (then cur = norm), skipped when q == 0 (then cur = p).
   // givens_norm runs unguarded on q == 0: its result (|p|, or NaN for 0/0) is discarded by the select.
   double *chain = q.sc2;                                    // nu <= n entries
-  WG_REP(3)
+  // seeded chain: the operands of lane c's rotation as the check loaded them, and whether the check let them through
+  [[maybe_unused]] bool seeded_ok = false;
+  [[maybe_unused]] double sdP = 0.0, sdQ = 0.0, sdN = 0.0;
+  WG_REP(3) {
+  if constexpr (kSeeded) {
+    seeded_ok = false;
+    if (nmode != kNormsExact && sweep_range_ok<true>(s, nact, nu, lane)) {
+      PT_SW_COUNT(PS_N_SEEDED);
+      typedef __attribute__((address_space(3))) double lds_f64;
+      double *seeds = q.sc0;                                // pairs {r, y} of rotation c at 2 c, 2 c + 1 (sc0 and sc1 are adjacent)
+      int top;                                              // s[top - 1]: the last non-zero entry (nact + 1 when there is none above s[nact])
+      {
+        // lane L makes the seeds of rotation c = nu - 1 - L: its entry s[c] squared, the sums of the squares of s[c .. nu) by a
+        // prefix scan over the lanes, and p = s[c - 1].  Lanes without a rotation compute on entries of the sweep and store nothing.
+        // Zeros at the end of s (structural zeros of Z: three sweeps in ten end in one) are rotations the reference skips,
+        // each handing its p on: their records are copies of s, written here, and the chain starts at the last non-zero entry.
+        const int j = nu - 1 - lane;
+        const bool in = j >= nact;
+        const double sj = s[in ? j : nact], pj = s[j > nact ? j - 1 : nact];
+        const unsigned long long nz = __ballot(in && j > nact && sj != 0.0);
+        top = nz ? nu - __builtin_ctzll(nz) : nact + 1;
+        if (in && j >= top - 1 && j < nu - 1) chain[j] = sj;
+        const double s2 = wave_prefix_sum(in ? sj * sj : 0.0);
+        const NormSeed sd = norms_seed(pj * pj, s2);
+        if (j > nact && j < top) { seeds[2 * j] = sd.r; seeds[2 * j + 1] = sd.y; }
+      }
+      WG_WSYNC();
+      // the chain, unrolled by two as below; the seeds of a rotation are fetched with its operand, one rotation ahead, through a
+      // third walking pointer (the pair fetched ahead of the last rotation belongs to rotation nact: inside sc0, never used)
+      const int rots = top - 1 - nact;                      // rotations below the last non-zero entry
+      if (rots > 0) {
+        double cur = s[top - 1];
+        double pa = s[top - 2], pb;
+        const lds_f64 *sp = (const lds_f64 *)(s + (top - 4));      // sp[1] = s[c - 2], sp[0] = s[c - 3]
+        lds_f64 *cp = (lds_f64 *)(chain + (top - 3));              // cp[1] = chain[c - 1], cp[0] = chain[c - 2]
+        const lds_f64 *dp = (const lds_f64 *)(seeds + 2 * (top - 3));   // dp[2], dp[3]: rotation c - 1;  dp[0], dp[1]: rotation c - 2
+        asm volatile("" : "+v"(sp), "+v"(cp), "+v"(dp));
+        double ra = dp[4], ya = dp[5], rb, yb;
+        auto step = [](double p, double cur_in, double r, double y) -> double {
+          double t, a;
+          asm("v_max_f64 %0, |%1|, |%2|" : "=v"(t) : "v"(p), "v"(cur_in));
+          asm("v_min_f64 %0, |%1|, |%2|" : "=v"(a) : "v"(p), "v"(cur_in));
+          return norms_step(t, a, r, y);
+        };
+        for (int k = rots >> 1; k > 0; --k) {
+          pb = sp[1]; rb = dp[2]; yb = dp[3];
+          cur = step(pa, cur, ra, ya); cp[1] = cur;
+          pa = sp[0]; ra = dp[0]; ya = dp[1];
+          cur = step(pb, cur, rb, yb); cp[0] = cur;
+          sp -= 2; cp -= 2; dp -= 4;
+        }
+        if (rots & 1) { cur = step(pa, cur, ra, ya); cp[1] = cur; }
+      }
+      WG_WSYNC();
+      // the check: lane c's rotation in the exact form, from the operands phase 2 needs anyway (lanes without one shadow lane nu - 1)
+      {
+        const bool mine = lane > nact && lane < nu;
+        const int c = mine ? lane : nu - 1;
+        sdP = s[c - 1];
+        sdQ = (c == nu - 1) ? s[nu - 1] : chain[c];
+        sdN = chain[c - 1];
+        const bool bad = !norms_rotation_ok(sdP, sdQ, sdN);
+        seeded_ok = (__ballot(bad) == 0ull) && nmode != kNormsDoubt;
+      }
+      if (!seeded_ok) PT_SW_COUNT(PS_N_SEED_FALLBACK);
+    }
+  }
+  if (kSeeded && seeded_ok) {
+  } else
   if (sweep_range_ok<true>(s, nact, nu, lane)) {
     // the usual case: the shorter norm; unrolled by two so that handing the prefetched operand on is a renaming.  The operand
     // and the record are reached through two walking pointers kept in vector registers (constant offsets in the ds instructions,
@@ -544,10 +626,13 @@ __device__ __forceinline__ void sweep_flat(const QlView &q, double *s, int nu, i
       p = p_next;
     }
   }
+  }   // WG_REP(3)
   WG_WSYNC();
   PT_SW(PS_SW_NORMS);
   double myP = 0.0, myQ = 0.0, myN = 0.0;
-  {
+  if (kSeeded && seeded_ok) {                               // the check has loaded them
+    myP = sdP; myQ = sdQ; myN = (sdQ == 0.0) ? 0.0 : sdN;
+  } else {
     const bool mine = lane > nact && lane < nu;
     const int c = mine ? lane : nu - 1;
     myP = s[c - 1];

@@ -242,7 +242,13 @@ template <class P> struct ActiveParamsOf<P, typename std::enable_if<P::kCompact>
 // (kSumsGuarded / kSumsOrdered / kSumsDoubt); every other policy keeps the reference's order and compiles none of it
 template <class P, class = void> struct GuardedSumsOf { static constexpr bool value = false; };
 template <class P> struct GuardedSumsOf<P, typename std::enable_if<P::kGuardedSums>::type> { static constexpr bool value = true; };
-enum : int { kSumsGuarded = 0, kSumsOrdered = 1, kSumsDoubt = 2 };
+enum : int { kSumsGuarded = 0, kSumsOrdered = 1, kSumsDoubt = 2, kSumsMask = 3 };
+// the sweep's norm chain from seeds, checked once (wg_ql_norms.hpp): a policy that declares kSeededNorms (it carries
+// `sums_mode` as well) keeps the mode in bits 8 - 9 of that word -- kNormsSeeded / kNormsExact (the exact chain throughout) /
+// kNormsDoubt (tests: the check reports a mismatch in every sweep); every other policy compiles none of it
+template <class P, class = void> struct SeededNormsOf { static constexpr bool value = false; };
+template <class P> struct SeededNormsOf<P, typename std::enable_if<P::kSeededNorms>::type> { static constexpr bool value = true; };
+enum : int { kNormsSeeded = 0, kNormsExact = 1 << 8, kNormsDoubt = 2 << 8, kNormsMask = 3 << 8 };
 constexpr int kQlDoubt = -7778;                            // QlResult::ifail of a guarded solve that must be run again (ql_solve_guarded)
 
 struct QlResult {

@@ -56,7 +56,7 @@ struct TickTables {
   double Z2[4 * kNMaxH * kNMaxH];                 // its inverse, column-major ld 2N, qld.cpp:937-975
   double diag_b;                                  // diagonal test over the constant block, qld.cpp:814-843
   int blocks_ok;
-  int ql_sums;                                    // the compact view's decision-only sums (wg_ql_view.hpp: kSumsGuarded / Ordered / Doubt)
+  int ql_sums;                                    // the compact view's decision-only sums (wg_ql_view.hpp: kSumsGuarded / Ordered / Doubt) and, in bits 8 - 9, its sweeps' norm chain (kNormsSeeded / Exact / Doubt)
   // Z2 is blockdiag(Zb, Zb) with zeros in between, but the recurrence leaves SIGNED zeros in the upper-right block
   // (-(x * 0) / r); bit i + j*N = sign of Z2(i, N + j).  The kernel fetches only Zb and re-creates the rest from this.
   unsigned long long z2_cross_sign[(kNMaxH * kNMaxH + 63) / 64];

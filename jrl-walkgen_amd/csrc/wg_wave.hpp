@@ -142,6 +142,19 @@ __device__ __forceinline__ double wave_sum_tree(double v) {
   v += dpp_zero<0x143, 0xc>(v);   // row_bcast:31 into rows 2 and 3
   return rl(v, 63);
 }
+// Inclusive prefix sums over the lanes on the same data path: lane i ends with v[0] + .. + v[i], added inside each row of 16 by
+// doubling distances, then row 0's total into row 1 and row 2's into row 3, then the lower half's total into the upper half
+// (wave_sum_tree's steps without the read-out).  NOT an order of the reference's: for values that only seed a computation checked
+// afterwards (wg_ql_norms.hpp, whose norms_prefix_scan is this order on the host).
+__device__ __forceinline__ double wave_prefix_sum(double v) {
+  v += dpp_zero<0x111, 0xf>(v);   // row_shr:1
+  v += dpp_zero<0x112, 0xf>(v);   // row_shr:2
+  v += dpp_zero<0x114, 0xf>(v);   // row_shr:4
+  v += dpp_zero<0x118, 0xf>(v);   // row_shr:8: every lane holds the prefix sum inside its row
+  v += dpp_zero<0x142, 0xa>(v);   // row_bcast:15 into rows 1 and 3
+  v += dpp_zero<0x143, 0xc>(v);   // row_bcast:31 into rows 2 and 3
+  return v;
+}
 // arg-max over the wave: larger v wins, equal v -> smaller idx.  idx < 0 = no candidate (then idx stays < 0).
 // Candidates must be finite.  Result is wave-uniform.
 __device__ __forceinline__ void wave_argmax_first(double &v, int &idx) {

@@ -33,6 +33,7 @@ names = ["norms", "diagchk", "chol", "inverse", "resid/reset+shift", "ZT*ww(resi
 tot = v[:28].sum()
 print(f"gait-ticks={n} mean QL iters={its/n:.1f} cycles/tick={tot/n:.0f}  route decisions/tick={v[28]/n:.1f} of which coordinate checks {v[29]/n:.2f}, dependent routes {v[30]/n:.2f}")
 print(f"   guarded sums (compact view): local fallbacks at the dependence test {v[43]/n:.2f} per tick, solves run again in the reference's order {v[44]/n:.2f} per tick")
+print(f"   seeded norm chain (compact view): sweeps {v[45]/n:.2f} per tick, of which from seeds {v[46]/n:.2f}, of which run again in the exact form {v[47]/n:.4f}")
 print(f"   of 'inverse' (factor): constant blocks into LDS {v[2]/n:.0f} cyc/tick, border rows of R {v[31]/n:.0f} cyc/tick")
 for k, nme in enumerate(names):
     print(f"{k:2d} {nme:22s} {v[k]/n:12.0f} cyc/tick  {100*v[k]/tot:5.1f}%")
