@@ -1042,6 +1042,69 @@ int wg_dimitrov_follow_fleet_dev(int B, const wg_dimitrov_fleet_t *fleet, int qc
                                  int tick_cap, int max_ticks, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs,
                                  int *ran_out, int max_iter, void *hip_stream);
 
+/* Herdt-2010 fleets with a model per gait ------------------------------------------------------------------------------------
+ *
+ * wg_mpc_configure gives a context one model.  A fleet whose gaits differ in their models -- robots of different size, a load
+ * sweep over com_height_qp, a Monte-Carlo run over alpha / beta / gamma, sole sizes, margins, hip limits and step timing drawn
+ * per gait -- carries them as BLOCKS instead: one opaque block of wg_mpc_block_bytes() bytes per model (76 032 bytes, a multiple
+ * of 128, whatever N is: the tables are laid out for the largest horizon), holding the wg_model_t as given, the tick tables
+ * wg_mpc_configure uploads behind it (S, U, Q_b, the packed factor R2 of blockdiag(Q_b, Q_b), its inverse Z2, the diagonal test,
+ * the cross-block sign words) and zeros everywhere else, so that blocks compare as bytes.  The arithmetic is one text
+ * (csrc/wg_tick_tables_math.hpp) compiled for the host and for the device: host blocks and device blocks are the same bytes.
+ * When the constant block has no factor (blocks_ok == 0: the diagonal test or a pivot fails) R2, Z2 and the sign words are zero;
+ * the tick then factors every QP itself, as it does for a configured model.
+ *
+ * wg_mpc_block(model, block): host arithmetic, no device call.  WG_ERR_BAD_ARG and an ALL-ZERO block for a model that is refused:
+ *   whatever wg_mpc_configure refuses (N outside 2 .. 32, T / Tctrl != 20, more than four previewed steps); either
+ *   WG_FLAG_GRAMIAN_MFMA_* flag (not available to fleets); a T, Tctrl, com_height_qp, alpha, beta, gamma or step_period that is not
+ *   finite.  The compact view's WG_QL_SUMS / WG_QL_NORMS knobs are read from the environment at the call, as wg_mpc_configure does.
+ * wg_mpc_block_unpack(block, ...): host arithmetic on a HOST copy of a block -- the model and the arrays at the block's own N
+ *   (Sv, Sz: N x 3; Uv, Uz, Qb: N x N row-major; R2: 2N (2N + 1) / 2, packed by columns; Z2: 2N x 2N column-major).  Any pointer
+ *   but block may be NULL.  WG_ERR_BAD_ARG for a refused (all-zero) block.
+ * wg_mpc_blocks_batch_dev(M, models, blocks, status, hip_stream): M models (DEVICE array of wg_model_t) into M blocks (DEVICE),
+ *   one wavefront per model; status[m] (DEVICE) is what wg_mpc_block returns for model m.  Every byte of block m is written once,
+ *   by its own wavefront; a refused model gets an all-zero block, never a NaN.  Asynchronous on hip_stream; keeps nothing in the
+ *   context.  wg_mpc_blocks_batch is the same call with HOST pointers, staged through the context's stream.
+ *
+ * The fleet descriptor is read on the host; blocks (M of them) and model_of (an int per gait) are DEVICE pointers.  `base`
+ * decides the launch plan -- the problem view, the LDS and slot sizes, the column cap -- exactly as wg_mpc_configure(base) would;
+ * it need not be one of the models.
+ *
+ * wg_mpc_tick_fleet_dev / wg_mpc_run_fleet_dev are wg_mpc_tick_batch_dev / wg_mpc_run_sched_dev with the fleet after B: gait g
+ * runs with blocks[model_of[g]], its model fields and its tables.  They read nothing of the context's configured model (no
+ * wg_mpc_configure is needed) and go through the same launcher as their twins: the context's slots, run buffer and launch
+ * ordering, the longest-solve-first order, wg_mpc_reserve's sizing.  The run form always hands gaits over inside an XCD;
+ * vref_sched == NULL is the unstaged run (wg_mpc_run_batch_dev).
+ * CONTRACT: gait g of a fleet launch leaves, byte for byte, the state, outs rows, diag rows and hist row that a context
+ * configured with model model_of[g] leaves for it through the twin call -- whichever view the fleet runs in.
+ * One launch shape: a gait is accepted when model_of[g] is in [0, M), its block is a good one, its N, T and Tctrl equal base's
+ * bit for bit, and its model is within the plan's step capacity: a compact plan (N == 16 and N T <= 2 step_period + 1e-12 for
+ * base) holds two previewed steps and accepts only models for which the same inequality holds; every other plan is sized for
+ * four and accepts all.  Any other gait is REFUSED: each of its ticks writes ifail = WG_IFAIL_NO_MODEL and five zeros into its
+ * six diagnostic ints (its diag row, and its out struct if there is one), 0 into the iteration count that orders the next
+ * launch, and nothing else -- no byte of its state changes (no clock advance, no staged reference), in a run launch it sits every
+ * tick out, and no other gait notices.
+ * Host-side refusals (WG_ERR_BAD_ARG before any device call): a NULL fleet, blocks or model_of; M < 1; B < 0; a base that
+ * wg_mpc_block would refuse; whatever the twin refuses.  B == 0 is WG_OK.
+ * Added without a change of wg_abi_version(): detect by symbol. */
+#define WG_IFAIL_NO_MODEL (-1)       /* QL's own codes are >= 0 */
+typedef struct wg_mpc_fleet {
+  wg_model_t base;
+  int M, pad_;
+  const void *blocks;
+  const int *model_of;
+} wg_mpc_fleet_t;
+size_t wg_mpc_block_bytes(void);
+int wg_mpc_block(const wg_model_t *model, void *block);
+int wg_mpc_block_unpack(const void *block, wg_model_t *model, double *Sv, double *Sz, double *Uv, double *Uz, double *Qb,
+                        double *R2, double *Z2, double *diag_b, int *blocks_ok);
+int wg_mpc_blocks_batch_dev(int M, const wg_model_t *models, void *blocks, int *status, void *hip_stream);
+int wg_mpc_blocks_batch(int M, const wg_model_t *models, void *blocks, int *status);
+int wg_mpc_tick_fleet_dev(int B, const wg_mpc_fleet_t *fleet, wg_gait_state_t *states, wg_tick_out_t *outs, int *diag,
+                          int advance_calls, int *hist, int hist_cap, int *hist_len, void *hip_stream);
+int wg_mpc_run_fleet_dev(int B, const wg_mpc_fleet_t *fleet, wg_gait_state_t *states, int n_ticks, int advance_calls,
+                         const double *vref_sched, int period, wg_tick_out_t *outs, int *diag, void *hip_stream);
+
 /* Invariant Hessian block on the matrix cores, batched over models -----------------------------------------------------
  *
  * wg_gramian_batch computes, for B models that differ in QP sampling period T[b] and CoM height h[b],
@@ -1191,6 +1254,13 @@ int wg_dimitrov_follow_fleet_dev_ctx(wg_ctx_t *ctx, int B, const wg_dimitrov_fle
                                      const wg_zmpdisc_state_t *walk, int flags, double *clock, int *ticks, int tick_cap,
                                      int max_ticks, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int *ran_out,
                                      int max_iter, void *hip_stream);
+int wg_mpc_blocks_batch_dev_ctx(wg_ctx_t *ctx, int M, const wg_model_t *models, void *blocks, int *status, void *hip_stream);
+int wg_mpc_blocks_batch_ctx(wg_ctx_t *ctx, int M, const wg_model_t *models, void *blocks, int *status);
+int wg_mpc_tick_fleet_dev_ctx(wg_ctx_t *ctx, int B, const wg_mpc_fleet_t *fleet, wg_gait_state_t *states, wg_tick_out_t *outs,
+                              int *diag, int advance_calls, int *hist, int hist_cap, int *hist_len, void *hip_stream);
+int wg_mpc_run_fleet_dev_ctx(wg_ctx_t *ctx, int B, const wg_mpc_fleet_t *fleet, wg_gait_state_t *states, int n_ticks,
+                             int advance_calls, const double *vref_sched, int period, wg_tick_out_t *outs, int *diag,
+                             void *hip_stream);
 
 #ifdef __cplusplus
 }

@@ -547,18 +547,8 @@ inline int tick_max_m(const wg_model_t &m) { return 1 + 4 * m.N + 5 * tick_smax(
 //    0  dense    G and A as LDS matrices: on request (WG_TICK_DENSE=1, while they fit the CU's 160 KiB) and for
 //                wg_mpc_assemble_batch, which writes the QP out
 // WG_TICK_VIEW=element sends N == 16 through the element view as well (tests).
-// The most steps a horizon can preview, from SupportFSM::set_support_state as wg_tick_device.hpp states it: a previewed support
-// changes at the first instant pi with time + 1e-6 + pi*T >= time_limit, and every change sets time_limit = time + pi*T +
-// step_period - T/10, so two changes are k = ceil((step_period - T/10 - 1e-6) / T) instants apart.  A change at pi = 1 is not
-// counted (`if (pi != 1) ++step_number`) and one at pi = 0 belongs to the current support: the earliest counted change is at
-// pi = 2, the most a horizon of N instants holds is 1 + floor((N - 2) / k).  The 1e-9 keeps k from being rounded UP past the
-// FSM's own figure (a smaller k only refuses more).  The kernels hold wg::kSMax steps: wg_mpc_configure refuses models beyond.
-inline int tick_max_prw_steps(const wg_model_t &m) {
-  const double q = (m.step_period - m.T / 10.0 - 1e-6) / m.T - 1e-9;
-  if (!(q == q)) return m.N;                                       // NaN: refuse
-  const int k = q <= 1.0 ? 1 : (q >= (double)m.N ? m.N : (int)ceil(q));
-  return 1 + (m.N - 2) / k;
-}
+// the most steps a horizon can preview (wg_tick_tables_math.hpp): the kernels hold wg::kSMax, wg_mpc_configure refuses models beyond
+inline int tick_max_prw_steps(const wg_model_t &m) { return wg::tt_max_prw_steps(m); }
 inline bool tick_compact(const wg_model_t &m) {
   const char *v = getenv("WG_TICK_VIEW");
   return m.N == 16 && m.N * m.T <= 2.0 * m.step_period + 1e-12 && !env_flag("WG_TICK_DENSE", false) && !(v && *v);
@@ -692,6 +682,29 @@ inline size_t run_buf_bytes(int B) { return sizeof(wg_xrun_ctl) + (size_t)kXcds 
 // hand-over inside one XCD (default) or through one device-wide queue (WG_RUN_QUEUE=global: A/B tests)
 inline bool run_queue_xcd() { const char *e = getenv("WG_RUN_QUEUE"); return !e || e[0] != 'g'; }
 
+// TickTables::ql_sums from the environment, read at the call (wg_mpc_configure, wg_mpc_block*): tests and A/B.
+int tick_ql_knobs(int *out) {
+  int k = 0;
+  // the compact view's decision-only sums: unset = guarded by certificates, "ordered" = the reference's order throughout,
+  // "doubt" = every dependence test falls back and every solve is run twice
+  if (const char *e = getenv("WG_QL_SUMS")) {
+    const std::string v(e);
+    if (v == "ordered") k = wg::kSumsOrdered;
+    else if (v == "doubt") k = wg::kSumsDoubt;
+    else if (!v.empty() && v != "guarded") return fail(WG_ERR_BAD_ARG, "WG_QL_SUMS=%s: ordered, doubt or unset", e);
+  }
+  // the compact view's norm chain of a sweep (in bits 8 - 9 of the same word): unset or "seeded" = from seeds, checked once;
+  // "exact" = the exact chain throughout; "doubt" = the check reports a mismatch in every sweep
+  if (const char *e = getenv("WG_QL_NORMS")) {
+    const std::string v(e);
+    if (v == "exact") k |= wg::kNormsExact;
+    else if (v == "doubt") k |= wg::kNormsDoubt;
+    else if (!v.empty() && v != "seeded") return fail(WG_ERR_BAD_ARG, "WG_QL_NORMS=%s: seeded, exact, doubt or unset", e);
+  }
+  *out = k;
+  return WG_OK;
+}
+
 int tick_check(wg_ctx *ctx, int B, const wg_gait_state_t *states) {
   if (int rc = use_ctx(ctx)) return rc;
   if (!ctx->model_set) return fail(WG_ERR_BAD_ARG, "wg_mpc_configure() has not been called on this context");
@@ -755,22 +768,7 @@ int wg_mpc_configure_ctx(wg_ctx_t *ctx, const wg_model_t *model) {
   wg::build_tables(*model, host_tables, qb.empty() ? nullptr : qb.data());
   if (!host_tables.blocks_ok && !qb.empty())
     return fail(WG_ERR_BAD_ARG, "the matrix-core Gramian is not positive definite enough for ql0002's factorisation");
-  // the compact view's decision-only sums (tests and A/B; read here, once per configuration): unset = guarded by certificates,
-  // "ordered" = the reference's order throughout, "doubt" = every dependence test falls back and every solve is run twice
-  if (const char *e = getenv("WG_QL_SUMS")) {
-    const std::string v(e);
-    if (v == "ordered") host_tables.ql_sums = wg::kSumsOrdered;
-    else if (v == "doubt") host_tables.ql_sums = wg::kSumsDoubt;
-    else if (!v.empty() && v != "guarded") return fail(WG_ERR_BAD_ARG, "WG_QL_SUMS=%s: ordered, doubt or unset", e);
-  }
-  // the compact view's norm chain of a sweep (tests and A/B; in bits 8 - 9 of the same word): unset or "seeded" = from seeds,
-  // checked once; "exact" = the exact chain throughout; "doubt" = the check reports a mismatch in every sweep
-  if (const char *e = getenv("WG_QL_NORMS")) {
-    const std::string v(e);
-    if (v == "exact") host_tables.ql_sums |= wg::kNormsExact;
-    else if (v == "doubt") host_tables.ql_sums |= wg::kNormsDoubt;
-    else if (!v.empty() && v != "seeded") return fail(WG_ERR_BAD_ARG, "WG_QL_NORMS=%s: seeded, exact, doubt or unset", e);
-  }
+  if (int rc = tick_ql_knobs(&host_tables.ql_sums)) return rc;
   if (!ctx->tables_dev) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ctx->tables_dev), sizeof(wg::TickTables)));
   if (!ctx->model_dev) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ctx->model_dev), sizeof(wg_model_t)));
   // a launch of an earlier configuration may still be reading the tables: this context's own launches, on whatever stream they
@@ -811,14 +809,66 @@ int wg_mpc_reserve_ctx(wg_ctx_t *ctx, int max_gaits) {
   return ctx->run_buf.reserve(run_buf_bytes(max_gaits));
 }
 
+/* ---- a model per gait: blocks (the model and its tick tables as opaque bytes, wg_tick_tables_math.hpp) ---------------------- */
+size_t wg_mpc_block_bytes(void) { return wg::kMpcBlockBytes; }
+
+// host arithmetic (tt_build through build_tables, as wg_mpc_configure runs it); no device call
+int wg_mpc_block(const wg_model_t *model, void *block) {
+  if (!block) return fail(WG_ERR_BAD_ARG, "null block");
+  memset(block, 0, wg::kMpcBlockBytes);
+  if (!model) return fail(WG_ERR_BAD_ARG, "null model");
+  if (!wg::tt_model_ok(*model))
+    return fail(WG_ERR_BAD_ARG, "not a model a block can be made of: N outside [2,%d], T/Tctrl != %d, more than %d previewed steps, a "
+                                "matrix-core Gramian flag, or a T, Tctrl, com_height_qp, alpha, beta, gamma or step_period that is not finite",
+                wg::kNMaxH, WG_SAMPLES_PER_TICK, wg::kSMax);
+  int knobs = 0;
+  if (int rc = tick_ql_knobs(&knobs)) return rc;
+  std::unique_ptr<wg::TickTables> t(new wg::TickTables);
+  wg::build_tables(*model, *t);
+  t->ql_sums = knobs;
+  memcpy(block, model, sizeof *model);
+  memcpy(static_cast<char *>(block) + wg::kMpcBlockTables, t.get(), sizeof *t);
+  return WG_OK;
+}
+
+int wg_mpc_block_unpack(const void *block, wg_model_t *model, double *Sv, double *Sz, double *Uv, double *Uz, double *Qb, double *R2, double *Z2, double *diag_b, int *blocks_ok) {
+  if (!block) return fail(WG_ERR_BAD_ARG, "null block");
+  const wg_model_t &m = *static_cast<const wg_model_t *>(block);
+  if (m.N < 2 || m.N > wg::kNMaxH) return fail(WG_ERR_BAD_ARG, "not a block of a model that exists (N = %d)", m.N);
+  const wg::TickTables &t = *reinterpret_cast<const wg::TickTables *>(static_cast<const char *>(block) + wg::kMpcBlockTables);
+  const size_t N = (size_t)m.N, M2 = 2 * N;
+  if (model) *model = m;
+  if (Sv) memcpy(Sv, t.Sv, 8 * N * 3);
+  if (Sz) memcpy(Sz, t.Sz, 8 * N * 3);
+  for (size_t i = 0; i < N; i++) {                       // the tables are laid out for kNMaxH: row by row
+    if (Uv) memcpy(Uv + i * N, t.Uv[i], 8 * N);
+    if (Uz) memcpy(Uz + i * N, t.Uz[i], 8 * N);
+    if (Qb) memcpy(Qb + i * N, t.Qb[i], 8 * N);
+  }
+  if (R2) memcpy(R2, t.R2, 8 * (M2 * (M2 + 1) / 2));
+  if (Z2) memcpy(Z2, t.Z2, 8 * M2 * M2);
+  if (diag_b) *diag_b = t.diag_b;
+  if (blocks_ok) *blocks_ok = t.blocks_ok;
+  return WG_OK;
+}
+
 }  // extern "C"
 namespace {
-int tick_launch(wg_ctx_t *ctx, int B, wg_gait_state_t *states, wg_tick_out_t *outs, int *diag, int advance_calls, int *hist, int hist_cap, int *hist_len, void *hip_stream, wg_gait_state_t *host_states, int *host_done) {
-  if (int rc = tick_check(ctx, B, states)) return rc;
+// what the fleet launches refuse on the host, before any device call
+int mpc_fleet_check(wg_ctx *ctx, int B, const wg_mpc_fleet_t *fl, const wg_gait_state_t *states) {
+  if (!fl || !fl->blocks || !fl->model_of) return fail(WG_ERR_BAD_ARG, "null fleet, blocks or model_of");
+  if (fl->M < 1 || B < 0) return fail(WG_ERR_BAD_ARG, "M = %d, B = %d", fl->M, B);
+  if (!wg::tt_model_ok(fl->base)) return fail(WG_ERR_BAD_ARG, "the fleet's base is not a model a block can be made of (wg_mpc_block refuses it)");
+  if (!states) return fail(WG_ERR_BAD_ARG, "bad arguments");
+  return use_ctx(ctx);
+}
+// fl == nullptr: the context's configured model; otherwise a model per gait (blocks[model_of[g]]) in the launch shape of fl->base
+int tick_launch(wg_ctx_t *ctx, int B, wg_gait_state_t *states, wg_tick_out_t *outs, int *diag, int advance_calls, int *hist, int hist_cap, int *hist_len, void *hip_stream, wg_gait_state_t *host_states, int *host_done, const wg_mpc_fleet_t *fl = nullptr) {
+  if (int rc = fl ? mpc_fleet_check(ctx, B, fl, states) : tick_check(ctx, B, states)) return rc;
   if (hist && (!hist_len || hist_cap <= 0)) return fail(WG_ERR_BAD_ARG, "hist needs hist_len and hist_cap > 0");
   if (B == 0) return WG_OK;
-  const TickPlan plan(ctx->model);
-  if (int rc = plan.raise_lds(WG_KERNEL_BY_VIEW(wg_mpc_tick_kernel, plan.view))) return rc;
+  const TickPlan plan(fl ? fl->base : ctx->model);
+  if (int rc = plan.raise_lds(fl ? WG_KERNEL_BY_VIEW(wg_mpc_tick_fleet_kernel, plan.view) : WG_KERNEL_BY_VIEW(wg_mpc_tick_kernel, plan.view))) return rc;
   const int grid = B;                             // one gait per block; the dispatcher balances uneven iteration counts
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
   std::lock_guard<std::mutex> launch_lk(ctx->launch_mu);   // ordering test, launch and event record are one critical section
@@ -830,8 +880,13 @@ int tick_launch(wg_ctx_t *ctx, int B, wg_gait_state_t *states, wg_tick_out_t *ou
   int *order = nullptr, *iters_out = nullptr;
   if (B > ctx->num_cu * plan.per_cu() && !host_states && env_flag("WG_TICK_LPT", true))
     if (int rc = lpt_prepare(ctx->tick_lpt, states, B, st, &order, &iters_out)) return rc;
-  WG_LAUNCH_BY_VIEW(wg_mpc_tick_kernel, plan.view, grid, plan.launch_lds, st, B, ctx->model, ctx->tables_dev, states, outs, diag, advance_calls, hist,
-                    hist_cap, hist_len, (unsigned)plan.qlb, zs, (unsigned)plan.zslot, plan.ecap, host_states, host_done, order, iters_out);
+  if (fl)
+    WG_LAUNCH_BY_VIEW(wg_mpc_tick_fleet_kernel, plan.view, grid, plan.launch_lds, st, B, fl->base.N, fl->base.T, fl->base.Tctrl, fl->M,
+                      static_cast<const unsigned char *>(fl->blocks), fl->model_of, states, outs, diag, advance_calls, hist, hist_cap, hist_len,
+                      (unsigned)plan.qlb, zs, (unsigned)plan.zslot, plan.ecap, order, iters_out);
+  else
+    WG_LAUNCH_BY_VIEW(wg_mpc_tick_kernel, plan.view, grid, plan.launch_lds, st, B, ctx->model, ctx->tables_dev, states, outs, diag, advance_calls, hist,
+                      hist_cap, hist_len, (unsigned)plan.qlb, zs, (unsigned)plan.zslot, plan.ecap, host_states, host_done, order, iters_out);
   HIP_TRY(hipGetLastError());
   return slot_mark(ctx->guard_order, st);
 }
@@ -951,16 +1006,31 @@ int wg_mpc_assemble_batch_ctx(wg_ctx_t *ctx, int B, const wg_gait_state_t *state
   return WG_OK;
 }
 
+}  // extern "C"
+namespace {
+int run_launch(wg_ctx_t *ctx, const wg_mpc_fleet_t *fl, int B, wg_gait_state_t *states, int n_ticks, int advance_calls, const double *vref_sched, int period, wg_tick_out_t *outs, int *diag, void *hip_stream);
+}
+extern "C" {
 int wg_mpc_run_batch_dev_ctx(wg_ctx_t *ctx, int B, wg_gait_state_t *states, int n_ticks, int advance_calls, wg_tick_out_t *outs, int *diag, void *hip_stream) {
   return wg_mpc_run_sched_dev_ctx(ctx, B, states, n_ticks, advance_calls, nullptr, 1, outs, diag, hip_stream);
 }
 
 int wg_mpc_run_sched_dev_ctx(wg_ctx_t *ctx, int B, wg_gait_state_t *states, int n_ticks, int advance_calls, const double *vref_sched, int period, wg_tick_out_t *outs, int *diag, void *hip_stream) {
-  if (int rc = use_ctx(ctx)) return rc;
-  if (!ctx->model_set) return fail(WG_ERR_BAD_ARG, "wg_mpc_configure() has not been called on this context");
+  return run_launch(ctx, nullptr, B, states, n_ticks, advance_calls, vref_sched, period, outs, diag, hip_stream);
+}
+
+}  // extern "C"
+namespace {
+// fl == nullptr: the context's configured model; otherwise a model per gait, always with the hand-over inside an XCD
+int run_launch(wg_ctx_t *ctx, const wg_mpc_fleet_t *fl, int B, wg_gait_state_t *states, int n_ticks, int advance_calls, const double *vref_sched, int period, wg_tick_out_t *outs, int *diag, void *hip_stream) {
+  if (fl) { if (int rc = mpc_fleet_check(ctx, B, fl, states)) return rc; }
+  else {
+    if (int rc = use_ctx(ctx)) return rc;
+    if (!ctx->model_set) return fail(WG_ERR_BAD_ARG, "wg_mpc_configure() has not been called on this context");
+  }
   if (B < 0 || n_ticks < 0 || !states || period < 1) return fail(WG_ERR_BAD_ARG, "bad arguments");
   if (B == 0 || n_ticks == 0) return WG_OK;
-  if (vref_sched && !run_queue_xcd()) {              // the device-wide queue of round 1 has no staged form: one launch per stretch
+  if (vref_sched && !fl && !run_queue_xcd()) {              // the device-wide queue of round 1 has no staged form: one launch per stretch
     for (int t = 0; t < n_ticks; t += period) {
       const int n = n_ticks - t < period ? n_ticks - t : period;
       if (int rc = wg_mpc_set_velref_dev_ctx(ctx, B, states, vref_sched + (size_t)(t / period) * B * 3, hip_stream)) return rc;
@@ -975,7 +1045,7 @@ int wg_mpc_run_sched_dev_ctx(wg_ctx_t *ctx, int B, wg_gait_state_t *states, int 
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
   std::lock_guard<std::mutex> launch_lk(ctx->launch_mu);   // ordering test, launch and event record are one critical section
   if (int rc = slot_claim(ctx, ctx->guard_order, st, "tick / run")) return rc;
-  const bool xcd_mode = run_queue_xcd();
+  const bool xcd_mode = fl || run_queue_xcd();
   const int cap = run_ring_cap(B);
   if (int rc = ctx->run_buf.reserve(xcd_mode ? run_buf_bytes(B) : sizeof(wg_run_queue) + (size_t)(total + B) * 4)) return rc;
   wg_run_queue *q = static_cast<wg_run_queue *>(ctx->run_buf.p);
@@ -988,9 +1058,12 @@ int wg_mpc_run_sched_dev_ctx(wg_ctx_t *ctx, int B, wg_gait_state_t *states, int 
     hipLaunchKernelGGL(wg_xrun_init_kernel, dim3((items + 255) / 256), dim3(256), 0, st, B, xctl, xrings, cap, xdone);
   } else
     hipLaunchKernelGGL(wg_run_queue_init_kernel, dim3((total + 255) / 256), dim3(256), 0, st, B, total, q, ring, done);
-  const TickPlan plan(ctx->model);
-  if (int rc = plan.raise_lds(WG_KERNEL_BY_VIEW(wg_mpc_run_kernel, plan.view))) return rc;
-  if (int rc = plan.raise_lds(WG_KERNEL_BY_VIEW(wg_mpc_run_xcd_kernel, plan.view))) return rc;
+  const TickPlan plan(fl ? fl->base : ctx->model);
+  if (fl) { if (int rc = plan.raise_lds(WG_KERNEL_BY_VIEW(wg_mpc_run_xcd_fleet_kernel, plan.view))) return rc; }
+  else {
+    if (int rc = plan.raise_lds(WG_KERNEL_BY_VIEW(wg_mpc_run_kernel, plan.view))) return rc;
+    if (int rc = plan.raise_lds(WG_KERNEL_BY_VIEW(wg_mpc_run_xcd_kernel, plan.view))) return rc;
+  }
   // as many blocks as the device keeps resident: LDS granules, and the waves the kernel's register budget admits per CU
   int grid = ctx->num_cu * plan.per_cu();
   if (grid > B) grid = B;
@@ -999,7 +1072,11 @@ int wg_mpc_run_sched_dev_ctx(wg_ctx_t *ctx, int B, wg_gait_state_t *states, int 
   int keep_k = 0;                                    // a wave keeps a gait that is behind its XCD's mean progress (see the kernel)
   if (const char *e = getenv("WG_RUN_KEEP")) keep_k = (e[0] == 'o' || e[0] == '-') ? -1 : atoi(e);
   else if (B <= grid) keep_k = -1;                   // a wave per gait: nothing waits, the launch takes what its slowest gait takes
-  if (xcd_mode)
+  if (fl)
+    WG_LAUNCH_BY_VIEW(wg_mpc_run_xcd_fleet_kernel, plan.view, grid, plan.launch_lds, st, B, n_ticks, fl->base.N, fl->base.T, fl->base.Tctrl, fl->M,
+                      static_cast<const unsigned char *>(fl->blocks), fl->model_of, states, outs, diag, advance_calls, xctl, xrings, cap, xdone,
+                      (unsigned)plan.qlb, zs, (unsigned)plan.zslot, vref_sched, period, plan.ecap, keep_k);
+  else if (xcd_mode)
     WG_LAUNCH_BY_VIEW(wg_mpc_run_xcd_kernel, plan.view, grid, plan.launch_lds, st, B, n_ticks, ctx->model_dev, ctx->tables_dev, states, outs, diag,
                       advance_calls, xctl, xrings, cap, xdone, (unsigned)plan.qlb, zs, (unsigned)plan.zslot, vref_sched, period, plan.ecap, keep_k);
   else
@@ -1007,6 +1084,52 @@ int wg_mpc_run_sched_dev_ctx(wg_ctx_t *ctx, int B, wg_gait_state_t *states, int 
                       advance_calls, q, ring, done, (unsigned)plan.qlb, zs, (unsigned)plan.zslot, plan.ecap);
   HIP_TRY(hipGetLastError());
   return slot_mark(ctx->guard_order, st);
+}
+}  // namespace
+extern "C" {
+
+// the launches of wg_mpc_tick_batch_dev and wg_mpc_run_sched_dev with blocks[model_of[g]] as gait g's model: the same launcher
+// code, the context's slots, run buffer, launch ordering and start order; nothing of the context's configured model is read
+int wg_mpc_tick_fleet_dev_ctx(wg_ctx_t *ctx, int B, const wg_mpc_fleet_t *fleet, wg_gait_state_t *states, wg_tick_out_t *outs, int *diag, int advance_calls, int *hist, int hist_cap, int *hist_len, void *hip_stream) {
+  if (!fleet) return fail(WG_ERR_BAD_ARG, "null fleet");
+  return tick_launch(ctx, B, states, outs, diag, advance_calls, hist, hist_cap, hist_len, hip_stream, nullptr, nullptr, fleet);
+}
+int wg_mpc_run_fleet_dev_ctx(wg_ctx_t *ctx, int B, const wg_mpc_fleet_t *fleet, wg_gait_state_t *states, int n_ticks, int advance_calls, const double *vref_sched, int period, wg_tick_out_t *outs, int *diag, void *hip_stream) {
+  if (!fleet) return fail(WG_ERR_BAD_ARG, "null fleet");
+  return run_launch(ctx, fleet, B, states, n_ticks, advance_calls, vref_sched, period, outs, diag, hip_stream);
+}
+
+// one wave per model (wg_tick_kernels.hpp); the host twin is wg_mpc_block, the arithmetic wg_tick_tables_math.hpp
+int wg_mpc_blocks_batch_dev_ctx(wg_ctx_t *ctx, int M, const wg_model_t *models, void *blocks, int *status, void *hip_stream) {
+  if (M < 0 || (M > 0 && (!models || !blocks || !status))) return fail(WG_ERR_BAD_ARG, "M = %d, or a NULL models, blocks or status", M);
+  int knobs = 0;
+  if (int rc = tick_ql_knobs(&knobs)) return rc;
+  if (int rc = use_ctx(ctx)) return rc;
+  if (M == 0) return WG_OK;
+  hipLaunchKernelGGL(wg_mpc_blocks_kernel, dim3(M), dim3(64), 0, reinterpret_cast<hipStream_t>(hip_stream), M, models,
+                     static_cast<unsigned char *>(blocks), status, knobs);
+  HIP_TRY(hipGetLastError());
+  return WG_OK;
+}
+
+// host pointers
+int wg_mpc_blocks_batch_ctx(wg_ctx_t *ctx, int M, const wg_model_t *models, void *blocks, int *status) {
+  if (M < 0 || (M > 0 && (!models || !blocks || !status))) return fail(WG_ERR_BAD_ARG, "M = %d, or a NULL models, blocks or status", M);
+  if (int rc = use_ctx(ctx)) return rc;
+  if (M == 0) return WG_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HostScope hs(ctx);
+  Arena a(ctx->tick_aux);
+  const auto sm = a.take<wg_model_t>((size_t)M);
+  const auto sk = a.take<unsigned char>((size_t)M * wg::kMpcBlockBytes);
+  const auto ss = a.take<int>((size_t)M);
+  if (int rc = a.reserve()) return rc;
+  WG_H2D(a(sm), models, sm.bytes());
+  if (int rc = wg_mpc_blocks_batch_dev_ctx(ctx, M, a(sm), a(sk), a(ss), hs.stream())) return rc;
+  WG_D2H(blocks, a(sk), sk.bytes());
+  WG_D2H(status, a(ss), ss.bytes());
+  WG_HOST_WAIT();
+  return WG_OK;
 }
 
 int wg_mpc_tick_batch_ctx(wg_ctx_t *ctx, int B, wg_gait_state_t *states, wg_tick_out_t *outs, int *diag, int advance_calls, int *hist, int hist_cap, int *hist_len) {
@@ -2176,6 +2299,10 @@ size_t wg_mpc_tick_lds_bytes(void) {                 // a query: does not create
 int wg_mpc_tick_batch_dev(int B, wg_gait_state_t *states, wg_tick_out_t *outs, int *diag, int advance_calls, int *hist, int hist_cap, int *hist_len, void *hip_stream) { return on_default(&wg_mpc_tick_batch_dev_ctx, B, states, outs, diag, advance_calls, hist, hist_cap, hist_len, hip_stream); }
 int wg_mpc_run_sched_dev(int B, wg_gait_state_t *states, int n_ticks, int advance_calls, const double *vref_sched, int period, wg_tick_out_t *outs, int *diag, void *hip_stream) { return on_default(&wg_mpc_run_sched_dev_ctx, B, states, n_ticks, advance_calls, vref_sched, period, outs, diag, hip_stream); }
 int wg_mpc_run_batch_dev(int B, wg_gait_state_t *states, int n_ticks, int advance_calls, wg_tick_out_t *outs, int *diag, void *hip_stream) { return on_default(&wg_mpc_run_batch_dev_ctx, B, states, n_ticks, advance_calls, outs, diag, hip_stream); }
+int wg_mpc_tick_fleet_dev(int B, const wg_mpc_fleet_t *fleet, wg_gait_state_t *states, wg_tick_out_t *outs, int *diag, int advance_calls, int *hist, int hist_cap, int *hist_len, void *hip_stream) { return on_default(&wg_mpc_tick_fleet_dev_ctx, B, fleet, states, outs, diag, advance_calls, hist, hist_cap, hist_len, hip_stream); }
+int wg_mpc_run_fleet_dev(int B, const wg_mpc_fleet_t *fleet, wg_gait_state_t *states, int n_ticks, int advance_calls, const double *vref_sched, int period, wg_tick_out_t *outs, int *diag, void *hip_stream) { return on_default(&wg_mpc_run_fleet_dev_ctx, B, fleet, states, n_ticks, advance_calls, vref_sched, period, outs, diag, hip_stream); }
+int wg_mpc_blocks_batch_dev(int M, const wg_model_t *models, void *blocks, int *status, void *hip_stream) { return on_default(&wg_mpc_blocks_batch_dev_ctx, M, models, blocks, status, hip_stream); }
+int wg_mpc_blocks_batch(int M, const wg_model_t *models, void *blocks, int *status) { return on_default(&wg_mpc_blocks_batch_ctx, M, models, blocks, status); }
 int wg_mpc_tick_batch(int B, wg_gait_state_t *states, wg_tick_out_t *outs, int *diag, int advance_calls, int *hist, int hist_cap, int *hist_len) { return on_default(&wg_mpc_tick_batch_ctx, B, states, outs, diag, advance_calls, hist, hist_cap, hist_len); }
 int wg_mpc_set_velref_dev(int B, wg_gait_state_t *states, const double *vref, void *hip_stream) { return on_default(&wg_mpc_set_velref_dev_ctx, B, states, vref, hip_stream); }
 int wg_pldp_configure(int N, const double *iPu, const double *Px, const double *Pu) { return on_default(&wg_pldp_configure_ctx, N, iPu, Px, Pu); }

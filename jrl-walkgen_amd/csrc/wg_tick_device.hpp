@@ -26,6 +26,7 @@
 #include "../../include/wg_trig.h"
 #include "wg_ql_device.hpp"
 #include "wg_ql_herdt.hpp"
+#include "wg_tick_tables_math.hpp"   // kNMaxH, kSMax, TickTables and the arithmetic that fills them
 
 namespace wg {
 
@@ -40,110 +41,16 @@ namespace wg {
   { const double *src = reinterpret_cast<const double *>(from); double *dst = reinterpret_cast<double *>(to);           \
     for (int i = lane; i < (int)(sizeof(wg_gait_state_t) / 8); i += 64) dst[i] = __hip_atomic_load(src + i, __ATOMIC_RELAXED, scope); }
 
-constexpr int kNMaxH = 32;   // largest horizon
-constexpr int kSMax = 4;     // largest number of previewed steps
 constexpr double kPi = 3.14159265358979323846;
 
-// Condensed cart-table maps + invariant Hessian block, built once per model on the host
-// (RigidBodySystem::compute_dyn_cjerk, rigid-body-system.cpp:377-452;
-//  GeneratorVelRef::build_invariant_part, generator-vel-ref.cpp:587-614).
-struct TickTables {
-  double Sv[kNMaxH][3], Sz[kNMaxH][3];
-  double Uv[kNMaxH][kNMaxH], Uz[kNMaxH][kNMaxH];
-  double Qb[kNMaxH][kNMaxH];
-  // gait-independent part of ql0002's set-up for C = blockdiag(Qb, Qb) + border (wg_ql_herdt.hpp):
-  double R2[2 * kNMaxH * (2 * kNMaxH + 1) / 2];   // packed Cholesky factor of blockdiag(Qb, Qb), qld.cpp:859-890
-  double Z2[4 * kNMaxH * kNMaxH];                 // its inverse, column-major ld 2N, qld.cpp:937-975
-  double diag_b;                                  // diagonal test over the constant block, qld.cpp:814-843
-  int blocks_ok;
-  int ql_sums;                                    // the compact view's decision-only sums (wg_ql_view.hpp: kSumsGuarded / Ordered / Doubt) and, in bits 8 - 9, its sweeps' norm chain (kNormsSeeded / Exact / Doubt)
-  // Z2 is blockdiag(Zb, Zb) with zeros in between, but the recurrence leaves SIGNED zeros in the upper-right block
-  // (-(x * 0) / r); bit i + j*N = sign of Z2(i, N + j).  The kernel fetches only Zb and re-creates the rest from this.
-  unsigned long long z2_cross_sign[(kNMaxH * kNMaxH + 63) / 64];
-};
-
-// qb_override (N x N, row-major) replaces the host loop's Q_b: the matrix-core Gramian of wg_gramian_batch
+// The tables of a model on the host: the one-lane run of wg_tick_tables_math.hpp (the kernel's is wg_mpc_blocks_kernel).
+// qb_override (N x N, row-major) replaces the loop's Q_b: the matrix-core Gramian of wg_gramian_batch
 // (WG_FLAG_GRAMIAN_MFMA_*); everything derived from Q_b (factor blocks, diagonal test) then follows the override.
+// ql_sums = 0 (guarded); the callers read the knob.
 inline void build_tables(const wg_model_t &m, TickTables &t, const double *qb_override = nullptr) {
-  const int N = m.N;
-  const double T = m.T, h = m.com_height_qp;
-  for (unsigned i = 0; i < (unsigned)kNMaxH; i++)
-    for (unsigned j = 0; j < (unsigned)kNMaxH; j++) { t.Uv[i][j] = 0.0; t.Uz[i][j] = 0.0; t.Qb[i][j] = 0.0; }
-  for (unsigned i = 0; i < (unsigned)N; i++) {
-    t.Sv[i][0] = 0.0; t.Sv[i][1] = 1.0; t.Sv[i][2] = (i + 1) * T;
-    t.Sz[i][0] = 1.0; t.Sz[i][1] = (i + 1) * T;
-    t.Sz[i][2] = (i + 1) * (i + 1) * T * T * 0.5 - h / 9.81;
-    for (unsigned j = 0; j <= i; j++) {
-      t.Uv[i][j] = (2 * (i - j) + 1) * T * T * 0.5;
-      t.Uz[i][j] = (1 + 3 * (i - j) + 3 * (i - j) * (i - j)) * T * T * T / 6.0 - T * h / 9.81;
-    }
-  }
-  for (int i = 0; i < N; i++)
-    for (int j = 0; j < N; j++) {
-      double pj = 0.0, pv = 0.0, pz = 0.0;
-      for (int k = 0; k < N; k++) {
-        pj += ((k == i) ? 1.0 : 0.0) * ((k == j) ? 1.0 : 0.0);
-        pv += t.Uv[k][i] * t.Uv[k][j];
-        pz += t.Uz[k][i] * t.Uz[k][j];
-      }
-      double q = 0.0;
-      q += pj * m.beta;
-      q += pv * m.alpha;
-      q += pz * m.gamma;
-      t.Qb[i][j] = qb_override ? qb_override[i * N + j] : q;
-    }
-  // ---- constant factor blocks: exactly ql0002's recurrences on blockdiag(Qb, Qb), eps = 1e-8 ----
-  {
-    const int M = 2 * N;
-    const double vsmall = 1e-8;
-    auto g2 = [&](int i, int j) -> double {
-      if (i < N && j < N) return t.Qb[i][j];
-      if (i >= N && j >= N) return t.Qb[i - N][j - N];
-      return 0.0;
-    };
-    double diag = 0.0;
-    for (int i = 0; i < M; ++i) {
-      const double wdi = g2(i, i);
-      diag = (diag >= vsmall - wdi) ? diag : vsmall - wdi;
-      for (int j = i + 1; j < M; ++j) {
-        const double gjj = g2(j, j), gij = g2(i, j);
-        double ga = -((wdi <= gjj) ? wdi : gjj);
-        const double gb = fabs(wdi - gjj) + fabs(gij);
-        if (gb > 0.0) ga += gij * gij / gb;
-        diag = (diag >= ga) ? diag : ga;
-      }
-    }
-    t.diag_b = diag;
-    t.blocks_ok = (diag <= 0.0) ? 1 : 0;
-    t.ql_sums = 0;                                // guarded; wg_mpc_configure reads the knob
-    auto R = [&](int i, int j) -> double & { return t.R2[(size_t)j * (j + 1) / 2 + i]; };
-    for (int j = 0; j < M && t.blocks_ok; ++j) {
-      double temp = 0.0;
-      for (int i = 0; i <= j; ++i) {
-        temp = g2(i, j);
-        for (int k = 0; k < i; ++k) temp -= R(k, j) * R(k, i);
-        if (i < j) R(i, j) = temp / R(i, i);
-      }
-      if (temp < vsmall) { t.blocks_ok = 0; break; }
-      R(j, j) = sqrt(temp);
-    }
-    auto Z = [&](int i, int j) -> double & { return t.Z2[(size_t)i + (size_t)j * M]; };
-    if (t.blocks_ok)
-      for (int i = 0; i < M; ++i) {
-        for (int j = 0; j < i; ++j) Z(i, j) = 0.0;
-        Z(i, i) = 1.0 / R(i, i);
-        for (int j = i; j < M - 1; ++j) {
-          double sum = 0.0;
-          for (int k = i; k <= j; ++k) sum += Z(i, k) * R(k, j + 1);
-          Z(i, j + 1) = -sum / R(j + 1, j + 1);
-        }
-      }
-    for (auto &w : t.z2_cross_sign) w = 0ull;
-    if (t.blocks_ok)
-      for (int j = 0; j < N; ++j)
-        for (int i = 0; i < N; ++i)
-          if (std::signbit(Z(i, N + j))) t.z2_cross_sign[(i + j * N) / 64] |= 1ull << ((i + j * N) % 64);
-  }
+  TtWork *w = new TtWork;
+  tt_build(TtHostExec{}, m, *w, t, 0, qb_override);
+  delete w;
 }
 
 struct Sup {

@@ -1,5 +1,6 @@
 // wg_tick_kernels.hpp -- the __global__ kernels of the Herdt-2010 tick (one launch per tick, many ticks per launch through a
-// device-wide queue, many ticks per launch with the hand-over kept inside one XCD) and their small helpers.  Included by
+// device-wide queue, many ticks per launch with the hand-over kept inside one XCD) and their small helpers; behind them the
+// kernels of fleets with a model per gait (wg_mpc_blocks_kernel, wg_mpc_tick_fleet_kernel, wg_mpc_run_xcd_fleet_kernel).  Included by
 // wg_capi.hip, which launches them and holds no kernel itself (the other back-ends' kernels: wg_ql_kernels.hpp,
 // wg_pldp_kernels.hpp, wg_dimitrov_kernels.hpp, and the preview / Gramian / ZMP headers); a translation unit of its own can
 // instantiate ONE of them (tools/one_kernel.sh: resource usage and ISA of a single kernel in seconds instead of the whole library).
@@ -412,3 +413,213 @@ __global__ void wg_set_velref_kernel(int B, wg_gait_state_t *states, const doubl
   }
 }
 
+
+// ---- a model per gait: the tables of M models on the device, and the fleet twins of the tick and the XCD run kernel ------------
+
+// the text of wg_tick_tables_math.hpp run by the 64 lanes of one wavefront
+struct TtWaveExec {
+  __device__ __forceinline__ int lane() const { return threadIdx.x & 63; }
+  __device__ __forceinline__ int lanes() const { return 64; }
+  __device__ __forceinline__ void sync() const { WG_WSYNC(); }
+};
+
+// wg_mpc_blocks_batch_dev: one wave (= one block) per model, its work area (TtWork, 58 112 B) in LDS -- two models per CU at a
+// time, which is plenty for a kernel that runs once per model.  Block m is written by wave m alone, every byte once: the model,
+// its tables (tt_build's last phase) and the zeros between and behind them, or zeros throughout when the model is refused;
+// status[m] says which.  ql_sums: the host's WG_QL_SUMS / WG_QL_NORMS knobs, read at the call.
+__global__ void __launch_bounds__(64)
+wg_mpc_blocks_kernel(int M, const wg_model_t *__restrict__ models, unsigned char *__restrict__ blocks, int *__restrict__ status, int ql_sums) {
+  __shared__ wg::TtWork tt_work;
+  const int m = blockIdx.x, lane = threadIdx.x & 63;
+  if (m >= M) return;
+  const wg_model_t model = models[m];
+  unsigned char *blk = blocks + (size_t)m * wg::kMpcBlockBytes;
+  unsigned long long *words = reinterpret_cast<unsigned long long *>(blk);
+  constexpr int kModelW = (int)(sizeof(wg_model_t) / 8), kT0 = (int)(wg::kMpcBlockTables / 8),
+                kT1 = kT0 + (int)(sizeof(wg::TickTables) / 8), kEnd = (int)(wg::kMpcBlockBytes / 8);
+  const bool ok = wg::tt_model_ok(model);
+  if (ok) {
+    wg::tt_build(TtWaveExec{}, model, tt_work, *reinterpret_cast<wg::TickTables *>(blk + wg::kMpcBlockTables), ql_sums);
+    const unsigned long long *src = reinterpret_cast<const unsigned long long *>(models + m);
+    for (int e = lane; e < kT0; e += 64) words[e] = e < kModelW ? src[e] : 0ull;
+    for (int e = kT1 + lane; e < kEnd; e += 64) words[e] = 0ull;
+  } else
+    for (int e = lane; e < kEnd; e += 64) words[e] = 0ull;
+  if (lane == 0) status[m] = ok ? WG_OK : WG_ERR_BAD_ARG;
+}
+
+// Gait g of a fleet launch runs with blocks[model_of[g]].  nullptr: the gait is refused -- model_of[g] outside [0, M); a failed
+// (all-zero) block, which a good one is told from by its N >= 2; a block whose N, T or Tctrl is not the launch's (bit for bit: the
+// launch shape, the slots and the sample count are the plan's); or, in the compact kernel, a model of the class "up to four
+// previewed steps" (tt_two_step_class: the compact view holds two -- a third would be a silently truncated QP).
+template <int NH>
+__device__ __forceinline__ const unsigned char *wg_mpc_fleet_block(const unsigned char *__restrict__ blocks, const int *__restrict__ model_of,
+                                                                   int M, int g, int N, double T, double Tctrl) {
+  const int mi = wg::uni(model_of[g]);
+  if (mi < 0 || mi >= M) return nullptr;
+  const unsigned char *blk = blocks + (size_t)mi * wg::kMpcBlockBytes;
+  const wg_model_t &bm = *reinterpret_cast<const wg_model_t *>(blk);
+  bool ok = bm.N >= 2 && bm.N == N && __double_as_longlong(bm.T) == __double_as_longlong(T) &&
+            __double_as_longlong(bm.Tctrl) == __double_as_longlong(Tctrl);
+  if (NH == 16) ok = ok && wg::tt_two_step_class(bm);
+  return wg::uni((int)ok) != 0 ? blk : nullptr;
+}
+// what a refused gait's tick leaves: WG_IFAIL_NO_MODEL and five zeros in the six diagnostic ints of its out struct (and, by the
+// caller, of its diag row), no iteration for the start order; of its state no byte is touched
+__device__ __forceinline__ wg::TickDiag wg_mpc_fleet_refuse(wg_tick_out_t *out) {
+  wg::TickDiag dg;
+  dg.ifail = WG_IFAIL_NO_MODEL; dg.n_iter = 0; dg.nact = 0; dg.n = 0; dg.m = 0; dg.ns = 0;
+  if (out && (threadIdx.x & 63) == 0) { out->ifail = dg.ifail; out->n_iter = 0; out->nact = 0; out->n = 0; out->m = 0; out->nb_prw_steps = 0; }
+  return dg;
+}
+
+// wg_mpc_tick_kernel with a model per gait (no one-robot path: that serves one configured model)
+template <int NH>
+__global__ __launch_bounds__(64) WG_TICK_WAVES(NH) void wg_mpc_tick_fleet_kernel(int B, int N, double T, double Tctrl, int M,
+                                                         const unsigned char *__restrict__ blocks, const int *__restrict__ model_of,
+                                                         wg_gait_state_t *__restrict__ states,
+                                                         wg_tick_out_t *__restrict__ outs, int *__restrict__ diag,
+                                                         int advance_calls, int *__restrict__ hist, int hist_cap,
+                                                         int *__restrict__ hist_len, unsigned ql_bytes, double *zscratch,
+                                                         unsigned zslot, int elem_cap,
+                                                         const int *__restrict__ order, int *__restrict__ iters_out) {
+  extern __shared__ __attribute__((aligned(16))) double wg_lds[];
+  const int lane = threadIdx.x & 63;
+  const int g = order ? wg::uni(order[blockIdx.x]) : (int)blockIdx.x;
+  if (g < B) {
+    const unsigned char *blk = wg_mpc_fleet_block<NH>(blocks, model_of, M, g, N, T, Tctrl);
+    wg::TickDiag dg;
+    if (!blk) dg = wg_mpc_fleet_refuse(outs ? outs + g : nullptr);
+    else {
+      const wg_model_t &model = *reinterpret_cast<const wg_model_t *>(blk);
+      const wg::TickTables *tb = reinterpret_cast<const wg::TickTables *>(blk + wg::kMpcBlockTables);
+      if (advance_calls > 0) {
+        if (lane == 0) {
+          double c = states[g].clock;
+          for (int k = 0; k < advance_calls; ++k) c += model.Tctrl;   // PatternGeneratorInterfacePrivate.cpp:1256
+          states[g].clock = c;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        WG_WSYNC();
+      }
+      dg = wg::mpc_tick<NH>(model, tb, states + g, outs ? outs + g : nullptr, wg_lds,
+                            reinterpret_cast<char *>(wg_lds) + ql_bytes, hist ? hist + (size_t)g * hist_cap : nullptr,
+                            hist_cap, hist_len ? hist_len + g : nullptr,
+                            zscratch ? zscratch + (size_t)blockIdx.x * zslot : nullptr, elem_cap);
+    }
+    if (diag && lane == 0) {
+      wg_diag_store(diag + (size_t)g * 6, dg);
+    }
+    if (iters_out && lane == 0) iters_out[g] = dg.n_iter;
+  }
+}
+
+// wg_mpc_run_xcd_kernel with a model per gait: the queue, the hand-over and the keep rule are the twin's, word for word; the
+// model is bound per item, after the gait is taken and before the pins.  A refused gait goes through the queue like any other --
+// its ticks cost nothing -- and sits every one of them out: no staged reference, no clock advance.
+template <int NH>
+__global__ __launch_bounds__(64) WG_TICK_WAVES(NH) void wg_mpc_run_xcd_fleet_kernel(
+    int B, int n_ticks, int N, double T, double Tctrl, int M, const unsigned char *__restrict__ blocks_p, const int *__restrict__ model_of_p,
+    wg_gait_state_t *__restrict__ states_p, wg_tick_out_t *__restrict__ outs_p, int *__restrict__ diag_p, int advance_calls,
+    wg_xrun_ctl *__restrict__ ctl_p, unsigned long long *__restrict__ rings_p, int cap, int *__restrict__ done_p,
+    unsigned ql_bytes, double *zscratch, unsigned zslot, const double *__restrict__ vsched, int vperiod, int elem_cap, int keep_k) {
+  extern __shared__ __attribute__((aligned(16))) double wg_lds[];
+  unsigned fresh_gone = 0;                                 // bit y: range y was seen exhausted (the counters only grow)
+  int kept_g = -1, kept_t = 0;                             // the gait this wave goes on with (it was behind its XCD's mean progress)
+  for (;;) {
+    int lane = threadIdx.x & 63;
+    asm volatile("" : "+v"(lane));
+    const unsigned char *blocks = blocks_p; const int *model_of = model_of_p; wg_gait_state_t *states = states_p;
+    wg_tick_out_t *outs = outs_p; int *diag = diag_p; wg_xrun_ctl *ctl = ctl_p; unsigned long long *rings = rings_p; int *done = done_p;
+    asm volatile("" : "+s"(ctl), "+s"(rings), "+s"(done));
+    int xcc;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(xcc));
+    xcc &= kXcds - 1;
+    int g = kept_g, t = kept_t;
+    kept_g = -1;
+    if (g < 0 && lane == 0) {
+      if (!((fresh_gone >> xcc) & 1u)) {
+        g = xrun_take_fresh(ctl, xcc);
+        if (g < 0) fresh_gone |= 1u << xcc;
+      }
+      if (g < 0) {
+        for (;;) {
+          const int h = xrun_rmw_load(&ctl->x[xcc].head), tl = xrun_rmw_load(&ctl->x[xcc].tail);
+          if (h >= tl) break;
+          int expect = h;
+          if (!__hip_atomic_compare_exchange_strong(&ctl->x[xcc].head, &expect, h + 1, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                                    __HIP_MEMORY_SCOPE_AGENT))
+            continue;
+          unsigned long long *slot = rings + (size_t)xcc * cap + (h & (cap - 1));
+          unsigned long long e;
+          while ((unsigned)((e = xrun_rmw_load(slot)) >> 32) != (unsigned)(h + 1))
+            __builtin_amdgcn_s_sleep(4);
+          g = (int)(e & 0xffffffffull);
+          t = xrun_rmw_load(done + g);                       // written (L2) before the entry was
+          break;
+        }
+      }
+      for (int y = 1; g < 0 && y < kXcds; ++y) {
+        const int z = (xcc + y) & (kXcds - 1);
+        if ((fresh_gone >> z) & 1u) continue;
+        g = xrun_take_fresh(ctl, z);
+        if (g < 0) fresh_gone |= 1u << z;
+      }
+    }
+    g = wg::uni(g); t = wg::uni(t); fresh_gone = (unsigned)wg::uni((int)fresh_gone);
+    if (g < 0) break;
+    // the gait's model: bound here, per item, and pinned with the other data pointers -- address-space-1 pointers, so that every
+    // access through them stays a global_ instruction (the comment at the head of this file)
+    WG_PIN_GLOBAL(blocks); WG_PIN_GLOBAL(model_of);
+    const unsigned char *blk = wg_mpc_fleet_block<NH>(blocks, model_of, M, g, N, T, Tctrl);
+    const bool bound = blk != nullptr;
+    const wg_model_t *mp = reinterpret_cast<const wg_model_t *>(blk);
+    const wg::TickTables *tb = reinterpret_cast<const wg::TickTables *>(bound ? blk + wg::kMpcBlockTables : blk);
+    WG_PIN_GLOBAL(mp); WG_PIN_GLOBAL(tb); WG_PIN_GLOBAL(states); WG_PIN_GLOBAL(outs); WG_PIN_GLOBAL(diag);
+    wg_tick_out_t *out = outs ? outs + (size_t)t * B + g : nullptr;
+    wg::TickDiag dg;
+    if (!bound) dg = wg_mpc_fleet_refuse(out);
+    else {
+      const wg_model_t &model = *mp;
+      if (vsched && t % vperiod == 0) {                      // staged references: what wg_set_velref_kernel writes between launches
+        if (lane < 3) states[g].vref[lane] = vsched[((size_t)(t / vperiod) * B + g) * 3 + lane];
+        xrun_stores_done();                                  // mpc_tick reads the state back from L2
+        WG_WSYNC();
+      }
+      if (advance_calls > 0) {
+        if (lane == 0) {
+          double c = __hip_atomic_load(&states[g].clock, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          for (int k = 0; k < advance_calls; ++k) c += model.Tctrl;   // PatternGeneratorInterfacePrivate.cpp:1256
+          states[g].clock = c;
+        }
+        xrun_stores_done();                                  // mpc_tick reads the state back from L2
+        WG_WSYNC();
+      }
+      dg = wg::mpc_tick<NH>(model, tb, states + g, out, wg_lds, reinterpret_cast<char *>(wg_lds) + ql_bytes, nullptr, 0, nullptr,
+                            zscratch ? zscratch + (size_t)blockIdx.x * zslot : nullptr, elem_cap);
+    }
+    if (diag && lane == 0) wg_diag_store(diag + ((size_t)t * B + g) * 6, dg);
+    WG_WSYNC();
+    if (t + 1 < n_ticks) {
+      if (keep_k >= 0) {
+        int keep = 0;
+        if (lane == 0) {
+          const int p = __hip_atomic_fetch_add(&ctl->x[xcc].prog, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          keep = (long long)(t + 1 + keep_k) * ctl->x[xcc].count <= (long long)p;
+        }
+        if (wg::uni(keep)) {
+          xrun_stores_done();                              // the state is read back from L2 by the next tick
+          kept_g = g; kept_t = t + 1;
+          continue;
+        }
+      }
+      if (lane == 0) done[g] = t + 1;
+      xrun_stores_done();                                  // state and tick count are in this XCD's L2 before the gait is offered
+      if (lane == 0) {
+        const int pos = __hip_atomic_fetch_add(&ctl->x[xcc].tail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_exchange(rings + (size_t)xcc * cap + (pos & (cap - 1)), ((unsigned long long)(unsigned)(pos + 1) << 32) | (unsigned)g,
+                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+  }
+}

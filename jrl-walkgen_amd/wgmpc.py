@@ -165,6 +165,17 @@ def lib():
                 [C.c_void_p] * 3 + [C.c_int, C.c_void_p]
             _lib.wg_dimitrov_follow_fleet_dev.argtypes = [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + \
                 [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 2 + [C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p]
+        if hasattr(_lib, "wg_mpc_block"):                    # absent from older experiment builds (WG_LIB_PATH, A/B runs)
+            _lib.wg_mpc_block_bytes.restype = C.c_size_t
+            _lib.wg_mpc_block_bytes.argtypes = []
+            _lib.wg_mpc_block.argtypes = [C.c_void_p, C.c_void_p]
+            _lib.wg_mpc_block_unpack.argtypes = [C.c_void_p] * 11
+        if hasattr(_lib, "wg_mpc_blocks_batch_dev"):
+            _lib.wg_mpc_blocks_batch.argtypes = [C.c_int] + [C.c_void_p] * 3
+            _lib.wg_mpc_blocks_batch_dev.argtypes = _lib.wg_mpc_blocks_batch.argtypes + [C.c_void_p]
+            _lib.wg_mpc_tick_fleet_dev.argtypes = [C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+            _lib.wg_mpc_run_fleet_dev.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int] + \
+                [C.c_void_p] * 3
         if hasattr(_lib, "wg_steps_plan_dev"):               # absent from older experiment builds (WG_LIB_PATH, A/B runs)
             _lib.wg_steps_count.argtypes = [C.c_void_p, C.c_int]
             _lib.wg_steps_plan.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
@@ -203,7 +214,8 @@ CTX_ENTRY_POINTS = ("wg_set_overlap_strict", "wg_overlap_serialised", "wg_qp_sol
                     "wg_dimitrov_walk_time", "wg_dimitrov_walk_safe_ticks", "wg_preview_follow_dev", "wg_dimitrov_follow_dev",
                     "wg_steps_plan_dev", "wg_riccati_gains_batch", "wg_riccati_gains_batch_dev", "wg_preview_run_fleet_dev",
                     "wg_preview_follow_fleet_dev", "wg_dimitrov_constants_batch", "wg_dimitrov_constants_batch_dev",
-                    "wg_dimitrov_tick_fleet_dev", "wg_dimitrov_walk_fleet_dev", "wg_dimitrov_follow_fleet_dev")
+                    "wg_dimitrov_tick_fleet_dev", "wg_dimitrov_walk_fleet_dev", "wg_dimitrov_follow_fleet_dev",
+                    "wg_mpc_blocks_batch", "wg_mpc_blocks_batch_dev", "wg_mpc_tick_fleet_dev", "wg_mpc_run_fleet_dev")
 
 
 class Context:
@@ -997,6 +1009,91 @@ def dimitrov_walk_safe_ticks(t0, t_have):
     n = int(lib().wg_dimitrov_walk_safe_ticks(float(t0), float(t_have)))
     _check(min(n, 0))
     return n
+
+
+# ---- Herdt fleets with a model per gait: blocks (the model and its tick tables), the fleet launches (wg_mpc.h) ----
+class MpcFleet(C.Structure):            # wg_mpc_fleet_t
+    _fields_ = [("base", Model), ("M", C.c_int), ("pad_", C.c_int), ("blocks", C.c_void_p), ("model_of", C.c_void_p)]
+
+
+IFAIL_NO_MODEL = -1                     # WG_IFAIL_NO_MODEL
+MPC_BLOCK_ARRAYS = ("Sv", "Sz", "Uv", "Uz", "Qb", "R2", "Z2")
+_NMAXH = 32                             # wg::kNMaxH: the tables are laid out for it
+MPC_BLOCK_TABLES = 256                  # where the tables start in a block
+MPC_BLOCK_TABLES_BYTES = 8 * (2 * 3 * _NMAXH + 3 * _NMAXH * _NMAXH + _NMAXH * (2 * _NMAXH + 1) + 4 * _NMAXH * _NMAXH) + 16 + \
+    8 * (_NMAXH * _NMAXH // 64)
+
+
+def mpc_block_bytes():
+    return int(lib().wg_mpc_block_bytes())
+
+
+def mpc_block(model):
+    """(rc, block): the model's block as a uint8 array, made on the host; all zeros when rc != 0"""
+    blk = np.zeros(mpc_block_bytes(), dtype=np.uint8)
+    return int(lib().wg_mpc_block(C.byref(model), _hp(blk))), blk
+
+
+def mpc_block_unpack(block):
+    """the arrays of a host copy of a block at the block's own N, by the names of MPC_BLOCK_ARRAYS (R2 packed, Z2 column-major
+    with leading dimension 2N), `sign` (the sign words of Z2's cross block, read from the block's bytes), `diag_b`, `blocks_ok`
+    and `model`"""
+    blk = np.ascontiguousarray(block, dtype=np.uint8)
+    N = int(blk[:4].view(np.int32)[0])
+    n = 2 * N
+    shapes = dict(Sv=(N, 3), Sz=(N, 3), Uv=(N, N), Uz=(N, N), Qb=(N, N), R2=(n * (n + 1) // 2,), Z2=(n * n,))
+    out = {k: np.zeros(shapes[k]) for k in MPC_BLOCK_ARRAYS}
+    m = Model()
+    diag_b, ok = C.c_double(0.0), C.c_int(0)
+    _check(lib().wg_mpc_block_unpack(_hp(blk), C.addressof(m), *[_hp(out[k]) for k in MPC_BLOCK_ARRAYS], C.addressof(diag_b),
+                                     C.addressof(ok)))
+    end = MPC_BLOCK_TABLES + MPC_BLOCK_TABLES_BYTES
+    out["sign"] = blk[end - 8 * (_NMAXH * _NMAXH // 64):end].view(np.uint64).copy()
+    out["diag_b"], out["blocks_ok"], out["model"] = diag_b.value, ok.value, m
+    return out
+
+
+def mpc_blocks_batch(models):
+    """(blocks [M][bytes] uint8, status [M]) of the models through the device, host arrays in and out"""
+    M = len(models)
+    arr = (Model * M)(*models)
+    blocks = np.zeros((M, mpc_block_bytes()), dtype=np.uint8)
+    status = np.zeros(M, dtype=np.int32)
+    _check(lib().wg_mpc_blocks_batch(M, C.addressof(arr), _hp(blocks), _hp(status)))
+    return blocks, status
+
+
+def mpc_blocks_batch_dev(M, models_ptr, blocks_ptr, status_ptr, stream=None):
+    """M blocks and M status ints on the device from M wg_model_t on the device"""
+    _check(lib().wg_mpc_blocks_batch_dev(int(M), models_ptr, blocks_ptr, status_ptr, stream))
+
+
+def mpc_fleet(base, M, blocks_ptr, model_of_ptr):
+    """the descriptor of the fleet launches: `base` decides the launch plan, M blocks and an int per gait on the device"""
+    return MpcFleet(Model.from_buffer_copy(bytes(base)), int(M), 0, blocks_ptr, model_of_ptr)
+
+
+def _fleet_ref(fleet):
+    return None if fleet is None else C.byref(fleet)
+
+
+def mpc_tick_fleet_dev(B, fleet, states_ptr, outs_ptr=None, diag_ptr=None, advance_calls=0, hist_ptr=None, hist_cap=0,
+                       hist_len_ptr=None, stream=None, ctx=None):
+    """mpc_tick_batch_dev with blocks[model_of[g]] as gait g's model; no configured model is read.  Returns the raw code."""
+    args = (int(B), _fleet_ref(fleet), states_ptr, outs_ptr, diag_ptr, int(advance_calls), hist_ptr, int(hist_cap), hist_len_ptr, stream)
+    if ctx is not None:
+        return int(lib().wg_mpc_tick_fleet_dev_ctx(ctx.handle if isinstance(ctx, Context) else ctx, *args))
+    return int(lib().wg_mpc_tick_fleet_dev(*args))
+
+
+def mpc_run_fleet_dev(B, fleet, states_ptr, n_ticks, advance_calls=20, vref_sched_ptr=None, period=1, outs_ptr=None, diag_ptr=None,
+                      stream=None, ctx=None):
+    """mpc_run_sched_dev with a model per gait (vref_sched_ptr None: the unstaged run).  Returns the raw code."""
+    args = (int(B), _fleet_ref(fleet), states_ptr, int(n_ticks), int(advance_calls), vref_sched_ptr, int(period), outs_ptr, diag_ptr,
+            stream)
+    if ctx is not None:
+        return int(lib().wg_mpc_run_fleet_dev_ctx(ctx.handle if isinstance(ctx, Context) else ctx, *args))
+    return int(lib().wg_mpc_run_fleet_dev(*args))
 
 
 # ---- invariant Hessian block on the matrix cores ----
