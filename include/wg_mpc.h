@@ -679,6 +679,55 @@ int wg_zmpdisc_end_dev(const wg_zmpdisc_model_t *model, int B, const int *select
                        double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm,
                        double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream);
 
+/* The same walks with a model per gait -----------------------------------------------------------------------------------
+ *
+ * Robots of different size differ in their support times, step height, foot geometry and ZMP offsets, not only in the CoM
+ * height the consumers' fleet forms take per gait.  wg_zmpdisc_full_fleet_dev, wg_zmpdisc_begin_fleet_dev, _append_fleet_dev and
+ * _end_fleet_dev are wg_zmpdisc_full_batch_dev, _begin_dev, _append_dev and _end_dev word for word, with a wg_zmpdisc_fleet_t in
+ * place of the one model: gait b walks with models[model_of[b]], or with models[b] where model_of is NULL (then M == B).
+ * CONTRACT: every byte the call writes for gait b -- length[b], its state blob, every output row, the at-rest rows past
+ * length[b] -- is the byte the one-model call writes for that gait when handed models[model_of[b]]; what that call leaves
+ * untouched stays untouched.  Every field but T may differ from gait to gait, preview_time included (it only enters the sample
+ * counts; wg_zmpdisc_length and wg_zmpdisc_length_after take the gait's own model when the caller sizes lcap).
+ *   base     read on the host: base.T fixes the filter window, which is the launch's shape (LDS); nothing else of it is read
+ *   models   M, DEVICE memory;  model_of  B, DEVICE memory, or NULL
+ * A gait whose model's T is not base.T bit for bit, or whose model_of[b] lies outside [0, M), is refused with
+ * WG_ZMPDISC_BAD_INPUT like every other per-gait refusal: decided before the gait's first sample, written to length[b] alone in
+ * the whole-sequence form, sticky in the state in the on-line forms (an earlier sticky code is reported first); a neighbour
+ * never notices.  Pass the same models to every call of a walk.
+ * Host-side errors (WG_ERR_BAD_ARG, nothing launched): NULL fleet or models, M < 1, model_of == NULL with M != B, a base.T the
+ * one-model calls refuse or whose window leaves no room for the wave's models beside it in LDS (more than 50 taps: T of about
+ * 1 ms and below), and everything the one-model calls refuse.  The gaits' models are staged once per wave in LDS beside the
+ * filter rings (16 doubles per gait).  Asynchronous on hip_stream; nothing is kept in the context.
+ * Added without a change of wg_abi_version(): detect by symbol. */
+typedef struct wg_zmpdisc_fleet {
+  wg_zmpdisc_model_t base;            /* read on the host; base.T fixes the filter window = the launch shape */
+  int M, pad_;
+  const wg_zmpdisc_model_t *models;   /* [M] device */
+  const int *model_of;                /* [B] device, or NULL: M == B and gait b walks with models[b] */
+} wg_zmpdisc_fleet_t;
+#define WG_ZMPDISC_FLEET_BYTES 152
+#ifdef __cplusplus
+static_assert(sizeof(wg_zmpdisc_fleet_t) == WG_ZMPDISC_FLEET_BYTES, "wg_zmpdisc_fleet_t is part of the ABI");
+#else
+_Static_assert(sizeof(wg_zmpdisc_fleet_t) == WG_ZMPDISC_FLEET_BYTES, "wg_zmpdisc_fleet_t is part of the ABI");
+#endif
+int wg_zmpdisc_full_fleet_dev(const wg_zmpdisc_fleet_t *fleet, int B, int smax, const wg_rel_step_t *steps,
+                              const int *n_steps, const double *init_feet, int lcap, double *zmp_x_tm, double *zmp_y_tm,
+                              double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm,
+                              int *right_type_tm, int *length, void *hip_stream);
+int wg_zmpdisc_begin_fleet_dev(const wg_zmpdisc_fleet_t *fleet, int B, int smax, const wg_rel_step_t *steps,
+                               const int *n_steps, const double *init_feet, int lcap, double *zmp_x_tm, double *zmp_y_tm,
+                               double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm,
+                               int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream);
+int wg_zmpdisc_append_fleet_dev(const wg_zmpdisc_fleet_t *fleet, int B, int smax, const wg_rel_step_t *steps,
+                                const int *n_steps, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm,
+                                int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm,
+                                wg_zmpdisc_state_t *state, int *length, void *hip_stream);
+int wg_zmpdisc_end_fleet_dev(const wg_zmpdisc_fleet_t *fleet, int B, const int *select, int lcap, double *zmp_x_tm,
+                             double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm,
+                             double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream);
+
 /* Where the steps come from: the step stack on the device ---------------------------------------------------------------
  *
  * The generators of the reference's StepStackHandler for B gaits at once, in the layout wg_zmpdisc_full_batch_dev,
@@ -736,6 +785,13 @@ int wg_steps_plan(const wg_step_cmd_t *cmds, int n_cmds, double ss, double ds, w
                   wg_rel_step_t *steps, int *n_steps);
 int wg_steps_plan_dev(int B, int ccap, const wg_step_cmd_t *cmds, const int *n_cmds, double ss, double ds,
                       wg_step_stack_t *stack, int smax, wg_rel_step_t *steps, int *n_steps, void *hip_stream);
+/* The same with support times per gait (robots of different cadence in one launch): ss, ds are DEVICE arrays of B, and gait b's
+ * bytes are those of wg_steps_plan_dev called with ss[b], ds[b].  A gait that runs (no sticky error, n_cmds[b] != 0) with a
+ * non-finite ss[b] or ds[b] is refused with WG_STEPS_BAD_INPUT ahead of its commands' own verdict, with the refusal semantics
+ * above (n_steps[b] = 0, sticky in stack[b].error, nothing else written); a gait that sits out is not looked at.  Host-side
+ * errors as above, the times aside: NULL ss or ds.  Added without a change of wg_abi_version(): detect by symbol. */
+int wg_steps_plan_fleet_dev(int B, int ccap, const wg_step_cmd_t *cmds, const int *n_cmds, const double *ss, const double *ds,
+                            wg_step_stack_t *stack, int smax, wg_rel_step_t *steps, int *n_steps, void *hip_stream);
 
 /* The preview that follows such a walk: every gait advances over exactly the rows its own queue has made safe -------------
  *
@@ -885,6 +941,30 @@ int wg_foot_constraints_append_dev(int B, int lcap, int first_sample, int *done,
                                    const double *left_tm, const int *left_type_tm, const double *right_tm, double sole_w,
                                    double sole_h, double constraint_x, double constraint_y, int qcap,
                                    wg_zmp_polytope_t *queues, double *t_start, double *t_end, int *count, void *hip_stream);
+/* Both with a sole per gait (robots of different foot size in one launch): soles is a DEVICE array of B in place of the four
+ * scalars, everything else is the call above.  Per gait count[b], the queue entries, t_start, t_end and, for the append form,
+ * done[b] are those of the one-sole call handed soles[b] -- the half sole minus the margins is made in the gait's lane with the
+ * host call's expression -- including the verdict of wg_foot_constraints on a sole it refuses (corners that span no polygon:
+ * WG_ERR_BAD_ARG in count[b]), which goes to that gait alone.  Host-side errors as above, and NULL soles.  Launches are
+ * ordered per context like the one-sole calls', through the same buffer.  Added without a change of wg_abi_version(): detect by
+ * symbol. */
+typedef struct wg_sole {
+  double sole_w, sole_h;              /* getSoleSize outputs */
+  double constraint_x, constraint_y;  /* the security margins (ConstraintOnX / Y) */
+} wg_sole_t;
+#define WG_SOLE_BYTES 32
+#ifdef __cplusplus
+static_assert(sizeof(wg_sole_t) == WG_SOLE_BYTES, "wg_sole_t is part of the ABI");
+#else
+_Static_assert(sizeof(wg_sole_t) == WG_SOLE_BYTES, "wg_sole_t is part of the ABI");
+#endif
+int wg_foot_constraints_fleet_dev(int B, int lcap, const int *length, const double *time, const double *left_tm,
+                                  const int *left_type_tm, const double *right_tm, const wg_sole_t *soles, int qcap,
+                                  wg_zmp_polytope_t *queues, double *t_start, double *t_end, int *count, void *hip_stream);
+int wg_foot_constraints_append_fleet_dev(int B, int lcap, int first_sample, int *done, const int *length, const double *time,
+                                         const double *left_tm, const int *left_type_tm, const double *right_tm,
+                                         const wg_sole_t *soles, int qcap, wg_zmp_polytope_t *queues, double *t_start,
+                                         double *t_end, int *count, void *hip_stream);
 /* The queue walk of one tick, BuildConstraintMatrices (ZMPConstrainedQPFastFormulation.cpp:785-796, 822-835), for B gaits:
  * the first entry q with t_start[q] <= t0 <= t_end[q] is the start; for i = 0 .. N-1, q advances by one when
  * t0 + i T > t_end[q] (the reference's StartingTime + i*T); polys[b][i] is a copy of entry q.  N and T are the configured
@@ -1261,6 +1341,37 @@ int wg_mpc_tick_fleet_dev_ctx(wg_ctx_t *ctx, int B, const wg_mpc_fleet_t *fleet,
 int wg_mpc_run_fleet_dev_ctx(wg_ctx_t *ctx, int B, const wg_mpc_fleet_t *fleet, wg_gait_state_t *states, int n_ticks,
                              int advance_calls, const double *vref_sched, int period, wg_tick_out_t *outs, int *diag,
                              void *hip_stream);
+int wg_zmpdisc_full_fleet_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_fleet_t *fleet, int B, int smax,
+                                  const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap,
+                                  double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm,
+                                  double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm,
+                                  int *length, void *hip_stream);
+int wg_zmpdisc_begin_fleet_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_fleet_t *fleet, int B, int smax,
+                                   const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap,
+                                   double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm,
+                                   double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm,
+                                   wg_zmpdisc_state_t *state, int *length, void *hip_stream);
+int wg_zmpdisc_append_fleet_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_fleet_t *fleet, int B, int smax,
+                                    const wg_rel_step_t *steps, const int *n_steps, int lcap, double *zmp_x_tm,
+                                    double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm,
+                                    int *left_type_tm, double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state,
+                                    int *length, void *hip_stream);
+int wg_zmpdisc_end_fleet_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_fleet_t *fleet, int B, const int *select, int lcap,
+                                 double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm,
+                                 int *left_type_tm, double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state,
+                                 int *length, void *hip_stream);
+int wg_steps_plan_fleet_dev_ctx(wg_ctx_t *ctx, int B, int ccap, const wg_step_cmd_t *cmds, const int *n_cmds, const double *ss,
+                                const double *ds, wg_step_stack_t *stack, int smax, wg_rel_step_t *steps, int *n_steps,
+                                void *hip_stream);
+int wg_foot_constraints_fleet_dev_ctx(wg_ctx_t *ctx, int B, int lcap, const int *length, const double *time,
+                                      const double *left_tm, const int *left_type_tm, const double *right_tm,
+                                      const wg_sole_t *soles, int qcap, wg_zmp_polytope_t *queues, double *t_start,
+                                      double *t_end, int *count, void *hip_stream);
+int wg_foot_constraints_append_fleet_dev_ctx(wg_ctx_t *ctx, int B, int lcap, int first_sample, int *done, const int *length,
+                                             const double *time, const double *left_tm, const int *left_type_tm,
+                                             const double *right_tm, const wg_sole_t *soles, int qcap,
+                                             wg_zmp_polytope_t *queues, double *t_start, double *t_end, int *count,
+                                             void *hip_stream);
 
 #ifdef __cplusplus
 }

@@ -1523,6 +1523,39 @@ int footcons_launch(wg_ctx *ctx, bool res, int B, int lcap, int first_sample, co
   HIP_TRY(hipGetLastError());
   return slot_mark(ctx->fc_order, st);
 }
+
+// The two calls, each in its two forms: kFleet = false with the launch's sole (S is empty), kFleet = true with a sole per gait in
+// S.soles (`sole` is then unused: the kernels make hw, hh in the gait's lane).
+template <bool kFleet>
+int footcons_batch(wg_ctx *ctx, int B, int lcap, const int *length, const double *time, const double *left_tm, const int *left_type_tm, const double *right_tm, const wg_sole_t &sole, wg::FcSoles<kFleet> S, int qcap, wg_zmp_polytope_t *queues, double *t_start, double *t_end, int *count, void *hip_stream) {
+  return footcons_launch(ctx, false, B, lcap, 0, nullptr, length, time, left_tm, left_type_tm, right_tm, sole.sole_w, sole.sole_h, sole.constraint_x, sole.constraint_y, qcap, queues, t_start, t_end, count, hip_stream,
+                         [&](const wg::FcIn &I, const wg::FcOut &Q, int *cnt, size_t, int, int chunks, hipStream_t st) -> int {
+    const dim3 grid((B + 63) / 64, chunks);
+    HIP_TRY(hipMemsetAsync(count, 0, (size_t)B * sizeof(int), st));
+    hipLaunchKernelGGL((wg::wg_footcons_kernel<false, false, kFleet>), grid, dim3(64), 0, st, I, Q, cnt, wg::FcRes{}, S);
+    hipLaunchKernelGGL((wg::wg_footcons_kernel<true, false, kFleet>), grid, dim3(64), 0, st, I, Q, cnt, wg::FcRes{}, S);
+    return WG_OK;
+  });
+}
+
+template <bool kFleet>
+int footcons_append(wg_ctx *ctx, int B, int lcap, int first_sample, int *done, const int *length, const double *time, const double *left_tm, const int *left_type_tm, const double *right_tm, const wg_sole_t &sole, wg::FcSoles<kFleet> S, int qcap, wg_zmp_polytope_t *queues, double *t_start, double *t_end, int *count, void *hip_stream) {
+  // chunks that lie wholly below first_sample hold no new sample of any gait: not launched (a gait whose done[b] is below it
+  // is refused on the device).  first_sample >= lcap: every gait sits out or is refused, the first kernel alone says so.
+  // done[b] / count[b] as they were on entry live behind the per-chunk counts
+  return footcons_launch(ctx, true, B, lcap, first_sample, done, length, time, left_tm, left_type_tm, right_tm, sole.sole_w, sole.sole_h, sole.constraint_x, sole.constraint_y, qcap, queues, t_start, t_end, count, hip_stream,
+                         [&](const wg::FcIn &I, const wg::FcOut &Q, int *cnt, size_t n_cnt, int chunk0, int chunks, hipStream_t st) -> int {
+    int *from = cnt + n_cnt, *base = from + (size_t)B;
+    hipLaunchKernelGGL(wg::wg_footcons_resume_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, lcap, first_sample, length, done, count, from, base);
+    if (chunks > 0) {
+      const wg::FcRes Z{from, base, done, chunk0};
+      const dim3 grid((B + 63) / 64, chunks);
+      hipLaunchKernelGGL((wg::wg_footcons_kernel<false, true, kFleet>), grid, dim3(64), 0, st, I, Q, cnt, Z, S);
+      hipLaunchKernelGGL((wg::wg_footcons_kernel<true, true, kFleet>), grid, dim3(64), 0, st, I, Q, cnt, Z, S);
+    }
+    return WG_OK;
+  });
+}
 }  // namespace
 
 extern "C" {
@@ -1530,32 +1563,21 @@ extern "C" {
 int wg_foot_constraints_chunk(void) { return wg::kFcChunk; }
 
 int wg_foot_constraints_batch_dev_ctx(wg_ctx_t *ctx, int B, int lcap, const int *length, const double *time, const double *left_tm, const int *left_type_tm, const double *right_tm, double sole_w, double sole_h, double constraint_x, double constraint_y, int qcap, wg_zmp_polytope_t *queues, double *t_start, double *t_end, int *count, void *hip_stream) {
-  return footcons_launch(ctx, false, B, lcap, 0, nullptr, length, time, left_tm, left_type_tm, right_tm, sole_w, sole_h, constraint_x, constraint_y, qcap, queues, t_start, t_end, count, hip_stream,
-                         [&](const wg::FcIn &I, const wg::FcOut &Q, int *cnt, size_t, int, int chunks, hipStream_t st) -> int {
-    const dim3 grid((B + 63) / 64, chunks);
-    HIP_TRY(hipMemsetAsync(count, 0, (size_t)B * sizeof(int), st));
-    hipLaunchKernelGGL((wg::wg_footcons_kernel<false, false>), grid, dim3(64), 0, st, I, Q, cnt, wg::FcRes{});
-    hipLaunchKernelGGL((wg::wg_footcons_kernel<true, false>), grid, dim3(64), 0, st, I, Q, cnt, wg::FcRes{});
-    return WG_OK;
-  });
+  return footcons_batch(ctx, B, lcap, length, time, left_tm, left_type_tm, right_tm, wg_sole_t{sole_w, sole_h, constraint_x, constraint_y}, wg::FcSoles<false>{}, qcap, queues, t_start, t_end, count, hip_stream);
 }
 
 int wg_foot_constraints_append_dev_ctx(wg_ctx_t *ctx, int B, int lcap, int first_sample, int *done, const int *length, const double *time, const double *left_tm, const int *left_type_tm, const double *right_tm, double sole_w, double sole_h, double constraint_x, double constraint_y, int qcap, wg_zmp_polytope_t *queues, double *t_start, double *t_end, int *count, void *hip_stream) {
-  // chunks that lie wholly below first_sample hold no new sample of any gait: not launched (a gait whose done[b] is below it
-  // is refused on the device).  first_sample >= lcap: every gait sits out or is refused, the first kernel alone says so.
-  // done[b] / count[b] as they were on entry live behind the per-chunk counts
-  return footcons_launch(ctx, true, B, lcap, first_sample, done, length, time, left_tm, left_type_tm, right_tm, sole_w, sole_h, constraint_x, constraint_y, qcap, queues, t_start, t_end, count, hip_stream,
-                         [&](const wg::FcIn &I, const wg::FcOut &Q, int *cnt, size_t n_cnt, int chunk0, int chunks, hipStream_t st) -> int {
-    int *from = cnt + n_cnt, *base = from + (size_t)B;
-    hipLaunchKernelGGL(wg::wg_footcons_resume_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, lcap, first_sample, length, done, count, from, base);
-    if (chunks > 0) {
-      const wg::FcRes Z{from, base, done, chunk0};
-      const dim3 grid((B + 63) / 64, chunks);
-      hipLaunchKernelGGL((wg::wg_footcons_kernel<false, true>), grid, dim3(64), 0, st, I, Q, cnt, Z);
-      hipLaunchKernelGGL((wg::wg_footcons_kernel<true, true>), grid, dim3(64), 0, st, I, Q, cnt, Z);
-    }
-    return WG_OK;
-  });
+  return footcons_append(ctx, B, lcap, first_sample, done, length, time, left_tm, left_type_tm, right_tm, wg_sole_t{sole_w, sole_h, constraint_x, constraint_y}, wg::FcSoles<false>{}, qcap, queues, t_start, t_end, count, hip_stream);
+}
+
+int wg_foot_constraints_fleet_dev_ctx(wg_ctx_t *ctx, int B, int lcap, const int *length, const double *time, const double *left_tm, const int *left_type_tm, const double *right_tm, const wg_sole_t *soles, int qcap, wg_zmp_polytope_t *queues, double *t_start, double *t_end, int *count, void *hip_stream) {
+  if (!soles) return fail(WG_ERR_BAD_ARG, "null soles");
+  return footcons_batch(ctx, B, lcap, length, time, left_tm, left_type_tm, right_tm, wg_sole_t{}, wg::FcSoles<true>{soles}, qcap, queues, t_start, t_end, count, hip_stream);
+}
+
+int wg_foot_constraints_append_fleet_dev_ctx(wg_ctx_t *ctx, int B, int lcap, int first_sample, int *done, const int *length, const double *time, const double *left_tm, const int *left_type_tm, const double *right_tm, const wg_sole_t *soles, int qcap, wg_zmp_polytope_t *queues, double *t_start, double *t_end, int *count, void *hip_stream) {
+  if (!soles) return fail(WG_ERR_BAD_ARG, "null soles");
+  return footcons_append(ctx, B, lcap, first_sample, done, length, time, left_tm, left_type_tm, right_tm, wg_sole_t{}, wg::FcSoles<true>{soles}, qcap, queues, t_start, t_end, count, hip_stream);
 }
 
 int wg_dimitrov_select_polys_dev_ctx(wg_ctx_t *ctx, int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count, double t0, wg_zmp_polytope_t *polys, int *ran_out, void *hip_stream) {
@@ -2121,6 +2143,17 @@ int zd_launch(const wg::ZdConst &K, int B, int smax, const wg_rel_step_t *steps,
   return WG_OK;
 }
 
+// what begin / append / end check of their arguments, the model aside
+int zd_online_check(int op, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap,
+                    const wg::ZdOut &O, const wg_zmpdisc_state_t *state) {
+  const int smin = op == wg::ZD_OP_BEGIN ? 2 : 1;
+  const bool steps_ok = op == wg::ZD_OP_END || (steps && n_steps && smax >= smin && smax <= WG_ZMPDISC_MAX_STEPS);
+  if (B < 0 || lcap < 1 || !state || !steps_ok || (op == wg::ZD_OP_BEGIN && !init_feet))
+    return fail(WG_ERR_BAD_ARG, "need B >= 0, %d <= smax <= %d, lcap >= 1, non-null inputs and state", smin, WG_ZMPDISC_MAX_STEPS);
+  if ((O.zx == nullptr) != (O.zy == nullptr)) return fail(WG_ERR_BAD_ARG, "zmp_x_tm and zmp_y_tm go together");
+  return WG_OK;
+}
+
 // begin / append / end of an on-line walk: the checks they share, then one launch of the resumable kernel
 int zd_online(wg_ctx *ctx, int op, const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps,
               const double *init_feet, const int *select, int lcap, const wg::ZdOut &O, wg_zmpdisc_state_t *state, int *length,
@@ -2128,11 +2161,7 @@ int zd_online(wg_ctx *ctx, int op, const wg_zmpdisc_model_t *model, int B, int s
   wg::ZdConst K;
   if (int rc = use_ctx(ctx)) return rc;
   if (int rc = zd_make_const(model, &K)) return rc;
-  const int smin = op == wg::ZD_OP_BEGIN ? 2 : 1;
-  const bool steps_ok = op == wg::ZD_OP_END || (steps && n_steps && smax >= smin && smax <= WG_ZMPDISC_MAX_STEPS);
-  if (B < 0 || lcap < 1 || !state || !steps_ok || (op == wg::ZD_OP_BEGIN && !init_feet))
-    return fail(WG_ERR_BAD_ARG, "need B >= 0, %d <= smax <= %d, lcap >= 1, non-null inputs and state", smin, WG_ZMPDISC_MAX_STEPS);
-  if ((O.zx == nullptr) != (O.zy == nullptr)) return fail(WG_ERR_BAD_ARG, "zmp_x_tm and zmp_y_tm go together");
+  if (int rc = zd_online_check(op, B, smax, steps, n_steps, init_feet, lcap, O, state)) return rc;
   if (B == 0) return WG_OK;
   const size_t lds = (size_t)K.nwin * 3 * 2 * 64 * 8;
   if (lds > 64 * 1024)
@@ -2142,6 +2171,44 @@ int zd_online(wg_ctx *ctx, int op, const wg_zmpdisc_model_t *model, int B, int s
                      K, op, B, smax, steps, n_steps, init_feet, select, lcap, O, state, length);
   HIP_TRY(hipGetLastError());
   return WG_OK;
+}
+
+// A model per gait: what the four fleet entry points check alike before the checks of their one-model twins -- the fleet itself,
+// its base model (-> K: the window and the taps; the gaits' own models are read on the device) and the room for the wave's models
+// in LDS beside the rings -- and the kernel's view of the fleet.
+int zd_fleet_check(wg_ctx *ctx, const wg_zmpdisc_fleet_t *fleet, int B, wg::ZdConst *K, wg::ZdFleet *FL) {
+  if (int rc = use_ctx(ctx)) return rc;
+  if (!fleet || !fleet->models) return fail(WG_ERR_BAD_ARG, "null fleet or models");
+  if (fleet->M < 1 || (!fleet->model_of && fleet->M != B))
+    return fail(WG_ERR_BAD_ARG, "M = %d: need M >= 1, and M == B = %d without model_of", fleet->M, B);
+  if (int rc = zd_make_const(&fleet->base, K)) return rc;
+  if (wg::zd_lds_bytes(K->nwin, true) > 160 * 1024)
+    return fail(WG_ERR_BAD_ARG, "filter window of %d taps leaves no room for the models of a wave in LDS", K->nwin);
+  *FL = wg::ZdFleet{fleet->models, fleet->model_of, fleet->M, 0};
+  return WG_OK;
+}
+
+template <class Kernel, class... Args>
+int zd_fleet_launch(Kernel kernel, const wg::ZdConst &K, int B, void *hip_stream, Args... args) {
+  const size_t lds = wg::zd_lds_bytes(K.nwin, true);
+  if (lds > 64 * 1024)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kernel, dim3((B + 63) / 64), dim3(64), lds, reinterpret_cast<hipStream_t>(hip_stream), K, args...);
+  HIP_TRY(hipGetLastError());
+  return WG_OK;
+}
+
+// begin / append / end with a model per gait: zd_online's checks, the fleet twin of its kernel
+int zd_online_fleet(wg_ctx *ctx, int op, const wg_zmpdisc_fleet_t *fleet, int B, int smax, const wg_rel_step_t *steps, const int *n_steps,
+                    const double *init_feet, const int *select, int lcap, const wg::ZdOut &O, wg_zmpdisc_state_t *state, int *length,
+                    void *hip_stream) {
+  wg::ZdConst K;
+  wg::ZdFleet FL;
+  if (int rc = zd_fleet_check(ctx, fleet, B, &K, &FL)) return rc;
+  if (int rc = zd_online_check(op, B, smax, steps, n_steps, init_feet, lcap, O, state)) return rc;
+  if (B == 0) return WG_OK;
+  return zd_fleet_launch(wg::wg_zmpdisc_online_fleet_kernel, K, B, hip_stream, FL, op, B, smax, steps, n_steps, init_feet, select, lcap, O,
+                         state, length);
 }
 }  // namespace
 
@@ -2204,6 +2271,45 @@ int wg_zmpdisc_append_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_model_t *model, in
 int wg_zmpdisc_end_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_model_t *model, int B, const int *select, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream) {
   const wg::ZdOut O{zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, right_tm, left_type_tm, right_type_tm};
   return zd_online(ctx, wg::ZD_OP_END, model, B, 0, nullptr, nullptr, nullptr, select, lcap, O, state, length, hip_stream);
+}
+
+// the four with a model per gait
+int wg_zmpdisc_full_fleet_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_fleet_t *fleet, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream) {
+  wg::ZdConst K;
+  wg::ZdFleet FL;
+  if (int rc = zd_fleet_check(ctx, fleet, B, &K, &FL)) return rc;
+  if (int rc = zd_check(ctx, &fleet->base, &K, B, smax, lcap, steps && n_steps && init_feet, "inputs")) return rc;
+  if ((zmp_x_tm == nullptr) != (zmp_y_tm == nullptr)) return fail(WG_ERR_BAD_ARG, "zmp_x_tm and zmp_y_tm go together");
+  if (B == 0) return WG_OK;
+  const wg::ZdOut O{zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, right_tm, left_type_tm, right_type_tm};
+  return zd_fleet_launch(wg::wg_zmpdisc_fleet_kernel, K, B, hip_stream, FL, B, smax, steps, n_steps, init_feet, lcap, O, length);
+}
+
+int wg_zmpdisc_begin_fleet_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_fleet_t *fleet, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream) {
+  const wg::ZdOut O{zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, right_tm, left_type_tm, right_type_tm};
+  return zd_online_fleet(ctx, wg::ZD_OP_BEGIN, fleet, B, smax, steps, n_steps, init_feet, nullptr, lcap, O, state, length, hip_stream);
+}
+
+int wg_zmpdisc_append_fleet_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_fleet_t *fleet, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream) {
+  const wg::ZdOut O{zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, right_tm, left_type_tm, right_type_tm};
+  return zd_online_fleet(ctx, wg::ZD_OP_APPEND, fleet, B, smax, steps, n_steps, nullptr, nullptr, lcap, O, state, length, hip_stream);
+}
+
+int wg_zmpdisc_end_fleet_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_fleet_t *fleet, int B, const int *select, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream) {
+  const wg::ZdOut O{zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, right_tm, left_type_tm, right_type_tm};
+  return zd_online_fleet(ctx, wg::ZD_OP_END, fleet, B, 0, nullptr, nullptr, nullptr, select, lcap, O, state, length, hip_stream);
+}
+
+// the same with the support times of each gait (wg_steps_plan_fleet_kernel: a non-finite time is the gait's own refusal)
+int wg_steps_plan_fleet_dev_ctx(wg_ctx_t *ctx, int B, int ccap, const wg_step_cmd_t *cmds, const int *n_cmds, const double *ss, const double *ds, wg_step_stack_t *stack, int smax, wg_rel_step_t *steps, int *n_steps, void *hip_stream) {
+  if (int rc = use_ctx(ctx)) return rc;
+  if (B < 0 || ccap < 1 || smax < 1 || smax > WG_ZMPDISC_MAX_STEPS || !cmds || !n_cmds || !ss || !ds || !stack || !steps || !n_steps)
+    return fail(WG_ERR_BAD_ARG, "need B >= 0, ccap >= 1, 1 <= smax <= %d, non-null arrays", WG_ZMPDISC_MAX_STEPS);
+  if (B == 0) return WG_OK;
+  hipLaunchKernelGGL(wg::wg_steps_plan_fleet_kernel, dim3((B + wg::kSpWaves - 1) / wg::kSpWaves), dim3(64 * wg::kSpWaves), 0,
+                     reinterpret_cast<hipStream_t>(hip_stream), B, ccap, cmds, n_cmds, ss, ds, stack, smax, steps, n_steps);
+  HIP_TRY(hipGetLastError());
+  return WG_OK;
 }
 
 // the step stack on the device: one wave per gait (wg_steps_kernels.hpp); the host twins are wg_steps.cpp
@@ -2377,6 +2483,13 @@ int wg_zmpdisc_begin_dev(const wg_zmpdisc_model_t *model, int B, int smax, const
 int wg_zmpdisc_append_dev(const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream) { return on_default(&wg_zmpdisc_append_dev_ctx, model, B, smax, steps, n_steps, lcap, zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, left_type_tm, right_tm, right_type_tm, state, length, hip_stream); }
 int wg_zmpdisc_end_dev(const wg_zmpdisc_model_t *model, int B, const int *select, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream) { return on_default(&wg_zmpdisc_end_dev_ctx, model, B, select, lcap, zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, left_type_tm, right_tm, right_type_tm, state, length, hip_stream); }
 int wg_steps_plan_dev(int B, int ccap, const wg_step_cmd_t *cmds, const int *n_cmds, double ss, double ds, wg_step_stack_t *stack, int smax, wg_rel_step_t *steps, int *n_steps, void *hip_stream) { return on_default(&wg_steps_plan_dev_ctx, B, ccap, cmds, n_cmds, ss, ds, stack, smax, steps, n_steps, hip_stream); }
+int wg_zmpdisc_full_fleet_dev(const wg_zmpdisc_fleet_t *fleet, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream) { return on_default(&wg_zmpdisc_full_fleet_dev_ctx, fleet, B, smax, steps, n_steps, init_feet, lcap, zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, left_type_tm, right_tm, right_type_tm, length, hip_stream); }
+int wg_zmpdisc_begin_fleet_dev(const wg_zmpdisc_fleet_t *fleet, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream) { return on_default(&wg_zmpdisc_begin_fleet_dev_ctx, fleet, B, smax, steps, n_steps, init_feet, lcap, zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, left_type_tm, right_tm, right_type_tm, state, length, hip_stream); }
+int wg_zmpdisc_append_fleet_dev(const wg_zmpdisc_fleet_t *fleet, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream) { return on_default(&wg_zmpdisc_append_fleet_dev_ctx, fleet, B, smax, steps, n_steps, lcap, zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, left_type_tm, right_tm, right_type_tm, state, length, hip_stream); }
+int wg_zmpdisc_end_fleet_dev(const wg_zmpdisc_fleet_t *fleet, int B, const int *select, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream) { return on_default(&wg_zmpdisc_end_fleet_dev_ctx, fleet, B, select, lcap, zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, left_type_tm, right_tm, right_type_tm, state, length, hip_stream); }
+int wg_steps_plan_fleet_dev(int B, int ccap, const wg_step_cmd_t *cmds, const int *n_cmds, const double *ss, const double *ds, wg_step_stack_t *stack, int smax, wg_rel_step_t *steps, int *n_steps, void *hip_stream) { return on_default(&wg_steps_plan_fleet_dev_ctx, B, ccap, cmds, n_cmds, ss, ds, stack, smax, steps, n_steps, hip_stream); }
+int wg_foot_constraints_fleet_dev(int B, int lcap, const int *length, const double *time, const double *left_tm, const int *left_type_tm, const double *right_tm, const wg_sole_t *soles, int qcap, wg_zmp_polytope_t *queues, double *t_start, double *t_end, int *count, void *hip_stream) { return on_default(&wg_foot_constraints_fleet_dev_ctx, B, lcap, length, time, left_tm, left_type_tm, right_tm, soles, qcap, queues, t_start, t_end, count, hip_stream); }
+int wg_foot_constraints_append_fleet_dev(int B, int lcap, int first_sample, int *done, const int *length, const double *time, const double *left_tm, const int *left_type_tm, const double *right_tm, const wg_sole_t *soles, int qcap, wg_zmp_polytope_t *queues, double *t_start, double *t_end, int *count, void *hip_stream) { return on_default(&wg_foot_constraints_append_fleet_dev_ctx, B, lcap, first_sample, done, length, time, left_tm, left_type_tm, right_tm, soles, qcap, queues, t_start, t_end, count, hip_stream); }
 int wg_zmpdisc_batch(const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap, double *zmp, double *zmp_theta, int *zmp_type, double *left, int *left_type, double *right, int *right_type, int *length) { return on_default(&wg_zmpdisc_batch_ctx, model, B, smax, steps, n_steps, init_feet, lcap, zmp, zmp_theta, zmp_type, left, left_type, right, right_type, length); }
 
 }  // extern "C"

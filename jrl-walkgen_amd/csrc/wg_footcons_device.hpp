@@ -3,6 +3,7 @@
 //   wg_footcons_kernel<kBuild, kRes>   polytope queues of B feet trajectories: <false / true, false> the whole trajectories
 //                                      (wg_foot_constraints_batch_dev), <false / true, true> behind wg_footcons_resume_kernel the
 //                                      samples that arrived since the last call (wg_foot_constraints_append_dev)
+//                                      <.., .., true> the same with a sole per gait (wg_foot_constraints_fleet_dev, _append_fleet_dev)
 //       FootConstraintsAsLinearSystem::BuildLinearConstraintInequalities  src/Mathematics/FootConstraintsAsLinearSystem.cpp:258-539
 //       ComputeLinearSystem :97-256, FindSimilarConstraints :55-92, ComputeConvexHull::DoComputeConvexHull ConvexHull.cpp:88-203
 //   wg_dimitrov_select_kernel          the queue walk of one tick (wg_dimitrov_select_polys_dev, wg_dimitrov_walk_dev)
@@ -88,9 +89,20 @@ wg_footcons_resume_kernel(int B, int lcap, int first_sample, const int *__restri
 // lines however the lanes' resume points differ; a lane skips the samples of its chunk below its own.  The state before a lane's
 // first new sample is found like the state before a chunk, walking back while the predecessor inherits -- across the resume point
 // and across chunks: the feet arrays hold the whole walk, nothing is carried from call to call but done[b] and count[b].
-template <bool kBuild, bool kRes>
+// kFleet = false: the half sole minus the margins is the launch's, I.hw / I.hh (S is empty).  kFleet = true
+// (wg_foot_constraints_fleet_dev, _append_fleet_dev): the gait's own, made in its lane from S.soles[b] with the launcher's expression.
+// The kernel text is one; the fleet form is a third template argument, off by default, and its one argument rides behind the
+// others in a struct that is empty without it: wg_footcons_kernel<kBuild, kRes> stays the kernel it was.
+template <bool kFleet>
+struct FcSoles {};
+template <>
+struct FcSoles<true> {
+  const wg_sole_t *soles;                // B
+};
+
+template <bool kBuild, bool kRes, bool kFleet = false>
 __global__ void __launch_bounds__(64)
-wg_footcons_kernel(FcIn I, FcOut Q, int *__restrict__ cnt /* [chunks][B] */, FcRes Z) {
+wg_footcons_kernel(FcIn I, FcOut Q, int *__restrict__ cnt /* [chunks][B] */, FcRes Z, FcSoles<kFleet> S) {
   __shared__ double fc_lds[kBuild ? kFcSlots * 2 * 64 : 1];
   const int lane = threadIdx.x, b = blockIdx.x * 64 + lane;
   int chunk = blockIdx.y, crel = blockIdx.y;              // absolute, and as cnt is indexed
@@ -148,6 +160,13 @@ wg_footcons_kernel(FcIn I, FcOut Q, int *__restrict__ cnt /* [chunks][B] */, FcR
     for (int c = cfirst; c < crel; c++) q += cnt[(size_t)c * sB + b];
   }
   const FcPts<64> P{fc_lds + lane};
+  double hw = I.hw, hh = I.hh;
+  if constexpr (kFleet && kBuild) {
+    const wg_sole_t sole = S.soles[b];
+    hw = sole.sole_w * 0.5; hh = sole.sole_h * 0.5;
+    hh -= sole.constraint_y;
+    hw -= sole.constraint_x;
+  }
   int found = 0;
   for (int k = k0; k < n; k++) {
     if (kBuild && found == own) break;
@@ -165,13 +184,13 @@ wg_footcons_kernel(FcIn I, FcOut Q, int *__restrict__ cnt /* [chunks][B] */, FcR
         const double lx = L[0], ly = L[sB], lz = L[2 * sB], lth = L[3 * sB], rx = R[0], ry = R[sB], rz = R[2 * sB], rth = R[3 * sB];
         int nh = 4;
         if (state == kFcDouble) {
-          fc_corners(P, 0, lx, ly, lth, I.hw, I.hh);
-          fc_corners(P, 4, rx, ry, rth, I.hw, I.hh);
+          fc_corners(P, 0, lx, ly, lth, hw, hh);
+          fc_corners(P, 4, rx, ry, rth, hw, hh);
           nh = fc_hull8(P);
         } else if (lz < rz) {
-          fc_corners(P, 0, lx, ly, lth, I.hw, I.hh);
+          fc_corners(P, 0, lx, ly, lth, hw, hh);
         } else {
-          fc_corners(P, 0, rx, ry, rth, I.hw, I.hh);
+          fc_corners(P, 0, rx, ry, rth, hw, hh);
         }
         if (!fc_polytope(P, nh, Q.queues + (size_t)b * Q.qcap + q)) atomicMin(Q.count + b, WG_ERR_BAD_ARG);
         Q.t_start[(size_t)b * Q.qcap + q] = t;

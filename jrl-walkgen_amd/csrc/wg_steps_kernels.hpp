@@ -16,10 +16,13 @@ namespace wg {
 
 constexpr int kSpWaves = 4;              // gaits (waves) per block
 
-__global__ __launch_bounds__(64 * kSpWaves) void wg_steps_plan_kernel(int B, int ccap, const wg_step_cmd_t *__restrict__ cmds,
-                                                                       const int *__restrict__ n_cmds, double ss, double ds,
-                                                                       wg_step_stack_t *stack, int smax,
-                                                                       wg_rel_step_t *__restrict__ steps, int *__restrict__ n_steps) {
+// FLEET = false: ss, ds are the call's (kernel arguments, checked on the host).  FLEET = true (wg_steps_plan_fleet_dev): the
+// gait's own, ss_b[b], ds_b[b]; a gait that runs with a non-finite one is refused like a gait with a bad list.
+template <bool FLEET>
+__device__ __forceinline__ void sp_plan_gait(int B, int ccap, const wg_step_cmd_t *__restrict__ cmds, const int *__restrict__ n_cmds,
+                                             double ss, double ds, const double *__restrict__ ss_b, const double *__restrict__ ds_b,
+                                             wg_step_stack_t *stack, int smax, wg_rel_step_t *__restrict__ steps,
+                                             int *__restrict__ n_steps) {
   const int b = blockIdx.x * kSpWaves + (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
   if (b >= B) return;
   const wg_step_stack_t S = stack[b];
@@ -27,7 +30,14 @@ __global__ __launch_bounds__(64 * kSpWaves) void wg_steps_plan_kernel(int B, int
   const wg_step_cmd_t *C = cmds + (size_t)b * ccap;
   const bool runs = S.error == 0 && nc != 0;              // else: a refused gait stays refused, an idle one sits out
   int keep = S.keep, w_cmd = 0, w_keep = 0, w_i = 0, total = 0;
-  if (runs) total = nc < 0 || nc > ccap || !sp_foot_ok(keep) ? WG_STEPS_BAD_INPUT : sp_scan(C, nc, smax, &keep, lane, &w_cmd, &w_keep, &w_i);
+  bool times_ok = true;
+  if constexpr (FLEET) {
+    if (runs) {
+      ss = ss_b[b]; ds = ds_b[b];
+      times_ok = sp_finite(ss) && sp_finite(ds);
+    }
+  }
+  if (runs) total = nc < 0 || nc > ccap || !sp_foot_ok(keep) || !times_ok ? WG_STEPS_BAD_INPUT : sp_scan(C, nc, smax, &keep, lane, &w_cmd, &w_keep, &w_i);
   if (lane < total) steps[(size_t)b * smax + lane] = sp_cmd_step(C[w_cmd], w_keep, w_i, ss, ds);
   if (lane != 0) return;
   n_steps[b] = total > 0 ? total : 0;
@@ -39,6 +49,21 @@ __global__ __launch_bounds__(64 * kSpWaves) void wg_steps_plan_kernel(int B, int
     T.n_given = S.n_given + total;
     stack[b] = T;
   }
+}
+
+__global__ __launch_bounds__(64 * kSpWaves) void wg_steps_plan_kernel(int B, int ccap, const wg_step_cmd_t *__restrict__ cmds,
+                                                                       const int *__restrict__ n_cmds, double ss, double ds,
+                                                                       wg_step_stack_t *stack, int smax,
+                                                                       wg_rel_step_t *__restrict__ steps, int *__restrict__ n_steps) {
+  sp_plan_gait<false>(B, ccap, cmds, n_cmds, ss, ds, nullptr, nullptr, stack, smax, steps, n_steps);
+}
+
+__global__ __launch_bounds__(64 * kSpWaves) void wg_steps_plan_fleet_kernel(int B, int ccap, const wg_step_cmd_t *__restrict__ cmds,
+                                                                             const int *__restrict__ n_cmds,
+                                                                             const double *__restrict__ ss, const double *__restrict__ ds,
+                                                                             wg_step_stack_t *stack, int smax,
+                                                                             wg_rel_step_t *__restrict__ steps, int *__restrict__ n_steps) {
+  sp_plan_gait<true>(B, ccap, cmds, n_cmds, 0.0, 0.0, ss, ds, stack, smax, steps, n_steps);
 }
 
 }  // namespace wg

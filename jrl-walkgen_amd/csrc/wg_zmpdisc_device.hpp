@@ -16,16 +16,20 @@
 // (lane-contiguous: conflict-free).  Operation order follows the oracle restatement (oracle/zmpdisc_oracle.c) line by
 // line; sin / cos come from include/wg_trig.h like in the tick kernel.
 //
-// The walk is one function template, zd_walk<RES>.  RES = false is the whole-sequence kernel (InitOnLine, every
+// The walk is one function template, zd_walk<RES, FLEET>.  RES = false is the whole-sequence kernel (InitOnLine, every
 // OnLineAddFoot, EndPhaseOfTheWalking in one launch; nothing kept).  RES = true is the on-line form of the reference's public
 // API: one launch runs InitOnLine + some steps (ZD_OP_BEGIN), some more OnLineAddFoot (ZD_OP_APPEND) or
 // EndPhaseOfTheWalking (ZD_OP_END) and carries what the walk keeps between phases in a wg_zmpdisc_state_t per gait.  The
 // walk only ever pushes samples and FilterOutValues reads at most nwin filtered samples back, so a resumed launch refills
 // the filtered ring from the gait's own rows of zmp_x_tm / zmp_y_tm (the reference's deque) -- or, when the caller does not
 // ask for the queue, from the tail the previous launch left in the state.  Everything resumable sits under
-// `if constexpr (RES)`: the whole-sequence instantiation carries none of it.
+// `if constexpr (RES)`: the whole-sequence instantiation carries none of it.  FLEET = true is the twin with a model per gait
+// (ZdLaneModel below).
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <type_traits>
 
 #include "../../include/wg_mpc.h"
 #ifndef WG_TRIG_FN
@@ -196,19 +200,77 @@ enum { ZD_INIT = 0, ZD_STEP = 1, ZD_END = 2 };
 enum { ZD_OP_BEGIN = 0, ZD_OP_APPEND = 1, ZD_OP_END = 2 };
 #define WG_ZD_STATE_MAGIC 0x5a4d5044     // wg_zmpdisc_state_t::begun once InitOnLine has run on it
 
+// A fleet launch (FLEET): a model per gait, models[model_of[g]], or models[g] where model_of is NULL (the host checks M == B).
+struct ZdFleet {
+  const wg_zmpdisc_model_t *models;      // [M]
+  const int *model_of;                   // [B] or NULL
+  int M, pad_;
+};
+
+constexpr int kZdModelWords = (int)(sizeof(wg_zmpdisc_model_t) / 8);
+static_assert(kZdModelWords * 8 == (int)sizeof(wg_zmpdisc_model_t), "wg_zmpdisc_model_t: doubles only");
+// LDS of a launch: the rings, and behind them the models of a fleet wave, [field][lane] like the rings (conflict-free)
+__host__ __device__ inline size_t zd_lds_bytes(int nwin, bool fleet) {
+  return ((size_t)nwin * 3 * 2 + (fleet ? kZdModelWords : 0)) * 64 * 8;
+}
+
+// The model as the walk reads it.  FLEET = false: the kernel argument itself, wave-uniform (SGPRs).  FLEET = true: the lane's
+// own model.  It is not carried in registers across the walk (the kernel sits at one wave per SIMD as it is): the lane keeps it
+// in its column of the LDS table above, and ZdLaneModel names the fields of that column like wg_zmpdisc_model_t names its own --
+// a field is read from LDS where the walk uses it: most of them at the head of a phase, t_single, omega and foot_b / h / f per
+// sample.  T is the launch's (a gait whose own T differs is refused), so the window, the taps and the filter stay wave-uniform.
+struct ZdLdsField {
+  const double *p;
+  __device__ __forceinline__ operator double() const { return *p; }
+};
+struct ZdLaneModel {
+  double T;
+  ZdLdsField preview_time, t_single, t_double, step_height, omega, modulation, zmp_neutral[2], zmp_shift[4], foot_b, foot_h, foot_f;
+#define WG_ZD_COL(field) {col + offsetof(wg_zmpdisc_model_t, field) / 8 * 64}
+  __device__ __forceinline__ ZdLaneModel(double T_, const double *col)
+      : T(T_), preview_time WG_ZD_COL(preview_time), t_single WG_ZD_COL(t_single), t_double WG_ZD_COL(t_double),
+        step_height WG_ZD_COL(step_height), omega WG_ZD_COL(omega), modulation WG_ZD_COL(modulation),
+        zmp_neutral{WG_ZD_COL(zmp_neutral[0]), WG_ZD_COL(zmp_neutral[1])},
+        zmp_shift{WG_ZD_COL(zmp_shift[0]), WG_ZD_COL(zmp_shift[1]), WG_ZD_COL(zmp_shift[2]), WG_ZD_COL(zmp_shift[3])},
+        foot_b WG_ZD_COL(foot_b), foot_h WG_ZD_COL(foot_h), foot_f WG_ZD_COL(foot_f) {}
+#undef WG_ZD_COL
+};
+template <bool FLEET>
+using ZdModelView = std::conditional_t<FLEET, const ZdLaneModel, const wg_zmpdisc_model_t &>;
+template <bool FLEET>
+__device__ __forceinline__ ZdModelView<FLEET> zd_model_view(const ZdConst &K, const double *col) {
+  if constexpr (FLEET) return ZdLaneModel(K.M.T, col);
+  else return K.M;
+}
+
 // RES = false: `op`, `select` and `state` are unused.  RES = true: `steps` holds only the steps of this launch (ZD_OP_BEGIN:
 // the first n_steps[g] >= 2 of the walk; ZD_OP_APPEND: n_steps[g] >= 0 further ones), `select` (ZD_OP_END, may be NULL)
 // names the gaits that end.  A gait that sits a launch out (0 steps, not selected) returns before it touches anything.
-template <bool RES>
-__device__ __forceinline__ void zd_walk(const ZdConst &K, int op, int B, int smax, const wg_rel_step_t *__restrict__ steps,
-                                        const int *__restrict__ n_steps, const double *__restrict__ init_feet,
-                                        const int *__restrict__ select, int lcap, const ZdOut &O,
-                                        wg_zmpdisc_state_t *__restrict__ state, int *__restrict__ length) {
+// FLEET = false: `FL` is unused and every gait walks with K.M.  FLEET = true: gait g walks with its own model out of FL; K.M is the
+// base model, of which only T is read.  A gait whose model_of lies outside [0, FL.M), or whose T is not the base's bit for bit,
+// is refused with WG_ZMPDISC_BAD_INPUT where the other refusals are decided.  Everything of the fleet sits under
+// `if constexpr (FLEET)` or in ZdLaneModel: the instantiations without it carry none of it.
+template <bool RES, bool FLEET>
+__device__ __forceinline__ void zd_walk(const ZdConst &K, const ZdFleet &FL, int op, int B, int smax,
+                                        const wg_rel_step_t *__restrict__ steps, const int *__restrict__ n_steps,
+                                        const double *__restrict__ init_feet, const int *__restrict__ select, int lcap,
+                                        const ZdOut &O, wg_zmpdisc_state_t *__restrict__ state, int *__restrict__ length) {
   extern __shared__ __attribute__((aligned(16))) double zd_lds[];
   const int lane = threadIdx.x;
   const int g = blockIdx.x * 64 + lane;
   if (g >= B) return;
-  const wg_zmpdisc_model_t &M = K.M;
+  [[maybe_unused]] wg_zmpdisc_model_t Mg;           // FLEET: the gait's model, from here to the LDS table and no further
+  [[maybe_unused]] bool model_ok = true;
+  [[maybe_unused]] auto load_model = [&]() {        // called once, by a gait that does not sit the launch out
+    const int mi = FL.model_of ? FL.model_of[g] : g;
+    model_ok = mi >= 0 && mi < FL.M;
+    Mg = FL.models[model_ok ? mi : 0];
+    model_ok = model_ok && __double_as_longlong(Mg.T) == __double_as_longlong(K.M.T);
+  };
+  const wg_zmpdisc_model_t &Mh = [&]() -> const wg_zmpdisc_model_t & {   // what the sample counts are made from
+    if constexpr (FLEET) return Mg;
+    else return K.M;
+  }();
   const size_t sB = (size_t)B;
   const wg_rel_step_t *st = steps + (size_t)g * smax;
   int S = 0;                                        // RES = false / ZD_OP_BEGIN: steps of the sequence, the first one included
@@ -216,7 +278,10 @@ __device__ __forceinline__ void zd_walk(const ZdConst &K, int op, int B, int sma
   wg_zmpdisc_state_t *sp = nullptr;
   if constexpr (!RES) {
     S = n_steps[g];
-    int Ltot = (S <= smax) ? zd_length(M, st, S) : WG_ZMPDISC_BAD_INPUT;
+    if constexpr (FLEET) load_model();
+    int Ltot = (S <= smax) ? zd_length(Mh, st, S) : WG_ZMPDISC_BAD_INPUT;
+    if constexpr (FLEET)
+      if (!model_ok) Ltot = WG_ZMPDISC_BAD_INPUT;
     if (Ltot > lcap) Ltot = WG_ZMPDISC_CAPACITY;
     if (length) length[g] = Ltot;
     if (Ltot < 0) return;
@@ -226,7 +291,10 @@ __device__ __forceinline__ void zd_walk(const ZdConst &K, int op, int B, int sma
     int code;
     if (op == ZD_OP_BEGIN) {
       S = n_steps[g];
-      code = (S >= 2 && S <= smax) ? zd_length_after(M, st, S, 0) : WG_ZMPDISC_BAD_INPUT;
+      if constexpr (FLEET) load_model();
+      code = (S >= 2 && S <= smax) ? zd_length_after(Mh, st, S, 0) : WG_ZMPDISC_BAD_INPUT;
+      if constexpr (FLEET)
+        if (!model_ok) code = WG_ZMPDISC_BAD_INPUT;
       if (code > lcap) code = WG_ZMPDISC_CAPACITY;
       if (code < 0) {
         sp->begun = WG_ZD_STATE_MAGIC; sp->error = code; sp->ended = 0; sp->n_samples = 0; sp->n_steps = 0;
@@ -234,16 +302,19 @@ __device__ __forceinline__ void zd_walk(const ZdConst &K, int op, int B, int sma
     } else {
       S = op == ZD_OP_APPEND ? n_steps[g] : (select ? (select[g] != 0) : 1);
       if (S == 0) return;
+      if constexpr (FLEET) load_model();
       const bool begun = sp->begun == WG_ZD_STATE_MAGIC;
       code = !begun ? WG_ZMPDISC_BAD_INPUT : sp->error;
       if (code == 0 && sp->ended) code = WG_ZMPDISC_BAD_INPUT;
+      if constexpr (FLEET)
+        if (code == 0 && !model_ok) code = WG_ZMPDISC_BAD_INPUT;
       if (code == 0) {
         nz0 = sp->n_samples;
         if (op == ZD_OP_END) {
-          code = zd_end_samples(M);
+          code = zd_end_samples(Mh);
           if (code >= 0 && (long long)nz0 + code > (1 << 24)) code = WG_ZMPDISC_BAD_INPUT;
         } else {
-          code = (S > 0 && S <= smax) ? zd_steps_samples(M, st, S, nz0) : WG_ZMPDISC_BAD_INPUT;
+          code = (S > 0 && S <= smax) ? zd_steps_samples(Mh, st, S, nz0) : WG_ZMPDISC_BAD_INPUT;
         }
         if (code >= 0 && nz0 + code > lcap) code = WG_ZMPDISC_CAPACITY;
       }
@@ -261,6 +332,14 @@ __device__ __forceinline__ void zd_walk(const ZdConst &K, int op, int B, int sma
   R.nf = 2 * K.nwin;
   R.z = zd_lds + lane;
   R.f = zd_lds + (size_t)K.nwin * 2 * 64 + lane;
+  double *mcol = nullptr;
+  if constexpr (FLEET) {                            // the lane's column of the model table: only this lane ever touches it
+    mcol = zd_lds + (size_t)K.nwin * 3 * 2 * 64 + lane;
+    const double *src = reinterpret_cast<const double *>(&Mg);
+#pragma unroll
+    for (int f = 0; f < kZdModelWords; f++) mcol[f * 64] = src[f];
+  }
+  ZdModelView<FLEET> M = zd_model_view<FLEET>(K, mcol);
 
   // ---- gait state -------------------------------------------------------------------------------------------------------
   double s00 = 1.0, s01 = 0.0, s02 = 0.0, s10 = 0.0, s11 = 1.0, s12 = 0.0;   // m_CurrentSupportFootPosition rows 0, 1
@@ -642,7 +721,7 @@ __device__ __forceinline__ void zd_walk(const ZdConst &K, int op, int B, int sma
 __global__ void __launch_bounds__(64)
 wg_zmpdisc_kernel(ZdConst K, int B, int smax, const wg_rel_step_t *__restrict__ steps, const int *__restrict__ n_steps,
                   const double *__restrict__ init_feet, int lcap, ZdOut O, int *__restrict__ length) {
-  zd_walk<false>(K, 0, B, smax, steps, n_steps, init_feet, nullptr, lcap, O, nullptr, length);
+  zd_walk<false, false>(K, ZdFleet{}, 0, B, smax, steps, n_steps, init_feet, nullptr, lcap, O, nullptr, length);
 }
 
 // BEGIN / APPEND / END of an on-line walk; `state` [B], one blob per gait
@@ -651,7 +730,23 @@ wg_zmpdisc_online_kernel(ZdConst K, int op, int B, int smax, const wg_rel_step_t
                          const int *__restrict__ n_steps, const double *__restrict__ init_feet,
                          const int *__restrict__ select, int lcap, ZdOut O, wg_zmpdisc_state_t *__restrict__ state,
                          int *__restrict__ length) {
-  zd_walk<true>(K, op, B, smax, steps, n_steps, init_feet, select, lcap, O, state, length);
+  zd_walk<true, false>(K, ZdFleet{}, op, B, smax, steps, n_steps, init_feet, select, lcap, O, state, length);
+}
+
+// The fleet twins of the two: a model per gait (wg_zmpdisc_full_fleet_dev; _begin_ / _append_ / _end_fleet_dev)
+__global__ void __launch_bounds__(64)
+wg_zmpdisc_fleet_kernel(ZdConst K, ZdFleet FL, int B, int smax, const wg_rel_step_t *__restrict__ steps,
+                        const int *__restrict__ n_steps, const double *__restrict__ init_feet, int lcap, ZdOut O,
+                        int *__restrict__ length) {
+  zd_walk<false, true>(K, FL, 0, B, smax, steps, n_steps, init_feet, nullptr, lcap, O, nullptr, length);
+}
+
+__global__ void __launch_bounds__(64)
+wg_zmpdisc_online_fleet_kernel(ZdConst K, ZdFleet FL, int op, int B, int smax, const wg_rel_step_t *__restrict__ steps,
+                               const int *__restrict__ n_steps, const double *__restrict__ init_feet,
+                               const int *__restrict__ select, int lcap, ZdOut O, wg_zmpdisc_state_t *__restrict__ state,
+                               int *__restrict__ length) {
+  zd_walk<true, true>(K, FL, op, B, smax, steps, n_steps, init_feet, select, lcap, O, state, length);
 }
 
 }  // namespace wg

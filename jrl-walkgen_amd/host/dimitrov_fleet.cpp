@@ -30,13 +30,22 @@
 // checks every model's status and holds gaits 0 and B - 1 to a context configured with their own model: one wg_dimitrov_walk_dev
 // over the gait's final queue.  LO = HI = 0.80 prints the checksum of the run without the option.
 //
+// With --robots LO:HI gait g is a robot of its own size, s = LO + (HI - LO) g / (B - 1): it implies --heights (h = 0.80 s) and scales
+// the sole with its margins, foot_b / h / f, the step height and the step lengths of the generated walks by s; the single support
+// comes from a table of multiples of T, 0.05 s per tenth of s around 0.7 s, so every phase keeps a whole sample count.  The producers
+// are then their fleet forms on the walk's stream -- wg_steps_plan_fleet_dev, wg_zmpdisc_*_fleet_dev (model_of NULL: a model per
+// gait), wg_foot_constraints_fleet_dev / _append_fleet_dev -- in every mode above but --fleet.  Gaits 0 and B - 1 are held to the
+// one-model path, each alone: wg_zmpdisc_full_batch_dev with its own model, wg_foot_constraints_batch_dev with its own sole, one
+// walk on a context configured with its own height.  LO = HI = 1 prints the checksum of the run without the option.
+//
 //   dimitrov_fleet [--batch B] [--steps S] [--ticks K] [--solver 0|1|2] [--fleet FILE] [--online K [--follow]] [--ragged]
-//                  [--plan | --plan-host] [--heights LO:HI]
+//                  [--plan | --plan-host] [--heights LO:HI | --robots LO:HI]
 //
 // --fleet FILE runs a fleet somebody else drew instead of the built-in one (tests/test_dimitrov_walk_gpu.py compares the
 // checksum with its own run of the same fleet): int32 B, int32 smax, wg_zmpdisc_model_t, B x smax wg_rel_step_t, B int32
 // n_steps, B x 6 doubles init_feet, in the machine's byte order.
 #include <chrono>
+#include <cmath>
 #include <cstdlib>
 #include <random>
 
@@ -47,8 +56,8 @@ using wg_fleet::dev_upload;
 
 int main(int argc, char **argv) {
   int B = 4096, S = 8, K = 40, solver = WG_DIMITROV_PLDP, online = 0;
-  bool follow = false, ragged = false, heights = false;
-  double h_lo = 0.0, h_hi = 0.0;
+  bool follow = false, ragged = false, heights = false, robots = false;
+  double h_lo = 0.0, h_hi = 0.0, r_lo = 1.0, r_hi = 1.0;
   int planned = 0;                                            // 1: --plan (steps planned on the device), 2: --plan-host
   const char *fleet = nullptr;
   for (int i = 1; i < argc; ++i) {
@@ -65,10 +74,15 @@ int main(int argc, char **argv) {
       heights = sscanf(argv[++i], "%lf:%lf", &h_lo, &h_hi) == 2;
       if (!heights || !(h_lo > 0.0) || !(h_hi >= h_lo) || !(h_hi < 1e3)) { fprintf(stderr, "FAILED: need --heights LO:HI with 0 < LO <= HI\n"); return 1; }
     }
+    else if (!strcmp(argv[i], "--robots") && i + 1 < argc) {
+      robots = sscanf(argv[++i], "%lf:%lf", &r_lo, &r_hi) == 2;
+      if (!robots || !(r_lo > 0.0) || !(r_hi >= r_lo) || !(r_hi < 1e3)) { fprintf(stderr, "FAILED: need --robots LO:HI with 0 < LO <= HI\n"); return 1; }
+    }
     else if (!strcmp(argv[i], "--online") && i + 1 < argc) { online = atoi(argv[++i]); if (online < 1 || online > WG_ZMPDISC_MAX_STEPS) { fprintf(stderr, "FAILED: need 1 <= --online K <= %d\n", WG_ZMPDISC_MAX_STEPS); return 1; } }
   }
   if (follow && !online) { fprintf(stderr, "FAILED: --follow needs --online K\n"); return 1; }
   if (planned && (ragged || fleet || S < 4)) { fprintf(stderr, "FAILED: --plan needs steps >= 4, no --ragged and no --fleet\n"); return 1; }
+  if (robots && (fleet || heights)) { fprintf(stderr, "FAILED: --robots goes with neither --fleet nor --heights (it implies them)\n"); return 1; }
   const bool on_device = planned == 1;
   wg_fleet::CommandPlan cp;
   wg_zmpdisc_model_t zm;
@@ -77,6 +91,25 @@ int main(int argc, char **argv) {
   std::vector<wg_rel_step_t> steps;
   std::vector<int> n_steps;
   std::vector<double> feet;
+  // --robots: a size, a walk model and a sole per gait (without it: size 1, zm and the one sole for every gait)
+  std::vector<double> size_of;
+  std::vector<wg_zmpdisc_model_t> zms;
+  std::vector<wg_sole_t> soles;
+  const wg_sole_t sole{0.24, 0.138, 0.02, 0.02};
+  if (robots) {
+    if (B < 1) { fprintf(stderr, "FAILED: need B >= 1\n"); return 1; }
+    static const double single[9] = {0.5, 0.55, 0.6, 0.65, 0.7, 0.75, 0.8, 0.85, 0.9};   // multiples of T, by the tenths of s around 1
+    size_of.resize(B); zms.assign(B, zm); soles.assign(B, sole);
+    for (int g = 0; g < B; ++g) {
+      const double s = size_of[g] = B > 1 ? r_lo + (r_hi - r_lo) * g / (B - 1) : r_lo;
+      const long k = lround((s - 1.0) * 10.0);
+      wg_zmpdisc_model_t &m = zms[g];
+      m.t_single = single[(k < -4 ? -4 : k > 4 ? 4 : k) + 4];
+      m.step_height *= s; m.foot_b *= s; m.foot_h *= s; m.foot_f *= s;
+      soles[g] = wg_sole_t{sole.sole_w * s, sole.sole_h * s, sole.constraint_x * s, sole.constraint_y * s};
+    }
+  }
+  auto zm_of = [&](int g) -> const wg_zmpdisc_model_t & { return robots ? zms[g] : zm; };
   if (fleet) {
     FILE *f = fopen(fleet, "rb");
     int32_t hdr[2];
@@ -104,9 +137,9 @@ int main(int argc, char **argv) {
         wg_rel_step_t &s = steps[(size_t)g * S + i];
         memset(&s, 0, sizeof s);
         const bool ends = i == 0 || i == n_steps[g] - 1;
-        s.sx = ends ? 0.0 : len(rng);
+        s.sx = ends ? 0.0 : len(rng) * (robots ? size_of[g] : 1.0);
         s.sy = side * (i == 0 ? 0.105 : 0.21);
-        s.ss_time = zm.t_single; s.ds_time = 0.0; s.step_type = 1;
+        s.ss_time = zm_of(g).t_single; s.ds_time = 0.0; s.step_type = 1;
         side = -side;
       }
       const double f[6] = {0.0, 0.095, 0.0, 0.0, -0.095, 0.0};
@@ -114,8 +147,8 @@ int main(int argc, char **argv) {
     }
     // --plan, --plan-host: the steps come from command lists instead.  On the host they are the twin's input, and with --plan what
     // the buffers are sized by (counts and times only) -- none of them is uploaded then
-    if (planned && (wg_fleet::command_plan(B, S, online, &cp) >= 0 ||
-                    wg_fleet::command_steps(cp, B, S, zm.t_single, zm.t_double, on_device, &steps, &n_steps) >= 0)) {
+    if (planned && (wg_fleet::command_plan(B, S, online, &cp, robots ? size_of.data() : nullptr) >= 0 ||
+                    wg_fleet::command_steps(cp, B, S, zm.t_single, zm.t_double, on_device, &steps, &n_steps, robots ? zms.data() : nullptr) >= 0)) {
       fprintf(stderr, "FAILED: the command lists do not give %d steps\n", S);
       return 1;
     }
@@ -129,7 +162,7 @@ int main(int argc, char **argv) {
 
   int lcap = 0;
   for (int g = 0; g < B; ++g) {
-    const int L = wg_zmpdisc_length(&zm, &steps[(size_t)g * S], n_steps[g]);
+    const int L = wg_zmpdisc_length(&zm_of(g), &steps[(size_t)g * S], n_steps[g]);
     if (L < 1) { fprintf(stderr, "FAILED: gait %d: sequence refused (%d)\n", g, L); return 1; }
     lcap = L > lcap ? L : lcap;
   }
@@ -169,9 +202,10 @@ int main(int argc, char **argv) {
   double *d_h = nullptr; unsigned char *d_blocks = nullptr; int *d_status = nullptr, *d_model_of = nullptr;
   std::vector<double> h_of(B, dm.com_height);
   wg_dimitrov_fleet_t dfl{dm.N, dm.solver, B, 0, dm.T, dm.Tctrl, nullptr, nullptr};
+  if (robots) { heights = true; h_lo = dm.com_height * r_lo; h_hi = dm.com_height * r_hi; }
   if (heights) {
     std::vector<int> ident(B);
-    for (int g = 0; g < B; ++g) { h_of[g] = B > 1 ? h_lo + (h_hi - h_lo) * g / (B - 1) : h_lo; ident[g] = g; }
+    for (int g = 0; g < B; ++g) { h_of[g] = robots ? dm.com_height * size_of[g] : B > 1 ? h_lo + (h_hi - h_lo) * g / (B - 1) : h_lo; ident[g] = g; }
     CHECK_HIP(dev_upload(&d_h, h_of));
     CHECK_HIP(dev_upload(&d_model_of, ident));
     CHECK_HIP(dev_alloc(&d_blocks, (size_t)B * wg_dimitrov_constants_bytes()));
@@ -183,6 +217,31 @@ int main(int argc, char **argv) {
     return heights ? wg_dimitrov_walk_fleet_dev(B, &dfl, qcap, d_queues, d_ts, d_te, d_count, t_, n_, d_states, nullptr, d_ran, 0, s_)
                    : wg_dimitrov_walk_dev(B, qcap, d_queues, d_ts, d_te, d_count, t_, n_, d_states, nullptr, d_ran, 0, s_);
   };
+  // the producers of every mode below: the one-model calls, or with --robots their fleet forms over a model, times and a sole per gait
+  wg_zmpdisc_model_t *d_zms = nullptr; wg_sole_t *d_soles = nullptr; double *d_ss = nullptr, *d_ds = nullptr;
+  wg_zmpdisc_fleet_t zfl{zm, B, 0, nullptr, nullptr};
+  if (robots) {
+    std::vector<double> ss(B), ds(B);
+    for (int g = 0; g < B; ++g) { ss[g] = zms[g].t_single; ds[g] = zms[g].t_double; }
+    CHECK_HIP(dev_upload(&d_zms, zms));
+    CHECK_HIP(dev_upload(&d_soles, soles));
+    CHECK_HIP(dev_upload(&d_ss, ss));
+    CHECK_HIP(dev_upload(&d_ds, ds));
+    zfl.models = d_zms;
+  }
+  auto plan_steps = [&](int ccap_, const wg_step_cmd_t *cmds_, const int *n_, int smax_, wg_rel_step_t *steps_, int *ns_, hipStream_t s_) {
+    return robots ? wg_steps_plan_fleet_dev(B, ccap_, cmds_, n_, d_ss, d_ds, d_stack, smax_, steps_, ns_, s_)
+                  : wg_steps_plan_dev(B, ccap_, cmds_, n_, zm.t_single, zm.t_double, d_stack, smax_, steps_, ns_, s_);
+  };
+  auto zd_full = [&](hipStream_t s_) {
+    return robots ? wg_zmpdisc_full_fleet_dev(&zfl, B, S, d_steps, d_ns, d_feet, lcap, nullptr, nullptr, nullptr, nullptr, d_left, d_lty, d_right, nullptr, d_len, s_)
+                  : wg_zmpdisc_full_batch_dev(&zm, B, S, d_steps, d_ns, d_feet, lcap, nullptr, nullptr, nullptr, nullptr, d_left, d_lty, d_right, nullptr, d_len, s_);
+  };
+  auto fc_batch = [&](hipStream_t s_) {
+    return robots ? wg_foot_constraints_fleet_dev(B, lcap, d_len, d_time, d_left, d_lty, d_right, d_soles, qcap, d_queues, d_ts, d_te, d_count, s_)
+                  : wg_foot_constraints_batch_dev(B, lcap, d_len, d_time, d_left, d_lty, d_right, sole.sole_w, sole.sole_h, sole.constraint_x,
+                                                  sole.constraint_y, qcap, d_queues, d_ts, d_te, d_count, s_);
+  };
   std::vector<wg_dimitrov_state_t> states(B);
   memset(states.data(), 0, sizeof(wg_dimitrov_state_t) * B);
   for (int g = 0; g < B; ++g) states[g].starting = 1;
@@ -193,7 +252,7 @@ int main(int argc, char **argv) {
   std::vector<int> ran_pieces;
   std::vector<hipEvent_t> ev;
   if (online) {
-    const int bad = wg_fleet::online_plan(zm, steps, n_steps, B, S, online, &plan, on_device ? &cp.first_steps : nullptr);
+    const int bad = wg_fleet::online_plan(zm, steps, n_steps, B, S, online, &plan, on_device ? &cp.first_steps : nullptr, robots ? zms.data() : nullptr);
     if (bad >= 0) { fprintf(stderr, "FAILED: gait %d: --online needs two steps to begin with\n", bad); return 1; }
     CHECK_HIP(dev_alloc(&d_walk, B));
     if (on_device) {                                          // one call's steps and counts, written in front of every append
@@ -218,7 +277,7 @@ int main(int argc, char **argv) {
   if (follow) {
     CHECK_HIP(dev_alloc(&d_clock, B));
     CHECK_HIP(dev_alloc(&d_ticks, B));
-    auto dur = [&](const wg_rel_step_t &s) { return s.ds_time != 0.0 ? s.ds_time + s.ss_time : zm.t_double + zm.t_single; };
+    auto dur = [&](const wg_rel_step_t &s, int g) { return s.ds_time != 0.0 ? s.ds_time + s.ss_time : zm_of(g).t_double + zm_of(g).t_single; };
     rounds.assign(plan.n_calls + 1, 0);
     for (int c = 0; c <= plan.n_calls; ++c) {
       double longest = 0.0;
@@ -226,11 +285,11 @@ int main(int argc, char **argv) {
         double d = 0.0;
         const int first = on_device ? cp.first_steps[g] : 2;   // the steps the begin call takes
         if (c == 0) {
-          for (int i = 1; i < first; ++i) d += dur(steps[(size_t)g * S + i]);
-          d = 2 * zm.preview_time + d;
+          for (int i = 1; i < first; ++i) d += dur(steps[(size_t)g * S + i], g);
+          d = 2 * zm_of(g).preview_time + d;
         } else if (on_device) {
-          for (int i = 0; i < plan.cns[(size_t)(c - 1) * B + g]; ++i) d += dur(steps[(size_t)g * S + first + (c - 1) * online + i]);
-        } else for (int i = 0; i < plan.cns[(size_t)(c - 1) * B + g]; ++i) d += dur(plan.chunks[((size_t)(c - 1) * B + g) * online + i]);
+          for (int i = 0; i < plan.cns[(size_t)(c - 1) * B + g]; ++i) d += dur(steps[(size_t)g * S + first + (c - 1) * online + i], g);
+        } else for (int i = 0; i < plan.cns[(size_t)(c - 1) * B + g]; ++i) d += dur(plan.chunks[((size_t)(c - 1) * B + g) * online + i], g);
         longest = d > longest ? d : longest;
       }
       const double r = longest / dm.T + 1.0;
@@ -266,8 +325,10 @@ int main(int argc, char **argv) {
           if (!ended[g] && (have < 0 || cur[g] < have)) have = cur[g];
           done[g] = cur[g];
         }
-        if (int rc = wg_foot_constraints_append_dev(B, lcap, first, d_done, d_len, d_time, d_left, d_lty, d_right, 0.24, 0.138, 0.02,
-                                                    0.02, qcap, d_queues, d_ts, d_te, d_count, st)) return rc;
+        if (int rc = robots ? wg_foot_constraints_append_fleet_dev(B, lcap, first, d_done, d_len, d_time, d_left, d_lty, d_right, d_soles, qcap,
+                                                                   d_queues, d_ts, d_te, d_count, st)
+                            : wg_foot_constraints_append_dev(B, lcap, first, d_done, d_len, d_time, d_left, d_lty, d_right, sole.sole_w, sole.sole_h,
+                                                             sole.constraint_x, sole.constraint_y, qcap, d_queues, d_ts, d_te, d_count, st)) return rc;
         if (follow) {                                          // every gait over the ticks its own queue has made safe
           hipEvent_t e0, e1;
           if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return WG_ERR_HIP;
@@ -305,8 +366,10 @@ int main(int argc, char **argv) {
           if (sel[(size_t)c * B + g]) { any = true; ended[g] = 1; cur[g] = len_ended[g]; }
         if (!any) return WG_OK;
         max_ticks = K;                                         // an ended gait's queue is final: whatever it has left
-        if (int rc = wg_zmpdisc_end_dev(&zm, B, d_sel + (size_t)c * B, lcap, nullptr, nullptr, nullptr, nullptr, d_left, d_lty, d_right,
-                                        nullptr, d_walk, d_len, st)) return rc;
+        if (int rc = robots ? wg_zmpdisc_end_fleet_dev(&zfl, B, d_sel + (size_t)c * B, lcap, nullptr, nullptr, nullptr, nullptr, d_left, d_lty,
+                                                       d_right, nullptr, d_walk, d_len, st)
+                            : wg_zmpdisc_end_dev(&zm, B, d_sel + (size_t)c * B, lcap, nullptr, nullptr, nullptr, nullptr, d_left, d_lty, d_right,
+                                                 nullptr, d_walk, d_len, st)) return rc;
         return grow_and_walk();
       };
       CHECK_HIP(hipMemsetAsync(d_done, 0, sizeof(int) * B, st));
@@ -318,19 +381,22 @@ int main(int argc, char **argv) {
       CHECK_HIP(hipStreamSynchronize(st));
       const auto t0 = std::chrono::steady_clock::now();
       // --plan: the support foot and the arc become the steps the begin call takes
-      if (on_device) CHECK_WG(wg_steps_plan_dev(B, cp.ccap, d_cmds, d_ncmds, zm.t_single, zm.t_double, d_stack, S, d_steps, d_ns, st));
-      CHECK_WG(wg_zmpdisc_begin_dev(&zm, B, S, d_steps, on_device ? d_ns : d_two, d_feet, lcap, nullptr, nullptr, nullptr, nullptr, d_left, d_lty, d_right,
-                                    nullptr, d_walk, d_len, st));
+      if (on_device) CHECK_WG(plan_steps(cp.ccap, d_cmds, d_ncmds, S, d_steps, d_ns, st));
+      CHECK_WG(robots ? wg_zmpdisc_begin_fleet_dev(&zfl, B, S, d_steps, on_device ? d_ns : d_two, d_feet, lcap, nullptr, nullptr, nullptr, nullptr,
+                                                   d_left, d_lty, d_right, nullptr, d_walk, d_len, st)
+                      : wg_zmpdisc_begin_dev(&zm, B, S, d_steps, on_device ? d_ns : d_two, d_feet, lcap, nullptr, nullptr, nullptr, nullptr, d_left,
+                                             d_lty, d_right, nullptr, d_walk, d_len, st));
       for (int g = 0; g < B; ++g) cur[g] = len_after[g];
       if (follow) max_ticks = rounds[0];
       CHECK_WG(grow_and_walk());
       CHECK_WG(end_those_out_of_steps(0));
       for (int c = 0; c < n_calls; ++c) {
         const size_t at = on_device ? 0 : (size_t)c * B;       // --plan: call c's steps are planned into the one chunk
-        if (on_device) CHECK_WG(wg_steps_plan_dev(B, online, d_later + (size_t)c * B * online, d_nlater + (size_t)c * B, zm.t_single,
-                                                  zm.t_double, d_stack, online, d_chunks, d_cns, st));
-        CHECK_WG(wg_zmpdisc_append_dev(&zm, B, online, d_chunks + at * online, d_cns + at, lcap, nullptr, nullptr,
-                                       nullptr, nullptr, d_left, d_lty, d_right, nullptr, d_walk, d_len, st));
+        if (on_device) CHECK_WG(plan_steps(online, d_later + (size_t)c * B * online, d_nlater + (size_t)c * B, online, d_chunks, d_cns, st));
+        CHECK_WG(robots ? wg_zmpdisc_append_fleet_dev(&zfl, B, online, d_chunks + at * online, d_cns + at, lcap, nullptr, nullptr, nullptr, nullptr,
+                                                      d_left, d_lty, d_right, nullptr, d_walk, d_len, st)
+                        : wg_zmpdisc_append_dev(&zm, B, online, d_chunks + at * online, d_cns + at, lcap, nullptr, nullptr, nullptr, nullptr,
+                                                d_left, d_lty, d_right, nullptr, d_walk, d_len, st));
         for (int g = 0; g < B; ++g)
           if (!ended[g]) cur[g] = len_after[(size_t)(c + 1) * B + g];
         if (follow) max_ticks = rounds[c + 1];
@@ -354,11 +420,9 @@ int main(int argc, char **argv) {
       continue;
     }
     const auto t0 = std::chrono::steady_clock::now();
-    if (on_device) CHECK_WG(wg_steps_plan_dev(B, cp.ccap, d_cmds, d_ncmds, zm.t_single, zm.t_double, d_stack, S, d_steps, d_ns, st));
-    CHECK_WG(wg_zmpdisc_full_batch_dev(&zm, B, S, d_steps, d_ns, d_feet, lcap, nullptr, nullptr, nullptr, nullptr, d_left, d_lty, d_right,
-                                       nullptr, d_len, st));
-    CHECK_WG(wg_foot_constraints_batch_dev(B, lcap, d_len, d_time, d_left, d_lty, d_right, 0.24, 0.138, 0.02, 0.02, qcap, d_queues, d_ts,
-                                           d_te, d_count, st));
+    if (on_device) CHECK_WG(plan_steps(cp.ccap, d_cmds, d_ncmds, S, d_steps, d_ns, st));
+    CHECK_WG(zd_full(st));
+    CHECK_WG(fc_batch(st));
     CHECK_HIP(hipStreamSynchronize(st));
     const auto t1 = std::chrono::steady_clock::now();
     CHECK_WG(walk(0.0, K, st));
@@ -384,22 +448,51 @@ int main(int argc, char **argv) {
     for (int g = 0; g < B; ++g)
       if (status[g] != WG_OK) { fprintf(stderr, "FAILED: model %d (height %.4f): status %d\n", g, h_of[g], status[g]); return 1; }
     // gaits 0 and B - 1 once more, each alone: the default context configured with the gait's own model, one walk over its final queue
+    // --robots: the gait's queue is made once more as well, through the one-model producers with the gait's own model and sole
     wg_dimitrov_state_t *d_one;
     CHECK_HIP(dev_alloc(&d_one, 1));
+    wg_rel_step_t *d_s1 = nullptr; int *d_n1 = nullptr, *d_len1 = nullptr, *d_lty1 = nullptr, *d_count1 = nullptr;
+    double *d_left1 = nullptr, *d_right1 = nullptr, *d_ts1 = nullptr, *d_te1 = nullptr; wg_zmp_polytope_t *d_q1 = nullptr;
+    if (robots) {
+      CHECK_HIP(dev_alloc(&d_s1, S)); CHECK_HIP(dev_alloc(&d_n1, 1)); CHECK_HIP(dev_alloc(&d_len1, 1)); CHECK_HIP(dev_alloc(&d_count1, 1));
+      CHECK_HIP(dev_alloc(&d_lty1, lcap)); CHECK_HIP(dev_alloc(&d_left1, 6 * (size_t)lcap)); CHECK_HIP(dev_alloc(&d_right1, 6 * (size_t)lcap));
+      CHECK_HIP(dev_alloc(&d_ts1, qcap)); CHECK_HIP(dev_alloc(&d_te1, qcap)); CHECK_HIP(dev_alloc(&d_q1, qcap));
+    }
     for (int g : {0, B - 1}) {
       wg_dimitrov_model_t own = dm;
       own.com_height = h_of[g];
       CHECK_WG(wg_dimitrov_configure(&own));
+      const wg_zmp_polytope_t *q_g = d_queues + (size_t)g * qcap;
+      const double *ts_g = d_ts + (size_t)g * qcap, *te_g = d_te + (size_t)g * qcap;
+      const int *count_g = d_count + g;
+      if (robots) {
+        std::vector<wg_rel_step_t> own_steps(&steps[(size_t)g * S], &steps[(size_t)g * S] + S);
+        int n_own = n_steps[g];
+        if (planned) {                                          // --plan keeps only the times of a gait's steps on the host: plan them here
+          wg_step_stack_t stack = {1, 0, 0, 0};
+          CHECK_WG(wg_steps_plan(&cp.whole[(size_t)g * S], cp.n_whole[g], zms[g].t_single, zms[g].t_double, &stack, S, own_steps.data(), &n_own));
+          if (stack.error || n_own != n_steps[g]) { fprintf(stderr, "FAILED: gait %d: its command list gives %d steps (%d)\n", g, n_own, stack.error); return 1; }
+        }
+        CHECK_HIP(hipMemcpy(d_s1, own_steps.data(), sizeof(wg_rel_step_t) * S, hipMemcpyHostToDevice));
+        CHECK_HIP(hipMemcpy(d_n1, &n_own, sizeof(int), hipMemcpyHostToDevice));
+        CHECK_WG(wg_zmpdisc_full_batch_dev(&zms[g], 1, S, d_s1, d_n1, d_feet + (size_t)g * 6, lcap, nullptr, nullptr, nullptr, nullptr, d_left1, d_lty1,
+                                           d_right1, nullptr, d_len1, st));
+        CHECK_WG(wg_foot_constraints_batch_dev(1, lcap, d_len1, d_time, d_left1, d_lty1, d_right1, soles[g].sole_w, soles[g].sole_h,
+                                               soles[g].constraint_x, soles[g].constraint_y, qcap, d_q1, d_ts1, d_te1, d_count1, st));
+        q_g = d_q1; ts_g = d_ts1; te_g = d_te1; count_g = d_count1;
+      }
       wg_dimitrov_state_t one;
       memset(&one, 0, sizeof one);
       one.starting = 1;
       CHECK_HIP(hipMemcpy(d_one, &one, sizeof one, hipMemcpyHostToDevice));
-      CHECK_WG(wg_dimitrov_walk_dev(1, qcap, d_queues + (size_t)g * qcap, d_ts + (size_t)g * qcap, d_te + (size_t)g * qcap, d_count + g, 0.0, K,
-                                    d_one, nullptr, nullptr, 0, st));
+      CHECK_WG(wg_dimitrov_walk_dev(1, qcap, q_g, ts_g, te_g, count_g, 0.0, K, d_one, nullptr, nullptr, 0, st));
       CHECK_HIP(hipStreamSynchronize(st));
       CHECK_HIP(hipMemcpy(&one, d_one, sizeof one, hipMemcpyDeviceToHost));
       if (memcmp(&one, &states[g], sizeof one)) { fprintf(stderr, "FAILED: gait %d differs from a context configured with its own model\n", g); return 1; }
     }
+    if (robots)
+      printf("dimitrov_fleet: robots of size %.4f .. %.4f, a walk model, support times and a sole per gait; gaits 0 and %d == the one-model "
+             "producers with their own model and sole\n", r_lo, r_hi, B - 1);
     printf("dimitrov_fleet: CoM heights %.4f .. %.4f m, the constants of %d models made on the device, all status 0; gaits 0 and %d == a "
            "context configured with their own model\n", h_lo, h_hi, B, B - 1);
   }

@@ -51,10 +51,12 @@ struct OnlinePlan {
 
 // steps [B][S], n_steps [B].  Returns -1, or the first gait with fewer than the two steps the begin call needs.
 // `first`: [B] or null -- the steps the begin call takes of each gait where that is not two of every one (--plan: the support
-// foot and the arc); only the times of `steps` are read then.
+// foot and the arc); only the times of `steps` are read then.  `models`: [B] or null -- a model per gait in place of zm.
 inline int online_plan(const wg_zmpdisc_model_t &zm, const std::vector<wg_rel_step_t> &steps, const std::vector<int> &n_steps, int B,
-                       int S, int K, OnlinePlan *plan, const std::vector<int> *first = nullptr) {
+                       int S, int K, OnlinePlan *plan, const std::vector<int> *first = nullptr,
+                       const wg_zmpdisc_model_t *models = nullptr) {
   OnlinePlan &p = *plan;
+  auto model = [&](int g) { return models ? &models[g] : &zm; };
   if (first) {
     int n_calls = 0;
     for (int g = 0; g < B; ++g) {
@@ -71,10 +73,10 @@ inline int online_plan(const wg_zmpdisc_model_t &zm, const std::vector<wg_rel_st
     for (int g = 0; g < B; ++g) {
       const wg_rel_step_t *sg = &steps[(size_t)g * S];
       const int f = (*first)[g];
-      p.len_ended[g] = wg_zmpdisc_length_after(&zm, sg, n_steps[g], 1);
+      p.len_ended[g] = wg_zmpdisc_length_after(model(g), sg, n_steps[g], 1);
       for (int c = 0; c <= n_calls; ++c) {
         const int given = f + c * K < n_steps[g] ? f + c * K : n_steps[g];
-        p.len_after[(size_t)c * B + g] = wg_zmpdisc_length_after(&zm, sg, given, 0);
+        p.len_after[(size_t)c * B + g] = wg_zmpdisc_length_after(model(g), sg, given, 0);
         p.sel[(size_t)c * B + g] = given == n_steps[g] && (c == 0 || f + (c - 1) * K < n_steps[g]);
         if (c < n_calls) p.cns[(size_t)c * B + g] = (f + (c + 1) * K < n_steps[g] ? f + (c + 1) * K : n_steps[g]) - given;
       }
@@ -93,10 +95,10 @@ inline int online_plan(const wg_zmpdisc_model_t &zm, const std::vector<wg_rel_st
   for (int g = 0; g < B; ++g) {
     if (n_steps[g] < 2) return g;
     const wg_rel_step_t *sg = &steps[(size_t)g * S];
-    p.len_ended[g] = wg_zmpdisc_length_after(&zm, sg, n_steps[g], 1);
+    p.len_ended[g] = wg_zmpdisc_length_after(model(g), sg, n_steps[g], 1);
     for (int c = 0; c <= n_calls; ++c) {
       const int given = 2 + c * K < n_steps[g] ? 2 + c * K : n_steps[g];
-      p.len_after[(size_t)c * B + g] = wg_zmpdisc_length_after(&zm, sg, given, 0);
+      p.len_after[(size_t)c * B + g] = wg_zmpdisc_length_after(model(g), sg, given, 0);
       p.sel[(size_t)c * B + g] = given == n_steps[g] && (c == 0 || 2 + (c - 1) * K < n_steps[g]);
     }
     for (int c = 0; c < n_calls; ++c) {
@@ -123,7 +125,8 @@ struct CommandPlan {
 };
 
 // Returns -1, or the first gait whose list does not give S steps (cannot be for 4 <= S <= WG_ZMPDISC_MAX_STEPS).  K == 0: no cuts.
-inline int command_plan(int B, int S, int K, CommandPlan *plan) {
+// `scale`: [B] or null -- the size of gait g's robot: its arc's radius and the lengths of its on-line steps grow with it.
+inline int command_plan(int B, int S, int K, CommandPlan *plan, const double *scale = nullptr) {
   CommandPlan &p = *plan;
   p.ccap = S;
   p.whole.assign((size_t)B * S, wg_step_cmd_t{WG_STEP_NONE, 0, {0.0, 0.0, 0.0}});
@@ -133,13 +136,14 @@ inline int command_plan(int B, int S, int K, CommandPlan *plan) {
   for (int g = 0; g < B; ++g) {
     wg_step_cmd_t *c = &p.whole[(size_t)g * S];
     const int foot = (g & 1) ? 1 : -1, most_arc = S - 3 < 5 ? S - 3 : 5, n_arc = 1 + g % most_arc;
-    const double R = 0.4 + 0.05 * (g % 17), deg = (n_arc - 0.5) * 0.15 / R * 180.0 / 3.14159265358979323846;
+    const double sc = scale ? scale[g] : 1.0;
+    const double R = (0.4 + 0.05 * (g % 17)) * sc, deg = (n_arc - 0.5) * 0.15 / R * 180.0 / 3.14159265358979323846;
     int n = 0;
     c[n++] = wg_step_cmd_t{WG_STEP_SUPPORT_FOOT, foot, {0.0, 0.0, 0.0}};
     c[n++] = wg_step_cmd_t{WG_STEP_ARC, -foot, {0.0, (g & 2) ? -R : R, deg}};   // n_arc - 1 whole steps and the shorter last one
     p.first_steps[g] = wg_steps_count(c, 2);
     if (p.first_steps[g] != 1 + n_arc) return g;
-    for (int i = 0; i < S - 2 - n_arc; ++i) c[n++] = wg_step_cmd_t{WG_STEP_ONLINE, 0, {0.1 + 0.01 * (g % 10), 0.0, (g % 7) - 3.0}};
+    for (int i = 0; i < S - 2 - n_arc; ++i) c[n++] = wg_step_cmd_t{WG_STEP_ONLINE, 0, {(0.1 + 0.01 * (g % 10)) * sc, 0.0, (g % 7) - 3.0}};
     c[n++] = wg_step_cmd_t{WG_STEP_LAST_SUPPORT, 0, {0.0, 0.0, 0.0}};
     p.n_whole[g] = n;
     if (wg_steps_count(c, n) != S) return g;
@@ -160,10 +164,12 @@ inline int command_plan(int B, int S, int K, CommandPlan *plan) {
 // write.  --plan (times_only) uploads none of them and only sizes its buffers: wg_steps_count steps per gait that carry the
 // call's times and nothing else -- a walk's length depends only on the count and the times (wg_zmpdisc_length_after) -- but for
 // gait 0, whose steps the programs check their device chain against.  Returns -1, or the first gait that does not give S steps.
+// `models`: [B] or null -- gait g's steps carry its own model's support times in place of ss, ds.
 inline int command_steps(const CommandPlan &p, int B, int S, double ss, double ds, bool times_only, std::vector<wg_rel_step_t> *steps,
-                         std::vector<int> *n_steps) {
+                         std::vector<int> *n_steps, const wg_zmpdisc_model_t *models = nullptr) {
   for (int g = 0; g < B; ++g) {
     wg_rel_step_t *sg = &(*steps)[(size_t)g * S];
+    if (models) { ss = models[g].t_single; ds = models[g].t_double; }
     if (times_only && g > 0) {
       const int n = (*n_steps)[g] = wg_steps_count(&p.whole[(size_t)g * S], p.n_whole[g]);
       if (n != S) return g;

@@ -181,6 +181,13 @@ def lib():
             _lib.wg_steps_plan.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
             _lib.wg_steps_plan_dev.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_int,
                                                C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(_lib, "wg_zmpdisc_full_fleet_dev"):       # absent from older experiment builds (WG_LIB_PATH, A/B runs)
+            for fleet, one in (("wg_zmpdisc_full_fleet_dev", "wg_zmpdisc_full_batch_dev"), ("wg_zmpdisc_begin_fleet_dev", "wg_zmpdisc_begin_dev"),
+                               ("wg_zmpdisc_append_fleet_dev", "wg_zmpdisc_append_dev"), ("wg_zmpdisc_end_fleet_dev", "wg_zmpdisc_end_dev")):
+                getattr(_lib, fleet).argtypes = getattr(_lib, one).argtypes      # a wg_zmpdisc_fleet_t * in place of the model
+            _lib.wg_steps_plan_fleet_dev.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 3
+            _lib.wg_foot_constraints_fleet_dev.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int] + [C.c_void_p] * 5
+            _lib.wg_foot_constraints_append_fleet_dev.argtypes = [C.c_int] * 3 + [C.c_void_p] * 7 + [C.c_int] + [C.c_void_p] * 5
         # contexts: NAME_ctx(ctx, args...) for every entry point NAME(args...) that keeps or stages device-side state
         _lib.wg_ctx_create.argtypes = [C.c_int, C.c_void_p]
         _lib.wg_ctx_destroy.argtypes = [C.c_void_p]
@@ -215,7 +222,9 @@ CTX_ENTRY_POINTS = ("wg_set_overlap_strict", "wg_overlap_serialised", "wg_qp_sol
                     "wg_steps_plan_dev", "wg_riccati_gains_batch", "wg_riccati_gains_batch_dev", "wg_preview_run_fleet_dev",
                     "wg_preview_follow_fleet_dev", "wg_dimitrov_constants_batch", "wg_dimitrov_constants_batch_dev",
                     "wg_dimitrov_tick_fleet_dev", "wg_dimitrov_walk_fleet_dev", "wg_dimitrov_follow_fleet_dev",
-                    "wg_mpc_blocks_batch", "wg_mpc_blocks_batch_dev", "wg_mpc_tick_fleet_dev", "wg_mpc_run_fleet_dev")
+                    "wg_mpc_blocks_batch", "wg_mpc_blocks_batch_dev", "wg_mpc_tick_fleet_dev", "wg_mpc_run_fleet_dev",
+                    "wg_zmpdisc_full_fleet_dev", "wg_zmpdisc_begin_fleet_dev", "wg_zmpdisc_append_fleet_dev", "wg_zmpdisc_end_fleet_dev",
+                    "wg_steps_plan_fleet_dev", "wg_foot_constraints_fleet_dev", "wg_foot_constraints_append_fleet_dev")
 
 
 class Context:
@@ -782,6 +791,42 @@ def zmpdisc_end_dev(model, B, lcap, outs, state_ptr, length_ptr=None, select_ptr
                                     stream))
 
 
+# ---- the same walks with a model per gait (include/wg_mpc.h, "The same walks with a model per gait") ----
+class ZmpDiscFleet(C.Structure):        # wg_zmpdisc_fleet_t
+    _fields_ = [("base", ZmpDiscModel), ("M", C.c_int), ("pad_", C.c_int), ("models", C.c_void_p), ("model_of", C.c_void_p)]
+
+
+ZMPDISC_FLEET_BYTES = 152
+
+
+def zmpdisc_fleet(base, M, models_ptr, model_of_ptr=None):
+    """wg_zmpdisc_fleet_t: `base` (its T fixes the launch shape), M models on the device, model_of [B] on the device or None
+    (M == B, gait b walks with models[b])"""
+    return ZmpDiscFleet(base, int(M), 0, models_ptr, model_of_ptr)
+
+
+def zmpdisc_full_fleet_dev(fleet, B, smax, steps_ptr, n_steps_ptr, init_feet_ptr, lcap, outs, length_ptr=None, stream=None):
+    """wg_zmpdisc_full_batch_dev with a model per gait; `outs` as in zmpdisc_begin_dev"""
+    _check(lib().wg_zmpdisc_full_fleet_dev(C.byref(fleet), int(B), int(smax), steps_ptr, n_steps_ptr, init_feet_ptr, int(lcap),
+                                           *_zd_outs(outs), length_ptr, stream))
+
+
+def zmpdisc_begin_fleet_dev(fleet, B, smax, steps_ptr, n_steps_ptr, init_feet_ptr, lcap, outs, state_ptr, length_ptr=None,
+                            stream=None):
+    _check(lib().wg_zmpdisc_begin_fleet_dev(C.byref(fleet), int(B), int(smax), steps_ptr, n_steps_ptr, init_feet_ptr, int(lcap),
+                                            *_zd_outs(outs), state_ptr, length_ptr, stream))
+
+
+def zmpdisc_append_fleet_dev(fleet, B, smax, steps_ptr, n_steps_ptr, lcap, outs, state_ptr, length_ptr=None, stream=None):
+    _check(lib().wg_zmpdisc_append_fleet_dev(C.byref(fleet), int(B), int(smax), steps_ptr, n_steps_ptr, int(lcap),
+                                             *_zd_outs(outs), state_ptr, length_ptr, stream))
+
+
+def zmpdisc_end_fleet_dev(fleet, B, lcap, outs, state_ptr, length_ptr=None, select_ptr=None, stream=None):
+    _check(lib().wg_zmpdisc_end_fleet_dev(C.byref(fleet), int(B), select_ptr, int(lcap), *_zd_outs(outs), state_ptr, length_ptr,
+                                          stream))
+
+
 # ---- the step stack: command lists -> the steps the zmpdisc calls read (include/wg_mpc.h, "Where the steps come from") ----
 STEP_NONE, STEP_SUPPORT_FOOT, STEP_ARC, STEP_LAST_SUPPORT, STEP_ADD, STEP_ONLINE, STEP_ONLINE_IDLE = range(7)
 STEPS_BAD_INPUT, STEPS_CAPACITY = -1, -2
@@ -831,6 +876,12 @@ def steps_plan_dev_ctx(ctx, B, ccap, cmds_ptr, n_cmds_ptr, ss, ds, stack_ptr, sm
                                        steps_ptr, n_steps_ptr, stream))
 
 
+def steps_plan_fleet_dev(B, ccap, cmds_ptr, n_cmds_ptr, ss_ptr, ds_ptr, stack_ptr, smax, steps_ptr, n_steps_ptr, stream=None):
+    """steps_plan_dev with the support times of each gait: ss, ds [B] on the device"""
+    _check(lib().wg_steps_plan_fleet_dev(int(B), int(ccap), cmds_ptr, n_cmds_ptr, ss_ptr, ds_ptr, stack_ptr, int(smax), steps_ptr,
+                                         n_steps_ptr, stream))
+
+
 def foot_constraints(time, left, left_type, right, sole_w, sole_h, constraint_x, constraint_y, cap=256):
     """wg_foot_constraints: (polys (ZmpPolytope * n), t_start[n], t_end[n])."""
     time = np.ascontiguousarray(time, dtype=np.float64); left = np.ascontiguousarray(left, dtype=np.float64)
@@ -871,6 +922,29 @@ def foot_constraints_append_dev(B, lcap, first_sample, done_ptr, length_ptr, tim
                                                 left_type_tm_ptr, right_tm_ptr, float(sole_w), float(sole_h), float(constraint_x),
                                                 float(constraint_y), int(qcap), queues_ptr, t_start_ptr, t_end_ptr, count_ptr,
                                                 stream))
+
+
+class Sole(C.Structure):                # wg_sole_t
+    _fields_ = [(k, C.c_double) for k in ("sole_w", "sole_h", "constraint_x", "constraint_y")]
+
+
+SOLE_BYTES = 32
+
+
+def foot_constraints_fleet_dev(B, lcap, length_ptr, time_ptr, left_tm_ptr, left_type_tm_ptr, right_tm_ptr, soles_ptr, qcap,
+                               queues_ptr, t_start_ptr, t_end_ptr, count_ptr, stream=None):
+    """foot_constraints_batch_dev with a sole per gait: soles (Sole * B) on the device"""
+    _check(lib().wg_foot_constraints_fleet_dev(int(B), int(lcap), length_ptr, time_ptr, left_tm_ptr, left_type_tm_ptr,
+                                               right_tm_ptr, soles_ptr, int(qcap), queues_ptr, t_start_ptr, t_end_ptr, count_ptr,
+                                               stream))
+
+
+def foot_constraints_append_fleet_dev(B, lcap, first_sample, done_ptr, length_ptr, time_ptr, left_tm_ptr, left_type_tm_ptr,
+                                      right_tm_ptr, soles_ptr, qcap, queues_ptr, t_start_ptr, t_end_ptr, count_ptr, stream=None):
+    """foot_constraints_append_dev with a sole per gait"""
+    _check(lib().wg_foot_constraints_append_fleet_dev(int(B), int(lcap), int(first_sample), done_ptr, length_ptr, time_ptr,
+                                                      left_tm_ptr, left_type_tm_ptr, right_tm_ptr, soles_ptr, int(qcap), queues_ptr,
+                                                      t_start_ptr, t_end_ptr, count_ptr, stream))
 
 
 def dimitrov_select_polys_dev(B, qcap, queues_ptr, t_start_ptr, t_end_ptr, count_ptr, t0, polys_ptr, ran_out_ptr=None,
