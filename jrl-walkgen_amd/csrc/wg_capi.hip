@@ -319,6 +319,16 @@ int lpt_prepare(Lpt &s, const void *key, int B, hipStream_t st, int **order, int
   return WG_OK;
 }
 
+// one launch with `lds` bytes of dynamic LDS: above 64 KB the kernel is first given leave to use them
+template <class Kernel, class... Args>
+int launch_lds(Kernel kernel, dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+  if (lds > 64 * 1024)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
+  HIP_TRY(hipGetLastError());
+  return WG_OK;
+}
+
 // the entry points without a context argument: the same call on the process-wide default context
 template <class R, class... P, class... A>
 R on_default(R (*fn)(wg_ctx *, P...), A... args) {
@@ -1288,53 +1298,48 @@ int dimitrov_check(wg_ctx *ctx, int B, const wg_zmp_polytope_t *polys, const wg_
   return WG_OK;
 }
 
-// the tick launch of wg_dimitrov_tick_batch_dev and of every tick of wg_dimitrov_walk_dev; with ctx->launch_mu held.  With `row`
-// (wg_dimitrov_follow_dev): the follow wrappers of the same ticks -- gait g writes row row[g] of outs, or sits the launch out
-// With `fl` (the wg_dimitrov_*_fleet_dev calls): the fleet twins of the same kernels -- gait g binds blocks[model_of[g]] where the
-// others bind the context's one model, of which nothing is read.
-int dimitrov_tick_launch(wg_ctx *ctx, int B, const wg_zmp_polytope_t *polys, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int max_iter, hipStream_t stq, const int *row = nullptr, const wg_dimitrov_fleet_t *fl = nullptr) {
-  const int solver = fl ? fl->solver : ctx->dim_host->solver;
-  const unsigned char *blocks = fl ? static_cast<const unsigned char *>(fl->blocks) : nullptr;
+// one tick launch of the form the two bindings name (wg_dimitrov_kernels.hpp); with ctx->launch_mu held.  The plain form goes by the
+// name and the arguments it is timed by, every other form is an instantiation of the form kernels.
+template <class Model, class Row>
+int dimitrov_launch_form(wg_ctx *ctx, int solver, int B, Model Mo, Row Ro, const wg_zmp_polytope_t *polys, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int max_iter, hipStream_t stq) {
+  constexpr bool plain = std::is_same<Model, DimOneModel>::value && std::is_same<Row, DimOwnRow>::value;
+  constexpr bool follows = std::is_same<Row, DimFollowRow>::value;
   if (solver != WG_DIMITROV_PLDP) {                      // modes QLD / QLDANDLQ: the in-wave ql0002 as the back-end
     const size_t ldsq = wg::dimitrov_qld_lds_bytes();
+    const bool lq = solver == WG_DIMITROV_QLDANDLQ;
     // more gaits than resident waves (eight per CU: 256 registers, two waves per SIMD): longest-solve-first by the previous tick
     // on the same state array (scheduling only).  The order lives in a buffer of the context: not while another stream's launch
     // of this context may still be reading it
     int *order = nullptr, *iters_out = nullptr;
     if ((size_t)B > (size_t)ctx->num_cu * per_cu_granules(ldsq, 8) && !slot_pending_elsewhere(ctx->aux_order, stq) && env_flag("WG_QL_LPT", true)) {
       // a follow launch writes the counts of the gaits that go only: the others keep their last one, which a fresh buffer has not
-      const bool fresh = row && !(ctx->dim_lpt.key == states && ctx->dim_lpt.B == B && ctx->dim_lpt.buf.p);
+      const bool fresh = follows && !(ctx->dim_lpt.key == states && ctx->dim_lpt.B == B && ctx->dim_lpt.buf.p);
       if (int rc = lpt_prepare(ctx->dim_lpt, states, B, stq, &order, &iters_out)) return rc;
       if (fresh) HIP_TRY(hipMemsetAsync(iters_out, 0, (size_t)B * sizeof(int), stq));
     }
-    if (fl && row) {
-      const auto kern = solver == WG_DIMITROV_QLDANDLQ ? wg_dimitrov_qld_fleet_follow_tick_kernel<true> : wg_dimitrov_qld_fleet_follow_tick_kernel<false>;
-      hipLaunchKernelGGL(kern, dim3(B), dim3(64), ldsq, stq, B, fl->N, fl->M, blocks, fl->model_of, polys, states, outs, row, order, iters_out);
-    } else if (fl) {
-      const auto kern = solver == WG_DIMITROV_QLDANDLQ ? wg_dimitrov_qld_fleet_tick_kernel<true> : wg_dimitrov_qld_fleet_tick_kernel<false>;
-      hipLaunchKernelGGL(kern, dim3(B), dim3(64), ldsq, stq, B, fl->N, fl->M, blocks, fl->model_of, polys, states, outs, order, iters_out);
-    } else if (row) {
-      const auto kern = solver == WG_DIMITROV_QLDANDLQ ? wg_dimitrov_qld_follow_tick_kernel<true> : wg_dimitrov_qld_follow_tick_kernel<false>;
-      hipLaunchKernelGGL(kern, dim3(B), dim3(64), ldsq, stq, B, ctx->dim_dev, polys, states, outs, row, order, iters_out);
+    if constexpr (plain) {
+      if (int rc = launch_lds(lq ? wg_dimitrov_qld_tick_kernel<true> : wg_dimitrov_qld_tick_kernel<false>, dim3(B), dim3(64), ldsq, stq, B, Mo.K, polys, states, outs, order, iters_out)) return rc;
     } else {
-      const auto kern = solver == WG_DIMITROV_QLDANDLQ ? wg_dimitrov_qld_tick_kernel<true> : wg_dimitrov_qld_tick_kernel<false>;
-      hipLaunchKernelGGL(kern, dim3(B), dim3(64), ldsq, stq, B, ctx->dim_dev, polys, states, outs, order, iters_out);
+      if (int rc = launch_lds(lq ? wg_dimitrov_qld_tick_form_kernel<true, Model, Row> : wg_dimitrov_qld_tick_form_kernel<false, Model, Row>, dim3(B), dim3(64), ldsq, stq, B, Mo, polys, states, outs, Ro, order, iters_out)) return rc;
     }
-    HIP_TRY(hipGetLastError());
-    return slot_mark(ctx->aux_order, stq);
+  } else if constexpr (plain) {
+    if (int rc = launch_lds(wg_dimitrov_tick_kernel, dim3(B), dim3(64), dimitrov_lds_bytes(), stq, B, Mo.K, polys, states, outs, max_iter)) return rc;
+  } else {
+    if (int rc = launch_lds(wg_dimitrov_tick_form_kernel<Model, Row>, dim3(B), dim3(64), dimitrov_lds_bytes(), stq, B, Mo, polys, states, outs, Ro, max_iter)) return rc;
   }
-  const size_t lds = dimitrov_lds_bytes();
-  if (lds > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute(fl ? (row ? reinterpret_cast<const void *>(wg_dimitrov_fleet_follow_tick_kernel) : reinterpret_cast<const void *>(wg_dimitrov_fleet_tick_kernel))
-                                   : (row ? reinterpret_cast<const void *>(wg_dimitrov_follow_tick_kernel) : reinterpret_cast<const void *>(wg_dimitrov_tick_kernel)),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int grid = B;
-  if (fl && row) hipLaunchKernelGGL(wg_dimitrov_fleet_follow_tick_kernel, dim3(grid), dim3(64), lds, stq, B, fl->N, fl->M, blocks, fl->model_of, polys, states, outs, row, max_iter);
-  else if (fl) hipLaunchKernelGGL(wg_dimitrov_fleet_tick_kernel, dim3(grid), dim3(64), lds, stq, B, fl->N, fl->M, blocks, fl->model_of, polys, states, outs, max_iter);
-  else if (row) hipLaunchKernelGGL(wg_dimitrov_follow_tick_kernel, dim3(grid), dim3(64), lds, stq, B, ctx->dim_dev, polys, states, outs, row, max_iter);
-  else hipLaunchKernelGGL(wg_dimitrov_tick_kernel, dim3(grid), dim3(64), lds, stq, B, ctx->dim_dev, polys, states, outs, max_iter);
-  HIP_TRY(hipGetLastError());
   return slot_mark(ctx->aux_order, stq);
+}
+
+// the tick launch of wg_dimitrov_tick_batch_dev and of every tick of wg_dimitrov_walk_dev.  With `row` (wg_dimitrov_follow_dev): gait g
+// writes row row[g] of outs, or sits the launch out.  With `fl` (the wg_dimitrov_*_fleet_dev calls): gait g binds
+// blocks[model_of[g]] where the others bind the context's one model, of which nothing is read.
+int dimitrov_tick_launch(wg_ctx *ctx, int B, const wg_zmp_polytope_t *polys, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int max_iter, hipStream_t stq, const int *row = nullptr, const wg_dimitrov_fleet_t *fl = nullptr) {
+  auto go = [&](int solver, auto Mo) {
+    return row ? dimitrov_launch_form(ctx, solver, B, Mo, DimFollowRow{row}, polys, states, outs, max_iter, stq)
+               : dimitrov_launch_form(ctx, solver, B, Mo, DimOwnRow{}, polys, states, outs, max_iter, stq);
+  };
+  if (fl) return go(fl->solver, DimFleetModels{fl->N, fl->M, static_cast<const unsigned char *>(fl->blocks), fl->model_of});
+  return go(ctx->dim_host->solver, DimOneModel{ctx->dim_dev});
 }
 }  // namespace
 
@@ -1777,18 +1782,58 @@ int preview_check(wg_ctx *ctx, int B, int L, const double *zmp_x, const double *
   if (B < 0 || L < 0 || !zmp_x || !zmp_y || !state) return fail(WG_ERR_BAD_ARG, "bad arguments");
   return WG_OK;
 }
-// the split-chain kernel's instantiations: T steps of the window per lane, eight lanes per gait-axis; [1]: the window is a whole
-// number of T (no tail test)
+// the split-chain kernel's instantiations, a table per form: T steps of the window per lane, eight lanes per gait-axis; full: the
+// window is a whole number of T (no tail test).  The batch form of one model goes by the name and the arguments it is timed by.
 constexpr int kSplitK = 8;
-typedef void (*SplitKernel)(int, int, wg::PreviewConst, const double *, const double *, const double *, double *, double *, double *, int);
-#define WG_SPLIT(T) {T, wg::wg_preview_split_kernel<T, kSplitK, true>, wg::wg_preview_split_kernel<T, kSplitK, false>}
-const struct { int T; SplitKernel full, part; } kSplitKernels[] = {WG_SPLIT(16), WG_SPLIT(24), WG_SPLIT(32), WG_SPLIT(40), WG_SPLIT(48)};
+template <int T, bool FULL, bool RAGGED, bool FLEET>
+constexpr auto split_kernel() {
+  if constexpr (!RAGGED && !FLEET) return &wg::wg_preview_split_kernel<T, kSplitK, FULL>;
+  else return &wg::wg_preview_split_form_kernel<T, kSplitK, FULL, RAGGED, FLEET>;
+}
+template <bool RAGGED, bool FLEET>
+constexpr auto l2_kernel() {
+  if constexpr (!RAGGED && !FLEET) return &wg::wg_preview_kernel;
+  else return &wg::wg_preview_form_kernel<RAGGED, FLEET>;
+}
+template <bool RAGGED, bool FLEET>
+struct SplitRow {
+  int T;
+  decltype(split_kernel<16, true, RAGGED, FLEET>()) full, part;
+};
+#define WG_SPLIT(T) {T, split_kernel<T, true, RAGGED, FLEET>(), split_kernel<T, false, RAGGED, FLEET>()}
+template <bool RAGGED, bool FLEET>
+constexpr SplitRow<RAGGED, FLEET> kSplitKernels[] = {WG_SPLIT(16), WG_SPLIT(24), WG_SPLIT(32), WG_SPLIT(40), WG_SPLIT(48)};
 #undef WG_SPLIT
-// ... and their follow forms (wg_preview_follow_dev): four gaits x two axes per wave
-typedef void (*FollowSplitKernel)(int, int, const int *, int *, wg::PreviewConst, const double *, const double *, const double *, double *, double *, double *, int);
-#define WG_SPLIT(T) {T, wg::wg_preview_follow_split_kernel<T, kSplitK, true>, wg::wg_preview_follow_split_kernel<T, kSplitK, false>}
-const struct { int T; FollowSplitKernel full, part; } kFollowSplitKernels[] = {WG_SPLIT(16), WG_SPLIT(24), WG_SPLIT(32), WG_SPLIT(40), WG_SPLIT(48)};
-#undef WG_SPLIT
+
+// The launch of the four preview entry points, behind their checks.  `may_split`: the split-chain kernel (eight lanes per
+// gait-axis, nothing re-read) where it covers the window, 64 .. 384 samples; else the ring kernel where the caller asks for it
+// (`ring`: the batch form of one model has one), else the L2 kernel.  The follow forms (RAGGED) put both axes of a gait in one wave,
+// the batch forms use blockIdx.y.
+template <bool RAGGED, bool FLEET>
+int preview_launch(int B, int L, const wg::PreviewRows<RAGGED> &R, const wg::PreviewConst &K, const wg::PreviewFleet<FLEET> &fl, const double *F, const double *zx, const double *zy, double *state, double *com, double *zmp2, int simulation, bool may_split, bool ring, hipStream_t st) {
+  constexpr int axes = RAGGED ? 1 : 2;                         // as grid rows; RAGGED: as halves of a wave
+  auto launch = [&](auto kern, int blocks, int threads, size_t lds) {
+    if constexpr (!RAGGED && !FLEET) hipLaunchKernelGGL(kern, dim3(blocks, axes), dim3(threads), lds, st, B, L, K, F, zx, zy, state, com, zmp2, simulation);
+    else hipLaunchKernelGGL(kern, dim3(blocks, axes), dim3(threads), lds, st, B, L, R, K, fl, F, zx, zy, state, com, zmp2, simulation);
+  };
+  const SplitRow<RAGGED, FLEET> *split = nullptr;              // smallest instantiated T with K T >= nl
+  for (const auto &s : kSplitKernels<RAGGED, FLEET>)
+    if (!split && kSplitK * s.T >= K.nl) split = &s;
+  if (may_split && split && K.nl >= 64) {
+    const int per_wave = 64 / kSplitK * axes / 2;
+    launch(K.nl % split->T == 0 ? split->full : split->part, (B + per_wave - 1) / per_wave, 64, (size_t)split->T * 64 * 8);
+  } else if (ring) {
+    int Rn = K.nl < 288 ? K.nl : 288;                          // 288 x 512 B = 144 KB of the CU's 160 KB
+    if (Rn < 1) Rn = 1;
+    return launch_lds(wg::wg_preview_ring_kernel, dim3((B + 63) / 64, 2), dim3(64), (size_t)Rn * 64 * 8, st, B, L, K, Rn, F, zx, zy, state, com, zmp2, simulation);
+  } else {
+    const int threads = !RAGGED && B >= 4096 ? 256 : 64;       // small batches: more blocks, one wave each
+    const int per_block = threads * axes / 2;
+    launch(l2_kernel<RAGGED, FLEET>(), (B + per_block - 1) / per_block, threads, 0);
+  }
+  HIP_TRY(hipGetLastError());
+  return WG_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1825,33 +1870,10 @@ int wg_preview_run_batch_dev_ctx(wg_ctx_t *ctx, int B, int L, const double *zmp_
   // SIMD several waves of the L2 kernel (measured: B = 4096: 0.62 vs 0.43 G gait-steps/s; B = 32768: 1.18 vs 1.50), and
   // a few steps do not repay filling the ring.
   const bool ring = force ? force[0] == 'r' : (L >= 8 && (long long)B * 2 <= (long long)ctx->num_cu * 64 * 2);
-  // The split-chain kernel (eight lanes per gait-axis, nothing re-read) covers the standard window sizes and wins at every
-  // batch size measured; other windows, and runs too short to repay filling its rings, use the kernels below.
-  SplitKernel split_kern = nullptr;                            // smallest instantiated T with K T >= nl
-  int splitT = 0;
-  for (const auto &s : kSplitKernels)
-    if (!splitT && kSplitK * s.T >= ctx->prev.nl) { splitT = s.T; split_kern = ctx->prev.nl % s.T == 0 ? s.full : s.part; }
-  const bool can_split = splitT != 0 && ctx->prev.nl >= 64;
-  const bool split = force ? (force[0] == 's' && can_split) : (can_split && L >= 4);
-  if (split) {
-    const int per_wave = 64 / kSplitK;
-    hipLaunchKernelGGL(split_kern, dim3((B + per_wave - 1) / per_wave, 2), dim3(64), (size_t)splitT * 64 * 8, st, B, L, ctx->prev, ctx->prev_F,
-                       zmp_x_tm, zmp_y_tm, state, com_tm, zmp2_tm, simulation);
-  } else if (ring) {
-    int R = ctx->prev.nl < 288 ? ctx->prev.nl : 288;                 // 288 x 512 B = 144 KB of the CU's 160 KB
-    if (R < 1) R = 1;
-    const size_t lds = (size_t)R * 64 * 8;
-    if (lds > 64 * 1024)
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(wg::wg_preview_ring_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(wg::wg_preview_ring_kernel, dim3((B + 63) / 64, 2), dim3(64), lds, st, B, L, ctx->prev, R, ctx->prev_F,
-                       zmp_x_tm, zmp_y_tm, state, com_tm, zmp2_tm, simulation);
-  } else {
-    const int threads = B >= 4096 ? 256 : 64;                  // small batches: more blocks, one wave each
-    hipLaunchKernelGGL(wg::wg_preview_kernel, dim3((B + threads - 1) / threads, 2), dim3(threads), 0, st, B, L, ctx->prev,
-                       ctx->prev_F, zmp_x_tm, zmp_y_tm, state, com_tm, zmp2_tm, simulation);
-  }
-  HIP_TRY(hipGetLastError());
+  // The split-chain kernel covers the standard window sizes and wins at every batch size measured; other windows, and runs too
+  // short to repay filling its rings, use the other two.
+  const bool may_split = force ? force[0] == 's' : L >= 4;
+  if (int rc = preview_launch<false, false>(B, L, {}, ctx->prev, {}, ctx->prev_F, zmp_x_tm, zmp_y_tm, state, com_tm, zmp2_tm, simulation, may_split, ring, st)) return rc;
   std::lock_guard<std::mutex> launch_lk(ctx->launch_mu);
   return slot_mark(ctx->aux_order, st);
 }
@@ -1863,20 +1885,7 @@ int wg_preview_follow_dev_ctx(wg_ctx_t *ctx, int B, int lcap, const int *length,
   if (B == 0) return WG_OK;
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
   const char *force = getenv("WG_PREVIEW_KERNEL");            // "l2" / "split" as in the batch call; "ring" has no follow form: l2
-  FollowSplitKernel split_kern = nullptr;                      // the batch call's T / FULL selection
-  int splitT = 0;
-  for (const auto &s : kFollowSplitKernels)
-    if (!splitT && kSplitK * s.T >= ctx->prev.nl) { splitT = s.T; split_kern = ctx->prev.nl % s.T == 0 ? s.full : s.part; }
-  const bool can_split = splitT != 0 && ctx->prev.nl >= 64;
-  if (force ? (force[0] == 's' && can_split) : can_split) {
-    const int per_wave = 64 / kSplitK / 2;                     // both axes of a gait in one wave
-    hipLaunchKernelGGL(split_kern, dim3((B + per_wave - 1) / per_wave), dim3(64), (size_t)splitT * 64 * 8, st, B, lcap, length, done, ctx->prev,
-                       ctx->prev_F, zmp_x_tm, zmp_y_tm, state, com_tm, zmp2_tm, simulation);
-  } else {
-    hipLaunchKernelGGL(wg::wg_preview_follow_kernel, dim3((B + 31) / 32), dim3(64), 0, st, B, lcap, length, done, ctx->prev, ctx->prev_F,
-                       zmp_x_tm, zmp_y_tm, state, com_tm, zmp2_tm, simulation);
-  }
-  HIP_TRY(hipGetLastError());
+  if (int rc = preview_launch<true, false>(B, 0, {lcap, length, done}, ctx->prev, {}, ctx->prev_F, zmp_x_tm, zmp_y_tm, state, com_tm, zmp2_tm, simulation, force ? force[0] == 's' : true, false, st)) return rc;
   std::lock_guard<std::mutex> launch_lk(ctx->launch_mu);
   return slot_mark(ctx->aux_order, st);
 }
@@ -1955,14 +1964,6 @@ wg::PreviewConst preview_fleet_const(const wg_preview_fleet_t *fleet) {
   k.nl = fleet->nl;
   return k;
 }
-typedef void (*FleetSplitKernel)(int, int, wg::PreviewConst, wg::PreviewFleetDev, const double *, const double *, const double *, double *, double *, double *, int);
-#define WG_SPLIT(T) {T, wg::wg_preview_fleet_split_kernel<T, kSplitK, true>, wg::wg_preview_fleet_split_kernel<T, kSplitK, false>}
-const struct { int T; FleetSplitKernel full, part; } kFleetSplitKernels[] = {WG_SPLIT(16), WG_SPLIT(24), WG_SPLIT(32), WG_SPLIT(40), WG_SPLIT(48)};
-#undef WG_SPLIT
-typedef void (*FollowFleetSplitKernel)(int, int, const int *, int *, wg::PreviewConst, wg::PreviewFleetDev, const double *, const double *, const double *, double *, double *, double *, int);
-#define WG_SPLIT(T) {T, wg::wg_preview_follow_fleet_split_kernel<T, kSplitK, true>, wg::wg_preview_follow_fleet_split_kernel<T, kSplitK, false>}
-const struct { int T; FollowFleetSplitKernel full, part; } kFollowFleetSplitKernels[] = {WG_SPLIT(16), WG_SPLIT(24), WG_SPLIT(32), WG_SPLIT(40), WG_SPLIT(48)};
-#undef WG_SPLIT
 }  // namespace
 
 extern "C" {
@@ -2007,53 +2008,22 @@ int wg_riccati_gains_batch_ctx(wg_ctx_t *ctx, int B, double T, const double *zc,
   return WG_OK;
 }
 
-// wg_preview_run_batch_dev with the gains of `fleet` per gait: reads nothing of the context's configured gains
+// wg_preview_run_batch_dev with the gains of `fleet` per gait: reads nothing of the context's configured gains; the split-chain
+// kernel for windows of 64 .. 384 samples, whatever L
 int wg_preview_run_fleet_dev_ctx(wg_ctx_t *ctx, int B, int L, const wg_preview_fleet_t *fleet, const double *zmp_x_tm, const double *zmp_y_tm, double *state, double *com_tm, double *zmp2_tm, int simulation, void *hip_stream) {
   if (int rc = preview_fleet_check(B, L, fleet, zmp_x_tm, zmp_y_tm, state)) return rc;
   if (int rc = use_ctx(ctx)) return rc;
   if (B == 0 || L == 0) return WG_OK;
-  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  const wg::PreviewConst K = preview_fleet_const(fleet);
-  const wg::PreviewFleetDev fl = {fleet->zc, fleet->K_tm};
-  FleetSplitKernel split_kern = nullptr;                       // the batch call's T / FULL selection
-  int splitT = 0;
-  for (const auto &s : kFleetSplitKernels)
-    if (!splitT && kSplitK * s.T >= K.nl) { splitT = s.T; split_kern = K.nl % s.T == 0 ? s.full : s.part; }
-  if (splitT != 0 && K.nl >= 64) {                             // windows of 64 .. 384 samples, whatever L
-    const int per_wave = 64 / kSplitK;
-    hipLaunchKernelGGL(split_kern, dim3((B + per_wave - 1) / per_wave, 2), dim3(64), (size_t)splitT * 64 * 8, st, B, L, K, fl, fleet->F_tm,
-                       zmp_x_tm, zmp_y_tm, state, com_tm, zmp2_tm, simulation);
-  } else {
-    const int threads = B >= 4096 ? 256 : 64;
-    hipLaunchKernelGGL(wg::wg_preview_fleet_kernel, dim3((B + threads - 1) / threads, 2), dim3(threads), 0, st, B, L, K, fl, fleet->F_tm,
-                       zmp_x_tm, zmp_y_tm, state, com_tm, zmp2_tm, simulation);
-  }
-  HIP_TRY(hipGetLastError());
-  return WG_OK;
+  return preview_launch<false, true>(B, L, {}, preview_fleet_const(fleet), {fleet->zc, fleet->K_tm}, fleet->F_tm, zmp_x_tm, zmp_y_tm, state, com_tm, zmp2_tm, simulation, true, false, reinterpret_cast<hipStream_t>(hip_stream));
 }
 
 int wg_preview_follow_fleet_dev_ctx(wg_ctx_t *ctx, int B, int lcap, const int *length, int *done, const wg_preview_fleet_t *fleet, const double *zmp_x_tm, const double *zmp_y_tm, double *state, double *com_tm, double *zmp2_tm, int simulation, void *hip_stream) {
   if (int rc = preview_follow_fleet_check(B, lcap, length, done, fleet, zmp_x_tm, zmp_y_tm, state)) return rc;
   if (int rc = use_ctx(ctx)) return rc;
   if (B == 0) return WG_OK;
-  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  const wg::PreviewConst K = preview_fleet_const(fleet);
-  const wg::PreviewFleetDev fl = {fleet->zc, fleet->K_tm};
-  FollowFleetSplitKernel split_kern = nullptr;
-  int splitT = 0;
-  for (const auto &s : kFollowFleetSplitKernels)
-    if (!splitT && kSplitK * s.T >= K.nl) { splitT = s.T; split_kern = K.nl % s.T == 0 ? s.full : s.part; }
-  if (splitT != 0 && K.nl >= 64) {
-    const int per_wave = 64 / kSplitK / 2;                     // both axes of a gait in one wave
-    hipLaunchKernelGGL(split_kern, dim3((B + per_wave - 1) / per_wave), dim3(64), (size_t)splitT * 64 * 8, st, B, lcap, length, done, K, fl,
-                       fleet->F_tm, zmp_x_tm, zmp_y_tm, state, com_tm, zmp2_tm, simulation);
-  } else {
-    hipLaunchKernelGGL(wg::wg_preview_follow_fleet_kernel, dim3((B + 31) / 32), dim3(64), 0, st, B, lcap, length, done, K, fl, fleet->F_tm,
-                       zmp_x_tm, zmp_y_tm, state, com_tm, zmp2_tm, simulation);
-  }
-  HIP_TRY(hipGetLastError());
-  return WG_OK;
+  return preview_launch<true, true>(B, 0, {lcap, length, done}, preview_fleet_const(fleet), {fleet->zc, fleet->K_tm}, fleet->F_tm, zmp_x_tm, zmp_y_tm, state, com_tm, zmp2_tm, simulation, true, false, reinterpret_cast<hipStream_t>(hip_stream));
 }
+
 
 }  // extern "C"
 
@@ -2131,16 +2101,14 @@ int zd_check(wg_ctx *ctx, const wg_zmpdisc_model_t *model, wg::ZdConst *K, int B
   return WG_OK;
 }
 
+// the one launch of the walk's kernels: a lane per gait, the rings (`fleet`: and the models of the wave) in LDS; K is their first argument
+template <class Kernel, class... Args>
+int zd_launch_kernel(Kernel kernel, const wg::ZdConst &K, int B, bool fleet, hipStream_t st, Args... args) {
+  return launch_lds(kernel, dim3((B + 63) / 64), dim3(64), wg::zd_lds_bytes(K.nwin, fleet), st, K, args...);
+}
 int zd_launch(const wg::ZdConst &K, int B, int smax, const wg_rel_step_t *steps, const int *n_steps,
               const double *init_feet, int lcap, const wg::ZdOut &O, int *length, hipStream_t st) {
-  const size_t lds = (size_t)K.nwin * 3 * 2 * 64 * 8;
-  if (lds > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(wg::wg_zmpdisc_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(wg::wg_zmpdisc_kernel, dim3((B + 63) / 64), dim3(64), lds, st, K, B, smax, steps, n_steps, init_feet,
-                     lcap, O, length);
-  HIP_TRY(hipGetLastError());
-  return WG_OK;
+  return zd_launch_kernel(wg::wg_zmpdisc_kernel, K, B, false, st, B, smax, steps, n_steps, init_feet, lcap, O, length);
 }
 
 // what begin / append / end check of their arguments, the model aside
@@ -2151,25 +2119,6 @@ int zd_online_check(int op, int B, int smax, const wg_rel_step_t *steps, const i
   if (B < 0 || lcap < 1 || !state || !steps_ok || (op == wg::ZD_OP_BEGIN && !init_feet))
     return fail(WG_ERR_BAD_ARG, "need B >= 0, %d <= smax <= %d, lcap >= 1, non-null inputs and state", smin, WG_ZMPDISC_MAX_STEPS);
   if ((O.zx == nullptr) != (O.zy == nullptr)) return fail(WG_ERR_BAD_ARG, "zmp_x_tm and zmp_y_tm go together");
-  return WG_OK;
-}
-
-// begin / append / end of an on-line walk: the checks they share, then one launch of the resumable kernel
-int zd_online(wg_ctx *ctx, int op, const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps,
-              const double *init_feet, const int *select, int lcap, const wg::ZdOut &O, wg_zmpdisc_state_t *state, int *length,
-              void *hip_stream) {
-  wg::ZdConst K;
-  if (int rc = use_ctx(ctx)) return rc;
-  if (int rc = zd_make_const(model, &K)) return rc;
-  if (int rc = zd_online_check(op, B, smax, steps, n_steps, init_feet, lcap, O, state)) return rc;
-  if (B == 0) return WG_OK;
-  const size_t lds = (size_t)K.nwin * 3 * 2 * 64 * 8;
-  if (lds > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(wg::wg_zmpdisc_online_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(wg::wg_zmpdisc_online_kernel, dim3((B + 63) / 64), dim3(64), lds, reinterpret_cast<hipStream_t>(hip_stream),
-                     K, op, B, smax, steps, n_steps, init_feet, select, lcap, O, state, length);
-  HIP_TRY(hipGetLastError());
   return WG_OK;
 }
 
@@ -2188,27 +2137,26 @@ int zd_fleet_check(wg_ctx *ctx, const wg_zmpdisc_fleet_t *fleet, int B, wg::ZdCo
   return WG_OK;
 }
 
-template <class Kernel, class... Args>
-int zd_fleet_launch(Kernel kernel, const wg::ZdConst &K, int B, void *hip_stream, Args... args) {
-  const size_t lds = wg::zd_lds_bytes(K.nwin, true);
-  if (lds > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kernel, dim3((B + 63) / 64), dim3(64), lds, reinterpret_cast<hipStream_t>(hip_stream), K, args...);
-  HIP_TRY(hipGetLastError());
-  return WG_OK;
-}
-
-// begin / append / end with a model per gait: zd_online's checks, the fleet twin of its kernel
-int zd_online_fleet(wg_ctx *ctx, int op, const wg_zmpdisc_fleet_t *fleet, int B, int smax, const wg_rel_step_t *steps, const int *n_steps,
-                    const double *init_feet, const int *select, int lcap, const wg::ZdOut &O, wg_zmpdisc_state_t *state, int *length,
-                    void *hip_stream) {
+// begin / append / end of an on-line walk, with one model or a model per gait (`mf`): the model checks of either, the checks
+// they share, then one launch of the resumable kernel
+template <class ModelOrFleet>
+int zd_online(wg_ctx *ctx, int op, const ModelOrFleet *mf, int B, int smax, const wg_rel_step_t *steps, const int *n_steps,
+              const double *init_feet, const int *select, int lcap, const wg::ZdOut &O, wg_zmpdisc_state_t *state, int *length,
+              void *hip_stream) {
+  constexpr bool fleet = std::is_same<ModelOrFleet, wg_zmpdisc_fleet_t>::value;
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
   wg::ZdConst K;
-  wg::ZdFleet FL;
-  if (int rc = zd_fleet_check(ctx, fleet, B, &K, &FL)) return rc;
+  [[maybe_unused]] wg::ZdFleet FL;
+  if constexpr (fleet) {
+    if (int rc = zd_fleet_check(ctx, mf, B, &K, &FL)) return rc;
+  } else {
+    if (int rc = use_ctx(ctx)) return rc;
+    if (int rc = zd_make_const(mf, &K)) return rc;
+  }
   if (int rc = zd_online_check(op, B, smax, steps, n_steps, init_feet, lcap, O, state)) return rc;
   if (B == 0) return WG_OK;
-  return zd_fleet_launch(wg::wg_zmpdisc_online_fleet_kernel, K, B, hip_stream, FL, op, B, smax, steps, n_steps, init_feet, select, lcap, O,
-                         state, length);
+  if constexpr (fleet) return zd_launch_kernel(wg::wg_zmpdisc_form_kernel<true, true>, K, B, true, st, FL, op, B, smax, steps, n_steps, init_feet, select, lcap, O, state, length);
+  else return zd_launch_kernel(wg::wg_zmpdisc_online_kernel, K, B, false, st, op, B, smax, steps, n_steps, init_feet, select, lcap, O, state, length);
 }
 }  // namespace
 
@@ -2282,47 +2230,57 @@ int wg_zmpdisc_full_fleet_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_fleet_t *fleet
   if ((zmp_x_tm == nullptr) != (zmp_y_tm == nullptr)) return fail(WG_ERR_BAD_ARG, "zmp_x_tm and zmp_y_tm go together");
   if (B == 0) return WG_OK;
   const wg::ZdOut O{zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, right_tm, left_type_tm, right_type_tm};
-  return zd_fleet_launch(wg::wg_zmpdisc_fleet_kernel, K, B, hip_stream, FL, B, smax, steps, n_steps, init_feet, lcap, O, length);
+  return zd_launch_kernel(wg::wg_zmpdisc_form_kernel<false, true>, K, B, true, reinterpret_cast<hipStream_t>(hip_stream), FL, 0, B, smax, steps,
+                          n_steps, init_feet, nullptr, lcap, O, nullptr, length);
 }
 
 int wg_zmpdisc_begin_fleet_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_fleet_t *fleet, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream) {
   const wg::ZdOut O{zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, right_tm, left_type_tm, right_type_tm};
-  return zd_online_fleet(ctx, wg::ZD_OP_BEGIN, fleet, B, smax, steps, n_steps, init_feet, nullptr, lcap, O, state, length, hip_stream);
+  return zd_online(ctx, wg::ZD_OP_BEGIN, fleet, B, smax, steps, n_steps, init_feet, nullptr, lcap, O, state, length, hip_stream);
 }
 
 int wg_zmpdisc_append_fleet_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_fleet_t *fleet, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream) {
   const wg::ZdOut O{zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, right_tm, left_type_tm, right_type_tm};
-  return zd_online_fleet(ctx, wg::ZD_OP_APPEND, fleet, B, smax, steps, n_steps, nullptr, nullptr, lcap, O, state, length, hip_stream);
+  return zd_online(ctx, wg::ZD_OP_APPEND, fleet, B, smax, steps, n_steps, nullptr, nullptr, lcap, O, state, length, hip_stream);
 }
 
 int wg_zmpdisc_end_fleet_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_fleet_t *fleet, int B, const int *select, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream) {
   const wg::ZdOut O{zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, right_tm, left_type_tm, right_type_tm};
-  return zd_online_fleet(ctx, wg::ZD_OP_END, fleet, B, 0, nullptr, nullptr, nullptr, select, lcap, O, state, length, hip_stream);
+  return zd_online(ctx, wg::ZD_OP_END, fleet, B, 0, nullptr, nullptr, nullptr, select, lcap, O, state, length, hip_stream);
 }
 
-// the same with the support times of each gait (wg_steps_plan_fleet_kernel: a non-finite time is the gait's own refusal)
+}  // extern "C"
+
+namespace {
+// the step stack on the device, one wave per gait (wg_steps_kernels.hpp): what the two entry points below check and launch alike.
+// `times_ok` and `refusal` (a format that takes WG_ZMPDISC_MAX_STEPS) are each one's own.
+template <class Kernel, class... Times>
+int steps_plan_launch(Kernel kernel, wg_ctx *ctx, int B, int ccap, const wg_step_cmd_t *cmds, const int *n_cmds, bool times_ok, const char *refusal, wg_step_stack_t *stack, int smax, wg_rel_step_t *steps, int *n_steps, void *hip_stream, Times... times) {
+  if (int rc = use_ctx(ctx)) return rc;
+  if (B < 0 || ccap < 1 || smax < 1 || smax > WG_ZMPDISC_MAX_STEPS || !cmds || !n_cmds || !stack || !steps || !n_steps || !times_ok)
+    return fail(WG_ERR_BAD_ARG, refusal, WG_ZMPDISC_MAX_STEPS);
+  if (B == 0) return WG_OK;
+  hipLaunchKernelGGL(kernel, dim3((B + wg::kSpWaves - 1) / wg::kSpWaves), dim3(64 * wg::kSpWaves), 0, reinterpret_cast<hipStream_t>(hip_stream), B, ccap, cmds,
+                     n_cmds, times..., stack, smax, steps, n_steps);
+  HIP_TRY(hipGetLastError());
+  return WG_OK;
+}
+}  // namespace
+
+extern "C" {
+
+// with the support times of each gait (a non-finite time is the gait's own refusal, on the device)
 int wg_steps_plan_fleet_dev_ctx(wg_ctx_t *ctx, int B, int ccap, const wg_step_cmd_t *cmds, const int *n_cmds, const double *ss, const double *ds, wg_step_stack_t *stack, int smax, wg_rel_step_t *steps, int *n_steps, void *hip_stream) {
-  if (int rc = use_ctx(ctx)) return rc;
-  if (B < 0 || ccap < 1 || smax < 1 || smax > WG_ZMPDISC_MAX_STEPS || !cmds || !n_cmds || !ss || !ds || !stack || !steps || !n_steps)
-    return fail(WG_ERR_BAD_ARG, "need B >= 0, ccap >= 1, 1 <= smax <= %d, non-null arrays", WG_ZMPDISC_MAX_STEPS);
-  if (B == 0) return WG_OK;
-  hipLaunchKernelGGL(wg::wg_steps_plan_fleet_kernel, dim3((B + wg::kSpWaves - 1) / wg::kSpWaves), dim3(64 * wg::kSpWaves), 0,
-                     reinterpret_cast<hipStream_t>(hip_stream), B, ccap, cmds, n_cmds, ss, ds, stack, smax, steps, n_steps);
-  HIP_TRY(hipGetLastError());
-  return WG_OK;
+  return steps_plan_launch(wg::wg_steps_plan_form_kernel<true>, ctx, B, ccap, cmds, n_cmds, ss && ds, "need B >= 0, ccap >= 1, 1 <= smax <= %d, non-null arrays",
+                           stack, smax, steps, n_steps, hip_stream, wg::SpTimes<true>{ss, ds});
 }
 
-// the step stack on the device: one wave per gait (wg_steps_kernels.hpp); the host twins are wg_steps.cpp
+// with the call's times; the host twins are wg_steps.cpp
 int wg_steps_plan_dev_ctx(wg_ctx_t *ctx, int B, int ccap, const wg_step_cmd_t *cmds, const int *n_cmds, double ss, double ds, wg_step_stack_t *stack, int smax, wg_rel_step_t *steps, int *n_steps, void *hip_stream) {
-  if (int rc = use_ctx(ctx)) return rc;
-  if (B < 0 || ccap < 1 || smax < 1 || smax > WG_ZMPDISC_MAX_STEPS || !cmds || !n_cmds || !stack || !steps || !n_steps || !wg::sp_finite(ss) || !wg::sp_finite(ds))
-    return fail(WG_ERR_BAD_ARG, "need B >= 0, ccap >= 1, 1 <= smax <= %d, finite times, non-null arrays", WG_ZMPDISC_MAX_STEPS);
-  if (B == 0) return WG_OK;
-  hipLaunchKernelGGL(wg::wg_steps_plan_kernel, dim3((B + wg::kSpWaves - 1) / wg::kSpWaves), dim3(64 * wg::kSpWaves), 0,
-                     reinterpret_cast<hipStream_t>(hip_stream), B, ccap, cmds, n_cmds, ss, ds, stack, smax, steps, n_steps);
-  HIP_TRY(hipGetLastError());
-  return WG_OK;
+  return steps_plan_launch(wg::wg_steps_plan_kernel, ctx, B, ccap, cmds, n_cmds, wg::sp_finite(ss) && wg::sp_finite(ds),
+                           "need B >= 0, ccap >= 1, 1 <= smax <= %d, finite times, non-null arrays", stack, smax, steps, n_steps, hip_stream, ss, ds);
 }
+
 
 int wg_zmpdisc_batch_ctx(wg_ctx_t *ctx, const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap, double *zmp, double *zmp_theta, int *zmp_type, double *left, int *left_type, double *right, int *right_type, int *length) {
   wg::ZdConst K;

@@ -1,73 +1,15 @@
 // wg_dimitrov_kernels.hpp -- the __global__ kernels of the Dimitrov-2008 tick (wg_dimitrov_tick_batch*): around PLDP, and around
 // the in-wave ql0002.  Included by wg_capi.hip, which launches them; the ticks themselves are wg_dimitrov_device.hpp.
-// Behind them the kernels of fleets with a model per gait: wg_dimitrov_constants_kernel (the constants of M models, the text of
-// wg_dimitrov_math.hpp run by a wavefront per model) and the fleet twins of the four ticks.
+// Each tick is one kernel template over two bindings -- which model a gait runs with, which row of outs it writes -- whose
+// instantiations are the follow, fleet and fleet-follow forms; the plain form, the one that is timed, stands beside it.  Ahead of them wg_dimitrov_constants_kernel: the constants of the M models
+// of a fleet (the text of wg_dimitrov_math.hpp run by a wavefront per model), the blocks the fleet binding reads.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "../../include/wg_mpc.h"
 #include "wg_dimitrov_device.hpp"
 
-// ---- Dimitrov-2008 tick around PLDP ------------------------------------------------------------------------------------
-
-__global__ void __launch_bounds__(64)
-wg_dimitrov_tick_kernel(int B, const wg::DimitrovConst *__restrict__ K, const wg_zmp_polytope_t *__restrict__ polys,
-                        wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int max_iter) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char dim_lds[];
-  const int N = K->N;
-  const int g = blockIdx.x;                       // one gait per block (grid == B), like the Herdt tick
-  // (a longest-solve-first start order as in the QL back-ends below was measured here and gave nothing: 5.19 against 5.20 M
-  // ticks/s -- PLDP's four iterations per tick leave nothing to order)
-  if (g < B) (void)wg::dimitrov_tick(*K, dim_lds, polys + (size_t)g * N, states + g, outs ? outs + g : nullptr, max_iter);
-}
-
-// modes QLD / QLDANDLQ: the same tick with the in-wave ql0002 as its back-end (wg_dimitrov_device.hpp, dimitrov_qld_tick)
-template <bool kLQ>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
-wg_dimitrov_qld_tick_kernel(int B, const wg::DimitrovConst *__restrict__ K, const wg_zmp_polytope_t *__restrict__ polys,
-                            wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, const int *__restrict__ order,
-                            int *__restrict__ iters_out) {
-  extern __shared__ __attribute__((aligned(16))) double dimq_lds[];
-  const int N = K->N;
-  const int g = order ? wg::uni(order[blockIdx.x]) : (int)blockIdx.x;     // longest-solve-first by the previous tick (scheduling only)
-  if (g < B) {
-    const int it = wg::dimitrov_qld_tick<kLQ>(*K, dimq_lds, polys + (size_t)g * N, states + g, outs ? outs + g : nullptr);
-    if (iters_out && (threadIdx.x & 63) == 0) iters_out[g] = it;
-  }
-}
-
-// ---- the ticks of wg_dimitrov_follow_dev: the same ticks, for the gaits wg_dimitrov_follow_select_kernel let go ---------------
-// row[g] is the row of outs ([tick_cap][B], absolute) gait g's tick writes, or -1: the gait sits this round out and its block
-// returns at once -- its state, its outs and, in the QL modes, its iteration count of the previous tick stay as they are.
-
-__global__ void __launch_bounds__(64)
-wg_dimitrov_follow_tick_kernel(int B, const wg::DimitrovConst *__restrict__ K, const wg_zmp_polytope_t *__restrict__ polys,
-                               wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, const int *__restrict__ row, int max_iter) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char dim_lds[];
-  const int N = K->N;
-  const int g = blockIdx.x;
-  if (g >= B) return;
-  const int r = wg::uni(row[g]);
-  if (r < 0) return;
-  (void)wg::dimitrov_tick(*K, dim_lds, polys + (size_t)g * N, states + g, outs ? outs + (size_t)r * (size_t)B + g : nullptr, max_iter);
-}
-
-template <bool kLQ>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
-wg_dimitrov_qld_follow_tick_kernel(int B, const wg::DimitrovConst *__restrict__ K, const wg_zmp_polytope_t *__restrict__ polys,
-                                   wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, const int *__restrict__ row,
-                                   const int *__restrict__ order, int *__restrict__ iters_out) {
-  extern __shared__ __attribute__((aligned(16))) double dimq_lds[];
-  const int N = K->N;
-  const int g = order ? wg::uni(order[blockIdx.x]) : (int)blockIdx.x;     // longest-solve-first by the gait's last tick (scheduling only)
-  if (g >= B) return;
-  const int r = wg::uni(row[g]);
-  if (r < 0) return;
-  const int it = wg::dimitrov_qld_tick<kLQ>(*K, dimq_lds, polys + (size_t)g * N, states + g, outs ? outs + (size_t)r * (size_t)B + g : nullptr);
-  if (iters_out && (threadIdx.x & 63) == 0) iters_out[g] = it;
-}
-
-// ---- a model per gait: the constants on the device, and the fleet twins of the four ticks ---------------------------------------
+// ---- a model per gait: the constants on the device -----------------------------------------------------------------------------
 
 // the text of wg_dimitrov_math.hpp run by the 64 lanes of one wavefront
 struct DmWaveExec {
@@ -99,79 +41,118 @@ wg_dimitrov_constants_kernel(int M, wg_dimitrov_model_t base, const double *__re
   if (lane == 0) status[m] = ok ? WG_OK : WG_ERR_BAD_ARG;
 }
 
-// Gait g of a fleet launch runs with blocks[model_of[g]].  nullptr: the gait is refused -- model_of[g] outside [0, M), or a failed
-// (all-zero) block, which a good one is told from by its N >= 1.
-__device__ __forceinline__ const wg::DimitrovConst *wg_dimitrov_fleet_block(const unsigned char *__restrict__ blocks,
-                                                                            const int *__restrict__ model_of, int M, int g) {
-  const int mi = wg::uni(model_of[g]);
-  if (mi < 0 || mi >= M) return nullptr;
-  const wg::DimitrovConst *K = reinterpret_cast<const wg::DimitrovConst *>(blocks + (size_t)mi * wg::kDimitrovBlockBytes);
-  return wg::uni(K->N) >= 1 ? K : nullptr;
-}
+// ---- the two bindings of a tick launch -----------------------------------------------------------------------------------------
+
+// Model binding, the launch's one model (wg_dimitrov_tick_batch_dev, _walk_dev, _follow_dev): every gait runs with *K, none is refused.
+struct DimOneModel {
+  const wg::DimitrovConst *K;
+  static constexpr bool kRefuses = false;
+  __device__ __forceinline__ int N() const { return K->N; }
+  __device__ __forceinline__ const wg::DimitrovConst *bind(int) const { return K; }
+};
+// Model binding, a model per gait (the wg_dimitrov_*_fleet_dev calls): gait g runs with blocks[model_of[g]].  nullptr: the gait is
+// refused -- model_of[g] outside [0, M), a failed (all-zero) block, which a good one is told from by its N >= 1, or a block of
+// another horizon than the launch's N.
+struct DimFleetModels {
+  int n, M;
+  const unsigned char *__restrict__ blocks;
+  const int *__restrict__ model_of;
+  static constexpr bool kRefuses = true;
+  __device__ __forceinline__ int N() const { return n; }
+  __device__ __forceinline__ const wg::DimitrovConst *bind(int g) const {
+    const int mi = wg::uni(model_of[g]);
+    if (mi < 0 || mi >= M) return nullptr;
+    const wg::DimitrovConst *K = reinterpret_cast<const wg::DimitrovConst *>(blocks + (size_t)mi * wg::kDimitrovBlockBytes);
+    return wg::uni(K->N) >= 1 && K->N == n ? K : nullptr;
+  }
+};
 // what a refused gait leaves: its return code and no iteration, in its out struct; of its state no byte is touched
-__device__ __forceinline__ void wg_dimitrov_fleet_refuse(wg_dimitrov_out_t *out) {
+__device__ __forceinline__ void wg_dimitrov_refuse(wg_dimitrov_out_t *out) {
   if (out && (threadIdx.x & 63) == 0) { out->ret = WG_PLDP_BAD_INPUT; out->n_iter = 0; }
 }
 
+// Row binding.  out(): false when the gait sits the launch out, else *out is the struct its tick writes (nullptr without outs).
+// Row g of outs [B]:
+struct DimOwnRow {
+  __device__ __forceinline__ bool out(wg_dimitrov_out_t *outs, int, int g, wg_dimitrov_out_t **out) const {
+    *out = outs ? outs + g : nullptr;
+    return true;
+  }
+};
+// The ticks of wg_dimitrov_follow_dev, for the gaits wg_dimitrov_follow_select_kernel let go: row[g] is the row of outs
+// ([tick_cap][B], absolute) gait g's tick writes, or -1: the gait sits this round out and its block returns at once -- its state,
+// its outs and, in the QL modes, its iteration count of the previous tick stay as they are.
+struct DimFollowRow {
+  const int *__restrict__ row;
+  __device__ __forceinline__ bool out(wg_dimitrov_out_t *outs, int B, int g, wg_dimitrov_out_t **out) const {
+    const int r = wg::uni(row[g]);
+    if (r < 0) return false;
+    *out = outs ? outs + (size_t)r * (size_t)B + g : nullptr;
+    return true;
+  }
+};
+
+// ---- Dimitrov-2008 tick around PLDP ------------------------------------------------------------------------------------
+
+// The follow, fleet and fleet-follow forms: one gait per block (grid == B), like the Herdt tick.
+// (a longest-solve-first start order as in the QL back-ends below was measured here and gave nothing: 5.19 against 5.20 M
+// ticks/s -- PLDP's four iterations per tick leave nothing to order)
+template <class Model, class Row>
 __global__ void __launch_bounds__(64)
-wg_dimitrov_fleet_tick_kernel(int B, int N, int M, const unsigned char *__restrict__ blocks, const int *__restrict__ model_of,
-                              const wg_zmp_polytope_t *__restrict__ polys, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs,
-                              int max_iter) {
+wg_dimitrov_tick_form_kernel(int B, Model Mo, const wg_zmp_polytope_t *__restrict__ polys, wg_dimitrov_state_t *states,
+                             wg_dimitrov_out_t *outs, Row Ro, int max_iter) {
   extern __shared__ __attribute__((aligned(16))) unsigned char dim_lds[];
+  const int N = Mo.N();
   const int g = blockIdx.x;
   if (g >= B) return;
-  wg_dimitrov_out_t *out = outs ? outs + g : nullptr;
-  const wg::DimitrovConst *K = wg_dimitrov_fleet_block(blocks, model_of, M, g);
-  if (!K || K->N != N) { wg_dimitrov_fleet_refuse(out); return; }
+  wg_dimitrov_out_t *out = nullptr;
+  if (!Ro.out(outs, B, g, &out)) return;
+  const wg::DimitrovConst *K = Mo.bind(g);
+  if (Model::kRefuses && !K) { wg_dimitrov_refuse(out); return; }
   (void)wg::dimitrov_tick(*K, dim_lds, polys + (size_t)g * N, states + g, out, max_iter);
 }
+// The plain form -- <DimOneModel, DimOwnRow>, which binds nothing and refuses nobody -- is timed by this name and these arguments,
+// and keeps its text: ANY function between the kernel and wg::dimitrov_tick, a shared body included, makes the compiler order its
+// first passes differently and changes a handful of the kernel's 2 541 instructions.
+__global__ void __launch_bounds__(64)
+wg_dimitrov_tick_kernel(int B, const wg::DimitrovConst *__restrict__ K, const wg_zmp_polytope_t *__restrict__ polys,
+                        wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int max_iter) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char dim_lds[];
+  const int N = K->N;
+  const int g = blockIdx.x;
+  if (g < B) (void)wg::dimitrov_tick(*K, dim_lds, polys + (size_t)g * N, states + g, outs ? outs + g : nullptr, max_iter);
+}
 
-template <bool kLQ>
+// ---- modes QLD / QLDANDLQ: the same tick with the in-wave ql0002 as its back-end (wg_dimitrov_device.hpp, dimitrov_qld_tick) --
+
+// `order`: longest-solve-first by the gait's last tick (scheduling only); iters_out[g] from lane 0, 0 for a refused gait.
+template <bool kLQ, class Model, class Row>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
-wg_dimitrov_qld_fleet_tick_kernel(int B, int N, int M, const unsigned char *__restrict__ blocks, const int *__restrict__ model_of,
-                                  const wg_zmp_polytope_t *__restrict__ polys, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs,
-                                  const int *__restrict__ order, int *__restrict__ iters_out) {
+wg_dimitrov_qld_tick_form_kernel(int B, Model Mo, const wg_zmp_polytope_t *__restrict__ polys, wg_dimitrov_state_t *states,
+                                 wg_dimitrov_out_t *outs, Row Ro, const int *__restrict__ order, int *__restrict__ iters_out) {
   extern __shared__ __attribute__((aligned(16))) double dimq_lds[];
+  const int N = Mo.N();
   const int g = order ? wg::uni(order[blockIdx.x]) : (int)blockIdx.x;
   if (g >= B) return;
-  wg_dimitrov_out_t *out = outs ? outs + g : nullptr;
-  const wg::DimitrovConst *K = wg_dimitrov_fleet_block(blocks, model_of, M, g);
+  wg_dimitrov_out_t *out = nullptr;
+  if (!Ro.out(outs, B, g, &out)) return;
+  const wg::DimitrovConst *K = Mo.bind(g);
   int it = 0;
-  if (!K || K->N != N) wg_dimitrov_fleet_refuse(out);
+  if (Model::kRefuses && !K) wg_dimitrov_refuse(out);
   else it = wg::dimitrov_qld_tick<kLQ>(*K, dimq_lds, polys + (size_t)g * N, states + g, out);
   if (iters_out && (threadIdx.x & 63) == 0) iters_out[g] = it;
 }
-
-__global__ void __launch_bounds__(64)
-wg_dimitrov_fleet_follow_tick_kernel(int B, int N, int M, const unsigned char *__restrict__ blocks, const int *__restrict__ model_of,
-                                     const wg_zmp_polytope_t *__restrict__ polys, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs,
-                                     const int *__restrict__ row, int max_iter) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char dim_lds[];
-  const int g = blockIdx.x;
-  if (g >= B) return;
-  const int r = wg::uni(row[g]);
-  if (r < 0) return;
-  wg_dimitrov_out_t *out = outs ? outs + (size_t)r * (size_t)B + g : nullptr;
-  const wg::DimitrovConst *K = wg_dimitrov_fleet_block(blocks, model_of, M, g);
-  if (!K || K->N != N) { wg_dimitrov_fleet_refuse(out); return; }
-  (void)wg::dimitrov_tick(*K, dim_lds, polys + (size_t)g * N, states + g, out, max_iter);
-}
-
+// the plain form, as above
 template <bool kLQ>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
-wg_dimitrov_qld_fleet_follow_tick_kernel(int B, int N, int M, const unsigned char *__restrict__ blocks, const int *__restrict__ model_of,
-                                         const wg_zmp_polytope_t *__restrict__ polys, wg_dimitrov_state_t *states,
-                                         wg_dimitrov_out_t *outs, const int *__restrict__ row, const int *__restrict__ order,
-                                         int *__restrict__ iters_out) {
+wg_dimitrov_qld_tick_kernel(int B, const wg::DimitrovConst *__restrict__ K, const wg_zmp_polytope_t *__restrict__ polys,
+                            wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, const int *__restrict__ order,
+                            int *__restrict__ iters_out) {
   extern __shared__ __attribute__((aligned(16))) double dimq_lds[];
-  const int g = order ? wg::uni(order[blockIdx.x]) : (int)blockIdx.x;
-  if (g >= B) return;
-  const int r = wg::uni(row[g]);
-  if (r < 0) return;
-  wg_dimitrov_out_t *out = outs ? outs + (size_t)r * (size_t)B + g : nullptr;
-  const wg::DimitrovConst *K = wg_dimitrov_fleet_block(blocks, model_of, M, g);
-  int it = 0;
-  if (!K || K->N != N) wg_dimitrov_fleet_refuse(out);
-  else it = wg::dimitrov_qld_tick<kLQ>(*K, dimq_lds, polys + (size_t)g * N, states + g, out);
-  if (iters_out && (threadIdx.x & 63) == 0) iters_out[g] = it;
+  const int N = K->N;
+  const int g = order ? wg::uni(order[blockIdx.x]) : (int)blockIdx.x;     // longest-solve-first by the previous tick (scheduling only)
+  if (g < B) {
+    const int it = wg::dimitrov_qld_tick<kLQ>(*K, dimq_lds, polys + (size_t)g * N, states + g, outs ? outs + g : nullptr);
+    if (iters_out && (threadIdx.x & 63) == 0) iters_out[g] = it;
+  }
 }

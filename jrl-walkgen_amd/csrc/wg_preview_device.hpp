@@ -34,12 +34,15 @@ struct PreviewConst {
 //   K_tm  [4][B]     Ks, Kx0, Kx1, Kx2
 //   F     [nl][B]    time-major like the ZMP references: tap i of gait g at i*B + g, a wave's loads are whole rows
 // The step arithmetic below is one text for both: FLEET changes where Kx, Ks, C2 and F[i] come from and nothing else.
-struct PreviewFleetDev {
+template <bool FLEET>
+struct PreviewFleet {};                  // the one-model forms: empty
+template <>
+struct PreviewFleet<true> {
   const double *zc, *K_tm;
 };
 // the constants of gait g: the launch's own (not FLEET: `own` is never touched), or `own` filled from them and the fleet's arrays
 template <bool FLEET>
-__device__ __forceinline__ const PreviewConst &pv_gains(const PreviewConst &K, PreviewConst &own, const PreviewFleetDev &fl, int g, int B) {
+__device__ __forceinline__ const PreviewConst &pv_gains(const PreviewConst &K, PreviewConst &own, const PreviewFleet<FLEET> &fl, int g, int B) {
   if constexpr (FLEET) {
     const size_t sB = (size_t)B;
     own = K;
@@ -65,6 +68,14 @@ __device__ __forceinline__ double pv_tap(const double *__restrict__ F, int i, in
 // rows are unwritten memory while the gait walks.
 // Both axes of a gait sit in ONE wave, which reads done[b] before its step loop and stores it behind it: were the axes
 // two blocks, as in the batch forms, one could store done[b] before the other has read it.
+template <bool RAGGED>
+struct PreviewRows {};                   // the batch forms: empty, every gait runs rows [0, L)
+template <>
+struct PreviewRows<true> {
+  int lcap;
+  const int *length;
+  int *done;
+};
 struct PreviewRange {
   const double *z;          // row done[b] of the gait's queue: the row of the call's first step
   size_t row0;              // done[b]
@@ -97,11 +108,10 @@ __device__ __forceinline__ void pv_range_store(const PreviewRange &r, int g, int
 // zmp2:    [L][2][B] or NULL   zmpx2, zmpy2 of each step
 // RAGGED: one wave per block, lanes 0..31 the x axes of 32 gaits, lanes 32..63 their y axes; L is not used.  The step loop has
 // a bound per lane here (no lane talks to another), so a lane's loads are those of its own steps and nothing else.
-template <bool RAGGED, bool FLEET = false>
-__device__ __forceinline__ void pv_l2_body(int B, int L, const PreviewConst &Kc, const double *__restrict__ F,
-                                           const double *__restrict__ zx, const double *__restrict__ zy, double *__restrict__ state,
-                                           double *__restrict__ com, double *__restrict__ zmp2, int simulation, int lcap,
-                                           const int *length, int *done, const PreviewFleetDev fl = PreviewFleetDev()) {
+template <bool RAGGED, bool FLEET>
+__device__ __forceinline__ void pv_l2_body(int B, int L, const PreviewRows<RAGGED> &R, const PreviewConst &Kc, const PreviewFleet<FLEET> &fl,
+                                           const double *__restrict__ F, const double *__restrict__ zx, const double *__restrict__ zy,
+                                           double *__restrict__ state, double *__restrict__ com, double *__restrict__ zmp2, int simulation) {
   const int g = RAGGED ? blockIdx.x * 32 + (threadIdx.x & 31) : blockIdx.x * blockDim.x + threadIdx.x;
   const int axis = RAGGED ? threadIdx.x >> 5 : blockIdx.y;
   if (g >= B) return;
@@ -112,7 +122,7 @@ __device__ __forceinline__ void pv_l2_body(int B, int L, const PreviewConst &Kc,
   const int nl = K.nl;
   PreviewRange rg;
   if constexpr (RAGGED) {
-    rg = pv_range(true, g, B, nl, lcap, z, length, done);
+    rg = pv_range(true, g, B, nl, R.lcap, z, R.length, R.done);
     z = rg.z; L = rg.n;
     if (com) com += rg.row0 * 6 * sB;
     if (zmp2) zmp2 += rg.row0 * 2 * sB;
@@ -154,39 +164,26 @@ __device__ __forceinline__ void pv_l2_body(int B, int L, const PreviewConst &Kc,
   }
   if constexpr (RAGGED) {
     if (L > 0) { st[3 * axis] = x0; st[3 * axis + 1] = x1; st[3 * axis + 2] = x2; st[6 + axis] = s; }
-    if (axis == 0) pv_range_store(rg, g, done);
+    if (axis == 0) pv_range_store(rg, g, R.done);
   } else {
     st[3 * axis] = x0; st[3 * axis + 1] = x1; st[3 * axis + 2] = x2; st[6 + axis] = s;
   }
 }
 
+// the follow, fleet and follow-fleet forms (RAGGED: L is not read)
+template <bool RAGGED, bool FLEET>
+__global__ void __launch_bounds__(RAGGED ? 64 : 256)
+wg_preview_form_kernel(int B, int L, PreviewRows<RAGGED> R, PreviewConst K, PreviewFleet<FLEET> fl, const double *__restrict__ F,
+                       const double *__restrict__ zx, const double *__restrict__ zy, double *__restrict__ state,
+                       double *__restrict__ com, double *__restrict__ zmp2, int simulation) {
+  pv_l2_body<RAGGED, FLEET>(B, L, R, K, fl, F, zx, zy, state, com, zmp2, simulation);
+}
+// the batch form of one model, under its own name and arguments
 __global__ void __launch_bounds__(256)
 wg_preview_kernel(int B, int L, PreviewConst K, const double *__restrict__ F, const double *__restrict__ zx,
                   const double *__restrict__ zy, double *__restrict__ state, double *__restrict__ com,
                   double *__restrict__ zmp2, int simulation) {
-  pv_l2_body<false>(B, L, K, F, zx, zy, state, com, zmp2, simulation, 0, nullptr, nullptr);
-}
-
-__global__ void __launch_bounds__(64)
-wg_preview_follow_kernel(int B, int lcap, const int *__restrict__ length, int *__restrict__ done, PreviewConst K,
-                         const double *__restrict__ F, const double *__restrict__ zx, const double *__restrict__ zy,
-                         double *__restrict__ state, double *__restrict__ com, double *__restrict__ zmp2, int simulation) {
-  pv_l2_body<true>(B, 0, K, F, zx, zy, state, com, zmp2, simulation, lcap, length, done);
-}
-
-__global__ void __launch_bounds__(256)
-wg_preview_fleet_kernel(int B, int L, PreviewConst K, PreviewFleetDev fl, const double *__restrict__ F, const double *__restrict__ zx,
-                        const double *__restrict__ zy, double *__restrict__ state, double *__restrict__ com,
-                        double *__restrict__ zmp2, int simulation) {
-  pv_l2_body<false, true>(B, L, K, F, zx, zy, state, com, zmp2, simulation, 0, nullptr, nullptr, fl);
-}
-
-__global__ void __launch_bounds__(64)
-wg_preview_follow_fleet_kernel(int B, int lcap, const int *__restrict__ length, int *__restrict__ done, PreviewConst K,
-                               PreviewFleetDev fl, const double *__restrict__ F, const double *__restrict__ zx,
-                               const double *__restrict__ zy, double *__restrict__ state, double *__restrict__ com,
-                               double *__restrict__ zmp2, int simulation) {
-  pv_l2_body<true, true>(B, 0, K, F, zx, zy, state, com, zmp2, simulation, lcap, length, done, fl);
+  pv_l2_body<false, false>(B, L, {}, K, {}, F, zx, zy, state, com, zmp2, simulation);
 }
 
 // The same iteration with the preview window staged in LDS.  wg_preview_kernel re-reads the whole window from L2 at every
@@ -293,12 +290,12 @@ __device__ __forceinline__ double pv_dpp(double v) {
 // as long as its longest gait: an evenly fed fleet loses nothing, a lone long gait costs its wave.
 // FLEET: the taps a lane keeps in registers are its gait's own (F [nl][B], loaded once per launch like the shared ones); a
 // surplus or sitting-out group loads gains like any other, through the gait index g that shadows B - 1 where the group has none.
-template <int T, int K, bool FULL, bool RAGGED, bool FLEET = false>     // FULL: nl is a multiple of T, the last used lane has T taps like the others
-__device__ __forceinline__ void pv_split_body(int B, int L, const PreviewConst &Kin, const double *__restrict__ F,
+template <int T, int K, bool FULL, bool RAGGED, bool FLEET>             // FULL: nl is a multiple of T, the last used lane has T taps like the others
+__device__ __forceinline__ void pv_split_body(int B, int L, const PreviewRows<RAGGED> &R, const PreviewConst &Kin,
+                                              const PreviewFleet<FLEET> &fl, const double *__restrict__ F,
                                               const double *__restrict__ zx, const double *__restrict__ zy,
                                               double *__restrict__ state, double *__restrict__ com, double *__restrict__ zmp2,
-                                              int simulation, int lcap, const int *length, int *done,
-                                              const PreviewFleetDev fl = PreviewFleetDev()) {
+                                              int simulation) {
   static_assert(K == 8, "the DPP controls below are written for groups of eight lanes");
   extern __shared__ __attribute__((aligned(16))) double pv_ring[];      // [T][64]
   constexpr int G = 64 / K;
@@ -319,7 +316,7 @@ __device__ __forceinline__ void pv_split_body(int B, int L, const PreviewConst &
   int n = L;                                                            // steps of this lane's gait
   PreviewRange rg;
   if constexpr (RAGGED) {
-    rg = pv_range(valid, g, B, nl, lcap, z, length, done);
+    rg = pv_range(valid, g, B, nl, R.lcap, z, R.length, R.done);
     z = rg.z; Lz = rg.Lz; n = rg.n;
     L = wave_max_int(n);
     if (com) com += rg.row0 * 6 * sB;
@@ -418,40 +415,23 @@ __device__ __forceinline__ void pv_split_body(int B, int L, const PreviewConst &
     so[3 * axis] = x0; so[3 * axis + 1] = x1; so[3 * axis + 2] = x2; so[6 + axis] = s;
   }
   if constexpr (RAGGED)
-    if (valid && first && axis == 0) pv_range_store(rg, g, done);
+    if (valid && first && axis == 0) pv_range_store(rg, g, R.done);
 }
 
+template <int T, int K, bool FULL, bool RAGGED, bool FLEET>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
+wg_preview_split_form_kernel(int B, int L, PreviewRows<RAGGED> R, PreviewConst Kc, PreviewFleet<FLEET> fl, const double *__restrict__ F,
+                             const double *__restrict__ zx, const double *__restrict__ zy, double *__restrict__ state,
+                             double *__restrict__ com, double *__restrict__ zmp2, int simulation) {
+  pv_split_body<T, K, FULL, RAGGED, FLEET>(B, L, R, Kc, fl, F, zx, zy, state, com, zmp2, simulation);
+}
+// the batch form of one model, under the name and with the arguments it is timed by
 template <int T, int K, bool FULL>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 wg_preview_split_kernel(int B, int L, PreviewConst Kc, const double *__restrict__ F, const double *__restrict__ zx,
                         const double *__restrict__ zy, double *__restrict__ state, double *__restrict__ com,
                         double *__restrict__ zmp2, int simulation) {
-  pv_split_body<T, K, FULL, false>(B, L, Kc, F, zx, zy, state, com, zmp2, simulation, 0, nullptr, nullptr);
-}
-
-template <int T, int K, bool FULL>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
-wg_preview_follow_split_kernel(int B, int lcap, const int *__restrict__ length, int *__restrict__ done, PreviewConst Kc,
-                               const double *__restrict__ F, const double *__restrict__ zx, const double *__restrict__ zy,
-                               double *__restrict__ state, double *__restrict__ com, double *__restrict__ zmp2, int simulation) {
-  pv_split_body<T, K, FULL, true>(B, 0, Kc, F, zx, zy, state, com, zmp2, simulation, lcap, length, done);
-}
-
-template <int T, int K, bool FULL>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
-wg_preview_fleet_split_kernel(int B, int L, PreviewConst Kc, PreviewFleetDev fl, const double *__restrict__ F,
-                              const double *__restrict__ zx, const double *__restrict__ zy, double *__restrict__ state,
-                              double *__restrict__ com, double *__restrict__ zmp2, int simulation) {
-  pv_split_body<T, K, FULL, false, true>(B, L, Kc, F, zx, zy, state, com, zmp2, simulation, 0, nullptr, nullptr, fl);
-}
-
-template <int T, int K, bool FULL>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
-wg_preview_follow_fleet_split_kernel(int B, int lcap, const int *__restrict__ length, int *__restrict__ done, PreviewConst Kc,
-                                     PreviewFleetDev fl, const double *__restrict__ F, const double *__restrict__ zx,
-                                     const double *__restrict__ zy, double *__restrict__ state, double *__restrict__ com,
-                                     double *__restrict__ zmp2, int simulation) {
-  pv_split_body<T, K, FULL, true, true>(B, 0, Kc, F, zx, zy, state, com, zmp2, simulation, lcap, length, done, fl);
+  pv_split_body<T, K, FULL, false, false>(B, L, {}, Kc, {}, F, zx, zy, state, com, zmp2, simulation);
 }
 
 // [B][cols] (gait-major) <-> [cols][B] (time-major) on the device, for the host-pointer entry point

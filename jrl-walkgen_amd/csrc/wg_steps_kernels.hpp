@@ -16,13 +16,21 @@ namespace wg {
 
 constexpr int kSpWaves = 4;              // gaits (waves) per block
 
-// FLEET = false: ss, ds are the call's (kernel arguments, checked on the host).  FLEET = true (wg_steps_plan_fleet_dev): the
-// gait's own, ss_b[b], ds_b[b]; a gait that runs with a non-finite one is refused like a gait with a bad list.
+// The support times of a launch.  FLEET = false: the call's ss, ds (checked on the host).  FLEET = true (wg_steps_plan_fleet_dev):
+// the gait's own, ss[b], ds[b]; a gait that runs with a non-finite one is refused like a gait with a bad list.
+template <bool FLEET>
+struct SpTimes {
+  double ss, ds;
+};
+template <>
+struct SpTimes<true> {
+  const double *__restrict__ ss, *__restrict__ ds;
+};
+
 template <bool FLEET>
 __device__ __forceinline__ void sp_plan_gait(int B, int ccap, const wg_step_cmd_t *__restrict__ cmds, const int *__restrict__ n_cmds,
-                                             double ss, double ds, const double *__restrict__ ss_b, const double *__restrict__ ds_b,
-                                             wg_step_stack_t *stack, int smax, wg_rel_step_t *__restrict__ steps,
-                                             int *__restrict__ n_steps) {
+                                             const SpTimes<FLEET> &t, wg_step_stack_t *stack, int smax,
+                                             wg_rel_step_t *__restrict__ steps, int *__restrict__ n_steps) {
   const int b = blockIdx.x * kSpWaves + (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
   if (b >= B) return;
   const wg_step_stack_t S = stack[b];
@@ -30,12 +38,15 @@ __device__ __forceinline__ void sp_plan_gait(int B, int ccap, const wg_step_cmd_
   const wg_step_cmd_t *C = cmds + (size_t)b * ccap;
   const bool runs = S.error == 0 && nc != 0;              // else: a refused gait stays refused, an idle one sits out
   int keep = S.keep, w_cmd = 0, w_keep = 0, w_i = 0, total = 0;
+  double ss = 0.0, ds = 0.0;
   bool times_ok = true;
   if constexpr (FLEET) {
     if (runs) {
-      ss = ss_b[b]; ds = ds_b[b];
+      ss = t.ss[b]; ds = t.ds[b];
       times_ok = sp_finite(ss) && sp_finite(ds);
     }
+  } else {
+    ss = t.ss; ds = t.ds;
   }
   if (runs) total = nc < 0 || nc > ccap || !sp_foot_ok(keep) || !times_ok ? WG_STEPS_BAD_INPUT : sp_scan(C, nc, smax, &keep, lane, &w_cmd, &w_keep, &w_i);
   if (lane < total) steps[(size_t)b * smax + lane] = sp_cmd_step(C[w_cmd], w_keep, w_i, ss, ds);
@@ -51,19 +62,19 @@ __device__ __forceinline__ void sp_plan_gait(int B, int ccap, const wg_step_cmd_
   }
 }
 
+template <bool FLEET>
+__global__ __launch_bounds__(64 * kSpWaves) void wg_steps_plan_form_kernel(int B, int ccap, const wg_step_cmd_t *__restrict__ cmds,
+                                                                            const int *__restrict__ n_cmds, SpTimes<FLEET> t,
+                                                                            wg_step_stack_t *stack, int smax,
+                                                                            wg_rel_step_t *__restrict__ steps, int *__restrict__ n_steps) {
+  sp_plan_gait<FLEET>(B, ccap, cmds, n_cmds, t, stack, smax, steps, n_steps);
+}
+// the form with the call's times, under its own name and arguments
 __global__ __launch_bounds__(64 * kSpWaves) void wg_steps_plan_kernel(int B, int ccap, const wg_step_cmd_t *__restrict__ cmds,
                                                                        const int *__restrict__ n_cmds, double ss, double ds,
                                                                        wg_step_stack_t *stack, int smax,
                                                                        wg_rel_step_t *__restrict__ steps, int *__restrict__ n_steps) {
-  sp_plan_gait<false>(B, ccap, cmds, n_cmds, ss, ds, nullptr, nullptr, stack, smax, steps, n_steps);
-}
-
-__global__ __launch_bounds__(64 * kSpWaves) void wg_steps_plan_fleet_kernel(int B, int ccap, const wg_step_cmd_t *__restrict__ cmds,
-                                                                             const int *__restrict__ n_cmds,
-                                                                             const double *__restrict__ ss, const double *__restrict__ ds,
-                                                                             wg_step_stack_t *stack, int smax,
-                                                                             wg_rel_step_t *__restrict__ steps, int *__restrict__ n_steps) {
-  sp_plan_gait<true>(B, ccap, cmds, n_cmds, 0.0, 0.0, ss, ds, stack, smax, steps, n_steps);
+  sp_plan_gait<false>(B, ccap, cmds, n_cmds, {ss, ds}, stack, smax, steps, n_steps);
 }
 
 }  // namespace wg

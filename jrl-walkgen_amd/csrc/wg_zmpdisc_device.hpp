@@ -733,20 +733,15 @@ wg_zmpdisc_online_kernel(ZdConst K, int op, int B, int smax, const wg_rel_step_t
   zd_walk<true, false>(K, ZdFleet{}, op, B, smax, steps, n_steps, init_feet, select, lcap, O, state, length);
 }
 
-// The fleet twins of the two: a model per gait (wg_zmpdisc_full_fleet_dev; _begin_ / _append_ / _end_fleet_dev)
+// Every form of the walk, zd_walk's own argument list; the two above are <false, false> and <true, false> under the names and with
+// the arguments they are timed and audited by.  Launched for a model per gait: <false, true> wg_zmpdisc_full_fleet_dev, <true, true>
+// _begin_ / _append_ / _end_fleet_dev.
+template <bool RES, bool FLEET>
 __global__ void __launch_bounds__(64)
-wg_zmpdisc_fleet_kernel(ZdConst K, ZdFleet FL, int B, int smax, const wg_rel_step_t *__restrict__ steps,
-                        const int *__restrict__ n_steps, const double *__restrict__ init_feet, int lcap, ZdOut O,
-                        int *__restrict__ length) {
-  zd_walk<false, true>(K, FL, 0, B, smax, steps, n_steps, init_feet, nullptr, lcap, O, nullptr, length);
-}
-
-__global__ void __launch_bounds__(64)
-wg_zmpdisc_online_fleet_kernel(ZdConst K, ZdFleet FL, int op, int B, int smax, const wg_rel_step_t *__restrict__ steps,
-                               const int *__restrict__ n_steps, const double *__restrict__ init_feet,
-                               const int *__restrict__ select, int lcap, ZdOut O, wg_zmpdisc_state_t *__restrict__ state,
-                               int *__restrict__ length) {
-  zd_walk<true, true>(K, FL, op, B, smax, steps, n_steps, init_feet, select, lcap, O, state, length);
+wg_zmpdisc_form_kernel(ZdConst K, ZdFleet FL, int op, int B, int smax, const wg_rel_step_t *__restrict__ steps,
+                       const int *__restrict__ n_steps, const double *__restrict__ init_feet, const int *__restrict__ select,
+                       int lcap, ZdOut O, wg_zmpdisc_state_t *__restrict__ state, int *__restrict__ length) {
+  zd_walk<RES, FLEET>(K, FL, op, B, smax, steps, n_steps, init_feet, select, lcap, O, state, length);
 }
 
 }  // namespace wg

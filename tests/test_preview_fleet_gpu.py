@@ -322,3 +322,19 @@ def test_follow_form_equals_one_batch_run_over_the_final_queue(B, nl):
         d = max(int(want[b]), 0)
         c_, q_, s_ = fl.oracle(b, ZX[b], ZY[b], s0[b], d, True)
         assert np.array_equal(st[b], s_) and np.array_equal(cm[:d, :, b], c_) and np.array_equal(zz[:d, :, b], q_), b
+
+
+# The windows above reach T = 16 (both), 40 FULL of the split form.  These reach the rest -- T = 24 FULL / not, 32 FULL / not,
+# 40 not, 48 FULL / not -- so that every instantiation of the fleet forms is launched: the batch form with one partial block,
+# the follow form with its sitting-out and its refused gait.
+SPLIT_REST = [144, 150, 224, 200, 300, 336, 350]
+
+
+@pytest.mark.parametrize("nl", SPLIT_REST)
+def test_batch_form_every_other_split_instantiation(nl):
+    test_batch_form_bit_parity_per_gait(9, nl)
+
+
+@pytest.mark.parametrize("nl", [64, 100] + SPLIT_REST)
+def test_follow_form_every_other_split_instantiation(nl):
+    test_follow_form_equals_one_batch_run_over_the_final_queue(70, nl)

@@ -190,14 +190,16 @@ def test_ragged_growth_equals_the_whole_preview(B):
     f.assert_unchanged(snap)
 
 
-SHAPES = [(64, "split"), (100, "split"), (200, "split"), (320, "split"), (350, "split"), (40, None), (400, None), (320, "l2")]
+SHAPES = [(64, "split"), (100, "split"), (200, "split"), (320, "split"), (350, "split"), (40, None), (400, None), (320, "l2"),
+          (144, "split"), (150, "split"), (224, "split"), (300, "split"), (336, "split")]
 
 
 @pytest.mark.parametrize("sim", [0, 1])
 @pytest.mark.parametrize("nl,kernel", SHAPES)
 def test_every_kernel_shape(nl, kernel, sim, monkeypatch):
     """check 4: T = 16 full, 16 part, 32 part, 40 full, 48 part of the split form; the plain form below and above the split's
-    windows and forced at nl = 320"""
+    windows and forced at nl = 320; second row of SHAPES: T = 24 full, 24 part, 32 full, 40 part, 48 full, so that every
+    instantiation of the follow form is launched"""
     if kernel:
         monkeypatch.setenv("WG_PREVIEW_KERNEL", kernel)
     else:
