@@ -35,11 +35,11 @@ namespace wg {
 // The solver.  Problem data must already be in LDS: G (copy of C, patched per
 // qld.cpp:442-444), A, d, b (INNER sign: b = -b_user, qld.cpp:469-475), xl, xu.
 // hist: optional global add(+code)/drop(-code) log written by lane 0.
-// compact view (n <= 36): the LDS-pipelined form with two 48-entry buffers; other views whose four scratch vectors hold two
+// compact view (n <= 36): the LDS-pipelined form with two 48-entry buffers, its bottom rows at their own lengths; other views whose four scratch vectors hold two
 // 96-entry buffers (n >= 48) take it too while every multiplier has a lane of its own (nact <= 60), the generic forms otherwise
 #define WG_BACKSUB(q, s, nact, lane)                                                                   \
   do {                                                                                                 \
-    if constexpr (P::kNM > 0 && P::kNM + 12 <= 48) backsub_lds<48>(q, s, nact, lane, q.sc0);          \
+    if constexpr (P::kNM > 0 && P::kNM + 12 <= 48) backsub_lds<48, ExactBacksubOf<P>::value>(q, s, nact, lane, q.sc0); \
     else if (P::kNM == 0 && (P::kWideN || q.n >= 48) && (nact) <= 60) backsub_lds<96>(q, s, nact, lane, q.sc0);     \
     else if (P::kNM == 0 && !P::kRowOps && q.n >= 24 && (nact) <= 36) backsub_lds<48>(q, s, nact, lane, q.sc0); \
     else backsub(q, s, nact, lane);                                                                    \

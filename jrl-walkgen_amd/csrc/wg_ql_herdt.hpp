@@ -245,6 +245,7 @@ struct HerdtProb {
   static constexpr int kFixedLdz = kNM | 1;    // Z in LDS, leading dimension of carve_fixed<kNM, ...>
   static constexpr bool kGuardedSums = true;   // the decision-only sums as trees over the lanes, under wg_ql_guard.hpp's certificates
   static constexpr bool kSeededNorms = true;   // the sweep's norm chain from lane-parallel seeds, checked once (wg_ql_norms.hpp)
+  static constexpr bool kExactBacksub = true;  // the back substitution's bottom eight rows add and read their own terms only (bs_row)
   static_assert(4 * NH == 64, "one CoP row per lane needs 4N == 64");
   // ---- LDS / global tables (wave-uniform pointers) ----
   const double *Qb;       // global (L1/L2-resident constant of the model), NH x kQbLd

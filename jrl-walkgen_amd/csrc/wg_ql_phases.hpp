@@ -306,7 +306,10 @@ struct BsState { double w, wprev, rr, sreg, dreg, rsd; int col, nact, lane; bool
 // kHead: what is known about the row's length at compile time (the rows go from the bottom up, so the r-th row from the bottom has
 // r terms): -1 nothing (three uniform branches per row), 0 no term, 4 / 8 at most so many (the prefetched head only: entries
 // past the row are +0.0), 9 more than eight (head and tail loop, no test) -- backsub_lds unrolls the first nine rows that way
-template <int kBsLen, int kHead = -1>                       // kBsLen: length of each of the two product buffers (>= nact + 12)
+// kExact (the compact view): kHead = 0 .. 8 is the row's length itself.  The row adds its kHead terms and requests the kHead
+// LDS-borne terms of the next row, nothing else: what the rounded-up heads add and read beyond the row are +0.0 entries, and a sum
+// that starts from +0.0 is never -0.0, so x + (+0.0) is x bit for bit -- 20 dependent adds and 16 LDS reads per nine rows less
+template <int kBsLen, int kHead = -1, bool kExact = false>  // kBsLen: length of each of the two product buffers (>= nact + 12)
 __device__ __forceinline__ void bs_row(const QlView &q, double *buf, int j, BsState &S, const double (&P)[9], double (&Nx)[9]) {
   const double *bj = buf + (j & 1) * kBsLen;
   double *bn = buf + ((j & 1) ^ 1) * kBsLen;
@@ -329,12 +332,18 @@ __device__ __forceinline__ void bs_row(const QlView &q, double *buf, int j, BsSt
     typedef __attribute__((address_space(3))) double lds_f64;
     const lds_f64 *np = (const lds_f64 *)(bn + j + 1);
     asm volatile("" : "+v"(np));
+    constexpr int kNext = kExact && kHead < 8 ? kHead : 8;  // the next row has one term more than this one, the first from registers
 #pragma unroll
-    for (int e = 0; e < 8; ++e) Nx[e] = np[e];              // prefetch: the next row's first terms
+    for (int e = 0; e < kNext; ++e) Nx[e] = np[e];          // prefetch: the next row's first terms
     Nx[8] = rl(S.rsd, jn);
   }
   const double sj = rl(S.sreg, j), dj = rl(S.dreg, j);
   double sum = 0.0;
+  if constexpr (kExact && kHead >= 1 && kHead <= 8) {
+    sum += P[8] * S.wprev;
+#pragma unroll
+    for (int e = 0; e < kHead - 1; ++e) sum += P[e];
+  } else
   if constexpr (kHead >= 4) {
     sum += P[8] * S.wprev;
     sum += P[0]; sum += P[1]; sum += P[2]; sum += P[3];
@@ -377,7 +386,7 @@ __device__ __forceinline__ void bs_row(const QlView &q, double *buf, int j, BsSt
   if (lane == j) S.w = v;
   S.wprev = v;
 }
-template <int kBsLen = 48>                                  // nact <= 64 (one multiplier per lane) and nact + 12 <= kBsLen
+template <int kBsLen = 48, bool kExact = false>             // nact <= 64 (one multiplier per lane) and nact + 12 <= kBsLen; kExact: bs_row
 __device__ __forceinline__ void backsub_lds(const QlView &q, const double *s, int nact, int lane, double *buf) {
   BsState S;
   S.mine = lane < nact; S.nact = nact; S.lane = lane;
@@ -408,15 +417,15 @@ __device__ __forceinline__ void backsub_lds(const QlView &q, const double *s, in
   int j = nact - 1;
   if constexpr (kBsLen <= 64) {
     // the first nine rows unrolled with their lengths known (one uniform test per row instead of three), the rest in pairs
-    if (nact > 0) { bs_row<kBsLen, 0>(q, buf, nact - 1, S, A9, B9);
-    if (nact > 1) { bs_row<kBsLen, 4>(q, buf, nact - 2, S, B9, A9);
-    if (nact > 2) { bs_row<kBsLen, 4>(q, buf, nact - 3, S, A9, B9);
-    if (nact > 3) { bs_row<kBsLen, 4>(q, buf, nact - 4, S, B9, A9);
-    if (nact > 4) { bs_row<kBsLen, 4>(q, buf, nact - 5, S, A9, B9);
-    if (nact > 5) { bs_row<kBsLen, 8>(q, buf, nact - 6, S, B9, A9);
-    if (nact > 6) { bs_row<kBsLen, 8>(q, buf, nact - 7, S, A9, B9);
-    if (nact > 7) { bs_row<kBsLen, 8>(q, buf, nact - 8, S, B9, A9);
-    if (nact > 8) { bs_row<kBsLen, 8>(q, buf, nact - 9, S, A9, B9);
+    if (nact > 0) { bs_row<kBsLen, 0, kExact>(q, buf, nact - 1, S, A9, B9);
+    if (nact > 1) { bs_row<kBsLen, kExact ? 1 : 4, kExact>(q, buf, nact - 2, S, B9, A9);
+    if (nact > 2) { bs_row<kBsLen, kExact ? 2 : 4, kExact>(q, buf, nact - 3, S, A9, B9);
+    if (nact > 3) { bs_row<kBsLen, kExact ? 3 : 4, kExact>(q, buf, nact - 4, S, B9, A9);
+    if (nact > 4) { bs_row<kBsLen, 4, kExact>(q, buf, nact - 5, S, A9, B9);
+    if (nact > 5) { bs_row<kBsLen, kExact ? 5 : 8, kExact>(q, buf, nact - 6, S, B9, A9);
+    if (nact > 6) { bs_row<kBsLen, kExact ? 6 : 8, kExact>(q, buf, nact - 7, S, A9, B9);
+    if (nact > 7) { bs_row<kBsLen, kExact ? 7 : 8, kExact>(q, buf, nact - 8, S, B9, A9);
+    if (nact > 8) { bs_row<kBsLen, 8, kExact>(q, buf, nact - 9, S, A9, B9);
       for (j = nact - 10; j >= 1; j -= 2) { bs_row<kBsLen, 9>(q, buf, j, S, B9, A9); bs_row<kBsLen, 9>(q, buf, j - 1, S, A9, B9); }
       if (j == 0) bs_row<kBsLen, 9>(q, buf, 0, S, B9, A9);
     }}}}}}}}}

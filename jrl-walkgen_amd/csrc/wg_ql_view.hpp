@@ -249,6 +249,10 @@ enum : int { kSumsGuarded = 0, kSumsOrdered = 1, kSumsDoubt = 2, kSumsMask = 3 }
 template <class P, class = void> struct SeededNormsOf { static constexpr bool value = false; };
 template <class P> struct SeededNormsOf<P, typename std::enable_if<P::kSeededNorms>::type> { static constexpr bool value = true; };
 enum : int { kNormsSeeded = 0, kNormsExact = 1 << 8, kNormsDoubt = 2 << 8, kNormsMask = 3 << 8 };
+// the back substitution's bottom rows at their own lengths (bs_row's kExact, wg_ql_phases.hpp): a policy that declares
+// kExactBacksub; every other policy keeps the rounded-up heads
+template <class P, class = void> struct ExactBacksubOf { static constexpr bool value = false; };
+template <class P> struct ExactBacksubOf<P, typename std::enable_if<P::kExactBacksub>::type> { static constexpr bool value = true; };
 constexpr int kQlDoubt = -7778;                            // QlResult::ifail of a guarded solve that must be run again (ql_solve_guarded)
 
 struct QlResult {
