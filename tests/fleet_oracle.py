@@ -3,7 +3,8 @@
 Every gait of a workload advanced on oracle/libwg_oracle_ptrig.so (the C restatement with the portable trigonometry: the
 bit-exact partner of the kernels), split into chunks over spawned worker processes -- the QL restatement keeps statics, so
 separate processes, never threads, and never fork.  A test queues the oracle first (submit), runs the GPU meanwhile and
-collects the results afterwards (FleetJob.result).
+collects the results afterwards (FleetJob.result).  A fleet with a model per gait goes through submit_fleet: grouped by model,
+one or more chunks per model, the result back in gait order.
 
 Workers are fresh interpreters that see only this module, numpy and ctypes: they never import torch, bench.py or the product's
 binding, and never load libwg_mpc.so or the HIP runtime.  The parent builds the oracle once (build_oracle) and hands the
@@ -105,6 +106,72 @@ def submit(pool, layout, model_bytes, start, vel, redraw, n_ticks, keep_ticks=()
         asyncs.append(pool.apply_async(advance, args))
         g0 += ng
     return FleetJob(asyncs, B, n_ticks, tuple(keep_ticks), outs)
+
+
+class MixedFleetJob:
+    """Chunks of a fleet with a model per gait in flight on a pool (submit_fleet); result() puts them back in gait order."""
+
+    def __init__(self, asyncs, index, accepted, start, state_size, out_size, n_ticks, keep_ticks, outs):
+        self._asyncs, self._index, self.accepted, self._start = asyncs, index, accepted, start
+        self._sz, self._osz, self.n_ticks, self.keep_ticks, self.outs = state_size, out_size, n_ticks, keep_ticks, outs
+        self.n_gaits = len(accepted)
+
+    def done(self):
+        """(chunks finished, chunks in all)"""
+        return sum(a.ready() for a in self._asyncs), len(self._asyncs)
+
+    def result(self, timeout=None):
+        """states, diag [n_ticks, B, 6] and the kept outs of all B gaits in gait order, and `accepted` [B]: a gait that was
+        not submitted holds its start state, zeros in diag and zeros in outs"""
+        B, sz, osz = self.n_gaits, self._sz, self._osz
+        states = np.frombuffer(self._start, dtype=np.uint8).reshape(B, sz).copy()
+        diag = np.zeros((self.n_ticks, B, 6), dtype=np.int32)
+        raw = self.outs == "raw"
+        kept = {t: (np.zeros((B, osz), dtype=np.uint8) if raw else np.zeros(B, dtype=np.uint64)) for t in self.keep_ticks}
+        workers = []
+        for a in self._asyncs:
+            p = a.get(timeout)
+            idx = self._index[p["g0"]]
+            assert p["ng"] == len(idx)
+            states[idx] = np.frombuffer(p["states"], dtype=np.uint8).reshape(len(idx), sz)
+            diag[:, idx] = p["diag"]
+            for t in self.keep_ticks:
+                kept[t][idx] = np.frombuffer(p["outs"][t], dtype=np.uint8).reshape(len(idx), osz) if raw else p["outs"][t]
+            workers.append(p["worker"])
+        return {"states": states.tobytes(), "diag": diag, "accepted": self.accepted.copy(), "workers": workers,
+                "outs": {t: (v.tobytes() if raw else v) for t, v in kept.items()}}
+
+
+def submit_fleet(pool, layout, models, model_of, start, vel, redraw, n_ticks, keep_ticks=(), outs="raw", nan_aware=False,
+                 chunk=None):
+    """submit's sibling for a fleet with a model per gait.  models: the bytes of every model, None where a block is none a
+    gait may run with; model_of [B]: gait g runs with models[model_of[g]].  A gait whose model_of is outside the list or names
+    a None is refused: it is not submitted.  start: B states' bytes; vel: [n_seg, B, 3].  The gaits are grouped by model and
+    every group is queued in chunks of at most `chunk` gaits (default: about four chunks per MAX_WORKERS over the fleet)
+    through `advance`."""
+    vel = np.ascontiguousarray(vel, dtype=np.float64)
+    model_of = np.asarray(model_of, dtype=np.int64)
+    B = vel.shape[1]
+    sz = layout["state_size"]
+    assert model_of.shape == (B,) and len(start) == B * sz and outs in ("raw", "digest")
+    usable = np.array([m is not None for m in models], dtype=bool)
+    inside = (model_of >= 0) & (model_of < len(models))
+    accepted = inside.copy()
+    accepted[inside] = usable[model_of[inside]]
+    if chunk is None:
+        chunk = max(1, -(-int(accepted.sum()) // (4 * MAX_WORKERS)))
+    assert chunk >= 1
+    st = np.frombuffer(start, dtype=np.uint8).reshape(B, sz)
+    asyncs, index = [], []
+    for k in np.unique(model_of[accepted]):
+        group = np.flatnonzero(accepted & (model_of == k))
+        for lo in range(0, len(group), chunk):
+            idx = group[lo:lo + chunk]
+            args = (layout, bytes(models[k]), st[idx].tobytes(), np.ascontiguousarray(vel[:, idx]), int(redraw), int(n_ticks),
+                    tuple(keep_ticks), outs, bool(nan_aware), len(index))
+            asyncs.append(pool.apply_async(advance, args))
+            index.append(idx)
+    return MixedFleetJob(asyncs, index, accepted, bytes(start), sz, layout["out_size"], n_ticks, tuple(keep_ticks), outs)
 
 
 # ---------------------------------------------------------------------------------------------------------- worker side
