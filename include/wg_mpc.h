@@ -1373,6 +1373,143 @@ int wg_foot_constraints_append_fleet_dev_ctx(wg_ctx_t *ctx, int B, int lcap, int
                                              wg_zmp_polytope_t *queues, double *t_start, double *t_end, int *count,
                                              void *hip_stream);
 
+/* Morisawa-2007 analytic walks: CoM, ZMP and feet of a step sequence in closed form, batched over gaits -----------------------
+ *
+ * What the reference computes after ":SetAlgoForZmpTrajectory Morisawa" for a ":stepseq" (no on-line change):
+ *     AnalyticalMorisawaCompact::GetZMPDiscretization      src/ZMPRefTrajectoryGeneration/AnalyticalMorisawaCompact.cpp:514-579
+ *       = BuildAndSolveCOMZMPForASetOfSteps (:360-512, IgnoreFirstRelativeFoot = true, DoNotPrepareLastFoot = false) with
+ *         InitializeBasicVariables (:170-224), BuildingTheZMatrix / ComputeZ1 / ComputeZj / ComputeZm (:944-1164), ComputeW
+ *         (:831-942), TransfertTheCoefficientsToTrajectories (:1166-1233), then FillQueues (:2230-2290; OnLine's analytic branch
+ *         :648-723 evaluates the same),
+ *     AnalyticalZMPCOGTrajectory::ComputeCOM / ComputeCOMSpeed / ComputeZMP by interval, GetIntervalIndexFromTime,
+ *       TransfertOneIntervalCoefficientsFromCOGTrajectoryToZMPOne, Building3rdOrderPolynomial
+ *                                                          src/Mathematics/AnalyticalZMPCOGTrajectory.cpp:175-196, 276-282,
+ *                                                          472-507, 386-410, 425-456
+ *     LeftAndRightFootTrajectoryGenerationMultiple::InitializeFromRelativeSteps (Continuity = false), SetAnInterval
+ *                                                          src/FootTrajectoryGeneration/LeftAndRightFootTrajectoryGenerationMultiple.cpp:168-572, 107-166
+ *     FootTrajectoryGenerationMultiple::Compute(t, FAP, index), FootTrajectoryGenerationStandard::
+ *       SetParametersWithInitPosInitSpeed / ComputeAll     FootTrajectoryGenerationMultiple.cpp:128-135,
+ *                                                          FootTrajectoryGenerationStandard.cpp:188-227, 307-333
+ *     Polynome4::SetParametersWithInitPosInitSpeed, Polynome5::SetParameters(FT, FP, p0, v0, 0),
+ *       Polynome3::SetParametersWithInitPosInitSpeed       src/Mathematics/PolynomeFoot.cpp:122-146, 226-240, 59-79
+ * The walk of S steps has 2 S + 1 intervals (3 t_single, then t_double and t_single in turn, 3 t_single) and one linear system
+ * Z y = w of n = 4 S + 8 unknowns per gait; x and y are two right-hand sides of one Z.  The reference hands it to LAPACK
+ * (dgetrf_ / dgesvx_, :263-357); here it is a partially pivoted LU without refinement, so parity is by tolerance.  Not here: the
+ * on-line window (InitOnLine, OnLineAddFoot, ChangeFootLandingPosition, TimeChange), the preview-control filter, ChangeOnLineStep,
+ * a CoM height per interval.
+ *
+ * Two steps: wg_morisawa_solve* turns each gait's steps into a TRAJECTORY BLOCK of wg_morisawa_block_bytes(smax) bytes (counts,
+ * interval times and omega_j, per interval the ZMP and CoG polynomials of x and y and the weights V, W, both feet's polynomials,
+ * the ZMP profile, the absolute support feet, w and y, Z's LU factor and pivots -- a new right-hand side can be solved from the
+ * block -- zeros elsewhere: blocks compare as bytes); wg_morisawa_sample* evaluates blocks on one clock.
+ *   steps      B x smax   gait b uses the first n_steps[b]; 2 <= n_steps[b] <= smax <= WG_MORISAWA_MAX_STEPS.  sx, sy, theta
+ *                         (degrees) are read; the times are the model's
+ *   init_feet  B x 6      left x, y, theta, right x, y, theta at the start (z, omega, omega2 and every speed 0)
+ *   com0       B x 3      start CoM x, y and height (lStartingCOMState; the height is every interval's CoMZ, ZMPZ is 0)
+ *   blocks     B blocks;  status B: WG_OK or WG_MORISAWA_BAD_INPUT (n_steps out of range; a time or the height not finite or not
+ *                         positive; another input not finite; omega_j dT_j > 40, beyond what cosh / sinh here are made for),
+ *                         WG_MORISAWA_SINGULAR (a zero or non-finite pivot).  A refused gait's block is left untouched.
+ * Sample k is at trajectory time t_start + k additions of T (the control loop's clock, PatternGeneratorInterfacePrivate.cpp:1256;
+ * the reference's queue starts at 2 t_single); a gait has the samples with t <= the sum of its interval times (FillQueues' loop).
+ * Outputs are time-major in the layouts of wg_zmpdisc_full_batch_dev: zmp_x_tm, zmp_y_tm [lcap][B]; com_tm [lcap][4][B] (x, dx,
+ * y, dy); left_tm, right_tm [lcap][6][B] (x, y, z, theta, omega, omega2); left_type_tm, right_type_tm [lcap][B] (the interval's
+ * nature, SetNatureInterval); any of them NULL.  Samples past a gait's length repeat its last one.  length[b] (may be NULL):
+ * the count, or status[b] < 0 handed on (status may be NULL: every block is taken as solved), WG_MORISAWA_BAD_INPUT for a block
+ * that is not one of this smax, WG_MORISAWA_CAPACITY for more samples than lcap; such a gait's outputs are left untouched.
+ * Host-side errors (WG_ERR_BAD_ARG, nothing launched): NULL inputs, B < 0, smax outside [2, WG_MORISAWA_MAX_STEPS], lcap < 1,
+ * T or t_start not finite, T <= 0, t_start < 0.  B == 0 is WG_OK.
+ * wg_morisawa_solve, _solve_fleet, _sample, _length, _system are host arithmetic without a device call -- the kernels' bytes.
+ * The _dev calls take DEVICE pointers and are asynchronous on hip_stream; wg_morisawa_walk_dev is solve and sample on that
+ * stream without a synchronisation between them (T = model->T).  The _fleet forms take B models, gait b its own (host array for
+ * wg_morisawa_solve_fleet, DEVICE array for the _dev forms): gait b's bytes are those of the one-model call handed model b. */
+#define WG_MORISAWA_MAX_STEPS 14     /* n = 4 S + 8 = 64: one row of Z per lane */
+#define WG_MORISAWA_BAD_INPUT (-1)
+#define WG_MORISAWA_CAPACITY (-2)
+#define WG_MORISAWA_SINGULAR (-3)
+typedef struct wg_morisawa_model {
+  double T;                           /* m_SamplingPeriod  0.005 */
+  double t_single, t_double;          /* m_Tsingle, m_Tdble  0.78, 0.02 (CommonTools.cpp:57-67 of the reference's tests) */
+  double step_height;                 /* m_StepHeight  0.07 */
+  double omega;                       /* m_Omega, degrees  0 */
+} wg_morisawa_model_t;
+/* a block, read on the host: pointers into it */
+typedef struct wg_morisawa_view {
+  int n_steps, n_int, n, smax;        /* S, 2 S + 1, 4 S + 8, the smax the block was made for */
+  double com_height, t_total;         /* CoMZ; the sum of the interval times */
+  const double *dT, *omega, *tref;    /* [n_int] m_DeltaTj, m_Omegaj, m_RefTime */
+  const double *zmp_x, *cog_x, *zmp_y, *cog_y;   /* [n_int][5] coefficients 0 .. 4 (interior intervals are cubics) */
+  const double *Vx, *Wx, *Vy, *Wy;    /* [n_int] */
+  const double *left, *right;         /* [n_int][6][6]: axis x y z theta omega omega2, coefficients 0 .. 5 */
+  const int *left_type, *right_type;  /* [n_int] m_NatureOfIntervals */
+  const double *profile_x, *profile_y;/* [n_int] ZMPProfil */
+  const double *support;              /* [n_steps][3] m_AbsoluteSupportFootPositions x, y, theta (degrees) */
+  const double *wx, *wy, *yx, *yy;    /* [n] */
+  const int *piv;                     /* [n] row k was swapped with row piv[k] >= k (LAPACK's ipiv, 0-based) */
+  const double *lu;                   /* P Z = L U, unit L below the diagonal; rows lu_pitch apart */
+  int lu_pitch, pad_;
+} wg_morisawa_view_t;
+#define WG_MORISAWA_MODEL_BYTES 40
+#define WG_MORISAWA_VIEW_BYTES 232
+#ifdef __cplusplus
+static_assert(sizeof(wg_morisawa_model_t) == WG_MORISAWA_MODEL_BYTES, "wg_morisawa_model_t is part of the ABI");
+static_assert(sizeof(wg_morisawa_view_t) == WG_MORISAWA_VIEW_BYTES, "wg_morisawa_view_t is part of the ABI");
+#else
+_Static_assert(sizeof(wg_morisawa_model_t) == WG_MORISAWA_MODEL_BYTES, "wg_morisawa_model_t is part of the ABI");
+_Static_assert(sizeof(wg_morisawa_view_t) == WG_MORISAWA_VIEW_BYTES, "wg_morisawa_view_t is part of the ABI");
+#endif
+void wg_morisawa_defaults(wg_morisawa_model_t *model);
+size_t wg_morisawa_block_bytes(int smax);                 /* a multiple of 128; 0 for an smax out of range */
+int wg_morisawa_block_unpack(const void *block, int smax, wg_morisawa_view_t *view);
+/* samples of a walk of n_steps steps from t_start, by the additions the sampler makes, or a negative code */
+int wg_morisawa_length(const wg_morisawa_model_t *model, int n_steps, double t_start);
+/* the library's cosh and sinh of x in [0, 40] (IEEE + - * / only, the same bits on host and device) */
+int wg_morisawa_coshsinh(double x, double *cosh_x, double *sinh_x);
+/* Z (n x n, rows n apart) and w of x and y before the elimination, one gait; returns n or a negative code */
+int wg_morisawa_system(const wg_morisawa_model_t *model, int n_steps, const wg_rel_step_t *steps, const double *init_feet,
+                       const double *com0, double *Z, double *wx, double *wy);
+int wg_morisawa_solve(const wg_morisawa_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps,
+                      const double *init_feet, const double *com0, void *blocks, int *status);
+int wg_morisawa_solve_fleet(const wg_morisawa_model_t *models, int B, int smax, const wg_rel_step_t *steps, const int *n_steps,
+                            const double *init_feet, const double *com0, void *blocks, int *status);
+int wg_morisawa_sample(int B, int smax, const void *blocks, const int *status, double t_start, double T, int lcap,
+                       double *zmp_x_tm, double *zmp_y_tm, double *com_tm, double *left_tm, int *left_type_tm, double *right_tm,
+                       int *right_type_tm, int *length);
+int wg_morisawa_solve_dev(const wg_morisawa_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps,
+                          const double *init_feet, const double *com0, void *blocks, int *status, void *hip_stream);
+int wg_morisawa_solve_fleet_dev(const wg_morisawa_model_t *models, int B, int smax, const wg_rel_step_t *steps,
+                                const int *n_steps, const double *init_feet, const double *com0, void *blocks, int *status,
+                                void *hip_stream);
+int wg_morisawa_sample_dev(int B, int smax, const void *blocks, const int *status, double t_start, double T, int lcap,
+                           double *zmp_x_tm, double *zmp_y_tm, double *com_tm, double *left_tm, int *left_type_tm,
+                           double *right_tm, int *right_type_tm, int *length, void *hip_stream);
+int wg_morisawa_walk_dev(const wg_morisawa_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps,
+                         const double *init_feet, const double *com0, void *blocks, int *status, double t_start, int lcap,
+                         double *zmp_x_tm, double *zmp_y_tm, double *com_tm, double *left_tm, int *left_type_tm,
+                         double *right_tm, int *right_type_tm, int *length, void *hip_stream);
+int wg_morisawa_walk_fleet_dev(const wg_morisawa_model_t *models, double T, int B, int smax, const wg_rel_step_t *steps,
+                               const int *n_steps, const double *init_feet, const double *com0, void *blocks, int *status,
+                               double t_start, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *com_tm, double *left_tm,
+                               int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream);
+/* the same on a context of the caller's: the sampler keeps its clock in the context, so launches of one context are ordered */
+int wg_morisawa_solve_dev_ctx(wg_ctx_t *ctx, const wg_morisawa_model_t *model, int B, int smax, const wg_rel_step_t *steps,
+                              const int *n_steps, const double *init_feet, const double *com0, void *blocks, int *status,
+                              void *hip_stream);
+int wg_morisawa_solve_fleet_dev_ctx(wg_ctx_t *ctx, const wg_morisawa_model_t *models, int B, int smax,
+                                    const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, const double *com0,
+                                    void *blocks, int *status, void *hip_stream);
+int wg_morisawa_sample_dev_ctx(wg_ctx_t *ctx, int B, int smax, const void *blocks, const int *status, double t_start, double T,
+                               int lcap, double *zmp_x_tm, double *zmp_y_tm, double *com_tm, double *left_tm, int *left_type_tm,
+                               double *right_tm, int *right_type_tm, int *length, void *hip_stream);
+int wg_morisawa_walk_dev_ctx(wg_ctx_t *ctx, const wg_morisawa_model_t *model, int B, int smax, const wg_rel_step_t *steps,
+                             const int *n_steps, const double *init_feet, const double *com0, void *blocks, int *status,
+                             double t_start, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *com_tm, double *left_tm,
+                             int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream);
+int wg_morisawa_walk_fleet_dev_ctx(wg_ctx_t *ctx, const wg_morisawa_model_t *models, double T, int B, int smax,
+                                   const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, const double *com0,
+                                   void *blocks, int *status, double t_start, int lcap, double *zmp_x_tm, double *zmp_y_tm,
+                                   double *com_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm,
+                                   int *length, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,7 @@
 #include "wg_dimitrov_kernels.hpp"
 #include "wg_steps_kernels.hpp"
 #include "wg_riccati_kernels.hpp"
+#include "wg_morisawa_kernels.hpp"
 
 
 namespace {
@@ -167,6 +168,9 @@ struct wg_ctx {
   DevBuf prev_buf;
   // staging of the host-pointer entry points
   DevBuf in, out, gram_buf, zd_buf;
+  // Morisawa walks: the sampler's clock of the launch (wg_morisawa_clock_kernel); one launch at a time uses it, claimed and marked
+  DevBuf mo_clock;
+  SlotOrder mo_order;
   void release_all() {
     if (tables_dev) (void)hipFree(tables_dev);
     if (model_dev) (void)hipFree(model_dev);
@@ -175,10 +179,10 @@ struct wg_ctx {
     if (prev_F) (void)hipFree(prev_F);
     tables_dev = nullptr; model_dev = nullptr; pldp_dev = nullptr; dim_dev = nullptr; prev_F = nullptr;
     model_set = false; pldp_N = 0; dim_set = false; prev_set = false;
-    for (DevBuf *b : {&tick_state, &tick_out, &tick_aux, &run_buf, &tick_z, &asm_state, &qp_slot, &pldp_buf, &dim_buf, &fc_buf, &walk_polys, &prev_buf, &in, &out, &gram_buf, &zd_buf})
+    for (DevBuf *b : {&tick_state, &tick_out, &tick_aux, &run_buf, &tick_z, &asm_state, &qp_slot, &pldp_buf, &dim_buf, &fc_buf, &walk_polys, &prev_buf, &in, &out, &gram_buf, &zd_buf, &mo_clock})
       b->release();
     for (Lpt *l : {&tick_lpt, &qp_lpt, &dim_lpt}) l->release();
-    for (SlotOrder *o : {&guard_order, &qp_order, &asm_order, &aux_order, &fc_order, &walk_order}) {
+    for (SlotOrder *o : {&guard_order, &qp_order, &asm_order, &aux_order, &fc_order, &walk_order, &mo_order}) {
       if (o->ev) (void)hipEventDestroy(o->ev);
       o->ev = nullptr; o->armed = false; o->stream = nullptr;
     }
@@ -256,7 +260,7 @@ int slot_claim(wg_ctx *ctx, wg_ctx::SlotOrder &o, hipStream_t st, const char *wh
 // the context's own streams) -- not for the device
 int ctx_wait_own(wg_ctx *ctx) {
   std::lock_guard<std::mutex> launch_lk(ctx->launch_mu);
-  for (wg_ctx::SlotOrder *o : {&ctx->guard_order, &ctx->qp_order, &ctx->asm_order, &ctx->aux_order, &ctx->fc_order, &ctx->walk_order})
+  for (wg_ctx::SlotOrder *o : {&ctx->guard_order, &ctx->qp_order, &ctx->asm_order, &ctx->aux_order, &ctx->fc_order, &ctx->walk_order, &ctx->mo_order})
     if (o->armed) HIP_TRY(hipEventSynchronize(o->ev));
   if (ctx->host_stream) HIP_TRY(hipStreamSynchronize(ctx->host_stream));
   if (ctx->pin_stream) HIP_TRY(hipStreamSynchronize(ctx->pin_stream));
@@ -2449,5 +2453,83 @@ int wg_steps_plan_fleet_dev(int B, int ccap, const wg_step_cmd_t *cmds, const in
 int wg_foot_constraints_fleet_dev(int B, int lcap, const int *length, const double *time, const double *left_tm, const int *left_type_tm, const double *right_tm, const wg_sole_t *soles, int qcap, wg_zmp_polytope_t *queues, double *t_start, double *t_end, int *count, void *hip_stream) { return on_default(&wg_foot_constraints_fleet_dev_ctx, B, lcap, length, time, left_tm, left_type_tm, right_tm, soles, qcap, queues, t_start, t_end, count, hip_stream); }
 int wg_foot_constraints_append_fleet_dev(int B, int lcap, int first_sample, int *done, const int *length, const double *time, const double *left_tm, const int *left_type_tm, const double *right_tm, const wg_sole_t *soles, int qcap, wg_zmp_polytope_t *queues, double *t_start, double *t_end, int *count, void *hip_stream) { return on_default(&wg_foot_constraints_append_fleet_dev_ctx, B, lcap, first_sample, done, length, time, left_tm, left_type_tm, right_tm, soles, qcap, queues, t_start, t_end, count, hip_stream); }
 int wg_zmpdisc_batch(const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap, double *zmp, double *zmp_theta, int *zmp_type, double *left, int *left_type, double *right, int *right_type, int *length) { return on_default(&wg_zmpdisc_batch_ctx, model, B, smax, steps, n_steps, init_feet, lcap, zmp, zmp_theta, zmp_type, left, left_type, right, right_type, length); }
+
+}  // extern "C"
+
+// ---- Morisawa-2007 analytic walks (wg_morisawa_kernels.hpp; the host twins are wg_morisawa.cpp) ---------------------------------
+namespace {
+
+int mo_solve_check(const void *models, int B, int smax, const void *steps, const void *n_steps, const void *init_feet, const void *com0, const void *blocks, const void *status) {
+  if (!models || B < 0 || smax < 2 || smax > WG_MORISAWA_MAX_STEPS || !steps || !n_steps || !init_feet || !com0 || !blocks || !status)
+    return fail(WG_ERR_BAD_ARG, "need a model, B >= 0, 2 <= smax <= %d, non-null steps, n_steps, init_feet, com0, blocks, status", WG_MORISAWA_MAX_STEPS);
+  return WG_OK;
+}
+int mo_sample_check(int B, int smax, const void *blocks, double t_start, double T, int lcap) {
+  if (!blocks || B < 0 || smax < 2 || smax > WG_MORISAWA_MAX_STEPS || lcap < 1 || lcap > (1 << 19) || !wg::mo_finite(T) || !(T > 0.0) || !wg::mo_finite(t_start) || t_start < 0.0)
+    return fail(WG_ERR_BAD_ARG, "need blocks, B >= 0, 2 <= smax <= %d, 1 <= lcap <= %d, finite T > 0 and t_start >= 0", WG_MORISAWA_MAX_STEPS, 1 << 19);
+  return WG_OK;
+}
+// one wave per gait, the gait's work area in LDS; under the context's launch lock like every launch of a context
+template <bool FLEET>
+int mo_solve_launch(wg_ctx *ctx, const wg_morisawa_model_t *mf, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, const double *com0, void *blocks, int *status, hipStream_t st) {
+  if (int rc = use_ctx(ctx)) return rc;
+  if (int rc = mo_solve_check(mf, B, smax, steps, n_steps, init_feet, com0, blocks, status)) return rc;
+  if (B == 0) return WG_OK;
+  wg_morisawa_model_t m;
+  memset(&m, 0, sizeof m);
+  if (!FLEET) m = *mf;
+  const size_t lds = (size_t)wg::mo_layout(smax).work_words * sizeof(double);
+  std::lock_guard<std::mutex> launch_lk(ctx->launch_mu);
+  return launch_lds(wg::wg_morisawa_solve_kernel<FLEET>, dim3(B), dim3(64), lds, st, m, FLEET ? mf : nullptr, B, smax, steps, n_steps, init_feet, com0, static_cast<double *>(blocks), status);
+}
+// the clock of the launch into the context's buffer, then a lane per gait and kMoSampleChunk samples
+int mo_sample_launch(wg_ctx *ctx, int B, int smax, const void *blocks, const int *status, double t_start, double T, int lcap, const wg::MoOut &O, int *length, hipStream_t st) {
+  if (int rc = use_ctx(ctx)) return rc;
+  if (int rc = mo_sample_check(B, smax, blocks, t_start, T, lcap)) return rc;
+  if (B == 0) return WG_OK;
+  std::lock_guard<std::mutex> launch_lk(ctx->launch_mu);
+  if (int rc = slot_claim(ctx, ctx->mo_order, st, "Morisawa sample")) return rc;
+  if (int rc = ctx->mo_clock.reserve((size_t)(lcap + 1) * sizeof(double))) return rc;
+  double *clock = static_cast<double *>(ctx->mo_clock.p);
+  hipLaunchKernelGGL(wg::wg_morisawa_clock_kernel, dim3(1), dim3(1), 0, st, t_start, T, lcap + 1, clock);
+  HIP_TRY(hipGetLastError());
+  const int chunks = (lcap + wg::kMoSampleChunk - 1) / wg::kMoSampleChunk;
+  hipLaunchKernelGGL(wg::wg_morisawa_sample_kernel, dim3((B + 63) / 64, chunks), dim3(64), 0, st, B, smax, static_cast<const double *>(blocks), status, clock, lcap, O, length);
+  HIP_TRY(hipGetLastError());
+  return slot_mark(ctx->mo_order, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+int wg_morisawa_solve_dev_ctx(wg_ctx_t *ctx, const wg_morisawa_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, const double *com0, void *blocks, int *status, void *hip_stream) {
+  return mo_solve_launch<false>(ctx, model, B, smax, steps, n_steps, init_feet, com0, blocks, status, reinterpret_cast<hipStream_t>(hip_stream));
+}
+int wg_morisawa_solve_fleet_dev_ctx(wg_ctx_t *ctx, const wg_morisawa_model_t *models, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, const double *com0, void *blocks, int *status, void *hip_stream) {
+  return mo_solve_launch<true>(ctx, models, B, smax, steps, n_steps, init_feet, com0, blocks, status, reinterpret_cast<hipStream_t>(hip_stream));
+}
+int wg_morisawa_sample_dev_ctx(wg_ctx_t *ctx, int B, int smax, const void *blocks, const int *status, double t_start, double T, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *com_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream) {
+  const wg::MoOut O{zmp_x_tm, zmp_y_tm, com_tm, left_tm, right_tm, left_type_tm, right_type_tm};
+  return mo_sample_launch(ctx, B, smax, blocks, status, t_start, T, lcap, O, length, reinterpret_cast<hipStream_t>(hip_stream));
+}
+// solve, then sample, on the caller's stream: the stream orders them, the host does not wait
+int wg_morisawa_walk_dev_ctx(wg_ctx_t *ctx, const wg_morisawa_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, const double *com0, void *blocks, int *status, double t_start, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *com_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream) {
+  if (int rc = mo_solve_check(model, B, smax, steps, n_steps, init_feet, com0, blocks, status)) return rc;
+  if (int rc = mo_sample_check(B, smax, blocks, t_start, model->T, lcap)) return rc;
+  if (int rc = wg_morisawa_solve_dev_ctx(ctx, model, B, smax, steps, n_steps, init_feet, com0, blocks, status, hip_stream)) return rc;
+  return wg_morisawa_sample_dev_ctx(ctx, B, smax, blocks, status, t_start, model->T, lcap, zmp_x_tm, zmp_y_tm, com_tm, left_tm, left_type_tm, right_tm, right_type_tm, length, hip_stream);
+}
+int wg_morisawa_walk_fleet_dev_ctx(wg_ctx_t *ctx, const wg_morisawa_model_t *models, double T, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, const double *com0, void *blocks, int *status, double t_start, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *com_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream) {
+  if (int rc = mo_solve_check(models, B, smax, steps, n_steps, init_feet, com0, blocks, status)) return rc;
+  if (int rc = mo_sample_check(B, smax, blocks, t_start, T, lcap)) return rc;
+  if (int rc = wg_morisawa_solve_fleet_dev_ctx(ctx, models, B, smax, steps, n_steps, init_feet, com0, blocks, status, hip_stream)) return rc;
+  return wg_morisawa_sample_dev_ctx(ctx, B, smax, blocks, status, t_start, T, lcap, zmp_x_tm, zmp_y_tm, com_tm, left_tm, left_type_tm, right_tm, right_type_tm, length, hip_stream);
+}
+int wg_morisawa_solve_dev(const wg_morisawa_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, const double *com0, void *blocks, int *status, void *hip_stream) { return on_default(&wg_morisawa_solve_dev_ctx, model, B, smax, steps, n_steps, init_feet, com0, blocks, status, hip_stream); }
+int wg_morisawa_solve_fleet_dev(const wg_morisawa_model_t *models, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, const double *com0, void *blocks, int *status, void *hip_stream) { return on_default(&wg_morisawa_solve_fleet_dev_ctx, models, B, smax, steps, n_steps, init_feet, com0, blocks, status, hip_stream); }
+int wg_morisawa_sample_dev(int B, int smax, const void *blocks, const int *status, double t_start, double T, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *com_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream) { return on_default(&wg_morisawa_sample_dev_ctx, B, smax, blocks, status, t_start, T, lcap, zmp_x_tm, zmp_y_tm, com_tm, left_tm, left_type_tm, right_tm, right_type_tm, length, hip_stream); }
+int wg_morisawa_walk_dev(const wg_morisawa_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, const double *com0, void *blocks, int *status, double t_start, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *com_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream) { return on_default(&wg_morisawa_walk_dev_ctx, model, B, smax, steps, n_steps, init_feet, com0, blocks, status, t_start, lcap, zmp_x_tm, zmp_y_tm, com_tm, left_tm, left_type_tm, right_tm, right_type_tm, length, hip_stream); }
+int wg_morisawa_walk_fleet_dev(const wg_morisawa_model_t *models, double T, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, const double *com0, void *blocks, int *status, double t_start, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *com_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream) { return on_default(&wg_morisawa_walk_fleet_dev_ctx, models, T, B, smax, steps, n_steps, init_feet, com0, blocks, status, t_start, lcap, zmp_x_tm, zmp_y_tm, com_tm, left_tm, left_type_tm, right_tm, right_type_tm, length, hip_stream); }
 
 }  // extern "C"

@@ -1,0 +1,161 @@
+// morisawa_fleet.cpp -- Morisawa-2007 analytic walks for a fleet from plain C++ through the C ABI (no Python, no PyTorch): B step
+// sequences in device memory -> wg_morisawa_walk_dev (one linear system per gait solved in a wavefront, then CoM, ZMP and both
+// feet sampled on the control loop's clock), nothing leaves the device in between.  Gait 0 walks TestMorisawa2007's short
+// straight walk where --steps allows it; gait 0 and gait B - 1 are checked against the host twins (wg_morisawa_solve +
+// wg_morisawa_sample on the same input, bit for bit); the others vary step length, heading and first foot.
+//
+// With --heights LO:HI gait b walks at its own CoM height, LO + (HI - LO) b / (B - 1), and with its own support times (a table of
+// multiples of T): a model per gait through wg_morisawa_walk_fleet_dev.
+//
+// Prints a checksum (FNV-1a, 64 bit, over the gaits' checksums of their own rows of CoM, ZMP and feet) and the milliseconds per fleet.
+//
+//   morisawa_fleet [--batch B] [--steps S] [--heights LO:HI]
+#include <chrono>
+#include <cstdlib>
+#include <random>
+
+#include "wg_fleet.hpp"
+
+using wg_fleet::dev_alloc;
+using wg_fleet::dev_upload;
+
+int main(int argc, char **argv) {
+  int B = 4096, S = 7;
+  bool heights = false;
+  double h_lo = 0.7116911, h_hi = 0.7116911;
+  for (int i = 1; i < argc; ++i) {
+    if (!strcmp(argv[i], "--batch") && i + 1 < argc) B = atoi(argv[++i]);
+    else if (!strcmp(argv[i], "--steps") && i + 1 < argc) S = atoi(argv[++i]);
+    else if (!strcmp(argv[i], "--heights") && i + 1 < argc) {
+      heights = sscanf(argv[++i], "%lf:%lf", &h_lo, &h_hi) == 2;
+      if (!heights || !(h_lo > 0.0) || !(h_hi >= h_lo) || !(h_hi < 1e3)) { fprintf(stderr, "FAILED: need --heights LO:HI with 0 < LO <= HI\n"); return 1; }
+    }
+  }
+  if (B < 1 || S < 2 || S > WG_MORISAWA_MAX_STEPS) { fprintf(stderr, "FAILED: need B >= 1, 2 <= steps <= %d\n", WG_MORISAWA_MAX_STEPS); return 1; }
+  CHECK_WG(wg_init(0));
+  wg_morisawa_model_t base;
+  wg_morisawa_defaults(&base);                                // 5 ms, 0.78 / 0.02 s supports, 0.07 m step height
+  std::vector<wg_morisawa_model_t> models(B, base);
+  std::vector<wg_rel_step_t> steps((size_t)B * S);
+  std::vector<int> n_steps(B, S);
+  std::vector<double> feet((size_t)B * 6), com0((size_t)B * 3);
+  static const int single_ticks[] = {140, 156, 160, 120}, double_ticks[] = {4, 8, 12, 20};
+  for (int g = 0; g < B; ++g) {
+    std::mt19937_64 rng(20070 + g);
+    std::uniform_real_distribution<double> len(0.1, 0.25), turn(-5.0, 5.0);
+    double side = (g & 1) ? 1.0 : -1.0;
+    for (int i = 0; i < S; ++i) {
+      wg_rel_step_t &s = steps[(size_t)g * S + i];
+      memset(&s, 0, sizeof s);
+      const bool ends = i == 0 || i == S - 1;
+      s.sx = ends ? 0.0 : (g == 0 ? 0.2 : len(rng));
+      s.sy = side * (i == 0 ? 0.105 : 0.19);
+      s.theta = (ends || g == 0) ? 0.0 : turn(rng);
+      s.step_type = 1;
+      side = -side;
+    }
+    const double f[6] = {0.0, 0.09, 0.0, 0.0, -0.09, 0.0};
+    memcpy(&feet[(size_t)g * 6], f, sizeof f);
+    com0[(size_t)g * 3 + 0] = 0.0316054587;
+    com0[(size_t)g * 3 + 1] = 0.0;
+    com0[(size_t)g * 3 + 2] = heights && B > 1 ? h_lo + (h_hi - h_lo) * g / (B - 1) : h_lo;
+    if (heights) {
+      models[g].t_single = single_ticks[g % 4] * base.T;
+      models[g].t_double = double_ticks[(g / 4) % 4] * base.T;
+    }
+  }
+  const double t_start = 2.0 * base.t_single;                 // the reference's queue starts there
+  std::vector<int> len_g(B);
+  int L = 0;
+  for (int g = 0; g < B; ++g) {
+    len_g[g] = wg_morisawa_length(&models[g], S, t_start);
+    if (len_g[g] < 1) { fprintf(stderr, "FAILED: gait %d has %d samples\n", g, len_g[g]); return 1; }
+    L = len_g[g] > L ? len_g[g] : L;
+  }
+  const size_t bb = wg_morisawa_block_bytes(S);
+
+  wg_rel_step_t *d_steps; int *d_ns, *d_status, *d_len, *d_lt, *d_rt; double *d_feet, *d_com0, *d_zx, *d_zy, *d_com, *d_left, *d_right;
+  wg_morisawa_model_t *d_models; void *d_blocks;
+  CHECK_HIP(dev_upload(&d_steps, steps));
+  CHECK_HIP(dev_upload(&d_ns, n_steps));
+  CHECK_HIP(dev_upload(&d_feet, feet));
+  CHECK_HIP(dev_upload(&d_com0, com0));
+  CHECK_HIP(dev_upload(&d_models, models));
+  CHECK_HIP(hipMalloc(&d_blocks, bb * B));
+  CHECK_HIP(dev_alloc(&d_status, B));
+  CHECK_HIP(dev_alloc(&d_len, B));
+  CHECK_HIP(dev_alloc(&d_zx, (size_t)L * B));
+  CHECK_HIP(dev_alloc(&d_zy, (size_t)L * B));
+  CHECK_HIP(dev_alloc(&d_com, (size_t)L * 4 * B));
+  CHECK_HIP(dev_alloc(&d_left, (size_t)L * 6 * B));
+  CHECK_HIP(dev_alloc(&d_right, (size_t)L * 6 * B));
+  CHECK_HIP(dev_alloc(&d_lt, (size_t)L * B));
+  CHECK_HIP(dev_alloc(&d_rt, (size_t)L * B));
+  hipStream_t st;
+  CHECK_HIP(hipStreamCreate(&st));
+  double sec = 0.0;
+  for (int rep = 0; rep < 2; ++rep) {                          // the second pass is the timed one
+    CHECK_HIP(hipStreamSynchronize(st));
+    const auto t0 = std::chrono::steady_clock::now();
+    if (heights)
+      CHECK_WG(wg_morisawa_walk_fleet_dev(d_models, base.T, B, S, d_steps, d_ns, d_feet, d_com0, d_blocks, d_status, t_start, L, d_zx, d_zy,
+                                          d_com, d_left, d_lt, d_right, d_rt, d_len, st));
+    else
+      CHECK_WG(wg_morisawa_walk_dev(&base, B, S, d_steps, d_ns, d_feet, d_com0, d_blocks, d_status, t_start, L, d_zx, d_zy, d_com, d_left,
+                                    d_lt, d_right, d_rt, d_len, st));
+    CHECK_HIP(hipStreamSynchronize(st));
+    sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  }
+  std::vector<int> status(B), len_h(B);
+  CHECK_HIP(hipMemcpy(status.data(), d_status, sizeof(int) * B, hipMemcpyDeviceToHost));
+  CHECK_HIP(hipMemcpy(len_h.data(), d_len, sizeof(int) * B, hipMemcpyDeviceToHost));
+  for (int g = 0; g < B; ++g) {
+    if (status[g] != WG_OK) { fprintf(stderr, "FAILED: gait %d: status %d\n", g, status[g]); return 1; }
+    if (len_h[g] != len_g[g]) { fprintf(stderr, "FAILED: gait %d has %d samples, not %d\n", g, len_h[g], len_g[g]); return 1; }
+  }
+  std::vector<double> zx((size_t)L * B), zy((size_t)L * B), com((size_t)L * 4 * B), left((size_t)L * 6 * B), right((size_t)L * 6 * B);
+  CHECK_HIP(hipMemcpy(zx.data(), d_zx, sizeof(double) * zx.size(), hipMemcpyDeviceToHost));
+  CHECK_HIP(hipMemcpy(zy.data(), d_zy, sizeof(double) * zy.size(), hipMemcpyDeviceToHost));
+  CHECK_HIP(hipMemcpy(com.data(), d_com, sizeof(double) * com.size(), hipMemcpyDeviceToHost));
+  CHECK_HIP(hipMemcpy(left.data(), d_left, sizeof(double) * left.size(), hipMemcpyDeviceToHost));
+  CHECK_HIP(hipMemcpy(right.data(), d_right, sizeof(double) * right.size(), hipMemcpyDeviceToHost));
+  // a gait against the host twins, one gait at a time
+  auto check_gait = [&](int g) -> int {
+    std::vector<double> blk(bb / sizeof(double)), hzx(L), hzy(L), hcom((size_t)L * 4), hl((size_t)L * 6), hr((size_t)L * 6);
+    int hs = 0, hlen = 0;
+    CHECK_WG(wg_morisawa_solve(&models[g], 1, S, &steps[(size_t)g * S], &n_steps[g], &feet[(size_t)g * 6], &com0[(size_t)g * 3], blk.data(), &hs));
+    CHECK_WG(wg_morisawa_sample(1, S, blk.data(), &hs, t_start, base.T, L, hzx.data(), hzy.data(), hcom.data(), hl.data(), nullptr, hr.data(),
+                                nullptr, &hlen));
+    bool same = hs == WG_OK && hlen == len_g[g];
+    for (int l = 0; same && l < L; ++l) {
+      same = zx[(size_t)l * B + g] == hzx[l] && zy[(size_t)l * B + g] == hzy[l];
+      for (int c = 0; c < 4; ++c) same = same && com[((size_t)l * 4 + c) * B + g] == hcom[(size_t)l * 4 + c];
+      for (int c = 0; c < 6; ++c) same = same && left[((size_t)l * 6 + c) * B + g] == hl[(size_t)l * 6 + c] && right[((size_t)l * 6 + c) * B + g] == hr[(size_t)l * 6 + c];
+    }
+    if (!same) { fprintf(stderr, "FAILED: device walk of gait %d differs from the host twins\n", g); return 1; }
+    return 0;
+  };
+  if (check_gait(0) || (B > 1 && check_gait(B - 1))) return 1;
+  std::vector<double> own;                                    // a gait's own rows; the checksum is over the gaits' checksums, in order
+  std::vector<unsigned long long> sums(B);
+  double far = 0.0;
+  for (int g = 0; g < B; ++g) {
+    own.clear();
+    for (int l = 0; l < len_g[g]; ++l) {
+      own.push_back(zx[(size_t)l * B + g]);
+      own.push_back(zy[(size_t)l * B + g]);
+      for (int c = 0; c < 4; ++c) own.push_back(com[((size_t)l * 4 + c) * B + g]);
+      for (int c = 0; c < 6; ++c) { own.push_back(left[((size_t)l * 6 + c) * B + g]); own.push_back(right[((size_t)l * 6 + c) * B + g]); }
+    }
+    sums[g] = wg_fleet::fnv1a64(own.data(), own.size() * sizeof(double));
+    const double x = com[((size_t)(len_g[g] - 1) * 4) * B + g];
+    far = x > far ? x : far;
+  }
+  const unsigned long long sum = wg_fleet::fnv1a64(sums.data(), sums.size() * sizeof(sums[0]));
+  if (heights) printf("morisawa_fleet: CoM heights %.4f .. %.4f m and support times per gait (a model per gait)\n", h_lo, h_hi);
+  printf("morisawa_fleet: %d analytic walks of %d steps (up to %d samples) in %.2f ms = %.0f walks/s; gait 0 ends at x = %.4f m (%d samples), "
+         "farthest %.2f m; gaits 0 and %d == host twins; checksum %016llx\n", B, S, L, sec * 1e3, B / sec,
+         com[((size_t)(len_g[0] - 1) * 4) * B + 0], len_g[0], far, B - 1, sum);
+  wg_shutdown();
+  return 0;
+}

@@ -200,6 +200,24 @@ def lib():
             _lib.wg_overlap_serialised.restype = C.c_longlong
         if hasattr(_lib, "wg_mpc_reserve"):                 # absent from older experiment builds (WG_LIB_PATH, A/B runs)
             _lib.wg_mpc_reserve.argtypes = [C.c_int]
+        if hasattr(_lib, "wg_morisawa_solve_dev"):           # absent from older experiment builds (WG_LIB_PATH, A/B runs)
+            mo_solve = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6
+            mo_sample = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int] + [C.c_void_p] * 8
+            _lib.wg_morisawa_defaults.argtypes = [C.c_void_p]
+            _lib.wg_morisawa_block_bytes.argtypes = [C.c_int]
+            _lib.wg_morisawa_block_bytes.restype = C.c_size_t
+            _lib.wg_morisawa_block_unpack.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+            _lib.wg_morisawa_length.argtypes = [C.c_void_p, C.c_int, C.c_double]
+            _lib.wg_morisawa_coshsinh.argtypes = [C.c_double, C.c_void_p, C.c_void_p]
+            _lib.wg_morisawa_system.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6
+            _lib.wg_morisawa_solve.argtypes = mo_solve
+            _lib.wg_morisawa_solve_fleet.argtypes = mo_solve
+            _lib.wg_morisawa_sample.argtypes = mo_sample
+            _lib.wg_morisawa_solve_dev.argtypes = mo_solve + [C.c_void_p]
+            _lib.wg_morisawa_solve_fleet_dev.argtypes = mo_solve + [C.c_void_p]
+            _lib.wg_morisawa_sample_dev.argtypes = mo_sample + [C.c_void_p]
+            _lib.wg_morisawa_walk_dev.argtypes = mo_solve + [C.c_double, C.c_int] + [C.c_void_p] * 9
+            _lib.wg_morisawa_walk_fleet_dev.argtypes = [C.c_void_p, C.c_double] + mo_solve[1:] + [C.c_double, C.c_int] + [C.c_void_p] * 9
         for name in CTX_ENTRY_POINTS:
             if not hasattr(_lib, name):
                 continue
@@ -224,7 +242,9 @@ CTX_ENTRY_POINTS = ("wg_set_overlap_strict", "wg_overlap_serialised", "wg_qp_sol
                     "wg_dimitrov_tick_fleet_dev", "wg_dimitrov_walk_fleet_dev", "wg_dimitrov_follow_fleet_dev",
                     "wg_mpc_blocks_batch", "wg_mpc_blocks_batch_dev", "wg_mpc_tick_fleet_dev", "wg_mpc_run_fleet_dev",
                     "wg_zmpdisc_full_fleet_dev", "wg_zmpdisc_begin_fleet_dev", "wg_zmpdisc_append_fleet_dev", "wg_zmpdisc_end_fleet_dev",
-                    "wg_steps_plan_fleet_dev", "wg_foot_constraints_fleet_dev", "wg_foot_constraints_append_fleet_dev")
+                    "wg_steps_plan_fleet_dev", "wg_foot_constraints_fleet_dev", "wg_foot_constraints_append_fleet_dev",
+                    "wg_morisawa_solve_dev", "wg_morisawa_solve_fleet_dev", "wg_morisawa_sample_dev", "wg_morisawa_walk_dev",
+                    "wg_morisawa_walk_fleet_dev")
 
 
 class Context:
@@ -1182,3 +1202,141 @@ def gramian_batch(N, T, h, alpha, beta, gamma, precision=GRAMIAN_F64):
     Qb = np.zeros((B, N, N))
     _check(lib().wg_gramian_batch(B, int(N), _hp(T), _hp(h), alpha, beta, gamma, int(precision), _hp(Qb)))
     return Qb
+
+
+# ---- Morisawa-2007 analytic walks: CoM, ZMP and feet of a step sequence in closed form (include/wg_mpc.h) ----
+MORISAWA_MAX_STEPS = 14
+MORISAWA_BAD_INPUT, MORISAWA_CAPACITY, MORISAWA_SINGULAR = -1, -2, -3
+MORISAWA_OUTPUTS = ("zmp_x", "zmp_y", "com", "left", "left_type", "right", "right_type")
+
+
+class MorisawaModel(C.Structure):       # wg_morisawa_model_t
+    _fields_ = [(k, C.c_double) for k in ("T", "t_single", "t_double", "step_height", "omega")]
+
+
+class MorisawaView(C.Structure):        # wg_morisawa_view_t
+    _fields_ = [(k, C.c_int) for k in ("n_steps", "n_int", "n", "smax")] + [("com_height", C.c_double), ("t_total", C.c_double)] + \
+               [(k, _dp) for k in ("dT", "omega", "tref", "zmp_x", "cog_x", "zmp_y", "cog_y", "Vx", "Wx", "Vy", "Wy", "left", "right")] + \
+               [("left_type", _ip), ("right_type", _ip)] + \
+               [(k, _dp) for k in ("profile_x", "profile_y", "support", "wx", "wy", "yx", "yy")] + \
+               [("piv", _ip), ("lu", _dp), ("lu_pitch", C.c_int), ("pad_", C.c_int)]
+
+
+def morisawa_defaults():
+    m = MorisawaModel()
+    lib().wg_morisawa_defaults(C.byref(m))
+    return m
+
+
+def morisawa_block_bytes(smax):
+    return int(lib().wg_morisawa_block_bytes(int(smax)))
+
+
+def morisawa_length(model, n_steps, t_start):
+    return int(lib().wg_morisawa_length(C.byref(model), int(n_steps), float(t_start)))
+
+
+def morisawa_coshsinh(x):
+    c, s = C.c_double(), C.c_double()
+    _check(lib().wg_morisawa_coshsinh(float(x), C.byref(c), C.byref(s)))
+    return c.value, s.value
+
+
+def morisawa_system(model, steps, init_feet, com0):
+    """Z [n, n], w of x, w of y of one gait before the elimination (host arithmetic); steps: (RelStep * S)"""
+    S = len(steps)
+    n = 4 * S + 8
+    Z, wx, wy = np.zeros((n, n)), np.zeros(n), np.zeros(n)
+    feet, com = np.ascontiguousarray(init_feet, dtype=np.float64), np.ascontiguousarray(com0, dtype=np.float64)
+    rc = lib().wg_morisawa_system(C.byref(model), S, C.addressof(steps), _hp(feet), _hp(com), _hp(Z), _hp(wx), _hp(wy))
+    if rc != n:
+        raise WgError(f"wg_morisawa_system: {rc}")
+    return Z, wx, wy
+
+
+def morisawa_solve(model, steps, n_steps, init_feet, com0, smax, blocks=None):
+    """Host twin.  model: one MorisawaModel, or (MorisawaModel * B) for a model per gait; steps: (RelStep * (B*smax)); n_steps [B];
+    init_feet [B, 6]; com0 [B, 3].  Returns (blocks [B, words] float64 -- `blocks` itself if given -- , status [B])."""
+    n_steps = np.ascontiguousarray(n_steps, dtype=np.int32); B = n_steps.shape[0]
+    init_feet = np.ascontiguousarray(init_feet, dtype=np.float64); com0 = np.ascontiguousarray(com0, dtype=np.float64)
+    assert init_feet.shape == (B, 6) and com0.shape == (B, 3) and len(steps) == B * smax
+    if blocks is None:
+        blocks = np.zeros((B, morisawa_block_bytes(smax) // 8))
+    status = np.zeros(B, np.int32)
+    fleet = not isinstance(model, MorisawaModel)
+    fn = lib().wg_morisawa_solve_fleet if fleet else lib().wg_morisawa_solve
+    _check(fn(C.addressof(model), B, int(smax), C.addressof(steps), _hp(n_steps), _hp(init_feet), _hp(com0), _hp(blocks), _hp(status)))
+    return blocks, status
+
+
+def morisawa_view(block, smax):
+    """dict of numpy arrays (copies) from one block: what wg_morisawa_block_unpack points at, cut to the gait's own sizes"""
+    block = np.ascontiguousarray(block, dtype=np.float64)
+    v = MorisawaView()
+    rc = lib().wg_morisawa_block_unpack(_hp(block), int(smax), C.byref(v))
+    if rc != 0:
+        raise WgError(f"wg_morisawa_block_unpack: {rc}")
+    I, n, S = v.n_int, v.n, v.n_steps
+    arr = lambda p, *shape: np.ctypeslib.as_array(p, shape=shape).copy()  # noqa: E731
+    r = dict(n_steps=S, n_int=I, n=n, smax=v.smax, com_height=v.com_height, t_total=v.t_total)
+    for k in ("dT", "omega", "tref", "Vx", "Wx", "Vy", "Wy", "profile_x", "profile_y", "left_type", "right_type"):
+        r[k] = arr(getattr(v, k), I)
+    for k in ("zmp_x", "cog_x", "zmp_y", "cog_y"):
+        r[k] = arr(getattr(v, k), I, 5)
+    for k in ("left", "right"):
+        r[k] = arr(getattr(v, k), I, 6, 6)
+    r["support"] = arr(v.support, S, 3)
+    for k in ("wx", "wy", "yx", "yy", "piv"):
+        r[k] = arr(getattr(v, k), n)
+    r["lu"] = arr(v.lu, v.lu_pitch, v.lu_pitch)[:n, :n]
+    return r
+
+
+def morisawa_sample(blocks, status, smax, t_start, T, lcap, want=MORISAWA_OUTPUTS, into=None):
+    """Host twin of the sampler.  Returns dict(zmp_x, zmp_y [lcap, B], com [lcap, 4, B], left, right [lcap, 6, B], left_type,
+    right_type [lcap, B] int32, length [B]) with the outputs named in `want`; `into`: arrays to write into instead of zeros."""
+    blocks = np.ascontiguousarray(blocks, dtype=np.float64); B = blocks.shape[0]
+    shapes = dict(zmp_x=(lcap, B), zmp_y=(lcap, B), com=(lcap, 4, B), left=(lcap, 6, B), right=(lcap, 6, B), left_type=(lcap, B),
+                  right_type=(lcap, B))
+    r = {}
+    for k in want:
+        r[k] = into[k] if into is not None and k in into else np.zeros(shapes[k], np.int32 if k.endswith("type") else np.float64)
+        assert r[k].shape == shapes[k] and r[k].flags.c_contiguous
+    r["length"] = into["length"] if into is not None and "length" in into else np.zeros(B, np.int32)
+    st = None if status is None else np.ascontiguousarray(status, dtype=np.int32)
+    _check(lib().wg_morisawa_sample(B, int(smax), _hp(blocks), _hp(st), float(t_start), float(T), int(lcap),
+                                    *[_hp(r.get(k)) for k in MORISAWA_OUTPUTS], _hp(r["length"])))
+    return r
+
+
+def _mo_outs(outs):
+    assert set(outs) <= set(MORISAWA_OUTPUTS), outs
+    return [outs.get(k) for k in MORISAWA_OUTPUTS]
+
+
+def morisawa_solve_dev(model, B, smax, steps_ptr, n_steps_ptr, init_feet_ptr, com0_ptr, blocks_ptr, status_ptr, stream=None):
+    """every pointer a device pointer; `model`: a MorisawaModel (host), or a device pointer to B of them (the fleet form)"""
+    if isinstance(model, MorisawaModel):
+        _check(lib().wg_morisawa_solve_dev(C.addressof(model), int(B), int(smax), steps_ptr, n_steps_ptr, init_feet_ptr, com0_ptr,
+                                           blocks_ptr, status_ptr, stream))
+    else:
+        _check(lib().wg_morisawa_solve_fleet_dev(model, int(B), int(smax), steps_ptr, n_steps_ptr, init_feet_ptr, com0_ptr,
+                                                 blocks_ptr, status_ptr, stream))
+
+
+def morisawa_sample_dev(B, smax, blocks_ptr, status_ptr, t_start, T, lcap, outs, length_ptr=None, stream=None):
+    """`outs`: device pointers by name (MORISAWA_OUTPUTS, time-major), absent = not wanted"""
+    _check(lib().wg_morisawa_sample_dev(int(B), int(smax), blocks_ptr, status_ptr, float(t_start), float(T), int(lcap),
+                                        *_mo_outs(outs), length_ptr, stream))
+
+
+def morisawa_walk_dev(model, B, smax, steps_ptr, n_steps_ptr, init_feet_ptr, com0_ptr, blocks_ptr, status_ptr, t_start, lcap, outs,
+                      length_ptr=None, stream=None, T=None):
+    """solve and sample on one stream; `model` as in morisawa_solve_dev, the fleet form needs the common sampling period T"""
+    if isinstance(model, MorisawaModel):
+        _check(lib().wg_morisawa_walk_dev(C.addressof(model), int(B), int(smax), steps_ptr, n_steps_ptr, init_feet_ptr, com0_ptr,
+                                          blocks_ptr, status_ptr, float(t_start), int(lcap), *_mo_outs(outs), length_ptr, stream))
+    else:
+        _check(lib().wg_morisawa_walk_fleet_dev(model, float(T), int(B), int(smax), steps_ptr, n_steps_ptr, init_feet_ptr, com0_ptr,
+                                                blocks_ptr, status_ptr, float(t_start), int(lcap), *_mo_outs(outs), length_ptr,
+                                                stream))
