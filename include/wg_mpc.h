@@ -1202,177 +1202,6 @@ int wg_gramian_batch(int B, int N, const double *T, const double *h, double alph
 int wg_gramian_batch_dev(int B, int N, const double *T, const double *h, double alpha, double beta, double gamma,
                          int precision, double *Qb, void *hip_stream);
 
-/* The context forms of the entry points above (same arguments after the context, same semantics). ---------------------- */
-int wg_qp_solve_batch_dev_ctx(wg_ctx_t *ctx, int B, int nmax, int mmax, const int *n, const int *m, const int *me,
-                              const double *C, const double *d, const double *A, const double *b, const double *xl,
-                              const double *xu, double eps, double *x, double *u, int *ifail, int *n_iter, int *iact,
-                              int *nact, int *hist, int hist_cap, int *hist_len, void *hip_stream);
-int wg_qp_solve_batch_ctx(wg_ctx_t *ctx, int B, int nmax, int mmax, const int *n, const int *m, const int *me,
-                          const double *C, const double *d, const double *A, const double *b, const double *xl,
-                          const double *xu, double eps, double *x, double *u, int *ifail, int *n_iter, int *iact,
-                          int *nact, int *hist, int hist_cap, int *hist_len);
-int wg_set_overlap_strict_ctx(wg_ctx_t *ctx, int on);
-long long wg_overlap_serialised_ctx(wg_ctx_t *ctx);
-int wg_mpc_configure_ctx(wg_ctx_t *ctx, const wg_model_t *model);
-size_t wg_mpc_tick_lds_bytes_ctx(wg_ctx_t *ctx);
-int wg_mpc_reserve_ctx(wg_ctx_t *ctx, int max_gaits);
-int wg_mpc_tick_batch_dev_ctx(wg_ctx_t *ctx, int B, wg_gait_state_t *states, wg_tick_out_t *outs, int *diag,
-                              int advance_calls, int *hist, int hist_cap, int *hist_len, void *hip_stream);
-int wg_mpc_run_batch_dev_ctx(wg_ctx_t *ctx, int B, wg_gait_state_t *states, int n_ticks, int advance_calls,
-                             wg_tick_out_t *outs, int *diag, void *hip_stream);
-int wg_mpc_run_sched_dev_ctx(wg_ctx_t *ctx, int B, wg_gait_state_t *states, int n_ticks, int advance_calls,
-                             const double *vref_sched, int period, wg_tick_out_t *outs, int *diag, void *hip_stream);
-int wg_mpc_tick_batch_ctx(wg_ctx_t *ctx, int B, wg_gait_state_t *states, wg_tick_out_t *outs, int *diag,
-                          int advance_calls, int *hist, int hist_cap, int *hist_len);
-int wg_mpc_set_velref_dev_ctx(wg_ctx_t *ctx, int B, wg_gait_state_t *states, const double *vref, void *hip_stream);
-int wg_mpc_tick_pinned_ctx(wg_ctx_t *ctx, wg_gait_state_t *state, wg_tick_out_t *out, int *diag, int advance_calls);
-int wg_mpc_assemble_batch_ctx(wg_ctx_t *ctx, int B, const wg_gait_state_t *states, int advance_calls, int nmax, int mmax,
-                              double *C, double *d, double *A, double *b, double *xl, double *xu, int *n, int *m);
-int wg_mpc_assemble_batch_dev_ctx(wg_ctx_t *ctx, int B, const wg_gait_state_t *states, int advance_calls, int nmax, int mmax,
-                                  double *C, double *d, double *A, double *b, double *xl, double *xu, int *n, int *m,
-                                  void *hip_stream);
-int wg_pldp_configure_ctx(wg_ctx_t *ctx, int N, const double *iPu, const double *Px, const double *Pu);
-int wg_pldp_solve_batch_dev_ctx(wg_ctx_t *ctx, int B, int mcap, const int *m, const double *D, const double *A,
-                                const double *b, const double *zmpref, const double *xkyk, const int *similar,
-                                const int *n_removed, const int *starting, int max_iter, wg_pldp_state_t *states,
-                                double *X, int *ret, int *n_iter, int *active, int *n_active, void *hip_stream);
-int wg_pldp_solve_batch_ctx(wg_ctx_t *ctx, int B, int mcap, const int *m, const double *D, const double *A,
-                            const double *b, const double *zmpref, const double *xkyk, const int *similar,
-                            const int *n_removed, const int *starting, int max_iter, wg_pldp_state_t *states,
-                            double *X, int *ret, int *n_iter, int *active, int *n_active);
-int wg_dimitrov_configure_ctx(wg_ctx_t *ctx, const wg_dimitrov_model_t *model);
-int wg_dimitrov_get_constants_ctx(wg_ctx_t *ctx, double *iLQ, double *OptB, double *OptC, double *Pu, double *iPu,
-                                  double *Px);
-int wg_dimitrov_get_qld_constants_ctx(wg_ctx_t *ctx, double *Q, double *OptB, double *OptC, double *PuT);
-int wg_dimitrov_tick_batch_dev_ctx(wg_ctx_t *ctx, int B, const wg_zmp_polytope_t *polys, wg_dimitrov_state_t *states,
-                                   wg_dimitrov_out_t *outs, int max_iter, void *hip_stream);
-int wg_dimitrov_tick_batch_ctx(wg_ctx_t *ctx, int B, const wg_zmp_polytope_t *polys, wg_dimitrov_state_t *states,
-                               wg_dimitrov_out_t *outs, int max_iter);
-int wg_foot_constraints_batch_dev_ctx(wg_ctx_t *ctx, int B, int lcap, const int *length, const double *time,
-                                      const double *left_tm, const int *left_type_tm, const double *right_tm, double sole_w,
-                                      double sole_h, double constraint_x, double constraint_y, int qcap,
-                                      wg_zmp_polytope_t *queues, double *t_start, double *t_end, int *count, void *hip_stream);
-int wg_foot_constraints_append_dev_ctx(wg_ctx_t *ctx, int B, int lcap, int first_sample, int *done, const int *length,
-                                       const double *time, const double *left_tm, const int *left_type_tm,
-                                       const double *right_tm, double sole_w, double sole_h, double constraint_x,
-                                       double constraint_y, int qcap, wg_zmp_polytope_t *queues, double *t_start,
-                                       double *t_end, int *count, void *hip_stream);
-double wg_dimitrov_walk_time_ctx(wg_ctx_t *ctx, double t0, int n_ticks);
-int wg_dimitrov_walk_safe_ticks_ctx(wg_ctx_t *ctx, double t0, double t_have);
-int wg_dimitrov_select_polys_dev_ctx(wg_ctx_t *ctx, int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start,
-                                     const double *t_end, const int *count, double t0, wg_zmp_polytope_t *polys, int *ran_out,
-                                     void *hip_stream);
-int wg_dimitrov_walk_dev_ctx(wg_ctx_t *ctx, int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start,
-                             const double *t_end, const int *count, double t0, int n_ticks, wg_dimitrov_state_t *states,
-                             wg_dimitrov_out_t *outs, int *ran_out, int max_iter, void *hip_stream);
-int wg_dimitrov_follow_dev_ctx(wg_ctx_t *ctx, int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start,
-                               const double *t_end, const int *count, int lcap, const double *time, const int *have,
-                               const wg_zmpdisc_state_t *walk, int flags, double *clock, int *ticks, int tick_cap,
-                               int max_ticks, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int *ran_out, int max_iter,
-                               void *hip_stream);
-int wg_preview_configure_ctx(wg_ctx_t *ctx, const wg_preview_gains_t *gains, const double *F);
-int wg_preview_window_ctx(wg_ctx_t *ctx);
-int wg_preview_run_batch_dev_ctx(wg_ctx_t *ctx, int B, int L, const double *zmp_x_tm, const double *zmp_y_tm,
-                                 double *state, double *com_tm, double *zmp2_tm, int simulation, void *hip_stream);
-int wg_preview_follow_dev_ctx(wg_ctx_t *ctx, int B, int lcap, const int *length, int *done, const double *zmp_x_tm,
-                              const double *zmp_y_tm, double *state, double *com_tm, double *zmp2_tm, int simulation,
-                              void *hip_stream);
-int wg_preview_run_batch_ctx(wg_ctx_t *ctx, int B, int L, const double *zmp_x, const double *zmp_y, double *state,
-                             double *com, double *zmp2, int simulation);
-int wg_gramian_batch_dev_ctx(wg_ctx_t *ctx, int B, int N, const double *T, const double *h, double alpha,
-                             double beta, double gamma, int precision, double *Qb, void *hip_stream);
-int wg_gramian_batch_ctx(wg_ctx_t *ctx, int B, int N, const double *T, const double *h, double alpha, double beta,
-                         double gamma, int precision, double *Qb);
-int wg_zmpdisc_batch_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_model_t *model, int B, int smax,
-                             const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap,
-                             double *zmp_x_tm, double *zmp_y_tm, int *length, void *hip_stream);
-int wg_zmpdisc_full_batch_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_model_t *model, int B, int smax,
-                                  const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap,
-                                  double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm,
-                                  double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm,
-                                  int *length, void *hip_stream);
-int wg_zmpdisc_batch_ctx(wg_ctx_t *ctx, const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps,
-                         const int *n_steps, const double *init_feet, int lcap, double *zmp, double *zmp_theta,
-                         int *zmp_type, double *left, int *left_type, double *right, int *right_type, int *length);
-int wg_zmpdisc_begin_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps,
-                             const int *n_steps, const double *init_feet, int lcap, double *zmp_x_tm, double *zmp_y_tm,
-                             double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm,
-                             int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream);
-int wg_zmpdisc_append_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps,
-                              const int *n_steps, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm,
-                              int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm,
-                              wg_zmpdisc_state_t *state, int *length, void *hip_stream);
-int wg_zmpdisc_end_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_model_t *model, int B, const int *select, int lcap,
-                           double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm,
-                           int *left_type_tm, double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length,
-                           void *hip_stream);
-int wg_steps_plan_dev_ctx(wg_ctx_t *ctx, int B, int ccap, const wg_step_cmd_t *cmds, const int *n_cmds, double ss, double ds,
-                          wg_step_stack_t *stack, int smax, wg_rel_step_t *steps, int *n_steps, void *hip_stream);
-int wg_riccati_gains_batch_dev_ctx(wg_ctx_t *ctx, int B, double T, const double *zc, double Q, double R, int Nl, int mode,
-                                   double *K_tm, double *F_tm, int *status, void *hip_stream);
-int wg_riccati_gains_batch_ctx(wg_ctx_t *ctx, int B, double T, const double *zc, double Q, double R, int Nl, int mode,
-                               double *K, double *F, int *status);
-int wg_preview_run_fleet_dev_ctx(wg_ctx_t *ctx, int B, int L, const wg_preview_fleet_t *fleet, const double *zmp_x_tm,
-                                 const double *zmp_y_tm, double *state, double *com_tm, double *zmp2_tm, int simulation,
-                                 void *hip_stream);
-int wg_preview_follow_fleet_dev_ctx(wg_ctx_t *ctx, int B, int lcap, const int *length, int *done,
-                                    const wg_preview_fleet_t *fleet, const double *zmp_x_tm, const double *zmp_y_tm,
-                                    double *state, double *com_tm, double *zmp2_tm, int simulation, void *hip_stream);
-int wg_dimitrov_constants_batch_dev_ctx(wg_ctx_t *ctx, int M, const wg_dimitrov_model_t *base, const double *com_height,
-                                        const double *alpha, const double *beta, void *blocks, int *status, void *hip_stream);
-int wg_dimitrov_constants_batch_ctx(wg_ctx_t *ctx, int M, const wg_dimitrov_model_t *base, const double *com_height,
-                                    const double *alpha, const double *beta, void *blocks, int *status);
-int wg_dimitrov_tick_fleet_dev_ctx(wg_ctx_t *ctx, int B, const wg_dimitrov_fleet_t *fleet, const wg_zmp_polytope_t *polys,
-                                   wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int max_iter, void *hip_stream);
-int wg_dimitrov_walk_fleet_dev_ctx(wg_ctx_t *ctx, int B, const wg_dimitrov_fleet_t *fleet, int qcap,
-                                   const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end,
-                                   const int *count, double t0, int n_ticks, wg_dimitrov_state_t *states,
-                                   wg_dimitrov_out_t *outs, int *ran_out, int max_iter, void *hip_stream);
-int wg_dimitrov_follow_fleet_dev_ctx(wg_ctx_t *ctx, int B, const wg_dimitrov_fleet_t *fleet, int qcap,
-                                     const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end,
-                                     const int *count, int lcap, const double *time, const int *have,
-                                     const wg_zmpdisc_state_t *walk, int flags, double *clock, int *ticks, int tick_cap,
-                                     int max_ticks, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int *ran_out,
-                                     int max_iter, void *hip_stream);
-int wg_mpc_blocks_batch_dev_ctx(wg_ctx_t *ctx, int M, const wg_model_t *models, void *blocks, int *status, void *hip_stream);
-int wg_mpc_blocks_batch_ctx(wg_ctx_t *ctx, int M, const wg_model_t *models, void *blocks, int *status);
-int wg_mpc_tick_fleet_dev_ctx(wg_ctx_t *ctx, int B, const wg_mpc_fleet_t *fleet, wg_gait_state_t *states, wg_tick_out_t *outs,
-                              int *diag, int advance_calls, int *hist, int hist_cap, int *hist_len, void *hip_stream);
-int wg_mpc_run_fleet_dev_ctx(wg_ctx_t *ctx, int B, const wg_mpc_fleet_t *fleet, wg_gait_state_t *states, int n_ticks,
-                             int advance_calls, const double *vref_sched, int period, wg_tick_out_t *outs, int *diag,
-                             void *hip_stream);
-int wg_zmpdisc_full_fleet_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_fleet_t *fleet, int B, int smax,
-                                  const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap,
-                                  double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm,
-                                  double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm,
-                                  int *length, void *hip_stream);
-int wg_zmpdisc_begin_fleet_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_fleet_t *fleet, int B, int smax,
-                                   const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap,
-                                   double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm,
-                                   double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm,
-                                   wg_zmpdisc_state_t *state, int *length, void *hip_stream);
-int wg_zmpdisc_append_fleet_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_fleet_t *fleet, int B, int smax,
-                                    const wg_rel_step_t *steps, const int *n_steps, int lcap, double *zmp_x_tm,
-                                    double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm,
-                                    int *left_type_tm, double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state,
-                                    int *length, void *hip_stream);
-int wg_zmpdisc_end_fleet_dev_ctx(wg_ctx_t *ctx, const wg_zmpdisc_fleet_t *fleet, int B, const int *select, int lcap,
-                                 double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm,
-                                 int *left_type_tm, double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state,
-                                 int *length, void *hip_stream);
-int wg_steps_plan_fleet_dev_ctx(wg_ctx_t *ctx, int B, int ccap, const wg_step_cmd_t *cmds, const int *n_cmds, const double *ss,
-                                const double *ds, wg_step_stack_t *stack, int smax, wg_rel_step_t *steps, int *n_steps,
-                                void *hip_stream);
-int wg_foot_constraints_fleet_dev_ctx(wg_ctx_t *ctx, int B, int lcap, const int *length, const double *time,
-                                      const double *left_tm, const int *left_type_tm, const double *right_tm,
-                                      const wg_sole_t *soles, int qcap, wg_zmp_polytope_t *queues, double *t_start,
-                                      double *t_end, int *count, void *hip_stream);
-int wg_foot_constraints_append_fleet_dev_ctx(wg_ctx_t *ctx, int B, int lcap, int first_sample, int *done, const int *length,
-                                             const double *time, const double *left_tm, const int *left_type_tm,
-                                             const double *right_tm, const wg_sole_t *soles, int qcap,
-                                             wg_zmp_polytope_t *queues, double *t_start, double *t_end, int *count,
-                                             void *hip_stream);
-
 /* Morisawa-2007 analytic walks: CoM, ZMP and feet of a step sequence in closed form, batched over gaits -----------------------
  *
  * What the reference computes after ":SetAlgoForZmpTrajectory Morisawa" for a ":stepseq" (no on-line change):
@@ -1490,25 +1319,185 @@ int wg_morisawa_walk_fleet_dev(const wg_morisawa_model_t *models, double T, int 
                                const int *n_steps, const double *init_feet, const double *com0, void *blocks, int *status,
                                double t_start, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *com_tm, double *left_tm,
                                int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream);
-/* the same on a context of the caller's: the sampler keeps its clock in the context, so launches of one context are ordered */
-int wg_morisawa_solve_dev_ctx(wg_ctx_t *ctx, const wg_morisawa_model_t *model, int B, int smax, const wg_rel_step_t *steps,
-                              const int *n_steps, const double *init_feet, const double *com0, void *blocks, int *status,
-                              void *hip_stream);
-int wg_morisawa_solve_fleet_dev_ctx(wg_ctx_t *ctx, const wg_morisawa_model_t *models, int B, int smax,
-                                    const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, const double *com0,
-                                    void *blocks, int *status, void *hip_stream);
-int wg_morisawa_sample_dev_ctx(wg_ctx_t *ctx, int B, int smax, const void *blocks, const int *status, double t_start, double T,
-                               int lcap, double *zmp_x_tm, double *zmp_y_tm, double *com_tm, double *left_tm, int *left_type_tm,
-                               double *right_tm, int *right_type_tm, int *length, void *hip_stream);
-int wg_morisawa_walk_dev_ctx(wg_ctx_t *ctx, const wg_morisawa_model_t *model, int B, int smax, const wg_rel_step_t *steps,
-                             const int *n_steps, const double *init_feet, const double *com0, void *blocks, int *status,
-                             double t_start, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *com_tm, double *left_tm,
-                             int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream);
-int wg_morisawa_walk_fleet_dev_ctx(wg_ctx_t *ctx, const wg_morisawa_model_t *models, double T, int B, int smax,
-                                   const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, const double *com0,
-                                   void *blocks, int *status, double t_start, int lcap, double *zmp_x_tm, double *zmp_y_tm,
-                                   double *com_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm,
-                                   int *length, void *hip_stream);
+
+/* The context forms of the entry points above (same arguments after the context, same semantics) ----------------------------
+ *
+ * Written out: those whose default-context form is more than a forward (a query that must not create the default context, or a
+ * fleet call that refuses its arguments before the default context, and with it the device, is looked for). */
+long long wg_overlap_serialised_ctx(wg_ctx_t *ctx);
+size_t wg_mpc_tick_lds_bytes_ctx(wg_ctx_t *ctx);
+int wg_preview_window_ctx(wg_ctx_t *ctx);
+int wg_riccati_gains_batch_dev_ctx(wg_ctx_t *ctx, int B, double T, const double *zc, double Q, double R, int Nl, int mode,
+                                   double *K_tm, double *F_tm, int *status, void *hip_stream);
+int wg_riccati_gains_batch_ctx(wg_ctx_t *ctx, int B, double T, const double *zc, double Q, double R, int Nl, int mode,
+                               double *K, double *F, int *status);
+int wg_preview_run_fleet_dev_ctx(wg_ctx_t *ctx, int B, int L, const wg_preview_fleet_t *fleet, const double *zmp_x_tm,
+                                 const double *zmp_y_tm, double *state, double *com_tm, double *zmp2_tm, int simulation,
+                                 void *hip_stream);
+int wg_preview_follow_fleet_dev_ctx(wg_ctx_t *ctx, int B, int lcap, const int *length, int *done,
+                                    const wg_preview_fleet_t *fleet, const double *zmp_x_tm, const double *zmp_y_tm,
+                                    double *state, double *com_tm, double *zmp2_tm, int simulation, void *hip_stream);
+int wg_dimitrov_constants_batch_dev_ctx(wg_ctx_t *ctx, int M, const wg_dimitrov_model_t *base, const double *com_height,
+                                        const double *alpha, const double *beta, void *blocks, int *status, void *hip_stream);
+int wg_dimitrov_constants_batch_ctx(wg_ctx_t *ctx, int M, const wg_dimitrov_model_t *base, const double *com_height,
+                                    const double *alpha, const double *beta, void *blocks, int *status);
+int wg_dimitrov_tick_fleet_dev_ctx(wg_ctx_t *ctx, int B, const wg_dimitrov_fleet_t *fleet, const wg_zmp_polytope_t *polys,
+                                   wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int max_iter, void *hip_stream);
+int wg_dimitrov_walk_fleet_dev_ctx(wg_ctx_t *ctx, int B, const wg_dimitrov_fleet_t *fleet, int qcap,
+                                   const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end,
+                                   const int *count, double t0, int n_ticks, wg_dimitrov_state_t *states,
+                                   wg_dimitrov_out_t *outs, int *ran_out, int max_iter, void *hip_stream);
+int wg_dimitrov_follow_fleet_dev_ctx(wg_ctx_t *ctx, int B, const wg_dimitrov_fleet_t *fleet, int qcap,
+                                     const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end,
+                                     const int *count, int lcap, const double *time, const int *have,
+                                     const wg_zmpdisc_state_t *walk, int flags, double *clock, int *ticks, int tick_cap,
+                                     int max_ticks, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int *ran_out,
+                                     int max_iter, void *hip_stream);
+/* Every other one, one entry X(ret, name, (params), (args)) each: this header makes the prototype `ret name_ctx(wg_ctx_t *ctx, params);`
+ * of it, the library the forwarder `ret name(params) { return name_ctx(<the default context>, args); }` (wrong params: no build). */
+#define WG_CTX_FORWARDED(X) \
+  X(int, wg_qp_solve_batch_dev, (int B, int nmax, int mmax, const int *n, const int *m, const int *me, const double *C, const double *d, const double *A, \
+    const double *b, const double *xl, const double *xu, double eps, double *x, double *u, int *ifail, int *n_iter, int *iact, int *nact, int *hist, \
+    int hist_cap, int *hist_len, void *hip_stream), (B, nmax, mmax, n, m, me, C, d, A, b, xl, xu, eps, x, u, ifail, n_iter, iact, nact, hist, hist_cap, \
+    hist_len, hip_stream)) \
+  X(int, wg_qp_solve_batch, (int B, int nmax, int mmax, const int *n, const int *m, const int *me, const double *C, const double *d, const double *A, \
+    const double *b, const double *xl, const double *xu, double eps, double *x, double *u, int *ifail, int *n_iter, int *iact, int *nact, int *hist, \
+    int hist_cap, int *hist_len), (B, nmax, mmax, n, m, me, C, d, A, b, xl, xu, eps, x, u, ifail, n_iter, iact, nact, hist, hist_cap, hist_len)) \
+  X(int, wg_set_overlap_strict, (int on), (on)) \
+  X(int, wg_mpc_configure, (const wg_model_t *model), (model)) \
+  X(int, wg_mpc_reserve, (int max_gaits), (max_gaits)) \
+  X(int, wg_mpc_tick_batch_dev, (int B, wg_gait_state_t *states, wg_tick_out_t *outs, int *diag, int advance_calls, int *hist, int hist_cap, int *hist_len, \
+    void *hip_stream), (B, states, outs, diag, advance_calls, hist, hist_cap, hist_len, hip_stream)) \
+  X(int, wg_mpc_run_batch_dev, (int B, wg_gait_state_t *states, int n_ticks, int advance_calls, wg_tick_out_t *outs, int *diag, void *hip_stream), (B, \
+    states, n_ticks, advance_calls, outs, diag, hip_stream)) \
+  X(int, wg_mpc_run_sched_dev, (int B, wg_gait_state_t *states, int n_ticks, int advance_calls, const double *vref_sched, int period, wg_tick_out_t *outs, \
+    int *diag, void *hip_stream), (B, states, n_ticks, advance_calls, vref_sched, period, outs, diag, hip_stream)) \
+  X(int, wg_mpc_tick_batch, (int B, wg_gait_state_t *states, wg_tick_out_t *outs, int *diag, int advance_calls, int *hist, int hist_cap, int *hist_len), (B, \
+    states, outs, diag, advance_calls, hist, hist_cap, hist_len)) \
+  X(int, wg_mpc_set_velref_dev, (int B, wg_gait_state_t *states, const double *vref, void *hip_stream), (B, states, vref, hip_stream)) \
+  X(int, wg_mpc_tick_pinned, (wg_gait_state_t *state, wg_tick_out_t *out, int *diag, int advance_calls), (state, out, diag, advance_calls)) \
+  X(int, wg_mpc_assemble_batch, (int B, const wg_gait_state_t *states, int advance_calls, int nmax, int mmax, double *C, double *d, double *A, double *b, \
+    double *xl, double *xu, int *n, int *m), (B, states, advance_calls, nmax, mmax, C, d, A, b, xl, xu, n, m)) \
+  X(int, wg_mpc_assemble_batch_dev, (int B, const wg_gait_state_t *states, int advance_calls, int nmax, int mmax, double *C, double *d, double *A, double *b, \
+    double *xl, double *xu, int *n, int *m, void *hip_stream), (B, states, advance_calls, nmax, mmax, C, d, A, b, xl, xu, n, m, hip_stream)) \
+  X(int, wg_pldp_configure, (int N, const double *iPu, const double *Px, const double *Pu), (N, iPu, Px, Pu)) \
+  X(int, wg_pldp_solve_batch_dev, (int B, int mcap, const int *m, const double *D, const double *A, const double *b, const double *zmpref, \
+    const double *xkyk, const int *similar, const int *n_removed, const int *starting, int max_iter, wg_pldp_state_t *states, double *X, int *ret, \
+    int *n_iter, int *active, int *n_active, void *hip_stream), (B, mcap, m, D, A, b, zmpref, xkyk, similar, n_removed, starting, max_iter, states, X, ret, \
+    n_iter, active, n_active, hip_stream)) \
+  X(int, wg_pldp_solve_batch, (int B, int mcap, const int *m, const double *D, const double *A, const double *b, const double *zmpref, const double *xkyk, \
+    const int *similar, const int *n_removed, const int *starting, int max_iter, wg_pldp_state_t *states, double *X, int *ret, int *n_iter, int *active, \
+    int *n_active), (B, mcap, m, D, A, b, zmpref, xkyk, similar, n_removed, starting, max_iter, states, X, ret, n_iter, active, n_active)) \
+  X(int, wg_dimitrov_configure, (const wg_dimitrov_model_t *model), (model)) \
+  X(int, wg_dimitrov_get_constants, (double *iLQ, double *OptB, double *OptC, double *Pu, double *iPu, double *Px), (iLQ, OptB, OptC, Pu, iPu, Px)) \
+  X(int, wg_dimitrov_get_qld_constants, (double *Q, double *OptB, double *OptC, double *PuT), (Q, OptB, OptC, PuT)) \
+  X(int, wg_dimitrov_tick_batch_dev, (int B, const wg_zmp_polytope_t *polys, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int max_iter, \
+    void *hip_stream), (B, polys, states, outs, max_iter, hip_stream)) \
+  X(int, wg_dimitrov_tick_batch, (int B, const wg_zmp_polytope_t *polys, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int max_iter), (B, polys, \
+    states, outs, max_iter)) \
+  X(int, wg_foot_constraints_batch_dev, (int B, int lcap, const int *length, const double *time, const double *left_tm, const int *left_type_tm, \
+    const double *right_tm, double sole_w, double sole_h, double constraint_x, double constraint_y, int qcap, wg_zmp_polytope_t *queues, double *t_start, \
+    double *t_end, int *count, void *hip_stream), (B, lcap, length, time, left_tm, left_type_tm, right_tm, sole_w, sole_h, constraint_x, constraint_y, qcap, \
+    queues, t_start, t_end, count, hip_stream)) \
+  X(int, wg_foot_constraints_append_dev, (int B, int lcap, int first_sample, int *done, const int *length, const double *time, const double *left_tm, \
+    const int *left_type_tm, const double *right_tm, double sole_w, double sole_h, double constraint_x, double constraint_y, int qcap, \
+    wg_zmp_polytope_t *queues, double *t_start, double *t_end, int *count, void *hip_stream), (B, lcap, first_sample, done, length, time, left_tm, \
+    left_type_tm, right_tm, sole_w, sole_h, constraint_x, constraint_y, qcap, queues, t_start, t_end, count, hip_stream)) \
+  X(double, wg_dimitrov_walk_time, (double t0, int n_ticks), (t0, n_ticks)) \
+  X(int, wg_dimitrov_walk_safe_ticks, (double t0, double t_have), (t0, t_have)) \
+  X(int, wg_dimitrov_select_polys_dev, (int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count, \
+    double t0, wg_zmp_polytope_t *polys, int *ran_out, void *hip_stream), (B, qcap, queues, t_start, t_end, count, t0, polys, ran_out, hip_stream)) \
+  X(int, wg_dimitrov_walk_dev, (int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count, double t0, \
+    int n_ticks, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int *ran_out, int max_iter, void *hip_stream), (B, qcap, queues, t_start, t_end, \
+    count, t0, n_ticks, states, outs, ran_out, max_iter, hip_stream)) \
+  X(int, wg_dimitrov_follow_dev, (int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count, int lcap, \
+    const double *time, const int *have, const wg_zmpdisc_state_t *walk, int flags, double *clock, int *ticks, int tick_cap, int max_ticks, \
+    wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int *ran_out, int max_iter, void *hip_stream), (B, qcap, queues, t_start, t_end, count, lcap, time, \
+    have, walk, flags, clock, ticks, tick_cap, max_ticks, states, outs, ran_out, max_iter, hip_stream)) \
+  X(int, wg_preview_configure, (const wg_preview_gains_t *gains, const double *F), (gains, F)) \
+  X(int, wg_preview_run_batch_dev, (int B, int L, const double *zmp_x_tm, const double *zmp_y_tm, double *state, double *com_tm, double *zmp2_tm, \
+    int simulation, void *hip_stream), (B, L, zmp_x_tm, zmp_y_tm, state, com_tm, zmp2_tm, simulation, hip_stream)) \
+  X(int, wg_preview_follow_dev, (int B, int lcap, const int *length, int *done, const double *zmp_x_tm, const double *zmp_y_tm, double *state, \
+    double *com_tm, double *zmp2_tm, int simulation, void *hip_stream), (B, lcap, length, done, zmp_x_tm, zmp_y_tm, state, com_tm, zmp2_tm, simulation, \
+    hip_stream)) \
+  X(int, wg_preview_run_batch, (int B, int L, const double *zmp_x, const double *zmp_y, double *state, double *com, double *zmp2, int simulation), (B, L, \
+    zmp_x, zmp_y, state, com, zmp2, simulation)) \
+  X(int, wg_gramian_batch_dev, (int B, int N, const double *T, const double *h, double alpha, double beta, double gamma, int precision, double *Qb, \
+    void *hip_stream), (B, N, T, h, alpha, beta, gamma, precision, Qb, hip_stream)) \
+  X(int, wg_gramian_batch, (int B, int N, const double *T, const double *h, double alpha, double beta, double gamma, int precision, double *Qb), (B, N, T, h, \
+    alpha, beta, gamma, precision, Qb)) \
+  X(int, wg_zmpdisc_batch_dev, (const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, \
+    int lcap, double *zmp_x_tm, double *zmp_y_tm, int *length, void *hip_stream), (model, B, smax, steps, n_steps, init_feet, lcap, zmp_x_tm, zmp_y_tm, \
+    length, hip_stream)) \
+  X(int, wg_zmpdisc_full_batch_dev, (const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, \
+    const double *init_feet, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, \
+    double *right_tm, int *right_type_tm, int *length, void *hip_stream), (model, B, smax, steps, n_steps, init_feet, lcap, zmp_x_tm, zmp_y_tm, zmp_theta_tm, \
+    zmp_type_tm, left_tm, left_type_tm, right_tm, right_type_tm, length, hip_stream)) \
+  X(int, wg_zmpdisc_batch, (const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, \
+    int lcap, double *zmp, double *zmp_theta, int *zmp_type, double *left, int *left_type, double *right, int *right_type, int *length), (model, B, smax, \
+    steps, n_steps, init_feet, lcap, zmp, zmp_theta, zmp_type, left, left_type, right, right_type, length)) \
+  X(int, wg_zmpdisc_begin_dev, (const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, \
+    int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, \
+    int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream), (model, B, smax, steps, n_steps, init_feet, lcap, zmp_x_tm, zmp_y_tm, \
+    zmp_theta_tm, zmp_type_tm, left_tm, left_type_tm, right_tm, right_type_tm, state, length, hip_stream)) \
+  X(int, wg_zmpdisc_append_dev, (const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, int lcap, \
+    double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, \
+    wg_zmpdisc_state_t *state, int *length, void *hip_stream), (model, B, smax, steps, n_steps, lcap, zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, \
+    left_type_tm, right_tm, right_type_tm, state, length, hip_stream)) \
+  X(int, wg_zmpdisc_end_dev, (const wg_zmpdisc_model_t *model, int B, const int *select, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, \
+    int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream), \
+    (model, B, select, lcap, zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, left_type_tm, right_tm, right_type_tm, state, length, hip_stream)) \
+  X(int, wg_steps_plan_dev, (int B, int ccap, const wg_step_cmd_t *cmds, const int *n_cmds, double ss, double ds, wg_step_stack_t *stack, int smax, \
+    wg_rel_step_t *steps, int *n_steps, void *hip_stream), (B, ccap, cmds, n_cmds, ss, ds, stack, smax, steps, n_steps, hip_stream)) \
+  X(int, wg_mpc_blocks_batch_dev, (int M, const wg_model_t *models, void *blocks, int *status, void *hip_stream), (M, models, blocks, status, hip_stream)) \
+  X(int, wg_mpc_blocks_batch, (int M, const wg_model_t *models, void *blocks, int *status), (M, models, blocks, status)) \
+  X(int, wg_mpc_tick_fleet_dev, (int B, const wg_mpc_fleet_t *fleet, wg_gait_state_t *states, wg_tick_out_t *outs, int *diag, int advance_calls, int *hist, \
+    int hist_cap, int *hist_len, void *hip_stream), (B, fleet, states, outs, diag, advance_calls, hist, hist_cap, hist_len, hip_stream)) \
+  X(int, wg_mpc_run_fleet_dev, (int B, const wg_mpc_fleet_t *fleet, wg_gait_state_t *states, int n_ticks, int advance_calls, const double *vref_sched, \
+    int period, wg_tick_out_t *outs, int *diag, void *hip_stream), (B, fleet, states, n_ticks, advance_calls, vref_sched, period, outs, diag, hip_stream)) \
+  X(int, wg_zmpdisc_full_fleet_dev, (const wg_zmpdisc_fleet_t *fleet, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, \
+    const double *init_feet, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, \
+    double *right_tm, int *right_type_tm, int *length, void *hip_stream), (fleet, B, smax, steps, n_steps, init_feet, lcap, zmp_x_tm, zmp_y_tm, zmp_theta_tm, \
+    zmp_type_tm, left_tm, left_type_tm, right_tm, right_type_tm, length, hip_stream)) \
+  X(int, wg_zmpdisc_begin_fleet_dev, (const wg_zmpdisc_fleet_t *fleet, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, \
+    const double *init_feet, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, \
+    double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream), (fleet, B, smax, steps, n_steps, init_feet, lcap, \
+    zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, left_type_tm, right_tm, right_type_tm, state, length, hip_stream)) \
+  X(int, wg_zmpdisc_append_fleet_dev, (const wg_zmpdisc_fleet_t *fleet, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, int lcap, \
+    double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, \
+    wg_zmpdisc_state_t *state, int *length, void *hip_stream), (fleet, B, smax, steps, n_steps, lcap, zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, \
+    left_type_tm, right_tm, right_type_tm, state, length, hip_stream)) \
+  X(int, wg_zmpdisc_end_fleet_dev, (const wg_zmpdisc_fleet_t *fleet, int B, const int *select, int lcap, double *zmp_x_tm, double *zmp_y_tm, \
+    double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length, \
+    void *hip_stream), (fleet, B, select, lcap, zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, left_type_tm, right_tm, right_type_tm, state, length, \
+    hip_stream)) \
+  X(int, wg_steps_plan_fleet_dev, (int B, int ccap, const wg_step_cmd_t *cmds, const int *n_cmds, const double *ss, const double *ds, wg_step_stack_t *stack, \
+    int smax, wg_rel_step_t *steps, int *n_steps, void *hip_stream), (B, ccap, cmds, n_cmds, ss, ds, stack, smax, steps, n_steps, hip_stream)) \
+  X(int, wg_foot_constraints_fleet_dev, (int B, int lcap, const int *length, const double *time, const double *left_tm, const int *left_type_tm, \
+    const double *right_tm, const wg_sole_t *soles, int qcap, wg_zmp_polytope_t *queues, double *t_start, double *t_end, int *count, void *hip_stream), (B, \
+    lcap, length, time, left_tm, left_type_tm, right_tm, soles, qcap, queues, t_start, t_end, count, hip_stream)) \
+  X(int, wg_foot_constraints_append_fleet_dev, (int B, int lcap, int first_sample, int *done, const int *length, const double *time, const double *left_tm, \
+    const int *left_type_tm, const double *right_tm, const wg_sole_t *soles, int qcap, wg_zmp_polytope_t *queues, double *t_start, double *t_end, int *count, \
+    void *hip_stream), (B, lcap, first_sample, done, length, time, left_tm, left_type_tm, right_tm, soles, qcap, queues, t_start, t_end, count, hip_stream)) \
+  X(int, wg_morisawa_solve_dev, (const wg_morisawa_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, \
+    const double *com0, void *blocks, int *status, void *hip_stream), (model, B, smax, steps, n_steps, init_feet, com0, blocks, status, hip_stream)) \
+  X(int, wg_morisawa_solve_fleet_dev, (const wg_morisawa_model_t *models, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, \
+    const double *init_feet, const double *com0, void *blocks, int *status, void *hip_stream), (models, B, smax, steps, n_steps, init_feet, com0, blocks, \
+    status, hip_stream)) \
+  X(int, wg_morisawa_sample_dev, (int B, int smax, const void *blocks, const int *status, double t_start, double T, int lcap, double *zmp_x_tm, \
+    double *zmp_y_tm, double *com_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream), (B, smax, \
+    blocks, status, t_start, T, lcap, zmp_x_tm, zmp_y_tm, com_tm, left_tm, left_type_tm, right_tm, right_type_tm, length, hip_stream)) \
+  X(int, wg_morisawa_walk_dev, (const wg_morisawa_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, \
+    const double *com0, void *blocks, int *status, double t_start, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *com_tm, double *left_tm, \
+    int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream), (model, B, smax, steps, n_steps, init_feet, com0, blocks, \
+    status, t_start, lcap, zmp_x_tm, zmp_y_tm, com_tm, left_tm, left_type_tm, right_tm, right_type_tm, length, hip_stream)) \
+  X(int, wg_morisawa_walk_fleet_dev, (const wg_morisawa_model_t *models, double T, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, \
+    const double *init_feet, const double *com0, void *blocks, int *status, double t_start, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *com_tm, \
+    double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream), (models, T, B, smax, steps, n_steps, init_feet, \
+    com0, blocks, status, t_start, lcap, zmp_x_tm, zmp_y_tm, com_tm, left_tm, left_type_tm, right_tm, right_type_tm, length, hip_stream))
+#define WG_CTX_UNPAREN_(...) __VA_ARGS__
+#define WG_CTX_PROTO_(ret, name, params, args) ret name##_ctx(wg_ctx_t *ctx, WG_CTX_UNPAREN_ params);
+WG_CTX_FORWARDED(WG_CTX_PROTO_)
 
 #ifdef __cplusplus
 }

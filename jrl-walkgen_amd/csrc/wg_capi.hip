@@ -2353,53 +2353,20 @@ int wg_zmpdisc_batch_ctx(wg_ctx_t *ctx, const wg_zmpdisc_model_t *model, int B, 
 // ---- the same entry points on the process-wide default context -----------------------------------------------------
 extern "C" {
 
-int wg_qp_solve_batch_dev(int B, int nmax, int mmax, const int *n, const int *m, const int *me, const double *C, const double *d, const double *A, const double *b, const double *xl, const double *xu, double eps, double *x, double *u, int *ifail, int *n_iter, int *iact, int *nact, int *hist, int hist_cap, int *hist_len, void *hip_stream) { return on_default(&wg_qp_solve_batch_dev_ctx, B, nmax, mmax, n, m, me, C, d, A, b, xl, xu, eps, x, u, ifail, n_iter, iact, nact, hist, hist_cap, hist_len, hip_stream); }
-int wg_qp_solve_batch(int B, int nmax, int mmax, const int *n, const int *m, const int *me, const double *C, const double *d, const double *A, const double *b, const double *xl, const double *xu, double eps, double *x, double *u, int *ifail, int *n_iter, int *iact, int *nact, int *hist, int hist_cap, int *hist_len) { return on_default(&wg_qp_solve_batch_ctx, B, nmax, mmax, n, m, me, C, d, A, b, xl, xu, eps, x, u, ifail, n_iter, iact, nact, hist, hist_cap, hist_len); }
-int wg_set_overlap_strict(int on) { return on_default(&wg_set_overlap_strict_ctx, on); }
+// the plain ones, one per entry of the header's list
+#define WG_CTX_FORWARD_(ret, name, params, args) ret name params { return on_default(&name##_ctx, WG_CTX_UNPAREN_ args); }
+WG_CTX_FORWARDED(WG_CTX_FORWARD_)
+#undef WG_CTX_FORWARD_
+
 long long wg_overlap_serialised(void) { return on_default(&wg_overlap_serialised_ctx); }
-int wg_mpc_configure(const wg_model_t *model) { return on_default(&wg_mpc_configure_ctx, model); }
-int wg_mpc_reserve(int max_gaits) { return on_default(&wg_mpc_reserve_ctx, max_gaits); }
 size_t wg_mpc_tick_lds_bytes(void) {                 // a query: does not create the default context
   std::lock_guard<std::mutex> lk(g_default_mu);
   return wg_mpc_tick_lds_bytes_ctx(g_default);
 }
-
-int wg_mpc_tick_batch_dev(int B, wg_gait_state_t *states, wg_tick_out_t *outs, int *diag, int advance_calls, int *hist, int hist_cap, int *hist_len, void *hip_stream) { return on_default(&wg_mpc_tick_batch_dev_ctx, B, states, outs, diag, advance_calls, hist, hist_cap, hist_len, hip_stream); }
-int wg_mpc_run_sched_dev(int B, wg_gait_state_t *states, int n_ticks, int advance_calls, const double *vref_sched, int period, wg_tick_out_t *outs, int *diag, void *hip_stream) { return on_default(&wg_mpc_run_sched_dev_ctx, B, states, n_ticks, advance_calls, vref_sched, period, outs, diag, hip_stream); }
-int wg_mpc_run_batch_dev(int B, wg_gait_state_t *states, int n_ticks, int advance_calls, wg_tick_out_t *outs, int *diag, void *hip_stream) { return on_default(&wg_mpc_run_batch_dev_ctx, B, states, n_ticks, advance_calls, outs, diag, hip_stream); }
-int wg_mpc_tick_fleet_dev(int B, const wg_mpc_fleet_t *fleet, wg_gait_state_t *states, wg_tick_out_t *outs, int *diag, int advance_calls, int *hist, int hist_cap, int *hist_len, void *hip_stream) { return on_default(&wg_mpc_tick_fleet_dev_ctx, B, fleet, states, outs, diag, advance_calls, hist, hist_cap, hist_len, hip_stream); }
-int wg_mpc_run_fleet_dev(int B, const wg_mpc_fleet_t *fleet, wg_gait_state_t *states, int n_ticks, int advance_calls, const double *vref_sched, int period, wg_tick_out_t *outs, int *diag, void *hip_stream) { return on_default(&wg_mpc_run_fleet_dev_ctx, B, fleet, states, n_ticks, advance_calls, vref_sched, period, outs, diag, hip_stream); }
-int wg_mpc_blocks_batch_dev(int M, const wg_model_t *models, void *blocks, int *status, void *hip_stream) { return on_default(&wg_mpc_blocks_batch_dev_ctx, M, models, blocks, status, hip_stream); }
-int wg_mpc_blocks_batch(int M, const wg_model_t *models, void *blocks, int *status) { return on_default(&wg_mpc_blocks_batch_ctx, M, models, blocks, status); }
-int wg_mpc_tick_batch(int B, wg_gait_state_t *states, wg_tick_out_t *outs, int *diag, int advance_calls, int *hist, int hist_cap, int *hist_len) { return on_default(&wg_mpc_tick_batch_ctx, B, states, outs, diag, advance_calls, hist, hist_cap, hist_len); }
-int wg_mpc_set_velref_dev(int B, wg_gait_state_t *states, const double *vref, void *hip_stream) { return on_default(&wg_mpc_set_velref_dev_ctx, B, states, vref, hip_stream); }
-int wg_pldp_configure(int N, const double *iPu, const double *Px, const double *Pu) { return on_default(&wg_pldp_configure_ctx, N, iPu, Px, Pu); }
-int wg_pldp_solve_batch_dev(int B, int mcap, const int *m, const double *D, const double *A, const double *b, const double *zmpref, const double *xkyk, const int *similar, const int *n_removed, const int *starting, int max_iter, wg_pldp_state_t *states, double *X, int *ret, int *n_iter, int *active, int *n_active, void *hip_stream) { return on_default(&wg_pldp_solve_batch_dev_ctx, B, mcap, m, D, A, b, zmpref, xkyk, similar, n_removed, starting, max_iter, states, X, ret, n_iter, active, n_active, hip_stream); }
-int wg_pldp_solve_batch(int B, int mcap, const int *m, const double *D, const double *A, const double *b, const double *zmpref, const double *xkyk, const int *similar, const int *n_removed, const int *starting, int max_iter, wg_pldp_state_t *states, double *X, int *ret, int *n_iter, int *active, int *n_active) { return on_default(&wg_pldp_solve_batch_ctx, B, mcap, m, D, A, b, zmpref, xkyk, similar, n_removed, starting, max_iter, states, X, ret, n_iter, active, n_active); }
-int wg_dimitrov_configure(const wg_dimitrov_model_t *model) { return on_default(&wg_dimitrov_configure_ctx, model); }
-int wg_dimitrov_get_constants(double *iLQ, double *OptB, double *OptC, double *Pu, double *iPu, double *Px) { return on_default(&wg_dimitrov_get_constants_ctx, iLQ, OptB, OptC, Pu, iPu, Px); }
-int wg_dimitrov_get_qld_constants(double *Q, double *OptB, double *OptC, double *PuT) { return on_default(&wg_dimitrov_get_qld_constants_ctx, Q, OptB, OptC, PuT); }
-int wg_dimitrov_tick_batch_dev(int B, const wg_zmp_polytope_t *polys, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int max_iter, void *hip_stream) { return on_default(&wg_dimitrov_tick_batch_dev_ctx, B, polys, states, outs, max_iter, hip_stream); }
-int wg_dimitrov_tick_batch(int B, const wg_zmp_polytope_t *polys, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int max_iter) { return on_default(&wg_dimitrov_tick_batch_ctx, B, polys, states, outs, max_iter); }
-int wg_foot_constraints_batch_dev(int B, int lcap, const int *length, const double *time, const double *left_tm, const int *left_type_tm, const double *right_tm, double sole_w, double sole_h, double constraint_x, double constraint_y, int qcap, wg_zmp_polytope_t *queues, double *t_start, double *t_end, int *count, void *hip_stream) { return on_default(&wg_foot_constraints_batch_dev_ctx, B, lcap, length, time, left_tm, left_type_tm, right_tm, sole_w, sole_h, constraint_x, constraint_y, qcap, queues, t_start, t_end, count, hip_stream); }
-int wg_dimitrov_select_polys_dev(int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count, double t0, wg_zmp_polytope_t *polys, int *ran_out, void *hip_stream) { return on_default(&wg_dimitrov_select_polys_dev_ctx, B, qcap, queues, t_start, t_end, count, t0, polys, ran_out, hip_stream); }
-int wg_foot_constraints_append_dev(int B, int lcap, int first_sample, int *done, const int *length, const double *time, const double *left_tm, const int *left_type_tm, const double *right_tm, double sole_w, double sole_h, double constraint_x, double constraint_y, int qcap, wg_zmp_polytope_t *queues, double *t_start, double *t_end, int *count, void *hip_stream) { return on_default(&wg_foot_constraints_append_dev_ctx, B, lcap, first_sample, done, length, time, left_tm, left_type_tm, right_tm, sole_w, sole_h, constraint_x, constraint_y, qcap, queues, t_start, t_end, count, hip_stream); }
-double wg_dimitrov_walk_time(double t0, int n_ticks) { return on_default(&wg_dimitrov_walk_time_ctx, t0, n_ticks); }
-int wg_dimitrov_walk_safe_ticks(double t0, double t_have) { return on_default(&wg_dimitrov_walk_safe_ticks_ctx, t0, t_have); }
-int wg_dimitrov_walk_dev(int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count, double t0, int n_ticks, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int *ran_out, int max_iter, void *hip_stream) { return on_default(&wg_dimitrov_walk_dev_ctx, B, qcap, queues, t_start, t_end, count, t0, n_ticks, states, outs, ran_out, max_iter, hip_stream); }
-int wg_mpc_tick_pinned(wg_gait_state_t *state, wg_tick_out_t *out, int *diag, int advance_calls) { return on_default(&wg_mpc_tick_pinned_ctx, state, out, diag, advance_calls); }
-int wg_mpc_assemble_batch_dev(int B, const wg_gait_state_t *states, int advance_calls, int nmax, int mmax, double *C, double *d, double *A, double *b, double *xl, double *xu, int *n, int *m, void *hip_stream) { return on_default(&wg_mpc_assemble_batch_dev_ctx, B, states, advance_calls, nmax, mmax, C, d, A, b, xl, xu, n, m, hip_stream); }
-int wg_mpc_assemble_batch(int B, const wg_gait_state_t *states, int advance_calls, int nmax, int mmax, double *C, double *d, double *A, double *b, double *xl, double *xu, int *n, int *m) { return on_default(&wg_mpc_assemble_batch_ctx, B, states, advance_calls, nmax, mmax, C, d, A, b, xl, xu, n, m); }
-int wg_preview_configure(const wg_preview_gains_t *gains, const double *F) { return on_default(&wg_preview_configure_ctx, gains, F); }
 int wg_preview_window(void) {                        // a query: does not create the default context
   std::lock_guard<std::mutex> lk(g_default_mu);
   return wg_preview_window_ctx(g_default);
 }
-
-int wg_preview_run_batch_dev(int B, int L, const double *zmp_x_tm, const double *zmp_y_tm, double *state, double *com_tm, double *zmp2_tm, int simulation, void *hip_stream) { return on_default(&wg_preview_run_batch_dev_ctx, B, L, zmp_x_tm, zmp_y_tm, state, com_tm, zmp2_tm, simulation, hip_stream); }
-int wg_dimitrov_follow_dev(int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count, int lcap, const double *time, const int *have, const wg_zmpdisc_state_t *walk, int flags, double *clock, int *ticks, int tick_cap, int max_ticks, wg_dimitrov_state_t *states, wg_dimitrov_out_t *outs, int *ran_out, int max_iter, void *hip_stream) { return on_default(&wg_dimitrov_follow_dev_ctx, B, qcap, queues, t_start, t_end, count, lcap, time, have, walk, flags, clock, ticks, tick_cap, max_ticks, states, outs, ran_out, max_iter, hip_stream); }
-int wg_preview_follow_dev(int B, int lcap, const int *length, int *done, const double *zmp_x_tm, const double *zmp_y_tm, double *state, double *com_tm, double *zmp2_tm, int simulation, void *hip_stream) { return on_default(&wg_preview_follow_dev_ctx, B, lcap, length, done, zmp_x_tm, zmp_y_tm, state, com_tm, zmp2_tm, simulation, hip_stream); }
-int wg_preview_run_batch(int B, int L, const double *zmp_x, const double *zmp_y, double *state, double *com, double *zmp2, int simulation) { return on_default(&wg_preview_run_batch_ctx, B, L, zmp_x, zmp_y, state, com, zmp2, simulation); }
 // the fleet calls refuse their arguments before the default context (and with it the device) is looked for
 int wg_riccati_gains_batch_dev(int B, double T, const double *zc, double Q, double R, int Nl, int mode, double *K_tm, double *F_tm, int *status, void *hip_stream) {
   if (int rc = riccati_batch_check(B, T, zc, R, Nl, mode, K_tm, F_tm, status)) return rc;
@@ -2437,22 +2404,6 @@ int wg_dimitrov_follow_fleet_dev(int B, const wg_dimitrov_fleet_t *fleet, int qc
   if (int rc = dimitrov_follow_fleet_check(B, fleet, qcap, queues, t_start, t_end, count, lcap, time, have, flags, clock, ticks, tick_cap, max_ticks, states)) return rc;
   return on_default(&wg_dimitrov_follow_fleet_dev_ctx, B, fleet, qcap, queues, t_start, t_end, count, lcap, time, have, walk, flags, clock, ticks, tick_cap, max_ticks, states, outs, ran_out, max_iter, hip_stream);
 }
-int wg_gramian_batch_dev(int B, int N, const double *T, const double *h, double alpha, double beta, double gamma, int precision, double *Qb, void *hip_stream) { return on_default(&wg_gramian_batch_dev_ctx, B, N, T, h, alpha, beta, gamma, precision, Qb, hip_stream); }
-int wg_gramian_batch(int B, int N, const double *T, const double *h, double alpha, double beta, double gamma, int precision, double *Qb) { return on_default(&wg_gramian_batch_ctx, B, N, T, h, alpha, beta, gamma, precision, Qb); }
-int wg_zmpdisc_batch_dev(const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap, double *zmp_x_tm, double *zmp_y_tm, int *length, void *hip_stream) { return on_default(&wg_zmpdisc_batch_dev_ctx, model, B, smax, steps, n_steps, init_feet, lcap, zmp_x_tm, zmp_y_tm, length, hip_stream); }
-int wg_zmpdisc_full_batch_dev(const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream) { return on_default(&wg_zmpdisc_full_batch_dev_ctx, model, B, smax, steps, n_steps, init_feet, lcap, zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, left_type_tm, right_tm, right_type_tm, length, hip_stream); }
-int wg_zmpdisc_begin_dev(const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream) { return on_default(&wg_zmpdisc_begin_dev_ctx, model, B, smax, steps, n_steps, init_feet, lcap, zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, left_type_tm, right_tm, right_type_tm, state, length, hip_stream); }
-int wg_zmpdisc_append_dev(const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream) { return on_default(&wg_zmpdisc_append_dev_ctx, model, B, smax, steps, n_steps, lcap, zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, left_type_tm, right_tm, right_type_tm, state, length, hip_stream); }
-int wg_zmpdisc_end_dev(const wg_zmpdisc_model_t *model, int B, const int *select, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream) { return on_default(&wg_zmpdisc_end_dev_ctx, model, B, select, lcap, zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, left_type_tm, right_tm, right_type_tm, state, length, hip_stream); }
-int wg_steps_plan_dev(int B, int ccap, const wg_step_cmd_t *cmds, const int *n_cmds, double ss, double ds, wg_step_stack_t *stack, int smax, wg_rel_step_t *steps, int *n_steps, void *hip_stream) { return on_default(&wg_steps_plan_dev_ctx, B, ccap, cmds, n_cmds, ss, ds, stack, smax, steps, n_steps, hip_stream); }
-int wg_zmpdisc_full_fleet_dev(const wg_zmpdisc_fleet_t *fleet, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream) { return on_default(&wg_zmpdisc_full_fleet_dev_ctx, fleet, B, smax, steps, n_steps, init_feet, lcap, zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, left_type_tm, right_tm, right_type_tm, length, hip_stream); }
-int wg_zmpdisc_begin_fleet_dev(const wg_zmpdisc_fleet_t *fleet, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream) { return on_default(&wg_zmpdisc_begin_fleet_dev_ctx, fleet, B, smax, steps, n_steps, init_feet, lcap, zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, left_type_tm, right_tm, right_type_tm, state, length, hip_stream); }
-int wg_zmpdisc_append_fleet_dev(const wg_zmpdisc_fleet_t *fleet, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream) { return on_default(&wg_zmpdisc_append_fleet_dev_ctx, fleet, B, smax, steps, n_steps, lcap, zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, left_type_tm, right_tm, right_type_tm, state, length, hip_stream); }
-int wg_zmpdisc_end_fleet_dev(const wg_zmpdisc_fleet_t *fleet, int B, const int *select, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *zmp_theta_tm, int *zmp_type_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, wg_zmpdisc_state_t *state, int *length, void *hip_stream) { return on_default(&wg_zmpdisc_end_fleet_dev_ctx, fleet, B, select, lcap, zmp_x_tm, zmp_y_tm, zmp_theta_tm, zmp_type_tm, left_tm, left_type_tm, right_tm, right_type_tm, state, length, hip_stream); }
-int wg_steps_plan_fleet_dev(int B, int ccap, const wg_step_cmd_t *cmds, const int *n_cmds, const double *ss, const double *ds, wg_step_stack_t *stack, int smax, wg_rel_step_t *steps, int *n_steps, void *hip_stream) { return on_default(&wg_steps_plan_fleet_dev_ctx, B, ccap, cmds, n_cmds, ss, ds, stack, smax, steps, n_steps, hip_stream); }
-int wg_foot_constraints_fleet_dev(int B, int lcap, const int *length, const double *time, const double *left_tm, const int *left_type_tm, const double *right_tm, const wg_sole_t *soles, int qcap, wg_zmp_polytope_t *queues, double *t_start, double *t_end, int *count, void *hip_stream) { return on_default(&wg_foot_constraints_fleet_dev_ctx, B, lcap, length, time, left_tm, left_type_tm, right_tm, soles, qcap, queues, t_start, t_end, count, hip_stream); }
-int wg_foot_constraints_append_fleet_dev(int B, int lcap, int first_sample, int *done, const int *length, const double *time, const double *left_tm, const int *left_type_tm, const double *right_tm, const wg_sole_t *soles, int qcap, wg_zmp_polytope_t *queues, double *t_start, double *t_end, int *count, void *hip_stream) { return on_default(&wg_foot_constraints_append_fleet_dev_ctx, B, lcap, first_sample, done, length, time, left_tm, left_type_tm, right_tm, soles, qcap, queues, t_start, t_end, count, hip_stream); }
-int wg_zmpdisc_batch(const wg_zmpdisc_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, int lcap, double *zmp, double *zmp_theta, int *zmp_type, double *left, int *left_type, double *right, int *right_type, int *length) { return on_default(&wg_zmpdisc_batch_ctx, model, B, smax, steps, n_steps, init_feet, lcap, zmp, zmp_theta, zmp_type, left, left_type, right, right_type, length); }
 
 }  // extern "C"
 
@@ -2526,10 +2477,5 @@ int wg_morisawa_walk_fleet_dev_ctx(wg_ctx_t *ctx, const wg_morisawa_model_t *mod
   if (int rc = wg_morisawa_solve_fleet_dev_ctx(ctx, models, B, smax, steps, n_steps, init_feet, com0, blocks, status, hip_stream)) return rc;
   return wg_morisawa_sample_dev_ctx(ctx, B, smax, blocks, status, t_start, T, lcap, zmp_x_tm, zmp_y_tm, com_tm, left_tm, left_type_tm, right_tm, right_type_tm, length, hip_stream);
 }
-int wg_morisawa_solve_dev(const wg_morisawa_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, const double *com0, void *blocks, int *status, void *hip_stream) { return on_default(&wg_morisawa_solve_dev_ctx, model, B, smax, steps, n_steps, init_feet, com0, blocks, status, hip_stream); }
-int wg_morisawa_solve_fleet_dev(const wg_morisawa_model_t *models, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, const double *com0, void *blocks, int *status, void *hip_stream) { return on_default(&wg_morisawa_solve_fleet_dev_ctx, models, B, smax, steps, n_steps, init_feet, com0, blocks, status, hip_stream); }
-int wg_morisawa_sample_dev(int B, int smax, const void *blocks, const int *status, double t_start, double T, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *com_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream) { return on_default(&wg_morisawa_sample_dev_ctx, B, smax, blocks, status, t_start, T, lcap, zmp_x_tm, zmp_y_tm, com_tm, left_tm, left_type_tm, right_tm, right_type_tm, length, hip_stream); }
-int wg_morisawa_walk_dev(const wg_morisawa_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, const double *com0, void *blocks, int *status, double t_start, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *com_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream) { return on_default(&wg_morisawa_walk_dev_ctx, model, B, smax, steps, n_steps, init_feet, com0, blocks, status, t_start, lcap, zmp_x_tm, zmp_y_tm, com_tm, left_tm, left_type_tm, right_tm, right_type_tm, length, hip_stream); }
-int wg_morisawa_walk_fleet_dev(const wg_morisawa_model_t *models, double T, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, const double *com0, void *blocks, int *status, double t_start, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *com_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream) { return on_default(&wg_morisawa_walk_fleet_dev_ctx, models, T, B, smax, steps, n_steps, init_feet, com0, blocks, status, t_start, lcap, zmp_x_tm, zmp_y_tm, com_tm, left_tm, left_type_tm, right_tm, right_type_tm, length, hip_stream); }
 
 }  // extern "C"

@@ -1,11 +1,13 @@
 """ctypes binding of include/wg_mpc.h (no compute here)."""
 import ctypes as C
 import os
+import re
 
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("WG_LIB_PATH", os.path.join(_HERE, "lib", "libwg_mpc.so"))
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "wg_mpc.h")     # the one statement of every signature
 
 SAMPLES = 20   # WG_SAMPLES_PER_TICK
 
@@ -62,6 +64,51 @@ class WgError(RuntimeError):
     pass
 
 
+_SCALARS = {"int": C.c_int, "double": C.c_double, "size_t": C.c_size_t, "long long": C.c_longlong}
+_RETURNS = dict(_SCALARS, **{"void": None, "const char *": C.c_char_p})
+
+
+def header_signatures(text):
+    """{name: (restype, argtypes)} of a header's text: every prototype `RET wg_name(PARAMS);`, and NAME_ctx -- NAME's own
+    signature behind the context pointer -- for every entry X(ret, NAME, (params), (args)) of its list of context forms.  A
+    pointer or array parameter is a c_void_p; a type that is not one of the ABI's is an error, never a default."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S).replace("\\\n", " ")
+    listed = re.findall(r"\bX\(\s*[\w ]+?,\s*(wg_\w+)\s*,", text)
+    text = re.sub(r"^\s*#.*$", "", text, flags=re.M)                      # preprocessor lines, the list among them
+    text = re.sub(r"\bstruct\s+\w*\s*\{[^{}]*\}", "struct", text)         # struct bodies
+    sigs = {}
+    for ret, name, params in re.findall(r"([\w\s*]+?)\b(wg_\w+)\s*\(([^()]*)\)\s*;", text):
+        ret = " ".join(ret.replace("*", " * ").split())
+        if ret not in _RETURNS:
+            raise WgError(f"{name}: return type '{ret}' is not one the binding knows")
+        args = []
+        for p in [] if params.strip() == "void" else params.split(","):
+            ctype = " ".join(p.split()[:-1])
+            if "*" not in p and "[" not in p and ctype not in _SCALARS:
+                raise WgError(f"{name}: parameter '{p.strip()}' has a type the binding does not know")
+            args.append(C.c_void_p if "*" in p or "[" in p else _SCALARS[ctype])
+        sigs[name] = (_RETURNS[ret], args)
+    for name in listed:
+        if name not in sigs:
+            raise WgError(f"{name} is in the list of context forms but has no prototype")
+        sigs[name + "_ctx"] = (sigs[name][0], [C.c_void_p] + sigs[name][1])
+    return sigs
+
+
+def bind(cdll):
+    """argtypes and restype, as include/wg_mpc.h states them, of every entry point that `cdll` exports; one it does not export
+    (an older build under WG_LIB_PATH, A/B runs) is skipped"""
+    if not os.path.exists(HEADER_PATH):
+        raise WgError(f"{HEADER_PATH} missing: the binding takes every signature from it")
+    with open(HEADER_PATH) as f:
+        sigs = header_signatures(f.read())
+    for name, (restype, argtypes) in sigs.items():
+        fn = getattr(cdll, name, None)
+        if fn is not None:
+            fn.restype, fn.argtypes = restype, argtypes
+    return cdll
+
+
 def lib():
     """Load libwg_mpc.so (fails loudly if it has not been built)."""
     global _lib
@@ -76,181 +123,30 @@ def lib():
             import torch  # noqa: F401
         except ImportError:
             pass
-        _lib = C.CDLL(LIB_PATH)
-        _lib.wg_last_error.restype = C.c_char_p
-        _lib.wg_qp_lds_bytes.restype = C.c_size_t
-        qp_args = [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 9 + [C.c_double] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p]
-        _lib.wg_qp_solve_batch.argtypes = qp_args
-        _lib.wg_qp_solve_batch_dev.argtypes = qp_args + [C.c_void_p]
-        _lib.wg_mpc_tick_lds_bytes.restype = C.c_size_t
-        _lib.wg_mpc_tick_lds_bytes_for.restype = C.c_size_t
-        _lib.wg_mpc_tick_lds_bytes_for.argtypes = [C.c_void_p]
-        _lib.wg_mpc_tick_batch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
-                                           C.c_void_p]
-        _lib.wg_mpc_tick_batch_dev.argtypes = _lib.wg_mpc_tick_batch.argtypes + [C.c_void_p]
-        _lib.wg_mpc_set_velref_dev.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        _lib.wg_mpc_run_batch_dev.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        _lib.wg_mpc_run_sched_dev.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
-                                              C.c_void_p]
-        _lib.wg_host_alloc.argtypes = [C.c_void_p, C.c_size_t]
-        _lib.wg_host_free.argtypes = [C.c_void_p]
-        _lib.wg_host_free.restype = None
-        _lib.wg_mpc_tick_pinned.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-        _lib.wg_mpc_assemble_batch.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 8
-        _lib.wg_mpc_assemble_batch_dev.argtypes = _lib.wg_mpc_assemble_batch.argtypes + [C.c_void_p]
-        _lib.wg_pldp_lds_bytes.restype = C.c_size_t
-        _lib.wg_pldp_configure.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        _lib.wg_pldp_solve_batch.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 9 + [C.c_int] + [C.c_void_p] * 6
-        _lib.wg_pldp_solve_batch_dev.argtypes = _lib.wg_pldp_solve_batch.argtypes + [C.c_void_p]
-        _lib.wg_dimitrov_tick_batch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-        _lib.wg_dimitrov_tick_batch_dev.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        _lib.wg_dimitrov_get_constants.argtypes = [C.c_void_p] * 6
-        if hasattr(_lib, "wg_dimitrov_get_qld_constants"):
-            _lib.wg_dimitrov_get_qld_constants.argtypes = [C.c_void_p] * 4
-        _lib.wg_riccati_solve.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int,
-                                          C.c_int, C.c_void_p, C.c_void_p]
-        _lib.wg_riccati_gains.argtypes = [C.c_double] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        _lib.wg_preview_configure.argtypes = [C.c_void_p, C.c_void_p]
-        _lib.wg_gramian_batch.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p] + [C.c_double] * 3 + [C.c_int, C.c_void_p]
-        _lib.wg_gramian_batch_dev.argtypes = _lib.wg_gramian_batch.argtypes + [C.c_void_p]
-        _lib.wg_preview_run_batch.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int]
-        _lib.wg_preview_run_batch_dev.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]
-        if hasattr(_lib, "wg_preview_follow_dev"):          # absent from older experiment builds (WG_LIB_PATH, A/B runs)
-            _lib.wg_preview_follow_dev.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p]
-        if hasattr(_lib, "wg_riccati_gains_batch_dev"):     # absent from older experiment builds (WG_LIB_PATH, A/B runs)
-            _lib.wg_riccati_gains_batch.argtypes = [C.c_int, C.c_double, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_int] + \
-                [C.c_void_p] * 3
-            _lib.wg_riccati_gains_batch_dev.argtypes = _lib.wg_riccati_gains_batch.argtypes + [C.c_void_p]
-            _lib.wg_preview_run_fleet_dev.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p]
-            _lib.wg_preview_follow_fleet_dev.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 8 + [C.c_int, C.c_void_p]
-        _lib.wg_zmpdisc_defaults.argtypes = [C.c_void_p]
-        _lib.wg_zmpdisc_length.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-        _lib.wg_zmpdisc_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + \
-            [C.c_void_p] * 8
-        _lib.wg_zmpdisc_batch_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + \
-            [C.c_void_p] * 4
-        _lib.wg_zmpdisc_full_batch_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + \
-            [C.c_void_p] * 10
-        if hasattr(_lib, "wg_zmpdisc_begin_dev"):           # absent from older experiment builds (WG_LIB_PATH, A/B runs)
-            _lib.wg_zmpdisc_length_after.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
-            _lib.wg_zmpdisc_begin_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + \
-                [C.c_void_p] * 11
-            _lib.wg_zmpdisc_append_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 11
-            _lib.wg_zmpdisc_end_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 11
-        _lib.wg_foot_constraints.argtypes = [C.c_int] + [C.c_void_p] * 4 + [C.c_double] * 4 + [C.c_int] + [C.c_void_p] * 3
-        if hasattr(_lib, "wg_foot_constraints_batch_dev"):   # absent from older experiment builds (WG_LIB_PATH, A/B runs)
-            _lib.wg_foot_constraints_batch_dev.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_double] * 4 + [C.c_int] + \
-                [C.c_void_p] * 5
-            _lib.wg_dimitrov_select_polys_dev.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_double] + [C.c_void_p] * 3
-            _lib.wg_dimitrov_walk_dev.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_double, C.c_int] + \
-                [C.c_void_p] * 3 + [C.c_int, C.c_void_p]
-        if hasattr(_lib, "wg_foot_constraints_append_dev"):  # absent from older experiment builds (WG_LIB_PATH, A/B runs)
-            _lib.wg_foot_constraints_append_dev.argtypes = [C.c_int] * 3 + [C.c_void_p] * 6 + [C.c_double] * 4 + [C.c_int] + \
-                [C.c_void_p] * 5
-            _lib.wg_dimitrov_walk_time.argtypes = [C.c_double, C.c_int]
-            _lib.wg_dimitrov_walk_time.restype = C.c_double
-            _lib.wg_dimitrov_walk_safe_ticks.argtypes = [C.c_double, C.c_double]
-        if hasattr(_lib, "wg_dimitrov_follow_dev"):          # absent from older experiment builds (WG_LIB_PATH, A/B runs)
-            _lib.wg_dimitrov_follow_dev.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int] + \
-                [C.c_void_p] * 2 + [C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p]
-        if hasattr(_lib, "wg_dimitrov_constants_batch_dev"):  # absent from older experiment builds (WG_LIB_PATH, A/B runs)
-            _lib.wg_dimitrov_constants_bytes.restype = C.c_size_t
-            _lib.wg_dimitrov_constants_bytes.argtypes = []
-            _lib.wg_dimitrov_constants.argtypes = [C.c_void_p, C.c_void_p]
-            _lib.wg_dimitrov_constants_unpack.argtypes = [C.c_void_p] * 13
-            _lib.wg_dimitrov_constants_batch.argtypes = [C.c_int] + [C.c_void_p] * 6
-            _lib.wg_dimitrov_constants_batch_dev.argtypes = _lib.wg_dimitrov_constants_batch.argtypes + [C.c_void_p]
-            _lib.wg_dimitrov_tick_fleet_dev.argtypes = [C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p]
-            _lib.wg_dimitrov_walk_fleet_dev.argtypes = [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_double, C.c_int] + \
-                [C.c_void_p] * 3 + [C.c_int, C.c_void_p]
-            _lib.wg_dimitrov_follow_fleet_dev.argtypes = [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + \
-                [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 2 + [C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p]
-        if hasattr(_lib, "wg_mpc_block"):                    # absent from older experiment builds (WG_LIB_PATH, A/B runs)
-            _lib.wg_mpc_block_bytes.restype = C.c_size_t
-            _lib.wg_mpc_block_bytes.argtypes = []
-            _lib.wg_mpc_block.argtypes = [C.c_void_p, C.c_void_p]
-            _lib.wg_mpc_block_unpack.argtypes = [C.c_void_p] * 11
-        if hasattr(_lib, "wg_mpc_blocks_batch_dev"):
-            _lib.wg_mpc_blocks_batch.argtypes = [C.c_int] + [C.c_void_p] * 3
-            _lib.wg_mpc_blocks_batch_dev.argtypes = _lib.wg_mpc_blocks_batch.argtypes + [C.c_void_p]
-            _lib.wg_mpc_tick_fleet_dev.argtypes = [C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-            _lib.wg_mpc_run_fleet_dev.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int] + \
-                [C.c_void_p] * 3
-        if hasattr(_lib, "wg_steps_plan_dev"):               # absent from older experiment builds (WG_LIB_PATH, A/B runs)
-            _lib.wg_steps_count.argtypes = [C.c_void_p, C.c_int]
-            _lib.wg_steps_plan.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-            _lib.wg_steps_plan_dev.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_int,
-                                               C.c_void_p, C.c_void_p, C.c_void_p]
-        if hasattr(_lib, "wg_zmpdisc_full_fleet_dev"):       # absent from older experiment builds (WG_LIB_PATH, A/B runs)
-            for fleet, one in (("wg_zmpdisc_full_fleet_dev", "wg_zmpdisc_full_batch_dev"), ("wg_zmpdisc_begin_fleet_dev", "wg_zmpdisc_begin_dev"),
-                               ("wg_zmpdisc_append_fleet_dev", "wg_zmpdisc_append_dev"), ("wg_zmpdisc_end_fleet_dev", "wg_zmpdisc_end_dev")):
-                getattr(_lib, fleet).argtypes = getattr(_lib, one).argtypes      # a wg_zmpdisc_fleet_t * in place of the model
-            _lib.wg_steps_plan_fleet_dev.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 3
-            _lib.wg_foot_constraints_fleet_dev.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int] + [C.c_void_p] * 5
-            _lib.wg_foot_constraints_append_fleet_dev.argtypes = [C.c_int] * 3 + [C.c_void_p] * 7 + [C.c_int] + [C.c_void_p] * 5
-        # contexts: NAME_ctx(ctx, args...) for every entry point NAME(args...) that keeps or stages device-side state
-        _lib.wg_ctx_create.argtypes = [C.c_int, C.c_void_p]
-        _lib.wg_ctx_destroy.argtypes = [C.c_void_p]
-        _lib.wg_ctx_destroy.restype = None
-        _lib.wg_ctx_device.argtypes = [C.c_void_p]
-        _lib.wg_mpc_configure.argtypes = [C.c_void_p]
-        if hasattr(_lib, "wg_set_overlap_strict"):          # absent from older experiment builds
-            _lib.wg_set_overlap_strict.argtypes = [C.c_int]
-            _lib.wg_overlap_serialised.argtypes = []
-            _lib.wg_overlap_serialised.restype = C.c_longlong
-        if hasattr(_lib, "wg_mpc_reserve"):                 # absent from older experiment builds (WG_LIB_PATH, A/B runs)
-            _lib.wg_mpc_reserve.argtypes = [C.c_int]
-        if hasattr(_lib, "wg_morisawa_solve_dev"):           # absent from older experiment builds (WG_LIB_PATH, A/B runs)
-            mo_solve = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6
-            mo_sample = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int] + [C.c_void_p] * 8
-            _lib.wg_morisawa_defaults.argtypes = [C.c_void_p]
-            _lib.wg_morisawa_block_bytes.argtypes = [C.c_int]
-            _lib.wg_morisawa_block_bytes.restype = C.c_size_t
-            _lib.wg_morisawa_block_unpack.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-            _lib.wg_morisawa_length.argtypes = [C.c_void_p, C.c_int, C.c_double]
-            _lib.wg_morisawa_coshsinh.argtypes = [C.c_double, C.c_void_p, C.c_void_p]
-            _lib.wg_morisawa_system.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6
-            _lib.wg_morisawa_solve.argtypes = mo_solve
-            _lib.wg_morisawa_solve_fleet.argtypes = mo_solve
-            _lib.wg_morisawa_sample.argtypes = mo_sample
-            _lib.wg_morisawa_solve_dev.argtypes = mo_solve + [C.c_void_p]
-            _lib.wg_morisawa_solve_fleet_dev.argtypes = mo_solve + [C.c_void_p]
-            _lib.wg_morisawa_sample_dev.argtypes = mo_sample + [C.c_void_p]
-            _lib.wg_morisawa_walk_dev.argtypes = mo_solve + [C.c_double, C.c_int] + [C.c_void_p] * 9
-            _lib.wg_morisawa_walk_fleet_dev.argtypes = [C.c_void_p, C.c_double] + mo_solve[1:] + [C.c_double, C.c_int] + [C.c_void_p] * 9
-        for name in CTX_ENTRY_POINTS:
-            if not hasattr(_lib, name):
-                continue
-            base, fn = getattr(_lib, name), getattr(_lib, name + "_ctx")
-            fn.argtypes = [C.c_void_p] + list(base.argtypes or [])
-            fn.restype = base.restype
+        _lib = bind(C.CDLL(LIB_PATH))
     return _lib
 
 
-CTX_ENTRY_POINTS = ("wg_set_overlap_strict", "wg_overlap_serialised", "wg_qp_solve_batch", "wg_qp_solve_batch_dev", "wg_mpc_configure", "wg_mpc_reserve", "wg_mpc_tick_lds_bytes", "wg_mpc_tick_batch",
-                    "wg_mpc_tick_batch_dev", "wg_mpc_run_batch_dev", "wg_mpc_run_sched_dev", "wg_mpc_set_velref_dev", "wg_mpc_tick_pinned",
-                    "wg_mpc_assemble_batch", "wg_mpc_assemble_batch_dev", "wg_pldp_configure",
-                    "wg_pldp_solve_batch", "wg_pldp_solve_batch_dev", "wg_dimitrov_configure", "wg_dimitrov_get_constants", "wg_dimitrov_get_qld_constants",
-                    "wg_dimitrov_tick_batch", "wg_dimitrov_tick_batch_dev", "wg_preview_configure", "wg_preview_window",
-                    "wg_preview_run_batch", "wg_preview_run_batch_dev", "wg_gramian_batch", "wg_gramian_batch_dev",
-                    "wg_zmpdisc_batch", "wg_zmpdisc_batch_dev", "wg_zmpdisc_full_batch_dev", "wg_foot_constraints_batch_dev",
-                    "wg_zmpdisc_begin_dev", "wg_zmpdisc_append_dev", "wg_zmpdisc_end_dev",
-                    "wg_dimitrov_select_polys_dev", "wg_dimitrov_walk_dev", "wg_foot_constraints_append_dev",
-                    "wg_dimitrov_walk_time", "wg_dimitrov_walk_safe_ticks", "wg_preview_follow_dev", "wg_dimitrov_follow_dev",
-                    "wg_steps_plan_dev", "wg_riccati_gains_batch", "wg_riccati_gains_batch_dev", "wg_preview_run_fleet_dev",
-                    "wg_preview_follow_fleet_dev", "wg_dimitrov_constants_batch", "wg_dimitrov_constants_batch_dev",
-                    "wg_dimitrov_tick_fleet_dev", "wg_dimitrov_walk_fleet_dev", "wg_dimitrov_follow_fleet_dev",
-                    "wg_mpc_blocks_batch", "wg_mpc_blocks_batch_dev", "wg_mpc_tick_fleet_dev", "wg_mpc_run_fleet_dev",
-                    "wg_zmpdisc_full_fleet_dev", "wg_zmpdisc_begin_fleet_dev", "wg_zmpdisc_append_fleet_dev", "wg_zmpdisc_end_fleet_dev",
-                    "wg_steps_plan_fleet_dev", "wg_foot_constraints_fleet_dev", "wg_foot_constraints_append_fleet_dev",
-                    "wg_morisawa_solve_dev", "wg_morisawa_solve_fleet_dev", "wg_morisawa_sample_dev", "wg_morisawa_walk_dev",
-                    "wg_morisawa_walk_fleet_dev")
+def _check(rc):
+    if rc != 0:
+        raise WgError(f"wg error {rc}: {lib().wg_last_error().decode()}")
+
+
+def _raw(name, ctx, *args):
+    """NAME(*args), or NAME_ctx(ctx, *args) for a Context or a raw wg_ctx_t handle: the way every wrapper reaches the library"""
+    if ctx is None:
+        return getattr(lib(), name)(*args)
+    return getattr(lib(), name + "_ctx")(ctx.handle if isinstance(ctx, Context) else ctx, *args)
+
+
+def _call(name, ctx, *args):
+    _check(_raw(name, ctx, *args))
 
 
 class Context:
     """wg_ctx_t: one configured model with its device tables and workspaces (include/wg_mpc.h, "Contexts").  Two contexts
-    may hold different models and run overlapping launches on different streams.  Only the Herdt-tick family is wrapped
-    here (what the tests and bench.py need); every other NAME_ctx is reachable through `call`."""
+    may hold different models and run overlapping launches on different streams.  Every wrapper of an entry point with a
+    context form takes ctx=; the methods here are the Herdt-tick family by its old names, `call` the raw NAME_ctx."""
 
     def __init__(self, device=0):
         h = C.c_void_p()
@@ -282,43 +178,27 @@ class Context:
         return int(lib().wg_ctx_device(self.handle))
 
     def mpc_configure(self, model):
-        _check(self.call("wg_mpc_configure", C.byref(model)))
+        mpc_configure(model, ctx=self)
 
     def mpc_tick_lds_bytes(self):
-        return int(self.call("wg_mpc_tick_lds_bytes"))
+        return mpc_tick_lds_bytes(ctx=self)
 
     def mpc_tick_batch(self, states, want_out=True, advance_calls=0, hist_cap=0):
-        B = len(states)
-        outs = (TickOut * B)() if want_out else None
-        diag = np.zeros((B, 6), dtype=np.int32)
-        hist = np.zeros((B, hist_cap), dtype=np.int32) if hist_cap else None
-        hlen = np.zeros(B, dtype=np.int32) if hist_cap else None
-        _check(self.call("wg_mpc_tick_batch", B, C.addressof(states), C.addressof(outs) if outs is not None else None,
-                         _hp(diag), advance_calls, _hp(hist), hist_cap, _hp(hlen)))
-        return outs, diag, hist, hlen
+        return mpc_tick_batch(states, want_out, advance_calls, hist_cap, ctx=self)
 
     def mpc_tick_batch_dev(self, B, states_ptr, outs_ptr=None, diag_ptr=None, advance_calls=0, hist_ptr=None, hist_cap=0,
                            hist_len_ptr=None, stream=None):
-        v = lambda p: C.c_void_p(p) if p else None
-        _check(self.call("wg_mpc_tick_batch_dev", B, v(states_ptr), v(outs_ptr), v(diag_ptr), advance_calls, v(hist_ptr),
-                         hist_cap, v(hist_len_ptr), v(stream)))
+        mpc_tick_batch_dev(B, states_ptr, outs_ptr, diag_ptr, advance_calls, hist_ptr, hist_cap, hist_len_ptr, stream, ctx=self)
 
     def mpc_run_batch_dev(self, B, states_ptr, n_ticks, advance_calls=20, outs_ptr=None, diag_ptr=None, stream=None):
-        _check(self.call("wg_mpc_run_batch_dev", B, states_ptr, int(n_ticks), int(advance_calls), outs_ptr, diag_ptr, stream))
+        mpc_run_batch_dev(B, states_ptr, n_ticks, advance_calls, outs_ptr, diag_ptr, stream, ctx=self)
 
     def mpc_run_sched_dev(self, B, states_ptr, n_ticks, vref_sched_ptr, period, advance_calls=20, outs_ptr=None, diag_ptr=None,
                           stream=None):
-        _check(self.call("wg_mpc_run_sched_dev", B, states_ptr, int(n_ticks), int(advance_calls), vref_sched_ptr, int(period),
-                         outs_ptr, diag_ptr, stream))
+        mpc_run_sched_dev(B, states_ptr, n_ticks, vref_sched_ptr, period, advance_calls, outs_ptr, diag_ptr, stream, ctx=self)
 
     def mpc_set_velref_dev(self, B, states_ptr, vref_ptr, stream=None):
-        v = lambda p: C.c_void_p(p) if p else None
-        _check(self.call("wg_mpc_set_velref_dev", B, v(states_ptr), v(vref_ptr), v(stream)))
-
-
-def _check(rc):
-    if rc != 0:
-        raise WgError(f"wg error {rc}: {lib().wg_last_error().decode()}")
+        mpc_set_velref_dev(B, states_ptr, vref_ptr, stream, ctx=self)
 
 
 def init(device=0):
@@ -357,28 +237,25 @@ def pack_qps(qps):
     return dict(B=B, nmax=nmax, mmax=mmax, n=n, m=m, me=me, C=Cb, d=d, A=Ab, b=b, xl=xl, xu=xu)
 
 
-def qp_solve_batch(pk, eps=1e-8, hist_cap=256):
+def qp_solve_batch(pk, eps=1e-8, hist_cap=256, ctx=None):
     """Host-pointer entry point (wg_qp_solve_batch): numpy in, numpy out."""
     B, nmax, mmax = pk["B"], pk["nmax"], pk["mmax"]
     x = np.zeros((B, nmax)); u = np.zeros((B, mmax + 2 * nmax))
     ifail = np.full(B, -99, dtype=np.int32); n_iter = np.zeros(B, dtype=np.int32)
     iact = np.zeros((B, nmax), dtype=np.int32); nact = np.zeros(B, dtype=np.int32)
     hist = np.zeros((B, hist_cap), dtype=np.int32); hist_len = np.zeros(B, dtype=np.int32)
-    rc = lib().wg_qp_solve_batch(B, nmax, mmax, _hp(pk["n"]), _hp(pk["m"]), _hp(pk["me"]), _hp(pk["C"]), _hp(pk["d"]),
-                                 _hp(pk["A"]), _hp(pk["b"]), _hp(pk["xl"]), _hp(pk["xu"]), eps, _hp(x), _hp(u),
-                                 _hp(ifail), _hp(n_iter), _hp(iact), _hp(nact), _hp(hist), hist_cap, _hp(hist_len))
-    _check(rc)
+    _call("wg_qp_solve_batch", ctx, B, nmax, mmax, _hp(pk["n"]), _hp(pk["m"]), _hp(pk["me"]), _hp(pk["C"]), _hp(pk["d"]),
+          _hp(pk["A"]), _hp(pk["b"]), _hp(pk["xl"]), _hp(pk["xu"]), eps, _hp(x), _hp(u), _hp(ifail), _hp(n_iter), _hp(iact),
+          _hp(nact), _hp(hist), hist_cap, _hp(hist_len))
     return dict(x=x, u=u, ifail=ifail, n_iter=n_iter, iact=iact, nact=nact, hist=hist, hist_len=hist_len)
 
 
-def qp_solve_batch_dev(B, nmax, mmax, n, m, me, Cd, d, A, b, xl, xu, eps, x, u, ifail, n_iter=None, iact=None,
-                       nact=None, hist=None, hist_cap=0, hist_len=None, stream=None):
+def qp_solve_batch_dev(B, nmax, mmax, n, m, me, Cd, d, A, b, xl, xu, eps, x, u, ifail, n_iter=None, iact=None, nact=None,
+                       hist=None, hist_cap=0, hist_len=None, stream=None, ctx=None):
     """Device-pointer entry point (wg_qp_solve_batch_dev).  Arguments are torch CUDA tensors or None."""
     p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-    rc = lib().wg_qp_solve_batch_dev(B, nmax, mmax, p(n), p(m), p(me), p(Cd), p(d), p(A), p(b), p(xl), p(xu), eps,
-                                     p(x), p(u), p(ifail), p(n_iter), p(iact), p(nact), p(hist), hist_cap,
-                                     p(hist_len), C.c_void_p(stream) if stream else None)
-    _check(rc)
+    _call("wg_qp_solve_batch_dev", ctx, B, nmax, mmax, p(n), p(m), p(me), p(Cd), p(d), p(A), p(b), p(xl), p(xu), eps, p(x),
+          p(u), p(ifail), p(n_iter), p(iact), p(nact), p(hist), hist_cap, p(hist_len), C.c_void_p(stream) if stream else None)
 
 
 # ---------------------------------------------------------------------------
@@ -397,8 +274,8 @@ def gait_init(model, com0, left_xyt, right_xyt):
     return s
 
 
-def mpc_configure(model):
-    _check(lib().wg_mpc_configure(C.byref(model)))
+def mpc_configure(model, ctx=None):
+    _call("wg_mpc_configure", ctx, C.byref(model))
 
 
 def mpc_tick_lds_bytes_for(model):
@@ -406,24 +283,23 @@ def mpc_tick_lds_bytes_for(model):
     return int(lib().wg_mpc_tick_lds_bytes_for(C.byref(model)))
 
 
-def mpc_tick_lds_bytes():
-    return int(lib().wg_mpc_tick_lds_bytes())
+def mpc_tick_lds_bytes(ctx=None):
+    return int(_raw("wg_mpc_tick_lds_bytes", ctx))
 
 
-def mpc_tick_batch(states, want_out=True, advance_calls=0, hist_cap=0):
+def mpc_tick_batch(states, want_out=True, advance_calls=0, hist_cap=0, ctx=None):
     """Host-pointer entry point.  `states` is a ctypes array (GaitState * B), updated in place."""
     B = len(states)
     outs = (TickOut * B)() if want_out else None
     diag = np.zeros((B, 6), dtype=np.int32)
     hist = np.zeros((B, hist_cap), dtype=np.int32) if hist_cap else None
     hlen = np.zeros(B, dtype=np.int32) if hist_cap else None
-    rc = lib().wg_mpc_tick_batch(B, C.addressof(states), C.addressof(outs) if outs is not None else None, _hp(diag),
-                                 advance_calls, _hp(hist), hist_cap, _hp(hlen))
-    _check(rc)
+    _call("wg_mpc_tick_batch", ctx, B, C.addressof(states), C.addressof(outs) if outs is not None else None, _hp(diag),
+          advance_calls, _hp(hist), hist_cap, _hp(hlen))
     return outs, diag, hist, hlen
 
 
-def mpc_assemble_batch(states, advance_calls=0, nmax=None, mmax=None, model=None):
+def mpc_assemble_batch(states, advance_calls=0, nmax=None, mmax=None, model=None, ctx=None):
     """The QP of every gait's next tick as QPProblem::solve hands it to ql0001_ (wg_mpc_assemble_batch): a pack_qps-style
     dict (C, d, A, b, xl, xu column-major with strides nmax / mmax, n, m, me) ready for qp_solve_batch.  `states` is a ctypes
     array (GaitState * B), not modified."""
@@ -433,8 +309,8 @@ def mpc_assemble_batch(states, advance_calls=0, nmax=None, mmax=None, model=None
     mmax = mmax or 1 + 4 * N + 20 + 1
     Cb = np.zeros((B, nmax * nmax)); Ab = np.zeros((B, mmax * nmax)); d = np.zeros((B, nmax)); b = np.zeros((B, mmax))
     xl = np.zeros((B, nmax)); xu = np.zeros((B, nmax)); n = np.zeros(B, dtype=np.int32); m = np.zeros(B, dtype=np.int32)
-    _check(lib().wg_mpc_assemble_batch(B, C.addressof(states), int(advance_calls), nmax, mmax, _hp(Cb), _hp(d), _hp(Ab), _hp(b),
-                                       _hp(xl), _hp(xu), _hp(n), _hp(m)))
+    _call("wg_mpc_assemble_batch", ctx, B, C.addressof(states), int(advance_calls), nmax, mmax, _hp(Cb), _hp(d), _hp(Ab),
+          _hp(b), _hp(xl), _hp(xu), _hp(n), _hp(m))
     return dict(B=B, nmax=nmax, mmax=mmax, n=n, m=m, me=np.zeros(B, dtype=np.int32), C=Cb, d=d, A=Ab, b=b, xl=xl, xu=xu)
 
 
@@ -452,8 +328,7 @@ class HostMapped:
         self.diag = (C.c_int * 6).from_address(p.value + C.sizeof(GaitState) + C.sizeof(TickOut))
 
     def tick(self, advance_calls=0, ctx=None):
-        args = (C.addressof(self.state), C.addressof(self.out), C.addressof(self.diag), int(advance_calls))
-        _check(ctx.call("wg_mpc_tick_pinned", *args) if ctx is not None else lib().wg_mpc_tick_pinned(*args))
+        _call("wg_mpc_tick_pinned", ctx, C.addressof(self.state), C.addressof(self.out), C.addressof(self.diag), int(advance_calls))
 
     def close(self):
         if self.ptr:
@@ -462,28 +337,29 @@ class HostMapped:
 
 
 def mpc_tick_batch_dev(B, states_ptr, outs_ptr=None, diag_ptr=None, advance_calls=0, hist_ptr=None, hist_cap=0,
-                       hist_len_ptr=None, stream=None):
+                       hist_len_ptr=None, stream=None, ctx=None):
     """Device-pointer entry point; pointers are plain ints (e.g. torch tensor.data_ptr())."""
     v = lambda p: C.c_void_p(p) if p else None
-    _check(lib().wg_mpc_tick_batch_dev(B, v(states_ptr), v(outs_ptr), v(diag_ptr), advance_calls, v(hist_ptr), hist_cap,
-                                       v(hist_len_ptr), v(stream)))
+    _call("wg_mpc_tick_batch_dev", ctx, B, v(states_ptr), v(outs_ptr), v(diag_ptr), advance_calls, v(hist_ptr), hist_cap,
+          v(hist_len_ptr), v(stream))
 
 
-def mpc_run_batch_dev(B, states_ptr, n_ticks, advance_calls=20, outs_ptr=None, diag_ptr=None, stream=None):
+def mpc_run_batch_dev(B, states_ptr, n_ticks, advance_calls=20, outs_ptr=None, diag_ptr=None, stream=None, ctx=None):
     """n_ticks ticks of every gait in one launch (device-side work queue); device pointers as integers."""
-    _check(lib().wg_mpc_run_batch_dev(B, states_ptr, int(n_ticks), int(advance_calls), outs_ptr, diag_ptr, stream))
+    _call("wg_mpc_run_batch_dev", ctx, B, states_ptr, int(n_ticks), int(advance_calls), outs_ptr, diag_ptr, stream)
 
 
-def mpc_run_sched_dev(B, states_ptr, n_ticks, vref_sched_ptr, period, advance_calls=20, outs_ptr=None, diag_ptr=None, stream=None):
+def mpc_run_sched_dev(B, states_ptr, n_ticks, vref_sched_ptr, period, advance_calls=20, outs_ptr=None, diag_ptr=None,
+                      stream=None, ctx=None):
     """mpc_run_batch_dev with the velocity references staged ahead: block t // period of vref_sched (ceil(n_ticks / period)
     x B x 3 doubles on the device) takes effect before tick t = 0, period, 2 period, ... of the launch."""
-    _check(lib().wg_mpc_run_sched_dev(B, states_ptr, int(n_ticks), int(advance_calls), vref_sched_ptr, int(period), outs_ptr,
-                                      diag_ptr, stream))
+    _call("wg_mpc_run_sched_dev", ctx, B, states_ptr, int(n_ticks), int(advance_calls), vref_sched_ptr, int(period), outs_ptr,
+          diag_ptr, stream)
 
 
-def mpc_set_velref_dev(B, states_ptr, vref_ptr, stream=None):
+def mpc_set_velref_dev(B, states_ptr, vref_ptr, stream=None, ctx=None):
     v = lambda p: C.c_void_p(p) if p else None
-    _check(lib().wg_mpc_set_velref_dev(B, v(states_ptr), v(vref_ptr), v(stream)))
+    _call("wg_mpc_set_velref_dev", ctx, B, v(states_ptr), v(vref_ptr), v(stream))
 
 
 RICCATI_WITH_INITIALPOS = 0
@@ -523,17 +399,17 @@ class PldpState(C.Structure):           # wg_pldp_state_t
                 ("prev_zmp", C.c_double * (2 * PLDP_N)), ("internal_time", C.c_double)]
 
 
-def pldp_configure(N, iPu, Px, Pu):
+def pldp_configure(N, iPu, Px, Pu, ctx=None):
     iPu = np.ascontiguousarray(iPu, dtype=np.float64); Px = np.ascontiguousarray(Px, dtype=np.float64)
     Pu = np.ascontiguousarray(Pu, dtype=np.float64)
-    _check(lib().wg_pldp_configure(int(N), _hp(iPu), _hp(Px), _hp(Pu)))
+    _call("wg_pldp_configure", ctx, int(N), _hp(iPu), _hp(Px), _hp(Pu))
 
 
 def pldp_lds_bytes():
     return int(lib().wg_pldp_lds_bytes())
 
 
-def pldp_solve_batch(N, mcap, m, D, A, b, zmpref, xkyk, similar, n_removed, starting, states, max_iter=0):
+def pldp_solve_batch(N, mcap, m, D, A, b, zmpref, xkyk, similar, n_removed, starting, states, max_iter=0, ctx=None):
     """Host-pointer batch solve.  Arrays follow include/wg_mpc.h (A: B x (mcap+1)*2N flat slots, leading dimension
     m[b]+1 inside a slot); `states` is a ctypes array of PldpState, updated in place."""
     B = len(m)
@@ -546,9 +422,8 @@ def pldp_solve_batch(N, mcap, m, D, A, b, zmpref, xkyk, similar, n_removed, star
     assert A.size == B * (mcap + 1) * n and b.size == B * mcap and similar.size == B * mcap
     X = np.zeros((B, n)); ret = np.zeros(B, dtype=np.int32); nit = np.zeros(B, dtype=np.int32)
     act = np.zeros((B, mcap), dtype=np.int32); nact = np.zeros(B, dtype=np.int32)
-    _check(lib().wg_pldp_solve_batch(B, int(mcap), _hp(m), _hp(D), _hp(A), _hp(b), _hp(zmpref), _hp(xkyk), _hp(similar),
-                                     _hp(n_removed), _hp(starting), int(max_iter), C.addressof(states), _hp(X), _hp(ret),
-                                     _hp(nit), _hp(act), _hp(nact)))
+    _call("wg_pldp_solve_batch", ctx, B, int(mcap), _hp(m), _hp(D), _hp(A), _hp(b), _hp(zmpref), _hp(xkyk), _hp(similar),
+          _hp(n_removed), _hp(starting), int(max_iter), C.addressof(states), _hp(X), _hp(ret), _hp(nit), _hp(act), _hp(nact))
     return dict(X=X, ret=ret, n_iter=nit, active=[act[i, :nact[i]].copy() for i in range(B)])
 
 
@@ -582,32 +457,32 @@ def dimitrov_defaults():
     return m
 
 
-def dimitrov_configure(model):
-    _check(lib().wg_dimitrov_configure(C.byref(model)))
+def dimitrov_configure(model, ctx=None):
+    _call("wg_dimitrov_configure", ctx, C.byref(model))
 
 
-def dimitrov_constants(N):
+def dimitrov_constants(N, ctx=None):
     n = 2 * N
     iLQ = np.zeros((n, n)); OptB = np.zeros((n, 6)); OptC = np.zeros((n, n))
     Pu = np.zeros((N, N)); iPu = np.zeros((N, N)); Px = np.zeros((N, 3))
-    _check(lib().wg_dimitrov_get_constants(_hp(iLQ), _hp(OptB), _hp(OptC), _hp(Pu), _hp(iPu), _hp(Px)))
+    _call("wg_dimitrov_get_constants", ctx, _hp(iLQ), _hp(OptB), _hp(OptC), _hp(Pu), _hp(iPu), _hp(Px))
     return dict(iLQ=iLQ, OptB=OptB, OptC=OptC, Pu=Pu, iPu=iPu, Px=Px)
 
 
-def dimitrov_qld_constants(N):
+def dimitrov_qld_constants(N, ctx=None):
     """what mode QLD hands to ql0001_ and builds its cost vector from: Q (column-major 2N x 2N), OptB / OptC as built, Pu'"""
     n = 2 * N
     Q = np.zeros((n, n)); OptB = np.zeros((n, 6)); OptC = np.zeros((n, n)); PuT = np.zeros((N, N))
-    _check(lib().wg_dimitrov_get_qld_constants(_hp(Q), _hp(OptB), _hp(OptC), _hp(PuT)))
+    _call("wg_dimitrov_get_qld_constants", ctx, _hp(Q), _hp(OptB), _hp(OptC), _hp(PuT))
     return dict(Q=Q, OptB=OptB, OptC=OptC, PuT=PuT)
 
 
-def dimitrov_tick_batch(polys, states, want_out=True, max_iter=0):
+def dimitrov_tick_batch(polys, states, want_out=True, max_iter=0, ctx=None):
     """polys: ctypes array (ZmpPolytope * (B*N)), states: (DimitrovState * B), updated in place."""
     B = len(states)
     outs = (DimitrovOut * B)() if want_out else None
-    _check(lib().wg_dimitrov_tick_batch(B, C.addressof(polys), C.addressof(states),
-                                        C.addressof(outs) if outs is not None else None, int(max_iter)))
+    _call("wg_dimitrov_tick_batch", ctx, B, C.addressof(polys), C.addressof(states),
+          C.addressof(outs) if outs is not None else None, int(max_iter))
     return outs
 
 
@@ -631,35 +506,35 @@ def preview_gains(T, zc, preview_time, mode=RICCATI_WITHOUT_INITIALPOS):
     return g, np.ascontiguousarray(F)
 
 
-def preview_configure(gains, F):
+def preview_configure(gains, F, ctx=None):
     F = np.ascontiguousarray(F, dtype=np.float64)
     assert F.shape == (gains.nl,)
-    _check(lib().wg_preview_configure(C.byref(gains), _hp(F)))
+    _call("wg_preview_configure", ctx, C.byref(gains), _hp(F))
 
 
-def preview_run_batch(zmp_x, zmp_y, state, L, simulation=True, want_com=True, want_zmp=True):
+def preview_run_batch(zmp_x, zmp_y, state, L, simulation=True, want_com=True, want_zmp=True, ctx=None):
     """Host-pointer entry point: zmp_x/zmp_y [B, L+nl-1], state [B, 8] (advanced in place).  Returns (com, zmp2)."""
     zmp_x = np.ascontiguousarray(zmp_x, dtype=np.float64); zmp_y = np.ascontiguousarray(zmp_y, dtype=np.float64)
     B = zmp_x.shape[0]
-    nl = int(lib().wg_preview_window())
+    nl = int(_raw("wg_preview_window", ctx))
     assert zmp_x.shape == zmp_y.shape == (B, L + nl - 1) and state.shape == (B, 8) and state.flags.c_contiguous
     com = np.zeros((B, L, 6)) if want_com else None
     z2 = np.zeros((B, L, 2)) if want_zmp else None
-    _check(lib().wg_preview_run_batch(B, L, _hp(zmp_x), _hp(zmp_y), _hp(state), _hp(com), _hp(z2), int(bool(simulation))))
+    _call("wg_preview_run_batch", ctx, B, L, _hp(zmp_x), _hp(zmp_y), _hp(state), _hp(com), _hp(z2), int(bool(simulation)))
     return com, z2
 
 
 def preview_run_batch_dev(B, L, zx_tm_ptr, zy_tm_ptr, state_ptr, com_tm_ptr=None, zmp2_tm_ptr=None, simulation=True,
-                          stream=None):
-    _check(lib().wg_preview_run_batch_dev(B, L, zx_tm_ptr, zy_tm_ptr, state_ptr, com_tm_ptr, zmp2_tm_ptr,
-                                          int(bool(simulation)), stream))
+                          stream=None, ctx=None):
+    _call("wg_preview_run_batch_dev", ctx, B, L, zx_tm_ptr, zy_tm_ptr, state_ptr, com_tm_ptr, zmp2_tm_ptr,
+          int(bool(simulation)), stream)
 
 
 def preview_follow_dev(B, lcap, length_ptr, done_ptr, zx_tm_ptr, zy_tm_ptr, state_ptr, com_tm_ptr=None, zmp2_tm_ptr=None,
-                       simulation=True, stream=None):
+                       simulation=True, stream=None, ctx=None):
     """every gait over the rows its own queue has made safe: steps [done[b], length[b] - nl + 1), absolute rows (wg_mpc.h)"""
-    _check(lib().wg_preview_follow_dev(B, lcap, length_ptr, done_ptr, zx_tm_ptr, zy_tm_ptr, state_ptr, com_tm_ptr, zmp2_tm_ptr,
-                                       int(bool(simulation)), stream))
+    _call("wg_preview_follow_dev", ctx, B, lcap, length_ptr, done_ptr, zx_tm_ptr, zy_tm_ptr, state_ptr, com_tm_ptr, zmp2_tm_ptr,
+          int(bool(simulation)), stream)
 
 
 # ---- Kajita fleets with a CoM height per gait: gains made on the device, preview with gains per gait ----
@@ -675,36 +550,36 @@ def preview_fleet(T, nl, zc_ptr, K_tm_ptr, F_tm_ptr):
     return f
 
 
-def riccati_gains_batch(T, zc, Q, R, Nl, mode):
+def riccati_gains_batch(T, zc, Q, R, Nl, mode, ctx=None):
     """wg_riccati_gains for every height of zc [B], on the device -> (K [B, 4], F [B, Nl], status [B]); host-pointer entry point."""
     zc = np.ascontiguousarray(zc, dtype=np.float64)
     B = zc.shape[0]
     K = np.zeros((B, 4))
     F = np.zeros((B, int(Nl)))
     status = np.zeros(B, dtype=np.int32)
-    _check(lib().wg_riccati_gains_batch(B, float(T), _hp(zc), float(Q), float(R), int(Nl), int(mode), _hp(K),
-                                        _hp(F) if Nl > 0 else None, _hp(status)))
+    _call("wg_riccati_gains_batch", ctx, B, float(T), _hp(zc), float(Q), float(R), int(Nl), int(mode), _hp(K),
+          _hp(F) if Nl > 0 else None, _hp(status))
     return K, F, status
 
 
-def riccati_gains_batch_dev(B, T, zc_ptr, Q, R, Nl, mode, K_tm_ptr, F_tm_ptr, status_ptr, stream=None):
+def riccati_gains_batch_dev(B, T, zc_ptr, Q, R, Nl, mode, K_tm_ptr, F_tm_ptr, status_ptr, stream=None, ctx=None):
     """one lane per gait: K_tm [4][B], F_tm [Nl][B] time-major, status [B] (all device pointers)"""
-    _check(lib().wg_riccati_gains_batch_dev(B, float(T), zc_ptr, float(Q), float(R), int(Nl), int(mode), K_tm_ptr, F_tm_ptr,
-                                            status_ptr, stream))
+    _call("wg_riccati_gains_batch_dev", ctx, B, float(T), zc_ptr, float(Q), float(R), int(Nl), int(mode), K_tm_ptr, F_tm_ptr,
+          status_ptr, stream)
 
 
 def preview_run_fleet_dev(B, L, fleet, zx_tm_ptr, zy_tm_ptr, state_ptr, com_tm_ptr=None, zmp2_tm_ptr=None, simulation=True,
-                          stream=None):
+                          stream=None, ctx=None):
     """wg_preview_run_batch_dev with the gains of `fleet` (a PreviewFleet) per gait instead of the context's"""
-    _check(lib().wg_preview_run_fleet_dev(B, L, C.addressof(fleet), zx_tm_ptr, zy_tm_ptr, state_ptr, com_tm_ptr, zmp2_tm_ptr,
-                                          int(bool(simulation)), stream))
+    _call("wg_preview_run_fleet_dev", ctx, B, L, C.addressof(fleet), zx_tm_ptr, zy_tm_ptr, state_ptr, com_tm_ptr, zmp2_tm_ptr,
+          int(bool(simulation)), stream)
 
 
 def preview_follow_fleet_dev(B, lcap, length_ptr, done_ptr, fleet, zx_tm_ptr, zy_tm_ptr, state_ptr, com_tm_ptr=None,
-                             zmp2_tm_ptr=None, simulation=True, stream=None):
+                             zmp2_tm_ptr=None, simulation=True, stream=None, ctx=None):
     """wg_preview_follow_dev with the gains of `fleet` (a PreviewFleet) per gait instead of the context's"""
-    _check(lib().wg_preview_follow_fleet_dev(B, lcap, length_ptr, done_ptr, C.addressof(fleet), zx_tm_ptr, zy_tm_ptr, state_ptr,
-                                             com_tm_ptr, zmp2_tm_ptr, int(bool(simulation)), stream))
+    _call("wg_preview_follow_fleet_dev", ctx, B, lcap, length_ptr, done_ptr, C.addressof(fleet), zx_tm_ptr, zy_tm_ptr,
+          state_ptr, com_tm_ptr, zmp2_tm_ptr, int(bool(simulation)), stream)
 
 
 # ---- Kajita stage-1 inputs: ZMPDiscretization, batched; FootConstraintsAsLinearSystem (host) ----
@@ -742,7 +617,7 @@ def zmpdisc_length(model, steps, n_steps=None):
     return int(lib().wg_zmpdisc_length(C.byref(model), C.addressof(steps), len(steps) if n_steps is None else int(n_steps)))
 
 
-def zmpdisc_batch(model, steps, n_steps, init_feet, smax, lcap, want_feet=True):
+def zmpdisc_batch(model, steps, n_steps, init_feet, smax, lcap, want_feet=True, ctx=None):
     """steps: (RelStep * (B*smax)); n_steps [B]; init_feet [B, 6].  Returns a dict of arrays and `length` [B]."""
     n_steps = np.ascontiguousarray(n_steps, dtype=np.int32); B = n_steps.shape[0]
     init_feet = np.ascontiguousarray(init_feet, dtype=np.float64)
@@ -753,16 +628,15 @@ def zmpdisc_batch(model, steps, n_steps, init_feet, smax, lcap, want_feet=True):
         r.update(left=np.zeros((B, lcap, 6)), right=np.zeros((B, lcap, 6)), left_type=np.zeros((B, lcap), np.int32),
                  right_type=np.zeros((B, lcap), np.int32))
     g = lambda k: _hp(r[k]) if k in r else None  # noqa: E731
-    _check(lib().wg_zmpdisc_batch(C.byref(model), B, int(smax), C.addressof(steps), _hp(n_steps), _hp(init_feet), int(lcap),
-                                  g("zmp"), g("zmp_theta"), g("zmp_type"), g("left"), g("left_type"), g("right"),
-                                  g("right_type"), _hp(r["length"])))
+    _call("wg_zmpdisc_batch", ctx, C.byref(model), B, int(smax), C.addressof(steps), _hp(n_steps), _hp(init_feet), int(lcap),
+          g("zmp"), g("zmp_theta"), g("zmp_type"), g("left"), g("left_type"), g("right"), g("right_type"), _hp(r["length"]))
     return r
 
 
 def zmpdisc_batch_dev(model, B, smax, steps_ptr, n_steps_ptr, init_feet_ptr, lcap, zx_tm_ptr, zy_tm_ptr, length_ptr,
-                      stream=None):
-    _check(lib().wg_zmpdisc_batch_dev(C.byref(model), int(B), int(smax), steps_ptr, n_steps_ptr, init_feet_ptr, int(lcap),
-                                      zx_tm_ptr, zy_tm_ptr, length_ptr, stream))
+                      stream=None, ctx=None):
+    _call("wg_zmpdisc_batch_dev", ctx, C.byref(model), int(B), int(smax), steps_ptr, n_steps_ptr, init_feet_ptr, int(lcap),
+          zx_tm_ptr, zy_tm_ptr, length_ptr, stream)
 
 
 # ---- the same walk on line: begin, any number of appends, end (include/wg_mpc.h, "steps as they arrive") ----
@@ -792,23 +666,23 @@ def _zd_outs(outs):
 
 
 def zmpdisc_begin_dev(model, B, smax, steps_ptr, n_steps_ptr, init_feet_ptr, lcap, outs, state_ptr, length_ptr=None,
-                      stream=None):
+                      stream=None, ctx=None):
     """InitOnLine on the first n_steps[b] >= 2 steps.  `outs`: device pointers by name (ZMPDISC_OUTPUTS, time-major as
     wg_zmpdisc_full_batch_dev writes them), absent = not wanted; the same set goes to every call of the walk."""
-    _check(lib().wg_zmpdisc_begin_dev(C.byref(model), int(B), int(smax), steps_ptr, n_steps_ptr, init_feet_ptr, int(lcap),
-                                      *_zd_outs(outs), state_ptr, length_ptr, stream))
+    _call("wg_zmpdisc_begin_dev", ctx, C.byref(model), int(B), int(smax), steps_ptr, n_steps_ptr, init_feet_ptr, int(lcap),
+          *_zd_outs(outs), state_ptr, length_ptr, stream)
 
 
-def zmpdisc_append_dev(model, B, smax, steps_ptr, n_steps_ptr, lcap, outs, state_ptr, length_ptr=None, stream=None):
+def zmpdisc_append_dev(model, B, smax, steps_ptr, n_steps_ptr, lcap, outs, state_ptr, length_ptr=None, stream=None, ctx=None):
     """OnLineAddFoot on n_steps[b] >= 0 further steps (`steps`: those of this call, [B][smax]); 0 = the gait sits it out"""
-    _check(lib().wg_zmpdisc_append_dev(C.byref(model), int(B), int(smax), steps_ptr, n_steps_ptr, int(lcap), *_zd_outs(outs),
-                                       state_ptr, length_ptr, stream))
+    _call("wg_zmpdisc_append_dev", ctx, C.byref(model), int(B), int(smax), steps_ptr, n_steps_ptr, int(lcap), *_zd_outs(outs),
+          state_ptr, length_ptr, stream)
 
 
-def zmpdisc_end_dev(model, B, lcap, outs, state_ptr, length_ptr=None, select_ptr=None, stream=None):
+def zmpdisc_end_dev(model, B, lcap, outs, state_ptr, length_ptr=None, select_ptr=None, stream=None, ctx=None):
     """EndPhaseOfTheWalking for every gait, or for those with select[b] != 0"""
-    _check(lib().wg_zmpdisc_end_dev(C.byref(model), int(B), select_ptr, int(lcap), *_zd_outs(outs), state_ptr, length_ptr,
-                                    stream))
+    _call("wg_zmpdisc_end_dev", ctx, C.byref(model), int(B), select_ptr, int(lcap), *_zd_outs(outs), state_ptr, length_ptr,
+          stream)
 
 
 # ---- the same walks with a model per gait (include/wg_mpc.h, "The same walks with a model per gait") ----
@@ -825,26 +699,28 @@ def zmpdisc_fleet(base, M, models_ptr, model_of_ptr=None):
     return ZmpDiscFleet(base, int(M), 0, models_ptr, model_of_ptr)
 
 
-def zmpdisc_full_fleet_dev(fleet, B, smax, steps_ptr, n_steps_ptr, init_feet_ptr, lcap, outs, length_ptr=None, stream=None):
+def zmpdisc_full_fleet_dev(fleet, B, smax, steps_ptr, n_steps_ptr, init_feet_ptr, lcap, outs, length_ptr=None, stream=None,
+                           ctx=None):
     """wg_zmpdisc_full_batch_dev with a model per gait; `outs` as in zmpdisc_begin_dev"""
-    _check(lib().wg_zmpdisc_full_fleet_dev(C.byref(fleet), int(B), int(smax), steps_ptr, n_steps_ptr, init_feet_ptr, int(lcap),
-                                           *_zd_outs(outs), length_ptr, stream))
+    _call("wg_zmpdisc_full_fleet_dev", ctx, C.byref(fleet), int(B), int(smax), steps_ptr, n_steps_ptr, init_feet_ptr, int(lcap),
+          *_zd_outs(outs), length_ptr, stream)
 
 
 def zmpdisc_begin_fleet_dev(fleet, B, smax, steps_ptr, n_steps_ptr, init_feet_ptr, lcap, outs, state_ptr, length_ptr=None,
-                            stream=None):
-    _check(lib().wg_zmpdisc_begin_fleet_dev(C.byref(fleet), int(B), int(smax), steps_ptr, n_steps_ptr, init_feet_ptr, int(lcap),
-                                            *_zd_outs(outs), state_ptr, length_ptr, stream))
+                            stream=None, ctx=None):
+    _call("wg_zmpdisc_begin_fleet_dev", ctx, C.byref(fleet), int(B), int(smax), steps_ptr, n_steps_ptr, init_feet_ptr,
+          int(lcap), *_zd_outs(outs), state_ptr, length_ptr, stream)
 
 
-def zmpdisc_append_fleet_dev(fleet, B, smax, steps_ptr, n_steps_ptr, lcap, outs, state_ptr, length_ptr=None, stream=None):
-    _check(lib().wg_zmpdisc_append_fleet_dev(C.byref(fleet), int(B), int(smax), steps_ptr, n_steps_ptr, int(lcap),
-                                             *_zd_outs(outs), state_ptr, length_ptr, stream))
+def zmpdisc_append_fleet_dev(fleet, B, smax, steps_ptr, n_steps_ptr, lcap, outs, state_ptr, length_ptr=None, stream=None,
+                             ctx=None):
+    _call("wg_zmpdisc_append_fleet_dev", ctx, C.byref(fleet), int(B), int(smax), steps_ptr, n_steps_ptr, int(lcap),
+          *_zd_outs(outs), state_ptr, length_ptr, stream)
 
 
-def zmpdisc_end_fleet_dev(fleet, B, lcap, outs, state_ptr, length_ptr=None, select_ptr=None, stream=None):
-    _check(lib().wg_zmpdisc_end_fleet_dev(C.byref(fleet), int(B), select_ptr, int(lcap), *_zd_outs(outs), state_ptr, length_ptr,
-                                          stream))
+def zmpdisc_end_fleet_dev(fleet, B, lcap, outs, state_ptr, length_ptr=None, select_ptr=None, stream=None, ctx=None):
+    _call("wg_zmpdisc_end_fleet_dev", ctx, C.byref(fleet), int(B), select_ptr, int(lcap), *_zd_outs(outs), state_ptr,
+          length_ptr, stream)
 
 
 # ---- the step stack: command lists -> the steps the zmpdisc calls read (include/wg_mpc.h, "Where the steps come from") ----
@@ -883,23 +759,17 @@ def steps_plan(cmds, n_cmds, ss, ds, stack, smax, steps=None):
     return steps, n.value
 
 
-def steps_plan_dev(B, ccap, cmds_ptr, n_cmds_ptr, ss, ds, stack_ptr, smax, steps_ptr, n_steps_ptr, stream=None):
+def steps_plan_dev(B, ccap, cmds_ptr, n_cmds_ptr, ss, ds, stack_ptr, smax, steps_ptr, n_steps_ptr, stream=None, ctx=None):
     """the same for B gaits on the device: cmds [B][ccap], n_cmds [B], stack [B] in/out, steps [B][smax], n_steps [B]"""
-    _check(lib().wg_steps_plan_dev(int(B), int(ccap), cmds_ptr, n_cmds_ptr, float(ss), float(ds), stack_ptr, int(smax), steps_ptr,
-                                   n_steps_ptr, stream))
+    _call("wg_steps_plan_dev", ctx, int(B), int(ccap), cmds_ptr, n_cmds_ptr, float(ss), float(ds), stack_ptr, int(smax),
+          steps_ptr, n_steps_ptr, stream)
 
 
-def steps_plan_dev_ctx(ctx, B, ccap, cmds_ptr, n_cmds_ptr, ss, ds, stack_ptr, smax, steps_ptr, n_steps_ptr, stream=None):
-    """the same on a Context (or a raw wg_ctx_t handle)"""
-    h = ctx.handle if isinstance(ctx, Context) else ctx
-    _check(lib().wg_steps_plan_dev_ctx(h, int(B), int(ccap), cmds_ptr, n_cmds_ptr, float(ss), float(ds), stack_ptr, int(smax),
-                                       steps_ptr, n_steps_ptr, stream))
-
-
-def steps_plan_fleet_dev(B, ccap, cmds_ptr, n_cmds_ptr, ss_ptr, ds_ptr, stack_ptr, smax, steps_ptr, n_steps_ptr, stream=None):
+def steps_plan_fleet_dev(B, ccap, cmds_ptr, n_cmds_ptr, ss_ptr, ds_ptr, stack_ptr, smax, steps_ptr, n_steps_ptr, stream=None,
+                         ctx=None):
     """steps_plan_dev with the support times of each gait: ss, ds [B] on the device"""
-    _check(lib().wg_steps_plan_fleet_dev(int(B), int(ccap), cmds_ptr, n_cmds_ptr, ss_ptr, ds_ptr, stack_ptr, int(smax), steps_ptr,
-                                         n_steps_ptr, stream))
+    _call("wg_steps_plan_fleet_dev", ctx, int(B), int(ccap), cmds_ptr, n_cmds_ptr, ss_ptr, ds_ptr, stack_ptr, int(smax),
+          steps_ptr, n_steps_ptr, stream)
 
 
 def foot_constraints(time, left, left_type, right, sole_w, sole_h, constraint_x, constraint_y, cap=256):
@@ -924,24 +794,23 @@ def foot_constraints_chunk():
 
 
 def foot_constraints_batch_dev(B, lcap, length_ptr, time_ptr, left_tm_ptr, left_type_tm_ptr, right_tm_ptr, sole_w, sole_h,
-                               constraint_x, constraint_y, qcap, queues_ptr, t_start_ptr, t_end_ptr, count_ptr, stream=None):
+                               constraint_x, constraint_y, qcap, queues_ptr, t_start_ptr, t_end_ptr, count_ptr, stream=None,
+                               ctx=None):
     """wg_foot_constraints for B gaits whose feet wg_zmpdisc_full_batch_dev left on the device: queues / t_start / t_end
     [B][qcap], count [B]."""
-    _check(lib().wg_foot_constraints_batch_dev(int(B), int(lcap), length_ptr, time_ptr, left_tm_ptr, left_type_tm_ptr,
-                                               right_tm_ptr, float(sole_w), float(sole_h), float(constraint_x),
-                                               float(constraint_y), int(qcap), queues_ptr, t_start_ptr, t_end_ptr, count_ptr,
-                                               stream))
+    _call("wg_foot_constraints_batch_dev", ctx, int(B), int(lcap), length_ptr, time_ptr, left_tm_ptr, left_type_tm_ptr,
+          right_tm_ptr, float(sole_w), float(sole_h), float(constraint_x), float(constraint_y), int(qcap), queues_ptr,
+          t_start_ptr, t_end_ptr, count_ptr, stream)
 
 
-def foot_constraints_append_dev(B, lcap, first_sample, done_ptr, length_ptr, time_ptr, left_tm_ptr, left_type_tm_ptr, right_tm_ptr,
-                                sole_w, sole_h, constraint_x, constraint_y, qcap, queues_ptr, t_start_ptr, t_end_ptr, count_ptr,
-                                stream=None):
+def foot_constraints_append_dev(B, lcap, first_sample, done_ptr, length_ptr, time_ptr, left_tm_ptr, left_type_tm_ptr,
+                                right_tm_ptr, sole_w, sole_h, constraint_x, constraint_y, qcap, queues_ptr, t_start_ptr,
+                                t_end_ptr, count_ptr, stream=None, ctx=None):
     """the same queues grown on line: samples [done[b], length[b]) of every gait are added, done[b] = length[b] afterwards;
     first_sample is a host-side lower bound on every done[b] (0 is always valid)"""
-    _check(lib().wg_foot_constraints_append_dev(int(B), int(lcap), int(first_sample), done_ptr, length_ptr, time_ptr, left_tm_ptr,
-                                                left_type_tm_ptr, right_tm_ptr, float(sole_w), float(sole_h), float(constraint_x),
-                                                float(constraint_y), int(qcap), queues_ptr, t_start_ptr, t_end_ptr, count_ptr,
-                                                stream))
+    _call("wg_foot_constraints_append_dev", ctx, int(B), int(lcap), int(first_sample), done_ptr, length_ptr, time_ptr,
+          left_tm_ptr, left_type_tm_ptr, right_tm_ptr, float(sole_w), float(sole_h), float(constraint_x), float(constraint_y),
+          int(qcap), queues_ptr, t_start_ptr, t_end_ptr, count_ptr, stream)
 
 
 class Sole(C.Structure):                # wg_sole_t
@@ -952,68 +821,51 @@ SOLE_BYTES = 32
 
 
 def foot_constraints_fleet_dev(B, lcap, length_ptr, time_ptr, left_tm_ptr, left_type_tm_ptr, right_tm_ptr, soles_ptr, qcap,
-                               queues_ptr, t_start_ptr, t_end_ptr, count_ptr, stream=None):
+                               queues_ptr, t_start_ptr, t_end_ptr, count_ptr, stream=None, ctx=None):
     """foot_constraints_batch_dev with a sole per gait: soles (Sole * B) on the device"""
-    _check(lib().wg_foot_constraints_fleet_dev(int(B), int(lcap), length_ptr, time_ptr, left_tm_ptr, left_type_tm_ptr,
-                                               right_tm_ptr, soles_ptr, int(qcap), queues_ptr, t_start_ptr, t_end_ptr, count_ptr,
-                                               stream))
+    _call("wg_foot_constraints_fleet_dev", ctx, int(B), int(lcap), length_ptr, time_ptr, left_tm_ptr, left_type_tm_ptr,
+          right_tm_ptr, soles_ptr, int(qcap), queues_ptr, t_start_ptr, t_end_ptr, count_ptr, stream)
 
 
 def foot_constraints_append_fleet_dev(B, lcap, first_sample, done_ptr, length_ptr, time_ptr, left_tm_ptr, left_type_tm_ptr,
-                                      right_tm_ptr, soles_ptr, qcap, queues_ptr, t_start_ptr, t_end_ptr, count_ptr, stream=None):
+                                      right_tm_ptr, soles_ptr, qcap, queues_ptr, t_start_ptr, t_end_ptr, count_ptr, stream=None,
+                                      ctx=None):
     """foot_constraints_append_dev with a sole per gait"""
-    _check(lib().wg_foot_constraints_append_fleet_dev(int(B), int(lcap), int(first_sample), done_ptr, length_ptr, time_ptr,
-                                                      left_tm_ptr, left_type_tm_ptr, right_tm_ptr, soles_ptr, int(qcap), queues_ptr,
-                                                      t_start_ptr, t_end_ptr, count_ptr, stream))
+    _call("wg_foot_constraints_append_fleet_dev", ctx, int(B), int(lcap), int(first_sample), done_ptr, length_ptr, time_ptr,
+          left_tm_ptr, left_type_tm_ptr, right_tm_ptr, soles_ptr, int(qcap), queues_ptr, t_start_ptr, t_end_ptr, count_ptr,
+          stream)
 
 
 def dimitrov_select_polys_dev(B, qcap, queues_ptr, t_start_ptr, t_end_ptr, count_ptr, t0, polys_ptr, ran_out_ptr=None,
-                              stream=None):
+                              stream=None, ctx=None):
     """the queue walk of one tick: polys [B][N] for wg_dimitrov_tick_batch_dev, ran_out [B] or None"""
-    _check(lib().wg_dimitrov_select_polys_dev(int(B), int(qcap), queues_ptr, t_start_ptr, t_end_ptr, count_ptr, float(t0),
-                                              polys_ptr, ran_out_ptr, stream))
+    _call("wg_dimitrov_select_polys_dev", ctx, int(B), int(qcap), queues_ptr, t_start_ptr, t_end_ptr, count_ptr, float(t0),
+          polys_ptr, ran_out_ptr, stream)
 
 
-def dimitrov_tick_batch_dev(B, polys_ptr, states_ptr, outs_ptr=None, max_iter=0, stream=None):
-    _check(lib().wg_dimitrov_tick_batch_dev(int(B), polys_ptr, states_ptr, outs_ptr, int(max_iter), stream))
+def dimitrov_tick_batch_dev(B, polys_ptr, states_ptr, outs_ptr=None, max_iter=0, stream=None, ctx=None):
+    _call("wg_dimitrov_tick_batch_dev", ctx, int(B), polys_ptr, states_ptr, outs_ptr, int(max_iter), stream)
 
 
 def dimitrov_walk_dev(B, qcap, queues_ptr, t_start_ptr, t_end_ptr, count_ptr, t0, n_ticks, states_ptr, outs_ptr=None,
-                      ran_out_ptr=None, max_iter=0, stream=None):
+                      ran_out_ptr=None, max_iter=0, stream=None, ctx=None):
     """n_ticks x { select at t; tick; t += T } on one stream; outs [n_ticks][B] or None, ran_out [B] or None"""
-    _check(lib().wg_dimitrov_walk_dev(int(B), int(qcap), queues_ptr, t_start_ptr, t_end_ptr, count_ptr, float(t0), int(n_ticks),
-                                      states_ptr, outs_ptr, ran_out_ptr, int(max_iter), stream))
+    _call("wg_dimitrov_walk_dev", ctx, int(B), int(qcap), queues_ptr, t_start_ptr, t_end_ptr, count_ptr, float(t0),
+          int(n_ticks), states_ptr, outs_ptr, ran_out_ptr, int(max_iter), stream)
 
 
 DIMITROV_FOLLOW_ALL_FINAL = 1
 
 
-def _dimitrov_follow_args(B, qcap, queues_ptr, t_start_ptr, t_end_ptr, count_ptr, lcap, time_ptr, have_ptr, walk_ptr, flags,
-                          clock_ptr, ticks_ptr, tick_cap, max_ticks, states_ptr, outs_ptr, ran_out_ptr, max_iter, stream):
-    return (int(B), int(qcap), queues_ptr, t_start_ptr, t_end_ptr, count_ptr, int(lcap), time_ptr, have_ptr, walk_ptr, int(flags),
-            clock_ptr, ticks_ptr, int(tick_cap), int(max_ticks), states_ptr, outs_ptr, ran_out_ptr, int(max_iter), stream)
-
-
 def dimitrov_follow_dev(B, qcap, queues_ptr, t_start_ptr, t_end_ptr, count_ptr, lcap, time_ptr, have_ptr, walk_ptr, flags,
                         clock_ptr, ticks_ptr, tick_cap, max_ticks, states_ptr, outs_ptr=None, ran_out_ptr=None, max_iter=0,
-                        stream=None):
+                        stream=None, ctx=None):
     """max_ticks rounds of { select; tick } in which gait b ticks at its own clock[b] while its own queue covers the tick
     (or is final: walk[b] ended, or DIMITROV_FOLLOW_ALL_FINAL) and ticks[b] < tick_cap; outs [tick_cap][B], absolute rows;
     ran_out is ORed, never cleared (wg_mpc.h)"""
-    _check(lib().wg_dimitrov_follow_dev(*_dimitrov_follow_args(B, qcap, queues_ptr, t_start_ptr, t_end_ptr, count_ptr, lcap,
-                                                               time_ptr, have_ptr, walk_ptr, flags, clock_ptr, ticks_ptr, tick_cap,
-                                                               max_ticks, states_ptr, outs_ptr, ran_out_ptr, max_iter, stream)))
-
-
-def dimitrov_follow_dev_ctx(ctx, B, qcap, queues_ptr, t_start_ptr, t_end_ptr, count_ptr, lcap, time_ptr, have_ptr, walk_ptr, flags,
-                            clock_ptr, ticks_ptr, tick_cap, max_ticks, states_ptr, outs_ptr=None, ran_out_ptr=None, max_iter=0,
-                            stream=None):
-    """the same on a Context (or a raw wg_ctx_t handle)"""
-    h = ctx.handle if isinstance(ctx, Context) else ctx
-    _check(lib().wg_dimitrov_follow_dev_ctx(h, *_dimitrov_follow_args(B, qcap, queues_ptr, t_start_ptr, t_end_ptr, count_ptr, lcap,
-                                                                      time_ptr, have_ptr, walk_ptr, flags, clock_ptr, ticks_ptr,
-                                                                      tick_cap, max_ticks, states_ptr, outs_ptr, ran_out_ptr,
-                                                                      max_iter, stream)))
+    _call("wg_dimitrov_follow_dev", ctx, int(B), int(qcap), queues_ptr, t_start_ptr, t_end_ptr, count_ptr, int(lcap), time_ptr,
+          have_ptr, walk_ptr, int(flags), clock_ptr, ticks_ptr, int(tick_cap), int(max_ticks), states_ptr, outs_ptr,
+          ran_out_ptr, int(max_iter), stream)
 
 
 # ---- Dimitrov fleets with a model per gait: the constants as blocks, the fleet launches (wg_mpc.h) ----
@@ -1049,19 +901,19 @@ def dimitrov_constants_unpack(block):
     return out
 
 
-def dimitrov_constants_batch(base, M, com_height=None, alpha=None, beta=None):
+def dimitrov_constants_batch(base, M, com_height=None, alpha=None, beta=None, ctx=None):
     """(blocks [M][bytes] uint8, status [M]) of M models through the device, host arrays in and out"""
     arr = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (com_height, alpha, beta)]
     blocks = np.zeros((M, dimitrov_constants_bytes()), dtype=np.uint8)
     status = np.zeros(M, dtype=np.int32)
-    _check(lib().wg_dimitrov_constants_batch(int(M), C.byref(base), _hp(arr[0]), _hp(arr[1]), _hp(arr[2]), _hp(blocks), _hp(status)))
+    _call("wg_dimitrov_constants_batch", ctx, int(M), C.byref(base), _hp(arr[0]), _hp(arr[1]), _hp(arr[2]), _hp(blocks), _hp(status))
     return blocks, status
 
 
-def dimitrov_constants_batch_dev(M, base, com_height_ptr, alpha_ptr, beta_ptr, blocks_ptr, status_ptr, stream=None):
+def dimitrov_constants_batch_dev(M, base, com_height_ptr, alpha_ptr, beta_ptr, blocks_ptr, status_ptr, stream=None, ctx=None):
     """M blocks and M status ints on the device; a per-model array that is None takes its value from base"""
-    _check(lib().wg_dimitrov_constants_batch_dev(int(M), C.byref(base), com_height_ptr, alpha_ptr, beta_ptr, blocks_ptr, status_ptr,
-                                                 stream))
+    _call("wg_dimitrov_constants_batch_dev", ctx, int(M), C.byref(base), com_height_ptr, alpha_ptr, beta_ptr, blocks_ptr,
+          status_ptr, stream)
 
 
 def dimitrov_fleet(base, M, blocks_ptr, model_of_ptr):
@@ -1069,38 +921,38 @@ def dimitrov_fleet(base, M, blocks_ptr, model_of_ptr):
     return DimitrovFleet(int(base.N), int(base.solver), int(M), 0, float(base.T), float(base.Tctrl), blocks_ptr, model_of_ptr)
 
 
-def dimitrov_tick_fleet_dev(B, fleet, polys_ptr, states_ptr, outs_ptr=None, max_iter=0, stream=None):
+def dimitrov_tick_fleet_dev(B, fleet, polys_ptr, states_ptr, outs_ptr=None, max_iter=0, stream=None, ctx=None):
     """dimitrov_tick_batch_dev with blocks[model_of[g]] as gait g's model; no configured model is read"""
-    _check(lib().wg_dimitrov_tick_fleet_dev(int(B), C.byref(fleet), polys_ptr, states_ptr, outs_ptr, int(max_iter), stream))
+    _call("wg_dimitrov_tick_fleet_dev", ctx, int(B), C.byref(fleet), polys_ptr, states_ptr, outs_ptr, int(max_iter), stream)
 
 
-def dimitrov_walk_fleet_dev(B, fleet, qcap, queues_ptr, t_start_ptr, t_end_ptr, count_ptr, t0, n_ticks, states_ptr, outs_ptr=None,
-                            ran_out_ptr=None, max_iter=0, stream=None):
+def dimitrov_walk_fleet_dev(B, fleet, qcap, queues_ptr, t_start_ptr, t_end_ptr, count_ptr, t0, n_ticks, states_ptr,
+                            outs_ptr=None, ran_out_ptr=None, max_iter=0, stream=None, ctx=None):
     """dimitrov_walk_dev with a model per gait"""
-    _check(lib().wg_dimitrov_walk_fleet_dev(int(B), C.byref(fleet), int(qcap), queues_ptr, t_start_ptr, t_end_ptr, count_ptr,
-                                            float(t0), int(n_ticks), states_ptr, outs_ptr, ran_out_ptr, int(max_iter), stream))
+    _call("wg_dimitrov_walk_fleet_dev", ctx, int(B), C.byref(fleet), int(qcap), queues_ptr, t_start_ptr, t_end_ptr, count_ptr,
+          float(t0), int(n_ticks), states_ptr, outs_ptr, ran_out_ptr, int(max_iter), stream)
 
 
 def dimitrov_follow_fleet_dev(B, fleet, qcap, queues_ptr, t_start_ptr, t_end_ptr, count_ptr, lcap, time_ptr, have_ptr, walk_ptr,
                               flags, clock_ptr, ticks_ptr, tick_cap, max_ticks, states_ptr, outs_ptr=None, ran_out_ptr=None,
-                              max_iter=0, stream=None):
+                              max_iter=0, stream=None, ctx=None):
     """dimitrov_follow_dev with a model per gait"""
-    a = _dimitrov_follow_args(B, qcap, queues_ptr, t_start_ptr, t_end_ptr, count_ptr, lcap, time_ptr, have_ptr, walk_ptr, flags,
-                              clock_ptr, ticks_ptr, tick_cap, max_ticks, states_ptr, outs_ptr, ran_out_ptr, max_iter, stream)
-    _check(lib().wg_dimitrov_follow_fleet_dev(a[0], C.byref(fleet), *a[1:]))
+    _call("wg_dimitrov_follow_fleet_dev", ctx, int(B), C.byref(fleet), int(qcap), queues_ptr, t_start_ptr, t_end_ptr, count_ptr,
+          int(lcap), time_ptr, have_ptr, walk_ptr, int(flags), clock_ptr, ticks_ptr, int(tick_cap), int(max_ticks), states_ptr,
+          outs_ptr, ran_out_ptr, int(max_iter), stream)
 
 
-def dimitrov_walk_time(t0, n_ticks):
+def dimitrov_walk_time(t0, n_ticks, ctx=None):
     """the t at which tick n_ticks of a walk started at t0 selects (the walk's own repeated addition of the configured T)"""
-    t = float(lib().wg_dimitrov_walk_time(float(t0), int(n_ticks)))
+    t = float(_raw("wg_dimitrov_walk_time", ctx, float(t0), int(n_ticks)))
     if t != t:
         raise WgError("dimitrov_walk_time: " + lib().wg_last_error().decode())
     return t
 
 
-def dimitrov_walk_safe_ticks(t0, t_have):
+def dimitrov_walk_safe_ticks(t0, t_have, ctx=None):
     """ticks from t0 on whose N previewed instants all lie at or before t_have"""
-    n = int(lib().wg_dimitrov_walk_safe_ticks(float(t0), float(t_have)))
+    n = int(_raw("wg_dimitrov_walk_safe_ticks", ctx, float(t0), float(t_have)))
     _check(min(n, 0))
     return n
 
@@ -1147,19 +999,19 @@ def mpc_block_unpack(block):
     return out
 
 
-def mpc_blocks_batch(models):
+def mpc_blocks_batch(models, ctx=None):
     """(blocks [M][bytes] uint8, status [M]) of the models through the device, host arrays in and out"""
     M = len(models)
     arr = (Model * M)(*models)
     blocks = np.zeros((M, mpc_block_bytes()), dtype=np.uint8)
     status = np.zeros(M, dtype=np.int32)
-    _check(lib().wg_mpc_blocks_batch(M, C.addressof(arr), _hp(blocks), _hp(status)))
+    _call("wg_mpc_blocks_batch", ctx, M, C.addressof(arr), _hp(blocks), _hp(status))
     return blocks, status
 
 
-def mpc_blocks_batch_dev(M, models_ptr, blocks_ptr, status_ptr, stream=None):
+def mpc_blocks_batch_dev(M, models_ptr, blocks_ptr, status_ptr, stream=None, ctx=None):
     """M blocks and M status ints on the device from M wg_model_t on the device"""
-    _check(lib().wg_mpc_blocks_batch_dev(int(M), models_ptr, blocks_ptr, status_ptr, stream))
+    _call("wg_mpc_blocks_batch_dev", ctx, int(M), models_ptr, blocks_ptr, status_ptr, stream)
 
 
 def mpc_fleet(base, M, blocks_ptr, model_of_ptr):
@@ -1174,20 +1026,15 @@ def _fleet_ref(fleet):
 def mpc_tick_fleet_dev(B, fleet, states_ptr, outs_ptr=None, diag_ptr=None, advance_calls=0, hist_ptr=None, hist_cap=0,
                        hist_len_ptr=None, stream=None, ctx=None):
     """mpc_tick_batch_dev with blocks[model_of[g]] as gait g's model; no configured model is read.  Returns the raw code."""
-    args = (int(B), _fleet_ref(fleet), states_ptr, outs_ptr, diag_ptr, int(advance_calls), hist_ptr, int(hist_cap), hist_len_ptr, stream)
-    if ctx is not None:
-        return int(lib().wg_mpc_tick_fleet_dev_ctx(ctx.handle if isinstance(ctx, Context) else ctx, *args))
-    return int(lib().wg_mpc_tick_fleet_dev(*args))
+    return int(_raw("wg_mpc_tick_fleet_dev", ctx, int(B), _fleet_ref(fleet), states_ptr, outs_ptr, diag_ptr, int(advance_calls), hist_ptr,
+                    int(hist_cap), hist_len_ptr, stream))
 
 
-def mpc_run_fleet_dev(B, fleet, states_ptr, n_ticks, advance_calls=20, vref_sched_ptr=None, period=1, outs_ptr=None, diag_ptr=None,
-                      stream=None, ctx=None):
+def mpc_run_fleet_dev(B, fleet, states_ptr, n_ticks, advance_calls=20, vref_sched_ptr=None, period=1, outs_ptr=None,
+                      diag_ptr=None, stream=None, ctx=None):
     """mpc_run_sched_dev with a model per gait (vref_sched_ptr None: the unstaged run).  Returns the raw code."""
-    args = (int(B), _fleet_ref(fleet), states_ptr, int(n_ticks), int(advance_calls), vref_sched_ptr, int(period), outs_ptr, diag_ptr,
-            stream)
-    if ctx is not None:
-        return int(lib().wg_mpc_run_fleet_dev_ctx(ctx.handle if isinstance(ctx, Context) else ctx, *args))
-    return int(lib().wg_mpc_run_fleet_dev(*args))
+    return int(_raw("wg_mpc_run_fleet_dev", ctx, int(B), _fleet_ref(fleet), states_ptr, int(n_ticks), int(advance_calls), vref_sched_ptr,
+                    int(period), outs_ptr, diag_ptr, stream))
 
 
 # ---- invariant Hessian block on the matrix cores ----
@@ -1195,12 +1042,12 @@ GRAMIAN_F64 = 0
 GRAMIAN_F32 = 1
 
 
-def gramian_batch(N, T, h, alpha, beta, gamma, precision=GRAMIAN_F64):
+def gramian_batch(N, T, h, alpha, beta, gamma, precision=GRAMIAN_F64, ctx=None):
     """Q_b[B, N, N] for models with sampling periods T[B] and CoM heights h[B] (wg_gramian_batch)."""
     T = np.ascontiguousarray(T, dtype=np.float64); h = np.ascontiguousarray(h, dtype=np.float64)
     B = T.shape[0]
     Qb = np.zeros((B, N, N))
-    _check(lib().wg_gramian_batch(B, int(N), _hp(T), _hp(h), alpha, beta, gamma, int(precision), _hp(Qb)))
+    _call("wg_gramian_batch", ctx, B, int(N), _hp(T), _hp(h), alpha, beta, gamma, int(precision), _hp(Qb))
     return Qb
 
 
@@ -1314,29 +1161,29 @@ def _mo_outs(outs):
     return [outs.get(k) for k in MORISAWA_OUTPUTS]
 
 
-def morisawa_solve_dev(model, B, smax, steps_ptr, n_steps_ptr, init_feet_ptr, com0_ptr, blocks_ptr, status_ptr, stream=None):
+def morisawa_solve_dev(model, B, smax, steps_ptr, n_steps_ptr, init_feet_ptr, com0_ptr, blocks_ptr, status_ptr, stream=None,
+                       ctx=None):
     """every pointer a device pointer; `model`: a MorisawaModel (host), or a device pointer to B of them (the fleet form)"""
     if isinstance(model, MorisawaModel):
-        _check(lib().wg_morisawa_solve_dev(C.addressof(model), int(B), int(smax), steps_ptr, n_steps_ptr, init_feet_ptr, com0_ptr,
-                                           blocks_ptr, status_ptr, stream))
+        _call("wg_morisawa_solve_dev", ctx, C.addressof(model), int(B), int(smax), steps_ptr, n_steps_ptr, init_feet_ptr,
+              com0_ptr, blocks_ptr, status_ptr, stream)
     else:
-        _check(lib().wg_morisawa_solve_fleet_dev(model, int(B), int(smax), steps_ptr, n_steps_ptr, init_feet_ptr, com0_ptr,
-                                                 blocks_ptr, status_ptr, stream))
+        _call("wg_morisawa_solve_fleet_dev", ctx, model, int(B), int(smax), steps_ptr, n_steps_ptr, init_feet_ptr, com0_ptr,
+              blocks_ptr, status_ptr, stream)
 
 
-def morisawa_sample_dev(B, smax, blocks_ptr, status_ptr, t_start, T, lcap, outs, length_ptr=None, stream=None):
+def morisawa_sample_dev(B, smax, blocks_ptr, status_ptr, t_start, T, lcap, outs, length_ptr=None, stream=None, ctx=None):
     """`outs`: device pointers by name (MORISAWA_OUTPUTS, time-major), absent = not wanted"""
-    _check(lib().wg_morisawa_sample_dev(int(B), int(smax), blocks_ptr, status_ptr, float(t_start), float(T), int(lcap),
-                                        *_mo_outs(outs), length_ptr, stream))
+    _call("wg_morisawa_sample_dev", ctx, int(B), int(smax), blocks_ptr, status_ptr, float(t_start), float(T), int(lcap),
+          *_mo_outs(outs), length_ptr, stream)
 
 
-def morisawa_walk_dev(model, B, smax, steps_ptr, n_steps_ptr, init_feet_ptr, com0_ptr, blocks_ptr, status_ptr, t_start, lcap, outs,
-                      length_ptr=None, stream=None, T=None):
+def morisawa_walk_dev(model, B, smax, steps_ptr, n_steps_ptr, init_feet_ptr, com0_ptr, blocks_ptr, status_ptr, t_start, lcap,
+                      outs, length_ptr=None, stream=None, T=None, ctx=None):
     """solve and sample on one stream; `model` as in morisawa_solve_dev, the fleet form needs the common sampling period T"""
     if isinstance(model, MorisawaModel):
-        _check(lib().wg_morisawa_walk_dev(C.addressof(model), int(B), int(smax), steps_ptr, n_steps_ptr, init_feet_ptr, com0_ptr,
-                                          blocks_ptr, status_ptr, float(t_start), int(lcap), *_mo_outs(outs), length_ptr, stream))
+        _call("wg_morisawa_walk_dev", ctx, C.addressof(model), int(B), int(smax), steps_ptr, n_steps_ptr, init_feet_ptr,
+              com0_ptr, blocks_ptr, status_ptr, float(t_start), int(lcap), *_mo_outs(outs), length_ptr, stream)
     else:
-        _check(lib().wg_morisawa_walk_fleet_dev(model, float(T), int(B), int(smax), steps_ptr, n_steps_ptr, init_feet_ptr, com0_ptr,
-                                                blocks_ptr, status_ptr, float(t_start), int(lcap), *_mo_outs(outs), length_ptr,
-                                                stream))
+        _call("wg_morisawa_walk_fleet_dev", ctx, model, float(T), int(B), int(smax), steps_ptr, n_steps_ptr, init_feet_ptr,
+              com0_ptr, blocks_ptr, status_ptr, float(t_start), int(lcap), *_mo_outs(outs), length_ptr, stream)

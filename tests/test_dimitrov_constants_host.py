@@ -31,7 +31,7 @@ def test_symbols_and_abi():
     lib = wg.lib()
     for name in NEW:
         assert hasattr(lib, name) and hasattr(lib, name + "_ctx"), name
-        assert name in wg.CTX_ENTRY_POINTS
+        assert getattr(lib, name + "_ctx").argtypes == [C.c_void_p] + getattr(lib, name).argtypes       # bound as a context form
     for name in ("wg_dimitrov_constants_bytes", "wg_dimitrov_constants", "wg_dimitrov_constants_unpack"):
         assert hasattr(lib, name), name
     assert lib.wg_abi_version() == 5

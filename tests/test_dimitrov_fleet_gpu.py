@@ -371,10 +371,10 @@ def follow_reference(fleet, solver, n_ticks=N_TICKS):
                 q = subset(Qfull, idx)
                 have = fleet["ln"][torch.from_numpy(idx).cuda()].contiguous()
                 A = arrays(len(idx), n_ticks)
-                wg.dimitrov_follow_dev_ctx(c, len(idx), QCAP, q["queues"].data_ptr(), q["ts"].data_ptr(), q["te"].data_ptr(),
-                                           q["count"].data_ptr(), int(fleet["time"].shape[0]), fleet["time"].data_ptr(), have.data_ptr(),
-                                           None, FINAL, A["clock"].data_ptr(), A["ticks"].data_ptr(), n_ticks, n_ticks, A["st"].data_ptr(),
-                                           A["outs"].data_ptr(), A["ran"].data_ptr(), 0, _stream())
+                wg.dimitrov_follow_dev(len(idx), QCAP, q["queues"].data_ptr(), q["ts"].data_ptr(), q["te"].data_ptr(),
+                                       q["count"].data_ptr(), int(fleet["time"].shape[0]), fleet["time"].data_ptr(), have.data_ptr(),
+                                       None, FINAL, A["clock"].data_ptr(), A["ticks"].data_ptr(), n_ticks, n_ticks, A["st"].data_ptr(),
+                                       A["outs"].data_ptr(), A["ran"].data_ptr(), 0, _stream(), ctx=c)
                 h = host(A)
                 assert (h["ticks"] == n_ticks).all()
                 ref["st"][idx], ref["outs"][:, idx], ref["ran"][idx], ref["clock"][idx] = h["st"], h["outs"], h["ran"], h["clock"]

@@ -2,7 +2,9 @@
 (wg_zmpdisc_length_after, the shared time array, N = 16, T = 0.1) does on the 70-gait fleet what the GPU tests of
 tests/test_dimitrov_follow_gpu.py rely on -- ragged tick counts, sit-outs beside advancers, gaits ahead of the lock-step walk.
 `feeding` and `replay` are what those tests hold the device's tick counts to."""
+import ctypes as C
 import importlib
+import inspect
 import os
 import sys
 
@@ -81,8 +83,9 @@ def replay(fleet, K, cap=N_TICKS, N=N_HORIZON, T=T_TICK):
 def test_follow_entry_points_exist_and_the_abi_version_stays():
     lib = wg.lib()
     assert hasattr(lib, "wg_dimitrov_follow_dev") and hasattr(lib, "wg_dimitrov_follow_dev_ctx")
-    assert callable(wg.dimitrov_follow_dev) and callable(wg.dimitrov_follow_dev_ctx) and wg.DIMITROV_FOLLOW_ALL_FINAL == 1
-    assert "wg_dimitrov_follow_dev" in wg.CTX_ENTRY_POINTS
+    assert callable(wg.dimitrov_follow_dev) and wg.DIMITROV_FOLLOW_ALL_FINAL == 1
+    assert "ctx" in inspect.signature(wg.dimitrov_follow_dev).parameters       # the context form: ctx= a Context or a raw handle
+    assert lib.wg_dimitrov_follow_dev_ctx.argtypes == [C.c_void_p] + lib.wg_dimitrov_follow_dev.argtypes
     assert len(lib.wg_dimitrov_follow_dev_ctx.argtypes) == len(lib.wg_dimitrov_follow_dev.argtypes) + 1 == 21
     assert lib.wg_abi_version() == 5
 

@@ -321,8 +321,8 @@ def test_empty_batches_and_bad_arguments():
         d = DevStack(3, 8, 1)
         raw, n = sp.cmd_bytes([sp.CIRCLE] * 3, 3)
         d_cmds, d_n = d.t.from_numpy(raw).cuda(), d.t.from_numpy(n).cuda()
-        wg.steps_plan_dev_ctx(ctx, 3, 3, d_cmds.data_ptr(), d_n.data_ptr(), sp.SS, sp.DS, d.stack[1:].data_ptr(), 8, d.steps[1:].data_ptr(),
-                              d.n[1:].data_ptr())
+        wg.steps_plan_dev(3, 3, d_cmds.data_ptr(), d_n.data_ptr(), sp.SS, sp.DS, d.stack[1:].data_ptr(), 8, d.steps[1:].data_ptr(),
+                          d.n[1:].data_ptr(), ctx=ctx)
         rows, n, st = d.read()
         assert (n == 5).all() and np.array_equal(rows[2, :5], sp.oracle_list(sp.CIRCLE)[0])
 

@@ -23,10 +23,8 @@ assert g.nl == nl
 wg.preview_configure(g, F)
 parent = None
 if os.environ.get("PARENT_LIB"):
-    parent = C.CDLL(os.environ["PARENT_LIB"])
+    parent = wg.bind(C.CDLL(os.environ["PARENT_LIB"]))                   # this header's signatures on what the parent exports
     assert not hasattr(parent, "wg_preview_run_fleet_dev"), "PARENT_LIB already has the fleet forms"
-    parent.wg_preview_configure.argtypes = [C.c_void_p, C.c_void_p]
-    parent.wg_preview_run_batch_dev.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]
     assert parent.wg_init(0) == 0 and parent.wg_preview_configure(C.byref(g), F.ctypes.data) == 0
 rng = np.random.default_rng(2003)
 steps = (wg.RelStep * (B * S))()

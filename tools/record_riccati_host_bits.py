@@ -11,6 +11,7 @@ Eight cases: T in {0.005, 0.01} x zc in {0.6, 0.814} x both modes, Nl = 320, Q =
 No device is needed: wg_riccati_gains is host arithmetic.
 """
 import ctypes as C
+import importlib
 import os
 import sys
 
@@ -26,8 +27,8 @@ def r_of(mode):
 
 
 def record(lib_path):
-    lib = C.CDLL(lib_path)
-    lib.wg_riccati_gains.argtypes = [C.c_double] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    sys.path.insert(0, ROOT)
+    lib = importlib.import_module("jrl-walkgen_amd").bind(C.CDLL(lib_path))      # signatures from include/wg_mpc.h
     K = np.zeros((len(CASES), 4))
     F = np.zeros((len(CASES), NL))
     for i, (T, zc, mode) in enumerate(CASES):
