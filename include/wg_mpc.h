@@ -1275,7 +1275,9 @@ typedef struct wg_morisawa_view {
   const double *wx, *wy, *yx, *yy;    /* [n] */
   const int *piv;                     /* [n] row k was swapped with row piv[k] >= k (LAPACK's ipiv, 0-based) */
   const double *lu;                   /* P Z = L U, unit L below the diagonal; rows lu_pitch apart */
-  int lu_pitch, pad_;
+  int lu_pitch, pad_;                 /* a long block (wg_morisawa_long_block_unpack): lu_pitch = 16 and lu is the ROW BAND, entry
+                                         (i, c) at lu[16 i + c - i + 5] for i - 5 <= c <= i + 9, with dgbtf2's multipliers: not
+                                         swapped by later steps.  piv reads the same.  See wg_morisawa_long_* below */
 } wg_morisawa_view_t;
 #define WG_MORISAWA_MODEL_BYTES 40
 #define WG_MORISAWA_VIEW_BYTES 232
@@ -1319,6 +1321,54 @@ int wg_morisawa_walk_fleet_dev(const wg_morisawa_model_t *models, double T, int 
                                const int *n_steps, const double *init_feet, const double *com0, void *blocks, int *status,
                                double t_start, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *com_tm, double *left_tm,
                                int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream);
+
+/* Morisawa walks of up to WG_MORISAWA_LONG_MAX_STEPS steps: a second family next to the first, wg_morisawa_long_* ---------------
+ *
+ * The same walk, the same arguments, statuses, refusals and outputs as the calls above with `_long` in the name; what differs is
+ * how Z y = w is solved and what a block holds behind the pivots.  Z's non-zeros lie within 5 below and 4 above the diagonal
+ * whatever S is, so the long family eliminates inside the band: the pivot of column k is looked for in rows k .. k + 5, a row
+ * update covers columns k + 1 .. k + 9.  It takes the pivots of the dense elimination and gives the same values (products with
+ * structural zeros are all it leaves out; a zero may differ in sign), so for smax <= WG_MORISAWA_MAX_STEPS the two families agree
+ * by value in every sample.  A long block is wg_morisawa_long_block_bytes(smax) bytes: the short block's sections in the short
+ * block's order up to the pivots, then the factor in ROW-BAND form, n rows 16 doubles apart: row i holds columns i - 5 .. i + 9
+ * in its words 0 .. 14 (column c at word c - i + 5; what falls outside the matrix and word 15 are zero).  wg_morisawa_long_block_
+ * unpack fills the same wg_morisawa_view_t with lu at the band and lu_pitch = 16.  The convention is LAPACK's dgbtf2: step k swaps
+ * rows k and piv[k] over columns k .. k + 9 only, so the multipliers of column k (rows k + 1 .. k + 5, words left of the diagonal)
+ * stay at the positions where they were made and are NOT swapped by later steps.  A new right-hand side b is solved as dgbtrs
+ * does: for k = 0 .. n - 2 swap b[k] and b[piv[k]], then b[i] -= lu(i, k) b[k] for i = k + 1 .. min(n - 1, k + 5); then, for c from
+ * n - 1 down, b[c] /= lu(c, c) and b[i] -= lu(i, c) b[c] for i = max(0, c - 9) .. c - 1.  The int at byte 32 of a long block (the
+ * header's first word behind the two doubles, zero in a short block) is 1; wg_morisawa_long_sample* refuse a block without it
+ * (WG_MORISAWA_BAD_INPUT), and a short block or one of another smax with it.  wg_morisawa_long_system writes Z before the
+ * elimination in that row-band form, n x 16.  Blocks of the two families are not interchangeable. */
+#define WG_MORISAWA_LONG_MAX_STEPS 64   /* n = 4 S + 8 = 264 */
+size_t wg_morisawa_long_block_bytes(int smax);            /* a multiple of 128; 0 for an smax outside [2, 64] */
+int wg_morisawa_long_block_unpack(const void *block, int smax, wg_morisawa_view_t *view);
+int wg_morisawa_long_length(const wg_morisawa_model_t *model, int n_steps, double t_start);
+int wg_morisawa_long_system(const wg_morisawa_model_t *model, int n_steps, const wg_rel_step_t *steps, const double *init_feet,
+                            const double *com0, double *Zband, double *wx, double *wy);
+int wg_morisawa_long_solve(const wg_morisawa_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps,
+                           const double *init_feet, const double *com0, void *blocks, int *status);
+int wg_morisawa_long_solve_fleet(const wg_morisawa_model_t *models, int B, int smax, const wg_rel_step_t *steps,
+                                 const int *n_steps, const double *init_feet, const double *com0, void *blocks, int *status);
+int wg_morisawa_long_sample(int B, int smax, const void *blocks, const int *status, double t_start, double T, int lcap,
+                            double *zmp_x_tm, double *zmp_y_tm, double *com_tm, double *left_tm, int *left_type_tm,
+                            double *right_tm, int *right_type_tm, int *length);
+int wg_morisawa_long_solve_dev(const wg_morisawa_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps,
+                               const double *init_feet, const double *com0, void *blocks, int *status, void *hip_stream);
+int wg_morisawa_long_solve_fleet_dev(const wg_morisawa_model_t *models, int B, int smax, const wg_rel_step_t *steps,
+                                     const int *n_steps, const double *init_feet, const double *com0, void *blocks, int *status,
+                                     void *hip_stream);
+int wg_morisawa_long_sample_dev(int B, int smax, const void *blocks, const int *status, double t_start, double T, int lcap,
+                                double *zmp_x_tm, double *zmp_y_tm, double *com_tm, double *left_tm, int *left_type_tm,
+                                double *right_tm, int *right_type_tm, int *length, void *hip_stream);
+int wg_morisawa_long_walk_dev(const wg_morisawa_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps,
+                              const double *init_feet, const double *com0, void *blocks, int *status, double t_start, int lcap,
+                              double *zmp_x_tm, double *zmp_y_tm, double *com_tm, double *left_tm, int *left_type_tm,
+                              double *right_tm, int *right_type_tm, int *length, void *hip_stream);
+int wg_morisawa_long_walk_fleet_dev(const wg_morisawa_model_t *models, double T, int B, int smax, const wg_rel_step_t *steps,
+                                    const int *n_steps, const double *init_feet, const double *com0, void *blocks, int *status,
+                                    double t_start, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *com_tm, double *left_tm,
+                                    int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream);
 
 /* The context forms of the entry points above (same arguments after the context, same semantics) ----------------------------
  *
@@ -1492,6 +1542,23 @@ int wg_dimitrov_follow_fleet_dev_ctx(wg_ctx_t *ctx, int B, const wg_dimitrov_fle
     int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream), (model, B, smax, steps, n_steps, init_feet, com0, blocks, \
     status, t_start, lcap, zmp_x_tm, zmp_y_tm, com_tm, left_tm, left_type_tm, right_tm, right_type_tm, length, hip_stream)) \
   X(int, wg_morisawa_walk_fleet_dev, (const wg_morisawa_model_t *models, double T, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, \
+    const double *init_feet, const double *com0, void *blocks, int *status, double t_start, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *com_tm, \
+    double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream), (models, T, B, smax, steps, n_steps, init_feet, \
+    com0, blocks, status, t_start, lcap, zmp_x_tm, zmp_y_tm, com_tm, left_tm, left_type_tm, right_tm, right_type_tm, length, hip_stream)) \
+  X(int, wg_morisawa_long_solve_dev, (const wg_morisawa_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, \
+    const double *init_feet, const double *com0, void *blocks, int *status, void *hip_stream), (model, B, smax, steps, n_steps, init_feet, com0, blocks, \
+    status, hip_stream)) \
+  X(int, wg_morisawa_long_solve_fleet_dev, (const wg_morisawa_model_t *models, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, \
+    const double *init_feet, const double *com0, void *blocks, int *status, void *hip_stream), (models, B, smax, steps, n_steps, init_feet, com0, blocks, \
+    status, hip_stream)) \
+  X(int, wg_morisawa_long_sample_dev, (int B, int smax, const void *blocks, const int *status, double t_start, double T, int lcap, double *zmp_x_tm, \
+    double *zmp_y_tm, double *com_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream), (B, smax, \
+    blocks, status, t_start, T, lcap, zmp_x_tm, zmp_y_tm, com_tm, left_tm, left_type_tm, right_tm, right_type_tm, length, hip_stream)) \
+  X(int, wg_morisawa_long_walk_dev, (const wg_morisawa_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, \
+    const double *init_feet, const double *com0, void *blocks, int *status, double t_start, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *com_tm, \
+    double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream), (model, B, smax, steps, n_steps, init_feet, \
+    com0, blocks, status, t_start, lcap, zmp_x_tm, zmp_y_tm, com_tm, left_tm, left_type_tm, right_tm, right_type_tm, length, hip_stream)) \
+  X(int, wg_morisawa_long_walk_fleet_dev, (const wg_morisawa_model_t *models, double T, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, \
     const double *init_feet, const double *com0, void *blocks, int *status, double t_start, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *com_tm, \
     double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream), (models, T, B, smax, steps, n_steps, init_feet, \
     com0, blocks, status, t_start, lcap, zmp_x_tm, zmp_y_tm, com_tm, left_tm, left_type_tm, right_tm, right_type_tm, length, hip_stream))

@@ -2408,35 +2408,43 @@ int wg_dimitrov_follow_fleet_dev(int B, const wg_dimitrov_fleet_t *fleet, int qc
 }  // extern "C"
 
 // ---- Morisawa-2007 analytic walks (wg_morisawa_kernels.hpp; the host twins are wg_morisawa.cpp) ---------------------------------
+// LONG: the wg_morisawa_long_* family -- its cap on smax, its layout and kernels; checks, lock and clock slot are the one text
 namespace {
 
+template <bool LONG>
+constexpr int mo_cap() { return LONG ? WG_MORISAWA_LONG_MAX_STEPS : WG_MORISAWA_MAX_STEPS; }
+template <bool LONG>
 int mo_solve_check(const void *models, int B, int smax, const void *steps, const void *n_steps, const void *init_feet, const void *com0, const void *blocks, const void *status) {
-  if (!models || B < 0 || smax < 2 || smax > WG_MORISAWA_MAX_STEPS || !steps || !n_steps || !init_feet || !com0 || !blocks || !status)
-    return fail(WG_ERR_BAD_ARG, "need a model, B >= 0, 2 <= smax <= %d, non-null steps, n_steps, init_feet, com0, blocks, status", WG_MORISAWA_MAX_STEPS);
+  if (!models || B < 0 || smax < 2 || smax > mo_cap<LONG>() || !steps || !n_steps || !init_feet || !com0 || !blocks || !status)
+    return fail(WG_ERR_BAD_ARG, "need a model, B >= 0, 2 <= smax <= %d, non-null steps, n_steps, init_feet, com0, blocks, status", mo_cap<LONG>());
   return WG_OK;
 }
+template <bool LONG>
 int mo_sample_check(int B, int smax, const void *blocks, double t_start, double T, int lcap) {
-  if (!blocks || B < 0 || smax < 2 || smax > WG_MORISAWA_MAX_STEPS || lcap < 1 || lcap > (1 << 19) || !wg::mo_finite(T) || !(T > 0.0) || !wg::mo_finite(t_start) || t_start < 0.0)
-    return fail(WG_ERR_BAD_ARG, "need blocks, B >= 0, 2 <= smax <= %d, 1 <= lcap <= %d, finite T > 0 and t_start >= 0", WG_MORISAWA_MAX_STEPS, 1 << 19);
+  if (!blocks || B < 0 || smax < 2 || smax > mo_cap<LONG>() || lcap < 1 || lcap > (1 << 19) || !wg::mo_finite(T) || !(T > 0.0) || !wg::mo_finite(t_start) || t_start < 0.0)
+    return fail(WG_ERR_BAD_ARG, "need blocks, B >= 0, 2 <= smax <= %d, 1 <= lcap <= %d, finite T > 0 and t_start >= 0", mo_cap<LONG>(), 1 << 19);
   return WG_OK;
 }
 // one wave per gait, the gait's work area in LDS; under the context's launch lock like every launch of a context
-template <bool FLEET>
+template <bool FLEET, bool LONG>
 int mo_solve_launch(wg_ctx *ctx, const wg_morisawa_model_t *mf, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, const double *com0, void *blocks, int *status, hipStream_t st) {
   if (int rc = use_ctx(ctx)) return rc;
-  if (int rc = mo_solve_check(mf, B, smax, steps, n_steps, init_feet, com0, blocks, status)) return rc;
+  if (int rc = mo_solve_check<LONG>(mf, B, smax, steps, n_steps, init_feet, com0, blocks, status)) return rc;
   if (B == 0) return WG_OK;
   wg_morisawa_model_t m;
   memset(&m, 0, sizeof m);
   if (!FLEET) m = *mf;
-  const size_t lds = (size_t)wg::mo_layout(smax).work_words * sizeof(double);
+  const size_t lds = (size_t)(LONG ? wg::mo_layout_long(smax) : wg::mo_layout(smax)).work_words * sizeof(double);
   std::lock_guard<std::mutex> launch_lk(ctx->launch_mu);
+  if (LONG)
+    return launch_lds(wg::wg_morisawa_solve_long_kernel<FLEET>, dim3(B), dim3(64), lds, st, m, FLEET ? mf : nullptr, B, smax, steps, n_steps, init_feet, com0, static_cast<double *>(blocks), status);
   return launch_lds(wg::wg_morisawa_solve_kernel<FLEET>, dim3(B), dim3(64), lds, st, m, FLEET ? mf : nullptr, B, smax, steps, n_steps, init_feet, com0, static_cast<double *>(blocks), status);
 }
 // the clock of the launch into the context's buffer, then a lane per gait and kMoSampleChunk samples
+template <bool LONG>
 int mo_sample_launch(wg_ctx *ctx, int B, int smax, const void *blocks, const int *status, double t_start, double T, int lcap, const wg::MoOut &O, int *length, hipStream_t st) {
   if (int rc = use_ctx(ctx)) return rc;
-  if (int rc = mo_sample_check(B, smax, blocks, t_start, T, lcap)) return rc;
+  if (int rc = mo_sample_check<LONG>(B, smax, blocks, t_start, T, lcap)) return rc;
   if (B == 0) return WG_OK;
   std::lock_guard<std::mutex> launch_lk(ctx->launch_mu);
   if (int rc = slot_claim(ctx, ctx->mo_order, st, "Morisawa sample")) return rc;
@@ -2445,37 +2453,45 @@ int mo_sample_launch(wg_ctx *ctx, int B, int smax, const void *blocks, const int
   hipLaunchKernelGGL(wg::wg_morisawa_clock_kernel, dim3(1), dim3(1), 0, st, t_start, T, lcap + 1, clock);
   HIP_TRY(hipGetLastError());
   const int chunks = (lcap + wg::kMoSampleChunk - 1) / wg::kMoSampleChunk;
-  hipLaunchKernelGGL(wg::wg_morisawa_sample_kernel, dim3((B + 63) / 64, chunks), dim3(64), 0, st, B, smax, static_cast<const double *>(blocks), status, clock, lcap, O, length);
+  hipLaunchKernelGGL(wg::wg_morisawa_sample_kernel<LONG>, dim3((B + 63) / 64, chunks), dim3(64), 0, st, B, smax, static_cast<const double *>(blocks), status, clock, lcap, O, length);
   HIP_TRY(hipGetLastError());
   return slot_mark(ctx->mo_order, st);
+}
+// solve, then sample, on the caller's stream: the stream orders them, the host does not wait
+template <bool FLEET, bool LONG>
+int mo_walk_launch(wg_ctx *ctx, const wg_morisawa_model_t *mf, double T, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, const double *com0, void *blocks, int *status, double t_start, int lcap, const wg::MoOut &O, int *length, hipStream_t st) {
+  if (int rc = mo_solve_check<LONG>(mf, B, smax, steps, n_steps, init_feet, com0, blocks, status)) return rc;
+  if (!FLEET) T = mf->T;
+  if (int rc = mo_sample_check<LONG>(B, smax, blocks, t_start, T, lcap)) return rc;
+  if (int rc = mo_solve_launch<FLEET, LONG>(ctx, mf, B, smax, steps, n_steps, init_feet, com0, blocks, status, st)) return rc;
+  return mo_sample_launch<LONG>(ctx, B, smax, blocks, status, t_start, T, lcap, O, length, st);
 }
 
 }  // namespace
 
 extern "C" {
 
-int wg_morisawa_solve_dev_ctx(wg_ctx_t *ctx, const wg_morisawa_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, const double *com0, void *blocks, int *status, void *hip_stream) {
-  return mo_solve_launch<false>(ctx, model, B, smax, steps, n_steps, init_feet, com0, blocks, status, reinterpret_cast<hipStream_t>(hip_stream));
-}
-int wg_morisawa_solve_fleet_dev_ctx(wg_ctx_t *ctx, const wg_morisawa_model_t *models, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, const double *com0, void *blocks, int *status, void *hip_stream) {
-  return mo_solve_launch<true>(ctx, models, B, smax, steps, n_steps, init_feet, com0, blocks, status, reinterpret_cast<hipStream_t>(hip_stream));
-}
-int wg_morisawa_sample_dev_ctx(wg_ctx_t *ctx, int B, int smax, const void *blocks, const int *status, double t_start, double T, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *com_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream) {
-  const wg::MoOut O{zmp_x_tm, zmp_y_tm, com_tm, left_tm, right_tm, left_type_tm, right_type_tm};
-  return mo_sample_launch(ctx, B, smax, blocks, status, t_start, T, lcap, O, length, reinterpret_cast<hipStream_t>(hip_stream));
-}
-// solve, then sample, on the caller's stream: the stream orders them, the host does not wait
-int wg_morisawa_walk_dev_ctx(wg_ctx_t *ctx, const wg_morisawa_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, const double *com0, void *blocks, int *status, double t_start, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *com_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream) {
-  if (int rc = mo_solve_check(model, B, smax, steps, n_steps, init_feet, com0, blocks, status)) return rc;
-  if (int rc = mo_sample_check(B, smax, blocks, t_start, model->T, lcap)) return rc;
-  if (int rc = wg_morisawa_solve_dev_ctx(ctx, model, B, smax, steps, n_steps, init_feet, com0, blocks, status, hip_stream)) return rc;
-  return wg_morisawa_sample_dev_ctx(ctx, B, smax, blocks, status, t_start, model->T, lcap, zmp_x_tm, zmp_y_tm, com_tm, left_tm, left_type_tm, right_tm, right_type_tm, length, hip_stream);
-}
-int wg_morisawa_walk_fleet_dev_ctx(wg_ctx_t *ctx, const wg_morisawa_model_t *models, double T, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, const double *com0, void *blocks, int *status, double t_start, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *com_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream) {
-  if (int rc = mo_solve_check(models, B, smax, steps, n_steps, init_feet, com0, blocks, status)) return rc;
-  if (int rc = mo_sample_check(B, smax, blocks, t_start, T, lcap)) return rc;
-  if (int rc = wg_morisawa_solve_fleet_dev_ctx(ctx, models, B, smax, steps, n_steps, init_feet, com0, blocks, status, hip_stream)) return rc;
-  return wg_morisawa_sample_dev_ctx(ctx, B, smax, blocks, status, t_start, T, lcap, zmp_x_tm, zmp_y_tm, com_tm, left_tm, left_type_tm, right_tm, right_type_tm, length, hip_stream);
-}
+#define WG_MO_ENTRIES_(stem, LONG)                                                                                                              \
+  int stem##solve_dev_ctx(wg_ctx_t *ctx, const wg_morisawa_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, const double *com0, void *blocks, int *status, void *hip_stream) { \
+    return mo_solve_launch<false, LONG>(ctx, model, B, smax, steps, n_steps, init_feet, com0, blocks, status, reinterpret_cast<hipStream_t>(hip_stream)); \
+  }                                                                                                                                             \
+  int stem##solve_fleet_dev_ctx(wg_ctx_t *ctx, const wg_morisawa_model_t *models, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, const double *com0, void *blocks, int *status, void *hip_stream) { \
+    return mo_solve_launch<true, LONG>(ctx, models, B, smax, steps, n_steps, init_feet, com0, blocks, status, reinterpret_cast<hipStream_t>(hip_stream)); \
+  }                                                                                                                                             \
+  int stem##sample_dev_ctx(wg_ctx_t *ctx, int B, int smax, const void *blocks, const int *status, double t_start, double T, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *com_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream) { \
+    const wg::MoOut O{zmp_x_tm, zmp_y_tm, com_tm, left_tm, right_tm, left_type_tm, right_type_tm};                                               \
+    return mo_sample_launch<LONG>(ctx, B, smax, blocks, status, t_start, T, lcap, O, length, reinterpret_cast<hipStream_t>(hip_stream));         \
+  }                                                                                                                                             \
+  int stem##walk_dev_ctx(wg_ctx_t *ctx, const wg_morisawa_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, const double *com0, void *blocks, int *status, double t_start, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *com_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream) { \
+    const wg::MoOut O{zmp_x_tm, zmp_y_tm, com_tm, left_tm, right_tm, left_type_tm, right_type_tm};                                               \
+    return mo_walk_launch<false, LONG>(ctx, model, 0.0, B, smax, steps, n_steps, init_feet, com0, blocks, status, t_start, lcap, O, length, reinterpret_cast<hipStream_t>(hip_stream)); \
+  }                                                                                                                                             \
+  int stem##walk_fleet_dev_ctx(wg_ctx_t *ctx, const wg_morisawa_model_t *models, double T, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, const double *com0, void *blocks, int *status, double t_start, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *com_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream) { \
+    const wg::MoOut O{zmp_x_tm, zmp_y_tm, com_tm, left_tm, right_tm, left_type_tm, right_type_tm};                                               \
+    return mo_walk_launch<true, LONG>(ctx, models, T, B, smax, steps, n_steps, init_feet, com0, blocks, status, t_start, lcap, O, length, reinterpret_cast<hipStream_t>(hip_stream)); \
+  }
+WG_MO_ENTRIES_(wg_morisawa_, false)
+WG_MO_ENTRIES_(wg_morisawa_long_, true)
+#undef WG_MO_ENTRIES_
 
 }  // extern "C"

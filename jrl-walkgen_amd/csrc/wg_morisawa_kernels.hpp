@@ -10,7 +10,16 @@
 // The pivot is the wave's arg-max "largest, then first" on the DPP path.  FLEET: the gait's own model from a device array; the
 // one-model form takes it by value.  One text, two bindings.
 //
-// wg_morisawa_sample_kernel: lanes = gaits.  The outputs are time-major with the gait index fastest, so consecutive lanes store
+// wg_morisawa_solve_long_kernel<FLEET> (wg_morisawa_long_*, smax up to 64): the same wave per gait around mo_solve_long.  LDS holds
+// the image without the feet's polynomials and Z as a row band, rows 16 doubles apart as in the block -- 19 080 B at smax = 15,
+// 38 800 B at 32, 75 920 B at 64: 8, 4 and 2 gaits per CU -- and the block is written only behind the factor.  In the elimination
+// a lane owns an ELEMENT of the live window, 5 rows x (9 columns + 2 right-hand sides) = 55 lanes per step, behind the step's
+// five multipliers; the pivot is a compare chain over the six words of the column that every lane reads (a broadcast), not a
+// reduction.  Pitch 16: in the window's read the rows k + 1 and k + 3 of the first half-wave meet on 7 of the 32 eight-byte bank pairs (two passes
+// for one ds_read_b64 per step); the next conflict-free pitch, 22, costs 12 672 B at smax = 64 and with them the second gait of a
+// CU, so the block's pitch is the work area's too.
+//
+// wg_morisawa_sample_kernel<LONG>: lanes = gaits; LONG reads blocks of the long layout and asks for their header tag.  The outputs are time-major with the gait index fastest, so consecutive lanes store
 // consecutive words (a lane per sample would scatter every store over B x 8 bytes); the price is that each lane gathers its own
 // gait's coefficients, which stay in cache across the kMoSampleChunk consecutive samples a lane makes.  The kernel is bound by its
 // stores: 152 B per gait and sample with every output wanted (2 + 4 + 12 doubles, 2 ints).  The clock -- t_start, then one
@@ -48,6 +57,23 @@ __global__ __launch_bounds__(64) void wg_morisawa_solve_kernel(const wg_morisawa
   for (int e = threadIdx.x; e < L.words; e += 64) blk[e] = mo_image_word(wg_mo_lds, L, e);
 }
 
+// The long walk (smax up to WG_MORISAWA_LONG_MAX_STEPS): the same wave per gait around mo_solve_long.  LDS holds the image without
+// the feet's polynomials and Z as a band (mo_work_long); the block is written by mo_solve_long itself, and only behind the factor.
+template <bool FLEET>
+__global__ __launch_bounds__(64) void wg_morisawa_solve_long_kernel(const wg_morisawa_model_t model, const wg_morisawa_model_t *models, int B,
+                                                                    int smax, const wg_rel_step_t *steps, const int *n_steps,
+                                                                    const double *init_feet, const double *com0, double *blocks,
+                                                                    int *status) {
+  extern __shared__ double wg_mo_lds[];
+  const int b = blockIdx.x;
+  if (b >= B) return;
+  const MoLayout L = mo_layout_long(smax);
+  const wg_morisawa_model_t m = FLEET ? models[b] : model;
+  const int rc = mo_solve_long(MoWaveExec(), m, smax, steps + (size_t)b * smax, n_steps[b], init_feet + 6 * (size_t)b,
+                               com0 + 3 * (size_t)b, wg_mo_lds, L, blocks + (size_t)b * L.words, nullptr);
+  if (threadIdx.x == 0) status[b] = rc;
+}
+
 __global__ void wg_morisawa_clock_kernel(double t_start, double T, int count, double *clock) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   double t = t_start;
@@ -63,14 +89,17 @@ struct MoOut {
 };
 constexpr int kMoSampleChunk = 8;
 
+// LONG: blocks of the long layout, which carry the header tag; one text, two bindings (the short binding's instructions are
+// those of the kernel before it had the parameter)
+template <bool LONG>
 __global__ __launch_bounds__(64) void wg_morisawa_sample_kernel(int B, int smax, const double *blocks, const int *status, const double *clock,
                                                                 int lcap, MoOut O, int *length) {
   const int b = blockIdx.x * 64 + threadIdx.x;
   if (b >= B) return;
-  const MoLayout L = mo_layout(smax);
+  const MoLayout L = LONG ? mo_layout_long(smax) : mo_layout(smax);
   const double *blk = blocks + (size_t)b * L.words;
   int len = status ? status[b] : WG_OK;
-  if (len >= 0) len = mo_block_ok(blk, smax) ? mo_count(clock, lcap, blk[3]) : WG_MORISAWA_BAD_INPUT;
+  if (len >= 0) len = (LONG ? mo_block_ok_long(blk, smax) : mo_block_ok(blk, smax)) ? mo_count(clock, lcap, blk[3]) : WG_MORISAWA_BAD_INPUT;
   if (len > lcap) len = WG_MORISAWA_CAPACITY;
   if (blockIdx.y == 0 && length) length[b] = len;
   if (len <= 0) return;

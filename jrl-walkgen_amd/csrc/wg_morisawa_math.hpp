@@ -28,6 +28,11 @@
 // of this project: mo_lu is a right-looking LU with partial pivoting and no refinement; parity with the reference is by
 // tolerance (tests/test_morisawa_golden.py, tests/test_morisawa_host.py).
 //
+// Two forms of the solve: mo_solve / mo_lu, dense, a row of Z per lane, up to WG_MORISAWA_MAX_STEPS steps (n <= 64), and
+// mo_solve_long / mo_band_lu, Z as a row band of 16 words, a lane per element of the elimination's live window, up to
+// WG_MORISAWA_LONG_MAX_STEPS steps (n <= 264).  The band takes the dense form's pivots and gives its values; mo_sample reads the
+// blocks of both through their layouts.
+//
 // Quirks of the reference kept on purpose, each marked where it is reproduced: g is 9.86 (:1106), the ZMP twin's
 // sTc = fabs(9.86 / (z_com - z_zmp)) (AnalyticalZMPCOGTrajectory.cpp:401), and the right-support branch clears the LEFT foot's
 // dz (LeftAndRightFootTrajectoryGenerationMultiple.cpp:419).
@@ -234,8 +239,9 @@ WG_MO_INLINE bool mo_model_ok(const wg_morisawa_model_t &m) {
 // FillQueues' loop (:2242) on the trajectory's own clock: t_start, then one addition of T per sample, while t <= the sum of the
 // interval times.  The sample at exactly that sum exists only if the additions land on or below it: with the reference's short
 // walk (7 steps from 2 t_single at T = 0.005) they end 1e-13 above it and the walk has 1588 samples, the rows of its golden file.
-WG_MO_INLINE int mo_length(const wg_morisawa_model_t &m, int S, double t_start) {
-  if (!mo_model_ok(m) || S < 2 || S > WG_MORISAWA_MAX_STEPS || !mo_finite(t_start) || t_start < 0.0) return WG_MORISAWA_BAD_INPUT;
+// cap: the family's own, WG_MORISAWA_MAX_STEPS or WG_MORISAWA_LONG_MAX_STEPS
+WG_MO_INLINE int mo_length(const wg_morisawa_model_t &m, int S, double t_start, int cap = WG_MORISAWA_MAX_STEPS) {
+  if (!mo_model_ok(m) || S < 2 || S > cap || !mo_finite(t_start) || t_start < 0.0) return WG_MORISAWA_BAD_INPUT;
   const double total = mo_tref(m, 2 * S + 1, 2 * S + 1);
   int n = 0;
   for (double t = t_start; t <= total; t += m.T) {
@@ -337,10 +343,10 @@ WG_MO_HD inline void mo_feet_chain(const wg_morisawa_model_t &m, const wg_rel_st
   }
 }
 
-// ---- one row of Z (:944-1164) into z[0 .. n), everything else of the row zero ----------------------------------------------------
-WG_MO_HD inline void mo_z_row(int r, int I, const double *dT, const double *om, const double *chv, const double *shv, double *z) {
-  const int n = 2 * I + 6;
-  for (int c = 0; c < n; c++) z[c] = 0.0;
+// ---- one row of Z (:944-1164): its non-zeros, z[c] for the row's own columns c and nothing else.  They lie in columns
+// r - 5 .. r + 4 whatever I is (the start block reaches five to the left, the rows of interval I - 2 four to the right), so the
+// band form hands in z = band row - (r - 5) ----------------------------------------------------------------------------------------
+WG_MO_INLINE void mo_z_fill(int r, int I, const double *dT, const double *om, const double *chv, const double *shv, double *z) {
   const double T0 = dT[0], O0 = om[0], Sq0 = O0 * O0;
   if (r == 0) { z[0] = 2.0 / Sq0; z[3] = 1.0; return; }        // BuildingTheZMatrix :1125-1129
   if (r == 1) { z[1] = 6.0 / Sq0; z[4] = O0; return; }
@@ -432,6 +438,12 @@ WG_MO_HD inline void mo_z_row(int r, int I, const double *dT, const double *om, 
       z[col + 2] = 4 * Deltat - 24.0 * Tm / Sqm;
     }
   }
+}
+// the dense form: row r into z[0 .. n), everything else of the row zero
+WG_MO_HD inline void mo_z_row(int r, int I, const double *dT, const double *om, const double *chv, const double *shv, double *z) {
+  const int n = 2 * I + 6;
+  for (int c = 0; c < n; c++) z[c] = 0.0;
+  mo_z_fill(r, I, dT, om, chv, shv, z);
 }
 
 // ---- one entry of w (ComputeW :831-942); cog: the CoG polynomials of the axis [I][5], zp: its ZMP profile ----------------------
@@ -653,10 +665,265 @@ WG_MO_INLINE double mo_image_word(const double *W, const MoLayout &L, int e) {
   return W[L.o_lu + r * (L.nmax + 1) + (q - r * L.nmax)];
 }
 
+// ---- the long walk: Z as a band, up to WG_MORISAWA_LONG_MAX_STEPS steps ----------------------------------------------------------
+// Z's non-zeros lie within kMoKl below and kMoKu above the diagonal for every S (mo_z_fill); partial pivoting inside the band lets
+// U reach kMoKu + kMoKl to the right.  Row-band storage: position i keeps columns i - 5 .. i + 9 in 15 words, rows kMoBand = 16
+// doubles apart, the 16th word zero.  The multipliers of column k stay at the positions where they were made and are not swapped
+// by later steps (LAPACK's dgbtf2 / dgbtrs convention): a later right-hand side is solved by, for k ascending, swapping b_k and
+// b_piv[k] and then taking the multipliers of positions k + 1 .. k + 5 times b_k off those entries.
+constexpr int kMoKl = 5, kMoKu = 4, kMoKuu = kMoKu + kMoKl, kMoBand = 16;
+WG_MO_INLINE int mo_band_at(int i, int c) { return i * kMoBand + (c - i + kMoKl); }
+
+// The long block has the short block's sections in the short block's order up to o_piv -- mo_sample reads it through this layout
+// unchanged -- then the band [nmax][16] in place of [nmax][nmax].  The header's word 4, the first behind the two doubles and zero
+// in a short block, holds the int 1 (int kMoTagInt of the header).  work_words: see mo_work_long.
+constexpr int kMoTagInt = 8;
+WG_MO_INLINE MoLayout mo_layout_long(int smax) {
+  MoLayout L = mo_layout(smax);
+  L.words = (L.o_lu + L.nmax * kMoBand + 15) & ~15;
+  L.o_seg = -1;
+  L.work_words = L.o_lu + L.nmax * kMoBand - 72 * L.imax;
+  return L;
+}
+// The work area of the long solve: the image without the feet's polynomials (72 doubles per interval, which go from the lanes'
+// registers to the block), so every section from o_nat on sits 72 imax lower.  The foot records of mo_feet_chain (24 doubles per
+// interval) share the band's words, 24 imax <= 16 nmax: they are there before the band is built and again after it has left.
+// 19 080 B at smax = 15, 38 800 B at 32, 75 920 B at 64: 8, 4 and 2 gaits on a CU of 160 KiB.
+WG_MO_INLINE MoLayout mo_work_long(const MoLayout &L) {
+  MoLayout Lw = L;
+  const int d = 72 * L.imax;
+  Lw.o_left = Lw.o_right = -1;
+  Lw.o_nat -= d; Lw.o_zpx -= d; Lw.o_zpy -= d; Lw.o_sup -= d; Lw.o_rhs -= d; Lw.o_piv -= d; Lw.o_lu -= d;
+  Lw.o_seg = Lw.o_lu;
+  return Lw;
+}
+// word e of the long block from the work area, for the sections the work area holds (e outside [o_left, o_nat)); zeros behind
+WG_MO_INLINE double mo_image_word_long(const double *W, const MoLayout &L, int e) {
+  if (e < L.o_left) return W[e];
+  if (e >= L.o_lu + L.nmax * kMoBand) return 0.0;
+  return W[e - 72 * L.imax];
+}
+
+// mo_lu restricted to the band: the same pivots and, element by element, the same operations in the same order minus the
+// products with structural zeros, so the same values (at most the sign of a zero differs).  The pivot of column k is the first
+// row of largest |a_ik| among k <= i <= min(n - 1, k + 5) -- six words that every lane reads and compares alike, no reduction --;
+// the rows k and p swap over columns k .. k + 9 and the right-hand sides; the live window of step k is 5 rows x (9 columns + 2
+// right-hand sides) = 55 elements, one per lane, behind the at most five multipliers a_ik / a_kk, a lane each.  U y = b column by
+// column from the last, over rows c - 9 .. c - 1.  false: a zero or non-finite pivot.
+template <class X>
+WG_MO_HD inline bool mo_band_lu(const X x, int n, double *a, int *piv, double *b0, double *b1) {
+  const int l0 = x.lane(), NL = x.lanes();
+  constexpr int kCols = kMoKuu + 2;                            // 9 columns right of the pivot, then b0 and b1
+  for (int k = 0; k < n; k++) {
+    const int ilast = k + kMoKl < n - 1 ? k + kMoKl : n - 1, clast = k + kMoKuu < n - 1 ? k + kMoKuu : n - 1;
+    double best = -1.0;
+    int p = -1;
+    for (int i = k; i <= ilast; i++) {
+      const double raw = mo_abs(a[mo_band_at(i, k)]);
+      const double v = mo_finite(raw) ? raw : __builtin_huge_val();
+      if (v > best) { best = v; p = i; }
+    }
+    if (!(best > 0.0) || !mo_finite(best)) return false;
+    if (l0 == 0) piv[k] = p;
+    if (p != k) {
+      for (int e = l0; e < kCols + 1; e += NL) {               // columns k .. k + 9, b0, b1
+        const int c = k + e;
+        if (e <= kMoKuu) {
+          if (c <= clast) {
+            const double t = a[mo_band_at(k, c)];
+            a[mo_band_at(k, c)] = a[mo_band_at(p, c)];
+            a[mo_band_at(p, c)] = t;
+          }
+        } else {
+          double *b = e == kMoKuu + 1 ? b0 : b1;
+          const double t = b[k]; b[k] = b[p]; b[p] = t;
+        }
+      }
+    }
+    x.sync();
+    const double akk = a[mo_band_at(k, k)];
+    for (int i = k + 1 + l0; i <= ilast; i += NL) a[mo_band_at(i, k)] = a[mo_band_at(i, k)] / akk;
+    x.sync();
+    for (int e = l0; e < kMoKl * kCols; e += NL) {
+      const int r = e / kCols, q = e - r * kCols, i = k + 1 + r, c = k + 1 + q;
+      if (i > ilast) continue;
+      const double mlt = a[mo_band_at(i, k)];
+      if (q < kMoKuu) {
+        if (c <= clast) {
+          const double prod = mlt * a[mo_band_at(k, c)];
+          a[mo_band_at(i, c)] = a[mo_band_at(i, c)] - prod;
+        }
+      } else if (q == kMoKuu) {
+        const double p0 = mlt * b0[k];
+        b0[i] = b0[i] - p0;
+      } else {
+        const double p1 = mlt * b1[k];
+        b1[i] = b1[i] - p1;
+      }
+    }
+    x.sync();
+  }
+  for (int c = n - 1; c >= 0; c--) {
+    const double ucc = a[mo_band_at(c, c)];
+    const double y0 = b0[c] / ucc, y1 = b1[c] / ucc;
+    x.sync();                                                  // every lane has read b[c] before lane 0 overwrites it
+    if (l0 == 0) { b0[c] = y0; b1[c] = y1; }
+    for (int e = l0; e < kMoKuu; e += NL) {
+      const int i = c - 1 - e;
+      if (i < 0) continue;
+      const double u = a[mo_band_at(i, c)];
+      const double p0 = u * y0, p1 = u * y1;
+      b0[i] = b0[i] - p0;
+      b1[i] = b1[i] - p1;
+    }
+    x.sync();
+  }
+  return true;
+}
+
+// what mo_solve refuses before it touches anything
+WG_MO_HD inline bool mo_inputs_ok(const wg_morisawa_model_t &m, int smax, const wg_rel_step_t *steps, int S, const double *feet6,
+                                  const double *com3) {
+  if (S < 2 || S > smax || !mo_model_ok(m)) return false;
+  const double h = com3[2];
+  if (!mo_time_ok(h) || !mo_finite(com3[0]) || !mo_finite(com3[1])) return false;
+  for (int k = 0; k < 6; k++)
+    if (!mo_finite(feet6[k])) return false;
+  for (int i = 0; i < S; i++)
+    if (!mo_finite(steps[i].sx) || !mo_finite(steps[i].sy) || !mo_finite(steps[i].theta)) return false;
+  const double omega = sqrt(kMoG / (h - 0.0));
+  return omega * (m.t_single * 3.0) <= kMoArgMax && omega * m.t_double <= kMoArgMax;
+}
+
+// ---- the whole long solve of one gait: work area W (mo_layout_long's work_words doubles), block blk ------------------------------
+// mo_solve's phases around what LDS holds.  Everything that can refuse comes first and writes W alone: the times, the feet chain
+// (for the support feet that the ZMP profile and w need; its foot records lie where the band will), the cubics, w, then the band
+// of Z and its factor.  blk is written only from there on, so a refused gait's block stays as it was: the image from W, then the
+// feet -- the chain once more, its records now in the words the band has left, and each polynomial from its lane to the block.
+// z_dump (host only, may be null): Z before the elimination in row-band form, n x 16.
+template <class X>
+WG_MO_HD inline int mo_solve_long(const X x, const wg_morisawa_model_t &m, int smax, const wg_rel_step_t *steps, int S,
+                                  const double *feet6, const double *com3, double *W, const MoLayout &L, double *blk, double *z_dump) {
+  const int l0 = x.lane(), NL = x.lanes();
+  if (!mo_inputs_ok(m, smax, steps, S, feet6, com3)) return WG_MORISAWA_BAD_INPUT;
+  const MoLayout Lw = mo_work_long(L);
+  const int I = 2 * S + 1, n = 2 * I + 6;
+  const double h = com3[2];
+  const double omega = sqrt(kMoG / (h - 0.0));                 // BuildingTheZMatrix :1106, lZMP = 0 (:387)
+
+  for (int e = l0; e < L.work_words; e += NL) W[e] = 0.0;
+  x.sync();
+  double *dT = W + Lw.o_dT, *om = W + Lw.o_om, *tref = W + Lw.o_tref;
+  double *chv = W + Lw.o_vx, *shv = W + Lw.o_wx;               // cosh, sinh of omega_j dT_j, until the weights of x take their place
+  double *zpx = W + Lw.o_zpx, *zpy = W + Lw.o_zpy, *sup = W + Lw.o_sup;
+  double *rhs = W + Lw.o_rhs, *a = W + Lw.o_lu;
+  int *hdr = reinterpret_cast<int *>(W), *piv = reinterpret_cast<int *>(W + Lw.o_piv);
+
+  // ---- interval times, their running sums, omega_j, cosh / sinh of omega_j dT_j; lane 0: the feet chain ----
+  for (int j = l0; j < I; j += NL) {
+    dT[j] = mo_dT(m, j, I);
+    om[j] = omega;
+    tref[j] = mo_tref(m, j, I);
+    mo_coshsinh(omega * dT[j], chv[j], shv[j]);
+  }
+  if (l0 == 0) {
+    hdr[0] = S; hdr[1] = I; hdr[2] = n; hdr[3] = smax; hdr[kMoTagInt] = 1;
+    W[2] = h;
+    W[3] = mo_tref(m, I, I);
+    mo_feet_chain(m, steps, S, feet6, W, Lw);
+  }
+  x.sync();
+
+  // ---- the ZMP profile, the interior cubics, w: as in mo_solve ----
+  const double finx = 0.5 * (sup[3 * (S - 2)] + sup[3 * (S - 1)]), finy = 0.5 * (sup[3 * (S - 2) + 1] + sup[3 * (S - 1) + 1]);
+  for (int j = l0; j < I; j += NL) {
+    zpx[j] = j == 0 ? com3[0] : (j >= 2 * S - 1 ? finx : sup[3 * ((j - 1) / 2)]);
+    zpy[j] = j == 0 ? com3[1] : (j >= 2 * S - 1 ? finy : sup[3 * ((j - 1) / 2) + 1]);
+  }
+  x.sync();
+  for (int e = l0; e < 2 * (I - 2); e += NL) {
+    const int ax = e / (I - 2), j = 1 + (e - ax * (I - 2));
+    const double *zp = ax ? zpy : zpx;
+    double *Zc = W + (ax ? Lw.o_zy : Lw.o_zx) + 5 * j, *Cc = W + (ax ? Lw.o_cy : Lw.o_cx) + 5 * j;
+    const double lTj = dT[j], Omegac = om[j];
+    Zc[0] = zp[j - 1];
+    Zc[1] = 0;
+    Zc[2] = (zp[j] - zp[j - 1]) * 3.0 / (lTj * lTj);
+    Zc[3] = -2.0 * Zc[2] / (3.0 * lTj);
+    Cc[3] = Zc[3];
+    Cc[2] = Zc[2];
+    Cc[1] = Zc[1] + Cc[3] * 6 / (Omegac * Omegac);
+    Cc[0] = Zc[0] + Cc[2] * 2 / (Omegac * Omegac);
+  }
+  x.sync();
+  for (int e = l0; e < 2 * n; e += NL) {
+    const int ax = e / n, q = e - ax * n;
+    const double v = mo_w_entry(q, I, dT, W + (ax ? Lw.o_cy : Lw.o_cx), ax ? zpy : zpx, ax ? com3[1] : com3[0], 0.0, ax ? finy : finx);
+    rhs[ax * L.nmax + q] = v;
+    rhs[(2 + ax) * L.nmax + q] = v;
+  }
+  // ---- the band of Z over the chain's foot records, row by row ----
+  for (int e = l0; e < L.nmax * kMoBand; e += NL) a[e] = 0.0;
+  x.sync();
+  for (int r = l0; r < n; r += NL) mo_z_fill(r, I, dT, om, chv, shv, a + mo_band_at(r, 0));
+  x.sync();
+  if (z_dump) {
+    for (int e = l0; e < n * kMoBand; e += NL) z_dump[e] = a[e];
+    x.sync();
+  }
+
+  if (!mo_band_lu(x, n, a, piv, rhs + 2 * L.nmax, rhs + 3 * L.nmax)) return WG_MORISAWA_SINGULAR;
+
+  // ---- TransfertTheCoefficientsToTrajectories: as in mo_solve ----
+  for (int e = l0; e < 2 * I; e += NL) {
+    const int ax = e / I, j = e - ax * I;
+    const double *y = rhs + (2 + ax) * L.nmax;
+    const int at = j < I - 1 ? 3 + 2 * j : 2 * I + 4;
+    W[(ax ? Lw.o_vy : Lw.o_vx) + j] = y[at];
+    W[(ax ? Lw.o_wy : Lw.o_wx) + j] = y[at + 1];
+  }
+  for (int e = l0; e < 4; e += NL) {
+    const int ax = e >> 1, last = e & 1, j = last ? I - 1 : 0;
+    const double *y = rhs + (2 + ax) * L.nmax + (last ? 2 * I + 1 : 0);
+    const double *zp = ax ? zpy : zpx;
+    double *Cc = W + (ax ? Lw.o_cy : Lw.o_cx) + 5 * j, *Zc = W + (ax ? Lw.o_zy : Lw.o_zx) + 5 * j;
+    for (int k = 2; k <= 4; k++) Cc[k] = y[k - 2];
+    Cc[1] = Cc[3] * 6.0 / (om[j] * om[j]);
+    Cc[0] = zp[j] + Cc[2] * 2.0 / (om[j] * om[j]);
+    const double sTc = mo_abs(kMoG / (h - 0.0));               // AnalyticalZMPCOGTrajectory.cpp:401
+    Zc[3] = Cc[3];
+    Zc[4] = Cc[4];
+    for (unsigned int i = 0; i < 3; ++i) Zc[i] = Cc[i] - ((double)(i + 1.0) * (double)(i + 2.0)) * (Cc[i + 2] / sTc);
+  }
+  x.sync();
+
+  // ---- the image to the block; then the feet: the chain's records where the band was, a polynomial per lane to the block ----
+  for (int e = l0; e < L.words; e += NL)
+    if (e < L.o_left || e >= L.o_nat) blk[e] = mo_image_word_long(W, L, e);
+  x.sync();
+  if (l0 == 0) mo_feet_chain(m, steps, S, feet6, W, Lw);
+  x.sync();
+  for (int e = l0; e < L.imax * 12; e += NL) {
+    const int j = e / 12, f = (e - 12 * j) / 6, ax = e - 12 * j - 6 * f;
+    double c[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (j < I) {
+      const double *sg = W + Lw.o_seg + 24 * j + 12 * f;
+      mo_foot_axis(ax, dT[j], sg[6 + ax], sg[ax], 0.0, c);
+    }
+    double *out = blk + (f ? L.o_right : L.o_left) + 36 * j + 6 * ax;
+    for (int k = 0; k < 6; k++) out[k] = c[k];
+  }
+  x.sync();
+  return WG_OK;
+}
+
 // ---- a block as the sampler reads it -------------------------------------------------------------------------------------------
 WG_MO_INLINE bool mo_block_ok(const double *blk, int smax) {
   const int *hdr = reinterpret_cast<const int *>(blk);
   return hdr[3] == smax && hdr[0] >= 2 && hdr[0] <= smax && hdr[1] == 2 * hdr[0] + 1 && hdr[2] == 2 * hdr[1] + 6;
+}
+WG_MO_INLINE bool mo_block_ok_long(const double *blk, int smax) {
+  return mo_block_ok(blk, smax) && reinterpret_cast<const int *>(blk)[kMoTagInt] == 1;
 }
 struct MoSample {
   double zx, zy, com[4], left[6], right[6];

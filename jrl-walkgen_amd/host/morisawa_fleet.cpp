@@ -7,9 +7,11 @@
 // With --heights LO:HI gait b walks at its own CoM height, LO + (HI - LO) b / (B - 1), and with its own support times (a table of
 // multiples of T): a model per gait through wg_morisawa_walk_fleet_dev.
 //
+// With --long the walk goes through the long family (wg_morisawa_long_*: Z eliminated as a band) and --steps may be up to 64.
+//
 // Prints a checksum (FNV-1a, 64 bit, over the gaits' checksums of their own rows of CoM, ZMP and feet) and the milliseconds per fleet.
 //
-//   morisawa_fleet [--batch B] [--steps S] [--heights LO:HI]
+//   morisawa_fleet [--batch B] [--steps S] [--heights LO:HI] [--long]
 #include <chrono>
 #include <cstdlib>
 #include <random>
@@ -21,17 +23,26 @@ using wg_fleet::dev_upload;
 
 int main(int argc, char **argv) {
   int B = 4096, S = 7;
-  bool heights = false;
+  bool heights = false, lng = false;
   double h_lo = 0.7116911, h_hi = 0.7116911;
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--batch") && i + 1 < argc) B = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--steps") && i + 1 < argc) S = atoi(argv[++i]);
+    else if (!strcmp(argv[i], "--long")) lng = true;
     else if (!strcmp(argv[i], "--heights") && i + 1 < argc) {
       heights = sscanf(argv[++i], "%lf:%lf", &h_lo, &h_hi) == 2;
       if (!heights || !(h_lo > 0.0) || !(h_hi >= h_lo) || !(h_hi < 1e3)) { fprintf(stderr, "FAILED: need --heights LO:HI with 0 < LO <= HI\n"); return 1; }
     }
   }
-  if (B < 1 || S < 2 || S > WG_MORISAWA_MAX_STEPS) { fprintf(stderr, "FAILED: need B >= 1, 2 <= steps <= %d\n", WG_MORISAWA_MAX_STEPS); return 1; }
+  const int cap = lng ? WG_MORISAWA_LONG_MAX_STEPS : WG_MORISAWA_MAX_STEPS;
+  if (B < 1 || S < 2 || S > cap) { fprintf(stderr, "FAILED: need B >= 1, 2 <= steps <= %d%s\n", cap, lng ? "" : " (--long: 64)"); return 1; }
+  // the two families have one argument list per call: --long chooses the set
+  const auto length_fn = lng ? wg_morisawa_long_length : wg_morisawa_length;
+  const auto block_bytes_fn = lng ? wg_morisawa_long_block_bytes : wg_morisawa_block_bytes;
+  const auto walk_fn = lng ? wg_morisawa_long_walk_dev : wg_morisawa_walk_dev;
+  const auto walk_fleet_fn = lng ? wg_morisawa_long_walk_fleet_dev : wg_morisawa_walk_fleet_dev;
+  const auto solve_fn = lng ? wg_morisawa_long_solve : wg_morisawa_solve;
+  const auto sample_fn = lng ? wg_morisawa_long_sample : wg_morisawa_sample;
   CHECK_WG(wg_init(0));
   wg_morisawa_model_t base;
   wg_morisawa_defaults(&base);                                // 5 ms, 0.78 / 0.02 s supports, 0.07 m step height
@@ -68,11 +79,11 @@ int main(int argc, char **argv) {
   std::vector<int> len_g(B);
   int L = 0;
   for (int g = 0; g < B; ++g) {
-    len_g[g] = wg_morisawa_length(&models[g], S, t_start);
+    len_g[g] = length_fn(&models[g], S, t_start);
     if (len_g[g] < 1) { fprintf(stderr, "FAILED: gait %d has %d samples\n", g, len_g[g]); return 1; }
     L = len_g[g] > L ? len_g[g] : L;
   }
-  const size_t bb = wg_morisawa_block_bytes(S);
+  const size_t bb = block_bytes_fn(S);
 
   wg_rel_step_t *d_steps; int *d_ns, *d_status, *d_len, *d_lt, *d_rt; double *d_feet, *d_com0, *d_zx, *d_zy, *d_com, *d_left, *d_right;
   wg_morisawa_model_t *d_models; void *d_blocks;
@@ -98,11 +109,11 @@ int main(int argc, char **argv) {
     CHECK_HIP(hipStreamSynchronize(st));
     const auto t0 = std::chrono::steady_clock::now();
     if (heights)
-      CHECK_WG(wg_morisawa_walk_fleet_dev(d_models, base.T, B, S, d_steps, d_ns, d_feet, d_com0, d_blocks, d_status, t_start, L, d_zx, d_zy,
-                                          d_com, d_left, d_lt, d_right, d_rt, d_len, st));
+      CHECK_WG(walk_fleet_fn(d_models, base.T, B, S, d_steps, d_ns, d_feet, d_com0, d_blocks, d_status, t_start, L, d_zx, d_zy,
+                             d_com, d_left, d_lt, d_right, d_rt, d_len, st));
     else
-      CHECK_WG(wg_morisawa_walk_dev(&base, B, S, d_steps, d_ns, d_feet, d_com0, d_blocks, d_status, t_start, L, d_zx, d_zy, d_com, d_left,
-                                    d_lt, d_right, d_rt, d_len, st));
+      CHECK_WG(walk_fn(&base, B, S, d_steps, d_ns, d_feet, d_com0, d_blocks, d_status, t_start, L, d_zx, d_zy, d_com, d_left,
+                       d_lt, d_right, d_rt, d_len, st));
     CHECK_HIP(hipStreamSynchronize(st));
     sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   }
@@ -123,9 +134,9 @@ int main(int argc, char **argv) {
   auto check_gait = [&](int g) -> int {
     std::vector<double> blk(bb / sizeof(double)), hzx(L), hzy(L), hcom((size_t)L * 4), hl((size_t)L * 6), hr((size_t)L * 6);
     int hs = 0, hlen = 0;
-    CHECK_WG(wg_morisawa_solve(&models[g], 1, S, &steps[(size_t)g * S], &n_steps[g], &feet[(size_t)g * 6], &com0[(size_t)g * 3], blk.data(), &hs));
-    CHECK_WG(wg_morisawa_sample(1, S, blk.data(), &hs, t_start, base.T, L, hzx.data(), hzy.data(), hcom.data(), hl.data(), nullptr, hr.data(),
-                                nullptr, &hlen));
+    CHECK_WG(solve_fn(&models[g], 1, S, &steps[(size_t)g * S], &n_steps[g], &feet[(size_t)g * 6], &com0[(size_t)g * 3], blk.data(), &hs));
+    CHECK_WG(sample_fn(1, S, blk.data(), &hs, t_start, base.T, L, hzx.data(), hzy.data(), hcom.data(), hl.data(), nullptr, hr.data(), nullptr,
+                       &hlen));
     bool same = hs == WG_OK && hlen == len_g[g];
     for (int l = 0; same && l < L; ++l) {
       same = zx[(size_t)l * B + g] == hzx[l] && zy[(size_t)l * B + g] == hzy[l];
@@ -153,8 +164,8 @@ int main(int argc, char **argv) {
   }
   const unsigned long long sum = wg_fleet::fnv1a64(sums.data(), sums.size() * sizeof(sums[0]));
   if (heights) printf("morisawa_fleet: CoM heights %.4f .. %.4f m and support times per gait (a model per gait)\n", h_lo, h_hi);
-  printf("morisawa_fleet: %d analytic walks of %d steps (up to %d samples) in %.2f ms = %.0f walks/s; gait 0 ends at x = %.4f m (%d samples), "
-         "farthest %.2f m; gaits 0 and %d == host twins; checksum %016llx\n", B, S, L, sec * 1e3, B / sec,
+  printf("morisawa_fleet: %d analytic walks%s of %d steps (up to %d samples) in %.2f ms = %.0f walks/s; gait 0 ends at x = %.4f m (%d samples), "
+         "farthest %.2f m; gaits 0 and %d == host twins; checksum %016llx\n", B, lng ? " (long family)" : "", S, L, sec * 1e3, B / sec,
          com[((size_t)(len_g[0] - 1) * 4) * B + 0], len_g[0], far, B - 1, sum);
   wg_shutdown();
   return 0;

@@ -1075,12 +1075,23 @@ def morisawa_defaults():
     return m
 
 
+_MO, _MOL = "wg_morisawa_", "wg_morisawa_long_"       # the two families: one set of wrappers, the prefix chooses
+
+
+def _mo_block_bytes(fam, smax):
+    return int(getattr(lib(), fam + "block_bytes")(int(smax)))
+
+
+def _mo_length(fam, model, n_steps, t_start):
+    return int(getattr(lib(), fam + "length")(C.byref(model), int(n_steps), float(t_start)))
+
+
 def morisawa_block_bytes(smax):
-    return int(lib().wg_morisawa_block_bytes(int(smax)))
+    return _mo_block_bytes(_MO, smax)
 
 
 def morisawa_length(model, n_steps, t_start):
-    return int(lib().wg_morisawa_length(C.byref(model), int(n_steps), float(t_start)))
+    return _mo_length(_MO, model, n_steps, t_start)
 
 
 def morisawa_coshsinh(x):
@@ -1101,28 +1112,31 @@ def morisawa_system(model, steps, init_feet, com0):
     return Z, wx, wy
 
 
-def morisawa_solve(model, steps, n_steps, init_feet, com0, smax, blocks=None):
-    """Host twin.  model: one MorisawaModel, or (MorisawaModel * B) for a model per gait; steps: (RelStep * (B*smax)); n_steps [B];
-    init_feet [B, 6]; com0 [B, 3].  Returns (blocks [B, words] float64 -- `blocks` itself if given -- , status [B])."""
+def _mo_solve(fam, model, steps, n_steps, init_feet, com0, smax, blocks):
     n_steps = np.ascontiguousarray(n_steps, dtype=np.int32); B = n_steps.shape[0]
     init_feet = np.ascontiguousarray(init_feet, dtype=np.float64); com0 = np.ascontiguousarray(com0, dtype=np.float64)
     assert init_feet.shape == (B, 6) and com0.shape == (B, 3) and len(steps) == B * smax
     if blocks is None:
-        blocks = np.zeros((B, morisawa_block_bytes(smax) // 8))
+        blocks = np.zeros((B, _mo_block_bytes(fam, smax) // 8))
     status = np.zeros(B, np.int32)
     fleet = not isinstance(model, MorisawaModel)
-    fn = lib().wg_morisawa_solve_fleet if fleet else lib().wg_morisawa_solve
+    fn = getattr(lib(), fam + ("solve_fleet" if fleet else "solve"))
     _check(fn(C.addressof(model), B, int(smax), C.addressof(steps), _hp(n_steps), _hp(init_feet), _hp(com0), _hp(blocks), _hp(status)))
     return blocks, status
 
 
-def morisawa_view(block, smax):
-    """dict of numpy arrays (copies) from one block: what wg_morisawa_block_unpack points at, cut to the gait's own sizes"""
+def morisawa_solve(model, steps, n_steps, init_feet, com0, smax, blocks=None):
+    """Host twin.  model: one MorisawaModel, or (MorisawaModel * B) for a model per gait; steps: (RelStep * (B*smax)); n_steps [B];
+    init_feet [B, 6]; com0 [B, 3].  Returns (blocks [B, words] float64 -- `blocks` itself if given -- , status [B])."""
+    return _mo_solve(_MO, model, steps, n_steps, init_feet, com0, smax, blocks)
+
+
+def _mo_view(fam, block, smax):
     block = np.ascontiguousarray(block, dtype=np.float64)
     v = MorisawaView()
-    rc = lib().wg_morisawa_block_unpack(_hp(block), int(smax), C.byref(v))
+    rc = getattr(lib(), fam + "block_unpack")(_hp(block), int(smax), C.byref(v))
     if rc != 0:
-        raise WgError(f"wg_morisawa_block_unpack: {rc}")
+        raise WgError(f"{fam}block_unpack: {rc}")
     I, n, S = v.n_int, v.n, v.n_steps
     arr = lambda p, *shape: np.ctypeslib.as_array(p, shape=shape).copy()  # noqa: E731
     r = dict(n_steps=S, n_int=I, n=n, smax=v.smax, com_height=v.com_height, t_total=v.t_total)
@@ -1135,13 +1149,19 @@ def morisawa_view(block, smax):
     r["support"] = arr(v.support, S, 3)
     for k in ("wx", "wy", "yx", "yy", "piv"):
         r[k] = arr(getattr(v, k), n)
-    r["lu"] = arr(v.lu, v.lu_pitch, v.lu_pitch)[:n, :n]
+    if fam == _MOL:
+        r["band"] = arr(v.lu, n, v.lu_pitch)        # row i: columns i - 5 .. i + 9 in words 0 .. 14, multipliers where they were made
+    else:
+        r["lu"] = arr(v.lu, v.lu_pitch, v.lu_pitch)[:n, :n]
     return r
 
 
-def morisawa_sample(blocks, status, smax, t_start, T, lcap, want=MORISAWA_OUTPUTS, into=None):
-    """Host twin of the sampler.  Returns dict(zmp_x, zmp_y [lcap, B], com [lcap, 4, B], left, right [lcap, 6, B], left_type,
-    right_type [lcap, B] int32, length [B]) with the outputs named in `want`; `into`: arrays to write into instead of zeros."""
+def morisawa_view(block, smax):
+    """dict of numpy arrays (copies) from one block: what wg_morisawa_block_unpack points at, cut to the gait's own sizes"""
+    return _mo_view(_MO, block, smax)
+
+
+def _mo_sample(fam, blocks, status, smax, t_start, T, lcap, want, into):
     blocks = np.ascontiguousarray(blocks, dtype=np.float64); B = blocks.shape[0]
     shapes = dict(zmp_x=(lcap, B), zmp_y=(lcap, B), com=(lcap, 4, B), left=(lcap, 6, B), right=(lcap, 6, B), left_type=(lcap, B),
                   right_type=(lcap, B))
@@ -1151,9 +1171,15 @@ def morisawa_sample(blocks, status, smax, t_start, T, lcap, want=MORISAWA_OUTPUT
         assert r[k].shape == shapes[k] and r[k].flags.c_contiguous
     r["length"] = into["length"] if into is not None and "length" in into else np.zeros(B, np.int32)
     st = None if status is None else np.ascontiguousarray(status, dtype=np.int32)
-    _check(lib().wg_morisawa_sample(B, int(smax), _hp(blocks), _hp(st), float(t_start), float(T), int(lcap),
-                                    *[_hp(r.get(k)) for k in MORISAWA_OUTPUTS], _hp(r["length"])))
+    _check(getattr(lib(), fam + "sample")(B, int(smax), _hp(blocks), _hp(st), float(t_start), float(T), int(lcap),
+                                          *[_hp(r.get(k)) for k in MORISAWA_OUTPUTS], _hp(r["length"])))
     return r
+
+
+def morisawa_sample(blocks, status, smax, t_start, T, lcap, want=MORISAWA_OUTPUTS, into=None):
+    """Host twin of the sampler.  Returns dict(zmp_x, zmp_y [lcap, B], com [lcap, 4, B], left, right [lcap, 6, B], left_type,
+    right_type [lcap, B] int32, length [B]) with the outputs named in `want`; `into`: arrays to write into instead of zeros."""
+    return _mo_sample(_MO, blocks, status, smax, t_start, T, lcap, want, into)
 
 
 def _mo_outs(outs):
@@ -1161,29 +1187,108 @@ def _mo_outs(outs):
     return [outs.get(k) for k in MORISAWA_OUTPUTS]
 
 
+def _mo_solve_dev(fam, model, B, smax, steps_ptr, n_steps_ptr, init_feet_ptr, com0_ptr, blocks_ptr, status_ptr, stream, ctx):
+    if isinstance(model, MorisawaModel):
+        _call(fam + "solve_dev", ctx, C.addressof(model), int(B), int(smax), steps_ptr, n_steps_ptr, init_feet_ptr,
+              com0_ptr, blocks_ptr, status_ptr, stream)
+    else:
+        _call(fam + "solve_fleet_dev", ctx, model, int(B), int(smax), steps_ptr, n_steps_ptr, init_feet_ptr, com0_ptr,
+              blocks_ptr, status_ptr, stream)
+
+
+def _mo_sample_dev(fam, B, smax, blocks_ptr, status_ptr, t_start, T, lcap, outs, length_ptr, stream, ctx):
+    _call(fam + "sample_dev", ctx, int(B), int(smax), blocks_ptr, status_ptr, float(t_start), float(T), int(lcap),
+          *_mo_outs(outs), length_ptr, stream)
+
+
+def _mo_walk_dev(fam, model, B, smax, steps_ptr, n_steps_ptr, init_feet_ptr, com0_ptr, blocks_ptr, status_ptr, t_start, lcap, outs,
+                 length_ptr, stream, T, ctx):
+    if isinstance(model, MorisawaModel):
+        _call(fam + "walk_dev", ctx, C.addressof(model), int(B), int(smax), steps_ptr, n_steps_ptr, init_feet_ptr,
+              com0_ptr, blocks_ptr, status_ptr, float(t_start), int(lcap), *_mo_outs(outs), length_ptr, stream)
+    else:
+        _call(fam + "walk_fleet_dev", ctx, model, float(T), int(B), int(smax), steps_ptr, n_steps_ptr, init_feet_ptr,
+              com0_ptr, blocks_ptr, status_ptr, float(t_start), int(lcap), *_mo_outs(outs), length_ptr, stream)
+
+
 def morisawa_solve_dev(model, B, smax, steps_ptr, n_steps_ptr, init_feet_ptr, com0_ptr, blocks_ptr, status_ptr, stream=None,
                        ctx=None):
     """every pointer a device pointer; `model`: a MorisawaModel (host), or a device pointer to B of them (the fleet form)"""
-    if isinstance(model, MorisawaModel):
-        _call("wg_morisawa_solve_dev", ctx, C.addressof(model), int(B), int(smax), steps_ptr, n_steps_ptr, init_feet_ptr,
-              com0_ptr, blocks_ptr, status_ptr, stream)
-    else:
-        _call("wg_morisawa_solve_fleet_dev", ctx, model, int(B), int(smax), steps_ptr, n_steps_ptr, init_feet_ptr, com0_ptr,
-              blocks_ptr, status_ptr, stream)
+    _mo_solve_dev(_MO, model, B, smax, steps_ptr, n_steps_ptr, init_feet_ptr, com0_ptr, blocks_ptr, status_ptr, stream, ctx)
 
 
 def morisawa_sample_dev(B, smax, blocks_ptr, status_ptr, t_start, T, lcap, outs, length_ptr=None, stream=None, ctx=None):
     """`outs`: device pointers by name (MORISAWA_OUTPUTS, time-major), absent = not wanted"""
-    _call("wg_morisawa_sample_dev", ctx, int(B), int(smax), blocks_ptr, status_ptr, float(t_start), float(T), int(lcap),
-          *_mo_outs(outs), length_ptr, stream)
+    _mo_sample_dev(_MO, B, smax, blocks_ptr, status_ptr, t_start, T, lcap, outs, length_ptr, stream, ctx)
 
 
 def morisawa_walk_dev(model, B, smax, steps_ptr, n_steps_ptr, init_feet_ptr, com0_ptr, blocks_ptr, status_ptr, t_start, lcap,
                       outs, length_ptr=None, stream=None, T=None, ctx=None):
     """solve and sample on one stream; `model` as in morisawa_solve_dev, the fleet form needs the common sampling period T"""
-    if isinstance(model, MorisawaModel):
-        _call("wg_morisawa_walk_dev", ctx, C.addressof(model), int(B), int(smax), steps_ptr, n_steps_ptr, init_feet_ptr,
-              com0_ptr, blocks_ptr, status_ptr, float(t_start), int(lcap), *_mo_outs(outs), length_ptr, stream)
-    else:
-        _call("wg_morisawa_walk_fleet_dev", ctx, model, float(T), int(B), int(smax), steps_ptr, n_steps_ptr, init_feet_ptr,
-              com0_ptr, blocks_ptr, status_ptr, float(t_start), int(lcap), *_mo_outs(outs), length_ptr, stream)
+    _mo_walk_dev(_MO, model, B, smax, steps_ptr, n_steps_ptr, init_feet_ptr, com0_ptr, blocks_ptr, status_ptr, t_start, lcap, outs,
+                 length_ptr, stream, T, ctx)
+
+
+# ---- the long family (wg_morisawa_long_*): walks of up to MORISAWA_LONG_MAX_STEPS steps, Z eliminated as a band.  The same
+# arguments and results as the wrappers above; blocks of the two families are not interchangeable ----
+MORISAWA_LONG_MAX_STEPS = 64
+MORISAWA_BAND_PITCH, MORISAWA_BAND_KL, MORISAWA_BAND_KU = 16, 5, 9     # row i of the band: columns i - 5 .. i + 9
+
+
+def morisawa_long_block_bytes(smax):
+    return _mo_block_bytes(_MOL, smax)
+
+
+def morisawa_long_length(model, n_steps, t_start):
+    return _mo_length(_MOL, model, n_steps, t_start)
+
+
+def morisawa_long_system(model, steps, init_feet, com0):
+    """Z before the elimination in row-band form [n, 16] (entry (i, c) at [i, c - i + 5]), w of x, w of y; steps: (RelStep * S)"""
+    S = len(steps)
+    n = 4 * S + 8
+    Zb, wx, wy = np.zeros((n, MORISAWA_BAND_PITCH)), np.zeros(n), np.zeros(n)
+    feet, com = np.ascontiguousarray(init_feet, dtype=np.float64), np.ascontiguousarray(com0, dtype=np.float64)
+    rc = lib().wg_morisawa_long_system(C.byref(model), S, C.addressof(steps), _hp(feet), _hp(com), _hp(Zb), _hp(wx), _hp(wy))
+    if rc != n:
+        raise WgError(f"wg_morisawa_long_system: {rc}")
+    return Zb, wx, wy
+
+
+def morisawa_band_to_dense(band):
+    """[n, 16] row band -> [n, n]"""
+    n = band.shape[0]
+    Z = np.zeros((n, n))
+    for i in range(n):
+        lo, hi = max(0, i - MORISAWA_BAND_KL), min(n - 1, i + MORISAWA_BAND_KU)
+        Z[i, lo:hi + 1] = band[i, lo - i + MORISAWA_BAND_KL:hi - i + MORISAWA_BAND_KL + 1]
+    return Z
+
+
+def morisawa_long_solve(model, steps, n_steps, init_feet, com0, smax, blocks=None):
+    """Host twin of the long solve: morisawa_solve's arguments and results"""
+    return _mo_solve(_MOL, model, steps, n_steps, init_feet, com0, smax, blocks)
+
+
+def morisawa_long_view(block, smax):
+    """morisawa_view of a long block; in place of "lu" it has "band" [n, 16] (see include/wg_mpc.h for the convention)"""
+    return _mo_view(_MOL, block, smax)
+
+
+def morisawa_long_sample(blocks, status, smax, t_start, T, lcap, want=MORISAWA_OUTPUTS, into=None):
+    return _mo_sample(_MOL, blocks, status, smax, t_start, T, lcap, want, into)
+
+
+def morisawa_long_solve_dev(model, B, smax, steps_ptr, n_steps_ptr, init_feet_ptr, com0_ptr, blocks_ptr, status_ptr, stream=None,
+                            ctx=None):
+    _mo_solve_dev(_MOL, model, B, smax, steps_ptr, n_steps_ptr, init_feet_ptr, com0_ptr, blocks_ptr, status_ptr, stream, ctx)
+
+
+def morisawa_long_sample_dev(B, smax, blocks_ptr, status_ptr, t_start, T, lcap, outs, length_ptr=None, stream=None, ctx=None):
+    _mo_sample_dev(_MOL, B, smax, blocks_ptr, status_ptr, t_start, T, lcap, outs, length_ptr, stream, ctx)
+
+
+def morisawa_long_walk_dev(model, B, smax, steps_ptr, n_steps_ptr, init_feet_ptr, com0_ptr, blocks_ptr, status_ptr, t_start, lcap,
+                           outs, length_ptr=None, stream=None, T=None, ctx=None):
+    _mo_walk_dev(_MOL, model, B, smax, steps_ptr, n_steps_ptr, init_feet_ptr, com0_ptr, blocks_ptr, status_ptr, t_start, lcap, outs,
+                 length_ptr, stream, T, ctx)

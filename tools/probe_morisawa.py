@@ -7,7 +7,8 @@ output resident, from 2 t_single as the reference's queue), on one stream:
                    hold no lock and ctypes drops the interpreter's)
 (a) and (d) must leave the same checksum (ZMP, CoM, lengths, every 64th row of both feet) -- the host's bytes are the kernel's --
 and every variant the same checksum in every repetition.  The variants alternate PR (5) times in one session; min, median, max.
-One JSON line at the end."""
+One JSON line at the end.
+With --long: the long family (wg_morisawa_long_*) at S = 7, 14, 32 and 64 next to the short solve at 7 and 14; see long_probe."""
 import concurrent.futures as cf, ctypes as C, importlib, json, os, sys, time, zlib, numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -18,6 +19,97 @@ dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()  # noqa: E731
 raw = lambda ct: torch.frombuffer(bytearray(bytes(ct)), dtype=torch.uint8).cuda()  # noqa: E731
 p = lambda t: t.data_ptr()  # noqa: E731
 stream = torch.cuda.Stream(); sp = stream.cuda_stream
+
+
+
+def long_probe():
+    """--long: the long family (wg_morisawa_long_*, Z as a band) at S = 7, 14, 32 and 64 on one fleet of B gaits per size: the long
+    solve and the long walk on the device, next to them at S = 7 and 14 the short solve of the same build on the same fleet, and the
+    host loop (wg_morisawa_long_solve + _long_sample in chunks on the cores granted).  PR alternating repetitions, medians.  The long
+    blocks of a chunk of gaits must be the host twin's bytes, and at S <= 14 the long walk's outputs the short walk's by value."""
+    m = wg.morisawa_defaults()
+    result = dict(B=B, reps=REPS, cores=CORES, sizes={})
+    pool = cf.ThreadPoolExecutor(CORES)
+    for S_ in (7, 14, 32, 64):
+        rng = np.random.default_rng(2007 + S_)
+        steps = (wg.RelStep * (B * S_))()
+        for g in range(B):
+            side = 1.0 if g & 1 else -1.0
+            for i in range(S_):
+                ends = i in (0, S_ - 1)
+                steps[g * S_ + i] = wg.RelStep(0.0 if ends else rng.uniform(0.1, 0.25), side * (0.105 if i == 0 else 0.19),
+                                               0.0 if ends else rng.uniform(-5.0, 5.0), 0.0, 0.0, 1, 0)
+                side = -side
+        n_steps = np.full(B, S_, np.int32)
+        feet = np.tile([0.0, 0.09, 0.0, 0.0, -0.09, 0.0], (B, 1))
+        com0 = np.tile([0.0316054587, 0.0, 0.7116911], (B, 1)); com0[:, 2] += np.linspace(0.0, 0.1, B)
+        t0 = 2.0 * m.t_single
+        lcap = wg.morisawa_long_length(m, S_, t0)
+        words = wg.morisawa_long_block_bytes(S_) // 8
+        d_steps, d_ns, d_feet, d_com0 = raw(steps), dev(n_steps), dev(feet), dev(com0)
+        f64 = lambda *s: torch.zeros(*s, dtype=torch.float64, device="cuda")  # noqa: E731
+        i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device="cuda")  # noqa: E731
+        O = dict(zmp_x=f64(lcap, B), zmp_y=f64(lcap, B), com=f64(lcap, 4, B), left=f64(lcap, 6, B), left_type=i32(lcap, B),
+                 right=f64(lcap, 6, B), right_type=i32(lcap, B))
+        outs = {k: p(v) for k, v in O.items()}
+        blocks, status, ln = f64(B, words), i32(B), i32(B)
+        args = (B, S_, p(d_steps), p(d_ns), p(d_feet), p(d_com0))
+        ways = {"long_walk": lambda: wg.morisawa_long_walk_dev(m, *args, p(blocks), p(status), t0, lcap, outs, p(ln), sp),
+                "long_solve": lambda: wg.morisawa_long_solve_dev(m, *args, p(blocks), p(status), sp),
+                "long_sample": lambda: wg.morisawa_long_sample_dev(B, S_, p(blocks), p(status), t0, m.T, lcap, outs, p(ln), sp)}
+        if S_ <= wg.MORISAWA_MAX_STEPS:
+            sblocks = f64(B, wg.morisawa_block_bytes(S_) // 8)
+            ways["short_solve"] = lambda: wg.morisawa_solve_dev(m, *args, p(sblocks), p(status), sp)
+            ways["short_walk"] = lambda: wg.morisawa_walk_dev(m, *args, p(sblocks), p(status), t0, lcap, outs, p(ln), sp)
+        CH = 32
+        step_bytes = bytes(steps)
+
+        def host_chunk(lo, keep=None):
+            hi = min(lo + CH, B)
+            st = (wg.RelStep * ((hi - lo) * S_)).from_buffer_copy(step_bytes[lo * S_ * 48:hi * S_ * 48])
+            blk, stat = wg.morisawa_long_solve(m, st, n_steps[lo:hi], feet[lo:hi], com0[lo:hi], S_)
+            r = wg.morisawa_long_sample(blk, stat, S_, t0, m.T, lcap, want=("zmp_x", "zmp_y", "com", "left", "right"))
+            if keep is not None:
+                keep.update(blocks=blk, **r)
+
+        # what is compared: the first chunk of gaits, host against device; at S <= 14 the long walk against the short walk
+        first = {}
+        host_chunk(0, first)
+        ways["long_walk"](); torch.cuda.synchronize()
+        assert int(status.abs().max()) == 0 and int(ln.min()) == int(ln.max()) == lcap
+        assert blocks[:CH].cpu().numpy().tobytes() == first["blocks"].tobytes()
+        for k in ("zmp_x", "zmp_y", "com", "left", "right"):
+            assert O[k][..., :CH].cpu().numpy().tobytes() == np.ascontiguousarray(first[k]).tobytes(), k
+        if "short_walk" in ways:
+            keep = {k: v.clone() for k, v in O.items()}
+            ways["short_walk"](); torch.cuda.synchronize()
+            assert all(bool((keep[k] == O[k]).all()) for k in O)
+        secs = {k: [] for k in list(ways) + ["host"]}
+        for _ in range(REPS):                                      # alternating: a drift of the machine hits every variant alike
+            for k in ways:
+                if k == "long_sample":
+                    ways["long_solve"](); torch.cuda.synchronize()
+                secs[k].append(clock(ways[k]))
+            t = time.perf_counter(); list(pool.map(host_chunk, range(0, B, CH))); secs["host"].append(time.perf_counter() - t)
+        row = dict(lcap=lcap, block_bytes=words * 8)
+        for k, v in secs.items():
+            ms = np.array(v) * 1e3
+            row[k] = dict(ms_median=float(np.median(ms)), ms_min=float(ms.min()), ms_max=float(ms.max()))
+        result["sizes"][S_] = row
+        print("S = %2d, %d gaits x %d samples, ms (median of %d): %s" % (S_, B, lcap, REPS, "  ".join("%s %.3f" % (k, row[k]["ms_median"]) for k in secs)))
+        del O, blocks, outs
+        torch.cuda.empty_cache()
+    print(json.dumps(result))
+
+
+if "--long" in sys.argv:
+    def clock(fn):
+        torch.cuda.synchronize(); t = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t
+    long_probe()
+    sys.exit(0)
 
 m = wg.morisawa_defaults()
 rng = np.random.default_rng(2007)
