@@ -1230,7 +1230,7 @@ int wg_gramian_batch_dev(int B, int N, const double *T, const double *h, double 
  * Two steps: wg_morisawa_solve* turns each gait's steps into a TRAJECTORY BLOCK of wg_morisawa_block_bytes(smax) bytes (counts,
  * interval times and omega_j, per interval the ZMP and CoG polynomials of x and y and the weights V, W, both feet's polynomials,
  * the ZMP profile, the absolute support feet, w and y, Z's LU factor and pivots -- a new right-hand side can be solved from the
- * block -- zeros elsewhere: blocks compare as bytes); wg_morisawa_sample* evaluates blocks on one clock.
+ * block, and wg_morisawa_resolve* below does -- zeros elsewhere: blocks compare as bytes); wg_morisawa_sample* evaluates blocks on one clock.
  *   steps      B x smax   gait b uses the first n_steps[b]; 2 <= n_steps[b] <= smax <= WG_MORISAWA_MAX_STEPS.  sx, sy, theta
  *                         (degrees) are read; the times are the model's
  *   init_feet  B x 6      left x, y, theta, right x, y, theta at the start (z, omega, omega2 and every speed 0)
@@ -1369,6 +1369,58 @@ int wg_morisawa_long_walk_fleet_dev(const wg_morisawa_model_t *models, double T,
                                     const int *n_steps, const double *init_feet, const double *com0, void *blocks, int *status,
                                     double t_start, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *com_tm, double *left_tm,
                                     int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream);
+
+/* Morisawa walks re-planned from a block's kept factor: wg_morisawa_resolve*, wg_morisawa_long_resolve* -------------------------
+ *
+ * Z depends on the interval times, the CoM height and the step count and on nothing else, so a solved block -- a FACTOR BLOCK --
+ * serves every other plan on its timing, as the reference's kept dgetrf_ result does until ResetTheResolutionOfThePolynomial
+ * (AnalyticalMorisawaCompact.cpp:263-357).  Given factor blocks and, per gait, a plan -- steps, initial feet, start CoM x and y --
+ * these calls write the block that wg_morisawa_solve* (wg_morisawa_long_solve*) would write for that plan with the model, CoM
+ * height and step count the gait's factor block was made with: every byte of it, the copies of dT, omega, tref, pivots and factor
+ * included, so blocks still compare as bytes and wg_morisawa[_long]_sample* read them unchanged.  Z is not built and no pivot is
+ * searched; both right-hand sides go through the stored factor, each entry meeting the products and differences of the full
+ * solve in the full solve's order.  The whole walk is planned from t = 0; nothing here changes a walk under way.
+ *   factors    n_factors blocks of this family and this smax (wg_morisawa[_long]_block_bytes(smax) apart)
+ *   factor_of  B ints: the factor block of gait b; NULL: every gait uses block 0
+ *   steps      B x smax   gait b uses as many as its factor block has steps: there is no n_steps
+ *   init_feet, com0, blocks, status   as for wg_morisawa_solve; com0[b][2] must be the factor block's height
+ * A gait is refused by itself, status WG_MORISAWA_BAD_INPUT and its block left untouched, when factor_of[b] is outside
+ * [0, n_factors); when its factor block is not a solved block of this family and smax (a short block handed to the long call and
+ * a long block handed to the short call among them, and a block whose pivots do not lie among their columns' rows); when the model's times do not give the block's interval times bit for bit;
+ * when com0[b][2] is not the block's CoM height bit for bit; when an input is not finite, as wg_morisawa_solve tests it.
+ * WG_MORISAWA_SINGULAR does not arise.  Host-side errors (WG_ERR_BAD_ARG, nothing launched): NULL inputs, B < 0, n_factors < 1,
+ * smax outside the family's range.  B == 0 is WG_OK.
+ * `blocks` must not overlap `factors`: a factor block is read while blocks are written; this is not checked.  Whether a factor
+ * block is the one the caller means is the caller's business: a stale block that is still a valid block of these times and this
+ * height gives the bytes of a solve with its header, which is what these calls promise.
+ * wg_morisawa_resolve, _resolve_fleet and their long forms are host arithmetic without a device call; the _dev forms take DEVICE
+ * pointers (the one-model forms the model on the host, by value into the launch, as wg_morisawa_solve_dev) and are asynchronous on
+ * hip_stream: factor blocks made by wg_morisawa[_long]_solve_dev earlier on that stream need no synchronisation, and
+ * wg_morisawa[_long]_sample_dev behind the call on that stream samples the new walks.
+ * Added without a change of wg_abi_version(): detect by symbol. */
+int wg_morisawa_resolve(const wg_morisawa_model_t *model, int B, int smax, const void *factors, int n_factors, const int *factor_of,
+                        const wg_rel_step_t *steps, const double *init_feet, const double *com0, void *blocks, int *status);
+int wg_morisawa_resolve_fleet(const wg_morisawa_model_t *models, int B, int smax, const void *factors, int n_factors,
+                              const int *factor_of, const wg_rel_step_t *steps, const double *init_feet, const double *com0,
+                              void *blocks, int *status);
+int wg_morisawa_resolve_dev(const wg_morisawa_model_t *model, int B, int smax, const void *factors, int n_factors,
+                            const int *factor_of, const wg_rel_step_t *steps, const double *init_feet, const double *com0,
+                            void *blocks, int *status, void *hip_stream);
+int wg_morisawa_resolve_fleet_dev(const wg_morisawa_model_t *models, int B, int smax, const void *factors, int n_factors,
+                                  const int *factor_of, const wg_rel_step_t *steps, const double *init_feet, const double *com0,
+                                  void *blocks, int *status, void *hip_stream);
+int wg_morisawa_long_resolve(const wg_morisawa_model_t *model, int B, int smax, const void *factors, int n_factors,
+                             const int *factor_of, const wg_rel_step_t *steps, const double *init_feet, const double *com0,
+                             void *blocks, int *status);
+int wg_morisawa_long_resolve_fleet(const wg_morisawa_model_t *models, int B, int smax, const void *factors, int n_factors,
+                                   const int *factor_of, const wg_rel_step_t *steps, const double *init_feet, const double *com0,
+                                   void *blocks, int *status);
+int wg_morisawa_long_resolve_dev(const wg_morisawa_model_t *model, int B, int smax, const void *factors, int n_factors,
+                                 const int *factor_of, const wg_rel_step_t *steps, const double *init_feet, const double *com0,
+                                 void *blocks, int *status, void *hip_stream);
+int wg_morisawa_long_resolve_fleet_dev(const wg_morisawa_model_t *models, int B, int smax, const void *factors, int n_factors,
+                                       const int *factor_of, const wg_rel_step_t *steps, const double *init_feet,
+                                       const double *com0, void *blocks, int *status, void *hip_stream);
 
 /* The context forms of the entry points above (same arguments after the context, same semantics) ----------------------------
  *
@@ -1561,7 +1613,19 @@ int wg_dimitrov_follow_fleet_dev_ctx(wg_ctx_t *ctx, int B, const wg_dimitrov_fle
   X(int, wg_morisawa_long_walk_fleet_dev, (const wg_morisawa_model_t *models, double T, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, \
     const double *init_feet, const double *com0, void *blocks, int *status, double t_start, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *com_tm, \
     double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream), (models, T, B, smax, steps, n_steps, init_feet, \
-    com0, blocks, status, t_start, lcap, zmp_x_tm, zmp_y_tm, com_tm, left_tm, left_type_tm, right_tm, right_type_tm, length, hip_stream))
+    com0, blocks, status, t_start, lcap, zmp_x_tm, zmp_y_tm, com_tm, left_tm, left_type_tm, right_tm, right_type_tm, length, hip_stream)) \
+  X(int, wg_morisawa_resolve_dev, (const wg_morisawa_model_t *model, int B, int smax, const void *factors, int n_factors, const int *factor_of, \
+    const wg_rel_step_t *steps, const double *init_feet, const double *com0, void *blocks, int *status, void *hip_stream), (model, B, smax, factors, \
+    n_factors, factor_of, steps, init_feet, com0, blocks, status, hip_stream)) \
+  X(int, wg_morisawa_resolve_fleet_dev, (const wg_morisawa_model_t *models, int B, int smax, const void *factors, int n_factors, const int *factor_of, \
+    const wg_rel_step_t *steps, const double *init_feet, const double *com0, void *blocks, int *status, void *hip_stream), (models, B, smax, factors, \
+    n_factors, factor_of, steps, init_feet, com0, blocks, status, hip_stream)) \
+  X(int, wg_morisawa_long_resolve_dev, (const wg_morisawa_model_t *model, int B, int smax, const void *factors, int n_factors, const int *factor_of, \
+    const wg_rel_step_t *steps, const double *init_feet, const double *com0, void *blocks, int *status, void *hip_stream), (model, B, smax, factors, \
+    n_factors, factor_of, steps, init_feet, com0, blocks, status, hip_stream)) \
+  X(int, wg_morisawa_long_resolve_fleet_dev, (const wg_morisawa_model_t *models, int B, int smax, const void *factors, int n_factors, \
+    const int *factor_of, const wg_rel_step_t *steps, const double *init_feet, const double *com0, void *blocks, int *status, void *hip_stream), (models, \
+    B, smax, factors, n_factors, factor_of, steps, init_feet, com0, blocks, status, hip_stream))
 #define WG_CTX_UNPAREN_(...) __VA_ARGS__
 #define WG_CTX_PROTO_(ret, name, params, args) ret name##_ctx(wg_ctx_t *ctx, WG_CTX_UNPAREN_ params);
 WG_CTX_FORWARDED(WG_CTX_PROTO_)

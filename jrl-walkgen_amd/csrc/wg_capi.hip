@@ -2440,6 +2440,22 @@ int mo_solve_launch(wg_ctx *ctx, const wg_morisawa_model_t *mf, int B, int smax,
     return launch_lds(wg::wg_morisawa_solve_long_kernel<FLEET>, dim3(B), dim3(64), lds, st, m, FLEET ? mf : nullptr, B, smax, steps, n_steps, init_feet, com0, static_cast<double *>(blocks), status);
   return launch_lds(wg::wg_morisawa_solve_kernel<FLEET>, dim3(B), dim3(64), lds, st, m, FLEET ? mf : nullptr, B, smax, steps, n_steps, init_feet, com0, static_cast<double *>(blocks), status);
 }
+// the re-plan from kept factors: the solve's launch shape and work area; a gait's step count is its factor block's
+template <bool FLEET, bool LONG>
+int mo_resolve_launch(wg_ctx *ctx, const wg_morisawa_model_t *mf, int B, int smax, const void *factors, int n_factors, const int *factor_of, const wg_rel_step_t *steps, const double *init_feet, const double *com0, void *blocks, int *status, hipStream_t st) {
+  if (int rc = use_ctx(ctx)) return rc;
+  if (!mf || B < 0 || smax < 2 || smax > mo_cap<LONG>() || !factors || n_factors < 1 || !steps || !init_feet || !com0 || !blocks || !status)
+    return fail(WG_ERR_BAD_ARG, "need a model, B >= 0, 2 <= smax <= %d, factors, n_factors >= 1, non-null steps, init_feet, com0, blocks, status", mo_cap<LONG>());
+  if (B == 0) return WG_OK;
+  wg_morisawa_model_t m;
+  memset(&m, 0, sizeof m);
+  if (!FLEET) m = *mf;
+  const size_t lds = (size_t)(LONG ? wg::mo_layout_long(smax) : wg::mo_layout(smax)).work_words * sizeof(double);
+  std::lock_guard<std::mutex> launch_lk(ctx->launch_mu);
+  if (LONG)
+    return launch_lds(wg::wg_morisawa_resolve_long_kernel<FLEET>, dim3(B), dim3(64), lds, st, m, FLEET ? mf : nullptr, B, smax, static_cast<const double *>(factors), n_factors, factor_of, steps, init_feet, com0, static_cast<double *>(blocks), status);
+  return launch_lds(wg::wg_morisawa_resolve_kernel<FLEET>, dim3(B), dim3(64), lds, st, m, FLEET ? mf : nullptr, B, smax, static_cast<const double *>(factors), n_factors, factor_of, steps, init_feet, com0, static_cast<double *>(blocks), status);
+}
 // the clock of the launch into the context's buffer, then a lane per gait and kMoSampleChunk samples
 template <bool LONG>
 int mo_sample_launch(wg_ctx *ctx, int B, int smax, const void *blocks, const int *status, double t_start, double T, int lcap, const wg::MoOut &O, int *length, hipStream_t st) {
@@ -2477,6 +2493,12 @@ extern "C" {
   }                                                                                                                                             \
   int stem##solve_fleet_dev_ctx(wg_ctx_t *ctx, const wg_morisawa_model_t *models, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, const double *com0, void *blocks, int *status, void *hip_stream) { \
     return mo_solve_launch<true, LONG>(ctx, models, B, smax, steps, n_steps, init_feet, com0, blocks, status, reinterpret_cast<hipStream_t>(hip_stream)); \
+  }                                                                                                                                             \
+  int stem##resolve_dev_ctx(wg_ctx_t *ctx, const wg_morisawa_model_t *model, int B, int smax, const void *factors, int n_factors, const int *factor_of, const wg_rel_step_t *steps, const double *init_feet, const double *com0, void *blocks, int *status, void *hip_stream) { \
+    return mo_resolve_launch<false, LONG>(ctx, model, B, smax, factors, n_factors, factor_of, steps, init_feet, com0, blocks, status, reinterpret_cast<hipStream_t>(hip_stream)); \
+  }                                                                                                                                             \
+  int stem##resolve_fleet_dev_ctx(wg_ctx_t *ctx, const wg_morisawa_model_t *models, int B, int smax, const void *factors, int n_factors, const int *factor_of, const wg_rel_step_t *steps, const double *init_feet, const double *com0, void *blocks, int *status, void *hip_stream) { \
+    return mo_resolve_launch<true, LONG>(ctx, models, B, smax, factors, n_factors, factor_of, steps, init_feet, com0, blocks, status, reinterpret_cast<hipStream_t>(hip_stream)); \
   }                                                                                                                                             \
   int stem##sample_dev_ctx(wg_ctx_t *ctx, int B, int smax, const void *blocks, const int *status, double t_start, double T, int lcap, double *zmp_x_tm, double *zmp_y_tm, double *com_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm, int *length, void *hip_stream) { \
     const wg::MoOut O{zmp_x_tm, zmp_y_tm, com_tm, left_tm, right_tm, left_type_tm, right_type_tm};                                               \

@@ -1,6 +1,6 @@
 // Morisawa-2007 analytic walks, host side of the C ABI (include/wg_mpc.h: wg_morisawa_defaults, _block_bytes, _block_unpack,
-// _length, _coshsinh, _system, _solve, _solve_fleet, _sample, and the wg_morisawa_long_* forms of all but the first and _coshsinh:
-// walks of up to WG_MORISAWA_LONG_MAX_STEPS steps, Z as a band).
+// _length, _coshsinh, _system, _solve, _solve_fleet, _resolve, _resolve_fleet, _sample, and the wg_morisawa_long_* forms of all but
+// the first and _coshsinh: walks of up to WG_MORISAWA_LONG_MAX_STEPS steps, Z as a band).
 //
 // The arithmetic is wg_morisawa_math.hpp, the one text this file and the kernels (wg_morisawa_kernels.hpp) compile: a block or a
 // sample made here has the bytes the device makes.  Nothing here calls the device, so these run where there is none.
@@ -30,6 +30,33 @@ int solve_host(bool lng, const wg_morisawa_model_t *models, bool per_gait, int B
     }
     const int rc = wg::mo_solve(wg::MoHostExec(), m, smax, steps + (size_t)b * smax, n_steps[b], init_feet + 6 * (size_t)b,
                                 com0 + 3 * (size_t)b, W.data(), L, nullptr);
+    status[b] = rc;
+    if (rc != WG_OK) continue;
+    for (int e = 0; e < L.words; e++) blk[e] = wg::mo_image_word(W.data(), L, e);
+  }
+  return WG_OK;
+}
+
+// the re-plan from kept factors (mo_resolve, mo_resolve_long): gait b's step count is its factor block's
+int resolve_host(bool lng, const wg_morisawa_model_t *models, bool per_gait, int B, int smax, const void *factors, int n_factors,
+                 const int *factor_of, const wg_rel_step_t *steps, const double *init_feet, const double *com0, void *blocks, int *status) {
+  if (!models || B < 0 || !smax_ok(smax, lng) || !factors || n_factors < 1 || !steps || !init_feet || !com0 || !blocks || !status)
+    return WG_ERR_BAD_ARG;
+  const wg::MoLayout L = layout_of(smax, lng);
+  std::vector<double> W((size_t)L.work_words);
+  for (int b = 0; b < B; b++) {
+    const wg_morisawa_model_t &m = models[per_gait ? b : 0];
+    const int f = factor_of ? factor_of[b] : 0;
+    if (f < 0 || f >= n_factors) { status[b] = WG_MORISAWA_BAD_INPUT; continue; }
+    const double *fac = static_cast<const double *>(factors) + (size_t)f * L.words;
+    double *blk = static_cast<double *>(blocks) + (size_t)b * L.words;
+    if (lng) {
+      status[b] = wg::mo_resolve_long(wg::MoHostExec(), m, smax, fac, steps + (size_t)b * smax, init_feet + 6 * (size_t)b,
+                                      com0 + 3 * (size_t)b, W.data(), L, blk);
+      continue;
+    }
+    const int rc = wg::mo_resolve(wg::MoHostExec(), m, smax, fac, steps + (size_t)b * smax, init_feet + 6 * (size_t)b,
+                                  com0 + 3 * (size_t)b, W.data(), L);
     status[b] = rc;
     if (rc != WG_OK) continue;
     for (int e = 0; e < L.words; e++) blk[e] = wg::mo_image_word(W.data(), L, e);
@@ -148,6 +175,17 @@ int wg_morisawa_solve_fleet(const wg_morisawa_model_t *models, int B, int smax, 
   return solve_host(false, models, true, B, smax, steps, n_steps, init_feet, com0, blocks, status);
 }
 
+int wg_morisawa_resolve(const wg_morisawa_model_t *model, int B, int smax, const void *factors, int n_factors, const int *factor_of,
+                        const wg_rel_step_t *steps, const double *init_feet, const double *com0, void *blocks, int *status) {
+  return resolve_host(false, model, false, B, smax, factors, n_factors, factor_of, steps, init_feet, com0, blocks, status);
+}
+
+int wg_morisawa_resolve_fleet(const wg_morisawa_model_t *models, int B, int smax, const void *factors, int n_factors,
+                              const int *factor_of, const wg_rel_step_t *steps, const double *init_feet, const double *com0,
+                              void *blocks, int *status) {
+  return resolve_host(false, models, true, B, smax, factors, n_factors, factor_of, steps, init_feet, com0, blocks, status);
+}
+
 int wg_morisawa_sample(int B, int smax, const void *blocks, const int *status, double t_start, double T, int lcap, double *zmp_x_tm,
                        double *zmp_y_tm, double *com_tm, double *left_tm, int *left_type_tm, double *right_tm, int *right_type_tm,
                        int *length) {
@@ -186,6 +224,18 @@ int wg_morisawa_long_solve(const wg_morisawa_model_t *model, int B, int smax, co
 int wg_morisawa_long_solve_fleet(const wg_morisawa_model_t *models, int B, int smax, const wg_rel_step_t *steps, const int *n_steps,
                                  const double *init_feet, const double *com0, void *blocks, int *status) {
   return solve_host(true, models, true, B, smax, steps, n_steps, init_feet, com0, blocks, status);
+}
+
+int wg_morisawa_long_resolve(const wg_morisawa_model_t *model, int B, int smax, const void *factors, int n_factors,
+                             const int *factor_of, const wg_rel_step_t *steps, const double *init_feet, const double *com0,
+                             void *blocks, int *status) {
+  return resolve_host(true, model, false, B, smax, factors, n_factors, factor_of, steps, init_feet, com0, blocks, status);
+}
+
+int wg_morisawa_long_resolve_fleet(const wg_morisawa_model_t *models, int B, int smax, const void *factors, int n_factors,
+                                   const int *factor_of, const wg_rel_step_t *steps, const double *init_feet, const double *com0,
+                                   void *blocks, int *status) {
+  return resolve_host(true, models, true, B, smax, factors, n_factors, factor_of, steps, init_feet, com0, blocks, status);
 }
 
 int wg_morisawa_long_sample(int B, int smax, const void *blocks, const int *status, double t_start, double T, int lcap, double *zmp_x_tm,

@@ -19,6 +19,10 @@
 // for one ds_read_b64 per step); the next conflict-free pitch, 22, costs 12 672 B at smax = 64 and with them the second gait of a
 // CU, so the block's pitch is the work area's too.
 //
+// wg_morisawa_resolve_kernel<FLEET>, wg_morisawa_resolve_long_kernel<FLEET> (wg_morisawa[_long]_resolve_*): a new plan on a solved
+// block's timing, both right-hand sides through the block's kept factor (mo_resolve, mo_resolve_long) in the work areas of the two
+// solves: no Z, no pivot search, no elimination of Z.
+//
 // wg_morisawa_sample_kernel<LONG>: lanes = gaits; LONG reads blocks of the long layout and asks for their header tag.  The outputs are time-major with the gait index fastest, so consecutive lanes store
 // consecutive words (a lane per sample would scatter every store over B x 8 bytes); the price is that each lane gathers its own
 // gait's coefficients, which stay in cache across the kMoSampleChunk consecutive samples a lane makes.  The kernel is bound by its
@@ -71,6 +75,52 @@ __global__ __launch_bounds__(64) void wg_morisawa_solve_long_kernel(const wg_mor
   const wg_morisawa_model_t m = FLEET ? models[b] : model;
   const int rc = mo_solve_long(MoWaveExec(), m, smax, steps + (size_t)b * smax, n_steps[b], init_feet + 6 * (size_t)b,
                                com0 + 3 * (size_t)b, wg_mo_lds, L, blocks + (size_t)b * L.words, nullptr);
+  if (threadIdx.x == 0) status[b] = rc;
+}
+
+// The re-plan (wg_morisawa_resolve_*): a wave per gait around mo_resolve, in mo_solve's work area.  The gait's factor block is
+// read over consecutive words, its rows into the padded pitch; in the substitution lane i owns row i as in mo_lu, so a column
+// access stays on distinct banks.  factor_of (may be null: block 0) is checked here, everything else by mo_replan_ok; a refused
+// gait writes its status and nothing else.
+template <bool FLEET>
+__global__ __launch_bounds__(64) void wg_morisawa_resolve_kernel(const wg_morisawa_model_t model, const wg_morisawa_model_t *models, int B,
+                                                                 int smax, const double *factors, int n_factors, const int *factor_of,
+                                                                 const wg_rel_step_t *steps, const double *init_feet, const double *com0,
+                                                                 double *blocks, int *status) {
+  extern __shared__ double wg_mo_lds[];
+  const int b = blockIdx.x;
+  if (b >= B) return;
+  const MoLayout L = mo_layout(smax);
+  const wg_morisawa_model_t m = FLEET ? models[b] : model;
+  const int f = factor_of ? factor_of[b] : 0;
+  int rc = WG_MORISAWA_BAD_INPUT;
+  if (f >= 0 && f < n_factors)
+    rc = mo_resolve(MoWaveExec(), m, smax, factors + (size_t)f * L.words, steps + (size_t)b * smax, init_feet + 6 * (size_t)b,
+                    com0 + 3 * (size_t)b, wg_mo_lds, L);
+  if (threadIdx.x == 0) status[b] = rc;
+  if (rc != WG_OK) return;
+  double *blk = blocks + (size_t)b * L.words;
+  for (int e = threadIdx.x; e < L.words; e += 64) blk[e] = mo_image_word(wg_mo_lds, L, e);
+}
+
+// Its long twin around mo_resolve_long: the band in LDS at pitch 16, the feet's polynomials from the lanes to the block, the work
+// area mo_work_long's; a lane per position and side in the forward pass, per row of the window in the backward pass.
+template <bool FLEET>
+__global__ __launch_bounds__(64) void wg_morisawa_resolve_long_kernel(const wg_morisawa_model_t model, const wg_morisawa_model_t *models,
+                                                                      int B, int smax, const double *factors, int n_factors,
+                                                                      const int *factor_of, const wg_rel_step_t *steps,
+                                                                      const double *init_feet, const double *com0, double *blocks,
+                                                                      int *status) {
+  extern __shared__ double wg_mo_lds[];
+  const int b = blockIdx.x;
+  if (b >= B) return;
+  const MoLayout L = mo_layout_long(smax);
+  const wg_morisawa_model_t m = FLEET ? models[b] : model;
+  const int f = factor_of ? factor_of[b] : 0;
+  int rc = WG_MORISAWA_BAD_INPUT;
+  if (f >= 0 && f < n_factors)
+    rc = mo_resolve_long(MoWaveExec(), m, smax, factors + (size_t)f * L.words, steps + (size_t)b * smax, init_feet + 6 * (size_t)b,
+                         com0 + 3 * (size_t)b, wg_mo_lds, L, blocks + (size_t)b * L.words);
   if (threadIdx.x == 0) status[b] = rc;
 }
 

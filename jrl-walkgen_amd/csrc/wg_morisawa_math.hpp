@@ -31,7 +31,8 @@
 // Two forms of the solve: mo_solve / mo_lu, dense, a row of Z per lane, up to WG_MORISAWA_MAX_STEPS steps (n <= 64), and
 // mo_solve_long / mo_band_lu, Z as a row band of 16 words, a lane per element of the elimination's live window, up to
 // WG_MORISAWA_LONG_MAX_STEPS steps (n <= 264).  The band takes the dense form's pivots and gives its values; mo_sample reads the
-// blocks of both through their layouts.
+// blocks of both through their layouts.  mo_resolve / mo_resolve_long (at the end of the file) re-plan a walk from a solved block's
+// kept factor: the solves' bytes without building or eliminating Z.
 //
 // Quirks of the reference kept on purpose, each marked where it is reproduced: g is 9.86 (:1106), the ZMP twin's
 // sTc = fabs(9.86 / (z_com - z_zmp)) (AnalyticalZMPCOGTrajectory.cpp:401), and the right-support branch clears the LEFT foot's
@@ -973,6 +974,271 @@ WG_MO_INLINE int mo_count(const double *clock, int lcap, double total) {
     else hi = mid;
   }
   return lo;
+}
+
+// ---- the re-plan: a new walk on a solved block's timing, from its kept factor ----------------------------------------------------
+// Z depends on the interval times, the CoM height and the step count alone (mo_z_fill), so a block solved for them -- the FACTOR
+// BLOCK -- serves every plan (steps, initial feet, start CoM x and y) on that timing: mo_resolve / mo_resolve_long make the block
+// that mo_solve / mo_solve_long would make for the plan, byte for byte, without building or eliminating Z (the reference's
+// m_NeedToReset: ComputePolynomialWeights2 :263-357 factors once, ResetTheResolutionOfThePolynomial forgets the factor only when
+// the times change).  What the timing fixes is copied from the factor block -- header, dT, omega, tref, pivots, factor --, what
+// the plan decides runs through the solves' own helpers, and both right-hand sides go through the stored factor with the
+// products and differences they meet inside mo_lu / mo_band_lu, in the same order: k ascending, a product and then a difference.
+WG_MO_INLINE bool mo_same_bits(double a, double b) {
+  long long x, y;
+  __builtin_memcpy(&x, &a, sizeof x);
+  __builtin_memcpy(&y, &b, sizeof y);
+  return x == y;
+}
+// May gait (m, steps, feet6, com3) be re-planned from the block fac of this family and smax?  fac is a solved block of the family
+// (a short block carries no tag, a long block the tag), of this smax; the model's times give the block's dT bit for bit, the
+// height is the block's bit for bit, and mo_solve would not refuse the plan at the block's step count.
+WG_MO_HD inline bool mo_replan_ok(const wg_morisawa_model_t &m, int smax, bool lng, const double *fac, const MoLayout &L,
+                                  const wg_rel_step_t *steps, const double *feet6, const double *com3) {
+  const int *hdr = reinterpret_cast<const int *>(fac);
+  if (!mo_block_ok(fac, smax) || hdr[kMoTagInt] != (lng ? 1 : 0)) return false;
+  const int S = hdr[0], I = hdr[1];
+  if (!mo_inputs_ok(m, smax, steps, S, feet6, com3)) return false;
+  if (!mo_same_bits(com3[2], fac[2])) return false;
+  for (int j = 0; j < I; j++)
+    if (!mo_same_bits(mo_dT(m, j, I), fac[L.o_dT + j])) return false;
+  return true;
+}
+// The pivots index the right-hand sides, so a block is a factor block only with each of them among its column's rows: k <= piv[k]
+// < n, and within the band's reach (n for the dense factor, kMoKl for the band)
+WG_MO_INLINE bool mo_piv_ok(const int *piv, int n, int reach) {
+  bool ok = true;
+  for (int k = 0; k < n; k++) ok = ok && piv[k] >= k && piv[k] < n && piv[k] - k <= reach;
+  return ok;
+}
+
+// The phases of mo_solve between the feet chain and the elimination, on the work area W laid out by Lw (mo_layout's own layout,
+// or mo_work_long's): the ZMP profile (:422-476), Building3rdOrderPolynomial for the interior intervals, w of x and y into rows 0
+// and 1 of rhs and again into rows 2 and 3, where the substitution turns them into y.  dT, omega and the support feet are in W.
+template <class X>
+WG_MO_HD inline void mo_plan_w(const X x, int S, const double *com3, double *W, const MoLayout &Lw) {
+  const int l0 = x.lane(), NL = x.lanes();
+  const int I = 2 * S + 1, n = 2 * I + 6;
+  const double *dT = W + Lw.o_dT, *om = W + Lw.o_om, *sup = W + Lw.o_sup;
+  double *zpx = W + Lw.o_zpx, *zpy = W + Lw.o_zpy, *rhs = W + Lw.o_rhs;
+  const double finx = 0.5 * (sup[3 * (S - 2)] + sup[3 * (S - 1)]), finy = 0.5 * (sup[3 * (S - 2) + 1] + sup[3 * (S - 1) + 1]);
+  for (int j = l0; j < I; j += NL) {
+    zpx[j] = j == 0 ? com3[0] : (j >= 2 * S - 1 ? finx : sup[3 * ((j - 1) / 2)]);
+    zpy[j] = j == 0 ? com3[1] : (j >= 2 * S - 1 ? finy : sup[3 * ((j - 1) / 2) + 1]);
+  }
+  x.sync();
+  for (int e = l0; e < 2 * (I - 2); e += NL) {
+    const int ax = e / (I - 2), j = 1 + (e - ax * (I - 2));
+    const double *zp = ax ? zpy : zpx;
+    double *Zc = W + (ax ? Lw.o_zy : Lw.o_zx) + 5 * j, *Cc = W + (ax ? Lw.o_cy : Lw.o_cx) + 5 * j;
+    const double lTj = dT[j], Omegac = om[j];
+    Zc[0] = zp[j - 1];
+    Zc[1] = 0;
+    Zc[2] = (zp[j] - zp[j - 1]) * 3.0 / (lTj * lTj);
+    Zc[3] = -2.0 * Zc[2] / (3.0 * lTj);
+    Cc[3] = Zc[3];
+    Cc[2] = Zc[2];
+    Cc[1] = Zc[1] + Cc[3] * 6 / (Omegac * Omegac);
+    Cc[0] = Zc[0] + Cc[2] * 2 / (Omegac * Omegac);
+  }
+  x.sync();
+  for (int e = l0; e < 2 * n; e += NL) {
+    const int ax = e / n, q = e - ax * n;
+    const double v = mo_w_entry(q, I, dT, W + (ax ? Lw.o_cy : Lw.o_cx), ax ? zpy : zpx, ax ? com3[1] : com3[0], 0.0, ax ? finy : finx);
+    rhs[ax * Lw.nmax + q] = v;
+    rhs[(2 + ax) * Lw.nmax + q] = v;
+  }
+  x.sync();
+}
+
+// TransfertTheCoefficientsToTrajectories (:1166-1233) from y in rows 2 and 3 of rhs, as mo_solve has it behind its elimination
+template <class X>
+WG_MO_HD inline void mo_transfer(const X x, int S, double h, double *W, const MoLayout &Lw) {
+  const int l0 = x.lane(), NL = x.lanes();
+  const int I = 2 * S + 1;
+  const double *om = W + Lw.o_om, *rhs = W + Lw.o_rhs;
+  for (int e = l0; e < 2 * I; e += NL) {
+    const int ax = e / I, j = e - ax * I;
+    const double *y = rhs + (2 + ax) * Lw.nmax;
+    const int at = j < I - 1 ? 3 + 2 * j : 2 * I + 4;
+    W[(ax ? Lw.o_vy : Lw.o_vx) + j] = y[at];
+    W[(ax ? Lw.o_wy : Lw.o_wx) + j] = y[at + 1];
+  }
+  for (int e = l0; e < 4; e += NL) {
+    const int ax = e >> 1, last = e & 1, j = last ? I - 1 : 0;
+    const double *y = rhs + (2 + ax) * Lw.nmax + (last ? 2 * I + 1 : 0);
+    const double *zp = W + (ax ? Lw.o_zpy : Lw.o_zpx);
+    double *Cc = W + (ax ? Lw.o_cy : Lw.o_cx) + 5 * j, *Zc = W + (ax ? Lw.o_zy : Lw.o_zx) + 5 * j;
+    for (int k = 2; k <= 4; k++) Cc[k] = y[k - 2];
+    Cc[1] = Cc[3] * 6.0 / (om[j] * om[j]);
+    Cc[0] = zp[j] + Cc[2] * 2.0 / (om[j] * om[j]);
+    const double sTc = mo_abs(kMoG / (h - 0.0));               // AnalyticalZMPCOGTrajectory.cpp:401
+    Zc[3] = Cc[3];
+    Zc[4] = Cc[4];
+    for (unsigned int i = 0; i < 3; ++i) Zc[i] = Cc[i] - ((double)(i + 1.0) * (double)(i + 2.0)) * (Cc[i + 2] / sTc);
+  }
+  x.sync();
+}
+
+// Both right-hand sides through mo_lu's stored factor (P Z = L U, the multipliers swapped along with their rows as dgetrf leaves
+// them): piv applied to b for k ascending, a lane per side; the unit-lower solve column by column, k ascending, lanes over the
+// rows i > k, each with its row's owner in mo_lu; then U y = b as mo_lu's second loop.  An entry of b travels with its row, so
+// at step k it meets the multiplier and the b_k it met inside mo_lu.
+template <class X>
+WG_MO_HD inline void mo_lu_resolve(const X x, int n, const double *a, int pitch, const int *piv, double *b0, double *b1) {
+  const int l0 = x.lane(), S = x.lanes();
+  for (int s = l0; s < 2; s += S) {
+    double *b = s ? b1 : b0;
+    for (int k = 0; k < n; k++) {
+      const int p = piv[k];
+      const double t = b[k]; b[k] = b[p]; b[p] = t;
+    }
+  }
+  x.sync();
+  for (int k = 0; k < n; k++) {
+    const double bk0 = b0[k], bk1 = b1[k];
+    for (int i = k + 1 + ((l0 - (k + 1) % S + S) % S); i < n; i += S) {
+      const double mlt = a[i * pitch + k];
+      const double p0 = mlt * bk0, p1 = mlt * bk1;
+      b0[i] = b0[i] - p0;
+      b1[i] = b1[i] - p1;
+    }
+    x.sync();
+  }
+  for (int c = n - 1; c >= 0; c--) {
+    const double ucc = a[c * pitch + c];
+    const double y0 = b0[c] / ucc, y1 = b1[c] / ucc;
+    x.sync();                                                  // every lane has read b[c] before its owner overwrites it
+    if (l0 == c % S) { b0[c] = y0; b1[c] = y1; }
+    for (int i = l0; i < c; i += S) {
+      const double u = a[i * pitch + c];
+      const double p0 = u * y0, p1 = u * y1;
+      b0[i] = b0[i] - p0;
+      b1[i] = b1[i] - p1;
+    }
+    x.sync();
+  }
+}
+
+// The same through mo_band_lu's factor, the dgbtrs procedure of include/wg_mpc.h: per k the swap of b_k and b_piv[k], a lane per
+// side, then the multipliers of positions k + 1 .. k + 5 times b_k off those entries, a lane per position and side; then U y = b
+// over rows c - 9 .. c - 1 as mo_band_lu's second loop.
+template <class X>
+WG_MO_HD inline void mo_band_resolve(const X x, int n, const double *a, const int *piv, double *b0, double *b1) {
+  const int l0 = x.lane(), NL = x.lanes();
+  for (int k = 0; k < n; k++) {
+    const int ilast = k + kMoKl < n - 1 ? k + kMoKl : n - 1, p = piv[k];
+    if (p != k)
+      for (int s = l0; s < 2; s += NL) {
+        double *b = s ? b1 : b0;
+        const double t = b[k]; b[k] = b[p]; b[p] = t;
+      }
+    x.sync();
+    for (int e = l0; e < 2 * kMoKl; e += NL) {
+      const int s = e / kMoKl, i = k + 1 + (e - s * kMoKl);
+      if (i > ilast) continue;
+      double *b = s ? b1 : b0;
+      const double prod = a[mo_band_at(i, k)] * b[k];
+      b[i] = b[i] - prod;
+    }
+    x.sync();
+  }
+  for (int c = n - 1; c >= 0; c--) {
+    const double ucc = a[mo_band_at(c, c)];
+    const double y0 = b0[c] / ucc, y1 = b1[c] / ucc;
+    x.sync();                                                  // every lane has read b[c] before lane 0 overwrites it
+    if (l0 == 0) { b0[c] = y0; b1[c] = y1; }
+    for (int e = l0; e < kMoKuu; e += NL) {
+      const int i = c - 1 - e;
+      if (i < 0) continue;
+      const double u = a[mo_band_at(i, c)];
+      const double p0 = u * y0, p1 = u * y1;
+      b0[i] = b0[i] - p0;
+      b1[i] = b1[i] - p1;
+    }
+    x.sync();
+  }
+}
+
+// ---- the re-plan of one gait from the factor block fac into the work area W (mo_layout's work_words doubles) --------------------
+// WG_OK, and the caller copies the image out (mo_image_word) as behind mo_solve; WG_MORISAWA_BAD_INPUT with W in an unspecified
+// state (the pivots are looked at where they have been copied to).  The factor's rows go from the block's pitch nmax to the work area's nmax + 1 over consecutive words of the block.  fac is read
+// only, and not through W: it must not overlap the block the caller writes.
+template <class X>
+WG_MO_HD inline int mo_resolve(const X x, const wg_morisawa_model_t &m, int smax, const double *fac, const wg_rel_step_t *steps,
+                               const double *feet6, const double *com3, double *W, const MoLayout &L) {
+  const int l0 = x.lane(), NL = x.lanes();
+  if (!mo_replan_ok(m, smax, false, fac, L, steps, feet6, com3)) return WG_MORISAWA_BAD_INPUT;
+  const int S = reinterpret_cast<const int *>(fac)[0], I = 2 * S + 1, n = 2 * I + 6, P = L.nmax + 1;
+
+  for (int e = l0; e < L.work_words; e += NL) W[e] = 0.0;
+  x.sync();
+  // ---- what the timing fixes: header, dT, omega, tref; pivots and factor; lane 0: the feet chain ----
+  for (int e = l0; e < L.o_zx; e += NL) W[e] = fac[e];
+  for (int e = L.o_piv + l0; e < L.o_lu + L.nmax * L.nmax; e += NL) {
+    const double v = fac[e];
+    if (e < L.o_lu) { W[e] = v; continue; }
+    const int q = e - L.o_lu, r = q / L.nmax;
+    W[L.o_lu + r * P + (q - r * L.nmax)] = v;
+  }
+  if (l0 == 0) mo_feet_chain(m, steps, S, feet6, W, L);
+  x.sync();
+  if (!mo_piv_ok(reinterpret_cast<const int *>(W + L.o_piv), n, n)) return WG_MORISAWA_BAD_INPUT;
+  // ---- what the plan decides: the feet's polynomials, the ZMP profile, the interior cubics, w ----
+  const double *dT = W + L.o_dT;
+  for (int e = l0; e < I * 12; e += NL) {
+    const int j = e / 12, f = (e - 12 * j) / 6, ax = e - 12 * j - 6 * f;
+    const double *sg = W + L.o_seg + 24 * j + 12 * f;
+    mo_foot_axis(ax, dT[j], sg[6 + ax], sg[ax], 0.0, W + (f ? L.o_right : L.o_left) + 36 * j + 6 * ax);
+  }
+  mo_plan_w(x, S, com3, W, L);
+  double *rhs = W + L.o_rhs;
+  mo_lu_resolve(x, n, W + L.o_lu, P, reinterpret_cast<const int *>(W + L.o_piv), rhs + 2 * L.nmax, rhs + 3 * L.nmax);
+  mo_transfer(x, S, com3[2], W, L);
+  return WG_OK;
+}
+
+// ---- the long re-plan: work area W (mo_layout_long's work_words doubles), block blk -----------------------------------------------
+// mo_solve_long's order turned round, since nothing can refuse behind the first test: the feet first -- the chain's records in
+// the words the band will take, each polynomial from its lane to the block --, then the band from the factor block over those
+// words, w, the substitution, and the image to the block as mo_solve_long writes it.
+template <class X>
+WG_MO_HD inline int mo_resolve_long(const X x, const wg_morisawa_model_t &m, int smax, const double *fac, const wg_rel_step_t *steps,
+                                    const double *feet6, const double *com3, double *W, const MoLayout &L, double *blk) {
+  const int l0 = x.lane(), NL = x.lanes();
+  if (!mo_replan_ok(m, smax, true, fac, L, steps, feet6, com3)) return WG_MORISAWA_BAD_INPUT;
+  const MoLayout Lw = mo_work_long(L);
+  const int S = reinterpret_cast<const int *>(fac)[0], I = 2 * S + 1, n = 2 * I + 6;
+
+  for (int e = l0; e < L.work_words; e += NL) W[e] = 0.0;
+  x.sync();
+  for (int e = l0; e < L.o_zx; e += NL) W[e] = fac[e];         // header, dT, omega, tref: the long layout's are the work area's
+  for (int e = L.o_piv + l0; e < L.o_lu; e += NL) W[e - 72 * L.imax] = fac[e];
+  if (l0 == 0) mo_feet_chain(m, steps, S, feet6, W, Lw);
+  x.sync();
+  if (!mo_piv_ok(reinterpret_cast<const int *>(W + Lw.o_piv), n, kMoKl)) return WG_MORISAWA_BAD_INPUT;   // blk is still untouched
+  const double *dT = W + Lw.o_dT;
+  for (int e = l0; e < L.imax * 12; e += NL) {
+    const int j = e / 12, f = (e - 12 * j) / 6, ax = e - 12 * j - 6 * f;
+    double c[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (j < I) {
+      const double *sg = W + Lw.o_seg + 24 * j + 12 * f;
+      mo_foot_axis(ax, dT[j], sg[6 + ax], sg[ax], 0.0, c);
+    }
+    double *out = blk + (f ? L.o_right : L.o_left) + 36 * j + 6 * ax;
+    for (int k = 0; k < 6; k++) out[k] = c[k];
+  }
+  x.sync();
+  // ---- the band, consecutive words of the factor block, over the chain's foot records ----
+  for (int e = L.o_lu + l0; e < L.o_lu + L.nmax * kMoBand; e += NL) W[e - 72 * L.imax] = fac[e];
+  mo_plan_w(x, S, com3, W, Lw);
+  double *rhs = W + Lw.o_rhs;
+  mo_band_resolve(x, n, W + Lw.o_lu, reinterpret_cast<const int *>(W + Lw.o_piv), rhs + 2 * L.nmax, rhs + 3 * L.nmax);
+  mo_transfer(x, S, com3[2], W, Lw);
+  for (int e = l0; e < L.words; e += NL)
+    if (e < L.o_left || e >= L.o_nat) blk[e] = mo_image_word_long(W, L, e);
+  x.sync();
+  return WG_OK;
 }
 
 }  // namespace wg

@@ -9,9 +9,13 @@
 //
 // With --long the walk goes through the long family (wg_morisawa_long_*: Z eliminated as a band) and --steps may be up to 64.
 //
+// With --replan K one gait is solved (wg_morisawa[_long]_solve_dev, B = 1) and K candidate plans -- other steps, the same times and
+// height -- are re-planned from its block's kept factor on the same stream (wg_morisawa[_long]_resolve_dev: no Z, no elimination);
+// the first and the last candidate's blocks are checked against the host's full solves of those plans, byte for byte.
+//
 // Prints a checksum (FNV-1a, 64 bit, over the gaits' checksums of their own rows of CoM, ZMP and feet) and the milliseconds per fleet.
 //
-//   morisawa_fleet [--batch B] [--steps S] [--heights LO:HI] [--long]
+//   morisawa_fleet [--batch B] [--steps S] [--heights LO:HI] [--long] [--replan K]
 #include <chrono>
 #include <cstdlib>
 #include <random>
@@ -22,19 +26,26 @@ using wg_fleet::dev_alloc;
 using wg_fleet::dev_upload;
 
 int main(int argc, char **argv) {
-  int B = 4096, S = 7;
+  int B = 4096, S = 7, replan = 0;
   bool heights = false, lng = false;
   double h_lo = 0.7116911, h_hi = 0.7116911;
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--batch") && i + 1 < argc) B = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--steps") && i + 1 < argc) S = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--long")) lng = true;
+    else if (!strcmp(argv[i], "--replan") && i + 1 < argc) {
+      replan = atoi(argv[++i]);
+      if (replan < 1) { fprintf(stderr, "FAILED: need --replan K with K >= 1\n"); return 1; }
+      B = replan;
+    }
     else if (!strcmp(argv[i], "--heights") && i + 1 < argc) {
       heights = sscanf(argv[++i], "%lf:%lf", &h_lo, &h_hi) == 2;
       if (!heights || !(h_lo > 0.0) || !(h_hi >= h_lo) || !(h_hi < 1e3)) { fprintf(stderr, "FAILED: need --heights LO:HI with 0 < LO <= HI\n"); return 1; }
     }
   }
   const int cap = lng ? WG_MORISAWA_LONG_MAX_STEPS : WG_MORISAWA_MAX_STEPS;
+  if (replan && heights) { fprintf(stderr, "FAILED: --replan shares one factor: the candidates have one height and one model\n"); return 1; }
+  if (replan) B = replan;
   if (B < 1 || S < 2 || S > cap) { fprintf(stderr, "FAILED: need B >= 1, 2 <= steps <= %d%s\n", cap, lng ? "" : " (--long: 64)"); return 1; }
   // the two families have one argument list per call: --long chooses the set
   const auto length_fn = lng ? wg_morisawa_long_length : wg_morisawa_length;
@@ -105,6 +116,41 @@ int main(int argc, char **argv) {
   hipStream_t st;
   CHECK_HIP(hipStreamCreate(&st));
   double sec = 0.0;
+  if (replan) {
+    const auto solve_dev_fn = lng ? wg_morisawa_long_solve_dev : wg_morisawa_solve_dev;
+    const auto resolve_dev_fn = lng ? wg_morisawa_long_resolve_dev : wg_morisawa_resolve_dev;
+    void *d_fac;
+    int *d_fst;
+    CHECK_HIP(hipMalloc(&d_fac, bb));
+    CHECK_HIP(dev_alloc(&d_fst, 1));
+    for (int rep = 0; rep < 2; ++rep) {                        // the second pass is the timed one: factor once, K plans from it
+      CHECK_HIP(hipStreamSynchronize(st));
+      const auto t0 = std::chrono::steady_clock::now();
+      CHECK_WG(solve_dev_fn(&base, 1, S, d_steps, d_ns, d_feet, d_com0, d_fac, d_fst, st));
+      CHECK_WG(resolve_dev_fn(&base, B, S, d_fac, 1, nullptr, d_steps, d_feet, d_com0, d_blocks, d_status, st));
+      CHECK_HIP(hipStreamSynchronize(st));
+      sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    }
+    std::vector<int> status(B);
+    std::vector<double> blocks(bb / sizeof(double) * B), blk(bb / sizeof(double));
+    CHECK_HIP(hipMemcpy(status.data(), d_status, sizeof(int) * B, hipMemcpyDeviceToHost));
+    CHECK_HIP(hipMemcpy(blocks.data(), d_blocks, bb * B, hipMemcpyDeviceToHost));
+    for (int g = 0; g < B; ++g)
+      if (status[g] != WG_OK) { fprintf(stderr, "FAILED: candidate %d: status %d\n", g, status[g]); return 1; }
+    for (int g : {0, B - 1}) {                                 // the full solve of the candidate's plan on the host: the same bytes
+      int hs = 0;
+      CHECK_WG(solve_fn(&base, 1, S, &steps[(size_t)g * S], &n_steps[g], &feet[(size_t)g * 6], &com0[(size_t)g * 3], blk.data(), &hs));
+      if (hs != WG_OK || memcmp(blk.data(), &blocks[bb / sizeof(double) * g], bb)) {
+        fprintf(stderr, "FAILED: the re-planned block of candidate %d differs from the full solve's\n", g);
+        return 1;
+      }
+    }
+    printf("morisawa_fleet: %d candidate plans%s of %d steps re-planned from one kept factor in %.2f ms = %.0f plans/s (one solve "
+           "included); candidates 0 and %d == full solves by bytes; checksum %016llx\n", B, lng ? " (long family)" : "", S, sec * 1e3, B / sec,
+           B - 1, (unsigned long long)wg_fleet::fnv1a64(blocks.data(), bb * B));
+    wg_shutdown();
+    return 0;
+  }
   for (int rep = 0; rep < 2; ++rep) {                          // the second pass is the timed one
     CHECK_HIP(hipStreamSynchronize(st));
     const auto t0 = std::chrono::steady_clock::now();

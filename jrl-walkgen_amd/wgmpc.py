@@ -1292,3 +1292,54 @@ def morisawa_long_walk_dev(model, B, smax, steps_ptr, n_steps_ptr, init_feet_ptr
                            outs, length_ptr=None, stream=None, T=None, ctx=None):
     _mo_walk_dev(_MOL, model, B, smax, steps_ptr, n_steps_ptr, init_feet_ptr, com0_ptr, blocks_ptr, status_ptr, t_start, lcap, outs,
                  length_ptr, stream, T, ctx)
+
+
+# ---- the re-plan from a block's kept factor (wg_morisawa_resolve*, wg_morisawa_long_resolve*): new steps, feet and start CoM x, y
+# on the timing of a solved block; the bytes of the full solve without building or eliminating Z.  A gait's step count is its
+# factor block's; `factor_of` [B] names each gait's factor block (None: block 0) ----
+def _mo_resolve(fam, model, factors, factor_of, steps, init_feet, com0, smax, blocks):
+    init_feet = np.ascontiguousarray(init_feet, dtype=np.float64); com0 = np.ascontiguousarray(com0, dtype=np.float64)
+    B = init_feet.shape[0]
+    words = _mo_block_bytes(fam, smax) // 8
+    factors = np.ascontiguousarray(factors, dtype=np.float64).reshape(-1, words)
+    fo = None if factor_of is None else np.ascontiguousarray(factor_of, dtype=np.int32)
+    assert init_feet.shape == (B, 6) and com0.shape == (B, 3) and len(steps) == B * smax and (fo is None or fo.shape == (B,))
+    if blocks is None:
+        blocks = np.zeros((B, words))
+    status = np.zeros(B, np.int32)
+    fleet = not isinstance(model, MorisawaModel)
+    fn = getattr(lib(), fam + ("resolve_fleet" if fleet else "resolve"))
+    _check(fn(C.addressof(model), B, int(smax), _hp(factors), factors.shape[0], _hp(fo), C.addressof(steps), _hp(init_feet), _hp(com0),
+              _hp(blocks), _hp(status)))
+    return blocks, status
+
+
+def morisawa_resolve(model, factors, factor_of, steps, init_feet, com0, smax, blocks=None):
+    """Host twin.  model as in morisawa_solve; factors [F, words] solved blocks of this smax; factor_of [B] or None; steps
+    (RelStep * (B*smax)); init_feet [B, 6]; com0 [B, 3] with the factor block's height.  Returns (blocks, status) as morisawa_solve."""
+    return _mo_resolve(_MO, model, factors, factor_of, steps, init_feet, com0, smax, blocks)
+
+
+def morisawa_long_resolve(model, factors, factor_of, steps, init_feet, com0, smax, blocks=None):
+    return _mo_resolve(_MOL, model, factors, factor_of, steps, init_feet, com0, smax, blocks)
+
+
+def _mo_resolve_dev(fam, model, B, smax, factors_ptr, n_factors, factor_of_ptr, steps_ptr, init_feet_ptr, com0_ptr, blocks_ptr, status_ptr,
+                    stream, ctx):
+    fleet = not isinstance(model, MorisawaModel)
+    _call(fam + ("resolve_fleet_dev" if fleet else "resolve_dev"), ctx, model if fleet else C.addressof(model), int(B), int(smax),
+          factors_ptr, int(n_factors), factor_of_ptr, steps_ptr, init_feet_ptr, com0_ptr, blocks_ptr, status_ptr, stream)
+
+
+def morisawa_resolve_dev(model, B, smax, factors_ptr, n_factors, factor_of_ptr, steps_ptr, init_feet_ptr, com0_ptr, blocks_ptr,
+                         status_ptr, stream=None, ctx=None):
+    """every pointer a device pointer (factor_of_ptr may be None); `model` as in morisawa_solve_dev.  `blocks` must not overlap
+    `factors`; morisawa_sample_dev on the same stream samples the new walks"""
+    _mo_resolve_dev(_MO, model, B, smax, factors_ptr, n_factors, factor_of_ptr, steps_ptr, init_feet_ptr, com0_ptr, blocks_ptr, status_ptr,
+                    stream, ctx)
+
+
+def morisawa_long_resolve_dev(model, B, smax, factors_ptr, n_factors, factor_of_ptr, steps_ptr, init_feet_ptr, com0_ptr, blocks_ptr,
+                              status_ptr, stream=None, ctx=None):
+    _mo_resolve_dev(_MOL, model, B, smax, factors_ptr, n_factors, factor_of_ptr, steps_ptr, init_feet_ptr, com0_ptr, blocks_ptr, status_ptr,
+                    stream, ctx)

@@ -8,7 +8,8 @@ output resident, from 2 t_single as the reference's queue), on one stream:
 (a) and (d) must leave the same checksum (ZMP, CoM, lengths, every 64th row of both feet) -- the host's bytes are the kernel's --
 and every variant the same checksum in every repetition.  The variants alternate PR (5) times in one session; min, median, max.
 One JSON line at the end.
-With --long: the long family (wg_morisawa_long_*) at S = 7, 14, 32 and 64 next to the short solve at 7 and 14; see long_probe."""
+With --long: the long family (wg_morisawa_long_*) at S = 7, 14, 32 and 64 next to the short solve at 7 and 14; see long_probe.
+With --resolve [--long]: the re-plan from a kept factor against the full solve of the same plans; see resolve_probe."""
 import concurrent.futures as cf, ctypes as C, importlib, json, os, sys, time, zlib, numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -102,13 +103,71 @@ def long_probe():
     print(json.dumps(result))
 
 
-if "--long" in sys.argv:
+def resolve_probe(lng):
+    """--resolve: B plans of S steps on one model and one CoM height, (a) solved in full (wg_morisawa[_long]_solve_dev) and (b) re-planned
+    from the kept factor of one solved block (wg_morisawa[_long]_resolve_dev, the block made beforehand and not timed), in one process on
+    one stream.  S = 7 and 14 for the short family, 7, 14, 32 and 64 with --long.  A warm-up of each, then PR alternating repetitions:
+    min, median, max.  Both must leave the same checksum (CRC-32 of all blocks) in every repetition: the re-plan's bytes are the
+    solve's.  "faster" is said only where the re-plan's max lies below the solve's min."""
+    fam = "morisawa_long_" if lng else "morisawa_"
+    solve_dev, resolve_dev, block_bytes = (getattr(wg, fam + k) for k in ("solve_dev", "resolve_dev", "block_bytes"))
+    m = wg.morisawa_defaults()
+    result = dict(B=B, reps=REPS, family="long" if lng else "short", sizes={})
+    for S_ in ((7, 14, 32, 64) if lng else (7, 14)):
+        rng = np.random.default_rng(2007 + S_)
+        steps = (wg.RelStep * (B * S_))()
+        for g in range(B):
+            side = 1.0 if g & 1 else -1.0
+            for i in range(S_):
+                ends = i in (0, S_ - 1)
+                steps[g * S_ + i] = wg.RelStep(0.0 if ends else rng.uniform(0.1, 0.25), side * (0.105 if i == 0 else 0.19),
+                                               0.0 if ends else rng.uniform(-5.0, 5.0), 0.0, 0.0, 1, 0)
+                side = -side
+        n_steps = np.full(B, S_, np.int32)
+        feet = np.tile([0.0, 0.09, 0.0, 0.0, -0.09, 0.0], (B, 1))
+        com0 = np.tile([0.0316054587, 0.0, 0.7116911], (B, 1)); com0[:, 0] += rng.uniform(-0.01, 0.01, B)
+        words = block_bytes(S_) // 8
+        d_steps, d_ns, d_feet, d_com0 = raw(steps), dev(n_steps), dev(feet), dev(com0)
+        blocks = torch.zeros(B, words, dtype=torch.float64, device="cuda")
+        factor = torch.zeros(1, words, dtype=torch.float64, device="cuda")
+        status, fstatus = torch.zeros(B, dtype=torch.int32, device="cuda"), torch.zeros(1, dtype=torch.int32, device="cuda")
+        ways = {"solve": lambda: solve_dev(m, B, S_, p(d_steps), p(d_ns), p(d_feet), p(d_com0), p(blocks), p(status), sp),
+                "resolve": lambda: resolve_dev(m, B, S_, p(factor), 1, None, p(d_steps), p(d_feet), p(d_com0), p(blocks), p(status), sp)}
+        solve_dev(m, 1, S_, p(d_steps), p(d_ns), p(d_feet), p(d_com0), p(factor), p(fstatus), sp)       # gait 0's block: the factor
+        for k in ways:                                               # warm-up: code objects, the LDS attribute
+            ways[k]()
+        torch.cuda.synchronize()
+        secs = {k: [] for k in ways}; sums = {k: [] for k in ways}
+        for _ in range(REPS):                                        # alternating: a drift of the machine hits both alike
+            for k in ways:
+                blocks.zero_(); status.fill_(-77); torch.cuda.synchronize()
+                secs[k].append(clock(ways[k]))
+                assert int(status.abs().max()) == 0 and int(fstatus[0]) == 0
+                sums[k].append("%08x" % zlib.crc32(blocks.cpu().numpy().tobytes()))
+        assert len(set(sums["solve"] + sums["resolve"])) == 1, sums
+        row = dict(block_bytes=words * 8, checksum=sums["solve"][0])
+        for k, v in secs.items():
+            ms = np.array(v) * 1e3
+            row[k] = dict(ms_min=float(ms.min()), ms_median=float(np.median(ms)), ms_max=float(ms.max()), ms=[round(float(x), 4) for x in ms])
+            print("%-5s S = %2d %-7s ms per %d gaits: min %.3f  median %.3f  max %.3f, checksum %s in each of %d repetitions: %s"
+                  % (result["family"], S_, k, B, ms.min(), np.median(ms), ms.max(), sums[k][0], REPS, " ".join("%.3f" % x for x in ms)))
+        row["resolve_faster"] = row["resolve"]["ms_max"] < row["solve"]["ms_min"]
+        row["solve_over_resolve_median"] = row["solve"]["ms_median"] / row["resolve"]["ms_median"]
+        print("%-5s S = %2d the re-plan's max %s the solve's min; medians solve / re-plan = %.2f"
+              % (result["family"], S_, "lies below" if row["resolve_faster"] else "does NOT lie below", row["solve_over_resolve_median"]))
+        result["sizes"][S_] = row
+        del blocks
+        torch.cuda.empty_cache()
+    print(json.dumps(result))
+
+
+if "--resolve" in sys.argv or "--long" in sys.argv:
     def clock(fn):
         torch.cuda.synchronize(); t = time.perf_counter()
         fn()
         torch.cuda.synchronize()
         return time.perf_counter() - t
-    long_probe()
+    resolve_probe("--long" in sys.argv) if "--resolve" in sys.argv else long_probe()
     sys.exit(0)
 
 m = wg.morisawa_defaults()
