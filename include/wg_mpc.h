@@ -965,6 +965,90 @@ int wg_foot_constraints_append_fleet_dev(int B, int lcap, int first_sample, int 
                                          const double *left_tm, const int *left_type_tm, const double *right_tm,
                                          const wg_sole_t *soles, int qcap, wg_zmp_polytope_t *queues, double *t_start,
                                          double *t_end, int *count, void *hip_stream);
+
+/* Walk audit: how far a ZMP track stays inside its gait's polytope queue -----------------------------------------------
+ *
+ * The verdict on a walk, on the device: for every control-period sample of every gait the ZMP's margin inside the polytope
+ * the gait's queue holds at that time, reduced to one wg_zmp_audit_t per gait.  The rule for "violated" is the reference's own
+ * check of the previewed instants, ZMPConstrainedQPFastFormulation::ValidationConstraints (ZMPConstrainedQPFastFormulation.cpp
+ * :248-381, called behind `if (0)` at :1403-1414): a constraint row below -1e-8 (:322).  The margin is the geometric one: the
+ * least distance to the polytope's boundary lines, positive inside.
+ * Per sample k < length[b], with t = time[k] and (x, y) the track's sample:
+ *   1. q is the first stored entry with t_start[q] <= t <= t_end[q] (the search of BuildConstraintMatrices, :785-796).  Adjacent
+ *      entries share their boundary instant, so the sample at a support change is audited against the EARLIER polytope.  No such
+ *      entry, or an entry whose nrows is outside 1 .. WG_POLY_MAX_ROWS: the sample is uncovered.  The queue is taken to be ordered
+ *      as the foot-constraints calls write it (t_end non-decreasing, t_start[q] <= t_end[q] <= t_start[q + 1]); the entry found in
+ *      a queue that is not is unspecified.
+ *   2. for the rows j < nrows:  v_j = (A[j][0] * x + A[j][1] * y) + B[j],  d_j = v_j / sqrt(A[j][0] * A[j][0] + A[j][1] * A[j][1]),
+ *      in exactly this order of operations (no contraction; / and sqrt are IEEE on both sides).  A d_j that is not finite counts
+ *      as -inf.
+ *   3. the sample's margin is the least d_j, the first j on a tie.  An uncovered sample, or one with a non-finite coordinate, has
+ *      margin -inf and no row.
+ *   4. the sample is violated when it is uncovered, when it is non-finite, or when some v_j < -1e-8 (the raw row value).
+ * All of a gait's fields below; margin (margin_tm) optionally receives every sample's margin. */
+typedef struct wg_zmp_audit {
+  double margin;      /* min over the gait's audited samples of the sample's margin, metres; +inf when none was audited */
+  int worst_sample;   /* the FIRST sample that attains it; -1 when none was audited */
+  int worst_row;      /* the first row of that sample's polytope that attains it; -1 for a sample without a margin */
+  int n_violated;     /* samples that fail the reference's test */
+  int n_uncovered;    /* samples whose time lies in no stored queue entry */
+  int n_nonfinite;    /* samples with a non-finite coordinate */
+  int status;         /* WG_OK, or WG_ERR_BAD_ARG: a refused gait, every other field as the caller left it */
+} wg_zmp_audit_t;
+#define WG_ZMP_AUDIT_BYTES 32
+#ifdef __cplusplus
+static_assert(sizeof(wg_zmp_audit_t) == WG_ZMP_AUDIT_BYTES, "wg_zmp_audit_t is part of the ABI");
+#else
+_Static_assert(sizeof(wg_zmp_audit_t) == WG_ZMP_AUDIT_BYTES, "wg_zmp_audit_t is part of the ABI");
+#endif
+/* One gait on the host: the bytes of the kernels.  Audits the samples [first_sample, n) of the track px[k * stride], py[k * stride]
+ * (HOST pointers) against the first min(count, qcap) entries of polys / t_start / t_end.  first_sample == 0 starts the audit;
+ * first_sample > 0 folds the samples into *audit as an earlier call left it (the result is that of one call over [0, n), however
+ * the walk is cut).  margin (n doubles, or NULL) receives the margins of the audited samples at their own indices.
+ * Returns WG_ERR_BAD_ARG with nothing written for NULL audit, polys, t_start or t_end, NULL time, px or py with a sample to
+ * audit, first_sample < 0, stride < 1, qcap < 1; and, with audit->status = WG_ERR_BAD_ARG and nothing else written, for a gait
+ * the device calls refuse: n < 0, count < 0, first_sample > n, first_sample > 0 with audit->status != WG_OK.  count == 0 is not
+ * a refusal: every sample is uncovered. */
+int wg_zmp_audit(int first_sample, int n, const double *time, const double *px, const double *py, int stride, int count,
+                 int qcap, const wg_zmp_polytope_t *polys, const double *t_start, const double *t_end, wg_zmp_audit_t *audit,
+                 double *margin);
+/* The same for B gaits on the device.  All pointers are DEVICE pointers; asynchronous on hip_stream.
+ *   length     B      samples of each gait; nothing at or past length[b] is read or written
+ *   time       lcap   ONE array shared by every gait, as for the foot-constraints calls
+ *   px_tm, py_tm, pitch   sample k of gait b at [k * pitch + b]:  pitch = B reads zmp_x_tm / zmp_y_tm (wg_zmpdisc_*,
+ *              wg_morisawa_*);  pitch = 2 B with py_tm = px_tm + B reads the preview's zmp2_tm [L][2][B];  pitch = 6 B with
+ *              py_tm = px_tm + B reads the ground projection of com_tm
+ *   queues, t_start, t_end [B][qcap], count B   what wg_foot_constraints_batch_dev / _append_dev / _fleet_dev wrote; only the
+ *              first min(count[b], qcap) entries exist
+ *   audit      B      the verdicts;  margin_tm  [lcap][B] or NULL: margin_tm[k * B + b] for k < length[b]
+ * Per gait the bytes of wg_zmp_audit(0, length[b], ...).  A gait is refused -- audit[b].status = WG_ERR_BAD_ARG, nothing else
+ * of it written, a neighbour never notices -- for length[b] < 0 (a gait a producer refused), length[b] > lcap, count[b] < 0.
+ * Host-side errors (WG_ERR_BAD_ARG, nothing launched): a NULL input, B < 0, lcap < 1, qcap < 1, pitch < B;  B == 0 is WG_OK.
+ * The time axis is split across blocks (chunks of wg_foot_constraints_chunk() samples); the per-chunk partial results live in
+ * a buffer of the context between the two kernels and are folded in chunk order -- the first sample to attain the least margin
+ * does not depend on the grid -- so launches of one context are ordered like the foot-constraints launches. */
+int wg_zmp_audit_dev(int B, int lcap, const int *length, const double *time, const double *px_tm, const double *py_tm,
+                     long long pitch, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end,
+                     const int *count, wg_zmp_audit_t *audit, double *margin_tm, void *hip_stream);
+/* The same on line, behind wg_foot_constraints_append_dev: audits the samples [done[b], length[b]), folds them into audit[b] and
+ * margin_tm, and sets done[b] = length[b].  done[b] == 0 starts a gait's audit: audit[b] is ignored on input.
+ * CONTRACT: after the call, audit[b] is byte for byte what wg_zmp_audit_dev writes for length[b] samples against the same queue.
+ * This holds after every call, however the walk is cut (the least margin, the first sample and row to attain it and the counts
+ * fold exactly), and on a queue still growing under wg_foot_constraints_append_dev: its provisional last t_end is
+ * time[length[b] - 1], so every sample below length[b] has its final entry.
+ *   length[b] == done[b]    the gait sits the call out: none of its bytes is touched.
+ *   refused, with audit[b].status = WG_ERR_BAD_ARG, done[b] unchanged and nothing else written:  length[b] < 0 (a gait
+ *       wg_zmpdisc_* refused);  length[b] > lcap;  count[b] < 0;  done[b] < 0;  done[b] > length[b];  done[b] < first_sample;
+ *       done[b] > 0 with audit[b].status != WG_OK -- errors are sticky through the status.  A neighbour never notices.
+ *   first_sample   a HOST-side lower bound on every done[b] (0 is always valid): the chunks of the time axis that lie wholly
+ *       below it are not launched, so that a long walk does not pay a grid over its past.
+ * Host-side errors as above, and NULL done or first_sample < 0.  Launches are ordered per context exactly like the batch
+ * call's (the same buffer of the context). */
+int wg_zmp_audit_append_dev(int B, int lcap, int first_sample, int *done, const int *length, const double *time,
+                            const double *px_tm, const double *py_tm, long long pitch, int qcap,
+                            const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count,
+                            wg_zmp_audit_t *audit, double *margin_tm, void *hip_stream);
+
 /* The queue walk of one tick, BuildConstraintMatrices (ZMPConstrainedQPFastFormulation.cpp:785-796, 822-835), for B gaits:
  * the first entry q with t_start[q] <= t0 <= t_end[q] is the start; for i = 0 .. N-1, q advances by one when
  * t0 + i T > t_end[q] (the reference's StartingTime + i*T); polys[b][i] is a copy of entry q.  N and T are the configured
@@ -1581,6 +1665,13 @@ int wg_dimitrov_follow_fleet_dev_ctx(wg_ctx_t *ctx, int B, const wg_dimitrov_fle
   X(int, wg_foot_constraints_append_fleet_dev, (int B, int lcap, int first_sample, int *done, const int *length, const double *time, const double *left_tm, \
     const int *left_type_tm, const double *right_tm, const wg_sole_t *soles, int qcap, wg_zmp_polytope_t *queues, double *t_start, double *t_end, int *count, \
     void *hip_stream), (B, lcap, first_sample, done, length, time, left_tm, left_type_tm, right_tm, soles, qcap, queues, t_start, t_end, count, hip_stream)) \
+  X(int, wg_zmp_audit_dev, (int B, int lcap, const int *length, const double *time, const double *px_tm, const double *py_tm, long long pitch, int qcap, \
+    const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count, wg_zmp_audit_t *audit, double *margin_tm, \
+    void *hip_stream), (B, lcap, length, time, px_tm, py_tm, pitch, qcap, queues, t_start, t_end, count, audit, margin_tm, hip_stream)) \
+  X(int, wg_zmp_audit_append_dev, (int B, int lcap, int first_sample, int *done, const int *length, const double *time, const double *px_tm, \
+    const double *py_tm, long long pitch, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count, \
+    wg_zmp_audit_t *audit, double *margin_tm, void *hip_stream), (B, lcap, first_sample, done, length, time, px_tm, py_tm, pitch, qcap, queues, t_start, \
+    t_end, count, audit, margin_tm, hip_stream)) \
   X(int, wg_morisawa_solve_dev, (const wg_morisawa_model_t *model, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, const double *init_feet, \
     const double *com0, void *blocks, int *status, void *hip_stream), (model, B, smax, steps, n_steps, init_feet, com0, blocks, status, hip_stream)) \
   X(int, wg_morisawa_solve_fleet_dev, (const wg_morisawa_model_t *models, int B, int smax, const wg_rel_step_t *steps, const int *n_steps, \

@@ -24,6 +24,7 @@
 #include "wg_gramian_device.hpp"
 #include "wg_zmpdisc_device.hpp"
 #include "wg_footcons_device.hpp"
+#include "wg_audit_device.hpp"
 #include "wg_ql_kernels.hpp"
 #include "wg_pldp_kernels.hpp"
 #include "wg_dimitrov_kernels.hpp"
@@ -161,6 +162,10 @@ struct wg_ctx {
   // them).  One launch at a time uses each: claimed and marked like the tick's buffers (fc_order, walk_order)
   DevBuf fc_buf, walk_polys;
   SlotOrder fc_order, walk_order;
+  // the walk audit: one wg_zmp_audit_t per (chunk, gait) between the two kernels of wg_zmp_audit_dev / _append_dev; one launch at
+  // a time uses it, claimed and marked (audit_order)
+  DevBuf audit_buf;
+  SlotOrder audit_order;
   // preview control
   wg::PreviewConst prev;
   double *prev_F = nullptr;            // device copy of the window gains
@@ -179,10 +184,10 @@ struct wg_ctx {
     if (prev_F) (void)hipFree(prev_F);
     tables_dev = nullptr; model_dev = nullptr; pldp_dev = nullptr; dim_dev = nullptr; prev_F = nullptr;
     model_set = false; pldp_N = 0; dim_set = false; prev_set = false;
-    for (DevBuf *b : {&tick_state, &tick_out, &tick_aux, &run_buf, &tick_z, &asm_state, &qp_slot, &pldp_buf, &dim_buf, &fc_buf, &walk_polys, &prev_buf, &in, &out, &gram_buf, &zd_buf, &mo_clock})
+    for (DevBuf *b : {&tick_state, &tick_out, &tick_aux, &run_buf, &tick_z, &asm_state, &qp_slot, &pldp_buf, &dim_buf, &fc_buf, &walk_polys, &prev_buf, &in, &out, &gram_buf, &zd_buf, &mo_clock, &audit_buf})
       b->release();
     for (Lpt *l : {&tick_lpt, &qp_lpt, &dim_lpt}) l->release();
-    for (SlotOrder *o : {&guard_order, &qp_order, &asm_order, &aux_order, &fc_order, &walk_order, &mo_order}) {
+    for (SlotOrder *o : {&guard_order, &qp_order, &asm_order, &aux_order, &fc_order, &walk_order, &mo_order, &audit_order}) {
       if (o->ev) (void)hipEventDestroy(o->ev);
       o->ev = nullptr; o->armed = false; o->stream = nullptr;
     }
@@ -260,7 +265,7 @@ int slot_claim(wg_ctx *ctx, wg_ctx::SlotOrder &o, hipStream_t st, const char *wh
 // the context's own streams) -- not for the device
 int ctx_wait_own(wg_ctx *ctx) {
   std::lock_guard<std::mutex> launch_lk(ctx->launch_mu);
-  for (wg_ctx::SlotOrder *o : {&ctx->guard_order, &ctx->qp_order, &ctx->asm_order, &ctx->aux_order, &ctx->fc_order, &ctx->walk_order, &ctx->mo_order})
+  for (wg_ctx::SlotOrder *o : {&ctx->guard_order, &ctx->qp_order, &ctx->asm_order, &ctx->aux_order, &ctx->fc_order, &ctx->walk_order, &ctx->mo_order, &ctx->audit_order})
     if (o->armed) HIP_TRY(hipEventSynchronize(o->ev));
   if (ctx->host_stream) HIP_TRY(hipStreamSynchronize(ctx->host_stream));
   if (ctx->pin_stream) HIP_TRY(hipStreamSynchronize(ctx->pin_stream));
@@ -1565,6 +1570,35 @@ int footcons_append(wg_ctx *ctx, int B, int lcap, int first_sample, int *done, c
     return WG_OK;
   });
 }
+// What wg_zmp_audit_dev (res = false: first_sample 0, no done) and _append_dev (res = true) share: the checks, the kernels'
+// arguments, the chunks from first_sample's on, the claim of the context's buffer -- the per-chunk partial results live there
+// between the two kernels: one launch at a time uses it -- and the mark behind the launches.
+template <bool kRes>
+int audit_launch(wg_ctx *ctx, int B, int lcap, int first_sample, int *done, const int *length, const double *time, const double *px_tm, const double *py_tm, long long pitch, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count, wg_zmp_audit_t *audit, double *margin_tm, void *hip_stream) {
+  if (int rc = use_ctx(ctx)) return rc;
+  if (B < 0 || lcap < 1 || qcap < 1 || first_sample < 0) return fail(WG_ERR_BAD_ARG, kRes ? "need B >= 0, lcap >= 1, qcap >= 1, first_sample >= 0" : "need B >= 0, lcap >= 1, qcap >= 1");
+  if (B == 0) return WG_OK;
+  if ((kRes && !done) || !length || !time || !px_tm || !py_tm || !queues || !t_start || !t_end || !count || !audit)
+    return fail(WG_ERR_BAD_ARG, "need non-null %slengths, times, tracks, queues, intervals, counts and audits", kRes ? "done, " : "");
+  if (pitch < (long long)B) return fail(WG_ERR_BAD_ARG, "pitch = %lld: the samples of B = %d gaits lie at least B apart", pitch, B);
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  const int chunk0 = first_sample / wg::kFcChunk, chunks = (lcap + wg::kFcChunk - 1) / wg::kFcChunk - chunk0;
+  if (chunks > 65535) return fail(WG_ERR_TOO_LARGE, "lcap = %d, first_sample = %d: more than 65535 chunks of %d samples", lcap, first_sample, wg::kFcChunk);
+  const wg::AuIn I{B, lcap, length, time, px_tm, py_tm, pitch, qcap, queues, t_start, t_end, count};
+  const wg::AuRes Z{done, first_sample, chunk0};
+  std::lock_guard<std::mutex> launch_lk(ctx->launch_mu);
+  if (int rc = slot_claim(ctx, ctx->audit_order, st, "walk-audit")) return rc;
+  const size_t n_part = (size_t)(chunks > 0 ? chunks : 0) * (size_t)B;
+  if (int rc = ctx->audit_buf.reserve((n_part ? n_part : 1) * sizeof(wg_zmp_audit_t))) return rc;
+  wg_zmp_audit_t *part = static_cast<wg_zmp_audit_t *>(ctx->audit_buf.p);
+  // chunks that lie wholly below first_sample hold no new sample of any gait: not launched (a gait whose done[b] is below it
+  // is refused on the device).  first_sample >= lcap: every gait sits out or is refused, the combine kernel alone says so.
+  if (chunks > 0)
+    hipLaunchKernelGGL((wg::wg_zmp_audit_kernel<kRes>), dim3((B + 63) / 64, chunks), dim3(64), 0, st, I, Z, audit, part, margin_tm);
+  hipLaunchKernelGGL((wg::wg_zmp_audit_combine_kernel<kRes>), dim3((B + 255) / 256), dim3(256), 0, st, I, Z, part, audit);
+  HIP_TRY(hipGetLastError());
+  return slot_mark(ctx->audit_order, st);
+}
 }  // namespace
 
 extern "C" {
@@ -1587,6 +1621,14 @@ int wg_foot_constraints_fleet_dev_ctx(wg_ctx_t *ctx, int B, int lcap, const int 
 int wg_foot_constraints_append_fleet_dev_ctx(wg_ctx_t *ctx, int B, int lcap, int first_sample, int *done, const int *length, const double *time, const double *left_tm, const int *left_type_tm, const double *right_tm, const wg_sole_t *soles, int qcap, wg_zmp_polytope_t *queues, double *t_start, double *t_end, int *count, void *hip_stream) {
   if (!soles) return fail(WG_ERR_BAD_ARG, "null soles");
   return footcons_append(ctx, B, lcap, first_sample, done, length, time, left_tm, left_type_tm, right_tm, wg_sole_t{}, wg::FcSoles<true>{soles}, qcap, queues, t_start, t_end, count, hip_stream);
+}
+
+int wg_zmp_audit_dev_ctx(wg_ctx_t *ctx, int B, int lcap, const int *length, const double *time, const double *px_tm, const double *py_tm, long long pitch, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count, wg_zmp_audit_t *audit, double *margin_tm, void *hip_stream) {
+  return audit_launch<false>(ctx, B, lcap, 0, nullptr, length, time, px_tm, py_tm, pitch, qcap, queues, t_start, t_end, count, audit, margin_tm, hip_stream);
+}
+
+int wg_zmp_audit_append_dev_ctx(wg_ctx_t *ctx, int B, int lcap, int first_sample, int *done, const int *length, const double *time, const double *px_tm, const double *py_tm, long long pitch, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count, wg_zmp_audit_t *audit, double *margin_tm, void *hip_stream) {
+  return audit_launch<true>(ctx, B, lcap, first_sample, done, length, time, px_tm, py_tm, pitch, qcap, queues, t_start, t_end, count, audit, margin_tm, hip_stream);
 }
 
 int wg_dimitrov_select_polys_dev_ctx(wg_ctx_t *ctx, int B, int qcap, const wg_zmp_polytope_t *queues, const double *t_start, const double *t_end, const int *count, double t0, wg_zmp_polytope_t *polys, int *ran_out, void *hip_stream) {

@@ -38,7 +38,12 @@
 // one-model path, each alone: wg_zmpdisc_full_batch_dev with its own model, wg_foot_constraints_batch_dev with its own sole, one
 // walk on a context configured with its own height.  LO = HI = 1 prints the checksum of the run without the option.
 //
-//   dimitrov_fleet [--batch B] [--steps S] [--ticks K] [--solver 0|1|2] [--fleet FILE] [--online K [--follow]] [--ragged]
+// With --online K [--follow] --audit the feeding calls also write the ZMP reference (zmp_x_tm / zmp_y_tm), and behind every
+// wg_foot_constraints_append_dev a wg_zmp_audit_append_dev folds the new samples into one verdict per gait, against the queue as
+// it grows.  At the end the verdicts must be the bytes of one wg_zmp_audit_dev over the finished walks, and gaits 0 and B - 1 those
+// of the host twin wg_zmp_audit; the fleet's least margin, its gait and time, and the violated count are printed.
+//
+//   dimitrov_fleet [--batch B] [--steps S] [--ticks K] [--solver 0|1|2] [--fleet FILE] [--online K [--follow] [--audit]] [--ragged]
 //                  [--plan | --plan-host] [--heights LO:HI | --robots LO:HI]
 //
 // --fleet FILE runs a fleet somebody else drew instead of the built-in one (tests/test_dimitrov_walk_gpu.py compares the
@@ -56,7 +61,7 @@ using wg_fleet::dev_upload;
 
 int main(int argc, char **argv) {
   int B = 4096, S = 8, K = 40, solver = WG_DIMITROV_PLDP, online = 0;
-  bool follow = false, ragged = false, heights = false, robots = false;
+  bool follow = false, ragged = false, heights = false, robots = false, audit = false;
   double h_lo = 0.0, h_hi = 0.0, r_lo = 1.0, r_hi = 1.0;
   int planned = 0;                                            // 1: --plan (steps planned on the device), 2: --plan-host
   const char *fleet = nullptr;
@@ -68,6 +73,7 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[i], "--fleet") && i + 1 < argc) fleet = argv[++i];
     else if (!strcmp(argv[i], "--follow")) follow = true;
     else if (!strcmp(argv[i], "--ragged")) ragged = true;
+    else if (!strcmp(argv[i], "--audit")) audit = true;
     else if (!strcmp(argv[i], "--plan")) planned = 1;
     else if (!strcmp(argv[i], "--plan-host")) planned = 2;
     else if (!strcmp(argv[i], "--heights") && i + 1 < argc) {
@@ -81,6 +87,7 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[i], "--online") && i + 1 < argc) { online = atoi(argv[++i]); if (online < 1 || online > WG_ZMPDISC_MAX_STEPS) { fprintf(stderr, "FAILED: need 1 <= --online K <= %d\n", WG_ZMPDISC_MAX_STEPS); return 1; } }
   }
   if (follow && !online) { fprintf(stderr, "FAILED: --follow needs --online K\n"); return 1; }
+  if (audit && !online) { fprintf(stderr, "FAILED: --audit needs --online K\n"); return 1; }
   if (planned && (ragged || fleet || S < 4)) { fprintf(stderr, "FAILED: --plan needs steps >= 4, no --ragged and no --fleet\n"); return 1; }
   if (robots && (fleet || heights)) { fprintf(stderr, "FAILED: --robots goes with neither --fleet nor --heights (it implies them)\n"); return 1; }
   const bool on_device = planned == 1;
@@ -198,6 +205,15 @@ int main(int argc, char **argv) {
   CHECK_HIP(dev_alloc(&d_te, nq));
   CHECK_HIP(dev_alloc(&d_queues, nq));
   CHECK_HIP(dev_alloc(&d_states, B));
+  // --audit: the ZMP reference of the feeding calls (without it they are not asked for it), the audit's own done array, the verdicts
+  double *d_zx = nullptr, *d_zy = nullptr; int *d_adone = nullptr;
+  wg_fleet::FleetAudit fa;
+  if (audit) {
+    CHECK_HIP(dev_alloc(&d_zx, row));
+    CHECK_HIP(dev_alloc(&d_zy, row));
+    CHECK_HIP(dev_alloc(&d_adone, B));
+    CHECK_HIP(dev_alloc(&fa.d_audit, B));
+  }
   // --heights: a model per gait; the blocks and the status are written by the device in front of every pass
   double *d_h = nullptr; unsigned char *d_blocks = nullptr; int *d_status = nullptr, *d_model_of = nullptr;
   std::vector<double> h_of(B, dm.com_height);
@@ -329,6 +345,9 @@ int main(int argc, char **argv) {
                                                                    d_queues, d_ts, d_te, d_count, st)
                             : wg_foot_constraints_append_dev(B, lcap, first, d_done, d_len, d_time, d_left, d_lty, d_right, sole.sole_w, sole.sole_h,
                                                              sole.constraint_x, sole.constraint_y, qcap, d_queues, d_ts, d_te, d_count, st)) return rc;
+        if (audit)                                             // the new samples against the queue they have just extended
+          if (int rc = wg_zmp_audit_append_dev(B, lcap, first, d_adone, d_len, d_time, d_zx, d_zy, B, qcap, d_queues, d_ts, d_te, d_count,
+                                               fa.d_audit, nullptr, st)) return rc;
         if (follow) {                                          // every gait over the ticks its own queue has made safe
           hipEvent_t e0, e1;
           if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return WG_ERR_HIP;
@@ -366,13 +385,14 @@ int main(int argc, char **argv) {
           if (sel[(size_t)c * B + g]) { any = true; ended[g] = 1; cur[g] = len_ended[g]; }
         if (!any) return WG_OK;
         max_ticks = K;                                         // an ended gait's queue is final: whatever it has left
-        if (int rc = robots ? wg_zmpdisc_end_fleet_dev(&zfl, B, d_sel + (size_t)c * B, lcap, nullptr, nullptr, nullptr, nullptr, d_left, d_lty,
+        if (int rc = robots ? wg_zmpdisc_end_fleet_dev(&zfl, B, d_sel + (size_t)c * B, lcap, d_zx, d_zy, nullptr, nullptr, d_left, d_lty,
                                                        d_right, nullptr, d_walk, d_len, st)
-                            : wg_zmpdisc_end_dev(&zm, B, d_sel + (size_t)c * B, lcap, nullptr, nullptr, nullptr, nullptr, d_left, d_lty, d_right,
+                            : wg_zmpdisc_end_dev(&zm, B, d_sel + (size_t)c * B, lcap, d_zx, d_zy, nullptr, nullptr, d_left, d_lty, d_right,
                                                  nullptr, d_walk, d_len, st)) return rc;
         return grow_and_walk();
       };
       CHECK_HIP(hipMemsetAsync(d_done, 0, sizeof(int) * B, st));
+      if (audit) CHECK_HIP(hipMemsetAsync(d_adone, 0, sizeof(int) * B, st));
       if (follow) {
         CHECK_HIP(hipMemsetAsync(d_clock, 0, sizeof(double) * B, st));
         CHECK_HIP(hipMemsetAsync(d_ticks, 0, sizeof(int) * B, st));
@@ -382,9 +402,9 @@ int main(int argc, char **argv) {
       const auto t0 = std::chrono::steady_clock::now();
       // --plan: the support foot and the arc become the steps the begin call takes
       if (on_device) CHECK_WG(plan_steps(cp.ccap, d_cmds, d_ncmds, S, d_steps, d_ns, st));
-      CHECK_WG(robots ? wg_zmpdisc_begin_fleet_dev(&zfl, B, S, d_steps, on_device ? d_ns : d_two, d_feet, lcap, nullptr, nullptr, nullptr, nullptr,
+      CHECK_WG(robots ? wg_zmpdisc_begin_fleet_dev(&zfl, B, S, d_steps, on_device ? d_ns : d_two, d_feet, lcap, d_zx, d_zy, nullptr, nullptr,
                                                    d_left, d_lty, d_right, nullptr, d_walk, d_len, st)
-                      : wg_zmpdisc_begin_dev(&zm, B, S, d_steps, on_device ? d_ns : d_two, d_feet, lcap, nullptr, nullptr, nullptr, nullptr, d_left,
+                      : wg_zmpdisc_begin_dev(&zm, B, S, d_steps, on_device ? d_ns : d_two, d_feet, lcap, d_zx, d_zy, nullptr, nullptr, d_left,
                                              d_lty, d_right, nullptr, d_walk, d_len, st));
       for (int g = 0; g < B; ++g) cur[g] = len_after[g];
       if (follow) max_ticks = rounds[0];
@@ -393,9 +413,9 @@ int main(int argc, char **argv) {
       for (int c = 0; c < n_calls; ++c) {
         const size_t at = on_device ? 0 : (size_t)c * B;       // --plan: call c's steps are planned into the one chunk
         if (on_device) CHECK_WG(plan_steps(online, d_later + (size_t)c * B * online, d_nlater + (size_t)c * B, online, d_chunks, d_cns, st));
-        CHECK_WG(robots ? wg_zmpdisc_append_fleet_dev(&zfl, B, online, d_chunks + at * online, d_cns + at, lcap, nullptr, nullptr, nullptr, nullptr,
+        CHECK_WG(robots ? wg_zmpdisc_append_fleet_dev(&zfl, B, online, d_chunks + at * online, d_cns + at, lcap, d_zx, d_zy, nullptr, nullptr,
                                                       d_left, d_lty, d_right, nullptr, d_walk, d_len, st)
-                        : wg_zmpdisc_append_dev(&zm, B, online, d_chunks + at * online, d_cns + at, lcap, nullptr, nullptr, nullptr, nullptr,
+                        : wg_zmpdisc_append_dev(&zm, B, online, d_chunks + at * online, d_cns + at, lcap, d_zx, d_zy, nullptr, nullptr,
                                                 d_left, d_lty, d_right, nullptr, d_walk, d_len, st));
         for (int g = 0; g < B; ++g)
           if (!ended[g]) cur[g] = len_after[(size_t)(c + 1) * B + g];
@@ -495,6 +515,20 @@ int main(int argc, char **argv) {
              "producers with their own model and sole\n", r_lo, r_hi, B - 1);
     printf("dimitrov_fleet: CoM heights %.4f .. %.4f m, the constants of %d models made on the device, all status 0; gaits 0 and %d == a "
            "context configured with their own model\n", h_lo, h_hi, B, B - 1);
+  }
+  if (audit) {                                                 // the folded verdicts are those of one call over the finished walks
+    std::vector<int> len_h(B);
+    CHECK_HIP(hipMemcpy(len_h.data(), d_len, sizeof(int) * B, hipMemcpyDeviceToHost));
+    wg_fleet::FleetAudit whole;
+    CHECK_HIP(dev_alloc(&whole.d_audit, B));
+    CHECK_WG(wg_zmp_audit_dev(B, lcap, d_len, d_time, d_zx, d_zy, B, qcap, d_queues, d_ts, d_te, d_count, whole.d_audit, nullptr, st));
+    CHECK_HIP(hipStreamSynchronize(st));
+    if (wg_fleet::audit_report("dimitrov_fleet", "the ZMP reference, folded call by call behind the growing queues", &fa, B, lcap, len_h.data(),
+                               time.data(), d_zx, d_zy, B, qcap, d_queues, d_ts, d_te, d_count)) return 1;
+    whole.audit.resize(B);
+    CHECK_HIP(hipMemcpy(whole.audit.data(), whole.d_audit, sizeof(wg_zmp_audit_t) * B, hipMemcpyDeviceToHost));
+    if (memcmp(whole.audit.data(), fa.audit.data(), sizeof(wg_zmp_audit_t) * B)) { fprintf(stderr, "FAILED: the folded audits differ from one audit of the finished walks\n"); return 1; }
+    printf("dimitrov_fleet: the audits folded on line == one wg_zmp_audit_dev over the finished walks, %d gaits by bytes\n", B);
   }
   const uint64_t h = wg_fleet::fnv1a64(states.data(), sizeof(wg_dimitrov_state_t) * B);
   double far = 0.0;

@@ -29,7 +29,13 @@
 // gains play no part.  Works with every mode above.  At the end every gait's status must be 0, and gait 0 AND gait B - 1 are
 // checked against the one-gait host path configured with that gait's own wg_riccati_gains.
 //
-//   kajita_fleet [--batch B] [--steps S] [--online K] [--ragged] [--plan | --plan-host] [--heights LO:HI]
+// With --audit (whole-sequence modes) the walks are judged where they lie, behind the chain above and on its stream:
+// wg_zmpdisc_full_batch_dev gives the same sequences' feet, wg_foot_constraints_batch_dev their polytope queues, and
+// wg_zmp_audit_dev audits the ZMP reference (pitch B) and the ZMP the preview realises, zmp2_tm [L][2][B], in place (pitch 2 B)
+// against them.  Only the verdicts come back; the fleet's least margin, its gait and time, and the violated count are printed,
+// gaits 0 and B - 1 are held to the host twin wg_zmp_audit.  The chain's own outputs and its checksum do not change.
+//
+//   kajita_fleet [--batch B] [--steps S] [--online K] [--ragged] [--plan | --plan-host] [--heights LO:HI] [--audit]
 #include <chrono>
 #include <cstdlib>
 #include <random>
@@ -41,13 +47,14 @@ using wg_fleet::dev_upload;
 
 int main(int argc, char **argv) {
   int B = 4096, S = 16, K = 0;
-  bool ragged = false, heights = false;
+  bool ragged = false, heights = false, audit = false;
   double zc_lo = 0.8078, zc_hi = 0.8078;
   int planned = 0;                                            // 1: --plan (steps planned on the device), 2: --plan-host
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--batch") && i + 1 < argc) B = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--steps") && i + 1 < argc) S = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--ragged")) ragged = true;
+    else if (!strcmp(argv[i], "--audit")) audit = true;
     else if (!strcmp(argv[i], "--plan")) planned = 1;
     else if (!strcmp(argv[i], "--plan-host")) planned = 2;
     else if (!strcmp(argv[i], "--heights") && i + 1 < argc) {
@@ -58,6 +65,7 @@ int main(int argc, char **argv) {
   }
   if (B < 1 || S < 2 || S > WG_ZMPDISC_MAX_STEPS) { fprintf(stderr, "FAILED: need B >= 1, 2 <= steps <= %d\n", WG_ZMPDISC_MAX_STEPS); return 1; }
   if (planned && (ragged || S < 4)) { fprintf(stderr, "FAILED: --plan needs steps >= 4 and no --ragged\n"); return 1; }
+  if (audit && K) { fprintf(stderr, "FAILED: --audit goes with the whole-sequence modes (no --online)\n"); return 1; }
   const bool on_device = planned == 1;
   CHECK_WG(wg_init(0));
   wg_zmpdisc_model_t zm;
@@ -255,6 +263,48 @@ int main(int argc, char **argv) {
     }
     CHECK_HIP(hipStreamSynchronize(st));
     sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  }
+  if (audit) {
+    const int qcap = 2 * S + 8 > 64 ? 2 * S + 8 : 64;         // two polytopes per step, the rest phases either side
+    const wg_sole_t sole{0.24, 0.138, 0.02, 0.02};
+    std::vector<double> time_h(L);
+    { double t = 0.0; for (int l = 0; l < L; ++l) { t += zm.T; time_h[l] = t - zm.T; } }
+    std::vector<int> len_run(B);
+    for (int g = 0; g < B; ++g) len_run[g] = len_g[g] - nl + 1;
+    double *d_time, *d_left, *d_right, *d_ts, *d_te, *d_zmp2; int *d_lty, *d_count, *d_len_run;
+    wg_zmp_polytope_t *d_queues;
+    wg_fleet::FleetAudit ref, real;
+    CHECK_HIP(dev_upload(&d_time, time_h));
+    CHECK_HIP(dev_upload(&d_len_run, len_run));
+    CHECK_HIP(dev_alloc(&d_left, (size_t)L * 6 * B));
+    CHECK_HIP(dev_alloc(&d_right, (size_t)L * 6 * B));
+    CHECK_HIP(dev_alloc(&d_lty, (size_t)L * B));
+    CHECK_HIP(dev_alloc(&d_zmp2, (size_t)Lrun * 2 * B));
+    CHECK_HIP(dev_alloc(&d_queues, (size_t)B * qcap));
+    CHECK_HIP(dev_alloc(&d_ts, (size_t)B * qcap));
+    CHECK_HIP(dev_alloc(&d_te, (size_t)B * qcap));
+    CHECK_HIP(dev_alloc(&d_count, B));
+    CHECK_HIP(dev_alloc(&ref.d_audit, B));
+    CHECK_HIP(dev_alloc(&real.d_audit, B));
+    CHECK_HIP(hipStreamSynchronize(st));
+    const auto t0 = std::chrono::steady_clock::now();
+    CHECK_WG(wg_zmpdisc_full_batch_dev(&zm, B, S, d_steps, d_ns, d_feet, L, nullptr, nullptr, nullptr, nullptr, d_left, d_lty, d_right, nullptr,
+                                       d_len, st));
+    CHECK_WG(wg_foot_constraints_batch_dev(B, L, d_len, d_time, d_left, d_lty, d_right, sole.sole_w, sole.sole_h, sole.constraint_x,
+                                           sole.constraint_y, qcap, d_queues, d_ts, d_te, d_count, st));
+    CHECK_WG(wg_zmp_audit_dev(B, L, d_len, d_time, d_zx, d_zy, B, qcap, d_queues, d_ts, d_te, d_count, ref.d_audit, nullptr, st));
+    // the preview once more from rest, this time asked for the ZMP it realises; the CoM it rewrites is the same
+    CHECK_HIP(hipMemsetAsync(d_state, 0, sizeof(double) * 8 * B, st));
+    CHECK_WG(heights ? wg_preview_run_fleet_dev(B, Lrun, &fleet, d_zx, d_zy, d_state, d_com, d_zmp2, 1, st)
+                     : wg_preview_run_batch_dev(B, Lrun, d_zx, d_zy, d_state, d_com, d_zmp2, 1, st));
+    CHECK_WG(wg_zmp_audit_dev(B, Lrun, d_len_run, d_time, d_zmp2, d_zmp2 + B, 2LL * B, qcap, d_queues, d_ts, d_te, d_count, real.d_audit, nullptr, st));
+    CHECK_HIP(hipStreamSynchronize(st));
+    const double sec_a = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    printf("kajita_fleet: feet, queues (<= %d polytopes), the preview's ZMP and two audits of %d walks in %.2f ms\n", qcap, B, sec_a * 1e3);
+    if (wg_fleet::audit_report("kajita_fleet", "the ZMP reference", &ref, B, L, len_g.data(), time_h.data(), d_zx, d_zy, B, qcap, d_queues, d_ts,
+                               d_te, d_count)) return 1;
+    if (wg_fleet::audit_report("kajita_fleet", "the ZMP the preview realises (zmp2_tm in place, pitch 2 B)", &real, B, Lrun, len_run.data(),
+                               time_h.data(), d_zmp2, d_zmp2 + B, 2LL * B, qcap, d_queues, d_ts, d_te, d_count)) return 1;
   }
   if (K) {                                                     // every gait must have arrived at the whole sequence's length
     std::vector<int> len_h(B);

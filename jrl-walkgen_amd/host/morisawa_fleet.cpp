@@ -13,9 +13,14 @@
 // height -- are re-planned from its block's kept factor on the same stream (wg_morisawa[_long]_resolve_dev: no Z, no elimination);
 // the first and the last candidate's blocks are checked against the host's full solves of those plans, byte for byte.
 //
+// With --audit the walks are judged where they lie: on the same stream, with no synchronisation in between, the sampler's feet and
+// natures go through wg_foot_constraints_batch_dev and its ZMP through wg_zmp_audit_dev against those queues; only the verdicts
+// come back (32 bytes per gait).  Gaits 0 and B - 1 are held to the host twin wg_zmp_audit.  With --replan K every candidate is
+// sampled and audited behind the re-plan, and the candidate whose ZMP keeps the largest margin is named.
+//
 // Prints a checksum (FNV-1a, 64 bit, over the gaits' checksums of their own rows of CoM, ZMP and feet) and the milliseconds per fleet.
 //
-//   morisawa_fleet [--batch B] [--steps S] [--heights LO:HI] [--long] [--replan K]
+//   morisawa_fleet [--batch B] [--steps S] [--heights LO:HI] [--long] [--replan K] [--audit]
 #include <chrono>
 #include <cstdlib>
 #include <random>
@@ -27,12 +32,13 @@ using wg_fleet::dev_upload;
 
 int main(int argc, char **argv) {
   int B = 4096, S = 7, replan = 0;
-  bool heights = false, lng = false;
+  bool heights = false, lng = false, audit = false;
   double h_lo = 0.7116911, h_hi = 0.7116911;
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--batch") && i + 1 < argc) B = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--steps") && i + 1 < argc) S = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--long")) lng = true;
+    else if (!strcmp(argv[i], "--audit")) audit = true;
     else if (!strcmp(argv[i], "--replan") && i + 1 < argc) {
       replan = atoi(argv[++i]);
       if (replan < 1) { fprintf(stderr, "FAILED: need --replan K with K >= 1\n"); return 1; }
@@ -116,6 +122,29 @@ int main(int argc, char **argv) {
   hipStream_t st;
   CHECK_HIP(hipStreamCreate(&st));
   double sec = 0.0;
+  // --audit: the shared time array, the queues and the verdicts; the three launches behind whatever made the samples
+  const int qcap = 2 * S + 4;                                 // a polytope per support phase: two per step and the ends
+  const wg_sole_t sole{0.24, 0.138, 0.02, 0.02};
+  std::vector<double> time_h(L);
+  double *d_time = nullptr, *d_ts = nullptr, *d_te = nullptr;
+  wg_zmp_polytope_t *d_queues = nullptr;
+  int *d_count = nullptr;
+  wg_fleet::FleetAudit fa;
+  if (audit) {
+    double t = 0.0;
+    for (int l = 0; l < L; ++l) { time_h[l] = t; t += base.T; }
+    CHECK_HIP(dev_upload(&d_time, time_h));
+    CHECK_HIP(dev_alloc(&d_queues, (size_t)B * qcap));
+    CHECK_HIP(dev_alloc(&d_ts, (size_t)B * qcap));
+    CHECK_HIP(dev_alloc(&d_te, (size_t)B * qcap));
+    CHECK_HIP(dev_alloc(&d_count, B));
+    CHECK_HIP(dev_alloc(&fa.d_audit, B));
+  }
+  auto audit_launch = [&]() -> int {
+    if (int rc = wg_foot_constraints_batch_dev(B, L, d_len, d_time, d_left, d_lt, d_right, sole.sole_w, sole.sole_h, sole.constraint_x,
+                                               sole.constraint_y, qcap, d_queues, d_ts, d_te, d_count, st)) return rc;
+    return wg_zmp_audit_dev(B, L, d_len, d_time, d_zx, d_zy, B, qcap, d_queues, d_ts, d_te, d_count, fa.d_audit, nullptr, st);
+  };
   if (replan) {
     const auto solve_dev_fn = lng ? wg_morisawa_long_solve_dev : wg_morisawa_solve_dev;
     const auto resolve_dev_fn = lng ? wg_morisawa_long_resolve_dev : wg_morisawa_resolve_dev;
@@ -128,6 +157,11 @@ int main(int argc, char **argv) {
       const auto t0 = std::chrono::steady_clock::now();
       CHECK_WG(solve_dev_fn(&base, 1, S, d_steps, d_ns, d_feet, d_com0, d_fac, d_fst, st));
       CHECK_WG(resolve_dev_fn(&base, B, S, d_fac, 1, nullptr, d_steps, d_feet, d_com0, d_blocks, d_status, st));
+      if (audit) {
+        const auto sample_dev_fn = lng ? wg_morisawa_long_sample_dev : wg_morisawa_sample_dev;
+        CHECK_WG(sample_dev_fn(B, S, d_blocks, d_status, t_start, base.T, L, d_zx, d_zy, nullptr, d_left, d_lt, d_right, nullptr, d_len, st));
+        CHECK_WG(audit_launch());
+      }
       CHECK_HIP(hipStreamSynchronize(st));
       sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     }
@@ -148,6 +182,11 @@ int main(int argc, char **argv) {
     printf("morisawa_fleet: %d candidate plans%s of %d steps re-planned from one kept factor in %.2f ms = %.0f plans/s (one solve "
            "included); candidates 0 and %d == full solves by bytes; checksum %016llx\n", B, lng ? " (long family)" : "", S, sec * 1e3, B / sec,
            B - 1, (unsigned long long)wg_fleet::fnv1a64(blocks.data(), bb * B));
+    if (audit) {
+      if (wg_fleet::audit_report("morisawa_fleet", "the candidates' ZMP (sampled, queued and audited behind the re-plan, in the time above)", &fa, B,
+                                 L, len_g.data(), time_h.data(), d_zx, d_zy, B, qcap, d_queues, d_ts, d_te, d_count)) return 1;
+      printf("morisawa_fleet: best candidate %d (least margin %.6f m)\n", fa.best_gait, fa.audit[fa.best_gait].margin);
+    }
     wg_shutdown();
     return 0;
   }
@@ -160,6 +199,7 @@ int main(int argc, char **argv) {
     else
       CHECK_WG(walk_fn(&base, B, S, d_steps, d_ns, d_feet, d_com0, d_blocks, d_status, t_start, L, d_zx, d_zy, d_com, d_left,
                        d_lt, d_right, d_rt, d_len, st));
+    if (audit) CHECK_WG(audit_launch());
     CHECK_HIP(hipStreamSynchronize(st));
     sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   }
@@ -213,6 +253,8 @@ int main(int argc, char **argv) {
   printf("morisawa_fleet: %d analytic walks%s of %d steps (up to %d samples) in %.2f ms = %.0f walks/s; gait 0 ends at x = %.4f m (%d samples), "
          "farthest %.2f m; gaits 0 and %d == host twins; checksum %016llx\n", B, lng ? " (long family)" : "", S, L, sec * 1e3, B / sec,
          com[((size_t)(len_g[0] - 1) * 4) * B + 0], len_g[0], far, B - 1, sum);
+  if (audit && wg_fleet::audit_report("morisawa_fleet", "the walks' ZMP (queues and audit behind the walk, in the time above)", &fa, B, L,
+                                      len_g.data(), time_h.data(), d_zx, d_zy, B, qcap, d_queues, d_ts, d_te, d_count)) return 1;
   wg_shutdown();
   return 0;
 }

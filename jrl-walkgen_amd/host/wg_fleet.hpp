@@ -37,6 +37,63 @@ inline uint64_t fnv1a64(const void *data, size_t n) {
   return h;
 }
 
+// The walk audit of a fleet program (--audit): the verdicts' device array, their host copy, and the report.  The programs launch
+// wg_zmp_audit_dev / _append_dev themselves, on their own stream behind the calls that made the tracks and the queues.
+struct FleetAudit {
+  wg_zmp_audit_t *d_audit = nullptr;     // [B]
+  std::vector<wg_zmp_audit_t> audit;     // the verdicts, once report() has run
+  int worst_gait = -1, best_gait = -1;   // the gaits of the fleet's least and largest margin (-1: every gait was refused)
+  long long violated = 0;
+};
+
+// After the stream was synchronised: copies the verdicts back, holds gaits 0 and B - 1 to the host twin (wg_zmp_audit on the
+// copied-back track and queue; the track is read in place through its pitch) and prints the fleet's verdict.  All d_ pointers are
+// the device arrays the audit call was given; len_h, time_h their host copies.  Returns 0, or 1 after printing FAILED.
+inline int audit_report(const char *prog, const char *what, FleetAudit *fa, int B, int lcap, const int *len_h, const double *time_h,
+                        const double *d_px, const double *d_py, long long pitch, int qcap, const wg_zmp_polytope_t *d_queues,
+                        const double *d_ts, const double *d_te, const int *d_count) {
+  fa->audit.resize(B);
+  CHECK_HIP(hipMemcpy(fa->audit.data(), fa->d_audit, sizeof(wg_zmp_audit_t) * B, hipMemcpyDeviceToHost));
+  const size_t span = (size_t)(lcap - 1) * (size_t)pitch + (size_t)B;
+  std::vector<double> hx(span), hy(span), ts(qcap), te(qcap);
+  std::vector<wg_zmp_polytope_t> q(qcap);
+  CHECK_HIP(hipMemcpy(hx.data(), d_px, sizeof(double) * span, hipMemcpyDeviceToHost));
+  CHECK_HIP(hipMemcpy(hy.data(), d_py, sizeof(double) * span, hipMemcpyDeviceToHost));
+  for (int g : {0, B - 1}) {
+    int count = 0;
+    CHECK_HIP(hipMemcpy(&count, d_count + g, sizeof(int), hipMemcpyDeviceToHost));
+    CHECK_HIP(hipMemcpy(q.data(), d_queues + (size_t)g * qcap, sizeof(wg_zmp_polytope_t) * qcap, hipMemcpyDeviceToHost));
+    CHECK_HIP(hipMemcpy(ts.data(), d_ts + (size_t)g * qcap, sizeof(double) * qcap, hipMemcpyDeviceToHost));
+    CHECK_HIP(hipMemcpy(te.data(), d_te + (size_t)g * qcap, sizeof(double) * qcap, hipMemcpyDeviceToHost));
+    wg_zmp_audit_t twin;
+    memset(&twin, 0, sizeof twin);
+    const int rc = wg_zmp_audit(0, len_h[g], time_h, hx.data() + g, hy.data() + g, (int)pitch, count, qcap, q.data(), ts.data(), te.data(), &twin, nullptr);
+    if (rc != WG_OK || memcmp(&twin, &fa->audit[g], sizeof twin)) {
+      fprintf(stderr, "FAILED: the device audit of gait %d (%s) differs from the host twin: margin %.17g at %d vs %.17g at %d\n", g, what,
+              fa->audit[g].margin, fa->audit[g].worst_sample, twin.margin, twin.worst_sample);
+      return 1;
+    }
+  }
+  fa->worst_gait = fa->best_gait = -1;
+  fa->violated = 0;
+  long long uncovered = 0, refused = 0;
+  for (int g = 0; g < B; ++g) {
+    const wg_zmp_audit_t &a = fa->audit[g];
+    if (a.status != WG_OK) { ++refused; continue; }
+    fa->violated += a.n_violated;
+    uncovered += a.n_uncovered;
+    if (fa->worst_gait < 0 || a.margin < fa->audit[fa->worst_gait].margin) fa->worst_gait = g;
+    if (fa->best_gait < 0 || a.margin > fa->audit[fa->best_gait].margin) fa->best_gait = g;
+  }
+  if (fa->worst_gait < 0) { fprintf(stderr, "FAILED: the audit refused every gait (%s)\n", what); return 1; }
+  const wg_zmp_audit_t &w = fa->audit[fa->worst_gait];
+  printf("%s: audit of %s: least margin %.6f m (gait %d at t = %.3f s, row %d); %lld samples violated, %lld uncovered, %lld gaits refused; "
+         "largest least margin %.6f m (gait %d); gaits 0 and %d == host twin\n", prog, what, w.margin, fa->worst_gait,
+         w.worst_sample >= 0 ? time_h[w.worst_sample] : 0.0, w.worst_row, fa->violated, uncovered, refused, fa->audit[fa->best_gait].margin,
+         fa->best_gait, B - 1);
+  return 0;
+}
+
 // The feeding plan of a fleet walked on line: wg_zmpdisc_begin_dev takes the first two steps of every gait (call 0), each of
 // the n_calls wg_zmpdisc_append_dev calls behind it the next K.  Host arithmetic, done once: nothing is read back while the
 // fleet walks.

@@ -836,6 +836,47 @@ def foot_constraints_append_fleet_dev(B, lcap, first_sample, done_ptr, length_pt
           stream)
 
 
+class ZmpAudit(C.Structure):            # wg_zmp_audit_t
+    _fields_ = [("margin", C.c_double), ("worst_sample", C.c_int), ("worst_row", C.c_int), ("n_violated", C.c_int),
+                ("n_uncovered", C.c_int), ("n_nonfinite", C.c_int), ("status", C.c_int)]
+
+
+ZMP_AUDIT_BYTES = 32
+
+
+def zmp_audit(time, px, py, polys, t_start, t_end, count=None, qcap=None, first_sample=0, n=None, audit=None, margin=None):
+    """wg_zmp_audit, one gait on the host: (ZmpAudit, margin[n]).  polys: (ZmpPolytope * k) or its bytes' owner; count / qcap
+    default to the number of intervals.  first_sample > 0 folds samples [first_sample, n) into `audit` and `margin` as an earlier
+    call left them.  Raises WgError where the call refuses."""
+    time = np.ascontiguousarray(time, dtype=np.float64); px = np.ascontiguousarray(px, dtype=np.float64)
+    py = np.ascontiguousarray(py, dtype=np.float64)
+    t_start = np.ascontiguousarray(t_start, dtype=np.float64); t_end = np.ascontiguousarray(t_end, dtype=np.float64)
+    n = time.shape[0] if n is None else int(n)
+    qcap = max(1, t_start.shape[0]) if qcap is None else int(qcap)
+    count = t_start.shape[0] if count is None else int(count)
+    audit = ZmpAudit() if audit is None else audit
+    margin = np.zeros(max(n, 0)) if margin is None else margin
+    _check(lib().wg_zmp_audit(int(first_sample), n, _hp(time), _hp(px), _hp(py), 1, count, qcap, C.addressof(polys), _hp(t_start),
+                              _hp(t_end), C.addressof(audit), _hp(margin)))
+    return audit, margin
+
+
+def zmp_audit_dev(B, lcap, length_ptr, time_ptr, px_tm_ptr, py_tm_ptr, pitch, qcap, queues_ptr, t_start_ptr, t_end_ptr, count_ptr,
+                  audit_ptr, margin_tm_ptr=None, stream=None, ctx=None):
+    """the walk audit of B gaits on the device: sample k of gait b at [k * pitch + b] of px_tm / py_tm against the queues the
+    foot-constraints calls wrote; audit (ZmpAudit * B), margin_tm [lcap][B] or None"""
+    _call("wg_zmp_audit_dev", ctx, int(B), int(lcap), length_ptr, time_ptr, px_tm_ptr, py_tm_ptr, int(pitch), int(qcap),
+          queues_ptr, t_start_ptr, t_end_ptr, count_ptr, audit_ptr, margin_tm_ptr, stream)
+
+
+def zmp_audit_append_dev(B, lcap, first_sample, done_ptr, length_ptr, time_ptr, px_tm_ptr, py_tm_ptr, pitch, qcap, queues_ptr,
+                         t_start_ptr, t_end_ptr, count_ptr, audit_ptr, margin_tm_ptr=None, stream=None, ctx=None):
+    """the same on line: samples [done[b], length[b]) of every gait are folded into audit[b], done[b] = length[b] afterwards;
+    first_sample is a host-side lower bound on every done[b] (0 is always valid)"""
+    _call("wg_zmp_audit_append_dev", ctx, int(B), int(lcap), int(first_sample), done_ptr, length_ptr, time_ptr, px_tm_ptr,
+          py_tm_ptr, int(pitch), int(qcap), queues_ptr, t_start_ptr, t_end_ptr, count_ptr, audit_ptr, margin_tm_ptr, stream)
+
+
 def dimitrov_select_polys_dev(B, qcap, queues_ptr, t_start_ptr, t_end_ptr, count_ptr, t0, polys_ptr, ran_out_ptr=None,
                               stream=None, ctx=None):
     """the queue walk of one tick: polys [B][N] for wg_dimitrov_tick_batch_dev, ran_out [B] or None"""

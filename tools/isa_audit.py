@@ -128,7 +128,7 @@ def main():
     ap.add_argument("--isa", default="/tmp/wg_capi_audit.s")
     ap.add_argument("--extra", default="", help="extra compiler flags (experiment builds)")
     ap.add_argument("--reuse", action="store_true", help="reuse the assembly file of an earlier run (skip both compilations)")
-    ap.add_argument("--kernels", default="wg_mpc_run_xcd_kernel,wg_mpc_tick_kernel,wg_ql_dense_kernel,wg_zmpdisc_kernel,wg_zmpdisc_online_kernel,wg_zmpdisc_form_kernel,wg_mpc_assemble_kernel,wg_morisawa_solve_kernel,wg_morisawa_solve_long_kernel,wg_morisawa_resolve_kernel,wg_morisawa_resolve_long_kernel,wg_morisawa_sample_kernel")
+    ap.add_argument("--kernels", default="wg_mpc_run_xcd_kernel,wg_mpc_tick_kernel,wg_ql_dense_kernel,wg_zmpdisc_kernel,wg_zmpdisc_online_kernel,wg_zmpdisc_form_kernel,wg_mpc_assemble_kernel,wg_morisawa_solve_kernel,wg_morisawa_solve_long_kernel,wg_morisawa_resolve_kernel,wg_morisawa_resolve_long_kernel,wg_morisawa_sample_kernel,wg_zmp_audit_kernel")
     args = ap.parse_args()
     extra = args.extra.split() if args.extra else []
     out = []
