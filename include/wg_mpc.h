@@ -1320,7 +1320,12 @@ int wg_gramian_batch_dev(int B, int N, const double *T, const double *h, double 
  *   init_feet  B x 6      left x, y, theta, right x, y, theta at the start (z, omega, omega2 and every speed 0)
  *   com0       B x 3      start CoM x, y and height (lStartingCOMState; the height is every interval's CoMZ, ZMPZ is 0)
  *   blocks     B blocks;  status B: WG_OK or WG_MORISAWA_BAD_INPUT (n_steps out of range; a time or the height not finite or not
- *                         positive; another input not finite; omega_j dT_j > 40, beyond what cosh / sinh here are made for),
+ *                         positive; another input not finite; an omega_j dT_j > WG_MORISAWA_WALK_ARG_MAX -- a bound of
+ *                         accuracy: V cosh + W sinh cancels by e^(omega dT), so the method in float64, the reference's
+ *                         arithmetic included, loses those digits; up to the bound 16 times the float64 restatement's
+ *                         distance from the 50-digit one stays below 1e-8 m for gaits in the suite's ranges, measured by
+ *                         tools/measure_morisawa_admission.py and filed as profiles/morisawa_admission.txt; a formulation that
+ *                         stays accurate beyond it is later work.  cosh / sinh themselves are made for [0, 40]),
  *                         WG_MORISAWA_SINGULAR (a zero or non-finite pivot).  A refused gait's block is left untouched.
  * Sample k is at trajectory time t_start + k additions of T (the control loop's clock, PatternGeneratorInterfacePrivate.cpp:1256;
  * the reference's queue starts at 2 t_single); a gait has the samples with t <= the sum of its interval times (FillQueues' loop).
@@ -1336,6 +1341,7 @@ int wg_gramian_batch_dev(int B, int N, const double *T, const double *h, double 
  * stream without a synchronisation between them (T = model->T).  The _fleet forms take B models, gait b its own (host array for
  * wg_morisawa_solve_fleet, DEVICE array for the _dev forms): gait b's bytes are those of the one-model call handed model b. */
 #define WG_MORISAWA_MAX_STEPS 14     /* n = 4 S + 8 = 64: one row of Z per lane */
+#define WG_MORISAWA_WALK_ARG_MAX 13.5 /* the largest admitted omega_j dT_j: X* of profiles/morisawa_admission.txt */
 #define WG_MORISAWA_BAD_INPUT (-1)
 #define WG_MORISAWA_CAPACITY (-2)
 #define WG_MORISAWA_SINGULAR (-3)

@@ -58,9 +58,14 @@ namespace wg {
 constexpr double kMoPi = 3.14159265358979323846;   // M_PI
 constexpr double kMoG = 9.86;                      // the reference's g on this path (:1106), not 9.81
 constexpr double kMoArgMax = 40.0;                 // cosh / sinh are made for [0, 40]
+constexpr double kMoWalkArgMax = WG_MORISAWA_WALK_ARG_MAX;   // a walk is accurate up to here: the method in float64, see the header
 
 // a double is finite iff x - x == 0 (inf - inf and nan - nan are nan)
 WG_MO_INLINE bool mo_finite(double x) { return x - x == 0.0; }
+// the admission of a gait's timing, for every solve and re-plan: no omega_j dT_j beyond the bound of accuracy (a NaN is beyond it)
+WG_MO_INLINE bool mo_args_ok(const wg_morisawa_model_t &m, double omega) {
+  return omega * (m.t_single * 3.0) <= kMoWalkArgMax && omega * m.t_double <= kMoWalkArgMax;
+}
 WG_MO_INLINE double mo_abs(double x) { return x < 0.0 ? -x : (x == 0.0 ? 0.0 : x); }
 
 // ---- cosh and sinh of x in [0, 40] as a fixed sequence of IEEE +, -, *, / (no libm, no ocml) ----------------------------------
@@ -558,7 +563,7 @@ WG_MO_HD inline int mo_solve(const X x, const wg_morisawa_model_t &m, int smax, 
     if (!mo_finite(steps[i].sx) || !mo_finite(steps[i].sy) || !mo_finite(steps[i].theta)) return WG_MORISAWA_BAD_INPUT;
   const int I = 2 * S + 1, n = 2 * I + 6, P = L.nmax + 1;
   const double omega = sqrt(kMoG / (h - 0.0));                 // BuildingTheZMatrix :1106, lZMP = 0 (:387)
-  if (!(omega * (m.t_single * 3.0) <= kMoArgMax) || !(omega * m.t_double <= kMoArgMax)) return WG_MORISAWA_BAD_INPUT;
+  if (!mo_args_ok(m, omega)) return WG_MORISAWA_BAD_INPUT;
 
   for (int e = l0; e < L.work_words; e += NL) W[e] = 0.0;
   x.sync();
@@ -793,7 +798,7 @@ WG_MO_HD inline bool mo_inputs_ok(const wg_morisawa_model_t &m, int smax, const 
   for (int i = 0; i < S; i++)
     if (!mo_finite(steps[i].sx) || !mo_finite(steps[i].sy) || !mo_finite(steps[i].theta)) return false;
   const double omega = sqrt(kMoG / (h - 0.0));
-  return omega * (m.t_single * 3.0) <= kMoArgMax && omega * m.t_double <= kMoArgMax;
+  return mo_args_ok(m, omega);
 }
 
 // ---- the whole long solve of one gait: work area W (mo_layout_long's work_words doubles), block blk ------------------------------

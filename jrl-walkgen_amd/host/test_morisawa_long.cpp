@@ -209,7 +209,7 @@ void refusals() {
   f.n_steps[1] = smax + 1;
   f.models[2].t_double = 0.0;
   f.com0[3 * 3 + 2] = NAN;
-  f.com0[3 * 4 + 2] = 0.01;                                   // omega dT > 40
+  f.com0[3 * 4 + 2] = 0.01;                                   // omega dT > 40, far beyond WG_MORISAWA_WALK_ARG_MAX
   std::vector<double> blocks((size_t)(B + 2) * words, CANARY);
   std::vector<int> status(B + 2, -77);
   int rc = wg_morisawa_long_solve_fleet(f.models.data(), B, smax, f.steps.data(), f.n_steps.data(), f.feet.data(), f.com0.data(), blocks.data() + words, status.data() + 1);
